@@ -11,8 +11,12 @@ with the step size recorded there, so the accept ratio is in [0.6, 0.9] whatever
 independent chain per GPU (chain_id = rank), no data-path collective; the RCCL all-gather of the sampled state
 (theta, eta) -- tbnn_gather_samples, the path's only exchange -- runs every --sampling-step epochs inside the timed
 region when N > 1.  value = leapfrog steps of all ranks / max-over-ranks wall time of one timed region of exactly --steps
-epochs; the region is measured --repeats times back to back (default 5, at most --max-region-seconds in all) and the median
-region is reported, every region's time under "timed_regions_ms".
+epochs; the region is measured --repeats times back to back (default 5, at most --max-region-seconds in all), every time from
+the state the warm-up ended in, and the median region is reported, every region's time under "timed_regions_ms".
+
+--dump-outputs DIR: rank 0 writes what the headline workload's last timed step computed -- the chain state after it (theta.npy,
+eta.npy) and the step's record (log_accept_ratio.npy, accepted.npy, logp_new.npy, ...; hyper_*.npy for the hyper transition) --
+so that two builds run with the same arguments can be compared output for output.
 
 At N = 1 the same invocation also measures BASELINE configs[3], configs[4] (weight transition + hyper transition with
 the reference's dual averaging per epoch) and configs[0], each with its own roofline and cpu_baseline, under
@@ -200,8 +204,9 @@ def roofline_bound(flops, alg_bytes):
     return "hbm" if alg_bytes / (MEASURED_HBM_GBPS * 1e9) > flops / (PEAK_TFLOPS * 1e12) else "mfma"
 
 
-def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
-    """one workload on this rank's GPU; returns the result dict (rank 0) or None"""
+def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1, dump_dir=None):
+    """one workload on this rank's GPU; returns the result dict (rank 0) or None.  dump_dir: rank 0 writes what the last timed step
+    computed there (write_dump)"""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -272,7 +277,7 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
             sample = torch.empty(ch.P + ch.H, dtype=torch.float32, device="cuda")
             gathered = torch.empty(world * (ch.P + ch.H), dtype=torch.float32, device=cdev)
 
-    hyp_acc, hyp_eps = [], []
+    hyp_acc, hyp_eps, hyp_last = [], [], []
 
     def run(epochs, eps):
         nonlocal da_epoch
@@ -284,6 +289,7 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
                 for _ in range(k):
                     outs.append(ch.hmc_step(eps, L))
                     h = ch.hyper_step(float(da.step_size), 100)
+                    hyp_last[:] = [h]
                     hyp_eps.append(float(da.step_size))
                     hyp_acc.append(float(da.update(da_epoch, h["log_accept_ratio"])))
                     da_epoch += 1
@@ -306,8 +312,28 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
             dist.barrier()
         torch.cuda.synchronize()
 
-    run(warmup, eps_warm)
+    # every timed region starts from the state the warm-up ends in: theta, eta, the epoch counter that keys the chain's draws (one per
+    # transition) and the dual averaging of the hyper step.  A region is then exactly `steps` transitions from one fixed state, the repeats
+    # measure the same computation again, and what the last step computed does not depend on how many regions ran.  The snapshot is taken
+    # one epoch early and restore() replays that last warm-up epoch outside the timed region: the region starts, as a free-running chain
+    # does, with the gradient at its state already cached (a restored state would pay one bootstrap pass inside the region)
+    w0 = max(warmup - 1, 0)
+    run(w0, eps_warm)
     hyp_acc.clear(); hyp_eps.clear()
+    theta_w, eta_w = ch.get_state(), ch.get_hypers()
+    da_w = (da.h, da.logEpsilonBar, da.step_size, da_epoch) if hyper else None
+
+    def restore():
+        nonlocal da_epoch
+        ch.set_state(theta_w)
+        ch.set_hypers(eta_w)
+        ch.set_epoch(w0)
+        if hyper:
+            da.h, da.logEpsilonBar, da.step_size, da_epoch = da_w
+        n_acc, n_eps = len(hyp_acc), len(hyp_eps)
+        run(warmup - w0, eps_warm)
+        del hyp_acc[n_acc:], hyp_eps[n_eps:]
+
     # hipEvent pairs around a sample of the fused passes: the event pool is created HERE, outside the timed region
     # hipEvent pair around every 47th fused pass inside the timed region (coprime to the trajectory lengths: the samples walk through
     # all positions of a trajectory).  Every pair costs the stream a bubble: at every 10th pass (rounds 1-3) the pairs themselves took
@@ -315,12 +341,13 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
     ch.set_profiling(int(os.environ.get("TBNN_BENCH_PROFILE_STRIDE", "47")))
     # The timed region: EXACTLY `steps` epochs between two fences (barrier + device synchronisation), max over ranks.  A region of a
     # few tens of ms (the driver's --steps 20 is 0.05 s at configs[1]) is at the mercy of one scheduling hiccup, so the region is
-    # measured `repeats` times back to back -- each again exactly `steps` epochs of the free-running chain -- and the MEDIAN region is
-    # the one reported (every region's time is in the full record); regions stop early once `--max-region-seconds` are spent.
+    # measured `repeats` times back to back -- each again exactly `steps` epochs from the post-warm-up state (restore) -- and the MEDIAN
+    # region is the one reported (every region's time is in the full record); regions stop early once `--max-region-seconds` are spent.
     regions, outs, dt_own = [], [], None
     throttled = 0.0
     t_all = time.perf_counter()
     for rep in range(max(1, repeats)):
+        restore()
         fence()
         thr0 = cgroup_throttled_ms()
         t0 = time.perf_counter()
@@ -344,6 +371,17 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
             stop = bool(t.item() > 0)
         if stop:
             break
+    # what the timed path computed in its last step, as its caller receives it: the chain state after it and the step's record
+    if rank == 0 and dump_dir:
+        last = regions[-1][2][-1]
+        dump = {"theta": ch.get_state(), "eta": ch.get_hypers()}
+        for k in ("log_accept_ratio", "accept_prob", "accepted", "logp_old", "logp_new", "kinetic_old", "kinetic_new", "sjd"):
+            dump[k] = np.asarray([last[k]], dtype=np.float64)
+        if hyper:
+            for k in ("log_accept_ratio", "accepted"):
+                dump["hyper_" + k] = np.asarray([hyp_last[0][k]], dtype=np.float64)
+            dump["hyper_step_size"] = np.asarray([hyp_eps[-1]], dtype=np.float64)
+        write_dump(dump_dir, dump)
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     med = order[(len(order) - 1) // 2]                  # the median region (the lower one of an even count: a region that was measured)
     dt, dt_own, _, thr = regions[med]
@@ -394,7 +432,6 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
             kernel_name = "traj:" + kernel_name
     except Exception:
         pass
-    theta_end, eta_end = (ch.get_state(), ch.get_hypers()) if rank == 0 else (None, None)
     P = ch.P
     if comm is not None:
         comm.close()
@@ -457,6 +494,19 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1):
         line["hyper_accept_ratio"] = round(float(np.mean(hyp_acc)), 4) if hyp_acc else None
         line["hyper_step_size"] = {"first": hyp_eps[0], "last": hyp_eps[-1], "rule": "dual averaging, network.py:457-469"} if hyp_eps else None
     return line
+
+
+def write_dump(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy, float32 / float64 as computed (whole arrays: a chain state is at most a few MB)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for k, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        total += a.nbytes
+        np.save(os.path.join(d, k + ".npy"), a)
+    assert total <= 64 << 20, f"dump of {total} bytes exceeds 64 MB"
 
 
 def run_chain_group(name, n_chains, steps, warmup, dev):
@@ -639,7 +689,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--from-initial", action="store_true", help="start from the initial state instead of the burned-in fixture")
     ap.add_argument("--kernel", default="auto", choices=["auto", "generic", "fast"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the headline workload's last timed step computed (rank 0's chain state theta / eta "
+                         "and the step's record) as DIR/<name>.npy; the same arguments give the same inputs on every run")
     args = ap.parse_args()
+    for k in ("steps", "warmup"):
+        if getattr(args, k) is not None and getattr(args, k) < (1 if k == "steps" else 0):
+            ap.error(f"--{k} must be >= {1 if k == 'steps' else 0}")
 
     # --gpus N > 1 without a launcher around us: start the N ranks ourselves (one process per GPU) as a CHILD
     # torch.distributed.run and relay rank 0's line.  Nothing in this process has touched the GPU (or imported torch) yet.
@@ -704,7 +760,7 @@ def main():
     wl = WORKLOADS[main_wl]
     steps = args.steps if args.steps is not None else wl["steps"]
     warmup = args.warmup if args.warmup is not None else wl["warmup"]
-    line = run_workload(main_wl, steps, warmup, args, rank, world, dev, ctx, repeats=args.repeats)
+    line = run_workload(main_wl, steps, warmup, args, rank, world, dev, ctx, repeats=args.repeats, dump_dir=args.dump_outputs)
     if args.workload is None and world == 1 and not args.no_secondary:
         sec = {}
         for name in ("c4", "c5", "c5g", "c1", "mn"):

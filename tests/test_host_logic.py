@@ -184,7 +184,9 @@ for k in range(3):
         assert np.all(st[k, c, :6] == 10 * c + k) and np.all(st[k, c, 6:] == 100 * c + k)
 if rank == 0:
     parallel.write_chain_folders(sys.argv[2], st, [(2, 2), (2, 1)], ["dense"], 2)
-torch.distributed.barrier()
+# gloo's own host-side barrier: torch.distributed.barrier() probes the GPU runtime, and on a GPU box every rank of this CPU test
+# would then hold the device open
+torch.distributed.monitored_barrier()
 # one marker file per rank (the launcher forwards the ranks' stdout through pipes and may interleave two lines)
 os.makedirs(sys.argv[2], exist_ok=True)
 open(os.path.join(sys.argv[2], f"rank{rank}.ok"), "w").write("ok")
@@ -439,6 +441,7 @@ def test_bench_spawns_its_own_ranks(monkeypatch):
         return 7
 
     monkeypatch.setattr(subprocess, "call", fake_call)
+    monkeypatch.setattr(bench, "visible_gpus", lambda: 4)                          # a box with the four GPUs asked for (whatever this one has)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4", "--steps", "3", "--warmup", "1"])
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):      # (conftest caps OpenBLAS for the test process itself)
         monkeypatch.delenv(k, raising=False)
@@ -480,10 +483,32 @@ def test_visible_gpus(monkeypatch, tmp_path):
     assert bench._kfd_gpu_nodes() == 3
     monkeypatch.setenv("HIP_VISIBLE_DEVICES", "0,2")
     assert bench._kfd_gpu_nodes() == 2
-    # the count that decides comes from a CHILD asking the native library (this process never touches HIP): no device here
+    # the count that decides comes from a CHILD asking the native library (this process never touches HIP); sysfs only when it cannot say
+    import subprocess
+    real_run, seen = subprocess.run, []
+
+    def child(out, rc=0):
+        def run(cmd, **kw):
+            seen.append(cmd)
+            return subprocess.CompletedProcess(cmd, rc, stdout=out, stderr="")
+        return run
+    monkeypatch.setattr(subprocess, "run", child("2\n"))
+    assert bench.visible_gpus() == 2
+    assert seen[-1][0] == sys.executable and "tbnn_device_count" in seen[-1][2] and seen[-1][3] == os.path.join(ROOT, "tensorbnn_amd", "libtbnn.so")
+    monkeypatch.setattr(subprocess, "run", child("-2\n"))                          # hipGetDeviceCount failed: the sysfs count (HIP_VISIBLE_DEVICES=0,2)
+    assert bench.visible_gpus() == 2
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "1")
+    monkeypatch.setattr(subprocess, "run", child("", rc=1))
+    assert bench.visible_gpus() == 1
+    # and on this machine: what the native library says in a child of its own (no device: 0, or None from a sysfs without GPUs)
     import builtins as _b
-    monkeypatch.setattr(_b, "open", real_open); monkeypatch.setattr(os, "listdir", real_listdir)
-    assert bench.visible_gpus() in (0, None)
+    monkeypatch.setattr(_b, "open", real_open); monkeypatch.setattr(os, "listdir", real_listdir); monkeypatch.setattr(subprocess, "run", real_run)
+    for v in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.delenv(v, raising=False)
+    r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, sys.argv[1]); from tensorbnn_amd import _native; print(_native.device_count())", ROOT],
+                       capture_output=True, text=True, timeout=120)
+    n = int(r.stdout.strip().splitlines()[-1])
+    assert (bench.visible_gpus() == n) if n > 0 else (bench.visible_gpus() in (0, None))
 
 
 def test_cpu_quota_warning(monkeypatch, tmp_path):
