@@ -47,12 +47,14 @@ static inline bool fused_ops_match(const FusedOps& o, const NetDev& nd) {
     return true;
 }
 
+// name: the table's name as given (the ahead-of-time tables); null: prefix<activations;dims>
 template <class S>
-static inline void fused_ops_shape(FusedOps* o, const char* prefix) {
+static inline void fused_ops_shape(FusedOps* o, const char* prefix, const char* name = nullptr) {
     o->abi = TBNN_JIT_ABI;
     o->nl = S::NL;
     for (int i = 0; i <= S::NL; ++i) o->dims[i] = S::D[i];
     o->hact = S::HCODE; o->lact = S::LACT; o->bern = S::BERN ? 1 : 0;      // (hact: one activation, or the packed per-layer code: Shape)
+    if (name) { snprintf(o->name, sizeof(o->name), "%s", name); return; }
     static const char* an[] = {"none", "relu", "tanh", "sigmoid", "exp", "elu", "?", "?"};
     int k = snprintf(o->name, sizeof(o->name), "%s<", prefix);
     if (S::HCODE & TBNN_ACT_PACKED) {

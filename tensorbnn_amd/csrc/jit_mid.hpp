@@ -1,7 +1,6 @@
 // Included by a run-time generated translation unit (tensorbnn_amd/jit.py): the mid-width fused kernel
-// (kernels_mid.hpp).  It speaks the narrow family's launch interface (one gradient slab per workgroup).
+// (kernels_mid.hpp), and by the ahead-of-time registry (tbnn_mid.hip).  It speaks the narrow family's launch interface (one gradient slab per workgroup).
 #pragma once
-#define TBNN_NO_FAST_REGISTRY
 #include "kernels_mid.hpp"
 #include "fused_ops.hpp"
 
@@ -17,8 +16,8 @@ struct JitMid {
         return mid_forward_t<S>(gx, nets, st, qimgs, img_stride, X, n, fouts, out_stride);
     }
     static void image_map(int* map) { mid_image_map<S>(map); }
-    static void fill(FusedOps* o) {
-        fused_ops_shape<S>(o, "jit-mid");
+    static void fill(FusedOps* o, const char* name = nullptr) {
+        fused_ops_shape<S>(o, "jit-mid", name);
         o->family = TBNN_FAMILY_NARROW;
         o->img_floats = MidCfg<S>::IMG_FLOATS;
         o->image_map = &image_map; o->grid = &grid; o->launch = &launch; o->nforward = &nforward;

@@ -1,7 +1,6 @@
 // Included by a run-time generated translation unit (tensorbnn_amd/jit.py) after `using S = Shape<...>;`
-// with JIT_FAST3 = 1 (k_fwd_bwd_fast3) or 0 (k_fwd_bwd_fast).
+// with JIT_FAST3 = 1 (k_fwd_bwd_fast3) or 0 (k_fwd_bwd_fast), and by the ahead-of-time registry (tbnn_narrow.hip).
 #pragma once
-#define TBNN_NO_FAST_REGISTRY
 #include "kernels_fast3.hpp"
 #include "kernels_traj.hpp"
 #include "fused_ops.hpp"
@@ -12,15 +11,20 @@ struct JitNarrow {
         const long ntiles = (n + 15) / 16, wgs = (ntiles + FAST_WAVES - 1) / FAST_WAVES;
         return (int)(wgs < 256 ? wgs : 256);
     }
-    static int launch(int g, hipStream_t st, const NetDev* nd, const float* qimg, const float* eta, const float* X, const float* Y,
-                      long n, float* slabs, int pitch, double* pstat, int nchains, ChainStride cs) {
+    // stamps: workgroup 0's shader-clock stamps (tbnn_debug_stamps; null in the table's launch)
+    static int launch_stamped(int g, hipStream_t st, const NetDev* nd, const float* qimg, const float* eta, const float* X, const float* Y,
+                              long n, float* slabs, int pitch, double* pstat, int nchains, ChainStride cs, unsigned long long* stamps) {
         if constexpr (F3)
             hipLaunchKernelGGL(k_fwd_bwd_fast3<S>, dim3(g, nchains), dim3(FAST_THREADS), 0, st, *nd, qimg, eta, X, Y, n, slabs, pitch, pstat,
-                               (unsigned long long*)nullptr, cs);
+                               stamps, cs);
         else
             hipLaunchKernelGGL(k_fwd_bwd_fast<S>, dim3(g, nchains), dim3(FAST_THREADS), 0, st, *nd, qimg, eta, X, Y, n, slabs, pitch, pstat,
-                               (unsigned long long*)nullptr, cs);
+                               stamps, cs);
         return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    static int launch(int g, hipStream_t st, const NetDev* nd, const float* qimg, const float* eta, const float* X, const float* Y,
+                      long n, float* slabs, int pitch, double* pstat, int nchains, ChainStride cs) {
+        return launch_stamped(g, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, nchains, cs, nullptr);
     }
     static int nforward(int gx, int nets, hipStream_t st, const float* qimgs, long img_stride, const float* X, long n, float* fouts,
                         long out_stride) {
@@ -45,8 +49,8 @@ struct JitNarrow {
         }
     }
     static void image_map(int* map) { ImageMap<S, 0>::run(map); }
-    static void fill(FusedOps* o) {
-        fused_ops_shape<S>(o, F3 ? "jit-fast3" : "jit-fast");
+    static void fill(FusedOps* o, const char* name = nullptr) {
+        fused_ops_shape<S>(o, F3 ? "jit-fast3" : "jit-fast", name);
         o->family = TBNN_FAMILY_NARROW;
         o->img_floats = FastCfg<S>::STATIC_FLOATS;
         o->image_map = &image_map; o->grid = &grid; o->launch = &launch;

@@ -2,7 +2,6 @@
 // the tall-fan-in fused kernel (kernels_tall.hpp).  It speaks the narrow family's launch interface (one gradient slab per
 // workgroup).
 #pragma once
-#define TBNN_NO_FAST_REGISTRY
 #include "kernels_tall.hpp"
 #include "fused_ops.hpp"
 

@@ -1,6 +1,6 @@
-// Included by a run-time generated translation unit (tensorbnn_amd/jit.py): the wide-layer family.
+// Included by a run-time generated translation unit (tensorbnn_amd/jit.py) and by the ahead-of-time registry
+// (tbnn_wide.hip): the wide-layer family.
 #pragma once
-#define TBNN_NO_FAST_REGISTRY
 #include "wide_api.hpp"
 #include "kernels_wide.hpp"
 #include "fused_ops.hpp"
@@ -16,8 +16,8 @@ struct JitWide {
         return wide_forward_t<S>(st, *nd, qimg, X, n, fout);
     }
     static void image_map(int* map) { wide_image_map<S>(map); }
-    static void fill(FusedOps* o) {
-        fused_ops_shape<S>(o, WideCfg<S>::RESIDENT ? "jit-wide(resident)" : "jit-wide");
+    static void fill(FusedOps* o, const char* name = nullptr) {
+        fused_ops_shape<S>(o, WideCfg<S>::RESIDENT ? "jit-wide(resident)" : "jit-wide", name);
         o->family = TBNN_FAMILY_WIDE;
         o->img_floats = WideCfg<S>::IMG_FLOATS;
         o->image_map = &image_map; o->grid = nullptr; o->launch = nullptr;

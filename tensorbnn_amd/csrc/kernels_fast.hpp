@@ -990,77 +990,3 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     TB_STAMP(4);
 #undef TB_STAMP
 }
-
-#ifndef TBNN_NO_FAST_REGISTRY
-// ---------------------------------------------------------------------------
-// registry of ahead-of-time instantiations (shapes of BASELINE.json's configs)
-// ---------------------------------------------------------------------------
-using ShapeC2 = Shape<TBNN_ACT_RELU, TBNN_ACT_NONE, false, 5, 50, 50, 50, 1>;      // configs[1], configs[2]
-using ShapeC1 = Shape<TBNN_ACT_RELU, TBNN_ACT_NONE, false, 1, 10, 10, 1>;          // configs[0]
-using ShapeTR = Shape<TBNN_ACT_TANH, TBNN_ACT_NONE, false, 1, 10, 10, 10, 1>;      // Examples/trainRegression.py
-using ShapeT3 = Shape<TBNN_ACT_SIGMOID, TBNN_ACT_NONE, false, 4, 7, 3>;            // test shape: last layer on the MFMA path
-
-template <class S>
-static bool shape_matches(const NetDev& nd) {
-    if (nd.nl != S::NL) return false;
-    if ((nd.lik == TBNN_LIK_BERNOULLI) != S::BERN) return false;
-    for (int l = 0; l < S::NL; ++l)
-        if (nd.in[l] != S::D[l] || nd.out[l] != S::D[l + 1] || nd.act[l] != S::act(l)) return false;
-    return true;
-}
-
-static inline int fast_lookup(const NetDev& nd) {
-    if (shape_matches<ShapeC2>(nd)) return 0;
-    if (shape_matches<ShapeC1>(nd)) return 1;
-    if (shape_matches<ShapeTR>(nd)) return 2;
-    if (shape_matches<ShapeT3>(nd)) return 3;
-    return -1;
-}
-static inline const char* fast_name(int id) {
-    switch (id) {
-        case 0: return "fast<relu;5,50,50,50,1>";
-        case 1: return "fast<relu;1,10,10,1>";
-        case 2: return "fast<tanh;1,10,10,10,1>";
-        case 3: return "fast<sigmoid;4,7,3>";
-        default: return "fast<none>";
-    }
-}
-// one workgroup (4 waves, 1 wave per SIMD) per CU; fewer when there are not enough tiles
-static inline int fast_grid(int, long n) {
-    const long ntiles = (n + 15) / 16;
-    const long wgs = (ntiles + FAST_WAVES - 1) / FAST_WAVES;
-    return (int)(wgs < 256 ? wgs : 256);
-}
-// qimg: the padded weight image of the position to evaluate
-static inline int fast_launch(int id, int grid, hipStream_t st, const NetDev& nd, const float* qimg, const float* eta,
-                              const float* X, const float* Y, long n, float* slabs, int pitch, double* pstat,
-                              unsigned long long* stamps = nullptr, int nchains = 1, ChainStride cs = ChainStride{0, 0, 0, nullptr, 0}) {
-    switch (id) {
-        case 0: hipLaunchKernelGGL(k_fwd_bwd_fast<ShapeC2>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        case 1: hipLaunchKernelGGL(k_fwd_bwd_fast<ShapeC1>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        case 2: hipLaunchKernelGGL(k_fwd_bwd_fast<ShapeTR>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        case 3: hipLaunchKernelGGL(k_fwd_bwd_fast<ShapeT3>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        default: return -1;
-    }
-    return 0;
-}
-// floats in the padded weight image and the parameter -> image-offset map
-static inline int fast_image_floats(int id) {
-    switch (id) {
-        case 0: return FastCfg<ShapeC2>::STATIC_FLOATS;
-        case 1: return FastCfg<ShapeC1>::STATIC_FLOATS;
-        case 2: return FastCfg<ShapeTR>::STATIC_FLOATS;
-        case 3: return FastCfg<ShapeT3>::STATIC_FLOATS;
-        default: return 0;
-    }
-}
-static inline void fast_image_map(int id, int* map) {
-    switch (id) {
-        case 0: ImageMap<ShapeC2, 0>::run(map); break;
-        case 1: ImageMap<ShapeC1, 0>::run(map); break;
-        case 2: ImageMap<ShapeTR, 0>::run(map); break;
-        case 3: ImageMap<ShapeT3, 0>::run(map); break;
-        default: break;
-    }
-}
-#endif  // TBNN_NO_FAST_REGISTRY

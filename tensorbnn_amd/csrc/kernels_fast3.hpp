@@ -1909,29 +1909,3 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         }
     }
 }
-
-#ifndef TBNN_NO_FAST_REGISTRY
-static inline bool fast3_available(int id) { return id == 0 || id == 1 || id == 2; }
-static inline int fast3_launch(int id, int grid, hipStream_t st, const NetDev& nd, const float* qimg, const float* eta,
-                               const float* X, const float* Y, long n, float* slabs, int pitch, double* pstat,
-                               unsigned long long* stamps = nullptr, int nchains = 1, ChainStride cs = ChainStride{0, 0, 0, nullptr, 0}) {
-    switch (id) {
-        case 0: hipLaunchKernelGGL(k_fwd_bwd_fast3<ShapeC2>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        case 1: hipLaunchKernelGGL(k_fwd_bwd_fast3<ShapeC1>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        case 2: hipLaunchKernelGGL(k_fwd_bwd_fast3<ShapeTR>, dim3(grid, nchains), dim3(FAST_THREADS), 0, st, nd, qimg, eta, X, Y, n, slabs, pitch, pstat, stamps, cs); break;
-        default: return -1;
-    }
-    return 0;
-}
-// forward-only launch: `nets` networks (grid.y), gx workgroups each
-static inline int fast3_forward(int id, int gx, int nets, hipStream_t st, const float* qimgs, long img_stride, const float* X, long n,
-                                float* fouts, long out_stride) {
-    switch (id) {
-        case 0: hipLaunchKernelGGL(k_forward_fast3<ShapeC2>, dim3(gx, nets), dim3(FAST_THREADS), 0, st, qimgs, img_stride, X, n, fouts, out_stride); break;
-        case 1: hipLaunchKernelGGL(k_forward_fast3<ShapeC1>, dim3(gx, nets), dim3(FAST_THREADS), 0, st, qimgs, img_stride, X, n, fouts, out_stride); break;
-        case 2: hipLaunchKernelGGL(k_forward_fast3<ShapeTR>, dim3(gx, nets), dim3(FAST_THREADS), 0, st, qimgs, img_stride, X, n, fouts, out_stride); break;
-        default: return -1;
-    }
-    return 0;
-}
-#endif  // TBNN_NO_FAST_REGISTRY

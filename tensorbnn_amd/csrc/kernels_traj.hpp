@@ -256,29 +256,3 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
 #ifndef TBNN_TRAJ_WAVES
 #define TBNN_TRAJ_WAVES 16
 #endif
-#ifndef TBNN_NO_FAST_REGISTRY
-// ahead-of-time instantiations: the registry ids of kernels_fast3.hpp whose shapes are eligible; 16 waves where they fit
-template <class S> struct TrajPick { static constexpr int NW = (TBNN_TRAJ_WAVES == 16 && TrajCfg<S, 16>::OK) ? 16 : 4; };
-template <class S> static inline long fast3_traj_rows_t() {
-    return !TrajCfg<S, TrajPick<S>::NW>::OK ? 0 : (TrajPick<S>::NW == 16 ? TBNN_TRAJ_MAX_ROWS : TBNN_TRAJ_MAX_ROWS_4);
-}
-// row count up to which registry shape `id` runs its transitions on the trajectory kernel (0: never)
-static inline long fast3_traj_max_rows(int id) { return id == 1 ? fast3_traj_rows_t<ShapeC1>() : id == 2 ? fast3_traj_rows_t<ShapeTR>() : 0; }
-template <class S>
-static inline void fast3_traj_launch_t(int nchains, hipStream_t st, const NetDev& nd, const float* qimg, long img_stride, const float* eta,
-                                       const float* X, const float* Y, long n, float* q, float* p, float* g, float* gd, const int* imgmap,
-                                       double* pstat, int nstat, float eps, int L, const StepCtl* ctl) {
-    constexpr int NW = TrajPick<S>::NW;
-    hipLaunchKernelGGL((k_traj_fast3<S, NW>), dim3(1, nchains), dim3(64 * NW), 0, st, nd, qimg, img_stride, eta, X, Y, n, q, p, g, gd, imgmap, pstat, nstat, eps, L, ctl);
-}
-static inline int fast3_traj_launch(int id, int nchains, hipStream_t st, const NetDev& nd, const float* qimg, long img_stride, const float* eta,
-                                    const float* X, const float* Y, long n, float* q, float* p, float* g, float* gd, const int* imgmap,
-                                    double* pstat, int nstat, float eps, int L, const StepCtl* ctl) {
-    switch (id) {
-        case 1: fast3_traj_launch_t<ShapeC1>(nchains, st, nd, qimg, img_stride, eta, X, Y, n, q, p, g, gd, imgmap, pstat, nstat, eps, L, ctl); break;
-        case 2: fast3_traj_launch_t<ShapeTR>(nchains, st, nd, qimg, img_stride, eta, X, Y, n, q, p, g, gd, imgmap, pstat, nstat, eps, L, ctl); break;
-        default: return -1;
-    }
-    return 0;
-}
-#endif

@@ -16,14 +16,8 @@
 #include "kernels_generic.hpp"
 #include "kernels_hmc.hpp"
 #include "kernels_hyper.hpp"
-#include "kernels_fast.hpp"
-#include "kernels_fast3.hpp"
-#include "kernels_traj.hpp"
 #include "kernels_layered.hpp"
-#include "wide_api.hpp"
-#include "mid_api.hpp"
-#include "tall_api.hpp"
-#include "fused_ops.hpp"
+#include "aot_ops.hpp"
 #include <mutex>
 
 static thread_local std::string g_err;
@@ -56,10 +50,7 @@ struct tbnn_ctx {
     uint32_t key0 = 0, key1 = 0, epoch = 0;
     int C = 1;                            // chains of this handle (tbnn_create_multi): every per-chain buffer is a [C][...] array, the per-chain
     uint32_t seed_hi = 0;                 // kernels run with gridDim.y = C; chain c draws from the Philox key (seed, chain_id + c)
-    int kernel = TBNN_KERNEL_GENERIC;     // resolved variant
-    int fast_id = -1;
-    int fast_ver = 1;                     // 1: kernels_fast.hpp, 3: kernels_fast3.hpp (fringe units off the 16x16 tiles)
-    int mid_id = -1;                      // >= 0: kernels_mid.hpp (mid-width fused kernel; narrow-family workspace and launch signature)
+    const FusedOps* ops = nullptr;        // the fused kernels of this shape: an ahead-of-time table (aot_ops.hpp) or a registered library
     bool lay = false; LayPlan lplan{}; float* lstore = nullptr;   // kernels_layered.hpp: run-time-shape MFMA kernels, activations through HBM
     float* lfwd = nullptr; size_t lfwd_floats = 0;                // its forward-only store (predict / metrics / ensembles): pooled, grown as needed
     std::string kernel_name;
@@ -76,14 +67,13 @@ struct tbnn_ctx {
     bool q_img_valid = false;             // h->qimg mirrors h->q (maintained by k_update)
     // fused-pass workspace
     int grid = 0, pitch = 0; float* slabs = nullptr; double* pstat = nullptr; float* scratch = nullptr;
-    // wide-layer path (kernels_wide.hpp): a fast-kernel variant with its own workspace
-    const FusedOps* jit = nullptr;         // run-time registered kernel library covering this shape (tbnn_register_kernel_lib)
-    int wide_id = -1; WidePlan wplan; float* wstore = nullptr; float* wslabA = nullptr; float* wslabB = nullptr;
+    // wide-layer family (kernels_wide.hpp): its own workspace
+    WidePlan wplan; float* wstore = nullptr; float* wslabA = nullptr; float* wslabB = nullptr;
     int nslab = 0;                        // gradient slabs k_update reduces (wide: 1, already reduced)
     // row-sharded chain (tbnn_set_row_shard): all-reduce of the dense data-term gradient row + statistic
     tbnn_comm* shard = nullptr; long n_total = 0; float* grow = nullptr; double* pstat_red = nullptr;
     double* shard_buf = nullptr;          // the all-reduce operand: P gradient values + the statistic, as doubles
-    int* imgmap = nullptr; float* qimg = nullptr; float* qimg_cur = nullptr; int img_floats = 0;   // fast kernel: padded weight images
+    int* imgmap = nullptr; float* qimg = nullptr; float* qimg_cur = nullptr; int img_floats = 0;   // ops / layered: padded weight images
     size_t scratchPerWG = 0;
     float* pin_dev = nullptr;              // device-side address of pin
     float* pin = nullptr;                  // pinned staging for the per-epoch state read-back (P + H floats): a 22-KB D2H copy
@@ -156,15 +146,18 @@ static const FusedOps* find_jit(const NetDev& nd) {
     for (const FusedOps* o : g_jit) if (fused_ops_match(*o, nd)) return o;
     return nullptr;
 }
-// a FusedOps table for this network: a run-time registered library first, then the ahead-of-time tall-fan-in instantiations
-static const FusedOps* find_ops(const NetDev& nd) {
+static bool env_off(const char* name) { const char* v = getenv(name); return v && atoi(v) == 0; }
+// the FusedOps table for this network, in selection order: the ahead-of-time narrow, mid and wide instantiations, a run-time
+// registered library, the ahead-of-time tall-fan-in instantiations
+static const FusedOps* find_ops(const NetDev& nd, bool mid_on) {
+    const FusedOps* o = narrow_find(nd);
+    if (!o && mid_on) o = mid_find(nd);
+    if (!o) o = wide_find(nd);
     // TBNN_REGISTERED=0 (the layered family's tests): tbnn_create ignores kernel libraries registered earlier in the process
-    const bool jit_on = !(getenv("TBNN_REGISTERED") && atoi(getenv("TBNN_REGISTERED")) == 0);
-    const FusedOps* o = jit_on ? find_jit(nd) : nullptr;
-    if (o) return o;
+    if (!o && !env_off("TBNN_REGISTERED")) o = find_jit(nd);
     // TBNN_TALL=0 (diagnostic / A-B runs, the layered family's tests): shapes the tall-fan-in registry covers take the layered path
-    const bool tall_on = !(getenv("TBNN_TALL") && atoi(getenv("TBNN_TALL")) == 0);
-    return tall_on ? tall_find(nd) : nullptr;
+    if (!o && !env_off("TBNN_TALL")) o = tall_find(nd);
+    return o;
 }
 extern "C" int tbnn_register_kernel_lib(const char* path) {
     if (!path) return fail(-1, "null path");
@@ -189,10 +182,10 @@ extern "C" int tbnn_fused_kernel_available(const tbnn_net_desc* desc) {
     NetDev nd;
     int rc = build_netdev(desc, nd);
     if (rc) return rc;
-    if (fast_lookup(nd) >= 0 || mid_lookup(nd) >= 0) return 1;
-    if (wide_lookup(nd) >= 0) return 2;
-    if (const FusedOps* o = find_ops(nd)) return o == find_jit(nd) ? 3 : 1;
-    return 0;
+    const FusedOps* o = find_ops(nd, true);
+    if (!o) return 0;
+    if (o == find_jit(nd)) return 3;
+    return o->family == TBNN_FAMILY_WIDE ? 2 : 1;
 }
 
 static void default_eta(const NetDev& nd, std::vector<float>& eta) {
@@ -311,84 +304,28 @@ static int create_impl(const tbnn_net_desc* desc, int device, uint64_t seed, uin
     for (size_t c = 0; c < NC; ++c) eta.insert(eta.end(), eta1.begin(), eta1.end());
     HIPB(hipMemcpy(h->eta, eta.data(), eta.size() * sizeof(float), hipMemcpyHostToDevice));
     // fused-kernel variant
-    h->kernel = TBNN_KERNEL_GENERIC; h->kernel_name = "generic";
+    h->kernel_name = "generic";
     const int want = desc->kernel;
-    const int fid = fast_lookup(nd);
     // TBNN_MID=0 (diagnostic / A-B runs): shapes both families cover take the wide path (two kernels through HBM)
-    const bool mid_on = !(getenv("TBNN_MID") && atoi(getenv("TBNN_MID")) == 0);
-    const int mid = (fid < 0 && mid_on) ? mid_lookup(nd) : -1;
-    const int wid = (fid < 0 && mid < 0) ? wide_lookup(nd) : -1;
-    const FusedOps* jo = (fid < 0 && mid < 0 && wid < 0) ? find_ops(nd) : nullptr;
-    if (want == TBNN_KERNEL_FAST && fid < 0 && mid < 0 && wid < 0 && !jo) return bail(-1, "TBNN_KERNEL_FAST requested but no specialised kernel covers this shape");
-    if ((want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) && mid >= 0) {
-        h->kernel = TBNN_KERNEL_FAST; h->mid_id = mid; h->kernel_name = mid_name(mid);
-        h->img_floats = mid_image_floats(mid);
-        std::vector<int> map(2 * (size_t)nd.P);
-        mid_image_map_id(mid, map.data());
-        HIPB(hipMalloc(&h->imgmap, map.size() * sizeof(int)));
-        HIPB(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPB(hipMalloc(&h->qimg, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMalloc(&h->qimg_cur, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMemset(h->qimg, 0, NC * (size_t)h->img_floats * sizeof(float)));       // padding stays zero for ever
-        HIPB(hipMemset(h->qimg_cur, 0, NC * (size_t)h->img_floats * sizeof(float)));
-    }
-    if ((want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) && jo) {
-        h->kernel = TBNN_KERNEL_FAST; h->jit = jo; h->kernel_name = jo->name;
-        if (jo->family == TBNN_FAMILY_WIDE) { h->wide_id = 1000; jo->plan(16, &h->wplan); }
-        h->img_floats = jo->img_floats;
-        std::vector<int> map(2 * (size_t)nd.P);
-        jo->image_map(map.data());
-        HIPB(hipMalloc(&h->imgmap, map.size() * sizeof(int)));
-        HIPB(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPB(hipMalloc(&h->qimg, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMalloc(&h->qimg_cur, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMemset(h->qimg, 0, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMemset(h->qimg_cur, 0, NC * (size_t)h->img_floats * sizeof(float)));
-    }
-    if ((want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) && wid >= 0) {
-        h->kernel = TBNN_KERNEL_FAST; h->wide_id = wid; h->kernel_name = wide_name(wid);
-        wide_plan(wid, 16, h->wplan);
-        h->img_floats = h->wplan.img_floats;
-        std::vector<int> map(2 * (size_t)nd.P);
-        wide_image_map_id(wid, map.data());
-        HIPB(hipMalloc(&h->imgmap, map.size() * sizeof(int)));
-        HIPB(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPB(hipMalloc(&h->qimg, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMalloc(&h->qimg_cur, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMemset(h->qimg, 0, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMemset(h->qimg_cur, 0, NC * (size_t)h->img_floats * sizeof(float)));
-    }
-    if ((want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) && fid >= 0) {
-        h->kernel = TBNN_KERNEL_FAST; h->fast_id = fid; h->kernel_name = fast_name(fid);
-        {   // TBNN_FAST_VER=1|3 selects the variant (default: 3 where available)
-            const char* ve = getenv("TBNN_FAST_VER");
-            int want = ve ? atoi(ve) : 3;
-            if (want != 3 || !fast3_available(fid)) want = 1;
-            h->fast_ver = want;
-        }
-        if (h->fast_ver != 1) h->kernel_name = std::string("fast") + char('0' + h->fast_ver) + (h->kernel_name.c_str() + 4);
-        h->img_floats = fast_image_floats(fid);
-        std::vector<int> map(2 * (size_t)nd.P);
-        fast_image_map(fid, map.data());
-        HIPB(hipMalloc(&h->imgmap, map.size() * sizeof(int)));
-        HIPB(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPB(hipMalloc(&h->qimg, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMalloc(&h->qimg_cur, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPB(hipMemset(h->qimg, 0, NC * (size_t)h->img_floats * sizeof(float)));       // padding stays zero for ever
-        HIPB(hipMemset(h->qimg_cur, 0, NC * (size_t)h->img_floats * sizeof(float)));
-    }
+    const FusedOps* ops = find_ops(nd, !env_off("TBNN_MID"));
+    if (want == TBNN_KERNEL_FAST && !ops) return bail(-1, "TBNN_KERNEL_FAST requested but no specialised kernel covers this shape");
+    if (want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) h->ops = ops;
     // no shape-specialised kernel (and none registered at run time): the layered MFMA family takes any architecture
     // (TBNN_LAYERED=0: the thread-per-row kernel, as before round 3)
-    const bool lay_on = !(getenv("TBNN_LAYERED") && atoi(getenv("TBNN_LAYERED")) == 0);
-    if (want == TBNN_KERNEL_AUTO && fid < 0 && mid < 0 && wid < 0 && !jo && lay_on) {
-        h->kernel = TBNN_KERNEL_FAST; h->lay = true;
+    h->lay = want == TBNN_KERNEL_AUTO && !ops && !env_off("TBNN_LAYERED");
+    if (h->ops) {
+        h->kernel_name = ops->name;
+        h->img_floats = ops->img_floats;
+    } else if (h->lay) {
         lay_plan_shape(nd, h->lplan);
         h->kernel_name = "layered<" + std::to_string(nd.in[0]);
         for (int l = 0; l < nd.nl; ++l) h->kernel_name += "," + std::to_string(nd.out[l]);
         h->kernel_name += ">";
         h->img_floats = h->lplan.img_floats;
+    }
+    if (h->ops || h->lay) {
         std::vector<int> map(2 * (size_t)nd.P);
-        lay_image_map(nd, h->lplan, map.data());
+        if (h->ops) h->ops->image_map(map.data()); else lay_image_map(nd, h->lplan, map.data());
         HIPB(hipMalloc(&h->imgmap, map.size() * sizeof(int)));
         HIPB(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
         HIPB(hipMalloc(&h->qimg, NC * (size_t)h->img_floats * sizeof(float)));
@@ -422,6 +359,8 @@ extern "C" int tbnn_set_profiling(tbnn_handle h, int stride) {
 }
 extern "C" int tbnn_set_epoch(tbnn_handle h, uint32_t epoch) { NEED(h); h->epoch = epoch; return 0; }
 
+static inline bool is_wide(const tbnn_ctx* h) { return h->ops && h->ops->family == TBNN_FAMILY_WIDE; }
+
 // (re)allocate the fused-pass workspace for n rows
 static int alloc_workspace(tbnn_ctx* h, long n) {
     const NetDev& nd = h->nd;
@@ -442,15 +381,15 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
         hipLaunchKernelGGL(k_lay_pack_x, dim3((int)std::min<long>(tot, 4096)), dim3(256), 0, h->stream, (const float*)h->dX, n, nd.d_in, h->lplan.TK[0],
                            h->lplan.ntiles, h->lstore + h->lplan.aOff[0]);
         HIPCHK(hipGetLastError());
-    } else if (h->wide_id >= 0) {
-        if (h->jit) h->jit->plan(n, &h->wplan); else wide_plan(h->wide_id, n, h->wplan);
+    } else if (is_wide(h)) {
+        h->ops->plan(n, &h->wplan);
         grid = h->wplan.gridA;
         h->scratchPerWG = 0;
         HIPCHK(hipMalloc(&h->wstore, h->wplan.store_floats * sizeof(float)));
         HIPCHK(hipMalloc(&h->wslabA, h->wplan.slabA_floats * sizeof(float)));
         HIPCHK(hipMalloc(&h->wslabB, h->wplan.slabB_floats * sizeof(float)));
-    } else if (h->kernel == TBNN_KERNEL_FAST) {
-        grid = h->jit ? h->jit->grid(n) : (h->mid_id >= 0 ? mid_grid_id(h->mid_id, n) : fast_grid(h->fast_id, n));
+    } else if (h->ops) {
+        grid = h->ops->grid(n);
         // test hook: a smaller grid puts small row counts into the many-rounds + cooperative-tail regime of the big ones
         if (const char* ge = getenv("TBNN_FAST_GRID")) { const int gg = atoi(ge); if (gg >= 1 && gg < grid) grid = gg; }
         h->scratchPerWG = 0;
@@ -463,7 +402,7 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
     // tbnn_forward always uses the generic forward kernel: keep a scratch for it
     h->grid = grid;
     h->pitch = (nd.P + 3) & ~3;                  // float4-readable slabs
-    h->nslab = h->wide_id >= 0 ? 1 : (h->lay ? h->lplan.NS : grid);
+    h->nslab = is_wide(h) ? 1 : (h->lay ? h->lplan.NS : grid);
     HIPCHK(hipMalloc(&h->slabs, (size_t)h->C * h->nslab * h->pitch * sizeof(float)));          // [C][nslab][pitch]
     HIPCHK(hipMemset(h->slabs, 0, (size_t)h->C * h->nslab * h->pitch * sizeof(float)));
     if (grid > PSTAT_CAP) return fail(-2, "grid exceeds PSTAT_CAP");
@@ -665,7 +604,7 @@ static inline int stat_entries(const tbnn_ctx* h) { return h->shard ? 1 : h->gri
 // local statistic buffer: entries >= grid stay zero; the all-reduced copy is separate (ranks may have different grids)
 static inline const double* stat_ptr(const tbnn_ctx* h) { return h->shard ? h->pstat_red : h->pstat; }
 // the gradient slabs k_update reduces
-static inline const float* grad_slabs(const tbnn_ctx* h) { return (h->shard && h->wide_id < 0) ? h->grow : h->slabs; }
+static inline const float* grad_slabs(const tbnn_ctx* h) { return (h->shard && !is_wide(h)) ? h->grow : h->slabs; }
 static inline int grad_nslab(const tbnn_ctx* h) { return h->shard ? 1 : h->nslab; }
 
 // ---- launch helpers (all on h->stream, no sync) ----
@@ -675,7 +614,7 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
     const float* img = nullptr;
     const int C = h->C;
     const long imgS = h->img_floats, slabS = (long)h->nslab * h->pitch;
-    if (h->kernel == TBNN_KERNEL_FAST) {
+    if (h->imgmap) {
         if (q == h->q && h->q_img_valid) img = h->qimg;
         else {
             hipLaunchKernelGGL(k_make_image, dim3((h->nd.P + 255) / 256, C), dim3(256), 0, h->stream, h->nd.P, q, h->imgmap, h->qimg_cur, (long)h->nd.P, imgS);
@@ -703,25 +642,17 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
             if (!done(c) && lay_launch(h->nd, h->lplan, h->stream, img + c * imgS, eta + (size_t)c * h->nd.H, h->dY, h->n, h->lstore, h->slabs + c * slabS, h->pitch,
                            h->pstat + (size_t)c * PSTAT_CAP))
                 return fail(-2, "layered kernel launch failed");
-    } else if (h->wide_id >= 0) {
+    } else if (is_wide(h)) {
         for (int c = 0; c < C; ++c) {
             if (done(c)) continue;
             const float* ic = img + c * imgS; const float* ec = eta + (size_t)c * h->nd.H;
             double* pc = h->pstat + (size_t)c * PSTAT_CAP; float* sl = h->slabs + c * slabS;
-            const int rc = h->jit ? h->jit->wlaunch(&h->wplan, h->stream, &h->nd, ic, ec, h->dX, h->dY, h->n, h->wstore, h->wslabA, h->wslabB, pc, sl)
-                                  : wide_launch(h->wplan, h->stream, h->nd, ic, ec, h->dX, h->dY, h->n, h->wstore, h->wslabA, h->wslabB, pc, sl);
-            if (rc) return fail(-2, "wide kernel launch failed");
+            if (h->ops->wlaunch(&h->wplan, h->stream, &h->nd, ic, ec, h->dX, h->dY, h->n, h->wstore, h->wslabA, h->wslabB, pc, sl))
+                return fail(-2, h->kernel_name + ": launch failed");
         }
-    } else if (h->kernel == TBNN_KERNEL_FAST && h->jit) {
-        if (h->jit->launch(h->grid, h->stream, &h->nd, img, eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, C, cs))
-            return fail(-2, "registered kernel launch failed");
-    } else if (h->kernel == TBNN_KERNEL_FAST && h->mid_id >= 0) {
-        if (mid_launch(h->mid_id, h->grid, h->stream, h->nd, img, eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, C, cs))
-            return fail(-2, "mid kernel launch failed");
-    } else if (h->kernel == TBNN_KERNEL_FAST) {
-        int rc = h->fast_ver == 3 ? fast3_launch(h->fast_id, h->grid, h->stream, h->nd, img, eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, nullptr, C, cs)
-                                  : fast_launch(h->fast_id, h->grid, h->stream, h->nd, img, eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, nullptr, C, cs);
-        if (rc) return fail(-2, "fast kernel launch failed");
+    } else if (h->ops) {
+        if (h->ops->launch(h->grid, h->stream, &h->nd, img, eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, C, cs))
+            return fail(-2, h->kernel_name + ": launch failed");
     } else {
         for (int c = 0; c < C; ++c)
             if (!done(c)) hipLaunchKernelGGL(k_fwd_bwd_generic, dim3(h->grid), dim3(GEN_RB), 0, h->stream, h->nd, q + (size_t)c * h->nd.P, eta + (size_t)c * h->nd.H, h->dX,
@@ -732,12 +663,12 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
         // statistic, summed to one value on the device, travel together as P + 1 doubles (the sum over the ranks is then
         // taken in double and rounded once; at configs[1]-class step times a second small all-reduce would cost as much as
         // the step), summed over the ranks in place, unpacked into the row k_update reads and pstat_red[0]
-        float* row = h->wide_id < 0 ? h->grow : h->slabs;
+        float* row = is_wide(h) ? h->slabs : h->grow;
         const int P = h->nd.P;
-        if (h->wide_id < 0)
+        if (!is_wide(h))
             hipLaunchKernelGGL(k_slab_reduce, dim3((P + 63) / 64), dim3(64, 4), 0, h->stream, (const float*)h->slabs, h->nslab,
                                h->pitch, P, (float*)nullptr, h->shard_buf);
-        hipLaunchKernelGGL(k_shard_pack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, h->wide_id < 0 ? (const float*)nullptr : (const float*)row,
+        hipLaunchKernelGGL(k_shard_pack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, is_wide(h) ? (const float*)row : (const float*)nullptr,
                            (const double*)h->pstat, h->grid, h->shard_buf);
         NCCLCHK(g_rccl.AllReduce(h->shard_buf, h->shard_buf, (size_t)P + 1, ncclDouble, ncclSum, h->shard->comm, h->stream));
         hipLaunchKernelGGL(k_shard_unpack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, (const double*)h->shard_buf, row, h->pstat_red);
@@ -750,7 +681,7 @@ static void launch_update(tbnn_ctx* h, int mode, float eps, const float* eta, fl
     const bool big = h->nd.P >= UPD_BIG_P;             // block geometry by parameter count (update_ops.hpp)
     const int ucols = big ? UPD_COLS_BIG : UPD_COLS;
     const int gx = (h->pitch / 4 + ucols - 1) / ucols;
-    const bool img = h->kernel == TBNN_KERNEL_FAST && q == h->q;
+    const bool img = h->imgmap && q == h->q;
     // the data-term gradient goes with its state: the proposal's (h->gd) or, for the bootstrap evaluation, the current one's
     float* gd = g == h->g_cur ? h->gd_cur : (g == h->g ? h->gd : nullptr);
     if (big)
@@ -826,20 +757,15 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     return 0;
 }
 
-// the narrow family's forward-only kernel exists for fast3 shapes (registry or run-time compiled)
-static inline bool narrow_fwd_ok(const tbnn_ctx* h) {
-    if (h->kernel != TBNN_KERNEL_FAST || h->wide_id >= 0) return false;
-    return h->jit ? h->jit->nforward != nullptr : (h->mid_id >= 0 || h->fast_ver == 3);
-}
+// the narrow family's forward-only kernel (fast3, mid and tall tables)
+static inline bool narrow_fwd_ok(const tbnn_ctx* h) { return h->ops && h->ops->nforward; }
 // `nets` networks whose images lie img_stride floats apart -> outputs out_stride floats apart
 static int narrow_forward(tbnn_ctx* h, int nets, const float* imgs, long img_stride, const float* dX, long n, float* dOut, long out_stride) {
     const long ntiles = (n + 15) / 16, wgs = (ntiles + FAST_WAVES - 1) / FAST_WAVES;
     // one network: fill the chip; an ensemble: the networks (grid.y) do that, fewer workgroups each re-use the image more
     const long cap = nets >= 64 ? 16 : (nets >= 8 ? 64 : 256);
     const int gx = (int)std::max<long>(1, std::min<long>(wgs, cap));
-    if (h->jit) return h->jit->nforward(gx, nets, h->stream, imgs, img_stride, dX, n, dOut, out_stride);
-    if (h->mid_id >= 0) return mid_forward(h->mid_id, gx, nets, h->stream, imgs, img_stride, dX, n, dOut, out_stride);
-    return fast3_forward(h->fast_id, gx, nets, h->stream, imgs, img_stride, dX, n, dOut, out_stride);
+    return h->ops->nforward(gx, nets, h->stream, imgs, img_stride, dX, n, dOut, out_stride);
 }
 
 // the layered family's forward chain (network.predict) on a store of its own: the rows are packed once, then any number of
@@ -877,13 +803,10 @@ static int lay_fwd_run(tbnn_ctx* h, const LayFwd& lf, const float* q, float* dOu
 // forward pass of the network at the weights q (device) over dX[n][d_in] -> dOut[d_out][n], on h->stream
 static int launch_forward(tbnn_ctx* h, const float* q, const float* dX, long n, float* dOut) {
     const NetDev& nd = h->nd;
-    const bool wide_fwd = h->wide_id >= 0 && (h->jit ? h->jit->wforward != nullptr : h->wplan.fwd_ok != 0);
-    if (wide_fwd) {
+    if (h->ops && h->ops->wforward) {
         // MFMA forward (k_chain_wide<S, FWD>): needs the padded image of q
         hipLaunchKernelGGL(k_make_image, dim3((nd.P + 255) / 256), dim3(256), 0, h->stream, nd.P, q, h->imgmap, h->qimg_cur);
-        const int rc = h->jit ? h->jit->wforward(h->stream, &h->nd, h->qimg_cur, dX, n, dOut)
-                              : wide_forward(h->wide_id, h->stream, h->nd, h->qimg_cur, dX, n, dOut);
-        if (rc) return fail(-2, "wide forward launch failed");
+        if (h->ops->wforward(h->stream, &h->nd, h->qimg_cur, dX, n, dOut)) return fail(-2, "wide forward launch failed");
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -1085,9 +1008,8 @@ static int enqueue_transition(tbnn_ctx* h, float eps, int L, const float* d_p0, 
     // a small problem on an ahead-of-time narrow kernel: the L leapfrog steps in ONE launch, one workgroup per chain (kernels_traj.hpp).
     // Not for a traced transition (per-step energies) or a sharded gradient.  Profiling (tbnn_set_profiling) does NOT change the path (round 6;
     // ADVICE round 5): a profiled trajectory launch is bracketed by one event pair and reported per leapfrog step (its time / L).
-    const bool traj = h->traj && !d_trace && L >= 1 && h->kernel == TBNN_KERNEL_FAST && h->wide_id < 0 && h->mid_id < 0 && !h->lay && !h->shard &&
-                      (h->jit ? (h->jit->family == TBNN_FAMILY_NARROW && h->jit->traj != nullptr && h->n <= h->jit->traj_max_rows)
-                              : (h->fast_ver == 3 && h->n <= fast3_traj_max_rows(h->fast_id)));
+    const bool traj = h->traj && !d_trace && L >= 1 && h->ops && h->ops->family == TBNN_FAMILY_NARROW && h->ops->traj && h->n <= h->ops->traj_max_rows &&
+                      !h->shard;
     h->last_path = traj ? "trajectory" : "per-step";
     if (traj) {
         hipEvent_t ea = nullptr, eb = nullptr;
@@ -1098,10 +1020,8 @@ static int enqueue_transition(tbnn_ctx* h, float eps, int L, const float* d_p0, 
             h->pev_div.push_back(L);
             hipEventRecord(ea, h->stream);
         }
-        const int trc = h->jit ? h->jit->traj(h->C, h->stream, &nd, h->qimg, (long)h->img_floats, h->eta, h->dX, h->dY, h->n, h->q, h->p, h->g, h->gd, h->imgmap,
-                                              h->pstat, stat_entries(h), eps, L, ctl)
-                               : fast3_traj_launch(h->fast_id, h->C, h->stream, nd, h->qimg, (long)h->img_floats, h->eta, h->dX, h->dY, h->n, h->q, h->p, h->g,
-                                                   h->gd, h->imgmap, h->pstat, stat_entries(h), eps, L, ctl);
+        const int trc = h->ops->traj(h->C, h->stream, &nd, h->qimg, (long)h->img_floats, h->eta, h->dX, h->dY, h->n, h->q, h->p, h->g, h->gd, h->imgmap,
+                                     h->pstat, stat_entries(h), eps, L, ctl);
         if (prof) hipEventRecord(eb, h->stream);
         if (trc)
             return fail(-2, "trajectory kernel launch failed");
@@ -1437,16 +1357,17 @@ extern "C" int tbnn_debug_draw(tbnn_handle h, uint32_t epoch, uint32_t purpose, 
 extern "C" int tbnn_debug_stamps(tbnn_handle h, uint64_t* out5) {
     if (!out5) return fail(-1, "null out16");
     NEED(h);
-    if (h->kernel != TBNN_KERNEL_FAST || h->wide_id >= 0 || h->mid_id >= 0 || h->jit || h->lay || !h->dX || h->C > 1) return fail(-1, "debug_stamps: narrow fast kernel + data required");
+    if (!h->ops || h->ops != narrow_find(h->nd) || !h->dX || h->C > 1) return fail(-1, "debug_stamps: narrow fast kernel + data required");
     HIPCHK(hipSetDevice(h->device));
     unsigned long long* d = nullptr;
     HIPCHK(hipMalloc(&d, 16 * sizeof(unsigned long long)));
     HIPCHK(hipMemset(d, 0, 16 * sizeof(unsigned long long)));
     hipLaunchKernelGGL(k_make_image, dim3((h->nd.P + 255) / 256), dim3(256), 0, h->stream, h->nd.P, h->q_cur, h->imgmap, h->qimg_cur);
-    for (int rep = 0; rep < 3; ++rep) {
-        if (h->fast_ver == 3) fast3_launch(h->fast_id, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d);
-        else fast_launch(h->fast_id, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d);
-    }
+    for (int rep = 0; rep < 3; ++rep)
+        if (narrow_launch_stamped(h->ops, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d)) {
+            hipFree(d);
+            return fail(-2, "debug_stamps: launch failed");
+        }
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out5, d, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     hipFree(d);
@@ -1462,7 +1383,7 @@ extern "C" int tbnn_debug_fused_burst(tbnn_handle h, int32_t reps, float* us_per
     const size_t PB = (size_t)h->C * h->nd.P * sizeof(float);
     // the proposal buffers (free between two transitions) take a copy of the current state; its image is built once
     HIPCHK(hipMemcpyAsync(h->q, h->q_cur, PB, hipMemcpyDeviceToDevice, h->stream));
-    if (h->kernel == TBNN_KERNEL_FAST) {
+    if (h->imgmap) {
         hipLaunchKernelGGL(k_make_image, dim3((h->nd.P + 255) / 256, h->C), dim3(256), 0, h->stream, h->nd.P, (const float*)h->q, h->imgmap, h->qimg, (long)h->nd.P,
                            (long)h->img_floats);
         h->q_img_valid = true;
@@ -1485,11 +1406,15 @@ extern "C" int tbnn_debug_fused_burst(tbnn_handle h, int32_t reps, float* us_per
 }
 
 #ifdef TBNN_TILE_STAMPS
+// the stamps of the narrow kernels (tbnn_narrow.hip's copy) over those of the hyper step (this unit's copy, kernels_hyper.hpp: HSTAMP)
 extern "C" int tbnn_debug_tile_stamps(tbnn_handle h, uint64_t* out64) {
     NEED(h);
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_tile_stamps), 64 * sizeof(uint64_t)));
+    unsigned long long narrow[64];
+    if (tbnn_jit_tile_stamps(narrow)) return fail(-2, "tbnn_jit_tile_stamps failed");
+    for (int k = 0; k < 64; ++k) if (narrow[k]) out64[k] = narrow[k];
     return 0;
 }
 #endif

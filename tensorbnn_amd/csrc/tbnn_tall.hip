@@ -2,7 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include "jit_tall.hpp"
-#include "tall_api.hpp"
+#include "aot_ops.hpp"
 
 using TShapeMnist = Shape<TBNN_ACT_RELU, TBNN_ACT_SIGMOID, true, 784, 20, 20, 1>;     // docs/ClassificationExample.md:103-173
 using TShapeT1 = Shape<TBNN_ACT_TANH, TBNN_ACT_NONE, false, 70, 24, 40, 1>;           // test: fan-in % 4 != 0 (scalar row loads), ragged widths

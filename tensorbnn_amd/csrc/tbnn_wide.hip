@@ -1,9 +1,8 @@
-// Registry + launchers of the wide-layer kernels (kernels_wide.hpp).
+// Registry of the ahead-of-time instantiations of the wide-layer kernels (kernels_wide.hpp).
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#define TBNN_NO_FAST_REGISTRY
-#include "wide_api.hpp"
-#include "kernels_wide.hpp"
+#include <mutex>
+#include "jit_wide.hpp"
+#include "aot_ops.hpp"
 
 using WShapeC4 = Shape<TBNN_ACT_RELU, TBNN_ACT_NONE, false, 10, 200, 200, 200, 1>;      // BASELINE configs[3]
 using WShapeC5 = Shape<TBNN_ACT_RELU, TBNN_ACT_SIGMOID, true, 20, 100, 100, 2>;         // BASELINE configs[4]
@@ -12,53 +11,18 @@ using WShapeT2 = Shape<TBNN_ACT_SIGMOID, TBNN_ACT_SIGMOID, true, 20, 32, 16, 48,
 
 template <> struct WideForceStream<WShapeT2> { static constexpr bool value = true; };   // keeps the ring path under the small-shape tests
 
-template <class S>
-static bool wshape_matches(const NetDev& nd) {
-    if (nd.nl != S::NL) return false;
-    if ((nd.lik == TBNN_LIK_BERNOULLI) != S::BERN) return false;
-    for (int l = 0; l < S::NL; ++l)
-        if (nd.in[l] != S::D[l] || nd.out[l] != S::D[l + 1] || nd.act[l] != S::act(l)) return false;
-    return true;
-}
+static FusedOps g_wide[4];
+static std::once_flag g_wide_once;
 
-int wide_lookup(const NetDev& nd) {
-    if (wshape_matches<WShapeC4>(nd)) return 0;
-    if (wshape_matches<WShapeC5>(nd)) return 1;
-    if (wshape_matches<WShapeT1>(nd)) return 2;
-    if (wshape_matches<WShapeT2>(nd)) return 3;
-    return -1;
-}
-const char* wide_name(int id) {
-    switch (id) {
-        case 0: return "wide<relu;10,200,200,200,1>";
-        case 1: return "wide<relu,sigmoid,bernoulli;20,100,100,2>";
-        case 2: return "wide<tanh;3,20,36,2>";
-        case 3: return "wide<sigmoid,sigmoid,bernoulli;20,32,16,48,2>";
-        default: return "wide<none>";
-    }
-}
-
-#define WIDE_DISPATCH(id, CALL)                                   \
-    switch (id) {                                                 \
-        case 0: { using S = WShapeC4; CALL; } break;              \
-        case 1: { using S = WShapeC5; CALL; } break;              \
-        case 2: { using S = WShapeT1; CALL; } break;              \
-        case 3: { using S = WShapeT2; CALL; } break;              \
-        default: break;                                           \
-    }
-
-void wide_image_map_id(int id, int* map) { WIDE_DISPATCH(id, wide_image_map<S>(map)); }
-void wide_plan(int id, long n, WidePlan& plan) { plan.id = id; WIDE_DISPATCH(id, (wide_plan_t<S>(n, plan), plan.fwd_ok = wide_forward_ok<S>() ? 1 : 0)); }
-int wide_forward(int id, hipStream_t st, const NetDev& nd, const float* qimg, const float* X, long n, float* fout) {
-    int rc = -1;
-    WIDE_DISPATCH(id, rc = wide_forward_t<S>(st, nd, qimg, X, n, fout));
-    return rc;
-}
-int wide_launch(const WidePlan& plan, hipStream_t st, const NetDev& nd, const float* qimg, const float* eta,
-                const float* X, const float* Y, long n, float* store, float* slabA, float* slabB, double* pstat, float* out) {
-    int rc = -1;
-    WIDE_DISPATCH(plan.id, rc = wide_launch_t<S>(plan, st, nd, qimg, eta, X, Y, n, store, slabA, slabB, pstat, out));
-    return rc;
+const FusedOps* wide_find(const NetDev& nd) {
+    std::call_once(g_wide_once, [] {
+        JitWide<WShapeC4>::fill(&g_wide[0], "wide<relu;10,200,200,200,1>");
+        JitWide<WShapeC5>::fill(&g_wide[1], "wide<relu,sigmoid,bernoulli;20,100,100,2>");
+        JitWide<WShapeT1>::fill(&g_wide[2], "wide<tanh;3,20,36,2>");
+        JitWide<WShapeT2>::fill(&g_wide[3], "wide<sigmoid,sigmoid,bernoulli;20,32,16,48,2>");
+    });
+    for (const FusedOps& o : g_wide) if (fused_ops_match(o, nd)) return &o;
+    return nullptr;
 }
 
 #ifdef WIDE_STAMPS

@@ -1,9 +1,9 @@
-// Host interface of the wide-layer path (kernels_wide.hpp), compiled in its own
-// translation unit (tbnn_wide.hip) so that the two big kernel families build in parallel.
+// Workgroup plan of the wide-layer path (kernels_wide.hpp): what FusedOps::plan fills and FusedOps::wlaunch reads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.hpp"
 
+// (id, fwd_ok: no longer read; they keep the layout the run-time libraries of TBNN_JIT_ABI 6 were built against)
 struct WidePlan {
     int id = -1;
     int gridA = 0;               // k_chain_wide workgroups (= entries of pstat)
@@ -13,15 +13,5 @@ struct WidePlan {
     size_t slabA_floats = 0;     // gridA x compact slab (first + last layer)
     size_t slabB_floats = 0;     // gridB x middle-layer slab
     int img_floats = 0;
-    int fwd_ok = 0;              // a forward-only instantiation exists (wide_forward)
+    int fwd_ok = 0;
 };
-
-int wide_lookup(const NetDev& nd);
-const char* wide_name(int id);
-void wide_image_map_id(int id, int* map);          // 2P ints
-void wide_plan(int id, long n, WidePlan& plan);
-// k_chain_wide + k_dw_wide + k_reduce_wide on `st`; out: one dense gradient row of P floats
-int wide_launch(const WidePlan& plan, hipStream_t st, const NetDev& nd, const float* qimg, const float* eta,
-                const float* X, const float* Y, long n, float* store, float* slabA, float* slabB, double* pstat, float* out);
-// forward only (network.predict): fout[d_out][n]; qimg = padded image of the weights
-int wide_forward(int id, hipStream_t st, const NetDev& nd, const float* qimg, const float* X, long n, float* fout);

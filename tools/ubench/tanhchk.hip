@@ -1,7 +1,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
-#define TBNN_NO_FAST_REGISTRY
 #include "../../tensorbnn_amd/csrc/kernels_fast.hpp"
 __global__ void k(const float* z, float* o, int n) { int i = blockIdx.x * 256 + threadIdx.x; if (i < n) o[i] = actc_fwd<TBNN_ACT_TANH>(z[i]); }
 int main() {
