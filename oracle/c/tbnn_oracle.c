@@ -140,7 +140,7 @@ double oracle_logp_grad(const onet* n, const float* th, const float* eta, const 
                         const float y = Y[(r0 + r) * d_out + i], fi = f[i * RB + r];
                         if (n->lik == 2) {
                             float p = fi < 1e-8f ? 1e-8f : (fi > 1.f - 1e-7f ? 1.f - 1e-7f : fi);   /* likelihood.py:226-231 */
-                            const int inside = fi > 1e-8f && fi < 1.f - 1e-7f;
+                            const int inside = fi >= 1e-8f && fi <= 1.f - 1e-7f;
                             st += (double)((y == 0.f ? 0.f : y * logf(p)) + ((1.f - y) == 0.f ? 0.f : (1.f - y) * log1pf(-p)));
                             da = inside ? (y / p - (1.f - y) / (1.f - p)) : 0.f;
                         } else {

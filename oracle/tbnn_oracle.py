@@ -314,7 +314,7 @@ def target_log_prob_and_grad(spec: NetSpec, theta, eta, X, Y, dtype=np.float32):
         d_a = ((y - f) / (sig * sig)).astype(dt)
     else:
         y = np.asarray(Y, dtype=dt).reshape(-1, f.shape[0]).T
-        inside = (f > dt(1e-8)) & (f < dt(1 - 1e-7))
+        inside = (f >= dt(1e-8)) & (f <= dt(1 - 1e-7))
         p = np.clip(f, dt(1e-8), dt(1 - 1e-7)).astype(dt)
         d_a = np.where(inside, y / p - (dt(1) - y) / (dt(1) - p), dt(0)).astype(dt)
     grads = [None] * len(spec.layers)

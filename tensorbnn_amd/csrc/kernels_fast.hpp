@@ -655,7 +655,7 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
     float da;
     if constexpr (S::BERN) {
         const float p = fminf(fmaxf(fi, 1e-8f), 1.f - 1e-7f);
-        const bool inside = (fi > 1e-8f) && (fi < 1.f - 1e-7f);
+        const bool inside = (fi >= 1e-8f) && (fi <= 1.f - 1e-7f);
 #if TBNN_FAST_BERN
         // hardware log2 / reciprocal (1 ulp) instead of the library logf / log1pf / IEEE division sequences: the fused
         // kernels are VALU-bound next to the f32 MFMA (every instruction ~9 cycles), the likelihood is ~100 of them

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
                 float da = 0.f;
                 if (nd.lik == TBNN_LIK_BERNOULLI) {
                     const float p = fminf(fmaxf(fi, 1e-8f), 1.f - 1e-7f);     // likelihood.py:226-231
-                    const bool inside = (fi > 1e-8f) && (fi < 1.f - 1e-7f);
+                    const bool inside = (fi >= 1e-8f) && (fi <= 1.f - 1e-7f);
                     if (valid) {
                         // tfd.Bernoulli.log_prob = xlogy(y,p) + xlog1py(1-y,-p)
                         const float t1 = (y == 0.f) ? 0.f : y * logf(p);

@@ -356,7 +356,7 @@ static inline void lay_gemm_launch(hipStream_t st, const float* img, int wpitch,
 // outputs per row they were half of the last layer's launch (784 -> 100 -> 100 -> 10: k_lay_last 12.7 us)
 __device__ __forceinline__ float lay_bernoulli(float fi, float y, double& stat) {
     const float p = fminf(fmaxf(fi, 1e-8f), 1.f - 1e-7f), q = 1.f - p;
-    const bool inside = (fi > 1e-8f) && (fi < 1.f - 1e-7f);
+    const bool inside = (fi >= 1e-8f) && (fi <= 1.f - 1e-7f);
     const float t1 = (y == 0.f) ? 0.f : y * __logf(p);
     const float t2 = (1.f - y == 0.f) ? 0.f : (1.f - y) * __logf(q);
     stat += (double)(t1 + t2);

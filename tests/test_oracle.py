@@ -150,6 +150,85 @@ def test_hand_coded_gradients_match_autograd(case):
         np.testing.assert_allclose(hg2, hg, rtol=1e-9, atol=1e-9 * np.abs(hg).max())
 
 
+# the last layer's activation: every one network.add takes after the final dense layer (Gaussian), and a Bernoulli likelihood on raw outputs,
+# clipped on both sides of [1e-8, 1 - 1e-7]
+LAST_CASES = {
+    "gauss_relu": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_GAUSSIAN, o.ACT_RELU),
+    "gauss_tanh": ([3, 12, 9, 2], 60, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_GAUSSIAN, o.ACT_TANH),
+    "gauss_sigmoid": ([4, 10, 3], 50, o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_GAUSSIAN, o.ACT_SIGMOID),
+    "gauss_exp": ([2, 8, 8, 1], 40, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_GAUSSIAN, o.ACT_EXP),
+    "gauss_elu": ([5, 16, 7, 3], 70, o.ACT_SIGMOID, o.PRIOR_GAUSSIAN, o.LIK_GAUSSIAN, o.ACT_ELU),
+    "bern_none": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_BERNOULLI, o.ACT_NONE),
+}
+
+
+@pytest.mark.parametrize("case", list(LAST_CASES))
+def test_hand_coded_gradients_match_autograd_last_activation(case):
+    dims, n, act, prior, lik, last = LAST_CASES[case]
+    spec, X, Y, theta, eta = o.synth_problem(dims, n, act, prior, lik)
+    spec.layers[-1].act = last
+    if last == o.ACT_NONE:
+        f = o.forward(spec, theta, X, np.float64)
+        assert (f > 1 - 1e-7).sum() > 10 and (f < 1e-8).sum() > 10 and ((f > 1e-8) & (f < 1 - 1e-7)).sum() > 10     # both clips + interior
+    rng = np.random.default_rng(1)
+    eta = (eta + 0.05 * rng.standard_normal(eta.size)).astype(np.float32)
+    lp_t, g_t, hl_t, hg_t = _torch_target(spec, theta, eta, X, Y)
+    lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)
+    assert abs(lp - lp_t) <= 1e-10 * abs(lp_t)
+    np.testing.assert_allclose(g, g_t, rtol=1e-9, atol=1e-9 * np.abs(g_t).max())
+    hl, hg = o.hyper_log_prob_and_grad(spec, eta, theta, X, Y, np.float64)
+    assert abs(hl - hl_t) <= 1e-10 * abs(hl_t)
+    np.testing.assert_allclose(hg, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
+
+
+def _tie_problem(last):
+    """1 -> 4 -> 1 relu, Bernoulli, every product and sum exact in fp32: the last layer's pre-activation of row r IS x_r.  last = sigmoid:
+    x over [15.5, 16.5), where the fp32 sigmoid returns exactly float32(1 - 1e-7) = 1 - 2^-23 (the clip's upper bound) on most rows; last = none:
+    raw outputs x exactly on both bounds, inside and outside them"""
+    if last == o.ACT_SIGMOID:
+        x = np.float32(15.5) + np.arange(64, dtype=np.float32) / np.float32(64)
+    else:
+        b_lo, b_hi = np.float32(1e-8), np.float32(1 - 1e-7)
+        x = np.array([b_lo] * 8 + [b_hi] * 8 + [0.25, 0.5, 0.75, 1.5, 2.0, -1.0, 1e-9, 0.0] * 2, np.float32)
+    spec = o.make_spec([1, 4, 1], o.ACT_RELU, o.PRIOR_GAUSSIAN, o.LIK_BERNOULLI, last)
+    W1, b1 = np.array([[1.0], [0.5], [-1.0], [2.0]], np.float32), np.zeros((4, 1), np.float32)
+    W2, b2 = np.array([[0.5, 1.0, 0.25, 0.0]], np.float32), np.zeros((1, 1), np.float32)
+    theta = o.flatten([(W1, b1), (W2, b2)]).astype(np.float32)
+    Y = (np.arange(x.size) % 4 == 3).astype(np.float32).reshape(-1, 1)                              # mostly label 0
+    return spec, x.reshape(-1, 1).astype(np.float32), Y, theta, o.default_hypers(spec, 0.5)
+
+
+@pytest.mark.parametrize("last", [o.ACT_SIGMOID, o.ACT_NONE])
+def test_fp32_clip_ties_match_autograd(last):
+    """tf.clip_by_value (likelihood.py:226-231) is minimum / maximum, whose gradients pass on ties, as torch.clamp's do: an fp32 output exactly on
+    a bound keeps its gradient (a label-0 row at 1 - 2^-23 behind a sigmoid: dL/dz = -p, about -1).  fp64 never meets the tie; this compares the
+    fp32 arms of the oracle and of autograd on rows that sit on it."""
+    import torch
+    from torch_ref import TorchTarget
+    spec, X, Y, theta, eta = _tie_problem(last)
+    f32 = o.forward(spec, theta, X, np.float32)
+    b_lo, b_hi = np.float32(1e-8), np.float32(1 - 1e-7)
+    tt = TorchTarget(spec, X, Y, torch.float32)
+    th = torch.tensor(theta)
+    a = tt.Xt
+    for i, l in enumerate(spec.layers):                      # the same forward in torch: the ties must be the same rows
+        W, b = (torch.from_numpy(p) for p in o.unflatten(spec, theta)[i])
+        a = W @ a + b
+        a = torch.relu(a) if l.act == o.ACT_RELU else torch.sigmoid(a) if l.act == o.ACT_SIGMOID else a
+    assert np.array_equal(a.numpy(), f32)
+    on = (f32 == b_hi) | (f32 == b_lo)
+    assert on.sum() >= (32 if last == o.ACT_SIGMOID else 16) and (f32 == b_hi).any() and ((f32 == b_hi) & (Y.T == 0)).sum() >= 4
+    lp_t, g_t = tt.value_and_grad(theta, eta)
+    lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
+    assert abs(lp - lp_t) <= 1e-6 * abs(lp_t)
+    for a_, b_ in ((0, 4), (4, 8), (8, 12), (12, 13)):
+        assert np.abs(g[a_:b_] - g_t[a_:b_]).max() <= 1e-5 * max(np.abs(g_t[a_:b_]).max(), 1e-3), (a_, g[a_:b_], g_t[a_:b_])
+    # the last bias collects dL/dz of every row: each label-0 row on the upper bound adds -p (or -1/(1-p) on raw outputs)
+    if last == o.ACT_SIGMOID:
+        at = (f32 == b_hi) & (Y.T == 0)
+        assert g[12] <= -0.99 * at.sum()
+
+
 @pytest.mark.parametrize("case", ["c1", "c2"])
 def test_float32_arm_within_stated_tolerance(case):
     """the reference's own arithmetic (fp32) sits inside the tolerance band the GPU tests use"""
