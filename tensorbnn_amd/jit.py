@@ -124,42 +124,72 @@ def families(dims) -> list:
 def wide_fits(dims) -> bool:
     """fan-in above 32 on the wide family (kernels_wide.hpp, WideCfg): W_0's operand granules (ceil(out_0 / 16) x ceil(d_in / 16) KB) in LDS next to the
     weight ring (4 slots of the widest layer's granules) and the per-wave scratch, and dW_0's ceil(out_0 / 16) x ceil((d_in + 1) / 16) accumulator
-    tiles beside the chain's registers (an estimate: the build refuses what does not fit or spills, and the next family takes the shape)"""
-    if dims[0] <= 32:
-        return True
+    tiles beside the chain's registers (an estimate: the build refuses what does not fit or spills, and the next family takes the shape).  At every
+    fan-in: k_chain_wide's register arrays (`regs`)"""
+    u = wide_usage(dims)
+    return all(u[k] <= v for k, v in WIDE_LIMITS.items() if k == "regs" or dims[0] > 32)
+
+
+# regs: 4 x (dW_0 tiles + the a_l tiles held in registers + the VALU last layer's weight tiles), k_chain_wide (WideCfg: DW0_TILES, ACT_TILES).
+# Measured over 63 wide builds (tests/golden/jit_build_outcomes.json): every shape up to 356 built without spilling, every shape from 372 spilled
+WIDE_LIMITS = {"lds": 156 * 1024, "tiles0": 63, "regs": 364}
+
+
+def wide_usage(dims) -> dict:
+    """`wide_fits`' estimates: LDS bytes and dW_0's accumulator tiles (mt0 * nt0)"""
     mt0, kg0, nt0 = _cdiv(dims[1], 16), _cdiv(dims[0], 16), _cdiv(dims[0] + 1, 16)
     maxgran = 4 * _cdiv(max(_cdiv(d, 16) for d in dims[1:-1]), 4)
     lds = (mt0 * kg0 * 256 + 4 * maxgran * 256 + 4 * (16 * (16 * nt0 + 4) + 16 * 68) + 16 * sum(_cdiv(d, 16) for d in dims[1:])) * 4
-    return lds <= 156 * 1024 and mt0 * nt0 <= 63
+    regs = 4 * (mt0 * nt0 + sum(_cdiv(d, 16) for d in dims[1:-1]) + (dims[-1] * _cdiv(dims[-2], 16) if dims[-1] <= 2 else 0))
+    return {"lds": lds, "tiles0": mt0 * nt0, "regs": regs}
 
 
 def mid_fits(dims) -> bool:
     """the mid-width fused kernel (kernels_mid.hpp, MidCfg): every dW tile of the MFMA layers in one wave's AccVGPRs (<= 63
     tiles) and the weight images + per-wave operand blocks in 160 KB of LDS.  <= 2 outputs: the last layer runs on the VALU; 3 .. 16
     outputs: it is one more MFMA layer (one output tile)"""
+    u = mid_usage(dims)
+    return all(u[k] <= v for k, v in MID_LIMITS.items())
+
+
+MID_LIMITS = {"tiles": 63, "lds": 160 * 1024}
+
+
+def mid_usage(dims) -> dict:
+    """`mid_fits`' estimates: dW tiles over the MFMA layers and LDS bytes"""
     nl = len(dims) - 1
     vl = dims[-1] <= 2
     nm = nl - 2 if vl else nl - 1               # MFMA layers behind layer 0: 1 .. nm
     tr = lambda l: _cdiv(dims[l], 16)           # tiles of a_l (input of layer l)
     ta = lambda l: _cdiv(dims[l] + 1, 16)
     tiles = tr(1) * ta(0) + sum(tr(l + 1) * ta(l) for l in range(1, nm + 1))
-    if tiles > 63:
-        return False
     r4 = lambda a: (a + 3) & ~3
     perm = r4(tr(1) * _cdiv(dims[0], 16) * 256 + sum(16 * tr(l + 1) for l in range(nm + 1)) + (dims[-1] * 16 * tr(nl - 1) + dims[-1] if vl else 0))
     img = r4(perm + sum(16 * tr(l + 1) * (16 * tr(l) + 4) for l in range(1, nm + 1)))
     maxt = max(tr(l) for l in range(1, nl if vl else nl + 1))
     wave = (ta(0) + sum(ta(l) for l in range(1, nm + 1)) + 2 * maxt) * 256      # (MidCfg::WAVE_FLOATS: two delta regions)
-    return (img + 4 * wave) * 4 + 64 <= 160 * 1024
+    return {"tiles": tiles, "lds": (img + 4 * wave) * 4 + 64}
 
 
 def tall_fits(dims) -> bool:
     """the tall-fan-in fused kernel (kernels_tall.hpp, TallCfg): a wave's chunk of W_0 and of dW_0 in its registers, the narrow
     layers' images, the exchange buffers and the per-wave operand blocks in 160 KB of LDS (an estimate: the build refuses a
     kernel that spills and the next family takes the shape).  <= 2 outputs: the last layer on the VALU; 3 .. 16: one more MFMA layer"""
+    u = tall_usage(dims)
+    return all(u[k] <= v for k, v in tall_limits(dims).items())
+
+
+def tall_limits(dims) -> dict:
+    # (one hidden layer: up to 128 units where the estimates below hold -- late round 6, as `families`)
+    # regs: a weighted sum of k_fwd_bwd_tall's register arrays -- the W_0 / dW_0 chunk (Wr, dW0: mt0 x ch tiles), the middle layers' dW tiles (dWm)
+    # and the VALU last layer's weights and accumulators (wL, LR.acc: d_out x TR(LL) tiles).  vgpr / vgpr_agpr alone do not tell spilling shapes
+    # from clean ones; over 55 tall builds (tests/golden/jit_build_outcomes.json) every shape up to 332 built without spilling, every one from 350 spilled
+    return {"hidden": 128 if len(dims) == 3 else 64, "vgpr": 256, "vgpr_agpr": 500, "lds": 160 * 1024, "regs": 340}
+
+
+def tall_usage(dims) -> dict:
+    """`tall_fits`' estimates: the widest hidden layer, VGPRs, VGPRs + AGPRs and LDS bytes"""
     nl = len(dims) - 1
-    if max(dims[1:-1]) > (128 if nl == 2 else 64):      # (one hidden layer: up to 128 units where the estimates below hold -- late round 6, as `families`)
-        return False
     vl = dims[-1] <= 2
     nm = nl - 2 if vl else nl - 1               # MFMA layers behind layer 0: 1 .. nm
     tr = lambda l: _cdiv(dims[l], 16)
@@ -168,14 +198,14 @@ def tall_fits(dims) -> bool:
     dwm = sum(tr(l + 1) * ta(l) for l in range(1, nm + 1))
     vgpr = 4 * mt0 * ch + 6 * ch + 70
     agpr = 4 * mt0 * ch + 4 * dwm
-    if vgpr > 256 or vgpr + agpr > 500:
-        return False
     r4 = lambda a: (a + 3) & ~3
     perm = r4(sum(16 * tr(l + 1) for l in range(nm + 1)) + (dims[-1] * 16 * tr(nl - 1) + dims[-1] if vl else 0))
     small = r4(perm + sum(16 * tr(l + 1) * (16 * tr(l) + 4) for l in range(1, nm + 1)))
     # exchange buffer of a group's 4 tiles | dW_0 staging of the epilogue, delta_0 of the group, per-wave a_l / delta_l blocks of the middle layers
     wave = (sum(ta(l) for l in range(1, nm + 1)) + sum(tr(l + 1) for l in range(1, nm + 1))) * 256
-    return (small + max(16 * mt0, 4 * ch) * 256 + 4 * mt0 * 256 + 4 * wave) * 4 + 64 <= 160 * 1024
+    lds = (small + max(16 * mt0, 4 * ch) * 256 + 4 * mt0 * 256 + 4 * wave) * 4 + 64
+    regs = 7 * mt0 * ch + 10 * dwm + 12 * (dims[-1] * tr(nl - 1) if vl else 0)
+    return {"hidden": max(dims[1:-1]), "vgpr": vgpr, "vgpr_agpr": vgpr + agpr, "lds": lds, "regs": regs}
 
 
 def source(dims, hact, lact, bern, family) -> str:

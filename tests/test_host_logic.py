@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import edge_shapes
 import tbnn_oracle as o
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -242,6 +243,63 @@ def test_jit_family_choice_and_source():
     assert jit.shape_of(same, nat.LIK_GAUSSIAN)[1] == nat.ACT_TANH          # one activation: the plain code, the kernels of every round before
     deep = [(4, 8, nat.ACT_RELU if i % 2 else nat.ACT_TANH, 0) for i in range(1)] + [(8, 8, nat.ACT_RELU if i % 2 else nat.ACT_TANH, 0) for i in range(9)] + [(8, 1, 0, 0)]
     assert jit.shape_of(deep, nat.LIK_GAUSSIAN) is None                     # 10 hidden layers with mixed activations: the layered family
+
+
+@pytest.mark.parametrize("case", edge_shapes.cases(), ids=lambda c: c["name"])
+def test_capacity_edge_pairs(monkeypatch, case):
+    """tests/edge_shapes.py: the largest shape each family admits along one dimension, and its first refused neighbour.  The family lists the shape
+    and not the neighbour; recomputing the tile / LDS / register / width totals, the shape keeps every rule and the neighbour breaks the named one
+    alone"""
+    import edge_shapes as es
+    from tensorbnn_amd import jit
+    monkeypatch.delenv("TBNN_JIT_SKIP", raising=False)
+    fam, dims, nb = case["family"], case["dims"], case["refused"]
+    assert fam in jit.families(dims), (dims, jit.families(dims))
+    assert es.over(fam, dims) == set(), es.usage(fam, dims)
+    if nb is None:
+        return
+    assert sum(a != b for a, b in zip(dims, nb)) == 1 and sum(abs(a - b) for a, b in zip(dims, nb)) == 1, (dims, nb)
+    assert fam not in jit.families(nb), (nb, jit.families(nb))
+    assert es.over(fam, nb) == {case["limit"]}, (nb, es.usage(fam, nb))
+    value, bound = es.usage(fam, dims)[case["limit"]]
+    assert value <= bound < es.usage(fam, nb)[case["limit"]][0]
+
+
+def test_capacity_rules_restate_families(monkeypatch):
+    """edge_shapes.usage restates jit.families rule for rule: over a fixed grid of shapes, a family lists a shape exactly when no rule is broken"""
+    import edge_shapes as es
+    from tensorbnn_amd import jit
+    monkeypatch.delenv("TBNN_JIT_SKIP", raising=False)
+    rng = np.random.default_rng(41)
+    seen = {f: 0 for f in es.SKIP}
+    for _ in range(6000):
+        nl = int(rng.integers(2, 6))
+        dims = [int(rng.choice([rng.integers(1, 40), rng.integers(1, 900)]))] + [int(rng.integers(1, 300)) for _ in range(nl - 1)] + [int(rng.integers(1, 19))]
+        fams = jit.families(dims)
+        for f in es.SKIP:
+            assert (f in fams) == (not es.over(f, dims)), (f, dims, fams, es.usage(f, dims))
+            seen[f] += f in fams
+    assert all(v >= 20 for v in seen.values()), seen
+
+
+def test_estimates_agree_with_measured_builds(monkeypatch):
+    """tests/golden/jit_build_outcomes.json: the tall and wide builds measured with the compiler (spill or not).  The estimates admit every shape
+    that built and refuse every shape that spilled -- admitted means buildable; and every shape edge_shapes.MUST_REFUSE lists is refused"""
+    import json
+    import fuzz_shapes as fz
+    from tensorbnn_amd import jit
+    monkeypatch.delenv("TBNN_JIT_SKIP", raising=False)
+    doc = json.load(open(os.path.join(ROOT, "tests", "golden", "jit_build_outcomes.json")))
+    wrong = [(r["family"], r["dims"], r["built"]) for r in doc["outcomes"] if (r["family"] in jit.families(r["dims"])) != r["built"]]
+    assert not wrong, wrong
+    assert sum(not r["built"] for r in doc["outcomes"]) >= 10 and sum(r["built"] for r in doc["outcomes"]) >= 80
+    for (fam, dims), why in edge_shapes.MUST_REFUSE.items():
+        assert fam not in jit.families(list(dims)), (fam, dims, why)
+    # every fuzz draw the build refused is either refused by the estimates now, or admitted and run by tests/test_gpu_capacity.py
+    admitted = {(f, tuple(d)) for f, d in edge_shapes.UNBUILDABLE_ADMITTED}
+    for (fam, dims), why in fz.UNBUILDABLE.items():
+        f = {"onehidden": "fast"}.get(fam, fam)
+        assert (f not in jit.families(list(dims))) != ((f, dims) in admitted), (fam, dims, why)
 
 
 def test_predictor_reweight_without_likelihood(tmp_path):
