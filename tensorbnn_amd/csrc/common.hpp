@@ -38,14 +38,9 @@ struct NetDev {
 // configs[1], bench.py --workload c2: plain stores 18.81 k leapfrog steps/s (fused pass 49.6 us by hipEvent), non-temporal stores
 // 19.31 k (47.9 us), write-through 19.72 k (47.1 us).  Small next to long launches (configs[4], the mid-width kernel: 2,788 -> 2,797 steps/s), neutral for small networks (P < 2048:
 // plain stores), negative for the layered family's many small dW launches (8 -> 300 -> 300 -> 1: 493 -> 511 us): plain stores there.
-// TBNN_SLAB_NT: 0 plain stores everywhere, 1 non-temporal, 2 write-through (default).
-#ifndef TBNN_SLAB_NT
-#define TBNN_SLAB_NT 2
-#endif
 template <bool NT>
 __device__ __forceinline__ void slab_store(float* ptr, float val) {
-    if constexpr (NT && TBNN_SLAB_NT == 2) __hip_atomic_store(ptr, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if constexpr (NT && TBNN_SLAB_NT == 1) __builtin_nontemporal_store(val, ptr);
+    if constexpr (NT) __hip_atomic_store(ptr, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *ptr = val;
 }
 
@@ -56,7 +51,7 @@ __device__ __forceinline__ void slab_store(float* ptr, float val) {
 typedef float tb_f32x4 __attribute__((ext_vector_type(4)));
 template <bool WT>
 __device__ __forceinline__ void store16(float* ptr, const tb_f32x4& v) {
-    if constexpr (WT && TBNN_SLAB_NT == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(ptr), "v"(v) : "memory");
+    if constexpr (WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(ptr), "v"(v) : "memory");
     else *reinterpret_cast<tb_f32x4*>(ptr) = v;
 }
 

@@ -45,9 +45,6 @@ struct Shape {
     static constexpr int act(int l) { return l == NL - 1 ? LACT_ : ((HACT_ & TBNN_ACT_PACKED) ? (HACT_ >> (3 * l)) & 7 : HACT_); }
 };
 
-#ifndef TBNN_FAST_ACT
-#define TBNN_FAST_ACT 1
-#endif
 // DIAGNOSTIC builds only (TBNN_BUILD_TAG=skel.. TBNN_EXTRA_FLAGS=-DTBNN_SKEL=n, tools/experiments/skeleton.sh; wrong results, right
 // instruction streams -- never the product): what the one-wave-per-SIMD design of k_fwd_bwd_fast3 can reach.
 //   bit 0 (1): no row tiles at all -- prologue + epilogue only: the launch's fixed cost
@@ -63,7 +60,6 @@ __device__ __forceinline__ float actc_fwd(float z) {
     if constexpr ((TBNN_SKEL & 2) != 0) return z;
     // relu as ONE integer max on the bit pattern (negative floats are negative ints; no NaN canonicalisation op)
     else if constexpr (ACT == TBNN_ACT_RELU) return __int_as_float(max(__float_as_int(z), 0));
-#if TBNN_FAST_ACT
     // hardware exp2 / reciprocal (about 2 ulp) instead of the library tanhf / expf + IEEE division: in the fused kernels
     // every VALU instruction costs MFMA time
     else if constexpr (ACT == TBNN_ACT_TANH) {
@@ -75,10 +71,6 @@ __device__ __forceinline__ float actc_fwd(float z) {
         return fabsf(z) < 0.3f ? small : big;
     }
     else if constexpr (ACT == TBNN_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.f + __expf(-z));
-#else
-    else if constexpr (ACT == TBNN_ACT_TANH) return tanhf(z);
-    else if constexpr (ACT == TBNN_ACT_SIGMOID) return 1.f / (1.f + expf(-z));
-#endif
     else if constexpr (ACT == TBNN_ACT_EXP) return expf(z);
     else if constexpr (ACT == TBNN_ACT_ELU) return z > 0.f ? z : expm1f(z);
     else return z;
@@ -204,10 +196,7 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 // ONE other 16x16x4 MFMA in between -- two accumulator tiles taken in turn -- the asm form read a stale accumulator: 8.5e-2 relative
 // error in dW of a 7 -> 17 -> 33 -> 2 network on the narrow family's hand-threaded dW block; a 4x4x1 form accumulating into its predecessor's
 // result likewise.  The wide family's k_dw_wide takes its a-blocks in PAIRS when a wave owns two M tiles -- four accumulators in turn, kernels_wide.hpp: QM == 2, DW0_FAR.)  Operands come from LDS loads; the kernels drain the pipe
-// (mfma_drain) before the epilogue reads the accumulators.  TBNN_ACC_AGPR=0: builtin everywhere.
-#ifndef TBNN_ACC_AGPR
-#define TBNN_ACC_AGPR 1
-#endif
+// (mfma_drain) before the epilogue reads the accumulators.
 // TBNN_ASM_MFMA_NOP=1: every asm MFMA carries two wait states of its own.  The hardware wants them between a VALU write of a VGPR and an MFMA
 // that reads it as SrcA / SrcB / SrcC; the compiler keeps them for its own MFMAs and inserts nothing around inline asm.  An operand the register
 // allocator parked in an AccVGPR comes back through v_accvgpr_read (a VALU write), possibly right in front of the asm MFMA (round 5: wrong,
@@ -226,21 +215,13 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 #endif
 template <bool FAR>
 __device__ __forceinline__ void mfma16_acc(f32x4& c, float a, float b) {
-#if TBNN_ACC_AGPR
     if constexpr (FAR) asm volatile(TBNN_MFMA_PRE "v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
     else c = mfma16(a, b, c);
-#else
-    c = mfma16(a, b, c);
-#endif
 }
 template <bool FAR>
 __device__ __forceinline__ void mfma4_acc(f32x4& c, float a, float b) {        // the 16-block 4x4x1 form, accumulator pinned like mfma16_acc
-#if TBNN_ACC_AGPR
     if constexpr (FAR) asm volatile(TBNN_MFMA_PRE "v_mfma_f32_4x4x1_16b_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
     else c = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
-#else
-    c = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
-#endif
 }
 // An accumulator tile born in AccVGPRs.  `acc = f32x4{0, 0, 0, 0}` is a v_mov into ArchVGPRs as far as the register allocator is concerned: the
 // loop-carried value of a "+a" accumulator then has TWO register classes (VGPR from the initialisation, AGPR from the asm MFMAs), the copies
@@ -249,21 +230,15 @@ __device__ __forceinline__ void mfma4_acc(f32x4& c, float a, float b) {        /
 // a machine where the f32 MFMA and the VALU share the issue slot: round 6, found in the disassembly after PMC showed one non-MFMA VALU
 // instruction per MFMA).  Written through asm "=a" outputs the initial value is of the accumulators' own class.
 __device__ __forceinline__ f32x4 acc_zero() {
-#if TBNN_ACC_AGPR
     float z0, z1, z2, z3;
     asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(z0));
     asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(z1));
     asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(z2));
     asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(z3));
     return f32x4{z0, z1, z2, z3};
-#else
-    return f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
 }
 __device__ __forceinline__ void mfma_drain() {
-#if TBNN_ACC_AGPR
     asm volatile("s_nop 15\n\ts_nop 15");
-#endif
 }
 // ... and every later read of the accumulators ordered BEHIND the drain: volatile asm statements keep their order, and an
 // empty one that "modifies" acc[t] makes each later use of acc[t] depend on it.  (mfma_drain() alone orders nothing that has
@@ -272,10 +247,8 @@ __device__ __forceinline__ void mfma_drain() {
 template <int N>
 __device__ __forceinline__ void mfma_drain_acc(f32x4 (&acc)[N]) {
     mfma_drain();
-#if TBNN_ACC_AGPR
 #pragma unroll
     for (int t = 0; t < N; ++t) asm volatile("" : "+a"(acc[t]));
-#endif
 }
 
 // ---- instruction-level helpers shared by the narrow (kernels_fast3.hpp) and wide (kernels_wide.hpp) kernels ----
@@ -302,27 +275,15 @@ __device__ __forceinline__ f32x2 pkfma_bc(f32x2 a, f32x2 b, f32x2 c) {
 // Relu derivative of a pair of activation outputs as {0, 1} floats in ONE packed instruction: clamp(a * FLT_MAX) to
 // [0, 1].  a >= 0 always; every normal a > 0 gives 1, a == 0 gives 0 (a positive denormal below 2.9e-39 would give a
 // fraction: a pre-activation in that interval does not occur in fp32 arithmetic of this size).  The mask is applied
-// with v_mul_legacy_f32 (0 * x = 0 for every x, inf and NaN included), so a masked-out element is an exact zero
-// like the select it replaces: 1.5 VALU instructions per element instead of v_cmp + v_cndmask.
-#ifndef TBNN_F3_RELU_PK
-#define TBNN_F3_RELU_PK 1
-#endif
+// by a packed multiply too (pkmul2): one VALU instruction per element instead of v_cmp + v_cndmask.
 __device__ __forceinline__ f32x2 relu_step2(f32x2 a, f32x2 big) {
     f32x2 d;
     asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(big));
     return d;
 }
-#ifndef TBNN_F3_RELU_PKMUL
-#define TBNN_F3_RELU_PKMUL 1
-#endif
 __device__ __forceinline__ f32x2 pkmul2(f32x2 a, f32x2 b) {
     f32x2 d;
     asm("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ float mul_legacy(float s, float x) {
-    float d;
-    asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(d) : "v"(s), "v"(x));
     return d;
 }
 // The opaque instructions above read MFMA results, and no software wait states are inserted for inline asm: settle()
@@ -351,19 +312,13 @@ template <int ACT, bool SETTLED>
 __device__ __forceinline__ f32x4 actc_bwd_mul4(f32x4 acc, f32x4 a) {
     f32x4 r;
     if constexpr ((TBNN_SKEL & 2) != 0) return acc;
-    else if constexpr (ACT == TBNN_ACT_RELU && TBNN_F3_RELU_PK && SETTLED) {
+    else if constexpr (ACT == TBNN_ACT_RELU && SETTLED) {
         const f32x2 big = {3.402823466e38f, 3.402823466e38f};
         const f32x2 s01 = relu_step2(f32x2{a[0], a[1]}, big), s23 = relu_step2(f32x2{a[2], a[3]}, big);
-#if TBNN_F3_RELU_PKMUL
-        // the mask applied by a PACKED multiply too: one instruction per register pair instead of one v_mul_legacy per register.
-        // (0 * inf = NaN here where the legacy multiply gives 0: a non-finite delta means a diverged trajectory, whose energy is
-        // non-finite either way -> rejected; the oracle's `delta * (a > 0)` makes the same NaN)
+        // (0 * inf = NaN: a non-finite delta means a diverged trajectory, whose energy is non-finite either way -> rejected; the
+        // oracle's `delta * (a > 0)` makes the same NaN)
         const f32x2 r01 = pkmul2(s01, f32x2{acc[0], acc[1]}), r23 = pkmul2(s23, f32x2{acc[2], acc[3]});
         r[0] = r01[0]; r[1] = r01[1]; r[2] = r23[0]; r[3] = r23[1];
-#else
-        r[0] = mul_legacy(s01[0], acc[0]); r[1] = mul_legacy(s01[1], acc[1]);
-        r[2] = mul_legacy(s23[0], acc[2]); r[3] = mul_legacy(s23[1], acc[3]);
-#endif
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) r[i] = actc_bwd_mul<ACT>(acc[i], a[i]);
@@ -383,35 +338,10 @@ __device__ __forceinline__ f32x2 pkmul_bc(f32x2 a, f32x2 b) {
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
 }
-// sum over the 4 lane groups, broadcast to every lane (row i16); C is the inline constant 0 (a bias travelling in C
-// would cost four v_mov to splat it, one v_add afterwards is cheaper)
-// Only register 0 of the result is used.  The other three are dead the moment the MFMA is issued as far as the register allocator knows -- and
-// the MFMA writes them eight passes LATER: an inline-asm VALU instruction (relu_step2, pkmul2 ..: invisible to the compiler's hazard recognizer)
-// allocated to one of them would have its result overwritten when the MFMA lands (round 6, hazard_lint rule R2c: `v_pk_mul_f32 v[40:41] .. clamp`
-// one instruction behind `v_mfma_f32_16x16x4_f32 v[38:41]` in the configs[1] kernel; every reader happened to come before the MFMA landed).
-// `then` is the consumer of the sum, compiler-generated VALU code (which waits for the result by itself); the empty asm behind it keeps the
-// three unused registers reserved until then.
-__device__ __forceinline__ float gsum(float p);
-// Round 6: the lane-group sum of the fringe units runs on the row-swap instructions (gsum: 4 VALU instructions) by default.  The MFMA form
-// (ones x p, rounds 4-5) costs the matrix pipe 8 passes per sum and makes its consumer wait 10 wait states for register 0 of the result
-// (the configs[1] tile loop carried ~85 wait states of s_nop behind its 11 lane-sum MFMAs); measured on one box, alternating runs of
-// bench.py --workload c2: 20,749 / 20,723 leapfrog steps/s with the MFMA form, 20,967 / 20,959 with the swaps (+1.1 %; the fused pass by
-// hipEvent 45.45 -> 44.98 us).  The two forms add the four lane groups in different orders (fp32 rounding: not bit-equal).
-#ifndef TBNN_GSUM_PERMLANE
-#define TBNN_GSUM_PERMLANE 1
-#endif
-template <class F>
-__device__ __forceinline__ float gsum_mfma(float p, F then) {
-    if constexpr (TBNN_GSUM_PERMLANE) return then(gsum(p));      // A/B: the lane-group sum on the row-swap instructions (4 VALU, no matrix pipe time, no 10-wait-state read)
-    const f32x4 r = mfma16(1.f, p, f32x4{0.f, 0.f, 0.f, 0.f});
-    float z = then(r[0]);
-    asm("" : "+v"(z) : "v"(r[1]), "v"(r[2]), "v"(r[3]));
-    return z;
-}
-
-
 // sum over the 4 lane groups (same lane&15) with the gfx950 row-swap instructions: VALU only, no
-// LDS round trip (ds_bpermute would put ~2 x 100 cycles of latency on the layer chain)
+// LDS round trip (ds_bpermute would put ~2 x 100 cycles of latency on the layer chain).  Round 6: this replaced the
+// MFMA form (ones x p, rounds 4-5), which cost the matrix pipe 8 passes per sum and made its consumer wait 10 wait
+// states for the result (bench.py --workload c2: +1.1 %; the two forms add the lane groups in different orders).
 __device__ __forceinline__ float gsum(float p) {
     const unsigned a = __float_as_uint(p);
     const auto r = __builtin_amdgcn_permlane32_swap(a, a, false, false);   // lanes l and l^32
@@ -419,6 +349,11 @@ __device__ __forceinline__ float gsum(float p) {
     const unsigned b = __float_as_uint(s);
     const auto q = __builtin_amdgcn_permlane16_swap(b, b, false, false);   // rows r and r^1
     return __uint_as_float(q[0]) + __uint_as_float(q[1]);
+}
+// then(gsum(p)): the consumer of the sum as a callable (the narrow kernels' register allocation depends on this form)
+template <class F>
+__device__ __forceinline__ float gsum_then(float p, F then) {
+    return then(gsum(p));
 }
 
 
@@ -444,11 +379,7 @@ struct TileRegs {
     float x0[C::KS0];
 };
 
-#ifdef TBNN_NOFENCE
-#define SCHED_FENCE() do {} while (0)
-#else
 #define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 
 // ---- forward: layer l.  Its first k-group of A operands and its bias tiles arrive preloaded
 // (An, Bn); before its last MFMAs it preloads those of layer l+1.  The transposed image of its
@@ -647,16 +578,12 @@ struct LastRegs {
 };
 
 // likelihood for one output value: statistic (counted when `count`), returns dL/df * act'
-#ifndef TBNN_FAST_BERN
-#define TBNN_FAST_BERN 1
-#endif
 template <class S>
 __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat) {
     float da;
     if constexpr (S::BERN) {
         const float p = fminf(fmaxf(fi, 1e-8f), 1.f - 1e-7f);
         const bool inside = (fi >= 1e-8f) && (fi <= 1.f - 1e-7f);
-#if TBNN_FAST_BERN
         // hardware log2 / reciprocal (1 ulp) instead of the library logf / log1pf / IEEE division sequences: the fused
         // kernels are VALU-bound next to the f32 MFMA (every instruction ~9 cycles), the likelihood is ~100 of them
         const float q = 1.f - p;
@@ -664,12 +591,6 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
         const float t2 = (1.f - yy == 0.f) ? 0.f : (1.f - yy) * __logf(q);
         if (count) stat += (double)(t1 + t2);
         da = inside ? (yy * __builtin_amdgcn_rcpf(p) - (1.f - yy) * __builtin_amdgcn_rcpf(q)) : 0.f;
-#else
-        const float t1 = (yy == 0.f) ? 0.f : yy * logf(p);
-        const float t2 = (1.f - yy == 0.f) ? 0.f : (1.f - yy) * log1pf(-p);
-        if (count) stat += (double)(t1 + t2);
-        da = inside ? (yy / p - (1.f - yy) / (1.f - p)) : 0.f;
-#endif
     } else {
         const float res = yy - fi;
         if (count) stat += (double)res * (double)res;
@@ -696,9 +617,6 @@ struct TileStep {
             const int u = 4 * t + g;
             if (u < d_in) wl[C::aoff(0) + i16 * C::PA(0) + u] = x[t];       // transposed image of x (ones column preset)
         }
-#ifdef TBNN_IGLP
-        __builtin_amdgcn_iglp_opt(TBNN_IGLP);
-#endif
         TSTAMP(0);
         FwdLayer<S, 0>::run(T, lds, wl, i16, g, A0, B0);
         f32x4 dz[C::MT(LM)];

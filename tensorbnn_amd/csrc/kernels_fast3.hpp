@@ -4,8 +4,8 @@
 // forward / delta-chain MFMAs and 4 of the 16 dW tiles of a layer exist for 2 units.  Here a layer with
 // out % 16 in {1, 2} keeps MTF = out/16 full tiles on the 16x16x4 path and computes its NF fringe units apart:
 //   forward   z_u = b_u + sum_k W[u][k] a[k]: per-lane partial sums over the lane's own k-slots on the 16-block
-//             v_mfma_f32_4x4x1 (fringe_partials), summed over the 4 lane groups by ONE 16x16x4 MFMA with A = 1
-//             (gsum_mfma); the result (all lanes) is dropped into register 0 of the fringe tile (lane group f) so
+//             v_mfma_f32_4x4x1 (fringe_partials), summed over the 4 lane groups by the row-swap instructions
+//             (gsum); the result (all lanes) is dropped into register 0 of the fringe tile (lane group f) so
 //             that it feeds the next layer's last k-step exactly like an MFMA result would;
 //   delta     d_u = act'(a_u) sum_i W[i][u] delta[i]: same shape, W^T image;
 //   dW rows   dW[u][k] += d_u a_{l-1}[k]: in the B-operand layout of the a_{l-1} image registers that feed the MFMA
@@ -15,7 +15,7 @@
 // On gfx950 the f32 MFMA and the f32 VALU share one issue slot (tools/ubench/coexec.hip: every VALU instruction
 // adds ~9 cycles to the MFMA stream), so the tile body is shaped by instruction count: AccVGPR-pinned dW
 // accumulators next to VGPR-form chain MFMAs (kernels_fast.hpp, mfma16_acc), LDS traffic threaded by hand through
-// the dW MFMAs (Pipe3), packed instructions kept packed (pkfma*), a 1.5-instruction relu derivative (actc_bwd_mul4).
+// the dW MFMAs (Pipe3), packed instructions kept packed (pkfma*), a one-instruction relu derivative (actc_bwd_mul4).
 // C2: 270 + 67 (4x4x1) + 11 MFMAs, 227 VALU and 148 LDS instructions per 16-row tile.  DESIGN.md section 4.
 #pragma once
 #include <type_traits>
@@ -26,24 +26,6 @@ template <int I, int N, class F>
 __device__ __forceinline__ void sfor3(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); sfor3<I + 1, N>(f); }
 }
-#ifndef TBNN_F3_HAND
-#define TBNN_F3_HAND 1
-#endif
-
-// MFMAs per LDS instruction when issue(l) is threaded through dW_{l+1} (0: separate phases, the round-1 schedule).
-// Measured on configs[1]: 54.3 us (0) -> 53.9 us (1..3).
-#ifndef TBNN_SGB
-#define TBNN_SGB 2
-#endif
-// 1: fringe dW rows in the B-operand layout (fewer registers: the f32 VALU shares the MFMA's issue slot, every
-// spill copy costs ~9 cycles of tile time); 0: per-lane sums in the D layout (the first fast3 version)
-#ifndef TBNN_F3_FB
-#define TBNN_F3_FB 1
-#endif
-// 1: thread the LDS instructions of issue(l) through the (asm) dW MFMAs of layer l+1 by hand
-#ifndef TBNN_F3_THREAD
-#define TBNN_F3_THREAD 1
-#endif
 template <class S>
 struct F3Cfg : FastCfg<S> {
     using B = FastCfg<S>;
@@ -58,13 +40,10 @@ struct F3Cfg : FastCfg<S> {
     // 48, 49 and the ones slot: image slots 48 + 4 j).  With at most 4 such columns the last N tile leaves the 16x16x4 path (MTF x 4
     // MFMAs of 32 cycles per tile and layer) for the 16-block 4x4x1 form: block b = units 4b .. 4b+3, columns = slots 48 + 4j, one
     // instruction (8 cycles) per data row -- 16 per tile and layer, ONE accumulator tile instead of MTF.  NTF: N tiles on the 16x16x4 path.
-#ifndef TBNN_F3_NFRINGE
-#define TBNN_F3_NFRINGE 1
-#endif
     // (only where the epilogue stages all dW tiles in ONE pass -- at most 39 tiles before the change: the pair of N-fringe accumulators is summed there)
     static constexpr int dw_tiles_plain() { int o = 0; for (int m = 0; m < NLM3; ++m) o += MTF(m) * B::NT(m); return o; }
     static constexpr bool NCF(int l) {
-        return TBNN_F3_NFRINGE && TBNN_ACC_AGPR && TBNN_F3_THREAD && dw_tiles_plain() <= 39 && l < NLM3 && B::NT(l) >= 2 && MTF(l) >= 1 && MTF(l) <= 4 && B::in(l) + 1 - 16 * (B::NT(l) - 1) <= 4;
+        return dw_tiles_plain() <= 39 && l < NLM3 && B::NT(l) >= 2 && MTF(l) >= 1 && MTF(l) <= 4 && B::in(l) + 1 - 16 * (B::NT(l) - 1) <= 4;
     }
     static constexpr int NTF(int l) { return NCF(l) ? B::NT(l) - 1 : B::NT(l); }
     // (two N-fringe accumulators, even / odd data rows: a 4x4x1 MFMA that accumulates into the result of the one before it needs
@@ -76,8 +55,9 @@ struct F3Cfg : FastCfg<S> {
     // per-lane k-slots of layer l's input: natural x for layer 0, else 4 registers of every tile of a_{l-1}
     static constexpr int KIN(int l) { return l == 0 ? B::KS0 : 4 * B::MT(l - 1); }
     // fringe rows of dW: layers with an MFMA dW part accumulate them in the *B-operand* layout (the a_{l-1} image
-    // registers that feed dW_l anyway): 2 registers per N tile instead of NF*(KIN+1) per-lane sums in the D layout.
-    static constexpr bool FB(int l) { return TBNN_F3_FB && NF(l) > 0 && MTF(l) > 0; }
+    // registers that feed dW_l anyway): 2 registers per N tile instead of NF*(KIN+1) per-lane sums in the D layout (fewer registers:
+    // the f32 VALU shares the MFMA's issue slot, every spill copy costs ~9 cycles of tile time).
+    static constexpr bool FB(int l) { return NF(l) > 0 && MTF(l) > 0; }
     static constexpr int fpn(int l) { return NF(l) == 0 ? 0 : (FB(l) ? 2 * B::NT(l) : NF(l) * (KIN(l) + 1)); }
     static constexpr int fpoff(int l) { int o = 0; for (int m = 0; m < l; ++m) o += fpn(m); return o; }
     static constexpr int FP_REGS = fpoff(B::NL);
@@ -105,16 +85,11 @@ struct Tile3 {
     float x0[C::KS0];
 };
 
-// TBNN_F3_M4 (default): the fringe dot products on the 16-block v_mfma_f32_4x4x1_f32 instead of VALU FMAs.
+// The fringe dot products run on the 16-block v_mfma_f32_4x4x1_f32 instead of VALU FMAs.
 // Block b = lane/4 = (lane group g, row quad i16/4) multiplies A[m = i16&3] = W[fringe unit m][k-slot of group g] by
 // B[n = i16&3] = a[k-slot][row i16] -- the D-layout activation register as it stands -- so after one instruction per
-// k-slot register, accumulator register m of every lane holds exactly the per-lane partial sum that dot_slots computes
-// for fringe unit m (2 passes = 8 cycles per instruction against ~12 cycles per dependent packed FMA).  The sum over
-// the 4 lane groups is ONE 16x16x4 MFMA with A = 1 (B[k = g][n = i16] is the register of partials as it stands):
-// every register of every lane of the result holds the finished pre-activation of row i16.
-#ifndef TBNN_F3_M4
-#define TBNN_F3_M4 1
-#endif
+// k-slot register, accumulator register m of every lane holds the per-lane partial sum over its own k-slots for fringe
+// unit m (2 passes = 8 cycles per instruction against ~12 cycles per dependent packed FMA).  gsum adds the 4 lane groups.
 #ifndef TBNN_F3_M4ACC
 #define TBNN_F3_M4ACC 2      // (4 until round 5; measured at configs[1]: 2 -> +0.5 %, 1 -> -0.2 %)
 #endif
@@ -140,28 +115,6 @@ __device__ __forceinline__ f32x4 fringe_partials(const float* __restrict__ prow,
         for (int a = 0; a + st < NA; a += 2 * st) acc[a] += acc[a + st];
     return acc[0];
 }
-// sum_k w[k-slot] * v[k-slot] over this lane's k-slots of a K dimension living in D-layout tiles
-// PK: `tiles` hold VALU results (activation outputs / masked deltas), so the opaque packed FMA may read them
-template <class S, int K, bool PK>
-__device__ __forceinline__ float dot_slots(const float* __restrict__ row, const f32x4* tiles, int g) {
-    using C = F3Cfg<S>;
-    // pairs of k-slots on v_pk_fma_f32 (two partial sums), the odd one out on a plain FMA
-    f32x2 p2 = {0.f, 0.f};
-    float p = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < C::cdiv(K, 16); ++kt) {
-        const f32x4 w = load_ks(row + 16 * kt + 4 * g, C::ksteps(K, kt));
-        const int ns = C::ksteps(K, kt);
-#pragma unroll
-        for (int s = 0; s + 1 < ns; s += 2) {
-            if constexpr (PK) p2 = pkfma(f32x2{w[s], w[s + 1]}, f32x2{tiles[kt][s], tiles[kt][s + 1]}, p2);
-            else p2 = f32x2{w[s], w[s + 1]} * f32x2{tiles[kt][s], tiles[kt][s + 1]} + p2;
-        }
-        if (ns & 1) p = fmaf(w[ns - 1], tiles[kt][ns - 1], p);
-    }
-    return (p2[0] + p2[1]) + p;
-}
-
 // IMG: write the transposed activation images the dW MFMAs read (off in the forward-only kernel)
 template <class S, int l, bool IMG = true>
 struct Fwd3 {
@@ -184,7 +137,7 @@ struct Fwd3 {
         }
     }
 
-    // ---- hand-scheduled form (TBNN_F3_HAND, default).  Left to itself the compiler requests an LDS operand two MFMAs before
+    // ---- hand-scheduled form.  Left to itself the compiler requests an LDS operand two MFMAs before
     // the MFMA that reads it and stalls on the round trip in every k-group, and it gathers the fringe 4x4x1 MFMAs at the end
     // of the layer, in front of the lane-sum MFMAs that depend on them (ISA of round 2: ~740 of a hidden layer's ~2,150
     // cycles are not MFMA time).  Here the issue order of a k-group is written out and pinned with scheduling fences
@@ -192,7 +145,7 @@ struct Fwd3 {
     // under the first MFMAs of the group one LDS read each -- the operands of the NEXT k-group, and in the last full group
     // the first operands of the next LAYER (A tiles, bias tiles, fringe weights).
     static constexpr int MTd = C::MTF(l) > 0 ? C::MTF(l) : 1;
-    static constexpr bool M4F = C::NF(l) > 0 && TBNN_F3_M4;                        // fringe dot products on the 4x4x1 MFMA
+    static constexpr bool M4F = C::NF(l) > 0;                       // fringe dot products on the 4x4x1 MFMA
     static constexpr int KGl = l == 0 ? 1 : C::KG(l);
     static constexpr int NFG = (C::MTF(l) == 0 && l > 0) ? KGl : 1;              // fringe-weight k-groups requested ahead (all of them for an all-fringe layer)
     struct Pre { f32x4 A[MTd]; f32x4 B[MTd]; f32x4 F[NFG]; };
@@ -300,11 +253,10 @@ struct Fwd3 {
             }
         }
         if constexpr (NF > 0) {
-            static_assert(TBNN_F3_M4, "the hand-scheduled form computes the fringe units on the 4x4x1 MFMA");
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                T.af[l][f] = gsum_mfma(pacc[f], [&](float s) { return actc_fwd<S::act(l)>(s + lds[C::boff(l) + C::fslot(l, f)]); });
+                T.af[l][f] = gsum_then(pacc[f], [&](float s) { return actc_fwd<S::act(l)>(s + lds[C::boff(l) + C::fslot(l, f)]); });
                 if (g == f) v[0] = T.af[l][f];
             }
             T.a[C::aroff(l) + MT] = v;
@@ -337,10 +289,9 @@ struct Fwd3 {
         constexpr bool more = l + 1 < C::NL;
         constexpr int MTN = more ? (C::MTF(l + 1) > 0 ? C::MTF(l + 1) : 1) : 1;
         f32x4 Anext[MTN], Bnext[MTN];
-        // ---- fringe units on the VALU (issued first: their two lane shuffles land under the MFMAs below)
-        float pf[NF > 0 ? NF : 1];
+        // ---- fringe units on the 4x4x1 MFMA (issued first: their two lane shuffles land under the MFMAs below)
         f32x4 pacc = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (NF > 0 && TBNN_F3_M4) {
+        if constexpr (NF > 0) {
             const float* prow = lds + C::woff(l) + (16 * MT + 4 * (i16 & 3)) * C::LDW(l);
             if constexpr (l == 0) {
 #pragma unroll
@@ -348,18 +299,6 @@ struct Fwd3 {
             } else {
                 pacc = fringe_partials<S, C::in(l)>(prow + 4 * g, &T.a[C::aroff(l - 1)]);
             }
-        }
-#pragma unroll
-        for (int f = 0; f < (TBNN_F3_M4 ? 0 : NF); ++f) {
-            const float* row = lds + C::woff(l) + C::fslot(l, f) * C::LDW(l);
-            float p = 0.f;
-            if constexpr (l == 0) {
-#pragma unroll
-                for (int t = 0; t < C::KS0; ++t) p = fmaf(row[4 * t + g], T.x0[t], p);
-            } else {
-                p = dot_slots<S, C::in(l), S::act(l - 1) != TBNN_ACT_NONE>(row, &T.a[C::aroff(l - 1)], g);
-            }
-            pf[f] = p;
         }
         // ---- full tiles on the MFMA path
         if constexpr (MT > 0) {
@@ -409,8 +348,7 @@ struct Fwd3 {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                if constexpr (TBNN_F3_M4) T.af[l][f] = gsum_mfma(pacc[f], [&](float s) { return actc_fwd<S::act(l)>(s + lds[C::boff(l) + C::fslot(l, f)]); });
-                else T.af[l][f] = actc_fwd<S::act(l)>(gsum(pf[f]) + lds[C::boff(l) + C::fslot(l, f)]);
+                T.af[l][f] = gsum_then(pacc[f], [&](float s) { return actc_fwd<S::act(l)>(s + lds[C::boff(l) + C::fslot(l, f)]); });
                 if (g == f) v[0] = T.af[l][f];
             }
             T.a[C::aroff(l) + MT] = v;
@@ -650,11 +588,9 @@ struct Bwd3 {
                                                f32x4 (&dzp)[C::MT(l > 0 ? l - 1 : 0)], float (&dzpf)[NFd]) {
         if constexpr (l > 0) {
             constexpr int MTP = C::MTF(l - 1), NFP = C::NF(l - 1), K = C::out(l);
-#if TBNN_F3_HAND
             if constexpr (MT > 0) {
                 // hand-scheduled chain (see Fwd3::run_h): k-step-major MFMAs, the fringe 4x4x1 behind each k-step, the next
                 // k-group's operands (MTP tiles of W^T + the fringe rows) one read per MFMA under the first MFMAs of the group
-                static_assert(TBNN_F3_M4, "the hand-scheduled form computes the fringe units on the 4x4x1 MFMA");
                 constexpr int KG = C::cdiv(K, 16), MTPd = MTP > 0 ? MTP : 1, NSL = MTP + (NFP > 0 ? 1 : 0);
                 constexpr int NA = KG < TBNN_F3_M4ACC ? KG : TBNN_F3_M4ACC;
                 f32x4 acc[MTPd], pa[NA], An[MTPd], Fn = {0.f, 0.f, 0.f, 0.f};
@@ -700,58 +636,13 @@ struct Bwd3 {
                         for (int a = 0; a + st < NA; a += 2 * st) pa[a] += pa[a + st];
                     pacc = pa[0];
                 }
-                if constexpr (S::act(l - 1) == TBNN_ACT_RELU && TBNN_F3_RELU_PK && MTP >= 1 && MTP <= 4) mfma_settle(acc);
+                if constexpr (S::act(l - 1) == TBNN_ACT_RELU && MTP >= 1 && MTP <= 4) mfma_settle(acc);
 #pragma unroll
                 for (int m = 0; m < MTP; ++m)
                     dzp[m] = actc_bwd_mul4<S::act(l - 1), (MTP >= 1 && MTP <= 4)>(acc[m], T.a[C::aroff(l - 1) + m]);
 #pragma unroll
                 for (int f = 0; f < NFP; ++f)
-                    dzpf[f] = gsum_mfma(pacc[f], [&](float s) { return actc_bwd_mul<S::act(l - 1)>(s, T.af[l - 1][f]); });
-#else
-            // fringe units of layer l-1 first (their shuffles land under the MFMAs)
-            float pf[NFP > 0 ? NFP : 1];
-            f32x4 pacc = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (MT > 0 && NFP > 0 && TBNN_F3_M4)
-                pacc = fringe_partials<S, K>(lds + C::toff(l) + (16 * MTP + 4 * (i16 & 3)) * C::LDT(l) + 4 * g, dz);
-            if constexpr (MT > 0 && !TBNN_F3_M4) {
-#pragma unroll
-                for (int f = 0; f < NFP; ++f)
-                    pf[f] = dot_slots<S, K, S::act(l) != TBNN_ACT_NONE>(lds + C::toff(l) + C::fslot(l - 1, f) * C::LDT(l), dz, g);
-            }
-            if constexpr (MT > 0) {
-                constexpr int KG = C::cdiv(K, 16);
-                f32x4 acc[MTP > 0 ? MTP : 1];
-#pragma unroll
-                for (int m = 0; m < MTP; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-                const float* trow = lds + C::toff(l) + i16 * C::LDT(l) + 4 * g;
-                f32x4 An[MTP > 0 ? MTP : 1];
-#pragma unroll
-                for (int m = 0; m < MTP; ++m) An[m] = load_ks(trow + 16 * m * C::LDT(l), C::ksteps(K, 0));
-#pragma unroll
-                for (int kt = 0; kt < KG; ++kt) {
-                    f32x4 A4[MTP > 0 ? MTP : 1];
-#pragma unroll
-                    for (int m = 0; m < MTP; ++m) A4[m] = An[m];
-                    if (kt + 1 < KG) {
-#pragma unroll
-                        for (int m = 0; m < MTP; ++m) An[m] = load_ks(trow + 16 * m * C::LDT(l) + 16 * (kt + 1), C::ksteps(K, kt + 1));
-                    }
-#pragma unroll
-                    for (int s = 0; s < C::ksteps(K, kt); ++s)
-#pragma unroll
-                        for (int m = 0; m < MTP; ++m) acc[m] = mfma16(A4[m][s], dz[kt][s], acc[m]);
-                }
-                if constexpr (S::act(l - 1) == TBNN_ACT_RELU && TBNN_F3_RELU_PK && MTP >= 1 && MTP <= 4) mfma_settle(acc);
-#pragma unroll
-                for (int m = 0; m < MTP; ++m)
-                    dzp[m] = actc_bwd_mul4<S::act(l - 1), (MTP >= 1 && MTP <= 4)>(acc[m], T.a[C::aroff(l - 1) + m]);
-#pragma unroll
-                for (int f = 0; f < NFP; ++f)
-                    {
-                    if constexpr (TBNN_F3_M4) dzpf[f] = gsum_mfma(pacc[f], [&](float s) { return actc_bwd_mul<S::act(l - 1)>(s, T.af[l - 1][f]); });
-                    else dzpf[f] = actc_bwd_mul<S::act(l - 1)>(gsum(pf[f]), T.af[l - 1][f]);
-                }
-#endif
+                    dzpf[f] = gsum_then(pacc[f], [&](float s) { return actc_bwd_mul<S::act(l - 1)>(s, T.af[l - 1][f]); });
             } else {
                 // all-fringe layer (the VALU last layer): K = NF fringe deltas, weights W_l[o][slot] read per lane
 #pragma unroll
@@ -798,25 +689,6 @@ struct Pipe3 {
                                                 const float (&Fup)[8]) {
         float Aop[Bwd3<S, l>::MTd][4], Bop[C::NT(l)][4], Fop[8];
         typename Bwd3<S, l>::NFOps NFop;
-        static_assert(!(C::NCF(l) || C::NCF(l + 1)) || (TBNN_ACC_AGPR && TBNN_F3_THREAD), "the N-side fringe rides in the hand-threaded pipeline");
-#if !(TBNN_ACC_AGPR && TBNN_F3_THREAD)
-        Bwd3<S, l>::issue(dz, dzf, wl, i16, g, Aop, Bop, Fop);
-#endif
-#if TBNN_SGB > 0 && !TBNN_ACC_AGPR
-        // the ~20 LDS instructions of issue(l) cost ~450 issue cycles on their own: thread them through the
-        // 48 MFMAs of dW_{l+1} (operands already in registers) -- 2 MFMAs, 1 DS, 2 MFMAs, 1 DS, ...
-        Bwd3<S, l + 1>::dw(dW, Aup, Bup);
-        {
-            constexpr int NDS = Bwd3<S, l>::MT > 0 ? 4 * Bwd3<S, l>::MT + C::NT(l) + Bwd3<S, l>::MT : 0;
-#pragma unroll
-            for (int i = 0; i < NDS; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, TBNN_SGB, 0);
-                __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);
-            }
-        }
-        SCHED_FENCE();
-        TSTAMP(10 + 4 * l);
-#elif TBNN_ACC_AGPR && TBNN_F3_THREAD
         {
             constexpr int NM = Bwd3<S, l + 1>::NMF, NL = Bwd3<S, l>::NLDS;
             static_assert(NM > 0, "the layer above has an MFMA dW part");
@@ -836,12 +708,6 @@ struct Pipe3 {
         }
         SCHED_FENCE();
         TSTAMP(10 + 4 * l);
-#else
-        SCHED_FENCE();
-        TSTAMP(10 + 4 * l);
-        Bwd3<S, l + 1>::dw(dW, Aup, Bup);
-        SCHED_FENCE();
-#endif
         TSTAMP(11 + 4 * l);
         Bwd3<S, l + 1>::fdw(FP, Fup, Bup);
         FringeDW<S, l>::run(FP, T, dzf, g);
@@ -992,10 +858,6 @@ struct FringeOut {
 // A wave issues ~90 MFMAs instead of ~350 and meets 4 barriers: ~0.4 of a tile time, for every workgroup at once.
 // Shapes with more than FAST_WAVES M tiles in a hidden layer (or no room for the 8.4-KB exchange buffers) keep the plain loop.
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef TBNN_F3_COOP
-#define TBNN_F3_COOP 1
-#endif
-
 template <class S>
 struct Coop3 {
     using C = F3Cfg<S>;
@@ -1003,13 +865,13 @@ struct Coop3 {
     static constexpr int NFd = C::maxNF() > 0 ? C::maxNF() : 1;
     static constexpr int HL = L > 0 ? L : 1;                              // hidden layers
     static constexpr bool shape_ok() {
-        if (C::NL < 2 || !TBNN_F3_M4 || !TBNN_F3_FB) return false;
+        if (C::NL < 2) return false;
         for (int l = 0; l < L; ++l) if (C::MT(l) > FAST_WAVES || C::MTF(l) < 1) return false;
         return true;
     }
     static constexpr int XAF = FAST_WAVES * 256;                          // fringe values behind the 4 tiles of an exchange buffer
     static constexpr int XB = XAF + 32;                                   // floats per exchange buffer; two alternate
-    static constexpr bool ENABLED = TBNN_F3_COOP && shape_ok() && ((size_t)C::LDS3_FLOATS + 2 * XB) * 4 + 64 <= 160 * 1024;
+    static constexpr bool ENABLED = shape_ok() && ((size_t)C::LDS3_FLOATS + 2 * XB) * 4 + 64 <= 160 * 1024;
     static constexpr int cwoff(int l) { int o = 0; for (int m = 0; m < l && m < C::NLM3; ++m) o += C::MTF(m) > 0 ? C::NT(m) : 0; return o; }
     static constexpr int DWC = cwoff(C::NL) > 0 ? cwoff(C::NL) : 1;
     static constexpr int FPd = C::FP_REGS > 0 ? C::FP_REGS : 1;
@@ -1076,7 +938,7 @@ struct Coop3 {
             }
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                const float a = gsum_mfma(pacc[f], [&](float s) { return actc_fwd<S::act(l)>(s + lds[C::boff(l) + C::fslot(l, f)]); });
+                const float a = gsum_then(pacc[f], [&](float s) { return actc_fwd<S::act(l)>(s + lds[C::boff(l) + C::fslot(l, f)]); });
                 if (g == f) mine[0] = a;
                 if (g == 0) xb[XAF + 16 * f + i16] = a;
             }
@@ -1178,7 +1040,7 @@ struct Coop3 {
                 const f32x4 pacc = fringe_partials<S, K>(lds + C::toff(l) + (16 * MTP + 4 * (i16 & 3)) * C::LDT(l) + 4 * g, dz);
 #pragma unroll
                 for (int f = 0; f < NFP; ++f) {
-                    dzpf[f] = gsum_mfma(pacc[f], [&](float s) { return actc_bwd_mul<S::act(l - 1)>(s, T.af[l - 1][f]); });
+                    dzpf[f] = gsum_then(pacc[f], [&](float s) { return actc_bwd_mul<S::act(l - 1)>(s, T.af[l - 1][f]); });
                     if (g == f) odz[0] = dzpf[f];
                     if constexpr (XCHG) { if (g == 0) xb[XAF + 16 * f + i16] = dzpf[f]; }
                 }
@@ -1342,12 +1204,6 @@ struct FringeVals {
 //  * the log-likelihood statistic is reduced after the stores are issued.
 // The sum over the four waves keeps its fixed order (c0 + c1) + (c2 + c3).
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef TBNN_F3_EPI
-#define TBNN_F3_EPI 1
-#endif
-#ifndef TBNN_F3_COOP_PEEL
-#define TBNN_F3_COOP_PEEL 1          // two copies of the cooperative tile instead of a loop (0: the loop; configs[1]: +0.3 us of register shuffles around it)
-#endif
 template <class S>
 struct Epi3 {
     using C = F3Cfg<S>;
@@ -1378,7 +1234,7 @@ struct Epi3 {
     static constexpr int ST_FLOATS = (3 * T + NFT) * 256;                         // staged tile copies
     static constexpr int LB_FLOATS = FAST_WAVES * C::FP_REGS * 64;                // fringe partials
     static constexpr int DENSE_OFF = ST_FLOATS + LB_FLOATS;
-    static constexpr bool ENABLED = TBNN_F3_EPI && C::DW3_TILES > 0 && C::EP3_TILES == C::DW3_TILES && C::P() >= 2048 &&
+    static constexpr bool ENABLED = C::DW3_TILES > 0 && C::EP3_TILES == C::DW3_TILES && C::P() >= 2048 &&
                                     (size_t)DENSE_OFF + P4 <= (size_t)C::LDS3_FLOATS;
 
     // wave W's cooperative accumulator for its copy of tile t (full tiles of its own M tile), or -1
@@ -1620,10 +1476,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     // The W^T images (delta chain: needed from the first BACKWARD pass on) do not go through registers: each wave sends its
     // share straight to LDS with global_load_lds (1 KB per instruction, no VGPRs held), and the wait + barrier that makes
     // them visible sits behind the first tile's forward pass -- the prologue proper stages the W / bias images only.
-#ifndef TBNN_F3_WTDMA
-#define TBNN_F3_WTDMA 1
-#endif
-    constexpr bool WTDMA = TBNN_F3_WTDMA && C::STATIC_FLOATS > C::WB_FLOATS;
+    constexpr bool WTDMA = C::STATIC_FLOATS > C::WB_FLOATS;
     if constexpr (WTDMA) {
         constexpr int WT = C::STATIC_FLOATS - C::WB_FLOATS, NCHUNK = (WT + 255) / 256;
         static_assert(C::WB_FLOATS % 4 == 0 && WT % 4 == 0, "16-B pieces");
@@ -1665,13 +1518,8 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int l = 1; l < C::NLM3; ++l)
         if (C::in(l) % 16 == 0 && g == 0) wl[C::aoff3(l) + C::in(l) * C::PR + i16] = 1.f;
-#if TBNN_F3_HAND
     typename Fwd3<S, 0>::Pre P0;                 // layer 0's operands (A, bias, fringe weights): the same for every tile
     Fwd3<S, 0>::pre_all(P0, lds, i16, g);
-#else
-    f32x4 A0[C::MTF(0) > 0 ? C::MTF(0) : 1], B0[C::MTF(0) > 0 ? C::MTF(0) : 1];
-    Fwd3<S, 0>::preload(A0, B0, lds, i16, g);
-#endif
 
     bool first = true;
     // the W^T images in flight: every wave of the workgroup must meet ONE barrier behind its own wait.  When all four waves
@@ -1696,11 +1544,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         for (int o = 0; o < d_out; ++o) y[o] = yn[o];
         fetch(tile + W);
         TSTAMP(0);
-#if TBNN_F3_HAND
         Fwd3<S, 0>::run_h(T, lds, wl, i16, g, P0);
-#else
-        Fwd3<S, 0>::run(T, lds, wl, i16, g, A0, B0);
-#endif
         if (wt_pending) {                       // first tile only, the same on all four waves
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -1728,16 +1572,12 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             if constexpr (C::NCF(LM)) FringeDW<S, L>::run(FP, T, dzf, g);
             TSTAMP(32);
             FringeDW<S, LM>::run(FP, T, dzpf, g);
-#ifndef TBNN_F3_NF_LATE
-#define TBNN_F3_NF_LATE 0
-#endif
-            if constexpr (!(TBNN_F3_NF_LATE && LM > 0)) Bwd3<S, LM>::nf_mfma(dW, NFop);
+            Bwd3<S, LM>::nf_mfma(dW, NFop);
             TSTAMP(33);
             if constexpr (LM > 0) {
                 f32x4 dzq[C::MT(LM - 1)];
                 float dzqf[NFd];
                 Bwd3<S, LM>::da(T, lds, i16, g, dzp, dzpf, dzq, dzqf);
-                if constexpr (TBNN_F3_NF_LATE != 0) Bwd3<S, LM>::nf_mfma(dW, NFop);
                 SCHED_FENCE();
                 TSTAMP(34);
                 Pipe3<S, LM - 1>::run(dW, FP, T, lds, wl, i16, g, dzq, dzqf, Aop, Bop, Fop);
@@ -1754,8 +1594,9 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int t = 0; t < CO::DWC; ++t) dWc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (CO::ENABLED) {
-        if constexpr (TBNN_F3_COOP_PEEL && C::P() >= 1024) {
-            // straight-line copies of the body, no loop: no loop-carried register shuffle around a tile (conditions are workgroup-uniform:
+        if constexpr (C::P() >= 1024) {
+            // straight-line copies of the body, no loop: no loop-carried register shuffle around a tile (configs[1]: the loop costs
+            // +0.3 us of register shuffles around it; conditions are workgroup-uniform:
             // the barriers inside are met by all 4 waves).  Small networks keep the loop: their launch is fetch- and launch-bound, the second
             // copy costs configs[0] 1 %
             const long ct0 = main_end + blockIdx.x, ct1 = ct0 + gridDim.x;
@@ -1882,13 +1723,8 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     constexpr int d_in = C::in(0), d_out = C::out(C::NL - 1), L = C::NL - 1;
     const long ntiles = (n + 15) / 16;
     const long W = (long)gridDim.x * FAST_WAVES;
-#if TBNN_F3_HAND
     typename Fwd3<S, 0, false>::Pre P0;
     Fwd3<S, 0, false>::pre_all(P0, lds, i16, g);
-#else
-    f32x4 A0[C::MTF(0) > 0 ? C::MTF(0) : 1], B0[C::MTF(0) > 0 ? C::MTF(0) : 1];
-    Fwd3<S, 0, false>::preload(A0, B0, lds, i16, g);
-#endif
     for (long tile = (long)blockIdx.x * FAST_WAVES + wave; tile < ntiles; tile += W) {
         Tile3<S> T;
         const long row = tile * 16 + i16;
@@ -1898,11 +1734,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             const int u = 4 * t + g;
             T.x0[t] = (ok && u < d_in) ? X[row * d_in + u] : 0.f;
         }
-#if TBNN_F3_HAND
         Fwd3<S, 0, false>::run_h(T, lds, nullptr, i16, g, P0);
-#else
-        Fwd3<S, 0, false>::run(T, lds, nullptr, i16, g, A0, B0);
-#endif
         if (ok && g == 0) {
 #pragma unroll
             for (int o = 0; o < d_out; ++o) fout[(size_t)o * n + row] = T.af[L][o];

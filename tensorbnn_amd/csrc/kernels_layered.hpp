@@ -58,18 +58,11 @@ struct LayPlan {
 // a result tile's 16 bytes per lane.  Every block this family stores is read by a LATER kernel, and between two kernels this part
 // writes every dirty L2 line back: stored write-through (sc1) nothing waits dirty for a launch's end (784-20-20-1: 56.4 -> 55.0 us per
 // leapfrog step, 100-50-50-1 at 1e5 rows: 153.4 -> 149.6; non-temporal stores instead: 56.4 -> 56.8 / 158.5 -- the reader then misses
-// L2 AND the memory-side cache).  LAY_ST_POLICY=0: plain stores.
-#ifndef LAY_ST_POLICY
-#define LAY_ST_POLICY 2
-#endif
+// L2 AND the memory-side cache).
 __device__ __forceinline__ void lay_block_store(float* p, const f32x4& v) {
-#if LAY_ST_POLICY == 2
     // (the s_nop: wait states between this > 64-bit store and a VALU write of its data registers, which the compiler's hazard
     // recognizer does not insert behind inline asm)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 #define LAY_RSRC_FLAGS 0x00020000           // raw buffer resources (as kernels_wide.hpp)
 static inline int lay_cdiv(long a, long b) { return (int)((a + b - 1) / b); }

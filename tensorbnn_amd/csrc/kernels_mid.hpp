@@ -123,10 +123,7 @@ struct MidCfg {
     // The D layout of the previous layer is the 4x4x1 form's B operand as it stands (block = (k phase g, row quad), as the narrow family uses it);
     // the four k phases are summed with the row-swap instructions (gsum) and unit 16 T + e lands in register 0 of lane group e: its slot (slot_of).
     // Worth it when the k loop is long (>= 8 k-steps: the sums cost ~20 VALU instructions).  dW's fringe strips are not built.
-#ifndef MID_FRINGE
-#define MID_FRINGE 1
-#endif
-    static constexpr bool fr_units(int U) { return MID_FRINGE && U > 16 && U % 16 >= 1 && U % 16 <= 4; }
+    static constexpr bool fr_units(int U) { return U > 16 && U % 16 >= 1 && U % 16 <= 4; }
     static constexpr int total_ksteps(int K) { return (K + 3) / 4; }
     static constexpr bool fr_out(int l) { return l >= 1 && fr_units(out(l)) && total_ksteps(in(l)) >= 8; }
     static constexpr bool fr_in(int l) { return l >= 1 && fr_units(in(l)) && total_ksteps(out(l)) >= 8; }
@@ -586,7 +583,7 @@ __global__ __launch_bounds__(MID_THREADS, 1) __attribute__((amdgpu_waves_per_eu(
             });
             MSTAMP(25 + 3 * SFOR_VAL(li));
             f32x4 dzp[C::MAXT];
-            constexpr bool PKR = S::act(l - 1) == TBNN_ACT_RELU && TBNN_F3_RELU_PK && MU <= 8;
+            constexpr bool PKR = S::act(l - 1) == TBNN_ACT_RELU && MU <= 8;
             if constexpr (PKR) mfma_settle(acc);
             if constexpr (C::fr_in(l)) {
                 float z[4];

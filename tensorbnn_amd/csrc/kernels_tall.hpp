@@ -94,11 +94,8 @@ struct TallCfg {
     static constexpr int MT0 = TR(1);
     // fringe: a first layer of 16 T + F units with 1 <= F <= 4 (20 = 16 + 4: the MNIST example) computes units 16 T .. 16 T + F - 1
     // on the 16-block v_mfma_f32_4x4x1 (8 cycles instead of 32 per k-step and column tile), in the forward pass and in dW_0
-#ifndef TALL_FRINGE
-#define TALL_FRINGE 1
-#endif
     static constexpr int F0 = out(0) % 16;
-    static constexpr bool FR0 = TALL_FRINGE && F0 >= 1 && F0 <= 4;
+    static constexpr bool FR0 = F0 >= 1 && F0 <= 4;
     static constexpr int MTF = FR0 ? MT0 - 1 : MT0;                     // full tiles of layer 0's units
     static constexpr int NT0 = cdiv(d_in + 1, 16);                      // column tiles of [x, 1]
     static constexpr int CH = cdiv(NT0, NW);                            // column tiles per wave
@@ -133,9 +130,6 @@ struct TallCfg {
         for (int m = 1; m <= NM; ++m) wave += (TA(m) + TR(m + 1)) * 256;
         return SMALL_FLOATS + (ex > stg ? ex : stg) + gmax * MT0 * 256 + NW * wave;
     }
-#ifndef TALL_C_REVERSE
-#define TALL_C_REVERSE 1
-#endif
 #ifndef TALL_GMAX
 #define TALL_GMAX 4
 #endif
@@ -265,11 +259,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int t = 0; t < MT0; ++t)
 #pragma unroll
-#ifdef TALL_DBG_NOPRO          // diagnostic build: what the W_0 chunk's loads cost
-            for (int c = 0; c < CH; ++c) Wr[t][c] = f32x4{0.001f * lane, 0.002f, 0.003f * c, 0.004f * t};
-#else
             for (int c = 0; c < CH; ++c) Wr[t][c] = w4[(size_t)(t * C::NTP + kt0 + c) * 64 + ((C::FR0 && t == C::MTF) ? flane : lane)];
-#endif
     }
     float* wl = lds + C::WAVE_OFF + wave * C::WAVE_FLOATS;
     {
@@ -367,22 +357,15 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
         }
         // dW_0's first operands (tile 0, k-step 0): requested here, used behind the narrow stretch
         float Bq[3][FWD ? 1 : CH];
-        __amdgpu_buffer_rsrc_t rsT = rsrc_rows(grp * Gr + (TALL_C_REVERSE ? Gr - 1 : 0));
+        __amdgpu_buffer_rsrc_t rsT = rsrc_rows(grp * Gr + (Gr - 1));
         auto ldT = [&](int s, float (&B)[FWD ? 1 : CH]) __attribute__((always_inline)) {
             if constexpr (!FWD) {
 #pragma unroll
-#ifdef TALL_DBG_NOLDT      // timing experiment only (wrong gradients): what the transposed re-read of the rows costs in phase C
-                for (int c = 0; c < CH; ++c) B[c] = 0.001f * (lane + s + c);
-#else
                 for (int c = 0; c < CH; ++c) B[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsT, vT, (4 * s * d_in + 16 * c) * 4, 0));
-#endif
             }
         };
-#ifndef TALL_DBG_NOC       // timing experiment only (no dW_0 at all: wrong gradients): what the pass costs WITHOUT phase C and without its slab stores --
-                           // the first kernel of a two-pass form whose second pass would contract delta_0^T X over column stripes (round 6, NOTES)
         ldT(0, Bq[0]);
         if (Gr * 4 > 1) ldT(1, Bq[1]);
-#endif
         TALL_STAMP_G(21);
         __syncthreads();
         TALL_STAMP_G(22);
@@ -563,24 +546,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
 
         // ---- C: dW_0 += delta_0^T [x, 1] over the group's tiles, this wave's column tiles; one k-step (rows 4 s .. 4 s + 3 of
         // tile tg) at a time, its rows requested two k-steps ahead
-#ifdef TALL_DBG_NOC
-        if constexpr (!FWD) {                                  // delta_0 of this wave's tile leaves for HBM instead (what the second pass would read)
-            if (wave < Gr) {
-                const float* db0 = lds + C::DB0_OFF + wave * (MT0 * 256);
-                float* dst = slabs + ((size_t)(grp * Gr + wave) * MT0) * 256;          // (inside the slab area: its contents mean nothing in this build)
-#pragma unroll
-                for (int t = 0; t < MT0; ++t) *reinterpret_cast<f32x4*>(dst + t * 256 + lane * 4) = *reinterpret_cast<const f32x4*>(db0 + t * 256 + lane * 4);
-            }
-        }
-#else
         if constexpr (!FWD) {
 #pragma unroll
             for (int q = 0; q < 4 * G; ++q) {
-                // (TALL_C_REVERSE: the group's LAST tile first -- its rows were read most recently in phase A and are the likeliest
+                // (the group's LAST tile first -- its rows were read most recently in phase A and are the likeliest
                 // to be in L2 still: 32 workgroups' groups of three are 4.8 MB against an XCD's 4 MB)
-                const int tg = TALL_C_REVERSE ? Gr - 1 - (q >> 2) : (q >> 2), s = q & 3;
+                const int tg = Gr - 1 - (q >> 2), s = q & 3;
                 if (q + 2 < 4 * Gr) {                                // two k-steps (52 MFMAs) ahead, three operand sets
-                    if (((q + 2) & 3) == 0) rsT = rsrc_rows(grp * Gr + (TALL_C_REVERSE ? Gr - 1 - ((q + 2) >> 2) : ((q + 2) >> 2)));
+                    if (((q + 2) & 3) == 0) rsT = rsrc_rows(grp * Gr + (Gr - 1 - ((q + 2) >> 2)));
                     ldT((q + 2) & 3, Bq[(q + 2) % 3]);
                 }
                 float (&Bop)[CH] = Bq[q % 3];
@@ -613,7 +586,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
                     }
             }
         }
-#endif
     }
     TALL_STAMP(18);
     if constexpr (!FWD) {
@@ -622,16 +594,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
         if constexpr (C::DWM_TILES > 0) mfma_drain_acc(dWm);
     }
     float* slab = slabs + (size_t)blockIdx.x * pitch;
-#ifndef TALL_WT
-#define TALL_WT 1
-#endif
-    constexpr bool WT = TALL_WT && C::P() >= 2048;
+    constexpr bool WT = C::P() >= 2048;
     // ---- dW_0: every wave writes its own column tiles.  D layout: lane (n = i16, g) reg r = dW[out slot 16t+4g+r][column 16kt+n]:
     // a lane's four registers are four ROWS of the slab.  With 16-B aligned rows the tiles of one M tile are turned through the
     // wave's own share of the staging area (the exchange buffer, dead by now; written [m][n], read back lane-linearly: lane l holds row
     // l / 4, columns 4 (l % 4) .. +3)
     // and leave as 16-byte write-through stores -- a 4-byte sc1 store is one fabric write per lane
-#ifndef TALL_DBG_NOC
     {
         constexpr int out0 = C::out(0);
         sfor<0, MT0>(SFOR_LAMBDA(t) {
@@ -656,11 +624,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
                     }
                     const int col = 16 * (kt0 + c) + n4;
                     if (row >= 0) {
-#ifdef TALL_DBG_NOSTORE        // diagnostic build: what the dW_0 slab stores cost
-                        if (col < d_in && v[0] == 123.456f) store16<WT>(slab + row * d_in + col, v);
-#else
                         if (col < d_in) store16<WT>(slab + row * d_in + col, v);
-#endif
                         else if (col == d_in) slab_store<WT>(slab + d_in * out0 + row, v[0]);      // the ones column: db_0
                     }
                 }
@@ -684,7 +648,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
             }
         });
     }
-#endif
     TALL_STAMP(19);
     const double wtot = wave_sum_lane0(stat);
     if (lane == 0) red[wave] = wtot;

@@ -124,13 +124,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
         for (int k = 0; k < C::FP_REGS; ++k) FP[k] = 0.f;
         stat = 0.0;
         // layer 0's operands (A, bias, fringe weights): the same for every tile of this step
-#if TBNN_F3_HAND
         typename Fwd3<S, 0>::Pre P0;
         Fwd3<S, 0>::pre_all(P0, lds, i16, gq);
-#else
-        f32x4 A0[C::MTF(0) > 0 ? C::MTF(0) : 1], B0[C::MTF(0) > 0 ? C::MTF(0) : 1];
-        Fwd3<S, 0>::preload(A0, B0, lds, i16, gq);
-#endif
 #pragma unroll 1
         for (long tile = wave; tile < ntiles; tile += NW) {
             Tile3<S> T;
@@ -146,11 +141,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
             }
 #pragma unroll
             for (int o = 0; o < d_out; ++o) y[o] = rvalid ? Y[row * d_out + o] : 0.f;
-#if TBNN_F3_HAND
             Fwd3<S, 0>::run_h(T, lds, wl, i16, gq, P0);
-#else
-            Fwd3<S, 0>::run(T, lds, wl, i16, gq, A0, B0);
-#endif
             float dzf[NFd];
 #pragma unroll
             for (int o = 0; o < NFd; ++o) dzf[o] = 0.f;

@@ -11,16 +11,14 @@
 //                  (200x200 fp32 = 160 KB): every wave walks ONE weight stream (W_1 .. W_NM, then
 //                  W_NM^T .. W_1^T, pre-swizzled into MFMA A-operand order by k_update; it lives in
 //                  L2) and fetches the next k-group's operands itself with buffer loads, one chunk
-//                  ahead of use (WIDE_DIRECT, round 3; WIDE_DIRECT=0 and shapes whose weights fit in
-//                  LDS: the round-1 design, one stream per workgroup through a 4-slot LDS ring).
+//                  ahead of use (round 3; shapes whose weights fit in LDS read them from there).
 //                  dW of the FIRST layer (fan-in <= 32) and of the LAST layer (<= 2 outputs, VALU) are
 //                  accumulated in registers as in the narrow kernel.  For every middle layer l the wave
 //                  stores a_l (+ ones slot) and delta_l to HBM in 1-KB [16 rows][16 slots] blocks,
-//                  already transposed for their consumer (WIDE_TBLOCK, round 3).
+//                  already transposed for their consumer (round 3).
 //   k_dw_wide      dW_l = delta_l^T a_l (contraction over ALL rows) for the middle layers: each
 //                  workgroup owns a row range and the whole 13x13-tile output (43 tiles per wave),
-//                  reads every operand with one 16-byte buffer load (no LDS; WIDE_TBLOCK=0: the blocks
-//                  go through a 4-slot LDS ring to be turned) and writes its partial dW to a private
+//                  reads every operand with one 16-byte buffer load (no LDS) and writes its partial dW to a private
 //                  slab; k_reduce_wide sums the slabs in fixed order (deterministic).
 //
 // Algorithmic HBM traffic of the split: 2 arrays (a_l, delta_l) x n x 4 B x padded width per middle
@@ -64,21 +62,10 @@ __device__ unsigned long long g_wide_stamps[256];
 #endif
 #define WIDE_THREADS 256
 #define WIDE_RING 4
-#ifndef WIDE_DW_PD
-// dW_0 accumulators pinned to AccVGPRs (kernels_fast.hpp, mfma16_acc) next to VGPR-form chain MFMAs (build.py): -1.5 % at configs[4]
-#ifndef WIDE_DW0_AGPR
-#define WIDE_DW0_AGPR 1
-#endif
-#define WIDE_DW_PD 1   // k_dw_wide: row tiles in flight from HBM beyond the two parked in LDS (measured: 1 = 2 = 4)
-#endif
 #ifndef WIDE_PD
 #define WIDE_PD 2      // weight-stream register sets: chunk c+2+k (k < WIDE_PD) is in flight while chunk c is consumed
 #endif
-#ifdef WIDE_DBG_NOBARRIER
-#define WIDE_CHUNK_BARRIER() do {} while (0)           // timing experiment (results wrong)
-#else
 #define WIDE_CHUNK_BARRIER() do { if constexpr (!C::RESIDENT) __syncthreads(); } while (0)
-#endif
 
 // test hook: shapes listed here take the streamed-weights path even though their image would fit in LDS
 template <class S> struct WideForceStream { static constexpr bool value = false; };
@@ -194,9 +181,6 @@ struct WideCfg {
     static constexpr int DWT(int l) { return QM(l) * TA(l) + QP(l); }           // accumulator tiles per wave
     static constexpr int maxDWT() { int m = 0; for (int l = 1; l <= NM; ++l) m = DWT(l) > m ? DWT(l) : m; return m; }
     static constexpr int SB(int l) { return TA(l) + TZ(l); }                    // 1-KB blocks per row tile
-    static constexpr int maxSB() { int m = 0; for (int l = 1; l <= NM; ++l) m = SB(l) > m ? SB(l) : m; return m; }
-    static constexpr int DW_SLOT_FLOATS = maxSB() * 256;
-    static constexpr int DW_NGW = cdiv(maxSB(), WIDE_WAVES);
     static constexpr int slabB_off(int l) { int o = 0; for (int m = 1; m < l; ++m) o += r4(in(m) * out(m) + out(m)); return o; }   // within one WG's slab
     static constexpr int SB_FLOATS = slabB_off(NM + 1);
 #ifndef WIDE_LL_COST8
@@ -215,16 +199,11 @@ struct WideCfg {
 #ifndef WIDE_DW_OCC_MAX
 #define WIDE_DW_OCC_MAX 2
 #endif
-#if !defined(WIDE_TBLOCK) || WIDE_TBLOCK
     // (transposed blocks, operands straight into registers: no LDS; two waves per SIMD when accumulators + operand sets fit)
     static constexpr int maxSmall() { int m = 0; for (int l = 1; l <= NM; ++l) { int v = TA(l) + 2 * QM(l) + 4 * QP(l); m = v > m ? v : m; } return m; }
     // (a layer with two M tiles per wave takes its a-blocks in pairs -- dw_wide_layer --: two operand blocks and their refills live at once)
     static constexpr bool anyQM2() { for (int l = 1; l <= NM; ++l) if (QM(l) == 2) return true; return false; }
     static constexpr int DW_OCC = (WIDE_DW_OCC_MAX >= 2 && 4 * maxDWT() + 4 * maxSmall() + 40 + (anyQM2() ? 36 : 0) <= 232) ? 2 : 1;
-#else
-    static constexpr int DW_OCC = (WIDE_DW_OCC_MAX >= 2 && 2 * WIDE_RING * DW_SLOT_FLOATS * 4 <= 150 * 1024 &&
-                                   4 * maxDWT() + 4 * DW_NGW * WIDE_DW_PD + 48 <= 232) ? 2 : 1;
-#endif
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -261,9 +240,6 @@ template <class S, int c, bool FWD = false>
 __device__ __forceinline__ void wide_stage(int base, f32x4 (&stgs)[WIDE_PD][WideCfg<S>::NGW], float* __restrict__ ring,
                                            const float* __restrict__ img, int wave, int lane) {
     using C = WideCfg<S>;
-#ifdef WIDE_DBG_NOSTREAM
-    return;                                            // timing experiment: ring never refilled (results wrong)
-#endif
     if constexpr (C::RESIDENT) return;
     constexpr int NCHE = FWD ? C::NCHF : C::NCH;       // the forward-only kernel cycles through the F segments only
     constexpr int cw = (c + 2) % NCHE, cl = (c + 2 + WIDE_PD) % NCHE;
@@ -272,11 +248,7 @@ __device__ __forceinline__ void wide_stage(int base, f32x4 (&stgs)[WIDE_PD][Wide
 #pragma unroll
     for (int j = 0; j < C::NGW; ++j)
         if (j < C::chunk_gran(cw) / WIDE_WAVES) {
-#ifdef WIDE_DBG_NOPARK
-            asm volatile("" :: "v"(stg[j]));           // timing experiment: loads stay alive, no LDS write (results wrong)
-#else
             *reinterpret_cast<f32x4*>(dst + j * WIDE_WAVES * 256) = stg[j];
-#endif
         }
     // rotate the sets (register renaming inside the unrolled block; plain moves only at the loop back-edge)
 #pragma unroll
@@ -287,24 +259,17 @@ __device__ __forceinline__ void wide_stage(int base, f32x4 (&stgs)[WIDE_PD][Wide
 #pragma unroll
     for (int j = 0; j < C::NGW; ++j)
         if (j < C::chunk_gran(cl) / WIDE_WAVES) {
-#ifdef WIDE_DBG_NOLOAD
-            asm volatile("" : "+v"(stgs[WIDE_PD - 1][j]));   // timing experiment: no global load (results wrong)
-#else
             stgs[WIDE_PD - 1][j] = *reinterpret_cast<const f32x4*>(src + j * WIDE_WAVES * C::gran_step(cl));
-#endif
         }
 }
 
-// ---- hand-scheduled chunk (WIDE_HANDSCHED, default): the compiler issues the 13 A-operand reads of the next chunk in one
+// ---- hand-scheduled chunk: the compiler issues the 13 A-operand reads of the next chunk in one
 // burst in front of the chunk barrier and drains them there (s_waitcnt lgkmcnt(0) precedes every s_barrier): ~300 of a
 // chunk's ~2,150 cycles at configs[3].  Here the MFMAs of a chunk run in tile GROUPS of two (k-step-major inside a group: an
 // accumulator is revisited every second MFMA, 64 cycles > the 40-cycle dependent latency), so a group's operand registers are
 // dead after 8 MFMAs and take the SAME tiles of chunk c+1 right then -- that slot was parked two barriers ago and is visible
 // to every wave.  Only the last group's operands have no MFMAs behind them in this chunk: they are requested at the top of
 // the next one, where they are needed last.  Scheduling fences (nothing crosses sched_barrier(0)) pin the order.
-#ifndef WIDE_HANDSCHED
-#define WIDE_HANDSCHED 1
-#endif
 #define WIDE_FENCE() __builtin_amdgcn_sched_barrier(0)
 template <class S>
 struct WideSched {
@@ -315,16 +280,13 @@ struct WideSched {
     static constexpr int deferred_from(int nt) { return gstart(nt, ngroups(nt) - 1); }   // first tile of the last group
 };
 // address of tile t of chunk cc in ring position rc (compile-time cc; RESIDENT: the image itself)
-// WIDE_DIRECT (default; streamed shapes only): the A operands do not go through LDS at all.  The image k_update maintains is
+// Direct mode (streamed shapes): the A operands do not go through LDS at all.  The image k_update maintains is
 // already in MFMA A-operand order -- granule t of a chunk is [lane][4], exactly the 16 bytes lane needs for tile t -- so every
 // wave loads its operands straight from L2 (the 4 waves of a workgroup walk the same chunks: the later ones hit the CU's L1)
 // into the registers the hand-scheduled chunk frees, ONE CHUNK (~1,700 cycles) ahead of their use.  No ring, no parking writes,
-// no chunk barrier, no staging registers; the waves of a workgroup no longer wait for each other.  WIDE_DIRECT=0: the 4-slot
-// LDS ring of rounds 1-2.
-#ifndef WIDE_DIRECT
-#define WIDE_DIRECT 1
-#endif
-template <class S> struct WideDirect { static constexpr bool value = WIDE_DIRECT && WIDE_HANDSCHED && !WideCfg<S>::RESIDENT; };
+// no chunk barrier, no staging registers; the waves of a workgroup no longer wait for each other (rounds 1-2 went through a
+// 4-slot LDS ring).
+template <class S> struct WideDirect { static constexpr bool value = !WideCfg<S>::RESIDENT; };
 template <class S, bool FWD>
 __device__ __forceinline__ const float* wide_tile_ptr(int base, int c, int cc_gran_off, const float* __restrict__ ring, int lane, int t) {
     using C = WideCfg<S>;
@@ -335,15 +297,12 @@ __device__ __forceinline__ const float* wide_tile_ptr(int base, int c, int cc_gr
 // tile so that the loads are not hoisted out of the row loop), the lane's 16 bytes the only VGPR -- no address arithmetic on
 // the VALU (global_load with 64-bit pointers cost two VALU adds per load: +280 instructions per 16-row tile).
 struct WideImg { __amdgpu_buffer_rsrc_t rs; int opq; };
-// ---- stored blocks, transposed layout (WIDE_TBLOCK, default).  A 1-KB block holds [16 rows][16 slots] of a_l or delta_l.
+// ---- stored blocks, transposed layout.  A 1-KB block holds [16 rows][16 slots] of a_l or delta_l.
 // k_dw_wide contracts over the ROWS: its MFMA operand for lane (i, g) and k-step s is (row 4s+g, slot i).  Round 1-2 stored a
 // block row-major (one 16-B store per lane of the D layout) and k_dw_wide re-read it lane-linearly through an LDS ring.  Here
 // element (row, slot) sits at slot*16 + (row % 4)*4 + row / 4: a lane's four k-steps are 16 contiguous bytes, so k_dw_wide
 // loads its operands straight from L2 into registers with ONE 16-B buffer load per block (no LDS ring, no parking, no barrier),
 // and the chain kernel pays four 4-B stores per block instead of one 16-B store.
-#ifndef WIDE_TBLOCK
-#define WIDE_TBLOCK 1
-#endif
 #define WIDE_RSRC_FLAGS 0x00020000
 // byte offset of this lane's component j in a block: writer lane (r = i16, g) holds (row r, slot 4g+j)
 __device__ __forceinline__ int tblk_wr_off(int i16, int g) { return ((4 * g) * 16 + (i16 & 3) * 4 + (i16 >> 2)) * 4; }   // + j * 64
@@ -410,18 +369,6 @@ __device__ __forceinline__ void wide_chunk(int base, f32x4 (&Anx)[WideCfg<S>::MA
     if constexpr (!DIRECT) WIDE_CHUNK_BARRIER();
 }
 
-// A operands of chunk c (already visible in its ring slot: parked two chunks earlier, one barrier ago)
-template <class S, int c, bool FWD = false>
-__device__ __forceinline__ void wide_load_A(int base, f32x4 (&A)[WideCfg<S>::MAXT], const float* __restrict__ ring, int lane) {
-    using C = WideCfg<S>;
-    // RESIDENT: `ring` is the LDS base and the chunk sits at its image offset
-    constexpr int cc = c % (FWD ? C::NCHF : C::NCH);
-    const float* sl = (C::RESIDENT ? ring + C::gran_off(cc, 0) : ring + ((base + c) & (WIDE_RING - 1)) * C::SLOT_FLOATS) + lane * 4;
-#pragma unroll
-    for (int t = 0; t < C::MAXT; ++t)
-        if (t < C::chunk_tiles(cc)) A[t] = *reinterpret_cast<const f32x4*>(sl + t * 256);
-}
-
 // FWD: forward pass only (network.predict, network.py:141-171): no likelihood, no delta chain, no stores;
 // fout[d_out][n] receives the network output.  Y, eta, store, slabA, pstat are unused (null).
 template <class S, bool FWD = false>
@@ -468,7 +415,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     for (int e = lane; e < C::XIMG_FLOATS; e += 64) ximg[e] = 0.f;
     __syncthreads();
     if (g == 0) ximg[i16 * C::PX + d_in] = 1.f;               // ones column of the x image (db_0)
-#if WIDE_HANDSCHED
     // operands of chunk 0 that the steady state requests behind the MFMAs of the chunk before it (wide_chunk)
     f32x4 Anx[C::MAXT];
     {
@@ -480,7 +426,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
                 Anx[t] = DIRECT ? wide_tile_direct<S>(WideImg{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qimg), 0, C::IMG_FLOATS * 4, 0x00020000), 0}, 0, lane, t) : *reinterpret_cast<const f32x4*>(wide_tile_ptr<S, FWD>(0, 0, C::gran_off(0, 0), ring, lane, t));
         }
     }
-#endif
 
     const float sigma = FWD ? 1.f : lik_sigma(nd, eta);
     const float inv_var = 1.f / (sigma * sigma);
@@ -532,11 +477,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         const WideImg im = {__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qimg), 0, C::IMG_FLOATS * 4, 0x00020000), opaque0};
         const long tile = blk * WIDE_WAVES + wave;
         const bool tvalid = tile < ntiles;
-#ifdef WIDE_DBG_STORE0
-        const long stile = tile & 1023;                // timing experiment: a_l / delta_l blocks stay in L2 (results wrong)
-#else
         const long stile = tile;
-#endif
         const bool rvalid = tile * 16 + i16 < n;
         WideRegs<S> T;
         float y[YN];
@@ -588,16 +529,10 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
                     if (t == os / 16 && g == (os % 16) / 4) v[t][os % 4] = 1.f;
                 }
                 if (!FWD && tvalid) {
-#if WIDE_TBLOCK
                     const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(store + C::act_off(l, ntiles) + ((size_t)stile * C::TA(l)) * 256, 0,
                                                                                          C::TA(l) * 1024, WIDE_RSRC_FLAGS);
 #pragma unroll
                     for (int t = 0; t < C::TA(l); ++t) tblk_store(rsw, tblk_wr_off(i16, g), t, v[t]);
-#else
-                    float* p = store + C::act_off(l, ntiles) + ((size_t)stile * C::TA(l)) * 256 + i16 * 16 + g * 4;
-#pragma unroll
-                    for (int t = 0; t < C::TA(l); ++t) *reinterpret_cast<f32x4*>(p + t * 256) = v[t];
-#endif
                 }
             }
             constexpr int MT = C::TR(l + 1);
@@ -606,21 +541,8 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             for (int t = 0; t < MT; ++t) acc[t] = *reinterpret_cast<const f32x4*>(lds + C::boff(l) + 16 * t + 4 * g);
             sfor<0, C::KG(C::in(l))>(SFOR_LAMBDA(kg) {
                 constexpr int kg = SFOR_VAL(kg), c = C::cF(l) + kg;
-#if WIDE_HANDSCHED
                 wide_chunk<S, c, FWD>(base, Anx, acc, T.a[kg], stg, ring, img, im, wave, lane);
                 WSTAMP(9 + 2 * c);
-#else
-                wide_stage<S, c, FWD>(base, stg, ring, img, wave, lane);
-                f32x4 Acur[C::MAXT];
-                wide_load_A<S, c, FWD>(base, Acur, ring, lane);
-#pragma unroll
-                for (int s = 0; s < C::ksteps(C::in(l), kg); ++s)
-#pragma unroll
-                    for (int t = 0; t < MT; ++t) acc[t] = mfma16(Acur[t][s], T.a[kg][s], acc[t]);
-                WSTAMP(8 + 2 * c);
-                WIDE_CHUNK_BARRIER();
-                WSTAMP(9 + 2 * c);
-#endif
             });
 #pragma unroll
             for (int t = 0; t < MT; ++t)
@@ -696,18 +618,11 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         sfor<0, NM>(SFOR_LAMBDA(li) {
             constexpr int l = NM - SFOR_VAL(li);
             if (tvalid) {       // delta_l -> HBM
-#if WIDE_TBLOCK
                 const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(store + C::dz_off(l, ntiles) + ((size_t)stile * C::TZ(l)) * 256, 0,
                                                                                      C::TZ(l) * 1024, WIDE_RSRC_FLAGS);
 #pragma unroll
                 for (int t = 0; t < C::MAXT; ++t)
                     if (t < C::TZ(l)) tblk_store(rsw, tblk_wr_off(i16, g), t, dz[t]);
-#else
-                float* p = store + C::dz_off(l, ntiles) + ((size_t)stile * C::TZ(l)) * 256 + i16 * 16 + g * 4;
-#pragma unroll
-                for (int t = 0; t < C::MAXT; ++t)
-                    if (t < C::TZ(l)) *reinterpret_cast<f32x4*>(p + t * 256) = dz[t];
-#endif
             }
             constexpr int MU = C::TR(l);
             // a_l (for act') comes back from the block this lane stored in the forward pass: nothing but the
@@ -722,32 +637,13 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             sfor<0, C::KG(C::out(l))>(SFOR_LAMBDA(kg) {
                 constexpr int kg = SFOR_VAL(kg), c = C::cB(l) + kg;
                 if constexpr (!RELU && kg == KG_RELOAD) {
-#if WIDE_TBLOCK
                     const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(store + C::act_off(l, ntiles) + ((size_t)(tvalid ? stile : 0) * C::TA(l)) * 256,
                                                                                          0, C::TA(l) * 1024, WIDE_RSRC_FLAGS);
 #pragma unroll
                     for (int u = 0; u < MU; ++u) arel[u] = tvalid ? tblk_load_d(rsr, tblk_wr_off(i16, g), u) : f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-                    const float* p = store + C::act_off(l, ntiles) + ((size_t)(tvalid ? stile : 0) * C::TA(l)) * 256 + i16 * 16 + g * 4;
-#pragma unroll
-                    for (int u = 0; u < MU; ++u) arel[u] = tvalid ? *reinterpret_cast<const f32x4*>(p + u * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
                 }
-#if WIDE_HANDSCHED
                 wide_chunk<S, c, false>(base, Anx, acc, dz[kg], stg, ring, img, im, wave, lane);
                 WSTAMP(9 + 2 * c);
-#else
-                wide_stage<S, c>(base, stg, ring, img, wave, lane);
-                f32x4 Acur[C::MAXT];
-                wide_load_A<S, c>(base, Acur, ring, lane);
-#pragma unroll
-                for (int s = 0; s < C::ksteps(C::out(l), kg); ++s)
-#pragma unroll
-                    for (int u = 0; u < MU; ++u) acc[u] = mfma16(Acur[u][s], dz[kg][s], acc[u]);
-                WSTAMP(8 + 2 * c);
-                WIDE_CHUNK_BARRIER();
-                WSTAMP(9 + 2 * c);
-#endif
             });
 #pragma unroll
             for (int u = 0; u < MU; ++u)
@@ -776,17 +672,14 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
                 for (int t = b0; t < b0 + C::DZB && t < C::MT0; ++t)
 #pragma unroll
                     for (int s = 0; s < 4; ++s) Aop[t - b0][s] = scr[(4 * g + s) * C::PZ + 16 * (t - b0) + i16];
+                // dW_0 accumulators pinned to AccVGPRs (kernels_fast.hpp, mfma16_acc) next to VGPR-form chain MFMAs (build.py): -1.5 % at configs[4]
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
                     for (int t = b0; t < b0 + C::DZB && t < C::MT0; ++t)
 #pragma unroll
                         for (int nt = 0; nt < C::NT0; ++nt)
-#if WIDE_DW0_AGPR
                             mfma16_acc<C::DW0_FAR>(dW0[t * C::NT0 + nt], Aop[t - b0][s], Bop[nt][s]);
-#else
-                            dW0[t * C::NT0 + nt] = mfma16(Aop[t - b0][s], Bop[nt][s], dW0[t * C::NT0 + nt]);
-#endif
             }
         }
         WSTAMP(5);
@@ -794,9 +687,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     }
 
     if constexpr (FWD) return;
-#if WIDE_DW0_AGPR
     mfma_drain_acc(dW0);
-#endif
     // ---- epilogue: compact slab [layer 0][last layer] of this workgroup
     const double wtot = wave_sum_lane0(stat);
     if (lane == 0) red[wave] = wtot;
@@ -876,7 +767,6 @@ struct WideDwArgs {
     int wg_lo[TBNN_MAX_LAYERS + 1];      // first workgroup of middle layer l (index l-1); [NM] = total
 };
 
-#if WIDE_TBLOCK
 // k_dw_wide on transposed blocks: every operand one 16-B buffer load straight into registers.  Loop order inside a row tile:
 // N-tile-major -- for a-block u the QM x 4 MFMAs of this wave's M tiles (an accumulator is revisited every QM-th MFMA), after
 // which B[u]'s registers are dead and take block u of the NEXT row tile (a whole row tile, ~170 MFMAs, ahead of its use); the
@@ -1067,117 +957,13 @@ __device__ __forceinline__ void dw_wide_layer(const float* __restrict__ store, l
     for (int q = 0; q < QP; ++q)
         if (pv[q]) put(pm[q], pu[q], acc[QM * TAl + q]);
 }
-#else
-template <class S, int l>
-__device__ __forceinline__ void dw_wide_layer(const float* __restrict__ store, long ntiles, long rt0, long rt1,
-                                              float* __restrict__ slab, float* lds, int wave, int lane) {
-    using C = WideCfg<S>;
-    constexpr int TAl = C::TA(l), TZl = C::TZ(l), QM = C::QM(l), RM = C::RM(l), QP = C::QP(l), SB = C::SB(l);
-    constexpr int NT = QM * TAl + QP;
-    constexpr int NG = C::cdiv(SB, WIDE_WAVES);
-    const float* abase = store + C::act_off(l, ntiles);
-    const float* zbase = store + C::dz_off(l, ntiles);
-    f32x4 acc[NT > 0 ? NT : 1];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = acc_zero();
-    // left-over pairs of this wave: p = wave + 4q -> (m = 4 QM + p / TA, u = p % TA); invalid ones recompute pair 0
-    int pm[QP > 0 ? QP : 1], pu[QP > 0 ? QP : 1];
-    bool pv[QP > 0 ? QP : 1];
-#pragma unroll
-    for (int q = 0; q < QP; ++q) {
-        const int p = wave + 4 * q;
-        pv[q] = p < RM * TAl;
-        const int pp = pv[q] ? p : 0;
-        pm[q] = 4 * QM + pp / TAl; pu[q] = pp % TAl;
-    }
-    // slot layout: [a blocks 0..TA-1][delta blocks 0..TZ-1], 256 floats each
-    f32x4 stg[WIDE_DW_PD][NG];
-    auto gload = [&](long rt, f32x4 (&dst)[NG]) {
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            const int b = wave + 4 * j;
-            if (b < SB && rt < rt1) {
-                const float* src = b < TAl ? abase + ((size_t)rt * TAl + b) * 256 : zbase + ((size_t)rt * TZl + (b - TAl)) * 256;
-                dst[j] = *reinterpret_cast<const f32x4*>(src + lane * 4);
-            } else dst[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto park = [&](int slot, const f32x4 (&src)[NG]) {
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            const int b = wave + 4 * j;
-            if (b < SB) *reinterpret_cast<f32x4*>(lds + slot * C::DW_SLOT_FLOATS + b * 256 + lane * 4) = src[j];
-        }
-    };
-    // prime: row tiles rt0, rt0+1 parked; rt0+2 .. rt0+1+PD in registers
-    gload(rt0, stg[0]); park(0, stg[0]);
-    gload(rt0 + 1, stg[0]); park(1, stg[0]);
-#pragma unroll
-    for (int k = 0; k < WIDE_DW_PD; ++k) gload(rt0 + 2 + k, stg[k]);
-    __syncthreads();
-    int it = 0;
-    for (long rt = rt0; rt < rt1; ++rt, ++it) {
-        park((it + 2) & (WIDE_RING - 1), stg[0]);
-#pragma unroll
-        for (int k = 0; k + 1 < WIDE_DW_PD; ++k)
-#pragma unroll
-            for (int j = 0; j < NG; ++j) stg[k][j] = stg[k + 1][j];
-        gload(rt + 2 + WIDE_DW_PD, stg[WIDE_DW_PD - 1]);
-        const float* sl = lds + (it & (WIDE_RING - 1)) * C::DW_SLOT_FLOATS + lane;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            float B[TAl], A[QM > 0 ? QM : 1];
-#pragma unroll
-            for (int u = 0; u < TAl; ++u) B[u] = sl[u * 256 + 64 * s];
-#pragma unroll
-            for (int j = 0; j < QM; ++j) A[j] = sl[(TAl + wave + 4 * j) * 256 + 64 * s];
-#pragma unroll
-            for (int j = 0; j < QM; ++j)
-#pragma unroll
-                for (int u = 0; u < TAl; ++u) acc[j * TAl + u] = mfma16(A[j], B[u], acc[j * TAl + u]);
-#pragma unroll
-            for (int q = 0; q < QP; ++q) {
-                const float a = sl[(TAl + pm[q]) * 256 + 64 * s], b = sl[pu[q] * 256 + 64 * s];
-                acc[QM * TAl + q] = mfma16(a, b, acc[QM * TAl + q]);
-            }
-        }
-        __syncthreads();
-    }
-    // write-out in theta order: D layout lane (n = lane & 15, g) reg j = dW[out 16m+4g+j][in 16u+n]
-    const int nn = lane & 15, gg = lane >> 4;
-    constexpr int inl = C::in(l), outl = C::out(l);
-    auto put = [&](int m, int u, const f32x4& v) {
-        const int col = unit_of(inl, 16 * u + nn, true);          // inl: the ones pseudo-unit (bias column)
-        if (col >= 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = unit_of(outl, 16 * m + 4 * gg + j, false);
-                if (row >= 0) slab[col < inl ? row * inl + col : inl * outl + row] = v[j];
-            }
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < QM; ++j)
-#pragma unroll
-        for (int u = 0; u < TAl; ++u) put(wave + 4 * j, u, acc[j * TAl + u]);
-#pragma unroll
-    for (int q = 0; q < QP; ++q)
-        if (pv[q]) put(pm[q], pu[q], acc[QM * TAl + q]);
-}
-
-#endif  // WIDE_TBLOCK
 
 template <class S>
 __global__ __launch_bounds__(WIDE_THREADS, WideCfg<S>::DW_OCC) void k_dw_wide(
     WideDwArgs args, const float* __restrict__ store, long n, float* __restrict__ slabB)
 {
     using C = WideCfg<S>;
-#if WIDE_TBLOCK
     float* lds = nullptr;                                // operands come straight from L2 (dw_wide_layer)
-#else
-    static_assert(WIDE_RING * C::DW_SLOT_FLOATS * 4 <= 160 * 1024, "LDS budget");
-    __shared__ __attribute__((aligned(16))) float lds[WIDE_RING * C::DW_SLOT_FLOATS];
-#endif
     // wave index as a SCALAR (the compiler does not know threadIdx.x >> 6 is wave-uniform: every `b = wave + 4j < SB` below
     // would become an exec-mask branch with zero-filled else arms, and the block addresses vector arithmetic)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev: A/B of a run-time compiled kernel variant on the GPU box: alternating bench.py runs with and without TBNN_JIT_FLAGS="$1"
 # (the variant libraries are compiled HERE first: TBNN_JIT_FLAGS=... python3 tools/experiments/jit_build.py 8,50,50,1)
-#   bash tools/experiments/jitab.sh "-DTBNN_F3_DENSE=0" c2 200
+#   bash tools/experiments/jitab.sh "-DTBNN_F3_M4ACC=1" c2 200
 FLAGS="$1"; W=${2:-c2}; STEPS=${3:-200}
 for rep in 1 2 3; do
   for v in base var; do
