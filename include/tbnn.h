@@ -43,8 +43,9 @@ enum { TBNN_ACT_NONE = 0, TBNN_ACT_RELU = 1, TBNN_ACT_TANH = 2, TBNN_ACT_SIGMOID
 /* prior family of a dense layer: CauchyDenseLayer (= DenseLayer) layer.py:101,
  * GaussianDenseLayer layer.py:282 */
 enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
-/* likelihood.py:63 (Gaussian), :136 (FixedGaussian), :205 (Bernoulli) */
-enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2 };
+/* likelihood.py:63 (Gaussian), :136 (FixedGaussian), :205 (Bernoulli); CATEGORICAL: a softmax over each row's d_out >= 2 outputs
+ * (logits: the last layer carries no activation), Y one-hot or probability rows: sum_rows sum_k y_k log softmax_k(f) */
+enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or

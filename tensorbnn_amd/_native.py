@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("TBNN_LIB") or os.path.join(_HERE, "libtbnn.so")
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
-LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
+LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL = 0, 1, 2, 3
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
 MAX_LAYERS = 16
 ABI_VERSION = 3          # TBNN_ABI_VERSION of include/tbnn.h

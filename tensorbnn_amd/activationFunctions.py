@@ -89,7 +89,8 @@ class Elu(_Activation):
 
 class Softmax(_Unsupported):
     _name = "softmax"
-    _why = "the reference's softmax runs over the data rows (last axis of [units, rows], activationFunctions.py:88)"
+    _why = ("the reference's softmax runs over the data rows (last axis of [units, rows], activationFunctions.py:88); "
+            "for a multi-class model leave the last layer without an activation and train with likelihood.CategoricalLikelihood()")
 
 
 class Leaky_relu(_Unsupported):

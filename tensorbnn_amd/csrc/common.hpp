@@ -8,6 +8,13 @@
 // (kernels_fast.hpp: Shape::act; fused_ops.hpp)
 #define TBNN_ACT_PACKED 0x40000000
 
+// the likelihood a fused kernel was instantiated for (kernels_fast.hpp: Shape::LIK; fused_ops.hpp: FusedOps::lik)
+enum { SHAPE_LIK_GAUSS = 0, SHAPE_LIK_BERN = 1, SHAPE_LIK_CAT = 2 };
+// ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
+__host__ __device__ constexpr int shape_lik(int lik) {
+    return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : SHAPE_LIK_GAUSS;
+}
+
 #define TBNN_WAVE 64
 #define PSTAT_CAP 512                     // entries of the per-workgroup statistic buffer (tbnn_api.hip): >= the grid of every fused pass
 
@@ -153,6 +160,26 @@ __device__ __forceinline__ double wave_sum_lane0(double v) {
     v = dpp_shl_add<0x102>(v);
     v = dpp_shl_add<0x101>(v);
     return v;
+}
+// max / sum over the four lane groups of a wave (lanes i16, i16 + 16, i16 + 32, i16 + 48: one data row of an MFMA D-layout tile), the result
+// in all four, bit for bit the same value: v_permlane32_swap pairs lane i with lane i ^ 32, then v_permlane16_swap lane i with i ^ 16.
+// Every lane of the wave must execute it (no divergent branch around the call).  The compiler's hazard recognizer keeps the two wait
+// states between a VALU write of an operand and the swap reading it (builtins, not inline asm).
+__device__ __forceinline__ float lanegroup_max(float v) {
+    const unsigned u = __float_as_uint(v);
+    const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);      // [0]: lane i <- lane i & 31, [1]: lane i <- 32 + (i & 31)
+    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+    const unsigned w = __float_as_uint(v);
+    const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);      // [0]: even row of the pair, [1]: odd row
+    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+__device__ __forceinline__ float lanegroup_sum(float v) {
+    const unsigned u = __float_as_uint(v);
+    const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+    const unsigned w = __float_as_uint(v);
+    const auto b = __builtin_amdgcn_permlane16_swap(w, w, false, false);
+    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 __device__ __forceinline__ float wave_sumf(float v) {
 #pragma unroll

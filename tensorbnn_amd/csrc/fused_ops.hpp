@@ -6,14 +6,14 @@
 #include "common.hpp"
 #include "wide_api.hpp"
 
-#define TBNN_JIT_ABI 6      // 5: ChainStride carries the per-chain step control; 6: the trajectory kernel of small problems (kernels_traj.hpp)
+#define TBNN_JIT_ABI 7      // 5: ChainStride carries the per-chain step control; 6: the trajectory kernel of small problems (kernels_traj.hpp); 7: FusedOps::lik
 enum { TBNN_FAMILY_NARROW = 1, TBNN_FAMILY_WIDE = 2 };
 
 struct FusedOps {
     int abi;                                  // TBNN_JIT_ABI
     int family;                               // TBNN_FAMILY_*
     int nl, dims[TBNN_MAX_LAYERS + 1];        // the shape the kernels were instantiated for
-    int hact, lact, bern;
+    int hact, lact, lik;                      // lik: SHAPE_LIK_* (common.hpp: shape_lik)
     char name[128];
     int img_floats;                           // padded weight image (k_update scatters theta into it through image_map)
     void (*image_map)(int* map /* 2P */);
@@ -39,7 +39,7 @@ struct FusedOps {
 };
 
 static inline bool fused_ops_match(const FusedOps& o, const NetDev& nd) {
-    if (o.nl != nd.nl || (nd.lik == TBNN_LIK_BERNOULLI) != (o.bern != 0)) return false;
+    if (o.nl != nd.nl || o.lik != shape_lik(nd.lik)) return false;
     for (int l = 0; l < nd.nl; ++l) {
         if (nd.in[l] != o.dims[l] || nd.out[l] != o.dims[l + 1]) return false;
         if (nd.act[l] != (l == nd.nl - 1 ? o.lact : ((o.hact & TBNN_ACT_PACKED) ? (o.hact >> (3 * l)) & 7 : o.hact))) return false;
@@ -53,14 +53,14 @@ static inline void fused_ops_shape(FusedOps* o, const char* prefix, const char* 
     o->abi = TBNN_JIT_ABI;
     o->nl = S::NL;
     for (int i = 0; i <= S::NL; ++i) o->dims[i] = S::D[i];
-    o->hact = S::HCODE; o->lact = S::LACT; o->bern = S::BERN ? 1 : 0;      // (hact: one activation, or the packed per-layer code: Shape)
+    o->hact = S::HCODE; o->lact = S::LACT; o->lik = S::LIK;      // (hact: one activation, or the packed per-layer code: Shape)
     if (name) { snprintf(o->name, sizeof(o->name), "%s", name); return; }
     static const char* an[] = {"none", "relu", "tanh", "sigmoid", "exp", "elu", "?", "?"};
     int k = snprintf(o->name, sizeof(o->name), "%s<", prefix);
     if (S::HCODE & TBNN_ACT_PACKED) {
         for (int l = 0; l + 1 < S::NL && k < (int)sizeof(o->name) - 16; ++l) k += snprintf(o->name + k, sizeof(o->name) - k, l ? "+%s" : "%s", an[S::act(l) & 7]);
     } else k += snprintf(o->name + k, sizeof(o->name) - k, "%s", an[S::HCODE & 7]);
-    k += snprintf(o->name + k, sizeof(o->name) - k, ",%s%s;", an[S::LACT], S::BERN ? ",bernoulli" : "");
+    k += snprintf(o->name + k, sizeof(o->name) - k, ",%s%s;", an[S::LACT], S::BERN ? ",bernoulli" : S::CAT ? ",categorical" : "");
     for (int i = 0; i <= S::NL && k < (int)sizeof(o->name) - 8; ++i) k += snprintf(o->name + k, sizeof(o->name) - k, i ? ",%d" : "%d", S::D[i]);
     snprintf(o->name + k, sizeof(o->name) - k, ">");
 }

@@ -30,17 +30,19 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FAST_THREADS (FAST_WAVES * 64)
 
 // HACT: activation after every hidden layer, LACT: after the last layer,
-// BERN: Bernoulli likelihood (else the Gaussian family) -- all compile-time so
-// the tile body is one straight-line block the scheduler can interleave.
+// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical; `false` / `true` still spell the first two) -- all
+// compile-time so the tile body is one straight-line block the scheduler can interleave.
 // Round 6: network.add takes any sequence of layers and activations (tensorBNN/network.py:173-191) -- a stack whose hidden layers do NOT all
 // carry the same activation has HACT = TBNN_ACT_PACKED | sum_l act_l << 3 l (hidden layer l = 0 .. NL - 2; at most 9 of them: fused_ops.hpp,
 // jit.shape_of); the kernels ask act(l) per layer and never HACT itself.
-template <int HACT_, int LACT_, bool BERN_, int... Ds>
+template <int HACT_, int LACT_, int LIK_, int... Ds>
 struct Shape {
     static constexpr int NL = sizeof...(Ds) - 1;
     static constexpr int D[sizeof...(Ds)] = {Ds...};
-    static constexpr int HCODE = HACT_, LACT = LACT_;
-    static constexpr bool BERN = BERN_;
+    static constexpr int HCODE = HACT_, LACT = LACT_, LIK = LIK_;
+    static constexpr bool BERN = LIK_ == SHAPE_LIK_BERN, CAT = LIK_ == SHAPE_LIK_CAT;
+    static_assert(LIK_ >= SHAPE_LIK_GAUSS && LIK_ <= SHAPE_LIK_CAT, "unknown likelihood code");
+    static_assert(!CAT || (LACT_ == TBNN_ACT_NONE && D[NL] >= 2), "categorical: logits (no last activation), at least 2 outputs");
     static_assert((HACT_ & TBNN_ACT_PACKED) == 0 || NL - 1 <= 9, "a packed activation code holds 9 hidden layers");
     static constexpr int act(int l) { return l == NL - 1 ? LACT_ : ((HACT_ & TBNN_ACT_PACKED) ? (HACT_ >> (3 * l)) & 7 : HACT_); }
 };
@@ -580,6 +582,7 @@ struct LastRegs {
 // likelihood for one output value: statistic (counted when `count`), returns dL/df * act'
 template <class S>
 __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat) {
+    static_assert(!S::CAT, "the categorical likelihood couples a row's outputs: cat_delta4 on the MFMA output tile, no per-element path");
     float da;
     if constexpr (S::BERN) {
         const float p = fminf(fmaxf(fi, 1e-8f), 1.f - 1e-7f);
@@ -597,6 +600,58 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
         da = res * inv_var;
     }
     return da * actc_bwd<S::LACT>(fi);
+}
+
+// Categorical likelihood (TBNN_LIK_CATEGORICAL) of the 16 rows of NT output tiles in the MFMA D layout: lane (row i16, group g) holds the
+// logits f[t][j] of slots 16t + 4g + j of its row and their labels y[t][j]; bit 4t + j of `live` marks the slots that are outputs (padding
+// counts -inf in the max, 0 in the sums, whatever its f).  Returns in dz dL/df_k = y_k - softmax_k sum_j y_j (live slots of valid rows, else
+// 0) and adds sum_k y_k (f_k - m - log sum_j e^(f_j - m)), m = max_j f_j, to `stat` once per valid row (lane group 0).  The shift by m
+// keeps it finite for any finite logits; hardware exp2 / log2 / reciprocal, as the Bernoulli path.  The row's max and sums cross the four
+// lane groups by permlane swaps: every lane of the wave calls this, with nothing divergent around the call.
+template <int NT>
+__device__ __forceinline__ void cat_delta(const f32x4 (&f)[NT], const f32x4 (&y)[NT], unsigned live, bool rvalid, int g, double& stat,
+                                          f32x4 (&dz)[NT]) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m = (live >> (4 * t + j)) & 1 ? fmaxf(m, f[t][j]) : m;
+    m = lanegroup_max(m);
+    float s = 0.f, sy = 0.f, sd = 0.f;
+    f32x4 e[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool on = (live >> (4 * t + j)) & 1;
+            const float d = f[t][j] - m;
+            e[t][j] = on ? __expf(d) : 0.f;
+            s += e[t][j];
+            sy += on ? y[t][j] : 0.f;
+            sd += on ? y[t][j] * d : 0.f;
+        }
+    s = lanegroup_sum(s);
+    sy = lanegroup_sum(sy);
+    sd = lanegroup_sum(sd);
+    if (rvalid && g == 0) stat += (double)(sd - sy * __logf(s));
+    const float ps = sy * __builtin_amdgcn_rcpf(s);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dz[t][j] = (rvalid && ((live >> (4 * t + j)) & 1)) ? y[t][j] - e[t][j] * ps : 0.f;
+}
+// the fused families' output tile (d_out <= 16 units in the slots of unit_of): the lane's four logits and labels -> their four deltas
+template <class S>
+__device__ __forceinline__ f32x4 cat_delta4(const f32x4& f, const float (&y)[4], bool rvalid, int g, double& stat) {
+    static_assert(S::CAT && S::D[S::NL] <= 16, "one output tile");
+    constexpr int d_out = S::D[S::NL];
+    unsigned live = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) live |= unit_of(d_out, 4 * g + r, false) >= 0 ? 1u << r : 0u;
+    const f32x4 fv[1] = {f}, yv[1] = {f32x4{y[0], y[1], y[2], y[3]}};
+    f32x4 dz[1];
+    cat_delta<1>(fv, yv, live, rvalid, g, stat, dz);
+    return dz[0];
 }
 
 // one step of the row loop: one 16-row tile through forward, likelihood, backward.

@@ -13,7 +13,8 @@
 //
 // Math restated from the reference: dense W@a+b layer.py:278, activations
 // activationFunctions.py:36/49/62, Gaussian residual likelihood.py:88-94 +
-// BNN_functions.py:23-32, Bernoulli likelihood.py:226-236; reverse mode per
+// BNN_functions.py:23-32, Bernoulli likelihood.py:226-236, categorical (softmax over a row's outputs:
+// include/tbnn.h TBNN_LIK_CATEGORICAL); reverse mode per
 // SURVEY.md A12 (TF autodiff has no source in the tree).
 #pragma once
 #include "common.hpp"
@@ -73,7 +74,24 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
         }
 
         // ---- likelihood: statistic + dL/df
-        {
+        if (nd.lik == TBNN_LIK_CATEGORICAL) {
+            // log softmax of the row's logits, shifted by their max (finite for any finite f): stat += sum_k y_k (f_k - m - log sum_j e^(f_j - m)),
+            // dL/df_k = y_k - softmax_k sum_j y_j
+            const float* f = ACT + (size_t)nd.actOff[nd.nl - 1] * GEN_RB;
+            float m = -INFINITY;
+            for (int i = 0; i < nd.d_out; ++i) m = fmaxf(m, f[i * GEN_RB + tid]);
+            float s = 0.f, sy = 0.f, t = 0.f;
+            for (int i = 0; i < nd.d_out; ++i) {
+                const float d = f[i * GEN_RB + tid] - m, y = valid ? Y[R * nd.d_out + i] : 0.f;
+                s += expf(d);
+                sy += y;
+                t = fmaf(y, d, t);
+            }
+            if (valid) stat += (double)(t - sy * logf(s));
+            const float ps = sy / s;
+            for (int i = 0; i < nd.d_out; ++i)
+                DA0[i * GEN_RB + tid] = valid ? Y[R * nd.d_out + i] - expf(f[i * GEN_RB + tid] - m) * ps : 0.f;
+        } else {
             const float* f = ACT + (size_t)nd.actOff[nd.nl - 1] * GEN_RB;
             for (int i = 0; i < nd.d_out; ++i) {
                 const float fi = f[i * GEN_RB + tid];

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_make_image(int P, const float* __restri
 
 // data-term log-likelihood from the reduced statistic
 __device__ __forceinline__ double data_logp(const NetDev& nd, const float* __restrict__ eta, double stat, long n) {
-    if (nd.lik == TBNN_LIK_BERNOULLI) return stat;
+    if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
     // multivariateLogProb with sigma broadcast to [n, d_out] (likelihood.py:92, BNN_functions.py:25-32)
     const double s = (double)lik_sigma(nd, eta);
     const double nel = (double)n * (double)nd.d_out;

@@ -356,7 +356,7 @@ __device__ __forceinline__ float lay_bernoulli(float fi, float y, double& stat) 
     return inside ? (y * __builtin_amdgcn_rcpf(p) - (1.f - y) * __builtin_amdgcn_rcpf(q)) : 0.f;
 }
 
-// likelihood (restated as in kernels_generic.hpp): statistic (Gaussian: sum of squared residuals; Bernoulli: log-prob) and
+// likelihood (restated as in kernels_generic.hpp): statistic (Gaussian: sum of squared residuals; Bernoulli, categorical: log-prob) and
 // dz of the last layer = dL/df * act'(f).  f, dz: blocks [row tile][TMl][16][16]; one thread per data row.  Only the real
 // (row, output) entries of dz are written: the padding was zeroed when the store was allocated and nothing else writes it.
 __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restrict__ eta, const float* __restrict__ f, const float* __restrict__ Y,
@@ -366,6 +366,32 @@ __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restr
     const float inv_var = 1.f / (sigma * sigma);
     const int lact = nd.act[nd.nl - 1];
     double stat = 0.0;
+    if (nd.lik == TBNN_LIK_CATEGORICAL) {
+        // one thread per data ROW (a row's outputs share the softmax), any number of outputs: max, then the sums, then dz
+        // (cat_delta's math, kernels_fast.hpp, in one thread)
+        for (long row = (long)blockIdx.x * 256 + threadIdx.x; row < n; row += (long)gridDim.x * 256) {
+            const size_t rb = (size_t)(row >> 4) * TMl * 256 + (row & 15) * 16;
+            const float* yr = Y + row * nd.d_out;
+            float m = -INFINITY;
+            for (int o = 0; o < nd.d_out; ++o) m = fmaxf(m, f[rb + (size_t)(o >> 4) * 256 + (o & 15)]);
+            float sm = 0.f, sy = 0.f, sd = 0.f;
+            for (int o = 0; o < nd.d_out; ++o) {
+                const float d = f[rb + (size_t)(o >> 4) * 256 + (o & 15)] - m, y = yr[o];
+                sm += __expf(d);
+                sy += y;
+                sd += y * d;
+            }
+            stat += (double)(sd - sy * __logf(sm));
+            const float ps = sy * __builtin_amdgcn_rcpf(sm);
+            for (int o = 0; o < nd.d_out; ++o) {
+                const size_t e = rb + (size_t)(o >> 4) * 256 + (o & 15);
+                dz[e] = yr[o] - __expf(f[e] - m) * ps;
+            }
+        }
+        const double tot = block_sum(stat, red);
+        if (threadIdx.x == 0) pstat[blockIdx.x] = tot;
+        return;
+    }
     // one thread per (row, output) element: with many outputs a thread per ROW ran the library logarithms of all of them one after the
     // other (784 -> 100 -> 100 -> 10 at n = 12 k: 9.6 us for 120 k elements)
     const long nel = n * nd.d_out;
@@ -554,7 +580,21 @@ __global__ __launch_bounds__(256) void k_lay_tail(NetDev nd, LayPlan p, const fl
         }
         // ---- likelihood: a = f (lane (row i16, g) holds outputs 16 t + 4 g + j)
         f32x4 dz[TT];
-        {
+        if (nd.lik == TBNN_LIK_CATEGORICAL) {
+            // the row's softmax over its outputs in the TT tiles, across the four lane groups
+            const long row = rt * 16 + i16;
+            f32x4 y[TT];
+            unsigned live = 0;
+#pragma unroll
+            for (int t = 0; t < TT; ++t)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o = 16 * t + 4 * g + j;
+                    live |= o < nd.d_out ? 1u << (4 * t + j) : 0u;
+                    y[t][j] = (row < n && o < nd.d_out) ? Y[row * nd.d_out + o] : 0.f;
+                }
+            cat_delta<TT>(a, y, live, row < n, g, stat, dz);
+        } else {
             const long row = rt * 16 + i16;
 #pragma unroll
             for (int t = 0; t < TT; ++t)
@@ -667,24 +707,40 @@ __global__ __launch_bounds__(256) void k_lay_last(NetDev nd, LayPlan p, const fl
             }
         f32x4 f, dz;
         const long row = rt * 16 + i16;
+        if (nd.lik == TBNN_LIK_CATEGORICAL) {
+            // the row's softmax over its <= 16 outputs, across the four lane groups (lact is NONE: tbnn_create)
+            f32x4 fv[1], yv[1], dv[1];
+            unsigned live = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int o = 4 * g + j;
-            f[j] = o < nd.d_out ? act_fwd(acc0[j] + acc1[j], lact) : 0.f;
-            float d = 0.f;
-            if (row < n && o < nd.d_out) {
-                const float fi = f[j], y = Y[row * nd.d_out + o];
-                float da;
-                if (nd.lik == TBNN_LIK_BERNOULLI) {
-                    da = lay_bernoulli(fi, y, stat);
-                } else {
-                    const float res = y - fi;                                  // likelihood.py:88-94
-                    stat += (double)res * (double)res;
-                    da = res * inv_var;
-                }
-                d = da * act_bwd(fi, lact);
+            for (int j = 0; j < 4; ++j) {
+                const int o = 4 * g + j;
+                f[j] = o < nd.d_out ? acc0[j] + acc1[j] : 0.f;
+                live |= o < nd.d_out ? 1u << j : 0u;
+                yv[0][j] = (row < n && o < nd.d_out) ? Y[row * nd.d_out + o] : 0.f;
             }
-            dz[j] = d;
+            fv[0] = f;
+            cat_delta<1>(fv, yv, live, row < n, g, stat, dv);
+            dz = dv[0];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int o = 4 * g + j;
+                f[j] = o < nd.d_out ? act_fwd(acc0[j] + acc1[j], lact) : 0.f;
+                float d = 0.f;
+                if (row < n && o < nd.d_out) {
+                    const float fi = f[j], y = Y[row * nd.d_out + o];
+                    float da;
+                    if (nd.lik == TBNN_LIK_BERNOULLI) {
+                        da = lay_bernoulli(fi, y, stat);
+                    } else {
+                        const float res = y - fi;                                  // likelihood.py:88-94
+                        stat += (double)res * (double)res;
+                        da = res * inv_var;
+                    }
+                    d = da * act_bwd(fi, lact);
+                }
+                dz[j] = d;
+            }
         }
         lay_block_store(store + p.aOff[L + 1] + (size_t)rt * 256 + lane_off, f);
         lay_block_store(store + p.dOff[L] + (size_t)rt * 256 + lane_off, dz);

@@ -467,10 +467,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
         f32x4 dz[C::MAXT];
         if constexpr (!C::VL) {
             // likelihood on the output tile: delta_LL (w.r.t. the pre-activation) in the D layout, every (row, output) element once
+            if constexpr (S::CAT) {
+                dz[0] = cat_delta4<S>(a[0], y, rvalid, g, stat);          // the row's softmax across the four lane groups
+            } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int u = unit_of(d_out, 4 * g + r, false);
-                dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(a[0][r], y[r], inv_var, true, stat) : 0.f;
+                for (int r = 0; r < 4; ++r) {
+                    const int u = unit_of(d_out, 4 * g + r, false);
+                    dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(a[0][r], y[r], inv_var, true, stat) : 0.f;
+                }
             }
         } else {
             // the last layer's dW / db sums of this tile's rows; delta_{LL-1} = (W_LL^T dz_LL) * act'(a_LL)

@@ -566,10 +566,14 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
                 base = (base + C::NCHF) & (WIDE_RING - 1);
                 continue;
             } else {
+                if constexpr (S::CAT) {
+                    dz[0] = cat_delta4<S>(T.a[0], y, rvalid, g, stat);          // the row's softmax across the four lane groups
+                } else {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int u = unit_of(d_out, 4 * g + r, false);
-                    dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(T.a[0][r], y[r], inv_var, true, stat) : 0.f;
+                    for (int r = 0; r < 4; ++r) {
+                        const int u = unit_of(d_out, 4 * g + r, false);
+                        dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(T.a[0][r], y[r], inv_var, true, stat) : 0.f;
+                    }
                 }
             }
         } else {

@@ -127,7 +127,12 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
         nd.actOff[l] = so; so += L.out_dim;
         mw = std::max(mw, std::max(L.in_dim, L.out_dim));
     }
-    if (d->likelihood < TBNN_LIK_GAUSSIAN || d->likelihood > TBNN_LIK_BERNOULLI) return fail(-1, "unknown likelihood");
+    if (d->likelihood < TBNN_LIK_GAUSSIAN || d->likelihood > TBNN_LIK_CATEGORICAL) return fail(-1, "unknown likelihood");
+    if (d->likelihood == TBNN_LIK_CATEGORICAL) {
+        if (nd.out[nd.nl - 1] < 2) return fail(-1, "the categorical likelihood needs at least 2 outputs (one logit per class)");
+        if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
+            return fail(-1, "the categorical likelihood takes the last layer's outputs as logits: the last layer must carry no activation");
+    }
     nd.P = off;
     nd.lik = d->likelihood;
     nd.H = 4 * nd.nl + (nd.lik == TBNN_LIK_GAUSSIAN ? 1 : 0);

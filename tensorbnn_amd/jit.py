@@ -68,9 +68,18 @@ def _sources_stamp() -> str:
 ACT_PACKED = 0x40000000          # csrc/common.hpp: TBNN_ACT_PACKED
 
 
+LIK_GAUSS, LIK_BERN, LIK_CAT = 0, 1, 2      # csrc/common.hpp: SHAPE_LIK_* (the Gaussian family, Bernoulli, categorical)
+
+
+def lik_code(likelihood: int) -> int:
+    """the kernels' likelihood code (csrc/common.hpp: shape_lik) of a LIK_* value: Gaussian and fixed-sd Gaussian share their kernels"""
+    from . import _native as nat
+    return {nat.LIK_BERNOULLI: LIK_BERN, nat.LIK_CATEGORICAL: LIK_CAT}.get(int(likelihood), LIK_GAUSS)
+
+
 def shape_of(layers: Sequence[tuple], likelihood: int):
-    """(dims, hact, lact, bern) or None when the fused kernels cannot express the network; hact: the hidden layers' activation, or the
-    packed per-layer code when they differ"""
+    """(dims, hact, lact, lik) or None when the fused kernels cannot express the network; hact: the hidden layers' activation, or the
+    packed per-layer code when they differ; lik: `lik_code`"""
     from . import _native as nat
     dims = [int(layers[0][0])] + [int(l[1]) for l in layers]
     acts = [int(l[2]) for l in layers]
@@ -83,12 +92,19 @@ def shape_of(layers: Sequence[tuple], likelihood: int):
         if len(acts) - 1 > 9 or any(not 0 <= a <= 7 for a in acts[:-1]):
             return None
         hact = ACT_PACKED | sum(a << (3 * l) for l, a in enumerate(acts[:-1]))
-    return dims, hact, acts[-1], int(likelihood == nat.LIK_BERNOULLI)
+    return dims, hact, acts[-1], lik_code(likelihood)
 
 
-def families(dims) -> list:
-    """candidate kernel families for `dims`, best first"""
+def families(dims, lik: int = LIK_GAUSS) -> list:
+    """candidate kernel families for `dims` and the likelihood code `lik` (`lik_code`), best first"""
     nl = len(dims) - 1
+    if lik == LIK_CAT:
+        # the categorical likelihood couples a row's outputs: only the MFMA output tile of the mid, tall and wide kernels carries it
+        # (csrc/kernels_fast.hpp: cat_delta4) -- 3 .. 16 outputs; the narrow family, its trajectory kernel and the VALU last layer
+        # (<= 2 outputs) compute the likelihood per element and do not take it (the layered family does)
+        if not 3 <= dims[-1] <= 16:
+            return []
+        return [f for f in families(dims) if f in ("mid", "tall", "wide")]
     out = []
     tiles = sum(_cdiv(dims[l + 1], 16) * _cdiv(dims[l] + 1, 16) for l in range(nl))
     # (widths: 64, the widest layer the hand-threaded dW phases of deeper networks were written and fuzzed for; a network with ONE hidden layer has
@@ -208,8 +224,9 @@ def tall_usage(dims) -> dict:
     return {"hidden": max(dims[1:-1]), "vgpr": vgpr, "vgpr_agpr": vgpr + agpr, "lds": lds, "regs": regs}
 
 
-def source(dims, hact, lact, bern, family) -> str:
-    shape = f"Shape<{hact}, {lact}, {'true' if bern else 'false'}, {', '.join(map(str, dims))}>"
+def source(dims, hact, lact, lik, family) -> str:
+    lik_arg = {LIK_GAUSS: "false", LIK_BERN: "true"}.get(int(lik), "SHAPE_LIK_CAT")
+    shape = f"Shape<{hact}, {lact}, {lik_arg}, {', '.join(map(str, dims))}>"
     if family == "wide":
         return (f'#include "{CSRC}/jit_wide.hpp"\nusing S = {shape};\n'
                 'extern "C" int tbnn_jit_ops(FusedOps* o) { JitWide<S>::fill(o); return 0; }\n')
@@ -239,6 +256,11 @@ def _warn_generic(dims, why):
                   f"not on a fused kernel: {why}", RuntimeWarning, stacklevel=3)
 
 
+def cache_key(dims, hact, lact, lik, extra=()) -> str:
+    """name of a shape's cached library (and of its `.fail`): everything that changes what is compiled"""
+    return hashlib.sha1(f"{dims}|{hact}|{lact}|{lik}|{_sources_stamp()}|{list(extra)}|{families(dims, lik)}|{NARROW_FLAGS}|{TALL_NOP}".encode()).hexdigest()[:20]
+
+
 def build(layers: Sequence[tuple], likelihood: int, verbose: bool = False) -> Optional[str]:
     """path of the compiled kernel library for this network, or None (layered kernels, with a note on stderr)"""
     import fcntl
@@ -247,14 +269,14 @@ def build(layers: Sequence[tuple], likelihood: int, verbose: bool = False) -> Op
         _warn_generic([int(layers[0][0])] + [int(l[1]) for l in layers],
                       "the fused kernels need >= 2 dense layers (and at most 9 hidden layers when their activations differ)")
         return None
-    dims, hact, lact, bern = sh
+    dims, hact, lact, lik = sh
     extra = os.environ.get("TBNN_JIT_FLAGS", "").split()          # diagnostic builds (-DTBNN_WPAD=8 ...); part of the cache key
     if os.environ.get("TBNN_JIT_LOG"):                            # which shapes a run asked for (tests/jit_shapes.json is made from this: `prebuild`)
         import json
         with open(os.environ["TBNN_JIT_LOG"], "a") as f:
             f.write(json.dumps({"layers": [list(map(int, l)) for l in layers], "likelihood": int(likelihood),
                                 "skip": os.environ.get("TBNN_JIT_SKIP", ""), "flags": os.environ.get("TBNN_JIT_FLAGS", "")}) + "\n")
-    key = hashlib.sha1(f"{dims}|{hact}|{lact}|{bern}|{_sources_stamp()}|{extra}|{families(dims)}|{NARROW_FLAGS}|{TALL_NOP}".encode()).hexdigest()[:20]
+    key = cache_key(dims, hact, lact, lik, extra)
     d = cache_dir()
     so, failed = os.path.join(d, f"tbnn_{key}.so"), os.path.join(d, f"tbnn_{key}.fail")
     if os.path.exists(so):
@@ -275,12 +297,12 @@ def build(layers: Sequence[tuple], likelihood: int, verbose: bool = False) -> Op
                 return None
             print(f"tensorbnn_amd: compiling MFMA kernels for network {dims} (once; cached in {d})", file=sys.stderr, flush=True)
             log, deterministic = [], True
-            for fam in families(dims):
+            for fam in families(dims, lik):
                 # per-process file names: nothing another process may be reading is ever truncated
                 src = os.path.join(d, f"tbnn_{key}_{fam}.{os.getpid()}.hip")
                 tmp = so + f".{os.getpid()}.tmp"
                 with open(src, "w") as f:
-                    f.write(source(dims, hact, lact, bern, fam))
+                    f.write(source(dims, hact, lact, lik, fam))
                 # compiled through checked_compile.run: hipcc's own steps with the MFMA hazard check (hazard_lint.py) between the device
                 # listing and the assembler -- wait states inserted where a pair lacks them, the finished library disassembled and checked
                 # again; a library is never handed out unchecked

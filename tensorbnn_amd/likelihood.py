@@ -81,3 +81,30 @@ class BernoulliLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+def log_softmax(f, axis=0):
+    """log softmax of logits along `axis`, shifted by their max (finite for any finite logits)"""
+    f = np.asarray(f, dtype=np.float64)
+    d = f - np.max(f, axis=axis, keepdims=True)
+    return d - np.log(np.sum(np.exp(d), axis=axis, keepdims=True))
+
+
+class CategoricalLikelihood(Likelihood):
+    """Multi-class classification: the last dense layer's d_out >= 2 outputs, with no activation after it, are a row's logits, and
+    the data term is sum_rows sum_k y_k log softmax_k(f) for one-hot or probability rows y (include/tbnn.h TBNN_LIK_CATEGORICAL).
+    Unlike K BernoulliLikelihood outputs, the class probabilities of a row sum to one.  No hyper-parameter."""
+    kind = nat.LIK_CATEGORICAL
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.mainProbsInHypers = False
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """y_k log softmax_k(f) per (output, row), [d_out, rows] as BernoulliLikelihood's; the sum is the data term"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [d_out, rows]
+        y = np.asarray(kwargs["realVals"], dtype=np.float64).reshape(-1, f.shape[0]).T
+        return y * log_softmax(f, axis=0)
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

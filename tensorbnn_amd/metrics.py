@@ -55,6 +55,23 @@ class PercentError(Metric):
               "validation percent error{: 7.3f}".format(self.percentErrorValidate))
 
 
+class CategoricalAccuracy(Metric):
+    """multi-class accuracy (likelihood.CategoricalLikelihood): the share of rows whose largest logit is the class of Y's largest entry
+    (one-hot or probability rows; mean / sd / scaleExp do not apply to logits and are ignored)"""
+
+    def calculate(self, predictionsTrain, predictionsValidate, realTrain, realValidate):
+        def acc(pred, real):
+            f = np.asarray(pred).T                                               # [rows, d_out]
+            y = np.asarray(real).reshape(f.shape)
+            return float(np.mean(np.argmax(f, axis=1) == np.argmax(y, axis=1)))
+        self.accuracyTrain = acc(predictionsTrain, realTrain)
+        self.accuracyValidate = acc(predictionsValidate, realValidate)
+
+    def display(self):
+        print("training accuracy{: 9.5f}".format(self.accuracyTrain),
+              "validation accuracy{: 9.5f}".format(self.accuracyValidate))
+
+
 class Accuracy(Metric):
     """metrics.py:110-141"""
 

@@ -106,13 +106,16 @@ class predictor(object):
     def _data_logprob(self, likelihood, trainX, trainY, n):
         """summed log-likelihood of the training rows under every n-th network (see the module docstring)"""
         from .layer import _multivariate_log_prob
-        from .likelihood import BernoulliLikelihood, FixedGaussianLikelihood
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, log_softmax
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
         for i, f in enumerate(preds):
             cur = np.asarray(f, dtype=np.float32).T                             # [rows, d_out]
             real = y.reshape(cur.shape)
+            if isinstance(likelihood, CategoricalLikelihood):
+                out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
+                continue
             if isinstance(likelihood, BernoulliLikelihood):
                 out.append(np.float32(0))                                       # likelihood.py:239-243
                 continue
