@@ -12,7 +12,8 @@ are hand-written and only their *shape parameters* are bound at run time.)
 Family choice (first that compiles wins, in the order below -- except that a narrow network with 3 .. 16 outputs tries mid first: `families`; a shape
 no family accepts is remembered as `.fail` and runs on the layered kernels):
   * narrow (`k_fwd_bwd_fast3`, else `k_fwd_bwd_fast`): every dW accumulator in one wave's registers --
-    fan-in <= 16, widths <= 64 (a network with ONE hidden layer: <= 256 units, <= 160 with more than two outputs), at most NARROW_TILES 16x16 dW tiles in total;
+    fan-in <= 16, widths <= 64 (a network with ONE hidden layer: <= 256 units, <= 160 with more than two outputs), at most NARROW_TILES 16x16 dW tiles in total,
+    and an LDS plan within 160 KB (`narrow_usage`: what bounds the depth);
   * mid (`k_fwd_bwd_mid`): >= 3 dense layers, <= 16 outputs (3 .. 16: the last layer is an MFMA layer too), fan-in <= 128, at most 63 dW tiles over the MFMA
     layers and weight images + operand blocks within 160 KB of LDS (`mid_fits`): one fused kernel, nothing through HBM;
   * tall (`k_fwd_bwd_tall`): a first-layer fan-in above the narrow family's 16 (.. a few thousand columns) in front of narrow hidden layers
@@ -20,7 +21,7 @@ no family accepts is remembered as `.fail` and runs on the layered kernels):
     (`tall_fits`) -- the reference's MNIST example 784 -> 20 -> 20 -> 1;
   * wide (`k_chain_wide` + `k_dw_wide`): >= 3 dense layers, <= 16 outputs (3 .. 16: the last layer is one more streamed middle layer), fan-in <= 32,
     hidden widths <= 256.
-Requirements common to all: dense layers only; hidden layers that do not all carry the same activation get a packed per-layer code (`shape_of`), nine
+Requirements common to all: dense layers only, at most MAX_LAYERS (16) of them; hidden layers that do not all carry the same activation get a packed per-layer code (`shape_of`), nine
 hidden layers at most.
 """
 import hashlib
@@ -36,6 +37,7 @@ TALL_NOP = ["-DTBNN_ASM_MFMA_NOP=0"]                      # the tall family: no 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 NARROW_TILES = 40
+MAX_LAYERS = 16              # include/tbnn.h: TBNN_MAX_LAYERS
 MID_MAX_FANIN = 128          # keep in step with kernels_mid.hpp
 
 
@@ -101,6 +103,8 @@ def shape_of(layers: Sequence[tuple], likelihood: int, weighted: bool = False):
 def families(dims, lik: int = LIK_GAUSS) -> list:
     """candidate kernel families for `dims` and the likelihood code `lik` (`lik_code`), best first"""
     nl = len(dims) - 1
+    if nl > MAX_LAYERS:
+        return []                       # tbnn_create refuses the network (TBNN_MAX_LAYERS)
     # (the weighted bit changes no family's reach: a weighted narrow table only goes without the trajectory kernel, jit_narrow.hpp)
     if lik & ~LIK_WEIGHTED == LIK_CAT:
         # the categorical likelihood couples a row's outputs: only the MFMA output tile of the mid, tall and wide kernels carries it
@@ -117,6 +121,9 @@ def families(dims, lik: int = LIK_GAUSS) -> list:
     # (one hidden layer: 256 units with one or two outputs, 160 with 3 .. 16 -- beyond those a random draw of 60 such shapes had 9 refused by the build:
     # fast3 spills from ~300 units, k_fwd_bwd_fast's LDS plan overflows with many outputs behind > 200 units)
     narrow = dims[0] <= 16 and tiles <= NARROW_TILES and (max(dims) <= 64 or (nl == 2 and max(dims) <= (256 if dims[-1] <= 2 else 160)))
+    # (depth: every layer adds its weight images and per-wave activation images to the LDS plan -- 29 tiles of 16-wide layers reach 15 layers,
+    # whose plan no longer fits: `narrow_usage`)
+    nu = narrow_usage(dims) if narrow else None
     mid = nl >= 3 and dims[-1] <= 16 and dims[0] <= MID_MAX_FANIN and mid_fits(dims)
     # 3 .. 16 outputs on a narrow network: fast3 does not take them, and the mid-width kernel (MFMA last layer, round 6) measures 7 - 13 % ahead of
     # k_fwd_bwd_fast there (5 -> 50 -> 50 -> 50 -> 3 at 1e5 rows 65.3 against 70.4 us per step, 8 -> 40 -> 40 -> 10 34.8 against 39.8): mid first
@@ -124,9 +131,10 @@ def families(dims, lik: int = LIK_GAUSS) -> list:
     if mid_first:
         out.append("mid")
     if narrow:
-        if dims[-1] <= 2 and nl >= 2:
+        if dims[-1] <= 2 and nl >= 2 and nu["fast3"] <= NARROW_LDS:
             out.append("fast3")
-        out.append("fast")
+        if nu["fast"] <= NARROW_LDS:
+            out.append("fast")
     if mid and not mid_first:
         out.append("mid")
     # (fan-in 17 .. 32 with ONE hidden layer: the narrow family stops at 16 inputs, mid and wide need two hidden layers -- the tall kernel is what such a
@@ -139,6 +147,39 @@ def families(dims, lik: int = LIK_GAUSS) -> list:
         out.append("wide")
     skip = {f for f in os.environ.get("TBNN_JIT_SKIP", "").split(",") if f}      # diagnostic / tests: e.g. "mid" forces the wide path
     return [f for f in out if f not in skip]
+
+
+# the narrow kernels' static LDS arrays (kernels_fast.hpp / kernels_fast3.hpp: the "LDS budget" static_asserts)
+NARROW_LDS = 160 * 1024
+
+
+def narrow_usage(dims) -> dict:
+    """LDS bytes of k_fwd_bwd_fast3 ("fast3") and k_fwd_bwd_fast ("fast"): FastCfg::LDS_FLOATS and F3Cfg::LDS3_FLOATS restated (TBNN_WPAD = TBNN_PPAD
+    = 4, FAST_WAVES = 4) -- the weight, bias and transposed images, the per-wave activation and delta images, the epilogue's dW staging.  fast3
+    adds its cooperative exchange buffers only where they fit and 4 floats otherwise: the smaller sum is what its static_assert bounds"""
+    nl, W = len(dims) - 1, 4
+    MT = lambda l: _cdiv(dims[l + 1], 16)
+    NT = lambda l: _cdiv(dims[l] + 1, 16)
+    KG = lambda l: _cdiv(dims[l], 16)
+    maxmt = max(MT(l) for l in range(nl))
+    wb = sum(16 * MT(l) * (16 * KG(l) + 4) + 16 * MT(l) for l in range(nl))
+    nlm = nl - 1 if nl >= 2 and dims[-1] <= 2 else nl                      # the VALU last layer has no images
+    static = wb + sum(16 * KG(l) * (16 * MT(l) + 4) for l in range(1, nlm))
+    staged = lambda t: t if t * W * 256 <= 39936 else min(t, 16)            # dW tiles per epilogue pass
+    dw = sum(MT(l) * NT(l) for l in range(nlm))
+    fast = max(static + W * (sum(16 * (16 * NT(l) + 4) for l in range(nlm)) + 16 * (16 * maxmt + 4)), staged(dw) * W * 256)
+    # fast3: fringe units (1 or 2 of a 16-unit tile) on the VALU, N-fringe pairs of dW (F3Cfg: NF, MTF, NCF, FP_REGS)
+    NF = lambda l: dims[l + 1] % 16 if dims[l + 1] % 16 in (1, 2) else 0
+    MTF = lambda l: MT(l) - 1 if NF(l) else MT(l)
+    nlm3 = nl - 1 if MTF(nl - 1) == 0 else nl
+    plain = sum(MTF(l) * NT(l) for l in range(nlm3))
+    ncf = lambda l: plain <= 39 and l < nlm3 and NT(l) >= 2 and 1 <= MTF(l) <= 4 and dims[l] + 1 - 16 * (NT(l) - 1) <= 4
+    dw3 = sum(MTF(l) * (NT(l) - ncf(l)) + 2 * ncf(l) for l in range(nlm3))
+    kin = lambda l: _cdiv(dims[0], 4) if l == 0 else 4 * MT(l - 1)
+    fp = sum(0 if not NF(l) else (2 * NT(l) if MTF(l) > 0 else NF(l) * (kin(l) + 1)) for l in range(nl))
+    wave3 = sum(16 * NT(l) * 20 for l in range(nlm3)) + 16 * maxmt * 20 + 128
+    fast3 = max(static + W * wave3, staged(dw3) * W * 256, W * max(fp, 1) * 64) + 4
+    return {"fast3": fast3 * 4 + 64, "fast": fast * 4 + 64}
 
 
 def wide_fits(dims) -> bool:

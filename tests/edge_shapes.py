@@ -1,7 +1,7 @@
 """Capacity edges of the fused kernel families, derived from the admission rules themselves (tensorbnn_amd/jit.py: `families`, `mid_usage`,
-`tall_usage`, `wide_usage`): no random draws.  Each case starts from a small shape its family takes, walks one dimension (fan-in, a hidden width, the
-depth, the output count) while the family still admits the shape, and records the last admitted shape (`dims`) and its first refused neighbour
-(`refused`).  `limit` names the rule that refuses the neighbour; tests/test_host_logic.py recomputes the estimates and checks that it is that rule
+`tall_usage`, `wide_usage`, `narrow_usage`): no random draws.  Each case starts from a small shape its family takes, walks one dimension (fan-in, a
+hidden width, the output count, or the depth: one more copy of the last hidden layer) while the family still admits the shape, and records the last
+admitted shape (`dims`) and its first refused neighbour (`refused`).  A depth walk ends at the C ABI's 16 dense layers at the latest (limit "abi").  `limit` names the rule that refuses the neighbour; tests/test_host_logic.py recomputes the estimates and checks that it is that rule
 alone, tests/test_gpu_capacity.py runs both shapes against the fp64 oracle.  __graft_entry__.build() prebuilds their run-time instantiations
 (`jit_jobs`).
 
@@ -18,8 +18,11 @@ SKIP = {"fast3": "mid,tall,wide", "fast": "fast3,mid,tall,wide", "mid": "fast3,f
         "wide": "fast3,fast,mid,tall"}
 NARROW_MAX_FANIN, NARROW_MAX_WIDTH = 16, 64
 
+MAX_LAYERS = 16                   # include/tbnn.h: TBNN_MAX_LAYERS (tbnn_create refuses deeper networks)
+DEPTH = "depth"
+
 # (name, family, base dims, index walked, step, limit): the walk moves dims[index] by step (+1 or -1) from the base while `family` is in
-# families(dims)
+# families(dims); index DEPTH inserts a copy of the last hidden layer instead (step +1)
 WALKS = [
     # narrow: every dW tile in one wave's registers
     ("narrow-fanin", "fast3", [8, 32, 32, 1], 0, +1, "fanin"),
@@ -51,6 +54,14 @@ WALKS = [
     ("wide-lds", "wide", [40, 80, 256, 1], 0, +1, "lds"),
     ("wide-regs", "wide", [8, 256, 240, 1], 0, +1, "regs"),
     ("wide-outputs", "wide", [10, 200, 120, 3], 3, +1, "outputs"),
+    # depth: every layer adds weight and activation images to the LDS plans of narrow, mid and tall; the wide family streams its middle
+    # layers through a ring of weight slots and reaches the ABI's 16 layers
+    ("narrow-depth", "fast3", [4, 16, 16, 1], DEPTH, +1, "lds"),
+    ("narrow-depth-fast", "fast", [4, 16, 16, 1], DEPTH, +1, "lds"),
+    ("mid-depth", "mid", [4, 16, 16, 2], DEPTH, +1, "abi"),
+    ("mid-depth-outputs", "mid", [4, 24, 24, 10], DEPTH, +1, "lds"),
+    ("tall-depth", "tall", [300, 16, 16, 2], DEPTH, +1, "lds"),
+    ("wide-depth", "wide", [10, 64, 64, 1], DEPTH, +1, "abi"),
 ]
 # pairs of admitted shapes on one family (refused None)
 PAIRS = [
@@ -88,6 +99,8 @@ def admits(family, dims):
 
 def _step(dims, index, step):
     d = list(dims)
+    if index == DEPTH:
+        return d[:-1] + [d[-2]] + d[-1:]
     d[index] += step
     return d
 
@@ -98,7 +111,7 @@ def walk(family, base, index, step):
     d = list(base)
     for _ in range(WALK_CAP):
         nxt = _step(d, index, step)
-        if min(nxt) < 1 or not admits(family, nxt):
+        if min(nxt) < 1 or not admits(family, nxt):        # (a network deeper than MAX_LAYERS: no family, `abi`)
             return d, nxt
         d = nxt
     raise AssertionError(f"{family}: no limit within {WALK_CAP} steps of {base}")
@@ -126,15 +139,18 @@ def usage(family, dims) -> dict:
     nl, out = len(dims) - 1, dims[-1]
     if family in ("fast3", "fast"):
         tiles = sum(jit._cdiv(dims[l + 1], 16) * jit._cdiv(dims[l] + 1, 16) for l in range(nl))
-        u = {"fanin": (dims[0], NARROW_MAX_FANIN), "tiles": (tiles, jit.NARROW_TILES)}
+        u = {"fanin": (dims[0], NARROW_MAX_FANIN), "tiles": (tiles, jit.NARROW_TILES), "abi": (nl, MAX_LAYERS)}
         if nl == 2:
             u["onehidden"] = (max(dims), 256 if out <= 2 else 160)
         else:
             u["width"] = (max(dims), NARROW_MAX_WIDTH)
         if family == "fast3":
             u["outputs"] = (out, 2)
+        # (the LDS plan is only evaluated for shapes the narrow rules above admit, as jit.families does)
+        if all(v <= b for v, b in u.values()):
+            u["lds"] = (jit.narrow_usage(dims)[family], jit.NARROW_LDS)
         return u
-    u = {"depth": (0 if nl >= (2 if family == "tall" else 3) else 1, 0), "outputs": (out, 16)}
+    u = {"depth": (0 if nl >= (2 if family == "tall" else 3) else 1, 0), "outputs": (out, 16), "abi": (nl, MAX_LAYERS)}
     if family == "mid":
         u["fanin"] = (dims[0], jit.MID_MAX_FANIN)
         est, lim = jit.mid_usage(dims), jit.MID_LIMITS
@@ -155,7 +171,10 @@ def over(family, dims) -> set:
 
 
 def landing(dims):
-    """the family a refused neighbour runs on with no TBNN_JIT_SKIP: the first of families(), or "layered\""""
+    """the family a refused neighbour runs on with no TBNN_JIT_SKIP: the first of families(), or "layered"; "abi" where tbnn_create refuses
+    the network"""
+    if len(dims) - 1 > MAX_LAYERS:
+        return "abi"
     f = [x for x in _families(dims)]
     return f[0] if f else "layered"
 
@@ -170,7 +189,7 @@ def jit_jobs():
     jobs = []
     for c in cases():
         jobs.append({"layers": layers_of(c["dims"], c["lik"]), "likelihood": c["lik"], "skip": SKIP[c["family"]], "flags": ""})
-        if c["refused"] is not None and landing(c["refused"]) != "layered":
+        if c["refused"] is not None and landing(c["refused"]) not in ("layered", "abi"):
             jobs.append({"layers": layers_of(c["refused"], c["lik"]), "likelihood": c["lik"], "skip": "", "flags": ""})
     return jobs
 

@@ -6,7 +6,7 @@ For each edge case:
       the fuzz tolerances (test_gpu_fuzz.py) with no fp32-oracle or relu-kink tier; every launch three times and bit-identical;
   (b) an injected transition with both decisions and a hyper transition on that shape, against o.weight_step / o.hyper_step;
   (c) the first refused neighbour runs, with no TBNN_JIT_SKIP, on the first family jit.families names for it (or the layered family), and is
-      checked as in (a);
+      checked as in (a) -- a neighbour deeper than the C ABI's 16 layers must be refused by tbnn_create;
   (d) the shapes whose fused build spills (edge_shapes.MUST_REFUSE), which the estimates refuse, run on the layered family and are checked as in (a).
 A few edges run with a Bernoulli likelihood as well (edge_shapes.BERNOULLI), their outputs kept off saturation.
 Row counts: a ragged last row tile; TBNN_FAST_GRID makes every workgroup of the narrow, mid and tall kernels walk many row tiles, and the wide
@@ -111,6 +111,11 @@ def test_admitted_edge_vs_fp64(native, monkeypatch, c):
 def test_refused_neighbour_lands_on_the_next_family(native, monkeypatch, c):
     fam = es.landing(c["refused"])
     assert c["family"] not in es._families(c["refused"])
+    if fam == "abi":                                          # deeper than TBNN_MAX_LAYERS: no kernel at all, tbnn_create refuses it
+        spec = o.make_spec(c["refused"], o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_GAUSSIAN, o.ACT_NONE)
+        with pytest.raises(native.TbnnError, match="n_layers"):
+            native.Chain(layers_of(spec), likelihood=spec.likelihood, jit=True)
+        return
     setenv(monkeypatch, fam, "")
     spec, X, Y, theta, eta = problem(c["refused"], N_WIDE if fam == "wide" else N_ROWS)
     value_gradient_forward(native, spec, X, Y, theta, eta, fam)

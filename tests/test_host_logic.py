@@ -258,7 +258,10 @@ def test_capacity_edge_pairs(monkeypatch, case):
     assert es.over(fam, dims) == set(), es.usage(fam, dims)
     if nb is None:
         return
-    assert sum(a != b for a, b in zip(dims, nb)) == 1 and sum(abs(a - b) for a, b in zip(dims, nb)) == 1, (dims, nb)
+    if any(w[3] == es.DEPTH for w in es.WALKS if w[0] == case["name"]):
+        assert nb == dims[:-1] + [dims[-2]] + dims[-1:], (dims, nb)          # one more copy of the last hidden layer
+    else:
+        assert sum(a != b for a, b in zip(dims, nb)) == 1 and sum(abs(a - b) for a, b in zip(dims, nb)) == 1, (dims, nb)
     assert fam not in jit.families(nb), (nb, jit.families(nb))
     assert es.over(fam, nb) == {case["limit"]}, (nb, es.usage(fam, nb))
     value, bound = es.usage(fam, dims)[case["limit"]]
@@ -300,6 +303,59 @@ def test_estimates_agree_with_measured_builds(monkeypatch):
     for (fam, dims), why in fz.UNBUILDABLE.items():
         f = {"onehidden": "fast"}.get(fam, fam)
         assert (f not in jit.families(list(dims))) != ((f, dims) in admitted), (fam, dims, why)
+
+
+def test_failed_builds_are_refused_by_the_rule_they_name(monkeypatch):
+    """tests/golden/jit_build_outcomes.json: a deep shape whose build failed (the "LDS budget" static_assert) breaks the rule its record names and
+    no other; the narrow family's LDS estimate (jit.narrow_usage) is what refuses 15 layers of 16 units"""
+    import json
+    from tensorbnn_amd import jit
+    monkeypatch.delenv("TBNN_JIT_SKIP", raising=False)
+    doc = json.load(open(os.path.join(ROOT, "tests", "golden", "jit_build_outcomes.json")))
+    named = [r for r in doc["outcomes"] if "rule" in r]
+    assert {r["family"] for r in named} >= {"fast3", "fast", "mid", "tall"}
+    for r in named:
+        assert not r["built"] and edge_shapes.over(r["family"], r["dims"]) == {r["rule"]}, (r, edge_shapes.usage(r["family"], r["dims"]))
+    deep = [4] + [16] * 14 + [1]
+    assert jit.families(deep) == ["mid", "wide"] and jit.narrow_usage(deep)["fast"] > jit.NARROW_LDS
+    assert jit.families(deep[:-2] + deep[-1:]) == ["fast", "mid", "wide"]
+    assert jit.families([4] + [16] * 16 + [1]) == [] and jit.families([4] + [16] * 15 + [1])      # TBNN_MAX_LAYERS
+
+
+def test_suite_and_bench_shapes_keep_their_family(monkeypatch):
+    """the narrow LDS rule and the 16-layer cap refuse no shape the suite or bench.py ran before them: every run-time instantiation (tests/
+    jit_shapes.json, the fuzz and edge shapes) and every bench workload gets the family it got without those two rules -- except the refused
+    neighbours of the depth walks, which exist to cross them"""
+    import json
+    import fuzz_shapes as fz
+    from tensorbnn_amd import jit, workloads
+    monkeypatch.delenv("TBNN_JIT_SKIP", raising=False)
+    crossing = {tuple(c["refused"]) for c in edge_shapes.cases() if c["refused"] is not None and c["limit"] in ("lds", "abi")
+                and c["family"] in ("fast3", "fast")}
+    jobs = json.load(open(os.path.join(ROOT, "tests", "jit_shapes.json"))) + fz.jit_jobs() + edge_shapes.jit_jobs()
+    shapes = []
+    for j in jobs:
+        sh = jit.shape_of([tuple(l) for l in j["layers"]], j["likelihood"], j.get("weighted", False))
+        if sh is not None:
+            shapes.append((sh[0], sh[3], j.get("skip", "")))
+    shapes += [(w["dims"], jit.lik_code(w["lik"]), "") for w in workloads.WORKLOADS.values()]
+
+    def first(dims, lik, skip):
+        monkeypatch.setenv("TBNN_JIT_SKIP", skip)
+        f = jit.families(dims, lik)
+        return f[0] if f else "layered"
+    seen = 0
+    for dims, lik, skip in shapes:
+        if tuple(dims) in crossing:
+            continue
+        now = first(dims, lik, skip)
+        with monkeypatch.context() as m:
+            m.setattr(jit, "NARROW_LDS", 1 << 40)
+            m.setattr(jit, "MAX_LAYERS", 1 << 10)
+            before = first(dims, lik, skip)
+        assert now == before, (dims, lik, skip, before, now)
+        seen += 1
+    assert seen >= 300 and any(len(d) - 1 == 16 for d, _, _ in shapes)
 
 
 def test_predictor_reweight_without_likelihood(tmp_path):
