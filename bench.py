@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py -- leapfrog steps/s of the HMC hot path on BASELINE configs[1] (+ the other configs as `secondary`).
+"""bench.py -- leapfrog steps/s of the HMC hot path on BASELINE configs[1] (--full: + the other configs as `secondary`).
 
   python bench.py --gpus N --steps K --warmup W
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
@@ -18,18 +18,22 @@ the state the warm-up ended in, and the median region is reported, every region'
 eta.npy) and the step's record (log_accept_ratio.npy, accepted.npy, logp_new.npy, ...; hyper_*.npy for the hyper transition) --
 so that two builds run with the same arguments can be compared output for output.
 
-At N = 1 the same invocation also measures BASELINE configs[3], configs[4] (weight transition + hyper transition with
-the reference's dual averaging per epoch) and configs[0], each with its own roofline and cpu_baseline, under
-"secondary" (--workload X measures X alone; --no-secondary skips them).
+A plain run does only what the headline figure needs: set up, warm up, the timed regions, --dump-outputs, the result line.
+--full adds everything that takes runs of its own: the fused-pass burst (roofline.kernel_us_burst), the cpu_baseline and, at
+N = 1, BASELINE configs[3], configs[4] (weight transition + hyper transition with the reference's dual averaging per epoch)
+and configs[0], each with its own roofline and cpu_baseline, under "secondary" (--workload X measures X alone; --no-secondary
+and --no-cpu-baseline leave those parts out of a --full run).
 
 roofline: dominant kernel = the fused forward+backward pass (k_fwd_bwd_fast3; k_chain_wide + k_dw_wide for the wide
 configs).  achieved = algorithmic matmul FLOP of one pass (2n(3S - in1*out1)) / its mean duration,
 measured with hipEvent pairs on the chain's own stream around every 47th pass inside the timed region.  peak = 157.3
 TFLOP/s (FP32 MFMA, dense, MI355X_MICROARCH.md).  traffic = HBM bytes per pass from the committed rocprofv3 PMC pass
 (profiles/) -- quoted, like frac_rocprof, only when that pass was measured on the build that is loaded (tbnn_build_id), else null.
-cpu_baseline: the oracle's C restatement (oracle/c, kind "port") timed on the host cores on a bounded sample of the
+cpu_baseline (--full): the oracle's C restatement (oracle/c, kind "port") timed on the host cores on a bounded sample of the
 same workload from the same state (rank 0, N = 1 only, outside the timed GPU region): best thread count of a short
 scan, a 1-thread figure, and a PyTorch-CPU value+grad cross-check (oracle/torch_ref.py).
+
+The whole record goes to stderr as one JSON line (--record FILE: to FILE as well); stdout carries the short result line.
 """
 import argparse
 import json
@@ -414,13 +418,13 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1, du
     value = total_leapfrog / dt
     prof = [o["fwdbwd_us"] for o in outs if o["fwdbwd_us"] > 0]
     k_pair_us = float(np.mean(prof)) if prof else None
-    # next to it: a burst of passes at the state the timed region ended in, back to back on the chain's stream between ONE pair of events
+    # next to it (--full): a burst of passes at the state the timed region ended in, back to back on the chain's stream between ONE pair of events
     # (tbnn_debug_fused_burst, ~20 ms).  It is a THROUGHPUT figure: consecutive launches of the same kernel overlap head and tail (41.9 us per
     # pass at configs[1] where rocprofv3 sees 42.6 us per launch), while an event pair around a single launch inside the timed region carries
     # ~3 us of its own cost (45.4).  `roofline.frac` stays on the event pairs (the conservative one); rocprofv3's duration is frac_rocprof.
     k_us = k_pair_us
     k_burst_us = None
-    if rank == 0 and k_pair_us:
+    if rank == 0 and k_pair_us and args.full:
         try:
             k_burst_us = ch.fused_burst_us(int(min(2000, max(5, 20000.0 / k_pair_us))))
         except Exception as e:               # (a diagnostic build without the entry point)
@@ -474,7 +478,7 @@ def run_workload(name, steps, warmup, args, rank, world, dev, ctx, repeats=1, du
         roofline = {"bound": "launch latency (7e5 FLOP per step: SURVEY 8(d) reports steps/s only)", "kernel": kernel_name,
                     "kernel_us": round(k_us, 2) if k_us else None, "frac": None}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and name != "c5g":      # c5g: configs[4]'s arithmetic, see its cpu_baseline
+    if args.full and world == 1 and not args.no_cpu_baseline and name != "c5g":      # c5g: configs[4]'s arithmetic, see its cpu_baseline
         cpu = cpu_baseline(name, wl, X, Y, theta0, eta0, eps, P)
     line = {
         "metric": "leapfrog steps/sec (whole node)", "value": round(value, 2), "unit": "leapfrog steps/s",
@@ -614,7 +618,7 @@ def compact_line(line):
                 e["hyper_step"] = float("%.3g" % r["hyper_step_size"]["last"]) if r.get("hyper_step_size") else None
             sec[key.replace(" with GaussianDenseLayer priors", "g").replace("docs example 784-20-20-1", "docs784")] = e
         out["secondary"] = sec
-        out["secondary_note"] = "[4]: Cauchy priors (Q1); [4]g: Gaussian priors; [0]x64: 64 chains, 1 GPU; docs784: tutorial shape; all: gpurun_out/bench_full.json"
+        out["secondary_note"] = "[4]: Cauchy priors (Q1); [4]g: Gaussian priors; [0]x64: 64 chains, 1 GPU; docs784: tutorial shape; all: the full record on stderr"
     return out
 
 
@@ -685,8 +689,11 @@ def main():
     ap.add_argument("--sampling-step", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5, help="timed regions of exactly --steps epochs each for the headline workload; the median region is reported")
     ap.add_argument("--max-region-seconds", type=float, default=20.0, help="no further timed region is started once this much time went into them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the fused-pass burst, the CPU baselines and (N = 1, no --workload) the secondary configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary configs")
+    ap.add_argument("--record", metavar="FILE", default=None, help="also write the whole record (the stderr line) to FILE")
     ap.add_argument("--from-initial", action="store_true", help="start from the initial state instead of the burned-in fixture")
     ap.add_argument("--kernel", default="auto", choices=["auto", "generic", "fast"])
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -761,7 +768,7 @@ def main():
     steps = args.steps if args.steps is not None else wl["steps"]
     warmup = args.warmup if args.warmup is not None else wl["warmup"]
     line = run_workload(main_wl, steps, warmup, args, rank, world, dev, ctx, repeats=args.repeats, dump_dir=args.dump_outputs)
-    if args.workload is None and world == 1 and not args.no_secondary:
+    if args.full and args.workload is None and world == 1 and not args.no_secondary:
         sec = {}
         for name in ("c4", "c5", "c5g", "c1", "mn"):
             w2 = WORKLOADS[name]
@@ -778,17 +785,17 @@ def main():
             sec["configs[0] x64 chains on one GPU"] = {"error": repr(e)[:300]}
         line["secondary"] = sec
     if rank == 0:
-        # the whole record (long `sample` / `workload` texts, thread scans, torch cross-check) goes to stderr and to
-        # gpurun_out/bench_full.json; stdout carries ONE line short enough that every config's value / roofline fraction /
-        # CPU baseline survives a 2-KB tail of it
+        # the whole record (long `sample` / `workload` texts, thread scans, torch cross-check) goes to stderr and to --record;
+        # stdout carries ONE line short enough that every config's value / roofline fraction / CPU baseline survives a 2-KB tail of it
         full = json.dumps(line)
         print(full, file=sys.stderr, flush=True)
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as fh:
-                fh.write(full + "\n")
-        except OSError:
-            pass
+        if args.record:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+                with open(args.record, "w") as fh:
+                    fh.write(full + "\n")
+            except OSError as e:
+                print(f"bench: record not written ({e})", file=sys.stderr)
         print(json.dumps(compact_line(line)), flush=True)
     if ctx["dist"]:
         dist.destroy_process_group()

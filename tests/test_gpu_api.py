@@ -288,6 +288,40 @@ def test_bench_more_ranks_than_gpus_fails_fast():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """a plain `bench.py --gpus 1` measures the headline config alone (its roofline from the event pairs inside the timed region); --full adds what
+    takes runs of its own: the fused-pass burst and the CPU baseline (and, at N = 1 without --workload, the secondary configs)"""
+    import json
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = _bench_env()
+    env.pop("TBNN_BENCH_SINGLE_GPU", None)
+    rec = tmp_path / "record.json"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--record", str(rec)]
+    t0 = time.time()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    t_plain = time.time() - t0
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["cpu_baseline"] is None and "secondary" not in d and d["roofline"]["frac"] > 0.05
+    full = [json.loads(l) for l in r.stderr.splitlines() if l.startswith("{")][-1]
+    assert full["roofline"]["kernel_us_burst"] is None and full["value"] == d["value"]
+    assert json.loads(rec.read_text()) == full
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "4", "--warmup", "2", "--full"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0 and "secondary" not in d
+    full = [json.loads(l) for l in r.stderr.splitlines() if l.startswith("{")][-1]
+    assert full["roofline"]["kernel_us_burst"] > 0
+    print(f"plain run: {t_plain:.1f} s in all")
+
+
 def test_classification_flow(tmp_path, monkeypatch, native):
     """the classification use (docs/ClassificationExample.md:103-173 with the activations this build supports): Relu hidden
     layers, Sigmoid output, BernoulliLikelihood (no hyper of its own), Accuracy metric, samples on disk, predictor"""

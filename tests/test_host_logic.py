@@ -660,7 +660,7 @@ def test_cpu_quota_warning(monkeypatch, tmp_path):
 
 def test_bench_line_says_what_the_hazard_check_did():
     """the stdout line's roofline object carries the build-time MFMA hazard check in short (units checked / pairs repaired in their listings);
-    the full status string stays in gpurun_out/bench_full.json"""
+    the full status string stays in the whole record (stderr, --record)"""
     sys.path.insert(0, ROOT)
     import bench
     full = ("tbnn_api.hip: listing checked (0 repaired); disassembly clean; tbnn_mid.hip: listing checked (2 repaired: R2c:2); disassembly clean; "
