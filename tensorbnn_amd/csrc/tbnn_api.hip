@@ -8,8 +8,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -35,65 +37,104 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define ONE_CHAIN(h, what)                                                                     \
     do { if ((h)->C > 1) return fail(-1, what ": not available on a multi-chain handle (tbnn_create_multi)"); } while (0)
 
+// ---- owners: every buffer, event and stream the library makes has exactly one, whose destructor releases it ----
+// n elements of device memory (Pinned: of pinned host memory, hipHostMalloc with the given flags).  hipFree synchronises the device:
+// a buffer is released where the calls that replace it (alloc / grow / reset) or its scope (tbnn_destroy, the end of a call) say.
+template <class T, bool Pinned = false>
+class Buf {
+    T* p_ = nullptr;
+    size_t cap_ = 0;                      // elements allocated
+  public:
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    Buf& operator=(Buf&& o) noexcept { reset(); std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
+    ~Buf() { reset(); }
+    operator T*() const { return p_; }
+    void reset() {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr; cap_ = 0;
+    }
+    hipError_t alloc(size_t n, unsigned flags = 0) {          // (what it held is freed first)
+        reset();
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, n * sizeof(T), flags) : hipMalloc((void**)&p_, n * sizeof(T));
+        if (e == hipSuccess) cap_ = n; else p_ = nullptr;
+        return e;
+    }
+    // a pooled buffer: kept while it holds `need` elements, else freed and `n` allocated
+    hipError_t grow(size_t need, size_t n) { return cap_ >= need ? hipSuccess : alloc(n); }
+};
+template <class T> using PinBuf = Buf<T, true>;
+// a stream or an event: created into .v, destroyed with its owner
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {
+    T v = nullptr;
+    Owned() = default;
+    explicit Owned(T x) : v(x) {}
+    Owned(Owned&& o) noexcept : v(std::exchange(o.v, nullptr)) {}
+    ~Owned() { if (v) (void)Destroy(v); }
+    operator T() const { return v; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
 
 struct tbnn_comm {
     ncclComm_t comm = nullptr;
     int world = 1, rank = 0;
     int device = 0;
-    float* gbuf = nullptr; size_t gbuf_floats = 0;     // library-owned gather buffer
+    Buf<float> gbuf;                      // library-owned gather buffer
 };
 
 struct tbnn_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;                        // (the first member: destroyed after every buffer and event)
     NetDev nd{};
     uint32_t key0 = 0, key1 = 0, epoch = 0;
     int C = 1;                            // chains of this handle (tbnn_create_multi): every per-chain buffer is a [C][...] array, the per-chain
     uint32_t seed_hi = 0;                 // kernels run with gridDim.y = C; chain c draws from the Philox key (seed, chain_id + c)
     const FusedOps* ops = nullptr;        // the fused kernels of this shape: an ahead-of-time table (aot_ops.hpp) or a registered library
-    bool lay = false; LayPlan lplan{}; float* lstore = nullptr;   // kernels_layered.hpp: run-time-shape MFMA kernels, activations through HBM
-    float* lfwd = nullptr; size_t lfwd_floats = 0;                // its forward-only store (predict / metrics / ensembles): pooled, grown as needed
+    bool lay = false; LayPlan lplan{}; Buf<float> lstore;   // kernels_layered.hpp: run-time-shape MFMA kernels, activations through HBM
+    Buf<float> lfwd;                      // its forward-only store (predict / metrics / ensembles): pooled, grown as needed
     std::string kernel_name;
-    // data
-    float* dX = nullptr; float* dY = nullptr; bool own_data = false; long n = 0;
+    // data: the rows tbnn_set_data staged (Xown / Yown), or the caller's (tbnn_set_data_device: borrowed)
+    Buf<float> Xown, Yown; const float* dX = nullptr; const float* dY = nullptr; long n = 0;
     // row weights (tbnn_set_row_weights): [n x d_out targets | n weights] in one buffer -- what the kernels read as Y while weights are
     // set (kernels_fast.hpp: row_weight) -- and W = their sum in fp64; null / 0: none
-    float* dYw = nullptr; double wsum = 0.0;
+    Buf<float> dYw; double wsum = 0.0;
     int want = TBNN_KERNEL_AUTO;          // tbnn_net_desc::kernel (the re-selection of tbnn_set_row_weights follows it)
     // validation data (network.py:47-51) and the prediction buffer of tbnn_predict / tbnn_metrics
-    float* dXv = nullptr; float* dYv = nullptr; long nv = 0;
-    float* fbuf = nullptr; size_t fbuf_floats = 0; double* mpart = nullptr;
+    Buf<float> dXv, dYv; long nv = 0;
+    Buf<float> fbuf; Buf<double> mpart;
     // chain state
-    float *q_cur = nullptr, *g_cur = nullptr, *q = nullptr, *p = nullptr, *g = nullptr, *eta = nullptr;
-    float *p0_inj = nullptr, *logu_inj = nullptr, *tmp = nullptr;
-    float *gd = nullptr, *gd_cur = nullptr, *eta_prev = nullptr;   // data-term gradient of the proposal / current state; eta before a hyper step
+    Buf<float> q_cur, g_cur, q, p, g, eta;
+    Buf<float> p0_inj, logu_inj, tmp;
+    Buf<float> gd, gd_cur, eta_prev;      // data-term gradient of the proposal / current state; eta before a hyper step
     bool cur_valid = false;               // (logp, grad, stat) cached at q_cur for the current eta/data
     bool q_img_valid = false;             // h->qimg mirrors h->q (maintained by k_update)
     // fused-pass workspace
-    int grid = 0, pitch = 0; float* slabs = nullptr; double* pstat = nullptr; float* scratch = nullptr;
+    int grid = 0, pitch = 0; Buf<float> slabs; Buf<double> pstat; Buf<float> scratch;
     // wide-layer family (kernels_wide.hpp): its own workspace
-    WidePlan wplan; float* wstore = nullptr; float* wslabA = nullptr; float* wslabB = nullptr;
+    WidePlan wplan; Buf<float> wstore, wslabA, wslabB;
     int nslab = 0;                        // gradient slabs k_update reduces (wide: 1, already reduced)
     // row-sharded chain (tbnn_set_row_shard): all-reduce of the dense data-term gradient row + statistic
-    tbnn_comm* shard = nullptr; long n_total = 0; float* grow = nullptr; double* pstat_red = nullptr;
-    double* shard_buf = nullptr;          // the all-reduce operand: P gradient values + the statistic, as doubles
-    int* imgmap = nullptr; float* qimg = nullptr; float* qimg_cur = nullptr; int img_floats = 0;   // ops / layered: padded weight images
+    tbnn_comm* shard = nullptr; long n_total = 0; Buf<float> grow; Buf<double> pstat_red;
+    Buf<double> shard_buf;                // the all-reduce operand: P gradient values + the statistic, as doubles
+    Buf<int> imgmap; Buf<float> qimg, qimg_cur; int img_floats = 0;   // ops / layered: padded weight images
     size_t scratchPerWG = 0;
     float* pin_dev = nullptr;              // device-side address of pin
-    float* pin = nullptr;                  // pinned staging for the per-epoch state read-back (P + H floats): a 22-KB D2H copy
+    PinBuf<float> pin;                     // pinned staging for the per-epoch state read-back (P + H floats): a 22-KB D2H copy
                                            // into pageable memory costs ~180 us, through pinned memory ~15 us
-    Scal* sc = nullptr; Scal* sc_host = nullptr; Scal* sc_out = nullptr;   // sc_out: device copy for host
-    double* trace = nullptr; int trace_cap = 0;
-    Scal* d_recs = nullptr; Scal* h_recs = nullptr; int recs_cap = 0;     // tbnn_hmc_run: per-epoch records (pooled)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Buf<Scal> sc; PinBuf<Scal> sc_host; Buf<Scal> sc_out;   // sc_out: device copy for host
+    Buf<double> trace;
+    Buf<Scal> d_recs; PinBuf<Scal> h_recs;                  // tbnn_hmc_run: per-epoch records (pooled)
+    Event ev0, ev1;
     int profile = 0; long launch_no = 0;   // profile: event pair around every profile-th fwd+bwd launch
-    std::vector<hipEvent_t> pev; size_t pev_used = 0;   // pooled events: created once, re-used after every drain (no allocator in the timed loop)
+    std::vector<Event> pev; size_t pev_used = 0;        // pooled events: created once, re-used after every drain (no allocator in the timed loop)
     std::vector<int> pev_div;                           // leapfrog steps the pair's launch covered (1: a fused pass; L: a trajectory launch)
     const char* last_path = "none";                     // which kernels ran the last transition's leapfrog steps (tbnn_last_transition_path)
     // hyper workspace
-    float* hyp_ws = nullptr;
+    Buf<float> hyp_ws;
     // per-chain step control (tbnn_hmc_step_each / tbnn_hyper_step_each): [C] on the device, staged through pinned memory
-    StepCtl* ctl = nullptr; StepCtl* ctl_host = nullptr; float* epsh = nullptr; float* epsh_host = nullptr;
+    Buf<StepCtl> ctl; PinBuf<StepCtl> ctl_host; Buf<float> epsh; PinBuf<float> epsh_host;
     bool merge_ends = true;                // TBNN_MERGE_ENDS (read at tbnn_create): decision + record + commit in one k_energy launch
     bool traj = true;                      // TBNN_TRAJ (read at tbnn_create; 0: off): whole trajectories of small problems in one launch (kernels_traj.hpp)
 };
@@ -215,36 +256,7 @@ extern "C" int tbnn_destroy(tbnn_handle h) {
     if (!h) return 0;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->own_data) { hipFree(h->dX); hipFree(h->dY); }
-    if (h->dYw) hipFree(h->dYw);
-    float* bufs[] = {h->q_cur, h->g_cur, h->q, h->p, h->g, h->eta, h->p0_inj, h->logu_inj, h->tmp, h->gd, h->gd_cur, h->eta_prev,
-                     h->slabs, h->scratch, h->hyp_ws, h->wstore, h->wslabA, h->wslabB, h->grow, h->dXv, h->dYv, h->fbuf};
-    if (h->mpart) hipFree(h->mpart);
-    for (float* b : bufs) if (b) hipFree(b);
-    if (h->pstat) hipFree(h->pstat);
-    if (h->pstat_red) hipFree(h->pstat_red);
-    if (h->shard_buf) hipFree(h->shard_buf);
-    if (h->imgmap) hipFree(h->imgmap);
-    if (h->qimg) hipFree(h->qimg);
-    if (h->qimg_cur) hipFree(h->qimg_cur);
-    if (h->sc) hipFree(h->sc);
-    if (h->sc_out) hipFree(h->sc_out);
-    if (h->lstore) hipFree(h->lstore);
-    if (h->lfwd) hipFree(h->lfwd);
-    if (h->trace) hipFree(h->trace);
-    if (h->d_recs) hipFree(h->d_recs);
-    if (h->h_recs) hipHostFree(h->h_recs);
-    if (h->sc_host) hipHostFree(h->sc_host);
-    if (h->ctl) hipFree(h->ctl);
-    if (h->ctl_host) hipHostFree(h->ctl_host);
-    if (h->epsh) hipFree(h->epsh);
-    if (h->epsh_host) hipHostFree(h->epsh_host);
-    if (h->pin) hipHostFree(h->pin);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    for (auto e : h->pev) hipEventDestroy(e);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                             // (its owners free the buffers and events, then the stream)
     return 0;
 }
 
@@ -279,8 +291,7 @@ static int select_kernels(tbnn_ctx* h, bool weighted) {
     if (want == TBNN_KERNEL_FAST && !ops)
         return fail(-1, weighted ? "TBNN_KERNEL_FAST requested but no weighted kernel library is registered for this shape (jit.ensure_registered(..., weighted=True))"
                                  : "TBNN_KERNEL_FAST requested but no specialised kernel covers this shape");
-    for (float** b : {&h->qimg, &h->qimg_cur}) if (*b) { hipFree(*b); *b = nullptr; }
-    if (h->imgmap) { hipFree(h->imgmap); h->imgmap = nullptr; }
+    h->qimg.reset(); h->qimg_cur.reset(); h->imgmap.reset();
     h->ops = nullptr; h->lay = false; h->img_floats = 0; h->q_img_valid = false; h->cur_valid = false;
     h->kernel_name = "generic";
     if (want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) h->ops = ops;
@@ -302,12 +313,13 @@ static int select_kernels(tbnn_ctx* h, bool weighted) {
     if (h->ops || h->lay) {
         std::vector<int> map(2 * (size_t)nd.P);
         if (h->ops) h->ops->image_map(map.data()); else lay_image_map(nd, h->lplan, map.data());
-        HIPCHK(hipMalloc(&h->imgmap, map.size() * sizeof(int)));
+        const size_t imgs = NC * (size_t)h->img_floats;
+        HIPCHK(h->imgmap.alloc(map.size()));
         HIPCHK(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&h->qimg, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPCHK(hipMalloc(&h->qimg_cur, NC * (size_t)h->img_floats * sizeof(float)));
-        HIPCHK(hipMemset(h->qimg, 0, NC * (size_t)h->img_floats * sizeof(float)));       // padding stays zero for ever
-        HIPCHK(hipMemset(h->qimg_cur, 0, NC * (size_t)h->img_floats * sizeof(float)));
+        HIPCHK(h->qimg.alloc(imgs));
+        HIPCHK(h->qimg_cur.alloc(imgs));
+        HIPCHK(hipMemset(h->qimg, 0, imgs * sizeof(float)));       // padding stays zero for ever
+        HIPCHK(hipMemset(h->qimg_cur, 0, imgs * sizeof(float)));
     }
     return 0;
 }
@@ -328,7 +340,9 @@ static int create_impl(const tbnn_net_desc* desc, int device, uint64_t seed, uin
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
         return fail(-3, std::string("device is ") + prop.gcnArchName + ", libtbnn is built for gfx950 only");
     HIPCHK(hipSetDevice(device));
-    tbnn_ctx* h = new (std::nothrow) tbnn_ctx();
+    // the new handle is tbnn_destroy'ed on every early return, and handed out at the end
+    std::unique_ptr<tbnn_ctx, int (*)(tbnn_handle)> owner(new (std::nothrow) tbnn_ctx(), tbnn_destroy);
+    tbnn_ctx* h = owner.get();
     if (!h) return fail(-4, "out of host memory");
     h->device = device; h->nd = nd; h->C = n_chains;
     // Philox key = (seed, chain_id); the high seed word is folded into the key
@@ -336,41 +350,38 @@ static int create_impl(const tbnn_net_desc* desc, int device, uint64_t seed, uin
     h->seed_hi = (uint32_t)(seed >> 32);
     h->key1 = chain_id ^ h->seed_hi;
     const size_t NC = (size_t)n_chains;
-    auto bail = [&](int code, const std::string& m) { tbnn_destroy(h); return fail(code, m); };
-#define HIPB(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(-2, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-    HIPB(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    const size_t PB = NC * (size_t)nd.P * sizeof(float);               // per-chain arrays: [C][P] (one chain: [P])
-    HIPB(hipMalloc(&h->q_cur, PB)); HIPB(hipMalloc(&h->g_cur, PB)); HIPB(hipMalloc(&h->q, PB));
-    HIPB(hipMalloc(&h->p, PB)); HIPB(hipMalloc(&h->g, PB));
-    HIPB(hipMalloc(&h->p0_inj, (size_t)std::max(nd.P, nd.H) * sizeof(float)));   // injected momentum of either transition (H > P for tiny networks)
-    HIPB(hipMalloc(&h->tmp, PB + NC * (size_t)nd.H * sizeof(float)));
-    HIPB(hipMalloc(&h->eta, NC * (size_t)nd.H * sizeof(float)));
-    HIPB(hipMalloc(&h->eta_prev, NC * (size_t)nd.H * sizeof(float)));
-    HIPB(hipMalloc(&h->gd, PB)); HIPB(hipMalloc(&h->gd_cur, PB));
-    HIPB(hipMalloc(&h->logu_inj, sizeof(float)));
-    HIPB(hipMalloc(&h->sc, NC * sizeof(Scal))); HIPB(hipMalloc(&h->sc_out, NC * sizeof(Scal)));
-    HIPB(hipHostMalloc(&h->sc_host, NC * sizeof(Scal)));
-    HIPB(hipHostMalloc(&h->pin, NC * ((size_t)nd.P + nd.H) * sizeof(float), hipHostMallocMapped));
-    HIPB(hipHostGetDevicePointer((void**)&h->pin_dev, h->pin, 0));
-    HIPB(hipMemset(h->sc, 0, NC * sizeof(Scal)));
-    HIPB(hipMemset(h->q_cur, 0, PB));
-    HIPB(hipEventCreate(&h->ev0)); HIPB(hipEventCreate(&h->ev1));
-    HIPB(hipMalloc(&h->hyp_ws, NC * hyper_ws_bytes(nd)));
-    HIPB(hipMalloc(&h->ctl, NC * sizeof(StepCtl))); HIPB(hipHostMalloc(&h->ctl_host, NC * sizeof(StepCtl)));
-    HIPB(hipMalloc(&h->epsh, NC * sizeof(float))); HIPB(hipHostMalloc(&h->epsh_host, NC * sizeof(float)));
+    HIPCHK(hipStreamCreateWithFlags(&h->stream.v, hipStreamNonBlocking));
+    const size_t PN = NC * (size_t)nd.P, HN = NC * (size_t)nd.H;    // per-chain arrays: [C][P], [C][H] (one chain: [P], [H])
+    HIPCHK(h->q_cur.alloc(PN)); HIPCHK(h->g_cur.alloc(PN)); HIPCHK(h->q.alloc(PN));
+    HIPCHK(h->p.alloc(PN)); HIPCHK(h->g.alloc(PN));
+    HIPCHK(h->p0_inj.alloc((size_t)std::max(nd.P, nd.H)));   // injected momentum of either transition (H > P for tiny networks)
+    HIPCHK(h->tmp.alloc(PN + HN));
+    HIPCHK(h->eta.alloc(HN));
+    HIPCHK(h->eta_prev.alloc(HN));
+    HIPCHK(h->gd.alloc(PN)); HIPCHK(h->gd_cur.alloc(PN));
+    HIPCHK(h->logu_inj.alloc(1));
+    HIPCHK(h->sc.alloc(NC)); HIPCHK(h->sc_out.alloc(NC));
+    HIPCHK(h->sc_host.alloc(NC));
+    HIPCHK(h->pin.alloc(PN + HN, hipHostMallocMapped));
+    HIPCHK(hipHostGetDevicePointer((void**)&h->pin_dev, h->pin, 0));
+    HIPCHK(hipMemset(h->sc, 0, NC * sizeof(Scal)));
+    HIPCHK(hipMemset(h->q_cur, 0, PN * sizeof(float)));
+    HIPCHK(hipEventCreate(&h->ev0.v)); HIPCHK(hipEventCreate(&h->ev1.v));
+    HIPCHK(h->hyp_ws.alloc(NC * hyper_ws_bytes(nd) / sizeof(float)));
+    HIPCHK(h->ctl.alloc(NC)); HIPCHK(h->ctl_host.alloc(NC));
+    HIPCHK(h->epsh.alloc(NC)); HIPCHK(h->epsh_host.alloc(NC));
     std::vector<float> eta1, eta; default_eta(nd, eta1);
     for (size_t c = 0; c < NC; ++c) eta.insert(eta.end(), eta1.begin(), eta1.end());
-    HIPB(hipMemcpy(h->eta, eta.data(), eta.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->eta, eta.data(), eta.size() * sizeof(float), hipMemcpyHostToDevice));
     // fused-kernel variant
     h->want = desc->kernel;
-    { const int rc = select_kernels(h, false); if (rc) { tbnn_destroy(h); return rc; } }
+    if (const int rc = select_kernels(h, false)) return rc;
     { const char* e1 = getenv("TBNN_FAST_SINGLE"); if (e1 && atoi(e1)) h->nd.reserved_flags |= 1; }
     { const char* e2 = getenv("TBNN_MERGE_ENDS"); h->merge_ends = !(e2 && atoi(e2) == 0); }
     { const char* e3 = getenv("TBNN_TRAJ"); h->traj = !(e3 && atoi(e3) == 0); }
     const char* env = getenv("TBNN_PROFILE_FWDBWD");
     h->profile = env ? atoi(env) : 0;
-#undef HIPB
-    *out = h;
+    *out = owner.release();
     return 0;
 }
 
@@ -384,7 +395,7 @@ extern "C" int tbnn_set_profiling(tbnn_handle h, int stride) {
     if (h->profile) {                       // fill the event pool now, outside any timed loop
         HIPCHK(hipSetDevice(h->device));
         // 256 pairs: more than any tbnn_hmc_run of bench.py profiles between two drains
-        while (h->pev.size() < 512) { hipEvent_t e = nullptr; HIPCHK(hipEventCreate(&e)); h->pev.push_back(e); }
+        while (h->pev.size() < 512) { hipEvent_t e = nullptr; HIPCHK(hipEventCreate(&e)); h->pev.emplace_back(e); }
     }
     return 0;
 }
@@ -395,17 +406,15 @@ static inline bool is_wide(const tbnn_ctx* h) { return h->ops && h->ops->family 
 // (re)allocate the fused-pass workspace for n rows
 static int alloc_workspace(tbnn_ctx* h, long n) {
     const NetDev& nd = h->nd;
-    if (h->slabs) { hipFree(h->slabs); h->slabs = nullptr; }
-    if (h->pstat) { hipFree(h->pstat); h->pstat = nullptr; }
-    if (h->scratch) { hipFree(h->scratch); h->scratch = nullptr; }
-    for (float** b : {&h->wstore, &h->wslabA, &h->wslabB}) if (*b) { hipFree(*b); *b = nullptr; }
+    h->slabs.reset(); h->pstat.reset(); h->scratch.reset();
+    h->wstore.reset(); h->wslabA.reset(); h->wslabB.reset();
     int grid;
-    if (h->lstore) { hipFree(h->lstore); h->lstore = nullptr; }
+    h->lstore.reset();
     if (h->lay) {
         lay_plan_rows(nd, n, h->lplan);
         grid = h->lplan.NP;                       // entries of the statistic buffer in use; the gradient slabs: lplan.NS
         h->scratchPerWG = 0;
-        HIPCHK(hipMalloc(&h->lstore, (size_t)h->lplan.store_floats * sizeof(float)));
+        HIPCHK(h->lstore.alloc((size_t)h->lplan.store_floats));
         HIPCHK(hipMemsetAsync(h->lstore, 0, (size_t)h->lplan.store_floats * sizeof(float), h->stream));     // dz padding: written once, here
         // a_0 = the rows in block form, once per data set
         const long tot = h->lplan.ntiles * h->lplan.TK[0];
@@ -416,9 +425,9 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
         h->ops->plan(n, &h->wplan);
         grid = h->wplan.gridA;
         h->scratchPerWG = 0;
-        HIPCHK(hipMalloc(&h->wstore, h->wplan.store_floats * sizeof(float)));
-        HIPCHK(hipMalloc(&h->wslabA, h->wplan.slabA_floats * sizeof(float)));
-        HIPCHK(hipMalloc(&h->wslabB, h->wplan.slabB_floats * sizeof(float)));
+        HIPCHK(h->wstore.alloc(h->wplan.store_floats));
+        HIPCHK(h->wslabA.alloc(h->wplan.slabA_floats));
+        HIPCHK(h->wslabB.alloc(h->wplan.slabB_floats));
     } else if (h->ops) {
         grid = h->ops->grid(n);
         // test hook: a smaller grid puts small row counts into the many-rounds + cooperative-tail regime of the big ones
@@ -428,31 +437,29 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
         const long nblk = (n + GEN_RB - 1) / GEN_RB;
         grid = (int)std::min<long>(nblk, 512);
         h->scratchPerWG = generic_scratch_floats(nd);
-        HIPCHK(hipMalloc(&h->scratch, h->scratchPerWG * sizeof(float) * (size_t)grid));
+        HIPCHK(h->scratch.alloc(h->scratchPerWG * (size_t)grid));
     }
     // tbnn_forward always uses the generic forward kernel: keep a scratch for it
     h->grid = grid;
     h->pitch = (nd.P + 3) & ~3;                  // float4-readable slabs
     h->nslab = is_wide(h) ? 1 : (h->lay ? h->lplan.NS : grid);
-    HIPCHK(hipMalloc(&h->slabs, (size_t)h->C * h->nslab * h->pitch * sizeof(float)));          // [C][nslab][pitch]
-    HIPCHK(hipMemset(h->slabs, 0, (size_t)h->C * h->nslab * h->pitch * sizeof(float)));
+    const size_t slab_floats = (size_t)h->C * h->nslab * h->pitch;
+    HIPCHK(h->slabs.alloc(slab_floats));                                             // [C][nslab][pitch]
+    HIPCHK(hipMemset(h->slabs, 0, slab_floats * sizeof(float)));
     if (grid > PSTAT_CAP) return fail(-2, "grid exceeds PSTAT_CAP");
-    HIPCHK(hipMalloc(&h->pstat, (size_t)h->C * PSTAT_CAP * sizeof(double)));                   // [C][PSTAT_CAP]
+    HIPCHK(h->pstat.alloc((size_t)h->C * PSTAT_CAP));                                // [C][PSTAT_CAP]
     HIPCHK(hipMemset(h->pstat, 0, (size_t)h->C * PSTAT_CAP * sizeof(double)));      // entries >= grid stay zero
-    if (h->pstat_red) { hipFree(h->pstat_red); h->pstat_red = nullptr; }
-    HIPCHK(hipMalloc(&h->pstat_red, (size_t)PSTAT_CAP * sizeof(double)));
+    HIPCHK(h->pstat_red.alloc(PSTAT_CAP));
     HIPCHK(hipMemset(h->pstat_red, 0, (size_t)PSTAT_CAP * sizeof(double)));
-    if (h->grow) { hipFree(h->grow); h->grow = nullptr; }
-    HIPCHK(hipMalloc(&h->grow, (size_t)h->pitch * sizeof(float)));
-    if (h->shard_buf) { hipFree(h->shard_buf); h->shard_buf = nullptr; }
-    HIPCHK(hipMalloc(&h->shard_buf, ((size_t)nd.P + 1) * sizeof(double)));
+    HIPCHK(h->grow.alloc((size_t)h->pitch));
+    HIPCHK(h->shard_buf.alloc((size_t)nd.P + 1));
     return 0;
 }
 
 // new rows: the row weights (which were the old rows') are dropped, and the unweighted kernels selected again
 static int drop_row_weights(tbnn_ctx* h) {
     if (!h->dYw) return 0;
-    hipFree(h->dYw); h->dYw = nullptr; h->wsum = 0.0;
+    h->dYw.reset(); h->wsum = 0.0;
     return select_kernels(h, false);
 }
 
@@ -461,8 +468,8 @@ extern "C" int tbnn_set_data_device(tbnn_handle h, const float* dX, const float*
     if (!dX || !dY || n < 1) return fail(-1, "set_data: null pointer or n < 1");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->own_data) { hipFree(h->dX); hipFree(h->dY); h->own_data = false; }
-    h->dX = const_cast<float*>(dX); h->dY = const_cast<float*>(dY); h->n = (long)n;
+    h->Xown.reset(); h->Yown.reset();
+    h->dX = dX; h->dY = dY; h->n = (long)n;
     h->cur_valid = false;
     if (const int rc = drop_row_weights(h)) return rc;
     return alloc_workspace(h, (long)n);
@@ -473,13 +480,13 @@ extern "C" int tbnn_set_data(tbnn_handle h, const float* X, const float* Y, int6
     if (!X || !Y || n < 1) return fail(-1, "set_data: null pointer or n < 1");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->own_data) { hipFree(h->dX); hipFree(h->dY); h->own_data = false; h->dX = h->dY = nullptr; }
-    float *dX = nullptr, *dY = nullptr;
-    HIPCHK(hipMalloc(&dX, (size_t)n * h->nd.d_in * sizeof(float)));
-    HIPCHK(hipMalloc(&dY, (size_t)n * h->nd.d_out * sizeof(float)));
-    HIPCHK(hipMemcpy(dX, X, (size_t)n * h->nd.d_in * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dY, Y, (size_t)n * h->nd.d_out * sizeof(float), hipMemcpyHostToDevice));
-    h->dX = dX; h->dY = dY; h->own_data = true; h->n = (long)n;
+    if (h->Xown) { h->Xown.reset(); h->Yown.reset(); h->dX = h->dY = nullptr; }
+    const size_t nx = (size_t)n * h->nd.d_in, ny = (size_t)n * h->nd.d_out;
+    HIPCHK(h->Xown.alloc(nx));
+    HIPCHK(h->Yown.alloc(ny));
+    HIPCHK(hipMemcpy(h->Xown, X, nx * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->Yown, Y, ny * sizeof(float), hipMemcpyHostToDevice));
+    h->dX = h->Xown; h->dY = h->Yown; h->n = (long)n;
     h->cur_valid = false;
     if (const int rc = drop_row_weights(h)) return rc;
     return alloc_workspace(h, (long)n);
@@ -507,27 +514,24 @@ extern "C" int tbnn_set_row_weights(tbnn_handle h, const float* w, int64_t n) {
     }
     if (!(W > 0.0)) return fail(-1, "set_row_weights: all weights are zero");
     const size_t ny = (size_t)h->n * h->nd.d_out;
-    float* buf = nullptr;
-    HIPCHK(hipMalloc(&buf, (ny + (size_t)h->n) * sizeof(float)));
+    Buf<float> buf;
+    HIPCHK(buf.alloc(ny + (size_t)h->n));
     if (hipMemcpy(buf, h->dY, ny * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
-        hipMemcpy(buf + ny, w, (size_t)h->n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(buf);
+        hipMemcpy(buf + ny, w, (size_t)h->n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(-2, "set_row_weights: staging the weights failed");
-    }
     // the weighted kernels first: a refusal (TBNN_KERNEL_FAST and no weighted table) leaves the handle as it was -- its kernels, weights
     // and workspace; any other failure re-selects the kernels of the weights the handle keeps
     int rc = select_kernels(h, true);
     if (rc == 0) rc = alloc_workspace(h, h->n);
     if (rc) {
-        hipFree(buf);
+        buf.reset();                                   // (before the handle's own kernels and workspace are made again)
         const std::string err = g_err;
         select_kernels(h, h->dYw != nullptr);          // (the kernels of the weights the handle keeps: they were selected before)
         alloc_workspace(h, h->n);
         g_err = err;
         return rc;
     }
-    if (h->dYw) hipFree(h->dYw);
-    h->dYw = buf; h->wsum = W;
+    h->dYw = std::move(buf); h->wsum = W;
     h->cur_valid = false;
     return 0;
 }
@@ -649,7 +653,7 @@ extern "C" int tbnn_comm_count(tbnn_comm_handle c) {
 extern "C" int tbnn_comm_destroy(tbnn_comm_handle c) {
     if (!c) return 0;
     hipSetDevice(c->device);
-    if (c->gbuf) hipFree(c->gbuf);
+    c->gbuf.reset();
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     delete c;
     return 0;
@@ -660,11 +664,7 @@ extern "C" int tbnn_gather_samples(tbnn_handle h, tbnn_comm_handle c, float* d_o
     HIPCHK(hipSetDevice(h->device));
     const size_t per = (size_t)h->nd.P + h->nd.H, tot = per * c->world;
     if (!d_out) {
-        if (c->gbuf_floats < tot) {
-            if (c->gbuf) hipFree(c->gbuf);
-            c->gbuf = nullptr; c->gbuf_floats = 0;
-            HIPCHK(hipMalloc(&c->gbuf, tot * sizeof(float))); c->gbuf_floats = tot;
-        }
+        HIPCHK(c->gbuf.grow(tot, tot));
         d_out = c->gbuf;
     }
     // (theta, eta) staged contiguously in tmp (P+H floats)
@@ -716,7 +716,7 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
     const bool prof = h->profile > 0 && (h->launch_no++ % h->profile) == 0;
     if (prof) {
         if (h->pev_used + 2 > h->pev.size()) {
-            hipEventCreate(&a); hipEventCreate(&b); h->pev.push_back(a); h->pev.push_back(b);
+            hipEventCreate(&a); hipEventCreate(&b); h->pev.emplace_back(a); h->pev.emplace_back(b);
         }
         a = h->pev[h->pev_used]; b = h->pev[h->pev_used + 1]; h->pev_used += 2;
         h->pev_div.push_back(1);
@@ -829,10 +829,7 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     hipLaunchKernelGGL((k_update<UPD_COLS, UPD_GROUPS>), dim3(gx), dim3(UPD_COLS, UPD_GROUPS), 0, h->stream, nd, (int)UPD_GRAD_ONLY, 0.f, de, grad_slabs(h), grad_nslab(h),
                        h->pitch, h->q_cur, h->g_cur, const_cast<float*>(dq), h->p, h->tmp, (const int*)nullptr, (float*)nullptr, (float*)nullptr);
     // EN_TRACE leaves the chain's scalar record alone; stat comes from the slabs
-    if (!h->trace || h->trace_cap < 2) {
-        if (h->trace) hipFree(h->trace);
-        HIPCHK(hipMalloc(&h->trace, 4096 * sizeof(double))); h->trace_cap = 4096;
-    }
+    HIPCHK(h->trace.grow(2, 4096));
     hipLaunchKernelGGL(k_energy, dim3(1), dim3(1024), 0, h->stream, nd, (int)EN_TRACE, de, dq, h->p, h->q_cur, stat_ptr(h),
                        stat_entries(h), rows_total(h), h->sc, h->trace);
     HIPCHK(hipGetLastError());
@@ -870,11 +867,7 @@ static int lay_fwd_prepare(tbnn_ctx* h, const float* dX, long n, LayFwd& lf) {
     lf.pp = h->lplan; lf.n = n;
     lay_plan_rows(nd, n, lf.pp);
     const size_t need = (size_t)(lf.pp.aOff[nd.nl] + lf.pp.ntiles * 256 * lf.pp.TM[nd.nl - 1]);
-    if (h->lfwd_floats < need) {
-        if (h->lfwd) { hipFree(h->lfwd); h->lfwd = nullptr; h->lfwd_floats = 0; }
-        HIPCHK(hipMalloc(&h->lfwd, need * sizeof(float)));
-        h->lfwd_floats = need;
-    }
+    HIPCHK(h->lfwd.grow(need, need));
     lf.st = h->lfwd;
     hipLaunchKernelGGL(k_lay_pack_x, dim3((int)std::min<long>(lf.pp.ntiles * lf.pp.TK[0], 4096)), dim3(256), 0, h->stream, dX, n, nd.d_in, lf.pp.TK[0],
                        lf.pp.ntiles, lf.st + lf.pp.aOff[0]);
@@ -917,12 +910,11 @@ static int launch_forward(tbnn_ctx* h, const float* q, const float* dX, long n, 
     const long nblk = (n + GEN_RB - 1) / GEN_RB;
     const int grid = (int)std::min<long>(nblk, 512);
     const size_t per = generic_scratch_floats(nd);
-    float* scr = nullptr;
-    HIPCHK(hipMalloc(&scr, per * sizeof(float) * grid));
+    Buf<float> scr;
+    HIPCHK(scr.alloc(per * grid));
     hipLaunchKernelGGL(k_forward_generic, dim3(grid), dim3(GEN_RB), 0, h->stream, nd, q, dX, n, scr, per, dOut);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(scr);
     return 0;
 }
 
@@ -934,17 +926,14 @@ extern "C" int tbnn_forward(tbnn_handle h, const float* theta, const float* X, i
     const NetDev& nd = h->nd;
     const float* dq = h->q_cur;
     if (theta) { HIPCHK(hipMemcpyAsync(h->q, theta, (size_t)nd.P * sizeof(float), hipMemcpyHostToDevice, h->stream)); dq = h->q; h->q_img_valid = false; }
-    float *dXf = nullptr, *dOut = nullptr;
-    HIPCHK(hipMalloc(&dXf, (size_t)n * nd.d_in * sizeof(float)));
-    HIPCHK(hipMalloc(&dOut, (size_t)n * nd.d_out * sizeof(float)));
+    Buf<float> dXf, dOut;
+    HIPCHK(dXf.alloc((size_t)n * nd.d_in));
+    HIPCHK(dOut.alloc((size_t)n * nd.d_out));
     HIPCHK(hipMemcpyAsync(dXf, X, (size_t)n * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    int rc = launch_forward(h, dq, dXf, (long)n, dOut);
-    if (!rc) {
-        HIPCHK(hipMemcpyAsync(out, dOut, (size_t)n * nd.d_out * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    hipFree(dXf); hipFree(dOut);
-    return rc;
+    if (const int rc = launch_forward(h, dq, dXf, (long)n, dOut)) return rc;
+    HIPCHK(hipMemcpyAsync(out, dOut, (size_t)n * nd.d_out * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 extern "C" int tbnn_set_validation(tbnn_handle h, const float* X, const float* Y, int64_t n) {
@@ -952,10 +941,9 @@ extern "C" int tbnn_set_validation(tbnn_handle h, const float* X, const float* Y
     if (!X || !Y || n < 1) return fail(-1, "set_validation: null pointer or n < 1");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->dXv) { hipFree(h->dXv); h->dXv = nullptr; }
-    if (h->dYv) { hipFree(h->dYv); h->dYv = nullptr; }
-    HIPCHK(hipMalloc(&h->dXv, (size_t)n * h->nd.d_in * sizeof(float)));
-    HIPCHK(hipMalloc(&h->dYv, (size_t)n * h->nd.d_out * sizeof(float)));
+    h->dXv.reset(); h->dYv.reset();
+    HIPCHK(h->dXv.alloc((size_t)n * h->nd.d_in));
+    HIPCHK(h->dYv.alloc((size_t)n * h->nd.d_out));
     HIPCHK(hipMemcpy(h->dXv, X, (size_t)n * h->nd.d_in * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->dYv, Y, (size_t)n * h->nd.d_out * sizeof(float), hipMemcpyHostToDevice));
     h->nv = (long)n;
@@ -972,11 +960,7 @@ static int predict_resident(tbnn_ctx* h, int which, const float* theta, long* n_
     const float* dq = h->q_cur;
     if (theta) { HIPCHK(hipMemcpyAsync(h->q, theta, (size_t)nd.P * sizeof(float), hipMemcpyHostToDevice, h->stream)); dq = h->q; h->q_img_valid = false; }
     const size_t need = (size_t)n * nd.d_out;
-    if (h->fbuf_floats < need) {
-        if (h->fbuf) hipFree(h->fbuf);
-        h->fbuf = nullptr; h->fbuf_floats = 0;
-        HIPCHK(hipMalloc(&h->fbuf, need * sizeof(float))); h->fbuf_floats = need;
-    }
+    HIPCHK(h->fbuf.grow(need, need));
     *n_out = n;
     return launch_forward(h, dq, dX, n, h->fbuf);
 }
@@ -1002,12 +986,12 @@ extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, 
     if (!thetas || !out || m < 1 || theta_stride < nd.P) return fail(-1, "forward_many: null pointer, m < 1 or theta_stride < P");
     HIPCHK(hipSetDevice(h->device));
     const float* dX = nullptr;
-    float* dXown = nullptr;
+    Buf<float> dXown;
     long rows = 0;
     if (X) {
         if (n < 1) return fail(-1, "forward_many: n < 1");
         rows = (long)n;
-        HIPCHK(hipMalloc(&dXown, (size_t)rows * nd.d_in * sizeof(float)));
+        HIPCHK(dXown.alloc((size_t)rows * nd.d_in));
         HIPCHK(hipMemcpyAsync(dXown, X, (size_t)rows * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
         dX = dXown;
     } else {
@@ -1018,20 +1002,18 @@ extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, 
     const size_t per_net = (size_t)rows * nd.d_out;
     // networks per pass: the output chunk stays below 1 GiB
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, ((size_t)1 << 28) / std::max<size_t>(per_net, 1)));
-    float *dTh = nullptr, *dOut = nullptr, *dImg = nullptr;
+    Buf<float> dTh, dOut, dImg;
     int rc = 0;
-    auto cleanup = [&]() { if (dTh) hipFree(dTh); if (dOut) hipFree(dOut); if (dImg) hipFree(dImg); if (dXown) hipFree(dXown); };
-#define FM_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(-2, hipGetErrorString(e_)); } } while (0)
-    FM_CHK(hipMalloc(&dTh, (size_t)chunk * nd.P * sizeof(float)));
-    FM_CHK(hipMalloc(&dOut, (size_t)chunk * per_net * sizeof(float)));
+    HIPCHK(dTh.alloc((size_t)chunk * nd.P));
+    HIPCHK(dOut.alloc((size_t)chunk * per_net));
     const bool batched = narrow_fwd_ok(h);
     if (batched) {
-        FM_CHK(hipMalloc(&dImg, (size_t)chunk * h->img_floats * sizeof(float)));
-        FM_CHK(hipMemsetAsync(dImg, 0, (size_t)chunk * h->img_floats * sizeof(float), h->stream));
+        HIPCHK(dImg.alloc((size_t)chunk * h->img_floats));
+        HIPCHK(hipMemsetAsync(dImg, 0, (size_t)chunk * h->img_floats * sizeof(float), h->stream));
     }
     for (int i0 = 0; i0 < m && !rc; i0 += chunk) {
         const int c = std::min(chunk, m - i0);
-        FM_CHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
+        HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
                                 (size_t)nd.P * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
         if (batched) {
             hipLaunchKernelGGL(k_make_image, dim3((nd.P + 255) / 256, c), dim3(256), 0, h->stream, nd.P, (const float*)dTh, h->imgmap, dImg,
@@ -1046,14 +1028,12 @@ extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, 
             for (int i = 0; i < c && !rc; ++i) rc = launch_forward(h, dTh + (size_t)i * nd.P, dX, rows, dOut + (size_t)i * per_net);
         }
         if (!rc) {
-            FM_CHK(hipGetLastError());
-            FM_CHK(hipMemcpyAsync(out + (size_t)i0 * per_net, dOut, (size_t)c * per_net * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            FM_CHK(hipStreamSynchronize(h->stream));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(out + (size_t)i0 * per_net, dOut, (size_t)c * per_net * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
         }
     }
-#undef FM_CHK
     hipStreamSynchronize(h->stream);
-    cleanup();
     return rc;
 }
 
@@ -1067,7 +1047,7 @@ extern "C" int tbnn_metrics(tbnn_handle h, int which, const float* theta, float 
     int rc = predict_resident(h, which, theta, &n);
     if (rc) return rc;
     const int MB = 256;
-    if (!h->mpart) HIPCHK(hipMalloc(&h->mpart, 3 * MB * sizeof(double)));
+    HIPCHK(h->mpart.grow(3 * MB, 3 * MB));
     const long tot = n * h->nd.d_out;
     const int grid = (int)std::min<long>(MB, (tot + 255) / 256);
     hipLaunchKernelGGL(k_metrics, dim3(grid), dim3(256), 0, h->stream, (const float*)h->fbuf, (const float*)(which ? h->dYv : h->dY), n,
@@ -1106,7 +1086,7 @@ static int enqueue_transition(tbnn_ctx* h, float eps, int L, const float* d_p0, 
         hipEvent_t ea = nullptr, eb = nullptr;
         const bool prof = h->profile > 0 && (h->launch_no++ % h->profile) == 0;
         if (prof) {
-            if (h->pev_used + 2 > h->pev.size()) { hipEventCreate(&ea); hipEventCreate(&eb); h->pev.push_back(ea); h->pev.push_back(eb); }
+            if (h->pev_used + 2 > h->pev.size()) { hipEventCreate(&ea); hipEventCreate(&eb); h->pev.emplace_back(ea); h->pev.emplace_back(eb); }
             ea = h->pev[h->pev_used]; eb = h->pev[h->pev_used + 1]; h->pev_used += 2;
             h->pev_div.push_back(L);
             hipEventRecord(ea, h->stream);
@@ -1167,11 +1147,7 @@ extern "C" int tbnn_hmc_step(tbnn_handle h, float eps, int32_t L, const float* p
     if (log_u) { HIPCHK(hipMemcpyAsync(h->logu_inj, log_u, sizeof(float), hipMemcpyHostToDevice, h->stream)); d_lu = h->logu_inj; }
     double* d_trace = nullptr;
     if (trace_logp) {
-        if (h->trace_cap < L + 1) {
-            if (h->trace) hipFree(h->trace);
-            h->trace = nullptr; h->trace_cap = 0;
-            HIPCHK(hipMalloc(&h->trace, (size_t)(L + 1 + 4096) * sizeof(double))); h->trace_cap = L + 1 + 4096;
-        }
+        HIPCHK(h->trace.grow((size_t)L + 1, (size_t)L + 1 + 4096));
         d_trace = h->trace;
     }
     // the bootstrap evaluation (Q10: the reference pays it every epoch) is outside the timed events only
@@ -1190,24 +1166,22 @@ extern "C" int tbnn_hmc_step(tbnn_handle h, float eps, int32_t L, const float* p
     return 0;
 }
 
+// per-epoch records: a pooled device buffer and a pooled pinned host mirror (no allocator call -- hipFree synchronises
+// the device -- inside a caller's timed loop once the pool has grown to the largest n_epochs seen)
+static int grow_records(tbnn_ctx* h, int n_epochs) {
+    const size_t need = (size_t)n_epochs * h->C;
+    HIPCHK(h->d_recs.grow(need, std::max<size_t>(need, 64)));
+    HIPCHK(h->h_recs.grow(need, std::max<size_t>(need, 64)));
+    return 0;
+}
 extern "C" int tbnn_hmc_run(tbnn_handle h, float eps, int32_t L, int32_t n_epochs, tbnn_step_out* outs) {
     NEED(h);
     if (!h->dX) return fail(-1, "tbnn_set_data has not been called");
     if (L < 1 || n_epochs < 1) return fail(-1, "L and n_epochs must be >= 1");
     if ((long long)n_epochs * (long long)h->C > (1LL << 24)) return fail(-1, "n_epochs x chains exceeds 2^24 records per call: split the run");
     HIPCHK(hipSetDevice(h->device));
-    // per-epoch records: a pooled device buffer and a pooled pinned host mirror (no allocator call -- hipFree synchronises
-    // the device -- inside a caller's timed loop once the pool has grown to the largest n_epochs seen)
     const int C = h->C;                                  // records: [epoch][chain] on the device, outs[chain][epoch] for the caller
-    if (h->recs_cap < n_epochs * C) {
-        if (h->d_recs) hipFree(h->d_recs);
-        if (h->h_recs) hipHostFree(h->h_recs);
-        h->d_recs = nullptr; h->h_recs = nullptr; h->recs_cap = 0;
-        const int cap = std::max(n_epochs * C, 64);
-        HIPCHK(hipMalloc(&h->d_recs, (size_t)cap * sizeof(Scal)));
-        HIPCHK(hipHostMalloc(&h->h_recs, (size_t)cap * sizeof(Scal)));
-        h->recs_cap = cap;
-    }
+    if (const int rc = grow_records(h, n_epochs)) return rc;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int e = 0; e < n_epochs; ++e) {
         int rc = enqueue_transition(h, eps, L, nullptr, nullptr, nullptr, h->d_recs + (size_t)e * C);
@@ -1248,15 +1222,7 @@ extern "C" int tbnn_hmc_run_each(tbnn_handle h, const float* eps, const int32_t*
     int Lmax = 0;
     int rc = stage_ctl(h, eps, L, &Lmax);
     if (rc) return rc;
-    if (h->recs_cap < n_epochs * C) {
-        if (h->d_recs) hipFree(h->d_recs);
-        if (h->h_recs) hipHostFree(h->h_recs);
-        h->d_recs = nullptr; h->h_recs = nullptr; h->recs_cap = 0;
-        const int cap = std::max(n_epochs * C, 64);
-        HIPCHK(hipMalloc(&h->d_recs, (size_t)cap * sizeof(Scal)));
-        HIPCHK(hipHostMalloc(&h->h_recs, (size_t)cap * sizeof(Scal)));
-        h->recs_cap = cap;
-    }
+    if ((rc = grow_records(h, n_epochs))) return rc;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int e = 0; e < n_epochs; ++e) {
         rc = enqueue_transition(h, 0.f, Lmax, nullptr, nullptr, nullptr, h->d_recs + (size_t)e * C, h->ctl);
@@ -1293,7 +1259,7 @@ extern "C" int tbnn_hyper_logp_grad(tbnn_handle h, const float* eta, double* log
     HIPCHK(hipMemcpyAsync(ws.data(), h->hyp_ws, hyper_ws_bytes(nd), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(h->sc_host, h->sc_out, sizeof(Scal), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (logp) *logp = h->sc_host->logp_new;
+    if (logp) *logp = h->sc_host[0].logp_new;
     if (grad) memcpy(grad, ws.data() + HYP_WS_GRAD * nd.H, (size_t)nd.H * sizeof(float));
     return 0;
 }
@@ -1382,26 +1348,22 @@ extern "C" int tbnn_hyper_probs_many(tbnn_handle h, const int32_t* priors, const
             nd.prior[l] = priors[l];
         }
     HIPCHK(hipSetDevice(h->device));
-    float *dTh = nullptr, *dEt = nullptr; double* dOut = nullptr;
-    auto cleanup = [&]() { if (dTh) hipFree(dTh); if (dEt) hipFree(dEt); if (dOut) hipFree(dOut); };
-#define HP_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(-2, hipGetErrorString(e_)); } } while (0)
+    Buf<float> dTh, dEt; Buf<double> dOut;
     const int chunk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / (size_t)nd.P));      // <= 1 GiB of weights per pass
-    HP_CHK(hipMalloc(&dTh, (size_t)chunk * nd.P * sizeof(float)));
-    HP_CHK(hipMalloc(&dEt, (size_t)chunk * 4 * nd.nl * sizeof(float)));
-    HP_CHK(hipMalloc(&dOut, (size_t)chunk * sizeof(double)));
+    HIPCHK(dTh.alloc((size_t)chunk * nd.P));
+    HIPCHK(dEt.alloc((size_t)chunk * 4 * nd.nl));
+    HIPCHK(dOut.alloc((size_t)chunk));
     for (int i0 = 0; i0 < m; i0 += chunk) {
         const int c = std::min(chunk, m - i0);
-        HP_CHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
+        HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
                                 (size_t)nd.P * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
-        HP_CHK(hipMemcpy2DAsync(dEt, (size_t)4 * nd.nl * sizeof(float), etas + (size_t)i0 * eta_stride, (size_t)eta_stride * sizeof(float),
+        HIPCHK(hipMemcpy2DAsync(dEt, (size_t)4 * nd.nl * sizeof(float), etas + (size_t)i0 * eta_stride, (size_t)eta_stride * sizeof(float),
                                 (size_t)4 * nd.nl * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_hyper_probs, dim3(c), dim3(256), 0, h->stream, nd, (const float*)dTh, (long)nd.P, (const float*)dEt, (long)(4 * nd.nl), dOut);
-        HP_CHK(hipGetLastError());
-        HP_CHK(hipMemcpyAsync(out + i0, dOut, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HP_CHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + i0, dOut, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
     }
-#undef HP_CHK
-    cleanup();
     return 0;
 }
 
@@ -1431,14 +1393,13 @@ extern "C" int tbnn_debug_draw(tbnn_handle h, uint32_t epoch, uint32_t purpose, 
     NEED(h);
     if (n < 1 || !out_normals) return fail(-1, "debug_draw: bad arguments");
     HIPCHK(hipSetDevice(h->device));
-    float* d = nullptr;
-    HIPCHK(hipMalloc(&d, (size_t)(n + 1) * sizeof(float)));
+    Buf<float> d;
+    HIPCHK(d.alloc((size_t)n + 1));
     hipLaunchKernelGGL(k_debug_draw, dim3((n + 255) / 256), dim3(256), 0, h->stream, epoch, purpose, h->key0, h->key1, (int)n, d, d + n);
     HIPCHK(hipGetLastError());
     std::vector<float> host(n + 1);
     HIPCHK(hipMemcpyAsync(host.data(), d, (size_t)(n + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(d);
     memcpy(out_normals, host.data(), (size_t)n * sizeof(float));
     if (out_log_u) *out_log_u = host[n];
     return 0;
@@ -1450,18 +1411,15 @@ extern "C" int tbnn_debug_stamps(tbnn_handle h, uint64_t* out5) {
     NEED(h);
     if (!h->ops || h->ops != narrow_find(h->nd) || !h->dX || h->C > 1) return fail(-1, "debug_stamps: narrow fast kernel + data required");
     HIPCHK(hipSetDevice(h->device));
-    unsigned long long* d = nullptr;
-    HIPCHK(hipMalloc(&d, 16 * sizeof(unsigned long long)));
+    Buf<unsigned long long> d;
+    HIPCHK(d.alloc(16));
     HIPCHK(hipMemset(d, 0, 16 * sizeof(unsigned long long)));
     hipLaunchKernelGGL(k_make_image, dim3((h->nd.P + 255) / 256), dim3(256), 0, h->stream, h->nd.P, h->q_cur, h->imgmap, h->qimg_cur);
     for (int rep = 0; rep < 3; ++rep)
-        if (narrow_launch_stamped(h->ops, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d)) {
-            hipFree(d);
+        if (narrow_launch_stamped(h->ops, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d))
             return fail(-2, "debug_stamps: launch failed");
-        }
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out5, d, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    hipFree(d);
     return 0;
 }
 

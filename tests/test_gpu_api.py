@@ -367,13 +367,27 @@ def _free_device_bytes():
     return free.value
 
 
-def test_create_destroy_returns_device_memory(native):
-    """tbnn_destroy frees what tbnn_create / tbnn_set_data / the first transition allocated, for every kernel family and for a chain
-    group: five create-run-destroy cycles leave the device's free memory where one cycle left it"""
+def _leak_problems():
+    """one problem per kernel family: (synth_problem, the family's kernel-name prefix)"""
     cases = [([5, 50, 50, 50, 1], 20000, o.LIK_GAUSSIAN, "fast3<"), ([20, 100, 100, 2], 8000, o.LIK_BERNOULLI, "mid<"),
              ([784, 20, 20, 1], 4000, o.LIK_BERNOULLI, "tall<"), ([10, 200, 200, 200, 1], 20000, o.LIK_GAUSSIAN, "wide<"),
              ([8, 300, 300, 1], 5000, o.LIK_GAUSSIAN, "layered<"), ([3, 7, 2], 900, o.LIK_GAUSSIAN, None)]
-    probs = [(o.synth_problem(d, n, o.ACT_RELU, o.PRIOR_CAUCHY, lik), fam) for d, n, lik, fam in cases]
+    return [(o.synth_problem(d, n, o.ACT_RELU, o.PRIOR_CAUCHY, lik), fam) for d, n, lik, fam in cases]
+
+
+def _assert_cycles_return_device_memory(cycle):
+    cycle()                                    # code objects, pinned staging, the runtime's own pools
+    base = _free_device_bytes()
+    for _ in range(5):
+        cycle()
+    lost = base - _free_device_bytes()
+    assert lost <= 32 << 20, f"{lost / 2**20:.1f} MiB of device memory did not come back"
+
+
+def test_create_destroy_returns_device_memory(native):
+    """tbnn_destroy frees what tbnn_create / tbnn_set_data / the first transition allocated, for every kernel family and for a chain
+    group: five create-run-destroy cycles leave the device's free memory where one cycle left it"""
+    probs = _leak_problems()
 
     def cycle():
         for (spec, X, Y, theta, eta), fam in probs:
@@ -393,12 +407,60 @@ def test_create_destroy_returns_device_memory(native):
         grp.hmc_run(1e-6, 2, 2)
         grp.close()
 
-    cycle()                                    # code objects, pinned staging, the runtime's own pools
-    base = _free_device_bytes()
-    for _ in range(5):
-        cycle()
-    lost = base - _free_device_bytes()
-    assert lost <= 32 << 20, f"{lost / 2**20:.1f} MiB of device memory did not come back"
+    _assert_cycles_return_device_memory(cycle)
+
+
+def test_released_and_regrown_buffers_return_device_memory(native, monkeypatch):
+    """the calls that release and regrow a handle's buffers, for every kernel family: new rows (staged twice, then the caller's), new
+    validation rows, row weights set, cleared and refused, forward passes and predictions over growing row counts, ensembles over
+    staged and host rows, record and trace pools that grow, and the per-call temporaries -- five cycles leave the device's free memory
+    where one cycle left it"""
+    import ctypes
+    from tensorbnn_amd._native import TbnnError
+    hip = ctypes.CDLL("libamdhip64.so")
+    monkeypatch.setenv("TBNN_REGISTERED", "0")          # no weighted table: weights take the layered family, TBNN_KERNEL_FAST is refused
+    probs = _leak_problems()
+    rng = np.random.default_rng(0)
+
+    def to_device(a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        p = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(a.nbytes)) == 0
+        assert hip.hipMemcpy(p, a.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(a.nbytes), 1) == 0     # hipMemcpyHostToDevice
+        return p
+
+    def cycle():
+        for (spec, X, Y, theta, eta), fam in probs:
+            layers = [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
+            n = len(X)
+            ch = native.Chain(layers, likelihood=spec.likelihood, fixed_sd=spec.fixed_sd, jit=False)
+            if fam:
+                assert fam in ch.kernel_name, ch.kernel_name
+            ch.set_data(X[:n // 2], Y[:n // 2]); ch.set_data(X, Y); ch.set_state(theta); ch.set_hypers(eta)
+            ch.set_validation(X[:64], Y[:64]); ch.predict(1)
+            ch.set_validation(X[:512], Y[:512]); ch.predict(1); ch.predict(0); ch.metrics(1)
+            ch.forward(X[:100], theta); ch.forward(X, theta)
+            thetas, etas = np.tile(theta, (3, 1)), np.tile(eta, (3, 1))
+            ch.forward_many(thetas); ch.forward_many(thetas, X[:300])
+            ch.set_row_weights(rng.uniform(0.5, 1.5, n)); ch.logp_grad(theta, eta)
+            ch.set_row_weights(None); ch.logp_grad(theta, eta)
+            ch.hmc_step(1e-6, 3, trace=True); ch.hmc_step(1e-6, 4096, trace=True)
+            ch.hmc_run(1e-6, 2, 3); ch.hmc_run(1e-6, 2, 80)
+            ch.hyper_probs_many(thetas, etas)
+            ch.debug_draw(0, 0, 1000)
+            dX, dY = to_device(X), to_device(Y)
+            ch.set_data_device(dX.value, dY.value, n); ch.hmc_step(1e-6, 2)
+            ch.close()
+            assert hip.hipFree(dX) == 0 and hip.hipFree(dY) == 0
+        (spec, X, Y, theta, eta), _ = probs[0]
+        layers = [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
+        ch = native.Chain(layers, likelihood=spec.likelihood, kernel=native.KERNEL_FAST, jit=False)
+        ch.set_data(X, Y)
+        with pytest.raises(TbnnError, match="TBNN_KERNEL_FAST"):
+            ch.set_row_weights(rng.uniform(0.5, 1.5, len(X)))
+        ch.close()
+
+    _assert_cycles_return_device_memory(cycle)
 
 
 @pytest.mark.parametrize("dims", [[5, 50, 50, 50, 1], [1, 10, 10, 1]])
