@@ -227,6 +227,28 @@ int tbnn_predict(tbnn_handle h, int which, const float* theta, float* out);
  * Narrow shapes run one batched launch of the forward-only MFMA kernel (grid.y = network). */
 int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
                       int64_t n, float* out);
+/* ---- reductions over the network axis of an ensemble, on the device chunk tbnn_forward_many holds: the forward passes are the very
+ * kernels of tbnn_forward_many (every kernel family, one-chain and multi-chain handles); no host traffic but the result.  Arguments up
+ * to `n` as tbnn_forward_many's.  net_w: m importance weights (predictor.reweight) or NULL = equal; finite and >= 0 with at least one
+ * > 0, refused otherwise (the rules of tbnn_set_row_weights).  Row weights (tbnn_set_row_weights) do not enter, as in tbnn_metrics. ---- */
+enum { TBNN_XFORM_NONE = 0, TBNN_XFORM_EXP = 1, TBNN_XFORM_SIGMOID = 2, TBNN_XFORM_SOFTMAX = 3 };
+/* Posterior-predictive moments.  Per (output, row): t_i = xform(f_i) * scale + shift in fp32 (the de-normalisation of tbnn_metrics;
+ * SOFTMAX: across the row's d_out >= 2 outputs, the row maximum subtracted first); with W = sum_i w_i
+ *   mean = sum_i w_i t_i / W,  var = sum_i w_i (t_i - mean)^2 / W   (population form: np.average with weights, np.var)
+ * summed in fp64 in network order.  mean_out, var_out: host [d_out][n] doubles; var_out may be NULL. */
+int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
+                          float scale, float shift, int which, const float* X, int64_t n, double* mean_out, double* var_out);
+/* Data log-likelihood of the rows under each of the m networks, reduced both ways.  likelihood: the TBNN_LIK_* to judge under,
+ * independent of the handle's own; sd: m per-network standard deviations for the Gaussian kinds, or NULL = the descriptor's fixed_sd
+ * (clipped to [1e-8, 1e8], layer.py:60-64).  Y: host targets [n, d_out] of the rows; NULL with X NULL = the staged targets of `which`
+ * (Y with X NULL: targets for the staged rows, n must match); X without Y is refused.  Terms: the Gaussian log density per output;
+ * Bernoulli with p clipped to [1e-8, 1 - 1e-7] (likelihood.py:78-80); categorical sum_k y_k log softmax_k(f) (likelihood.py:86-107).
+ *   per_net[i]   = sum over rows and outputs of the terms under network i          (m doubles, or NULL)
+ *   lppd_rows[r] = log sum_i w_i p(y_r | theta_i) - log W, p the product over the row's outputs   (n doubles, or NULL)
+ * Both are the same bits from run to run. */
+int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                         const float* net_w, int which, const float* X, const float* Y, int64_t n, double* per_net,
+                         double* lppd_rows);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)
  *   out3[0] = mean (p-r)^2            SquaredError

@@ -21,6 +21,7 @@ ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL = 0, 1, 2, 3
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
+XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
 MAX_LAYERS = 16
 ABI_VERSION = 3          # TBNN_ABI_VERSION of include/tbnn.h
 
@@ -92,6 +93,8 @@ SYMBOLS = [
     ("tbnn_set_validation", C.c_int, [_H, _fp, _fp, C.c_int64]),
     ("tbnn_predict", C.c_int, [_H, C.c_int, _fp, _fp]),
     ("tbnn_forward_many", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int64, _fp]),
+    ("tbnn_ensemble_moments", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
+    ("tbnn_ensemble_loglik", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
     ("tbnn_hyper_probs_many", C.c_int, [_H, C.POINTER(C.c_int32), _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _dp]),
     ("tbnn_register_kernel_lib", C.c_int, [C.c_char_p]),
@@ -411,6 +414,51 @@ class Chain:
         out = np.empty((th.shape[0], self.d_out, n), dtype=np.float32)
         _check(lib.tbnn_forward_many(self._h, _p(th), th.shape[0], th.shape[1], int(which), _p(xp), n, _p(out)))
         return out
+
+    def _ensemble_args(self, thetas, X, which, weights):
+        th = np.ascontiguousarray(thetas, dtype=np.float32)
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError(f"thetas must be [m, {self.P}]")
+        if X is None:
+            n, xp = (getattr(self, "nv", 0) if which else self.n), None
+        else:
+            xp = _f32(X).reshape(-1, self.d_in)
+            n = xp.shape[0]
+        w = None if weights is None else _f32(weights).reshape(-1)
+        if w is not None and w.size != th.shape[0]:
+            raise ValueError(f"weights must be one per network ({th.shape[0]})")
+        return th, xp, n, w
+
+    def ensemble_moments(self, thetas, X=None, which: int = 1, weights=None, xform: int = XFORM_NONE, scale: float = 1.0,
+                         shift: float = 0.0, var: bool = True):
+        """posterior-predictive mean and population variance over an ensemble, reduced on the device (tbnn_ensemble_moments):
+        thetas [m, P] -> (mean, var) float64 [d_out, rows] of xform(f) * scale + shift; weights: one per network or None (equal);
+        var=False: (mean, None).  X None: the staged rows (0 train, 1 validation)"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        mean = np.empty((self.d_out, n), dtype=np.float64)
+        vr = np.empty((self.d_out, n), dtype=np.float64) if var else None
+        _check(lib.tbnn_ensemble_moments(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), float(shift), int(which),
+                                         _p(xp), n, mean.ctypes.data_as(_dp), None if vr is None else vr.ctypes.data_as(_dp)))
+        return mean, vr
+
+    def ensemble_loglik(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None):
+        """data log-likelihood of the rows under every network of an ensemble, reduced on the device (tbnn_ensemble_loglik): (per_net
+        float64 [m]: summed over rows and outputs; lppd_rows float64 [rows]: log of the weighted mixture of the networks' row likelihoods).
+        likelihood: the LIK_* to judge under (None: the chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd);
+        Y None with X None: the staged targets"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        if xp is not None and Y is None:
+            raise ValueError("rows X need their targets Y")
+        yp = None if Y is None else _f32(Y).reshape(-1, self.d_out)
+        if yp is not None and yp.shape[0] != n:
+            raise ValueError(f"Y must hold {n} rows")
+        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (th.shape[0],)))
+        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        per_net = np.empty(th.shape[0], dtype=np.float64)
+        rows = np.empty(n, dtype=np.float64)
+        _check(lib.tbnn_ensemble_loglik(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
+                                        per_net.ctypes.data_as(_dp), rows.ctypes.data_as(_dp)))
+        return per_net, rows
 
     def hyper_probs_many(self, thetas, etas, priors=None) -> np.ndarray:
         """sum over the dense layers of calculateHyperProbs for m saved networks (predictor.trainProbs / reweight):

@@ -19,6 +19,7 @@
 #include "kernels_hmc.hpp"
 #include "kernels_hyper.hpp"
 #include "kernels_layered.hpp"
+#include "kernels_ensemble.hpp"
 #include "aot_ops.hpp"
 #include <mutex>
 
@@ -977,19 +978,22 @@ extern "C" int tbnn_predict(tbnn_handle h, int which, const float* theta, float*
     return 0;
 }
 
-// Ensemble prediction (predictor.py:132-155): m networks, theta_i = thetas + i * theta_stride, over the same rows.
-// X == null: the staged rows selected by `which` (0 training, 1 validation); else n host rows.  out[m][d_out][n].
-extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
-                                 int64_t n, float* out) {
-    NEED(h);
+// The part tbnn_forward_many and the ensemble reductions share: m networks, theta_i = thetas + i * theta_stride, over the same rows.
+// X == null: the staged rows selected by `which` (0 training, 1 validation); else n host rows.  The rows are staged, the networks cut
+// into chunks whose predictions take at most chunk_floats floats, each chunk's weights (and, narrow shapes, images) built and its forward
+// passes run into dOut[c][d_out][rows] on h->stream.  begin(rows, chunk) runs once before the first chunk (the consumer's buffers),
+// each(i0, c, dOut, rows) after every chunk's forward passes are enqueued; the stream is synchronised after each chunk.
+template <class Begin, class Each>
+static int ensemble_forward(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
+                            int64_t n, size_t chunk_floats, Begin&& begin, Each&& each) {
     const NetDev& nd = h->nd;
-    if (!thetas || !out || m < 1 || theta_stride < nd.P) return fail(-1, "forward_many: null pointer, m < 1 or theta_stride < P");
+    if (!thetas || m < 1 || theta_stride < nd.P) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     HIPCHK(hipSetDevice(h->device));
     const float* dX = nullptr;
     Buf<float> dXown;
     long rows = 0;
     if (X) {
-        if (n < 1) return fail(-1, "forward_many: n < 1");
+        if (n < 1) return fail(-1, who + ": n < 1");
         rows = (long)n;
         HIPCHK(dXown.alloc((size_t)rows * nd.d_in));
         HIPCHK(hipMemcpyAsync(dXown, X, (size_t)rows * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -1000,10 +1004,10 @@ extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, 
         if (!dX || rows < 1) return fail(-1, which ? "tbnn_set_validation has not been called" : "tbnn_set_data has not been called");
     }
     const size_t per_net = (size_t)rows * nd.d_out;
-    // networks per pass: the output chunk stays below 1 GiB
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, ((size_t)1 << 28) / std::max<size_t>(per_net, 1)));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, chunk_floats / std::max<size_t>(per_net, 1)));
     Buf<float> dTh, dOut, dImg;
-    int rc = 0;
+    int rc = begin(rows, chunk);
+    if (rc) { hipStreamSynchronize(h->stream); return rc; }
     HIPCHK(dTh.alloc((size_t)chunk * nd.P));
     HIPCHK(dOut.alloc((size_t)chunk * per_net));
     const bool batched = narrow_fwd_ok(h);
@@ -1029,12 +1033,183 @@ extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, 
         }
         if (!rc) {
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(out + (size_t)i0 * per_net, dOut, (size_t)c * per_net * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
+            rc = each(i0, c, (const float*)dOut, rows);
+            if (!rc) HIPCHK(hipStreamSynchronize(h->stream));
         }
     }
     hipStreamSynchronize(h->stream);
     return rc;
+}
+// networks per pass: the chunk of predictions stays below 1 GiB
+static const size_t ENS_CHUNK_FLOATS = (size_t)1 << 28;
+// the ensemble reductions alone: TBNN_ENS_CHUNK_FLOATS (debug) cuts the chunks smaller, so that a test reaches the carry-over between
+// chunks with a small problem; tbnn_forward_many does not read it
+static size_t ens_chunk_floats() {
+    if (const char* e = getenv("TBNN_ENS_CHUNK_FLOATS")) { const long long v = atoll(e); if (v >= 1 && (size_t)v < ENS_CHUNK_FLOATS) return (size_t)v; }
+    return ENS_CHUNK_FLOATS;
+}
+
+// Ensemble prediction (predictor.py:132-155).  out[m][d_out][n].
+extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
+                                 int64_t n, float* out) {
+    NEED(h);
+    if (!out) return fail(-1, "forward_many: null pointer, m < 1 or theta_stride < P");
+    const size_t d_out = (size_t)h->nd.d_out;
+    return ensemble_forward(h, "forward_many", thetas, m, theta_stride, which, X, n, ENS_CHUNK_FLOATS, [](long, int) { return 0; },
+                            [&](int i0, int c, const float* dOut, long rows) -> int {
+                                const size_t per_net = (size_t)rows * d_out;
+                                HIPCHK(hipMemcpyAsync(out + (size_t)i0 * per_net, dOut, (size_t)c * per_net * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+                                return 0;
+                            });
+}
+
+// importance weights of the networks: the rules of tbnn_set_row_weights.  W = their sum (fp64, network order); null: equal, W = m
+static int ens_check_weights(const std::string& who, const float* net_w, int32_t m, double* W) {
+    double s = 0.0;
+    for (int32_t i = 0; i < m; ++i) {
+        if (!net_w) { s += 1.0; continue; }
+        if (!std::isfinite(net_w[i])) return fail(-1, who + ": weight " + std::to_string(i) + " is not finite");
+        if (net_w[i] < 0.f) return fail(-1, who + ": weight " + std::to_string(i) + " is negative");
+        s += (double)net_w[i];
+    }
+    if (!(s > 0.0)) return fail(-1, who + ": all weights are zero");
+    *W = s;
+    return 0;
+}
+
+static int ens_grid(long items) { return (int)std::max<long>(1, std::min<long>((items + ENS_TB - 1) / ENS_TB, 4096)); }
+
+extern "C" int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
+                                     float scale, float shift, int which, const float* X, int64_t n, double* mean_out, double* var_out) {
+    NEED(h);
+    const std::string who = "ensemble_moments";
+    const int d_out = h->nd.d_out;
+    if (!mean_out) return fail(-1, who + ": null mean_out");
+    if (xform < TBNN_XFORM_NONE || xform > TBNN_XFORM_SOFTMAX) return fail(-1, who + ": unknown transform");
+    if (xform == TBNN_XFORM_SOFTMAX && d_out < 2) return fail(-1, who + ": a softmax needs at least 2 outputs (one logit per class)");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    double W = 0.0;
+    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
+    Buf<double> acc;
+    Buf<float> dW;
+    long tot = 0;
+    int rc = ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, ens_chunk_floats(),
+        [&](long rows, int) -> int {
+            tot = rows * d_out;
+            HIPCHK(acc.alloc(3 * (size_t)tot));
+            if (net_w) {
+                HIPCHK(dW.alloc((size_t)m));
+                HIPCHK(hipMemcpyAsync(dW, net_w, (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            }
+            return 0;
+        },
+        [&](int i0, int c, const float* dOut, long rows) -> int {
+            const float* w = net_w ? dW + i0 : nullptr;
+            if (xform == TBNN_XFORM_SOFTMAX)
+                hipLaunchKernelGGL(k_ens_moments_softmax, dim3(ens_grid(rows)), dim3(ENS_TB), 0, h->stream, dOut, c, rows, d_out, scale, shift, w,
+                                   (int)(i0 == 0), (double*)acc);
+            else
+                hipLaunchKernelGGL(k_ens_moments, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, dOut, c, tot, xform, scale, shift, w, (int)(i0 == 0),
+                                   (double*)acc);
+            HIPCHK(hipGetLastError());
+            return 0;
+        });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ens_moments_finish, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, tot, W);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(mean_out, acc, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (var_out) HIPCHK(hipMemcpyAsync(var_out, acc + tot, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                                    const float* net_w, int which, const float* X, const float* Y, int64_t n, double* per_net,
+                                    double* lppd_rows) {
+    NEED(h);
+    const std::string who = "ensemble_loglik";
+    const int d_out = h->nd.d_out;
+    if (!per_net && !lppd_rows) return fail(-1, who + ": per_net and lppd_rows are both null");
+    if (likelihood < TBNN_LIK_GAUSSIAN || likelihood > TBNN_LIK_CATEGORICAL) return fail(-1, who + ": unknown likelihood");
+    if (likelihood == TBNN_LIK_CATEGORICAL && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    double W = 0.0;
+    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
+    const bool gauss = likelihood == TBNN_LIK_GAUSSIAN || likelihood == TBNN_LIK_FIXED_GAUSSIAN;
+    // per network: sigma clipped to [1e-8, 1e8] (layer.py:62), -log sigma - 1/2 log 2 pi, log w
+    std::vector<float> sig;
+    std::vector<double> cst, lw;
+    if (gauss) {
+        sig.resize((size_t)m); cst.resize((size_t)m);
+        for (int32_t i = 0; i < m; ++i) {
+            const float s = sd ? sd[i] : h->nd.fixed_sd;
+            if (std::isnan(s)) return fail(-1, who + ": sd " + std::to_string(i) + " is not a number");
+            sig[i] = std::min(std::max(s, 1e-8f), 1e8f);
+            cst[i] = -std::log((double)sig[i]) - 0.5 * std::log(2.0 * M_PI);
+        }
+    }
+    if (net_w && lppd_rows) {
+        lw.resize((size_t)m);
+        for (int32_t i = 0; i < m; ++i) lw[i] = std::log((double)net_w[i]);          // (log 0 = -inf: the network drops out of the mixture)
+    }
+    Buf<float> dSig, dY;
+    Buf<double> dCst, dLw, lse, part;
+    std::vector<double> hpart;
+    const float* dYrows = nullptr;
+    int nblk = 0;
+    long nrows = 0;
+    int rc = ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, ens_chunk_floats(),
+        [&](long rows, int chunk) -> int {
+            nrows = rows;
+            if (Y) {
+                if (n != rows) return fail(-1, who + ": n = " + std::to_string((long long)n) + " does not match the " + std::to_string(rows) + " staged rows");
+                HIPCHK(dY.alloc((size_t)rows * d_out));
+                HIPCHK(hipMemcpyAsync(dY, Y, (size_t)rows * d_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                dYrows = dY;
+            } else {
+                dYrows = which ? h->dYv : h->dY;
+                if (!dYrows) return fail(-1, who + ": no staged targets");
+            }
+            nblk = (int)((rows + ENS_TB - 1) / ENS_TB);
+            if (gauss) {
+                HIPCHK(dSig.alloc((size_t)m)); HIPCHK(dCst.alloc((size_t)m));
+                HIPCHK(hipMemcpyAsync(dSig, sig.data(), (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(hipMemcpyAsync(dCst, cst.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            }
+            if (!lw.empty()) {
+                HIPCHK(dLw.alloc((size_t)m));
+                HIPCHK(hipMemcpyAsync(dLw, lw.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            }
+            if (lppd_rows) HIPCHK(lse.alloc(2 * (size_t)rows));
+            if (per_net) {
+                HIPCHK(part.alloc((size_t)nblk * chunk));
+                hpart.resize((size_t)nblk * chunk);
+                for (int32_t i = 0; i < m; ++i) per_net[i] = 0.0;
+            }
+            return 0;
+        },
+        [&](int i0, int c, const float* dOut, long rows) -> int {
+            hipLaunchKernelGGL(k_ens_loglik, dim3(nblk), dim3(ENS_TB), 0, h->stream, dOut, c, rows, d_out, likelihood, dYrows,
+                               gauss ? (const float*)(dSig + i0) : nullptr, gauss ? (const double*)(dCst + i0) : nullptr,
+                               lw.empty() ? nullptr : (const double*)(dLw + i0), (int)(i0 == 0), (double*)lse, (double*)part);
+            HIPCHK(hipGetLastError());
+            if (per_net) {
+                // the workgroups' partial sums of this chunk, added in index order: the same bits from run to run
+                HIPCHK(hipMemcpyAsync(hpart.data(), part, (size_t)nblk * c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+                for (int b = 0; b < nblk; ++b) for (int i = 0; i < c; ++i) per_net[i0 + i] += hpart[(size_t)b * c + i];
+            }
+            return 0;
+        });
+    if (rc) return rc;
+    if (lppd_rows) {
+        hipLaunchKernelGGL(k_ens_lppd_finish, dim3(ens_grid(nrows)), dim3(ENS_TB), 0, h->stream, (double*)lse, nrows, std::log(W));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(lppd_rows, lse, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
 }
 
 extern "C" int tbnn_metrics(tbnn_handle h, int which, const float* theta, float mean, float sd, int exp_pred, int exp_real,

@@ -127,6 +127,50 @@ class predictor(object):
             out.append(np.float32(np.sum(_multivariate_log_prob(np.ones_like(cur) * sd, cur, real))))
         return out
 
+    # ---- reductions over the saved networks on the device (tbnn_ensemble_moments / tbnn_ensemble_loglik) ----
+    _TRANSFORMS = {"none": nat.XFORM_NONE, "exp": nat.XFORM_EXP, "sigmoid": nat.XFORM_SIGMOID, "softmax": nat.XFORM_SOFTMAX}
+
+    def _picked(self, n, weights):
+        picked = np.stack([self.vectors[m] for m in range(0, self.numNetworks, n)])
+        w = None if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1)
+        if w is not None and w.size != picked.shape[0]:
+            raise ValueError(f"weights must hold one value per picked network ({picked.shape[0]})")
+        return picked, w
+
+    def predictMoments(self, inputMatrix, n=1, weights=None, transform=None, sd=1.0, mean=0.0):
+        """Posterior-predictive mean and population variance of every n-th network's predictions, (mean, var) as float64 [d_out, rows],
+        reduced on the device: only the two results cross to the host.  Per value t = transform(f) * sd + mean (the de-normalisation of
+        the metrics).  transform None: softmax under a CategoricalLikelihood -- class probabilities averaged over the posterior, not
+        averaged logits -- and none otherwise; "exp" / "sigmoid" / "softmax" / "none" override.  weights: one per picked network, e.g.
+        what reweight returns."""
+        from .likelihood import CategoricalLikelihood
+        if transform is None:
+            transform = "softmax" if isinstance(self.likelihood, CategoricalLikelihood) else "none"
+        if transform not in self._TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
+        picked, w = self._picked(n, weights)
+        ch = self._ensure_chain()
+        return ch.ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=self._TRANSFORMS[transform],
+                                   scale=float(sd), shift=float(mean))
+
+    def logPredictiveDensity(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
+        """(per_network, per_row) under `likelihood` (None: the predictor's own): per_network[i] the summed log-likelihood of the rows
+        under the i-th picked network (the data term of trainProbs / reweight, in fp64), per_row[r] the log of the weighted mixture of
+        the networks' likelihoods of row r, whose sum is the log predictive density of held-out rows.  Under a GaussianLikelihood the
+        standard deviation of each network is its saved last hyper, read as _data_logprob reads it."""
+        from .likelihood import FixedGaussianLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        picked, w = self._picked(n, weights)
+        sd = None
+        if isinstance(lik, FixedGaussianLikelihood):
+            sd = np.full(picked.shape[0], np.float32(lik.sd), dtype=np.float32)                 # likelihood.py:195 (not squared)
+        elif isinstance(lik, GaussianLikelihood):
+            sd = np.array([np.float32(self.hypers[m][-1]) if len(self.hypers) else np.float32(0.1)
+                           for m in range(0, self.numNetworks, n)], dtype=np.float32)           # likelihood.py:116-117
+        ch = self._ensure_chain()
+        return ch.ensemble_loglik(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
+                                  likelihood=lik.kind, sd=sd, weights=w)
+
     def _ensure_chain(self):
         if self._chain is None:
             self._chain = nat.Chain(self._descriptor(), likelihood=nat.LIK_FIXED_GAUSSIAN, fixed_sd=1.0,

@@ -1,0 +1,60 @@
+"""Times the two routes to an ensemble's predictive moments on the GPU:
+  (a) Chain.forward_many, then np.mean / np.var in fp64 on the host (every prediction crosses to the host: 4 m d_out n bytes);
+  (b) Chain.ensemble_moments (the reduction on the device: 16 d_out n bytes cross).
+Shapes: the headline 5-50-50-50-1 with m = 256 networks over n = 100,000 rows, and the tutorial 784-20-20-1 with m = 256, n = 12,000.
+Each route: one warm-up call, then the median of five calls on a host clock -- every call returns after its stream work has completed
+(include/tbnn.h), so the clock covers the forward passes, the copies and, for (a), the host's pass.  Prints one JSON line per shape with the
+library's build id.  Needs a gfx950 device; there is no fallback."""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tensorbnn_amd import _native as nat                     # noqa: E402
+
+SHAPES = {
+    "headline": ([5, 50, 50, 50, 1], nat.ACT_RELU, nat.ACT_NONE, nat.LIK_GAUSSIAN, 256, 100_000),
+    "tutorial": ([784, 20, 20, 1], nat.ACT_RELU, nat.ACT_SIGMOID, nat.LIK_BERNOULLI, 256, 12_000),
+}
+
+
+def median_of(fn, runs=5):
+    fn()                                                   # warm-up: code objects loaded, pooled buffers grown
+    ts = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts), out
+
+
+def main():
+    if nat.device_count() < 1:
+        sys.exit("time_ensemble: no gfx950 device")
+    for name, (dims, act, last, lik, m, n) in SHAPES.items():
+        layers = [(dims[i], dims[i + 1], act if i < len(dims) - 2 else last, 0) for i in range(len(dims) - 1)]
+        ch = nat.Chain(layers, likelihood=lik)
+        rng = np.random.default_rng(0)
+        X = (rng.standard_normal((n, dims[0])) / np.sqrt(max(dims[0] / 16.0, 1.0))).astype(np.float32)
+        thetas = (rng.standard_normal((m, ch.P)) * 0.3).astype(np.float32)
+
+        def host_route():
+            f = ch.forward_many(thetas, X=X).astype(np.float64)
+            return f.mean(axis=0), f.var(axis=0)
+
+        ta, (mean_a, var_a) = median_of(host_route)
+        tb, (mean_b, var_b) = median_of(lambda: ch.ensemble_moments(thetas, X=X))
+        print(json.dumps({"shape": name, "dims": dims, "kernel": ch.kernel_name, "m": m, "n": n, "build_id": nat.build_id(),
+                          "forward_many_numpy_ms": round(ta * 1e3, 3), "ensemble_moments_ms": round(tb * 1e3, 3), "ratio": round(ta / tb, 2),
+                          "bytes_to_host": {"forward_many": 4 * m * dims[-1] * n, "ensemble_moments": 16 * dims[-1] * n},
+                          "max_abs_diff_mean": float(np.abs(mean_a - mean_b).max()), "max_abs_diff_var": float(np.abs(var_a - var_b).max())}),
+              flush=True)
+        ch.close()
+
+
+if __name__ == "__main__":
+    main()
