@@ -44,8 +44,16 @@ enum { TBNN_ACT_NONE = 0, TBNN_ACT_RELU = 1, TBNN_ACT_TANH = 2, TBNN_ACT_SIGMOID
  * GaussianDenseLayer layer.py:282 */
 enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
 /* likelihood.py:63 (Gaussian), :136 (FixedGaussian), :205 (Bernoulli); CATEGORICAL: a softmax over each row's d_out >= 2 outputs
- * (logits: the last layer carries no activation), Y one-hot or probability rows: sum_rows sum_k y_k log softmax_k(f) */
-enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3 };
+ * (logits: the last layer carries no activation), Y one-hot or probability rows: sum_rows sum_k y_k log softmax_k(f);
+ * POISSON: counts, any d_out >= 1 independent outputs, the last layer without an activation and its output f the LOG of the rate:
+ * log p(y | f) = y f - exp(f) - lgamma(y + 1) per (row, output), dL/df = y - exp(f).  Y finite and >= 0 (non-integers allowed):
+ * tbnn_set_data[_device] refuses anything else.  No likelihood hyper.  The constant C = sum_i w_i sum_k lgamma(y_ik + 1) is computed
+ * once when the data (or row weights) are staged, in fp64 and bit for bit the same from run to run; the kernels accumulate y f - exp(f)
+ * and C is subtracted where the log-probability is formed.  After tbnn_set_data_device C does not follow later in-place changes of the
+ * caller's Y (stage the data again).  A log-rate beyond the fp32 range of exp gives a non-finite log-probability: such a proposal is
+ * rejected (log_accept_ratio -inf) and the chain keeps its state.  Code 4 is not assigned: it is refused as an unknown likelihood, as
+ * before TBNN_LIK_POISSON existed. */
+enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or
@@ -75,7 +83,7 @@ typedef struct tbnn_step_out {
     int32_t n_leapfrog;        /* leapfrog steps executed (= L) */
     float log_accept_ratio;    /* TFP log_accept_ratio (non-finite -> -inf) */
     float accept_prob;         /* lar<0 ? exp(lar) : 1   network.py:410-411 */
-    double logp_old;           /* target log-prob at the start state */
+    double logp_old;           /* target log-prob at the start state (the true log-density: Poisson includes its constant C) */
     double logp_new;           /* target log-prob at the proposal */
     double kinetic_old;        /* 1/2 |p0|^2 */
     double kinetic_new;        /* 1/2 |p_L|^2 */
@@ -139,7 +147,9 @@ int tbnn_set_data_device(tbnn_handle h, const float* dX, const float* dY, int64_
  * (tbnn_set_row_shard, in either order: a weighted shard would need the weight sum of all ranks).  A refused call leaves the handle as
  * it was (its kernels and its previous weights, if any).  The weights are staged together with a COPY of the targets: after
  * tbnn_set_data_device, a weighted handle does not see later in-place changes of the caller's Y (an unweighted one reads Y live, and
- * both read X live) -- call tbnn_set_row_weights again after changing Y.  tbnn_metrics is not weighted. */
+ * both read X live) -- call tbnn_set_row_weights again after changing Y.  tbnn_metrics is not weighted.  Under TBNN_LIK_POISSON setting and
+ * clearing also recompute the constant C with the new weights (a row of weight 0 adds nothing to it); there even an UNWEIGHTED handle
+ * staged from device pointers keeps the C of the Y it was staged with. */
 int tbnn_set_row_weights(tbnn_handle h, const float* w, int64_t n);
 
 /* network.states / network.hyperStates, network.py:53-56 */
@@ -151,7 +161,8 @@ int tbnn_get_hypers(tbnn_handle h, float* eta);
 /* the target closure calculateProbs (network.py:370-392) and its gradient
  * (TF autodiff inside TFP).  theta/eta may be NULL = use the
  * handle's current state.  stat (optional) receives the data-term statistic:
- * sum((y-f)^2) for the Gaussian likelihoods, the log-likelihood for Bernoulli. */
+ * sum((y-f)^2) for the Gaussian likelihoods, the log-likelihood for Bernoulli, categorical and Poisson (logp and stat are the true
+ * log-density there: Poisson's include the constant -C, TBNN_LIK_POISSON above). */
 int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* eta, double* logp,
                    float* grad, double* stat);
 
@@ -242,7 +253,9 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
  * independent of the handle's own; sd: m per-network standard deviations for the Gaussian kinds, or NULL = the descriptor's fixed_sd
  * (clipped to [1e-8, 1e8], layer.py:60-64).  Y: host targets [n, d_out] of the rows; NULL with X NULL = the staged targets of `which`
  * (Y with X NULL: targets for the staged rows, n must match); X without Y is refused.  Terms: the Gaussian log density per output;
- * Bernoulli with p clipped to [1e-8, 1 - 1e-7] (likelihood.py:78-80); categorical sum_k y_k log softmax_k(f) (likelihood.py:86-107).
+ * Bernoulli with p clipped to [1e-8, 1 - 1e-7] (likelihood.py:78-80); categorical sum_k y_k log softmax_k(f) (likelihood.py:86-107);
+ * Poisson y f - exp(f) - lgamma(y + 1) per output in fp64, f the log-rate (the posterior mean and variance of the rate itself:
+ * tbnn_ensemble_moments with TBNN_XFORM_EXP).
  *   per_net[i]   = sum over rows and outputs of the terms under network i          (m doubles, or NULL)
  *   lppd_rows[r] = log sum_i w_i p(y_r | theta_i) - log W, p the product over the row's outputs   (n doubles, or NULL)
  * Both are the same bits from run to run. */

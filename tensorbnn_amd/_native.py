@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("TBNN_LIB") or os.path.join(_HERE, "libtbnn.so")
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
-LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL = 0, 1, 2, 3
+LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
 XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
 MAX_LAYERS = 16

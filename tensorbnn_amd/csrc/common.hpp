@@ -9,12 +9,12 @@
 #define TBNN_ACT_PACKED 0x40000000
 
 // the likelihood a fused kernel was instantiated for (kernels_fast.hpp: Shape::LIK; fused_ops.hpp: FusedOps::lik)
-enum { SHAPE_LIK_GAUSS = 0, SHAPE_LIK_BERN = 1, SHAPE_LIK_CAT = 2 };
+enum { SHAPE_LIK_GAUSS = 0, SHAPE_LIK_BERN = 1, SHAPE_LIK_CAT = 2, SHAPE_LIK_POIS = 3 };
 // flag bit of the code: the kernel scales each row's data term by its weight (tbnn_set_row_weights; kernels_fast.hpp: row_weight)
 enum { SHAPE_LIK_WEIGHTED = 4 };
 // ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
 __host__ __device__ constexpr int shape_lik(int lik) {
-    return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : SHAPE_LIK_GAUSS;
+    return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS : SHAPE_LIK_GAUSS;
 }
 
 #define TBNN_WAVE 64

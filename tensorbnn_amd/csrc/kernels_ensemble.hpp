@@ -112,6 +112,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_moments_finish(double* __restric
 //                    cst = -log sigma - 1/2 log 2 pi)
 //   Bernoulli        xlogy(y, p) + xlog1py(1 - y, -p), p = clip(f, 1e-8, 1 - 1e-7) (likelihood.py:78-80; kernels_generic.hpp)
 //   categorical      sum_k y_k (f_k - max - log sum_j exp(f_j - max)) (likelihood.py:86-107)
+//   Poisson          y f - exp(f) - lgamma(y + 1) per output, f the log-rate, in fp64 (include/tbnn.h TBNN_LIK_POISSON)
 __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restrict__ f, long n, const float* __restrict__ y, int d_out, float sigma,
                                                  double cst) {
     double l = 0.0;
@@ -126,6 +127,11 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
             t = fma((double)y[k], (double)d, t);
         }
         l = t - sy * (double)logf(s);
+    } else if (lik == TBNN_LIK_POISSON) {
+        for (int k = 0; k < d_out; ++k) {
+            const double fk = (double)f[(size_t)k * n], yk = (double)y[k];
+            l += fma(yk, fk, -exp(fk)) - lgamma(yk + 1.0);
+        }
     } else if (lik == TBNN_LIK_BERNOULLI) {
         for (int k = 0; k < d_out; ++k) {
             const float p = fminf(fmaxf(f[(size_t)k * n], 1e-8f), 1.f - 1e-7f), yk = y[k];

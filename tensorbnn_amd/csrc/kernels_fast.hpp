@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FAST_THREADS (FAST_WAVES * 64)
 
 // HACT: activation after every hidden layer, LACT: after the last layer,
-// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical; `false` / `true` still spell the first two) -- all
+// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson; `false` / `true` still spell the first two) -- all
 // compile-time so the tile body is one straight-line block the scheduler can interleave.
 // Round 6: network.add takes any sequence of layers and activations (tensorBNN/network.py:173-191) -- a stack whose hidden layers do NOT all
 // carry the same activation has HACT = TBNN_ACT_PACKED | sum_l act_l << 3 l (hidden layer l = 0 .. NL - 2; at most 9 of them: fused_ops.hpp,
@@ -40,8 +40,10 @@ struct Shape {
     static constexpr int NL = sizeof...(Ds) - 1;
     static constexpr int D[sizeof...(Ds)] = {Ds...};
     static constexpr int HCODE = HACT_, LACT = LACT_, LIK = LIK_;
-    static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT, WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0;
-    static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & 3) <= SHAPE_LIK_CAT && LIK_ < 2 * SHAPE_LIK_WEIGHTED, "unknown likelihood code");
+    static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT, POIS = (LIK_ & 3) == SHAPE_LIK_POIS,
+                          WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0;
+    static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & 3) <= SHAPE_LIK_POIS && LIK_ < 2 * SHAPE_LIK_WEIGHTED, "unknown likelihood code");
+    static_assert(!POIS || LACT_ == TBNN_ACT_NONE, "Poisson: the last layer's output is the log-rate (no last activation)");
     static_assert(!CAT || (LACT_ == TBNN_ACT_NONE && D[NL] >= 2), "categorical: logits (no last activation), at least 2 outputs");
     static_assert((HACT_ & TBNN_ACT_PACKED) == 0 || NL - 1 <= 9, "a packed activation code holds 9 hidden layers");
     static constexpr int act(int l) { return l == NL - 1 ? LACT_ : ((HACT_ & TBNN_ACT_PACKED) ? (HACT_ >> (3 * l)) & 7 : HACT_); }
@@ -609,6 +611,19 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
         } else {
             if (count) stat += (double)(t1 + t2);
             da = inside ? (yy * __builtin_amdgcn_rcpf(p) - (1.f - yy) * __builtin_amdgcn_rcpf(q)) : 0.f;
+        }
+    } else if constexpr (S::POIS) {
+        // fi is the log-rate: the term y f - e^f (its constant -lgamma(y + 1) is summed once per data staging: data_logp, kernels_hmc.hpp) and
+        // dL/df = y - e^f, with the hardware exp2 as the Bernoulli path's log2.  A log-rate past the fp32 range gives e^f = inf: the
+        // statistic is -inf (or NaN) and k_energy rejects the proposal.
+        const float mu = __expf(fi);
+        const float term = yy * fi - mu, res = yy - mu;
+        if constexpr (S::WTD) {
+            if (count) stat += (double)(wt * term);
+            da = wt * res;
+        } else {
+            if (count) stat += (double)term;
+            da = res;
         }
     } else {
         const float res = yy - fi;

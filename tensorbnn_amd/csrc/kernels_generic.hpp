@@ -14,7 +14,7 @@
 // Math restated from the reference: dense W@a+b layer.py:278, activations
 // activationFunctions.py:36/49/62, Gaussian residual likelihood.py:88-94 +
 // BNN_functions.py:23-32, Bernoulli likelihood.py:226-236, categorical (softmax over a row's outputs:
-// include/tbnn.h TBNN_LIK_CATEGORICAL); reverse mode per
+// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON); reverse mode per
 // SURVEY.md A12 (TF autodiff has no source in the tree).
 #pragma once
 #include "common.hpp"
@@ -109,6 +109,10 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
                         stat += (double)(wt * (t1 + t2));
                         da = inside ? wt * (y / p - (1.f - y) / (1.f - p)) : 0.f;
                     }
+                } else if (nd.lik == TBNN_LIK_POISSON) {
+                    // fi is the log-rate: y f - e^f (the constant -lgamma(y + 1) is the handle's: data_logp), dL/df = y - e^f; library expf
+                    const float mu = expf(fi);
+                    if (valid) { stat += (double)(wt * (y * fi - mu)); da = wt * (y - mu); }
                 } else {
                     const float r = y - fi;
                     const float wr = wt * r;

@@ -96,8 +96,10 @@ __global__ __launch_bounds__(256) void k_slab_reduce(const float* __restrict__ s
 
 // row-sharded chains: the operand of the ONE all-reduce per fused pass -- buf[0..P) = the dense gradient row as doubles
 // (row == null: k_slab_reduce has already written them), buf[P] = this rank's statistic summed over its workgroups
+// sub: what this rank takes off its statistic before the ranks are summed (Poisson: the constant C of ITS rows, so that the all-reduced
+// statistic is the full data's log-probability; 0 otherwise)
 __global__ __launch_bounds__(256) void k_shard_pack(int P, const float* __restrict__ row, const double* __restrict__ pstat, int nstat,
-                                                     double* __restrict__ buf) {
+                                                     double* __restrict__ buf, double sub) {
     __shared__ double red[4];
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (row && j < P) buf[j] = (double)row[j];
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void k_shard_pack(int P, const float* __restri
         double st = 0.0;
         for (int w = threadIdx.x; w < nstat; w += blockDim.x) st += pstat[w];
         st = block_sum(st, red);
-        if (threadIdx.x == 0) buf[P] = st;
+        if (threadIdx.x == 0) buf[P] = st - sub;
     }
 }
 __global__ __launch_bounds__(256) void k_shard_unpack(int P, const double* __restrict__ buf, float* __restrict__ row,
@@ -113,6 +115,27 @@ __global__ __launch_bounds__(256) void k_shard_unpack(int P, const double* __res
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < P) row[j] = (float)buf[j];
     if (j == 0) stat_red[0] = buf[P];
+}
+
+// Poisson targets at data staging (TBNN_LIK_POISSON): the constant C = sum_i w_i sum_k lgamma(y_ik + 1) of the log-probability, which the
+// fused kernels leave out of their statistic (no lgamma in the hot loop), and the count of targets that are not finite and >= 0 (the
+// staging call refuses the data then).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and counts out[2 b + 1]) the
+// host adds in block order: the same bits from run to run.  w: one weight per row, null: weight 1.
+#define LIKC_BLOCKS 64
+__global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y, const float* __restrict__ w, long n, int d_out,
+                                                     double* __restrict__ out) {
+    __shared__ double red[4];
+    double c = 0.0, bad = 0.0;
+    const long nel = n * d_out;
+    for (long el = (long)blockIdx.x * 256 + threadIdx.x; el < nel; el += (long)LIKC_BLOCKS * 256) {
+        const float y = Y[el];
+        if (!(y >= 0.f && y < INFINITY)) { bad += 1.0; continue; }
+        const double wt = w ? (double)w[el / d_out] : 1.0;
+        c += wt * lgamma((double)y + 1.0);
+    }
+    c = block_sum(c, red);
+    bad = block_sum(bad, red);
+    if (threadIdx.x == 0) { out[2 * blockIdx.x] = c; out[2 * blockIdx.x + 1] = bad; }
 }
 
 // plain copy (tbnn_get_state: theta into device-mapped pinned host memory)
@@ -131,8 +154,10 @@ __global__ __launch_bounds__(256) void k_make_image(int P, const float* __restri
     if (j < P) { const float v = q[j]; qimg[imgmap[j]] = v; const int m1 = imgmap[P + j]; if (m1 >= 0) qimg[m1] = v; }
 }
 
-// data-term log-likelihood from the reduced statistic; n: the rows that normalise the Gaussian (their count, or W = sum of the row weights)
-__device__ __forceinline__ double data_logp(const NetDev& nd, const float* __restrict__ eta, double stat, double n) {
+// data-term log-likelihood from the reduced statistic; n: the rows that normalise the Gaussian (their count, or W = sum of the row weights);
+// lik_c: Poisson's constant C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (tbnn_api.hip: stage_lik_const; 0 otherwise)
+__device__ __forceinline__ double data_logp(const NetDev& nd, const float* __restrict__ eta, double stat, double n, double lik_c) {
+    if (nd.lik == TBNN_LIK_POISSON) return stat - lik_c;                                   // the statistic is sum w (y f - e^f)
     if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
     // multivariateLogProb with sigma broadcast to [n, d_out] (likelihood.py:92, BNN_functions.py:25-32)
     const double s = (double)lik_sigma(nd, eta);
@@ -212,7 +237,7 @@ enum { EN_CUR = 0, EN_NEW = 1, EN_TRACE = 2, EN_REFRESH = 3 };   // EN_REFRESH: 
 __global__ __launch_bounds__(1024) void k_energy(
     NetDev nd, int which, const float* __restrict__ eta, const float* __restrict__ q,
     const float* __restrict__ p, const float* q_cur,              // (no restrict: the merged commit writes the same array)
-    const double* __restrict__ partial_stat, int nslab, double n,
+    const double* __restrict__ partial_stat, int nslab, double n, double lik_c,
     Scal* __restrict__ sc, double* __restrict__ trace_slot,
     // EN_NEW with commit_out: the transition's end in this one launch -- the record for the host (k_commit_scal) and, when
     // accepted, cur <- proposal (k_commit: q, g, gd); two launches fewer per transition
@@ -257,7 +282,7 @@ __global__ __launch_bounds__(1024) void k_energy(
     if (threadIdx.x != 0 && !commit) return;
     if (threadIdx.x == 0) {
         if (which == EN_REFRESH) { st = sc->stat_cur; which = EN_CUR; }
-        const double lp = pr + data_logp(nd, eta, st, n);
+        const double lp = pr + data_logp(nd, eta, st, n, lik_c);
         if (which == EN_TRACE) { *trace_slot = lp; return; }
         if (which == EN_CUR) {
             sc->stat_cur = st; sc->prior_cur = pr; sc->logp_cur = lp;

@@ -356,8 +356,15 @@ __device__ __forceinline__ float lay_bernoulli(float fi, float y, double& stat, 
     stat += (double)(wt * (t1 + t2));
     return inside ? wt * (y * __builtin_amdgcn_rcpf(p) - (1.f - y) * __builtin_amdgcn_rcpf(q)) : 0.f;
 }
+// Poisson likelihood (TBNN_LIK_POISSON) of one (row, output) element, fi the log-rate: adds wt (y f - e^f) to stat (the constant
+// -lgamma(y + 1) is the handle's: data_logp, kernels_hmc.hpp), returns wt (y - e^f); the hardware exp2, as lik_delta (kernels_fast.hpp)
+__device__ __forceinline__ float lay_poisson(float fi, float y, double& stat, float wt) {
+    const float mu = __expf(fi);
+    stat += (double)(wt * (y * fi - mu));
+    return wt * (y - mu);
+}
 
-// likelihood (restated as in kernels_generic.hpp): statistic (Gaussian: sum of squared residuals; Bernoulli, categorical: log-prob) and
+// likelihood (restated as in kernels_generic.hpp): statistic (Gaussian: sum of squared residuals; Bernoulli, categorical, Poisson: log-prob) and
 // dz of the last layer = dL/df * act'(f).  f, dz: blocks [row tile][TMl][16][16]; one thread per data row.  Only the real
 // (row, output) entries of dz are written: the padding was zeroed when the store was allocated and nothing else writes it.
 // wrow: one weight per row (tbnn_set_row_weights), null: weight 1 -- a row's residual / term and its dz are scaled by it before any sum.
@@ -407,6 +414,8 @@ __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restr
             float da;
             if (nd.lik == TBNN_LIK_BERNOULLI) {
                 da = lay_bernoulli(fi, y, stat, wt);
+            } else if (nd.lik == TBNN_LIK_POISSON) {
+                da = lay_poisson(fi, y, stat, wt);
             } else {
                 const float res = y - fi;                                   // likelihood.py:88-94
                 const float wr = wt * res;
@@ -613,6 +622,8 @@ __global__ __launch_bounds__(256) void k_lay_tail(NetDev nd, LayPlan p, const fl
                         float da;
                         if (nd.lik == TBNN_LIK_BERNOULLI) {
                             da = lay_bernoulli(fi, y, stat, wt);
+                        } else if (nd.lik == TBNN_LIK_POISSON) {
+                            da = lay_poisson(fi, y, stat, wt);
                         } else {
                             const float res = y - fi;                                  // likelihood.py:88-94
                             const float wr = wt * res;
@@ -741,6 +752,8 @@ __global__ __launch_bounds__(256) void k_lay_last(NetDev nd, LayPlan p, const fl
                     float da;
                     if (nd.lik == TBNN_LIK_BERNOULLI) {
                         da = lay_bernoulli(fi, y, stat, wt);
+                    } else if (nd.lik == TBNN_LIK_POISSON) {
+                        da = lay_poisson(fi, y, stat, wt);
                     } else {
                         const float res = y - fi;                                  // likelihood.py:88-94
                         const float wr = wt * res;

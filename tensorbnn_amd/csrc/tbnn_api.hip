@@ -101,6 +101,8 @@ struct tbnn_ctx {
     // row weights (tbnn_set_row_weights): [n x d_out targets | n weights] in one buffer -- what the kernels read as Y while weights are
     // set (kernels_fast.hpp: row_weight) -- and W = their sum in fp64; null / 0: none
     Buf<float> dYw; double wsum = 0.0;
+    // TBNN_LIK_POISSON: C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (stage_lik_const; all chains share it); 0 otherwise
+    double lik_c = 0.0;
     int want = TBNN_KERNEL_AUTO;          // tbnn_net_desc::kernel (the re-selection of tbnn_set_row_weights follows it)
     // validation data (network.py:47-51) and the prediction buffer of tbnn_predict / tbnn_metrics
     Buf<float> dXv, dYv; long nv = 0;
@@ -155,6 +157,9 @@ extern "C" int tbnn_device_count(void) {
     return n;
 }
 
+// the TBNN_LIK_* values (4 is not one of them: include/tbnn.h)
+static bool lik_known(int lik) { return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON; }
+
 static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
     if (!d || !d->layers) return fail(-1, "null descriptor");
     if (d->n_layers < 1 || d->n_layers > TBNN_MAX_LAYERS) return fail(-1, "n_layers must be in [1,16]");
@@ -173,7 +178,9 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
         nd.actOff[l] = so; so += L.out_dim;
         mw = std::max(mw, std::max(L.in_dim, L.out_dim));
     }
-    if (d->likelihood < TBNN_LIK_GAUSSIAN || d->likelihood > TBNN_LIK_CATEGORICAL) return fail(-1, "unknown likelihood");
+    if (!lik_known(d->likelihood)) return fail(-1, "unknown likelihood");
+    if (d->likelihood == TBNN_LIK_POISSON && nd.act[nd.nl - 1] != TBNN_ACT_NONE)
+        return fail(-1, "the Poisson likelihood takes the last layer's outputs as log-rates (log link): the last layer must carry no activation");
     if (d->likelihood == TBNN_LIK_CATEGORICAL) {
         if (nd.out[nd.nl - 1] < 2) return fail(-1, "the categorical likelihood needs at least 2 outputs (one logit per class)");
         if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
@@ -457,6 +464,27 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
     return 0;
 }
 
+// Poisson (TBNN_LIK_POISSON; any other likelihood: C = 0, nothing runs): the constant C of the n rows dY (device) under the row weights dw
+// (device, null: none) -- k_pois_const, its partials added here in block order -- and the refusal of targets that are not counts.  Called
+// by everything that stages rows or weights BEFORE it changes the handle: a refusal leaves the handle as it was.
+static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY, const float* dw, long n, double* C) {
+    *C = 0.0;
+    if (h->nd.lik != TBNN_LIK_POISSON) return 0;
+    Buf<double> part;
+    HIPCHK(part.alloc(2 * LIKC_BLOCKS));
+    hipLaunchKernelGGL(k_pois_const, dim3(LIKC_BLOCKS), dim3(256), 0, h->stream, dY, dw, n, h->nd.d_out, (double*)part);
+    HIPCHK(hipGetLastError());
+    double host[2 * LIKC_BLOCKS];
+    HIPCHK(hipMemcpyAsync(host, part, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double c = 0.0, bad = 0.0;
+    for (int b = 0; b < LIKC_BLOCKS; ++b) { c += host[2 * b]; bad += host[2 * b + 1]; }
+    if (bad > 0.0)
+        return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are negative or not finite: the Poisson likelihood takes counts (finite, >= 0)");
+    *C = c;
+    return 0;
+}
+
 // new rows: the row weights (which were the old rows') are dropped, and the unweighted kernels selected again
 static int drop_row_weights(tbnn_ctx* h) {
     if (!h->dYw) return 0;
@@ -469,8 +497,10 @@ extern "C" int tbnn_set_data_device(tbnn_handle h, const float* dX, const float*
     if (!dX || !dY || n < 1) return fail(-1, "set_data: null pointer or n < 1");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
+    double C = 0.0;
+    if (const int rc = stage_lik_const(h, "set_data", dY, nullptr, (long)n, &C)) return rc;
     h->Xown.reset(); h->Yown.reset();
-    h->dX = dX; h->dY = dY; h->n = (long)n;
+    h->dX = dX; h->dY = dY; h->n = (long)n; h->lik_c = C;
     h->cur_valid = false;
     if (const int rc = drop_row_weights(h)) return rc;
     return alloc_workspace(h, (long)n);
@@ -481,13 +511,24 @@ extern "C" int tbnn_set_data(tbnn_handle h, const float* X, const float* Y, int6
     if (!X || !Y || n < 1) return fail(-1, "set_data: null pointer or n < 1");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->Xown) { h->Xown.reset(); h->Yown.reset(); h->dX = h->dY = nullptr; }
     const size_t nx = (size_t)n * h->nd.d_in, ny = (size_t)n * h->nd.d_out;
+    double C = 0.0;
+    Buf<float> newY;
+    if (h->nd.lik == TBNN_LIK_POISSON) {
+        // the targets are staged and judged first: refused ones leave the handle with the rows it had
+        HIPCHK(newY.alloc(ny));
+        HIPCHK(hipMemcpy(newY, Y, ny * sizeof(float), hipMemcpyHostToDevice));
+        if (const int rc = stage_lik_const(h, "set_data", newY, nullptr, (long)n, &C)) return rc;
+    }
+    if (h->Xown) { h->Xown.reset(); h->Yown.reset(); h->dX = h->dY = nullptr; }
     HIPCHK(h->Xown.alloc(nx));
-    HIPCHK(h->Yown.alloc(ny));
     HIPCHK(hipMemcpy(h->Xown, X, nx * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->Yown, Y, ny * sizeof(float), hipMemcpyHostToDevice));
-    h->dX = h->Xown; h->dY = h->Yown; h->n = (long)n;
+    if (newY) h->Yown = std::move(newY);
+    else {
+        HIPCHK(h->Yown.alloc(ny));
+        HIPCHK(hipMemcpy(h->Yown, Y, ny * sizeof(float), hipMemcpyHostToDevice));
+    }
+    h->dX = h->Xown; h->dY = h->Yown; h->n = (long)n; h->lik_c = C;
     h->cur_valid = false;
     if (const int rc = drop_row_weights(h)) return rc;
     return alloc_workspace(h, (long)n);
@@ -503,6 +544,9 @@ extern "C" int tbnn_set_row_weights(tbnn_handle h, const float* w, int64_t n) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (!w) {
+        double C = 0.0;
+        if (const int rc = stage_lik_const(h, "set_row_weights", h->dY, nullptr, h->n, &C)) return rc;
+        h->lik_c = C; h->cur_valid = false;               // (a cached logp_cur carries the constant it was formed with)
         if (const int rc = drop_row_weights(h)) return rc;
         return alloc_workspace(h, h->n);
     }
@@ -520,6 +564,8 @@ extern "C" int tbnn_set_row_weights(tbnn_handle h, const float* w, int64_t n) {
     if (hipMemcpy(buf, h->dY, ny * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
         hipMemcpy(buf + ny, w, (size_t)h->n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(-2, "set_row_weights: staging the weights failed");
+    double C = 0.0;
+    if (const int rc = stage_lik_const(h, "set_row_weights", buf, buf + ny, h->n, &C)) return rc;
     // the weighted kernels first: a refusal (TBNN_KERNEL_FAST and no weighted table) leaves the handle as it was -- its kernels, weights
     // and workspace; any other failure re-selects the kernels of the weights the handle keeps
     int rc = select_kernels(h, true);
@@ -532,7 +578,7 @@ extern "C" int tbnn_set_row_weights(tbnn_handle h, const float* w, int64_t n) {
         g_err = err;
         return rc;
     }
-    h->dYw = std::move(buf); h->wsum = W;
+    h->dYw = std::move(buf); h->wsum = W; h->lik_c = C;
     h->cur_valid = false;
     return 0;
 }
@@ -689,6 +735,9 @@ extern "C" int tbnn_set_row_shard(tbnn_handle h, tbnn_comm_handle c, int64_t n_t
 }
 // rows that normalise the likelihood (the sum of the row weights when they are set) / entries of the statistic buffer to sum
 static inline double rows_total(const tbnn_ctx* h) { return h->dYw ? h->wsum : (double)(h->shard ? h->n_total : h->n); }
+// Poisson's constant as data_logp takes it off the statistic; a row-sharded chain's statistic arrives without it: every rank took the C
+// of its own rows off before the all-reduce (k_shard_pack), so all ranks hold the same full-data value and take the same decisions
+static inline double lik_const(const tbnn_ctx* h) { return h->shard ? 0.0 : h->lik_c; }
 // the targets the fused pass reads (with the row weights behind them when they are set) and the weights alone (null: none)
 static inline const float* pass_Y(const tbnn_ctx* h) { return h->dYw ? h->dYw : h->dY; }
 static inline const float* pass_w(const tbnn_ctx* h) { return h->dYw ? h->dYw + (size_t)h->n * h->nd.d_out : nullptr; }
@@ -761,7 +810,7 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
             hipLaunchKernelGGL(k_slab_reduce, dim3((P + 63) / 64), dim3(64, 4), 0, h->stream, (const float*)h->slabs, h->nslab,
                                h->pitch, P, (float*)nullptr, h->shard_buf);
         hipLaunchKernelGGL(k_shard_pack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, is_wide(h) ? (const float*)row : (const float*)nullptr,
-                           (const double*)h->pstat, h->grid, h->shard_buf);
+                           (const double*)h->pstat, h->grid, h->shard_buf, h->lik_c);
         NCCLCHK(g_rccl.AllReduce(h->shard_buf, h->shard_buf, (size_t)P + 1, ncclDouble, ncclSum, h->shard->comm, h->stream));
         hipLaunchKernelGGL(k_shard_unpack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, (const double*)h->shard_buf, row, h->pstat_red);
     }
@@ -786,7 +835,7 @@ static void launch_update(tbnn_ctx* h, int mode, float eps, const float* eta, fl
 }
 static void launch_energy(tbnn_ctx* h, int which, const float* eta, const float* q, double* slot) {
     hipLaunchKernelGGL(k_energy, dim3(1, h->C), dim3(1024), 0, h->stream, h->nd, which, eta, q, h->p, h->q_cur, stat_ptr(h),
-                       stat_entries(h), rows_total(h), h->sc, slot);
+                       stat_entries(h), rows_total(h), lik_const(h), h->sc, slot);
 }
 
 // make (logp, grad, stat) at q_cur valid
@@ -832,7 +881,7 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     // EN_TRACE leaves the chain's scalar record alone; stat comes from the slabs
     HIPCHK(h->trace.grow(2, 4096));
     hipLaunchKernelGGL(k_energy, dim3(1), dim3(1024), 0, h->stream, nd, (int)EN_TRACE, de, dq, h->p, h->q_cur, stat_ptr(h),
-                       stat_entries(h), rows_total(h), h->sc, h->trace);
+                       stat_entries(h), rows_total(h), lik_const(h), h->sc, h->trace);
     HIPCHK(hipGetLastError());
     double lp = 0.0;
     HIPCHK(hipMemcpyAsync(&lp, h->trace, sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -842,7 +891,7 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->profile) drain_profile(h);
     if (logp) *logp = lp;
-    if (stat) { double s = 0; for (double v : ps) s += v; *stat = s; }
+    if (stat) { double s = 0; for (double v : ps) s += v; *stat = s - lik_const(h); }      // (Poisson: the log-likelihood with its constant)
     return 0;
 }
 
@@ -1130,7 +1179,7 @@ extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t 
     const std::string who = "ensemble_loglik";
     const int d_out = h->nd.d_out;
     if (!per_net && !lppd_rows) return fail(-1, who + ": per_net and lppd_rows are both null");
-    if (likelihood < TBNN_LIK_GAUSSIAN || likelihood > TBNN_LIK_CATEGORICAL) return fail(-1, who + ": unknown likelihood");
+    if (!lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
     if (likelihood == TBNN_LIK_CATEGORICAL && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
     if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
     if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
@@ -1287,7 +1336,7 @@ static int enqueue_transition(tbnn_ctx* h, float eps, int L, const float* d_p0, 
     // workgroup copies in a few trips (TBNN_MERGE_ENDS=0: three launches, as before round 3)
     if (h->merge_ends && nd.P <= 32768) {
         hipLaunchKernelGGL(k_energy, dim3(1, h->C), dim3(1024), 0, h->stream, h->nd, (int)EN_NEW, (const float*)h->eta, (const float*)h->q, (const float*)h->p,
-                           (const float*)h->q_cur, stat_ptr(h), stat_entries(h), rows_total(h), h->sc, d_trace ? d_trace + L : (double*)nullptr,
+                           (const float*)h->q_cur, stat_ptr(h), stat_entries(h), rows_total(h), lik_const(h), h->sc, d_trace ? d_trace + L : (double*)nullptr,
                            d_out, (const float*)h->g, h->q_cur, h->g_cur, (const float*)h->gd, h->gd_cur);
     } else {
         launch_energy(h, EN_NEW, h->eta, h->q, d_trace ? d_trace + L : nullptr);
@@ -1500,7 +1549,7 @@ static int hyper_step_impl(tbnn_handle h, float eps_h, const float* eps_each, in
                                (const float*)h->eta, (const float*)h->q_cur, (const float*)h->gd_cur, h->g_cur, gate);
             hipLaunchKernelGGL(k_energy, dim3(1, C), dim3(1024), 0, h->stream, nd, (int)EN_REFRESH, (const float*)h->eta,
                                (const float*)h->q_cur, (const float*)h->p, (const float*)h->q_cur,
-                               stat_ptr(h), stat_entries(h), rows_total(h), h->sc, (double*)nullptr,
+                               stat_ptr(h), stat_entries(h), rows_total(h), lik_const(h), h->sc, (double*)nullptr,
                                (Scal*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, (float*)nullptr, gate);
             HIPCHK(hipGetLastError());
         }

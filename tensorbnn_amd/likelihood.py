@@ -108,3 +108,23 @@ class CategoricalLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+class PoissonLikelihood(Likelihood):
+    """Count data: the last dense layer's outputs, with no activation after it, are the LOGS of the rates (log link), one independent
+    rate per output, and the data term is sum over (row, output) of y f - exp(f) - lgamma(y + 1) for targets y >= 0 (non-integers
+    allowed; include/tbnn.h TBNN_LIK_POISSON).  No hyper-parameter."""
+    kind = nat.LIK_POISSON
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.mainProbsInHypers = False
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """y f - exp(f) - lgamma(y + 1) per (output, row) in float64, [d_out, rows] as BernoulliLikelihood's; the sum is the data term"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [d_out, rows]: log-rates
+        y = np.asarray(kwargs["realVals"], dtype=np.float64).reshape(-1, f.shape[0]).T
+        return y * f - np.exp(f) - np.vectorize(math.lgamma, otypes=[np.float64])(y + 1.0)
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

@@ -106,7 +106,7 @@ class predictor(object):
     def _data_logprob(self, likelihood, trainX, trainY, n):
         """summed log-likelihood of the training rows under every n-th network (see the module docstring)"""
         from .layer import _multivariate_log_prob
-        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, log_softmax
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, PoissonLikelihood, log_softmax
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
@@ -115,6 +115,10 @@ class predictor(object):
             real = y.reshape(cur.shape)
             if isinstance(likelihood, CategoricalLikelihood):
                 out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
+                continue
+            if isinstance(likelihood, PoissonLikelihood):
+                terms = likelihood.makeResponseLikelihood(None, predict=lambda *_a, _f=cur.T: _f, realVals=real)
+                out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1)
                 continue
             if isinstance(likelihood, BernoulliLikelihood):
                 out.append(np.float32(0))                                       # likelihood.py:239-243
@@ -137,21 +141,27 @@ class predictor(object):
             raise ValueError(f"weights must hold one value per picked network ({picked.shape[0]})")
         return picked, w
 
-    def predictMoments(self, inputMatrix, n=1, weights=None, transform=None, sd=1.0, mean=0.0):
+    def predictMoments(self, inputMatrix, n=1, weights=None, transform=None, sd=1.0, mean=0.0, countVariance=False):
         """Posterior-predictive mean and population variance of every n-th network's predictions, (mean, var) as float64 [d_out, rows],
         reduced on the device: only the two results cross to the host.  Per value t = transform(f) * sd + mean (the de-normalisation of
         the metrics).  transform None: softmax under a CategoricalLikelihood -- class probabilities averaged over the posterior, not
-        averaged logits -- and none otherwise; "exp" / "sigmoid" / "softmax" / "none" override.  weights: one per picked network, e.g.
-        what reweight returns."""
-        from .likelihood import CategoricalLikelihood
+        averaged logits --, exp under a PoissonLikelihood -- the posterior mean and variance of the RATE -- and none otherwise; "exp" /
+        "sigmoid" / "softmax" / "none" override.  weights: one per picked network, e.g. what reweight returns.  countVariance (with the
+        exp transform, sd = 1, mean = 0): the second array is the total predictive variance of a COUNT, E[rate] + Var[rate] (the Poisson
+        noise plus the posterior spread of the rate), added on the host to the two arrays the device returns."""
+        from .likelihood import CategoricalLikelihood, PoissonLikelihood
         if transform is None:
-            transform = "softmax" if isinstance(self.likelihood, CategoricalLikelihood) else "none"
+            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
+                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
+        if countVariance and (transform != "exp" or float(sd) != 1.0 or float(mean) != 0.0):
+            raise ValueError("countVariance needs the rate itself: transform 'exp' (the default under a PoissonLikelihood), sd = 1, mean = 0")
         if transform not in self._TRANSFORMS:
             raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
         picked, w = self._picked(n, weights)
         ch = self._ensure_chain()
-        return ch.ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=self._TRANSFORMS[transform],
+        m, v = ch.ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=self._TRANSFORMS[transform],
                                    scale=float(sd), shift=float(mean))
+        return (m, m + v) if countVariance else (m, v)
 
     def logPredictiveDensity(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
         """(per_network, per_row) under `likelihood` (None: the predictor's own): per_network[i] the summed log-likelihood of the rows
