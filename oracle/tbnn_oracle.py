@@ -29,6 +29,14 @@ the arithmetic: ``np.float32`` mimics the reference op by op (it computes in
 tf.float32 everywhere: Examples/trainRegression.py:41, layer.py:116,
 paramAdapter.py:60); ``np.float64`` is the high-precision arm used to bound
 rounding error.
+
+EXTENSIONS BEYOND THE REFERENCE.  The categorical and Poisson likelihoods and
+the per-row likelihood weights ``w`` are the library's own (definitions:
+``include/tbnn.h`` TBNN_LIK_CATEGORICAL / TBNN_LIK_POISSON /
+tbnn_set_row_weights, ``tensorbnn_amd/likelihood.py``): there are no reference
+lines to cite, and torch.autograd alone pins them (tests/test_oracle.py).  Their
+docstrings say "extension".  With ``w=None`` the Gaussian, fixed-sd Gaussian
+and Bernoulli paths are the reference's, operation by operation.
 """
 from __future__ import annotations
 
@@ -46,6 +54,8 @@ import numpy as np
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
+LIK_CATEGORICAL, LIK_POISSON = 3, 5       # extensions: include/tbnn.h TBNN_LIK_* (4 is unassigned)
+LIKELIHOODS = (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON)
 
 
 @dataclass
@@ -243,31 +253,77 @@ def likelihood_sigma(spec: NetSpec, eta, dtype=np.float32):
     or the fixed sd un-squared (likelihood.py:162)."""
     if spec.likelihood == LIK_GAUSSIAN:
         return dtype(np.asarray(eta, dtype=dtype)[-1] ** 2)
-    return dtype(spec.fixed_sd)
+    if spec.likelihood == LIK_FIXED_GAUSSIAN:
+        return dtype(spec.fixed_sd)
+    raise ValueError(spec.likelihood)
 
 
-def log_likelihood(spec: NetSpec, eta, f, Y, dtype=np.float32):
+lgamma = np.vectorize(math.lgamma, otypes=[np.float64])
+
+
+def _poisson_terms(f, Y, dtype, w):
+    """(sum_i w_i sum_k (y f - exp f) in ``dtype``, C = sum_i w_i sum_k lgamma(y + 1) in fp64 whatever ``dtype`` is: the library
+    computes C once per data staging, in fp64 -- include/tbnn.h TBNN_LIK_POISSON)."""
+    y = np.asarray(Y, dtype=dtype).reshape(f.shape[1], -1).T         # [d_out, n]
+    t = y * f - np.exp(f)
+    lg = lgamma(y.astype(np.float64) + 1.0)
+    if w is not None:
+        w = np.asarray(w, dtype=dtype)
+        t, lg = w * t, w.astype(np.float64) * lg
+    return np.sum(t, dtype=dtype), np.sum(lg)
+
+
+def _log_softmax(f):
+    """log softmax over the outputs of each row of f[K, n], shifted by the row's max."""
+    z = f - f.max(axis=0, keepdims=True)
+    return z - np.log(np.exp(z).sum(axis=0, keepdims=True))
+
+
+def log_likelihood(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
     """makeResponseLikelihood summed (network.py:388-391): Gaussian
-    likelihood.py:69-96, fixed :143-169, Bernoulli :210-237.  f is [d_out,n]."""
+    likelihood.py:69-96, fixed :143-169, Bernoulli :210-237.  f is [d_out,n].
+
+    Extensions (no reference lines; include/tbnn.h, tensorbnn_amd/likelihood.py):
+    categorical: sum_k y_k (f_k - m - log sum_j exp(f_j - m)), m the row's max, labels one-hot or soft;
+    Poisson: y f - exp(f) - lgamma(y + 1), returned in fp64 in either arm (it carries the fp64 constant);
+    ``w``: one weight >= 0 per row (None = 1) scales the row's term before the sum, and a Gaussian row counts w_i times
+    (the row count becomes sum w)."""
     dt = dtype
     f = np.asarray(f, dtype=dt)
+    if w is not None:
+        w = np.asarray(w, dtype=dt)
     if spec.likelihood in (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN):
         cur = f.T                                                   # :91
-        sigma = np.ones_like(cur) * likelihood_sigma(spec, eta, dt)  # :92
         real = np.asarray(Y, dtype=dt).reshape(cur.shape)           # :93
+        if w is not None:                                           # extension: the closed form of :94 with weighted rows
+            s = min(max(likelihood_sigma(spec, eta, dt), dt(1e-8)), dt(1e8))
+            n_el = np.sum(w, dtype=dt) * dt(cur.shape[1])
+            S = np.sum(w[:, None] * ((real - cur) / s) ** 2, dtype=dt)
+            return dt(-0.5) * (dt(2) * n_el * np.log(s) + S + n_el * np.log(dt(2 * math.pi)))
+        sigma = np.ones_like(cur) * likelihood_sigma(spec, eta, dt)  # :92
         return multivariate_log_prob(sigma, cur, real, dt)          # :94
-    # Bernoulli: clip :226-231; tfd.Bernoulli(probs).log_prob(y) =
-    # xlogy(y,p) + xlog1py(1-y,-p) (TFP 0.12 bernoulli.py _log_prob)
-    p = np.clip(f, dt(1e-8), dt(1 - 1e-7)).astype(dt)
-    y = np.asarray(Y, dtype=dt).reshape(-1, f.shape[0]).T           # :236 transpose(realVals)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t1 = np.where(y == 0, dt(0), y * np.log(p))
-        t2 = np.where((dt(1) - y) == 0, dt(0), (dt(1) - y) * np.log1p(-p))
-    return dt(np.sum((t1 + t2).astype(dt), dtype=dt))
+    if spec.likelihood == LIK_BERNOULLI:
+        # clip :226-231; tfd.Bernoulli(probs).log_prob(y) =
+        # xlogy(y,p) + xlog1py(1-y,-p) (TFP 0.12 bernoulli.py _log_prob)
+        p = np.clip(f, dt(1e-8), dt(1 - 1e-7)).astype(dt)
+        y = np.asarray(Y, dtype=dt).reshape(-1, f.shape[0]).T           # :236 transpose(realVals)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t1 = np.where(y == 0, dt(0), y * np.log(p))
+            t2 = np.where((dt(1) - y) == 0, dt(0), (dt(1) - y) * np.log1p(-p))
+        t = t1 + t2 if w is None else w * (t1 + t2)
+        return dt(np.sum(t.astype(dt), dtype=dt))
+    if spec.likelihood == LIK_CATEGORICAL:
+        y = np.asarray(Y, dtype=dt).reshape(f.shape[1], -1).T       # [K, n]
+        return dt(np.sum((y if w is None else w * y) * _log_softmax(f)))
+    if spec.likelihood == LIK_POISSON:
+        data, const = _poisson_terms(f, Y, dt, w)
+        return np.float64(data) - const
+    raise ValueError(spec.likelihood)
 
 
-def target_log_prob(spec: NetSpec, theta, eta, X, Y, dtype=np.float32):
-    """The closure calculateProbs of network.py:370-392 (= :290-314)."""
+def target_log_prob(spec: NetSpec, theta, eta, X, Y, dtype=np.float32, w=None):
+    """The closure calculateProbs of network.py:370-392 (= :290-314).  ``w``: row weights of the likelihood (extension; the priors
+    are not weighted)."""
     dt = dtype
     theta = np.asarray(theta, dtype=dt)
     eta = np.asarray(eta, dtype=dt)
@@ -275,7 +331,10 @@ def target_log_prob(spec: NetSpec, theta, eta, X, Y, dtype=np.float32):
     for i, (l, (W, b)) in enumerate(zip(spec.layers, unflatten(spec, theta))):
         prob = dt(prob + layer_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt))   # :382-384
     f = forward(spec, theta, X, dt)
-    return dt(prob + log_likelihood(spec, eta, f, Y, dt))            # :388-391
+    if spec.likelihood == LIK_POISSON:      # extension: (priors + data term) - C in fp64, the library's order, in either arm
+        data, const = _poisson_terms(f, Y, dt, w)
+        return np.float64(prob) + np.float64(data) - const
+    return dt(prob + log_likelihood(spec, eta, f, Y, dt, w))         # :388-391
 
 
 # ----------------------------------------------------------------------------
@@ -296,7 +355,32 @@ def prior_grad(l: DenseSpec, h4, W, b, dtype=np.float32):
     return out
 
 
-def target_log_prob_and_grad(spec: NetSpec, theta, eta, X, Y, dtype=np.float32):
+def likelihood_grad(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
+    """dL/df [d_out, n] of :func:`log_likelihood`.  Extensions: categorical y_k - softmax_k sum_j y_j, Poisson y - exp(f), and
+    ``w`` scaling a row's dL/df."""
+    dt = dtype
+    n = f.shape[1]
+    if spec.likelihood in (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN):
+        sig = likelihood_sigma(spec, eta, dt)
+        sig = min(max(sig, dt(1e-8)), dt(1e8))
+        y = np.asarray(Y, dtype=dt).reshape(n, -1).T
+        d_a = ((y - f) / (sig * sig)).astype(dt)
+    elif spec.likelihood == LIK_BERNOULLI:
+        y = np.asarray(Y, dtype=dt).reshape(-1, f.shape[0]).T
+        inside = (f >= dt(1e-8)) & (f <= dt(1 - 1e-7))
+        p = np.clip(f, dt(1e-8), dt(1 - 1e-7)).astype(dt)
+        d_a = np.where(inside, y / p - (dt(1) - y) / (dt(1) - p), dt(0)).astype(dt)
+    elif spec.likelihood == LIK_CATEGORICAL:
+        y = np.asarray(Y, dtype=dt).reshape(n, -1).T
+        d_a = y - np.exp(_log_softmax(f)) * y.sum(axis=0, keepdims=True)
+    elif spec.likelihood == LIK_POISSON:
+        d_a = np.asarray(Y, dtype=dt).reshape(n, -1).T - np.exp(f)
+    else:
+        raise ValueError(spec.likelihood)
+    return d_a if w is None else np.asarray(w, dtype=dt) * d_a
+
+
+def target_log_prob_and_grad(spec: NetSpec, theta, eta, X, Y, dtype=np.float32, w=None):
     """value_and_gradient of the target w.r.t. theta (what TFP asks TF autodiff
     for inside the leapfrog loop; call sites network.py:394-408)."""
     dt = dtype
@@ -304,19 +388,8 @@ def target_log_prob_and_grad(spec: NetSpec, theta, eta, X, Y, dtype=np.float32):
     eta = np.asarray(eta, dtype=dt)
     parts = unflatten(spec, theta)
     f, acts = forward(spec, theta, X, dt, keep=True)
-    logp = target_log_prob(spec, theta, eta, X, Y, dt)
-    n = f.shape[1]
-    # dL/df  [d_out, n]
-    if spec.likelihood in (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN):
-        sig = likelihood_sigma(spec, eta, dt)
-        sig = min(max(sig, dt(1e-8)), dt(1e8))
-        y = np.asarray(Y, dtype=dt).reshape(n, -1).T
-        d_a = ((y - f) / (sig * sig)).astype(dt)
-    else:
-        y = np.asarray(Y, dtype=dt).reshape(-1, f.shape[0]).T
-        inside = (f >= dt(1e-8)) & (f <= dt(1 - 1e-7))
-        p = np.clip(f, dt(1e-8), dt(1 - 1e-7)).astype(dt)
-        d_a = np.where(inside, y / p - (dt(1) - y) / (dt(1) - p), dt(0)).astype(dt)
+    logp = target_log_prob(spec, theta, eta, X, Y, dt, w)
+    d_a = likelihood_grad(spec, eta, f, Y, dt, w)                    # dL/df  [d_out, n]
     grads = [None] * len(spec.layers)
     for i in range(len(spec.layers) - 1, -1, -1):
         l = spec.layers[i]
@@ -393,17 +466,17 @@ def hmc_step(value_and_grad, q0, eps, L, p0, log_u, dtype=np.float32, energy_dty
                       sjd=sjd, trace_logp=trace, theta_proposed=q.copy(), p_final=p.copy())
 
 
-def weight_step(spec, theta, eta, X, Y, eps, L, p0, log_u, dtype=np.float32, energy_dtype=None):
+def weight_step(spec, theta, eta, X, Y, eps, L, p0, log_u, dtype=np.float32, energy_dtype=None, w=None):
     """InnerStepMain, network.py:368-412."""
-    vg = lambda q: target_log_prob_and_grad(spec, q, eta, X, Y, dtype)
+    vg = lambda q: target_log_prob_and_grad(spec, q, eta, X, Y, dtype, w)
     return hmc_step(vg, theta, eps, L, p0, log_u, dtype, energy_dtype)
 
 
 # ----------------------------------------------------------------------------
 # A14: hyper-parameter transition + dual averaging (network.py:414-471)
 # ----------------------------------------------------------------------------
-def hyper_log_prob(spec: NetSpec, eta, theta, X, Y, dtype=np.float32):
-    """closure calculateProbs of InnerStepHyper, network.py:416-440."""
+def hyper_log_prob(spec: NetSpec, eta, theta, X, Y, dtype=np.float32, w=None):
+    """closure calculateProbs of InnerStepHyper, network.py:416-440.  ``w``: row weights of the Gaussian data term (extension)."""
     dt = dtype
     eta = np.asarray(eta, dtype=dt)
     theta = np.asarray(theta, dtype=dt)
@@ -412,15 +485,18 @@ def hyper_log_prob(spec: NetSpec, eta, theta, X, Y, dtype=np.float32):
         prob = dt(prob + layer_hyper_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt))   # :429-431
     if spec.likelihood == LIK_GAUSSIAN:                              # mainProbsInHypers, likelihood.py:67
         f = forward(spec, theta, X, dt)
-        prob = dt(prob + log_likelihood(spec, eta, f, Y, dt))        # :435-438
+        prob = dt(prob + log_likelihood(spec, eta, f, Y, dt, w))     # :435-438
+    elif spec.likelihood not in LIKELIHOODS:                         # (the others have no hyper: the priors alone)
+        raise ValueError(spec.likelihood)
     return prob
 
 
-def hyper_log_prob_and_grad(spec: NetSpec, eta, theta, X, Y, dtype=np.float32, S=None):
+def hyper_log_prob_and_grad(spec: NetSpec, eta, theta, X, Y, dtype=np.float32, S=None, w=None):
     """Hand-coded gradient of :func:`hyper_log_prob` w.r.t. eta (checked vs
     torch.autograd in tests).  ``S`` = sum((y-f)^2) may be supplied (SURVEY
     section 7.3 closed form); the value then uses
-    -1/2 (2 n log s + S/s^2 + n log 2pi)."""
+    -1/2 (2 n log s + S/s^2 + n log 2pi).  ``w``: row weights of the Gaussian data
+    term (extension): S = sum_i w_i sum_k (y-f)^2 and n = sum(w) d_out."""
     dt = dtype
     eta = np.asarray(eta, dtype=dt)
     theta = np.asarray(theta, dtype=dt)
@@ -435,9 +511,9 @@ def hyper_log_prob_and_grad(spec: NetSpec, eta, theta, X, Y, dtype=np.float32, S
             scale = gg * gg
             if l.prior == PRIOR_CAUCHY:
                 z = (x - loc) / scale
-                w = dt(2) * z / (dt(1) + z * z)
-                d_loc = np.sum(-w / scale, dtype=dt)
-                d_scale = np.sum(-w * z / scale - dt(1) / scale, dtype=dt)
+                u = dt(2) * z / (dt(1) + z * z)
+                d_loc = np.sum(-u / scale, dtype=dt)
+                d_scale = np.sum(-u * z / scale - dt(1) / scale, dtype=dt)
                 d_loc += -(loc - dt(0)) / dt(0.2) ** 2
                 d_scale += -(scale - dt(0.5 ** 0.5)) / dt(0.5) ** 2
             else:
@@ -454,26 +530,30 @@ def hyper_log_prob_and_grad(spec: NetSpec, eta, theta, X, Y, dtype=np.float32, S
         s = min(max(s_raw, dt(1e-8)), dt(1e8))
         clamped = not (dt(1e-8) < s_raw < dt(1e8))
         f = None
+        rows = None if w is None else float(np.sum(np.asarray(w, dtype=np.float64)))   # extension: sum(w) in place of the row count
         if S is None:
             f = forward(spec, theta, X, dt)
-            n_el = f.size
+            n_el = f.size if w is None else rows * f.shape[0]
             y = np.asarray(Y, dtype=dt).reshape(f.shape[1], -1).T
-            S_ = np.sum((y - f).astype(np.float64) ** 2)
-            prob = dt(prob + log_likelihood(spec, eta, f, Y, dt))
+            r2 = (y - f).astype(np.float64) ** 2
+            S_ = np.sum(r2 if w is None else np.asarray(w, dtype=np.float64) * r2)
+            prob = dt(prob + log_likelihood(spec, eta, f, Y, dt, w))
         else:
             S_ = float(S)
-            n_el = int(np.asarray(Y).size)
+            n_el = int(np.asarray(Y).size) if w is None else rows * spec.layers[-1].out_dim
             prob = dt(prob + dt(-0.5) * (dt(2 * n_el) * np.log(s) + dt(S_) / (s * s)
                                           + dt(n_el) * np.log(dt(2 * math.pi))))
         d_s = dt(0) if clamped else dt(-n_el / float(s) + S_ / float(s) ** 3)
         g[-1] = d_s * dt(2) * eta[-1]
+    elif spec.likelihood not in LIKELIHOODS:
+        raise ValueError(spec.likelihood)
     return prob, g
 
 
 def hyper_step(spec, eta, theta, X, Y, eps_h, L_h, p0, log_u, dtype=np.float32, S=None,
-               energy_dtype=None):
+               energy_dtype=None, w=None):
     """InnerStepHyper's HMC part, network.py:442-456."""
-    vg = lambda e: hyper_log_prob_and_grad(spec, e, theta, X, Y, dtype, S=S)
+    vg = lambda e: hyper_log_prob_and_grad(spec, e, theta, X, Y, dtype, S=S, w=w)
     return hmc_step(vg, eta, eps_h, L_h, p0, log_u, dtype, energy_dtype)
 
 

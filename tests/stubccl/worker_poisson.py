@@ -1,6 +1,6 @@
 """One rank of the world-2 Poisson test of the row-sharded chain (tests/test_gpu_poisson.py): run as a child process with TBNN_RCCL_LIB
-pointing at the stub collective library.  argv: rank world idfile outfile.  (tests/stubccl/worker.py builds its problems from the oracle's
-descriptors, which stop at Bernoulli.)"""
+pointing at the stub collective library.  argv: rank world idfile outfile.  (The problems are tests/test_gpu_poisson.py's: counts, and a
+state whose log-rates stay within [-5, 5].)"""
 import os
 import sys
 
@@ -17,7 +17,6 @@ from tensorbnn_amd import _native as nat    # noqa: E402
 from tensorbnn_amd import parallel          # noqa: E402
 from worker import exchange_id              # noqa: E402
 
-LIK_POIS = 5
 SHAPES = {
     # dims, rows, hidden activation, prior, jit
     "narrow": ([5, 50, 50, 50, 1], 3001, o.ACT_RELU, o.PRIOR_CAUCHY, True),        # the run-time fast3 table of tests/test_gpu_poisson.py
@@ -36,8 +35,8 @@ def chain_of(name, spec):
     jit = SHAPES[name][4]
     layers = [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
     if jit is None:
-        return nat.Chain(layers, likelihood=LIK_POIS, kernel=nat.KERNEL_GENERIC)
-    return nat.Chain(layers, likelihood=LIK_POIS, kernel=nat.KERNEL_AUTO, jit=jit)
+        return nat.Chain(layers, likelihood=o.LIK_POISSON, kernel=nat.KERNEL_GENERIC)
+    return nat.Chain(layers, likelihood=o.LIK_POISSON, kernel=nat.KERNEL_AUTO, jit=jit)
 
 
 def main():

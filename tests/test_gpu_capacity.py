@@ -16,7 +16,7 @@ import pytest
 
 import edge_shapes as es
 import tbnn_oracle as o
-from test_gpu_edges import grad_err
+from tensor_checks import layers_of, tensor_err
 
 pytestmark = pytest.mark.gpu
 
@@ -43,10 +43,6 @@ def problem(dims, n, lik=o.LIK_GAUSSIAN):
         f = o.forward(spec, theta, X, np.float64)
         assert np.all((f > 1e-4) & (f < 1 - 1e-4)), "Bernoulli outputs off saturation"
     return spec, X, Y, theta, eta
-
-
-def layers_of(spec):
-    return [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
 
 
 def setenv(monkeypatch, family, skip):
@@ -89,7 +85,7 @@ def value_gradient_forward(native, spec, X, Y, theta, eta, family):
     lp64, g64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)[:2]
     e_lp = abs(lp - lp64) / max(abs(lp64), 1.0)
     assert e_lp <= 4e-6, f"{name}: logp {lp} against {lp64} ({e_lp:.2e} relative, bound 4e-6)"
-    e_g = grad_err(spec, g, g64)
+    e_g = tensor_err(spec, g, g64, 1e-3)
     assert e_g <= 1e-4, f"{name}: gradient {e_g:.3e} of the tensor's inf-norm (1e-4)"
     e_f = 0.0
     for got, th in ((f, theta), (pr, theta), (fm[0], th2[0]), (fm[1], th2[1])):

@@ -1,7 +1,7 @@
 """GPU: CategoricalLikelihood (TBNN_LIK_CATEGORICAL) -- a softmax over each row's outputs -- on every kernel family that takes it: the mid,
 tall and wide fused kernels (cat_delta4 on the MFMA output tile, the row's max and sums across the four lane groups), the layered family
-on each of its likelihood paths (k_lay_tail, k_lay_last, k_lay_lik; any number of outputs) and the generic kernel.  Against an fp64
-reference written here on the oracle's forward pass, layer priors and prior gradients: value, gradient per tensor, forward logits, an
+on each of its likelihood paths (k_lay_tail, k_lay_last, k_lay_lik; any number of outputs) and the generic kernel.  Against the fp64
+oracle (o.target_log_prob_and_grad under LIK_CATEGORICAL): value, gradient per tensor, forward logits, an
 injected weight transition with both decisions, a hyper transition (prior only: the likelihood has no hyper), every launch repeated bit
 for bit; saturated logits, soft labels; a Gaussian and a categorical chain of the same shape in one process; trainChains against solo
 runs; an end-to-end fit."""
@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 
 import tbnn_oracle as o
-from test_gpu_freerun import layers_of, SEED
+from tensor_checks import layers_of, tensor_err
+from test_gpu_freerun import SEED
 
 pytestmark = pytest.mark.gpu
 
-LIK_CAT = 3                      # include/tbnn.h TBNN_LIK_CATEGORICAL (the oracle's descriptors stop at Bernoulli)
 FUSED = {"mid": "fast3,fast,tall,wide", "tall": "fast3,fast,mid,wide", "wide": "fast3,fast,mid,tall"}
 
 CASES = {
@@ -50,10 +50,10 @@ def jit_jobs():
     jobs = []
     for dims, _n, act, prior, fam, _env, _lab in CASES.values():
         if fam in FUSED:
-            jobs.append({"layers": [list(l) for l in layers_of(spec_of(dims, act, prior))], "likelihood": LIK_CAT, "skip": FUSED[fam], "flags": ""})
+            jobs.append({"layers": [list(l) for l in layers_of(spec_of(dims, act, prior))], "likelihood": o.LIK_CATEGORICAL, "skip": FUSED[fam], "flags": ""})
     for dims, act in (([30, 80, 80, 10], o.ACT_RELU), ([2, 16, 16, 3], o.ACT_RELU)):
         spec = spec_of(dims, act, o.PRIOR_CAUCHY)
-        jobs.append({"layers": [list(l) for l in layers_of(spec)], "likelihood": LIK_CAT, "skip": "", "flags": ""})
+        jobs.append({"layers": [list(l) for l in layers_of(spec)], "likelihood": o.LIK_CATEGORICAL, "skip": "", "flags": ""})
     gspec = o.make_spec([30, 80, 80, 10], o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_GAUSSIAN)
     jobs.append({"layers": [list(l) for l in layers_of(gspec)], "likelihood": o.LIK_GAUSSIAN, "skip": FUSED["mid"], "flags": ""})
     # the predictor's forward chain of the fitted three-class network (a fixed-sd Gaussian handle: forward passes only)
@@ -71,7 +71,7 @@ def prebuilt():
 
 
 def spec_of(dims, act, prior):
-    return o.make_spec(dims, act, prior, LIK_CAT, o.ACT_NONE)
+    return o.make_spec(dims, act, prior, o.LIK_CATEGORICAL, o.ACT_NONE)
 
 
 def softmax_rows(z):
@@ -102,61 +102,31 @@ def problem(name):
     return spec, X, Y, theta, eta
 
 
-def log_softmax(f, axis):
-    d = f - f.max(axis=axis, keepdims=True)
-    return d - np.log(np.exp(d).sum(axis=axis, keepdims=True))
-
-
-def cat_value_and_grad(spec, theta, eta, X, Y):
-    """fp64: sum of the layer priors + sum_rows sum_k y_k log softmax_k(f), and its gradient (dL/df = y - softmax * sum_k y_k)"""
-    dt = np.float64
-    theta, eta = np.asarray(theta, dt), np.asarray(eta, dt)
-    parts = o.unflatten(spec, theta)
-    f, acts = o.forward(spec, theta, X, dt, keep=True)
-    y = np.asarray(Y, dt).reshape(f.shape[1], -1).T                   # [K, n]
-    ls = log_softmax(f, axis=0)
-    lp = sum(o.layer_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt) for i, (l, (W, b)) in enumerate(zip(spec.layers, parts)))
-    lp = lp + np.sum(y * ls)
-    d_a = y - np.exp(ls) * y.sum(axis=0, keepdims=True)
-    grads = [None] * len(spec.layers)
-    for i in range(len(spec.layers) - 1, -1, -1):
-        l = spec.layers[i]
-        W, b = parts[i]
-        delta = d_a * o.act_grad_from_output(acts[i + 1], l.act)
-        pW, pb = o.prior_grad(l, eta[4 * i:4 * i + 4], W, b, dt)
-        grads[i] = (delta @ acts[i].T + pW, delta.sum(axis=1, keepdims=True) + pb)
-        if i > 0:
-            d_a = W.T @ delta
-    return lp, o.flatten(grads)
-
-
 def make_chain(native, monkeypatch, name, spec, **kw):
     fam, env = CASES[name][4], CASES[name][5]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     if fam in FUSED:
         monkeypatch.setenv("TBNN_JIT_SKIP", FUSED[fam])
-        ch = native.Chain(layers_of(spec), likelihood=LIK_CAT, jit=True, **kw)
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_CATEGORICAL, jit=True, **kw)
         assert ch.kernel_name.startswith(f"jit-{fam}") and ",categorical;" in ch.kernel_name, ch.kernel_name
     elif fam == "layered":
         monkeypatch.setenv("TBNN_TALL", "0")
         monkeypatch.setenv("TBNN_REGISTERED", "0")
-        ch = native.Chain(layers_of(spec), likelihood=LIK_CAT, jit=False, **kw)
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_CATEGORICAL, jit=False, **kw)
         assert ch.kernel_name.startswith("layered<"), ch.kernel_name
     else:
-        ch = native.Chain(layers_of(spec), likelihood=LIK_CAT, kernel=native.KERNEL_GENERIC, **kw)
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_CATEGORICAL, kernel=native.KERNEL_GENERIC, **kw)
         assert ch.kernel_name == "generic", ch.kernel_name
     assert ch.H == 4 * len(spec.layers)
     return ch
 
 
 def check_value_gradient(name, lp, g, spec, theta, eta, X, Y):
-    lp64, g64 = cat_value_and_grad(spec, theta, eta, X, Y)
+    lp64, g64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)
     assert np.isfinite(lp) and np.all(np.isfinite(g))
     assert abs(lp - lp64) <= 4e-6 * max(abs(lp64), 1.0), (name, lp, lp64)
-    for l, (ow, ob) in zip(spec.layers, spec.offsets()):
-        for a, b in ((ow, ob), (ob, ob + l.out_dim)):
-            assert np.abs(g[a:b] - g64[a:b]).max() <= 1e-4 * max(np.abs(g64[a:b]).max(), 1e-3), (name, a, b)
+    assert tensor_err(spec, g, g64, 1e-3) <= 1e-4, name
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -186,7 +156,7 @@ def test_transitions(native, monkeypatch, name):
     p0 = rng.standard_normal(spec.n_params).astype(np.float32)
     ch = make_chain(native, monkeypatch, name, spec, seed=SEED, chain_id=2)
     ch.set_data(X, Y)
-    vg = lambda q: cat_value_and_grad(spec, q, eta, X, Y)
+    vg = lambda q: o.target_log_prob_and_grad(spec, q, eta, X, Y, np.float64)
     lp64 = vg(theta)[0]
     for log_u in (-1e30, 1e30):
         ch.set_state(theta); ch.set_hypers(eta)
@@ -220,7 +190,7 @@ def test_gaussian_then_categorical_chain_of_one_shape(native, monkeypatch):
     geta = np.concatenate([eta, [np.sqrt(0.1)]]).astype(np.float32)
     gch.set_data(X, Y)
     glp, gg, _ = gch.logp_grad(theta, geta)
-    ch = native.Chain(layers_of(spec), likelihood=LIK_CAT, jit=True)
+    ch = native.Chain(layers_of(spec), likelihood=o.LIK_CATEGORICAL, jit=True)
     assert ch.kernel_name == "jit-mid<relu,none,categorical;30,80,80,10>", ch.kernel_name
     ch.set_data(X, Y)
     lp, g, _ = ch.logp_grad(theta, eta)

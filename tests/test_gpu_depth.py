@@ -14,8 +14,7 @@ import pytest
 
 import edge_shapes as es
 import tbnn_oracle as o
-from test_gpu_categorical import LIK_CAT, cat_value_and_grad
-from test_gpu_edges import blocks
+from tensor_checks import layers_of, tensor_err
 from test_gpu_layered import scaled_problem
 
 pytestmark = pytest.mark.gpu
@@ -72,10 +71,6 @@ def problem(dims, n, acts=None, alternate=False, lik=o.LIK_GAUSSIAN, seed=0):
     return spec, X, Y, theta, eta
 
 
-def layers_of(spec):
-    return [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
-
-
 def setenv(monkeypatch, fam):
     monkeypatch.setenv("TBNN_JIT_SKIP", SKIP[fam])
     if fam in ("wide", "layered", "generic"):
@@ -97,9 +92,7 @@ def make_chain(native, spec, fam, likelihood=None, **kw):
     return ch
 
 
-def tensor_err(spec, g, g64):
-    """the worst error of any W_l / b_l against that tensor's own inf-norm"""
-    return max(float(np.abs(np.asarray(g[a:b], np.float64) - g64[a:b]).max() / max(np.abs(g64[a:b]).max(), 1e-30)) for a, b in blocks(spec))
+FLOOR = 1e-30                     # of a tensor's inf-norm in tensor_err: none of these gradients is all but zero
 
 
 def fwd_err(got, want):
@@ -123,7 +116,7 @@ def value_gradient_forward(native, spec, X, Y, theta, eta, fam):
     # the fp32 oracle inside the bounds first: the problem is conditioned well enough to judge the device
     lp32, g32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)[:2]
     assert abs(lp32 - lp64) <= LOGP_RTOL * max(abs(lp64), 1.0), ("fp32 oracle", lp32, lp64)
-    assert tensor_err(spec, g32, g64) <= GRAD_TOL, ("fp32 oracle gradient", tensor_err(spec, g32, g64))
+    assert tensor_err(spec, g32, g64, FLOOR) <= GRAD_TOL, ("fp32 oracle gradient", tensor_err(spec, g32, g64, FLOOR))
     assert fwd_err(o.forward(spec, theta, X, np.float32), f64[0]) <= FWD_TOL, "fp32 oracle forward"
     ch = make_chain(native, spec, fam)
     try:
@@ -134,7 +127,7 @@ def value_gradient_forward(native, spec, X, Y, theta, eta, fam):
     finally:
         ch.close()
     e_lp = abs(lp - lp64) / max(abs(lp64), 1.0)
-    e_g = tensor_err(spec, g, g64)
+    e_g = tensor_err(spec, g, g64, FLOOR)
     e_f = max(fwd_err(f, f64[0]), fwd_err(pr, f64[0]), fwd_err(fm[0], f64[0]), fwd_err(fm[1], f64[1]))
     print(f"{name}: logp {e_lp:.2e} ({LOGP_RTOL}) gradient per tensor {e_g:.2e} ({GRAD_TOL}) forward {e_f:.2e} ({FWD_TOL})")
     assert e_lp <= LOGP_RTOL, f"{name}: logp {lp} against {lp64} ({e_lp:.2e} relative)"
@@ -341,11 +334,11 @@ def test_deep_categorical(native, monkeypatch, fam):
     setenv(monkeypatch, fam)
     dims = CATEGORICAL[fam]
     spec, X, Yg, theta, eta = problem(dims, N_ROWS, seed=9)
-    spec.likelihood = LIK_CAT
+    spec.likelihood = o.LIK_CATEGORICAL
     eta = np.asarray(eta[:spec.n_hypers], dtype=np.float32)              # no likelihood hyper
     Y = np.eye(dims[-1], dtype=np.float32)[np.argmax(Yg, axis=1)]
-    lp64, g64 = cat_value_and_grad(spec, theta, eta, X, Y)
-    ch = make_chain(native, spec, fam, likelihood=LIK_CAT)
+    lp64, g64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)
+    ch = make_chain(native, spec, fam, likelihood=o.LIK_CATEGORICAL)
     try:
         assert ",categorical;" in ch.kernel_name, ch.kernel_name
         ch.set_data(X, Y)
@@ -353,7 +346,7 @@ def test_deep_categorical(native, monkeypatch, fam):
         f = thrice(lambda: (ch.forward(X, theta),))[0]
     finally:
         ch.close()
-    e_lp, e_g = abs(lp - lp64) / max(abs(lp64), 1.0), tensor_err(spec, g, g64)
+    e_lp, e_g = abs(lp - lp64) / max(abs(lp64), 1.0), tensor_err(spec, g, g64, FLOOR)
     e_f = fwd_err(f, o.forward(spec, theta, X, np.float64))
     print(f"{fam} categorical: logp {e_lp:.2e} gradient per tensor {e_g:.2e} forward {e_f:.2e}")
     assert e_lp <= LOGP_RTOL and e_g <= GRAD_TOL and e_f <= FWD_TOL, (e_lp, e_g, e_f)
@@ -376,5 +369,5 @@ def jit_jobs():
         add(problem(dims, 8, acts=MIXED_ACTS)[0], fam)
     add(problem(TRAJ, 8)[0], "fast3")
     for fam, dims in CATEGORICAL.items():
-        add(problem(dims, 8)[0], fam, LIK_CAT)
+        add(problem(dims, 8)[0], fam, o.LIK_CATEGORICAL)
     return jobs

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import tbnn_oracle as o
-from test_gpu_freerun import layers_of
+from tensor_checks import layers_of, tensor_err
 from test_gpu_layered import scaled_problem
 
 pytestmark = pytest.mark.gpu
@@ -97,21 +97,13 @@ def run(native, monkeypatch, fam, spec, X, Y, theta, eta, *, ens=True):
     return name, lp, g, f, pr, (th2, fm)
 
 
-def blocks(spec):
-    return [(a, b) for l, (ow, ob) in zip(spec.layers, spec.offsets()) for a, b in ((ow, ob), (ob, ob + l.out_dim))]
-
-
-def grad_err(spec, g, gref):
-    return max(np.abs(g[a:b] - gref[a:b]).max() / max(np.abs(gref[a:b]).max(), 1e-3) for a, b in blocks(spec))
-
-
 def check(native, monkeypatch, fam, spec, X, Y, theta, eta, ens=True):
     name, lp, g, f, pr, (th2, fm) = run(native, monkeypatch, fam, spec, X, Y, theta, eta, ens=ens)
     g64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)[1]
     lp64 = ref_logp(spec, theta, eta, X, Y)
     tol_lp = 4e-6 * max(abs(lp64), 1.0) + ulp_slack(spec, theta, X, Y)
     assert abs(lp - lp64) <= tol_lp, f"{name}: logp {lp} against {lp64} (bound {tol_lp:.3e})"
-    e_g = grad_err(spec, g, g64)
+    e_g = tensor_err(spec, g, g64, 1e-3)
     assert e_g <= 1e-4, f"{name}: gradient {e_g:.3e} of the tensor's inf-norm (1e-4)"
     f64 = o.forward(spec, theta, X, np.float64)
     fwd_tol = 1e-4 * np.maximum(1.0, np.abs(f64))                    # (exp outputs: relative above 1)
@@ -384,6 +376,6 @@ def test_mn_burned_full_size(native, monkeypatch):
     lp32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)[0]
     assert abs(lp - lp32) <= 4e-6 * abs(lp32), (lp, lp32)
     g64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)[1]
-    e_g = grad_err(spec, g, g64)
+    e_g = tensor_err(spec, g, g64, 1e-3)
     print(f"mn_burned: {clipped} clipped outputs, gradient {e_g:.2e} of the tensor's inf-norm from fp64, logp {abs(lp - lp32) / abs(lp32):.2e} from fp32")
     assert e_g <= 1e-4, e_g

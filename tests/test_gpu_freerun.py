@@ -22,6 +22,7 @@ import pytest
 
 import c_oracle
 import tbnn_oracle as o
+from tensor_checks import layers_of
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +33,6 @@ SEED = 50
 
 def lar_tol(lar, logp):
     return 2e-2 + 1e-4 * abs(lar) + 1e-6 * abs(logp)
-
-
-def layers_of(spec):
-    return [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
 
 
 def draws(P, chain_id, epoch, hyper=False):

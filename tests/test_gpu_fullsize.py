@@ -19,6 +19,7 @@ import pytest
 
 import c_oracle
 import tbnn_oracle as o
+from tensor_checks import layers_of
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +33,6 @@ def lar_tol(lar, logp):
     configs[1] state |logp| = 1.06e5, so 0.1 of absolute slack is the resolution of the quantity itself"""
     return 2e-2 + 1e-4 * abs(lar) + 1e-6 * abs(logp)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def layers_of(spec):
-    return [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
 
 
 def check_full_size(native, dims, n, lik, eps, L, family):

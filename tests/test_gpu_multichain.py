@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import tbnn_oracle as o
+from tensor_checks import layers_of
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +21,6 @@ SHAPES = {
     "bern_mid": ([20, 32, 48, 2], 700, o.ACT_SIGMOID, o.PRIOR_CAUCHY, o.LIK_BERNOULLI),
 }
 REC = ("log_accept_ratio", "accepted", "logp_old", "logp_new", "kinetic_old", "kinetic_new", "sjd", "accept_prob")
-
-
-def layers_of(spec):
-    return [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

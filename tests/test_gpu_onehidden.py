@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import tbnn_oracle as o
-from test_gpu_freerun import Tally, draws, layers_of, SEED
+from tensor_checks import layers_of
+from test_gpu_freerun import Tally, draws, SEED
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,7 @@
 """GPU: PoissonLikelihood (TBNN_LIK_POISSON) -- counts under a log link, log p(y | f) = y f - exp(f) - lgamma(y + 1) -- on every kernel
 family: the narrow fast3 and fast kernels and their one-launch trajectory kernel, mid, tall and wide (the VALU last layer of one or two
 outputs and the MFMA output tile of 3 .. 16), each likelihood path of the layered family (k_lay_tail, k_lay_last, k_lay_lik) and the
-generic kernel.  Against an fp64 reference written here on the oracle's forward pass, layer priors and prior gradients: value (with the
+generic kernel.  Against the fp64 oracle (o.target_log_prob_and_grad under LIK_POISSON): value (with the
 constant C = sum lgamma(y + 1) the library computes once per data staging), gradient per tensor, forward log-rates, an injected weight
 transition with both decisions, a hyper transition, every launch repeated bit for bit.  Then: overflowing proposals, row weights, refused
 targets and descriptors, trainChains against solo runs, a Gaussian and a Poisson chain side by side, the ensemble reductions, a
@@ -10,7 +10,8 @@ row-sharded chain on the stub collective library, and an end-to-end fit judged b
 Bands: those of tests/test_gpu_categorical.py.  The inputs keep the log-rates in about [-3, 6].  The one "large rate" case has log-rates
 up to 20 (rates to 5e8): there an fp32 evaluation of the log-rate itself (rounding ~1e-7 |f| sqrt(fan-in), i.e. ~1e-5 absolute at f = 20)
 moves exp(f) by ~1e-5 relative, which is more than the 4e-6 band of the value.  `test_reference_in_fp32_stays_inside_the_bands` (CPU
-arithmetic only) evaluates the fp64 reference's own formula in fp32 and asserts that it stays inside the project's bands for every normal
+arithmetic only) evaluates the oracle's fp32 arm (the fp64 reference's own formula in fp32) and asserts that it stays inside the project's
+bands for every normal
 case; for the large-rate case it measures the fp32-vs-fp64 gap of that reference, and the band there is max(project band, 8 x that gap):
 8 = two independent fp32 evaluations (the reference's and the kernel's, each that far from fp64) x 4 for the kernel's other summation
 order and its hardware exp2 (whose argument f log2(e) is rounded once more: 0.7 ulp(29) = 7e-7 relative at f = 20, next to the 1e-5
@@ -30,14 +31,13 @@ import numpy as np
 import pytest
 
 import tbnn_oracle as o
-from test_gpu_freerun import layers_of, SEED
+from tensor_checks import layers_of, tensor_errs
+from test_gpu_freerun import SEED
 
 pytestmark = pytest.mark.gpu
 
-LIK_POIS = 5                     # include/tbnn.h TBNN_LIK_POISSON (the oracle's descriptors stop at Bernoulli)
 HERE = os.path.dirname(os.path.abspath(__file__))
 FUSED = {"fast3": "", "fast": "fast3", "mid": "fast3,fast,tall,wide", "tall": "fast3,fast,mid,wide", "wide": "fast3,fast,mid,tall"}
-LGAMMA = np.vectorize(math.lgamma, otypes=[np.float64])
 
 CASES = {
     # dims, rows, hidden activation, prior, family, environment, kind
@@ -66,10 +66,10 @@ NET = [1, 16, 16, 1]                                              # the network(
 
 
 def spec_of(dims, act, prior):
-    return o.make_spec(dims, act, prior, LIK_POIS, o.ACT_NONE)
+    return o.make_spec(dims, act, prior, o.LIK_POISSON, o.ACT_NONE)
 
 
-def job(spec, lik=LIK_POIS, skip="", weighted=False):
+def job(spec, lik=o.LIK_POISSON, skip="", weighted=False):
     j = {"layers": [list(l) for l in layers_of(spec)], "likelihood": lik, "skip": skip, "flags": ""}
     if weighted:
         j["weighted"] = True
@@ -131,31 +131,6 @@ def problem(name):
     return problem_of(dims, n, act, prior, kind)
 
 
-def pois_value_and_grad(spec, theta, eta, X, Y, w=None, dt=np.float64):
-    """sum of the layer priors + sum_rows w_i sum_k (y f - exp(f) - lgamma(y + 1)), and its gradient (dL/df = w (y - exp(f))), in `dt`
-    (the constant in fp64 always: the library computes it in fp64 too)"""
-    theta, eta = np.asarray(theta, dt), np.asarray(eta, dt)
-    parts = o.unflatten(spec, theta)
-    f, acts = o.forward(spec, theta, np.asarray(X, dt), dt, keep=True)
-    y = np.asarray(Y, dt).reshape(f.shape[1], -1).T                   # [K, n]
-    wt = np.ones(f.shape[1], dt) if w is None else np.asarray(w, dt)
-    mu = np.exp(f)
-    lp = sum(o.layer_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt) for i, (l, (W, b)) in enumerate(zip(spec.layers, parts)))
-    const = np.sum(wt.astype(np.float64) * LGAMMA(y.astype(np.float64) + 1.0))
-    lp = np.float64(lp) + np.float64(np.sum(wt * (y * f - mu), dtype=dt)) - const
-    d_a = wt * (y - mu)
-    grads = [None] * len(spec.layers)
-    for i in range(len(spec.layers) - 1, -1, -1):
-        l = spec.layers[i]
-        W, b = parts[i]
-        delta = d_a * o.act_grad_from_output(acts[i + 1], l.act)
-        pW, pb = o.prior_grad(l, eta[4 * i:4 * i + 4], W, b, dt)
-        grads[i] = (delta @ acts[i].T + pW, delta.sum(axis=1, keepdims=True) + pb)
-        if i > 0:
-            d_a = W.T @ delta
-    return float(lp), np.asarray(o.flatten(grads), dtype=np.float64)
-
-
 def data_terms_gap32(spec, theta, X, Y):
     """sum over (row, output) of y f - exp(f) evaluated in fp32 minus the same in fp64, both summed in fp64, at the fp32 state `theta`"""
     out = []
@@ -166,15 +141,9 @@ def data_terms_gap32(spec, theta, X, Y):
     return out[0] - out[1]
 
 
-def tensors(spec):
-    for l, (ow, ob) in zip(spec.layers, spec.offsets()):
-        yield ow, ob
-        yield ob, ob + l.out_dim
-
-
 def gaps(spec, lp, g, lp64, g64):
     """(value error / max(|lp64|, 1), per tensor: gradient error / max(|g64|_inf, 1e-3))"""
-    return abs(lp - lp64) / max(abs(lp64), 1.0), [np.abs(g[a:b] - g64[a:b]).max() / max(np.abs(g64[a:b]).max(), 1e-3) for a, b in tensors(spec)]
+    return abs(lp - lp64) / max(abs(lp64), 1.0), tensor_errs(spec, g, g64, 1e-3)
 
 
 def bands(name, spec, theta, eta, X, Y, ref64):
@@ -182,14 +151,14 @@ def bands(name, spec, theta, eta, X, Y, ref64):
     nt = 2 * len(spec.layers)
     if CASES.get(name, (0,) * 7)[6] != "large":
         return 4e-6, [1e-4] * nt
-    lp32, g32 = pois_value_and_grad(spec, theta, eta, X, Y, dt=np.float32)
+    lp32, g32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
     gv, gg = gaps(spec, lp32, g32, *ref64)
     print(f"[poisson] {name}: fp32 reference vs fp64: value gap {gv:.3e}, gradient gaps max {max(gg):.3e}")
     return max(4e-6, 8 * gv), [max(1e-4, 8 * x) for x in gg]
 
 
 def check_value_gradient(name, lp, g, spec, theta, eta, X, Y, w=None):
-    ref64 = pois_value_and_grad(spec, theta, eta, X, Y, w)
+    ref64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64, w=w)
     bv, bg = bands(name, spec, theta, eta, X, Y, ref64)
     ev, eg = gaps(spec, lp, g, *ref64)
     print(f"[poisson] {name}: logp {lp:.9g} (fp64 {ref64[0]:.9g}) err {ev:.3e} of band {bv:.3e}; gradient err/band max {max(e / b for e, b in zip(eg, bg)):.3f}")
@@ -204,8 +173,8 @@ def test_reference_in_fp32_stays_inside_the_bands(name):
     """CPU arithmetic only: the reference's own formula evaluated in fp32 against fp64 -- inside the project's bands for every normal
     case (so the bands are a fair demand on an fp32 kernel); the large-rate case reports the gap its margin is derived from"""
     spec, X, Y, theta, eta = problem(name)
-    ref64 = pois_value_and_grad(spec, theta, eta, X, Y)
-    lp32, g32 = pois_value_and_grad(spec, theta, eta, X, Y, dt=np.float32)
+    ref64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64)
+    lp32, g32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
     gv, gg = gaps(spec, lp32, g32, *ref64)
     f = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
     print(f"[poisson] {name}: log-rates [{f.min():.2f}, {f.max():.2f}], counts to {Y.max():.0f}; fp32 reference: value gap {gv:.3e}, gradient gap {max(gg):.3e}")
@@ -222,15 +191,15 @@ def make_chain(native, monkeypatch, name, spec, **kw):
         monkeypatch.setenv(k, v)
     if fam in FUSED:
         monkeypatch.setenv("TBNN_JIT_SKIP", FUSED[fam])
-        ch = native.Chain(layers_of(spec), likelihood=LIK_POIS, jit=True, **kw)
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_POISSON, jit=True, **kw)
         assert ch.kernel_name.startswith(f"jit-{fam}<") and ",poisson;" in ch.kernel_name, ch.kernel_name
     elif fam == "layered":
         monkeypatch.setenv("TBNN_TALL", "0")
         monkeypatch.setenv("TBNN_REGISTERED", "0")
-        ch = native.Chain(layers_of(spec), likelihood=LIK_POIS, jit=False, **kw)
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_POISSON, jit=False, **kw)
         assert ch.kernel_name.startswith("layered<"), ch.kernel_name
     else:
-        ch = native.Chain(layers_of(spec), likelihood=LIK_POIS, kernel=native.KERNEL_GENERIC, **kw)
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_POISSON, kernel=native.KERNEL_GENERIC, **kw)
         assert ch.kernel_name == "generic", ch.kernel_name
     assert ch.H == 4 * len(spec.layers)
     return ch
@@ -266,7 +235,7 @@ def test_transitions(native, monkeypatch, name):
     p0 = rng.standard_normal(spec.n_params).astype(np.float32)
     ch = make_chain(native, monkeypatch, name, spec, seed=SEED, chain_id=2)
     ch.set_data(X, Y)
-    vg = lambda q: pois_value_and_grad(spec, q, eta, X, Y)
+    vg = lambda q: o.target_log_prob_and_grad(spec, q, eta, X, Y, np.float64)
     lp64 = vg(theta)[0]
     # (large rates: the fp64 gradient's largest entry is 2.8e9 there against 4.8e4 in the normal case of the same shape; the step size
     # shrinks by that ratio, 3e-5 x 4.8e4 / 2.8e9, so that one kick eps |g| moves the momentum as far as it does there -- a choice of input
@@ -311,11 +280,11 @@ def test_trajectory_kernel(native, monkeypatch):
     spec, X, Y, theta, eta = problem_of(dims, n, act, prior)
     monkeypatch.setenv("TBNN_TRAJ", "1")
     monkeypatch.setenv("TBNN_JIT_SKIP", "")
-    ch = native.Chain(layers_of(spec), likelihood=LIK_POIS, jit=True, seed=SEED)
+    ch = native.Chain(layers_of(spec), likelihood=o.LIK_POISSON, jit=True, seed=SEED)
     assert ch.kernel_name.startswith("jit-fast3<") and ",poisson;" in ch.kernel_name, ch.kernel_name
     ch.set_data(X, Y)
     p0 = np.random.default_rng(5).standard_normal(spec.n_params).astype(np.float32)
-    vg = lambda q: pois_value_and_grad(spec, q, eta, X, Y)
+    vg = lambda q: o.target_log_prob_and_grad(spec, q, eta, X, Y, np.float64)
     lp64 = vg(theta)[0]
     for L in (1, 9):
         ref = o.hmc_step(vg, theta, 2e-4, L, p0, -1e30, np.float64)
@@ -421,9 +390,9 @@ def test_refusals(native, monkeypatch):
     check_value_gradient("refusals", lp, g, spec, theta, eta, X[:100], Y[:100])
     ch.close()
     for act in (o.ACT_EXP, o.ACT_SIGMOID):
-        layers = layers_of(o.make_spec([5, 8, 1], o.ACT_RELU, o.PRIOR_CAUCHY, LIK_POIS, act))
+        layers = layers_of(o.make_spec([5, 8, 1], o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_POISSON, act))
         with pytest.raises(native.TbnnError, match="log-rate"):
-            native.Chain(layers, likelihood=LIK_POIS, jit=False)
+            native.Chain(layers, likelihood=o.LIK_POISSON, jit=False)
 
 
 def test_gaussian_and_poisson_chain_of_one_shape(native, monkeypatch):
@@ -465,13 +434,13 @@ def test_ensemble_loglik(native, monkeypatch):
     for tag, ch in handles.items():
         f = ch.forward_many(thetas, X=X).astype(np.float64)                          # [m, d_out, n]
         y = Y.reshape(n, d_out).T.astype(np.float64)[None]
-        t1, t2, t3 = y * f, np.exp(f), LGAMMA(y + 1.0) + 0 * f
+        t1, t2, t3 = y * f, np.exp(f), o.lgamma(y + 1.0) + 0 * f
         l = (t1 - t2 - t3).sum(axis=1)                                               # [m, n]
         err = (8 * U * (np.abs(t1) + t2 + np.abs(t3))).sum(axis=1)
         mag = np.abs(t1 - t2 - t3).sum(axis=(1, 2))
         for wts in (None, np.array([1, 0, 2.5, 1, 0.25, 3], dtype=np.float32)):
-            per_net, rows = ch.ensemble_loglik(thetas, Y=Y, X=X, likelihood=LIK_POIS, weights=wts)
-            again = ch.ensemble_loglik(thetas, Y=Y, X=X, likelihood=LIK_POIS, weights=wts)
+            per_net, rows = ch.ensemble_loglik(thetas, Y=Y, X=X, likelihood=o.LIK_POISSON, weights=wts)
+            again = ch.ensemble_loglik(thetas, Y=Y, X=X, likelihood=o.LIK_POISSON, weights=wts)
             assert np.array_equal(per_net, again[0]) and np.array_equal(rows, again[1])
             want = l.sum(axis=1)
             tol = err.sum(axis=1) + n * d_out * U * mag + np.spacing(np.abs(want))
@@ -597,7 +566,7 @@ def test_train_beats_the_constant_rate_model(tmp_path, monkeypatch, native):
     X, Y = counts(600, 1)
     Xv, Yv = counts(300, 2)
     yv = Yv.astype(np.float64)
-    logpmf = lambda rate: yv * np.log(rate) - rate - LGAMMA(yv + 1.0)
+    logpmf = lambda rate: yv * np.log(rate) - rate - o.lgamma(yv + 1.0)
     base = float(np.mean(logpmf(np.full_like(yv, Y.astype(np.float64).mean()))))
     truth = float(np.mean(logpmf(rate_of(Xv.astype(np.float64)))))
     assert truth > base + 0.5, (truth, base)                         # the generating function itself wins by a wide margin: no luck needed

@@ -1,8 +1,9 @@
 """GPU: per-row likelihood weights (tbnn_set_row_weights) on every kernel family -- narrow fast3 and fast, mid, tall, wide, the layered
 family on each of its likelihood kernels (k_lay_tail, k_lay_last, k_lay_lik) and the generic kernel -- with the Gaussian, Bernoulli and
 categorical likelihoods.  All-ones weights against the unweighted handle bit for bit (value, gradient, a traced injected weight transition,
-an injected hyper transition); integer weights against the rows repeated; real weights against an fp64 reference written here on the
-oracle's forward pass and priors (value, gradient per tensor, a Gaussian hyper transition that depends on the weighted S and on W); the
+an injected hyper transition); integer weights against the rows repeated; real weights against the fp64 oracle's weighted targets
+(o.target_log_prob_and_grad and o.hyper_step with w=: value, gradient per tensor, a Gaussian hyper transition that depends on the
+weighted S and on W); the
 refusals of bad weights, of a TBNN_KERNEL_FAST handle without a weighted table (which keeps its kernels) and of row sharding in either
 order; clearing, and set_data dropping them; an untraced small weighted problem on the per-step kernels; several chains behind one handle
 against solo chains; trainChains against solo train runs; an imbalanced Bernoulli fit."""
@@ -10,11 +11,11 @@ import numpy as np
 import pytest
 
 import tbnn_oracle as o
-from test_gpu_freerun import layers_of, SEED
+from tensor_checks import layers_of, tensor_err
+from test_gpu_freerun import SEED
 
 pytestmark = pytest.mark.gpu
 
-LIK_CAT = 3                      # include/tbnn.h TBNN_LIK_CATEGORICAL
 NARROW3, NARROW = "fast,mid,tall,wide", "fast3,mid,tall,wide"
 MID, TALL, WIDE = "fast3,fast,tall,wide", "fast3,fast,mid,wide", "fast3,fast,mid,tall"
 
@@ -26,26 +27,26 @@ CASES = {
     "fast_bern": ([4, 24, 24, 2], 1001, o.ACT_RELU, o.LIK_BERNOULLI, "fast", NARROW),
     "mid_gauss": ([30, 80, 80, 10], 3001, o.ACT_RELU, o.LIK_GAUSSIAN, "mid", MID),
     "mid_bern": ([20, 64, 64, 2], 1999, o.ACT_RELU, o.LIK_BERNOULLI, "mid", MID),
-    "mid_cat": ([30, 80, 80, 10], 3001, o.ACT_RELU, LIK_CAT, "mid", MID),
+    "mid_cat": ([30, 80, 80, 10], 3001, o.ACT_RELU, o.LIK_CATEGORICAL, "mid", MID),
     "tall_gauss": ([784, 20, 20, 1], 1205, o.ACT_RELU, o.LIK_GAUSSIAN, "tall", TALL),
-    "tall_cat": ([784, 20, 20, 10], 1205, o.ACT_RELU, LIK_CAT, "tall", TALL),
+    "tall_cat": ([784, 20, 20, 10], 1205, o.ACT_RELU, o.LIK_CATEGORICAL, "tall", TALL),
     "tall_bern": ([784, 20, 20, 2], 1205, o.ACT_RELU, o.LIK_BERNOULLI, "tall", TALL),
     "wide_gauss": ([10, 200, 200, 10], 3001, o.ACT_RELU, o.LIK_GAUSSIAN, "wide", WIDE),
-    "wide_cat": ([10, 200, 200, 10], 3001, o.ACT_RELU, LIK_CAT, "wide", WIDE),
+    "wide_cat": ([10, 200, 200, 10], 3001, o.ACT_RELU, o.LIK_CATEGORICAL, "wide", WIDE),
     "wide_bern": ([10, 200, 200, 2], 3001, o.ACT_RELU, o.LIK_BERNOULLI, "wide", WIDE),
     "lay_tail_gauss": ([784, 20, 20, 10], 1205, o.ACT_RELU, o.LIK_GAUSSIAN, "layered", {}),                      # k_lay_tail
     "lay_tail_bern": ([784, 20, 20, 10], 1205, o.ACT_RELU, o.LIK_BERNOULLI, "layered", {}),
-    "lay_tail_cat": ([784, 20, 20, 10], 1205, o.ACT_RELU, LIK_CAT, "layered", {}),                              # cat_delta<TT, true>
-    "lay_tail_cat_k20": ([9, 30, 20], 450, o.ACT_TANH, LIK_CAT, "layered", {}),                                # k_lay_tail, two tiles
-    "lay_last_cat": ([784, 100, 100, 10], 1205, o.ACT_RELU, LIK_CAT, "layered", {}),                             # k_lay_last
+    "lay_tail_cat": ([784, 20, 20, 10], 1205, o.ACT_RELU, o.LIK_CATEGORICAL, "layered", {}),                              # cat_delta<TT, true>
+    "lay_tail_cat_k20": ([9, 30, 20], 450, o.ACT_TANH, o.LIK_CATEGORICAL, "layered", {}),                                # k_lay_tail, two tiles
+    "lay_last_cat": ([784, 100, 100, 10], 1205, o.ACT_RELU, o.LIK_CATEGORICAL, "layered", {}),                             # k_lay_last
     "lay_last_gauss": ([784, 100, 100, 10], 1205, o.ACT_RELU, o.LIK_GAUSSIAN, "layered", {}),
     "lay_last_bern": ([784, 100, 100, 10], 1205, o.ACT_RELU, o.LIK_BERNOULLI, "layered", {}),
     "lay_lik_gauss": ([784, 100, 100, 10], 1205, o.ACT_RELU, o.LIK_GAUSSIAN, "layered", {"TBNN_LAY_LAST": "0"}),  # k_lay_lik
     "lay_lik_bern": ([784, 100, 100, 10], 1205, o.ACT_RELU, o.LIK_BERNOULLI, "layered", {"TBNN_LAY_LAST": "0"}),  # k_lay_lik
-    "lay_lik_cat": ([20, 64, 64, 20], 1500, o.ACT_TANH, LIK_CAT, "layered", {}),                                 # k_lay_lik, K > 16
+    "lay_lik_cat": ([20, 64, 64, 20], 1500, o.ACT_TANH, o.LIK_CATEGORICAL, "layered", {}),                                 # k_lay_lik, K > 16
     "generic_gauss": ([5, 16, 16, 4], 517, o.ACT_TANH, o.LIK_GAUSSIAN, "generic", {}),
     "generic_bern": ([5, 16, 16, 1], 517, o.ACT_TANH, o.LIK_BERNOULLI, "generic", {}),
-    "generic_cat": ([5, 16, 16, 4], 517, o.ACT_TANH, LIK_CAT, "generic", {}),
+    "generic_cat": ([5, 16, 16, 4], 517, o.ACT_TANH, o.LIK_CATEGORICAL, "generic", {}),
 }
 
 
@@ -65,7 +66,7 @@ def jit_jobs():
         jobs.append({"layers": layers, "likelihood": lik, "skip": skip, "flags": "", "weighted": True})
         if name != "fast3_configs1":
             jobs.append({"layers": layers, "likelihood": lik, "skip": skip, "flags": ""})
-    for spec, lik in ((blob_spec(), LIK_CAT), (bern_spec(), o.LIK_BERNOULLI)):
+    for spec, lik in ((blob_spec(), o.LIK_CATEGORICAL), (bern_spec(), o.LIK_BERNOULLI)):
         for w in (True, False):
             jobs.append({"layers": [list(l) for l in layers_of(spec)], "likelihood": lik, "skip": "", "flags": "", "weighted": w})
     jobs.append({"layers": [list(l) for l in layers_of(traj_spec())], "likelihood": o.LIK_GAUSSIAN, "skip": NARROW3, "flags": "", "weighted": True})
@@ -78,7 +79,7 @@ def traj_spec():
 
 
 def blob_spec():
-    return o.make_spec([2, 16, 16, 3], o.ACT_RELU, o.PRIOR_CAUCHY, LIK_CAT, o.ACT_NONE)
+    return o.make_spec([2, 16, 16, 3], o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, o.ACT_NONE)
 
 
 def bern_spec():
@@ -100,7 +101,7 @@ def problem(name, n=None):
     spec = spec_of(name)
     if dims[0] > 64:
         X = (X / np.sqrt(dims[0] / 16.0)).astype(np.float32)          # keep a long fan-in's pre-activations O(1)
-    if lik == LIK_CAT:
+    if lik == o.LIK_CATEGORICAL:
         Y = np.eye(dims[-1], dtype=np.float32)[np.argmax(Y, axis=1)]
         eta = eta[:spec.n_hypers]
     return spec, X, np.asarray(Y, np.float32), theta, np.asarray(eta, np.float32)
@@ -232,14 +233,6 @@ def test_refused_fast_handle_keeps_its_kernels(native, monkeypatch):
     assert np.isfinite(out["log_accept_ratio"]) and np.all(np.isfinite(ch.get_state()))
 
 
-def tensor_max_err(spec, a, b):
-    out = []
-    for l, (ow, ob) in zip(spec.layers, spec.offsets()):
-        for s, e in ((ow, ob), (ob, ob + l.out_dim)):
-            out.append((np.abs(a[s:e] - b[s:e]).max(), np.abs(b[s:e]).max()))
-    return out
-
-
 @pytest.mark.parametrize("name", ["fast3_configs1", "fast_gauss", "mid_bern", "mid_cat", "tall_gauss", "wide_cat", "lay_tail_bern",
                                   "lay_last_cat", "lay_lik_bern", "generic_gauss"])
 def test_integer_weights_equal_repeated_rows(native, monkeypatch, name):
@@ -255,8 +248,7 @@ def test_integer_weights_equal_repeated_rows(native, monkeypatch, name):
     lw, gw, _ = ch_w.logp_grad(theta, eta)
     lr, gr, _ = ch_r.logp_grad(theta, eta)
     assert abs(lw - lr) <= 1e-5 * max(abs(lr), 1.0), (name, lw, lr)
-    for err, scale in tensor_max_err(spec, gw, gr):
-        assert err <= 1e-4 * max(scale, 1e-3), (name, err, scale)
+    assert tensor_err(spec, gw, gr, 1e-3) <= 1e-4, name
     p0 = np.random.default_rng(6).standard_normal(spec.n_params).astype(np.float32)
     for log_u in (-1e30, 1e30):
         for ch in (ch_w, ch_r):
@@ -264,42 +256,6 @@ def test_integer_weights_equal_repeated_rows(native, monkeypatch, name):
         a, b = ch_w.hmc_step(2e-5, 3, p0=p0, log_u=log_u), ch_r.hmc_step(2e-5, 3, p0=p0, log_u=log_u)
         assert a["accepted"] == b["accepted"] == (log_u < 0)
     ch_w.close(); ch_r.close()
-
-
-def weighted_value_and_grad(spec, theta, eta, X, Y, w):
-    """fp64: the layer priors + the weighted data term (Gaussian: n -> W, S -> sum w r^2; Bernoulli / categorical: sum_i w_i term_i) and its
-    gradient (the output-layer delta of row i times w_i)"""
-    dt = np.float64
-    theta, eta, w = np.asarray(theta, dt), np.asarray(eta, dt), np.asarray(w, dt)
-    parts = o.unflatten(spec, theta)
-    f, acts = o.forward(spec, theta, X, dt, keep=True)
-    y = np.asarray(Y, dt).reshape(f.shape[1], -1).T                   # [d_out, n]
-    lp = sum(o.layer_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt) for i, (l, (W, b)) in enumerate(zip(spec.layers, parts)))
-    if spec.likelihood in (o.LIK_GAUSSIAN, o.LIK_FIXED_GAUSSIAN):
-        s = min(max(float(o.likelihood_sigma(spec, eta, dt)), 1e-8), 1e8)
-        W_, d = w.sum(), f.shape[0]
-        lp += -0.5 * (2 * W_ * d * np.log(s) + np.sum(w * (y - f) ** 2) / s ** 2 + W_ * d * np.log(2 * np.pi))
-        d_a = w * (y - f) / s ** 2
-    elif spec.likelihood == o.LIK_BERNOULLI:
-        p = np.clip(f, 1e-8, 1 - 1e-7)
-        lp += np.sum(w * (np.where(y == 0, 0.0, y * np.log(p)) + np.where(y == 1, 0.0, (1 - y) * np.log1p(-p))))
-        inside = (f >= 1e-8) & (f <= 1 - 1e-7)
-        d_a = w * np.where(inside, y / p - (1 - y) / (1 - p), 0.0)
-    else:
-        z = f - f.max(axis=0, keepdims=True)
-        ls = z - np.log(np.exp(z).sum(axis=0, keepdims=True))
-        lp += np.sum(w * y * ls)
-        d_a = w * (y - np.exp(ls) * y.sum(axis=0, keepdims=True))
-    grads = [None] * len(spec.layers)
-    for i in range(len(spec.layers) - 1, -1, -1):
-        l = spec.layers[i]
-        W, b = parts[i]
-        delta = d_a * o.act_grad_from_output(acts[i + 1], l.act)
-        pW, pb = o.prior_grad(l, eta[4 * i:4 * i + 4], W, b, dt)
-        grads[i] = (delta @ acts[i].T + pW, delta.sum(axis=1, keepdims=True) + pb)
-        if i > 0:
-            d_a = W.T @ delta
-    return lp, o.flatten(grads)
 
 
 def real_weights(n, seed=3):
@@ -322,10 +278,9 @@ def test_real_weights_against_fp64(native, monkeypatch, name):
     assert "weighted" in ch.kernel_name
     lp, g, _ = ch.logp_grad(theta, eta)
     assert np.array_equal(g, ch.logp_grad(theta, eta)[1])
-    lp64, g64 = weighted_value_and_grad(spec, theta, eta, X, Y, w)
+    lp64, g64 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64, w=w)
     assert np.isfinite(lp) and abs(lp - lp64) <= 4e-6 * max(abs(lp64), 1.0), (name, lp, lp64)
-    for err, scale in tensor_max_err(spec, g, g64):
-        assert err <= 1e-4 * max(scale, 1e-3), (name, err, scale)
+    assert tensor_err(spec, g, g64, 1e-3) <= 1e-4, name
     ch.close()
 
 
@@ -343,22 +298,11 @@ def test_weighted_gaussian_hyper_transition(native, monkeypatch, name):
     eta = eta.copy()
     eta[-1] = np.float32((S / (W_ * d)) ** 0.25)          # sd near its weighted optimum: a gentle trajectory fp32 and fp64 agree on
     ch.set_state(theta); ch.set_hypers(eta)
-    prior_spec = o.make_spec([l.in_dim for l in spec.layers] + [spec.layers[-1].out_dim], spec.layers[0].act, o.PRIOR_CAUCHY,
-                             o.LIK_FIXED_GAUSSIAN, spec.layers[-1].act)
-
-    def vg(e):
-        e = np.asarray(e, np.float64)
-        v, g = o.hyper_log_prob_and_grad(prior_spec, e[:-1], theta, X, Y, np.float64)      # the layer hyper-priors alone
-        s_raw = e[-1] ** 2
-        s = min(max(s_raw, 1e-8), 1e8)
-        v = v + -0.5 * (2 * W_ * d * np.log(s) + S / s ** 2 + W_ * d * np.log(2 * np.pi))
-        ds = 0.0 if not 1e-8 < s_raw < 1e8 else -W_ * d / s + S / s ** 3
-        return v, np.concatenate([g, [ds * 2 * e[-1]]])
     ph = np.random.default_rng(8).standard_normal(len(eta)).astype(np.float32)
     for log_u in (-1e30, 1e30):
         ch.set_state(theta); ch.set_hypers(eta)
         out = ch.hyper_step(1e-5, 4, p0=ph, log_u=log_u)
-        ref = o.hmc_step(vg, eta, 1e-5, 4, ph, log_u, np.float64)
+        ref = o.hyper_step(spec, eta, theta, X, Y, 1e-5, 4, ph, log_u, np.float64, S=S, w=w)
         assert bool(out["accepted"]) == ref.accepted == (log_u < 0)
         assert abs(out["log_accept_ratio"] - ref.log_accept_ratio) <= 1e-2 + 1e-4 * abs(ref.log_accept_ratio)
         assert np.abs(ch.get_hypers() - ref.theta).max() <= 1e-5 * max(1.0, np.abs(ref.theta).max())
@@ -401,7 +345,8 @@ import tbnn_oracle as o
 from tensorbnn_amd import _native as nat, parallel
 from tensorbnn_amd._native import TbnnError
 from test_gpu_row_weights import problem, spec_of, real_weights
-from test_gpu_freerun import layers_of, SEED
+from tensor_checks import layers_of
+from test_gpu_freerun import SEED
 
 
 def refused(fn, what):

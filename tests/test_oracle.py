@@ -3,7 +3,8 @@
 The reference supplies no golden vectors and cannot be imported (no TensorFlow),
 so the oracle is pinned by: scipy closed forms for the density helpers (with the
 reference's quirks Q1/Q2 asserted as deltas), torch.autograd (fp64) for every
-hand-coded gradient, HMC invariants, the committed fixtures (tests/golden) and
+hand-coded gradient (the extensions beyond the reference -- the categorical and
+Poisson likelihoods, row weights -- have nothing else), HMC invariants, the committed fixtures (tests/golden) and
 agreement between the NumPy and the C restatement.
 """
 import math
@@ -58,11 +59,13 @@ def test_mvn_diag_scalar_vs_scipy():
 
 
 # ---------------------------------------------------------------- gradients vs torch.autograd (fp64)
-def _torch_target(spec, theta, eta, X, Y):
+def _torch_target(spec, theta, eta, X, Y, w=None):
+    """w: row weights of the likelihood term (None: every row counts once)"""
     import torch
     th = torch.tensor(np.asarray(theta, dtype=np.float64), requires_grad=True)
     et = torch.tensor(np.asarray(eta, dtype=np.float64), requires_grad=True)
     Xt, Yt = torch.tensor(X, dtype=torch.float64), torch.tensor(Y, dtype=torch.float64)
+    wt = torch.ones(len(X), dtype=torch.float64) if w is None else torch.tensor(np.asarray(w, dtype=np.float64))
 
     def N(loc, sc):
         return torch.distributions.Normal(torch.tensor(loc, dtype=torch.float64), torch.tensor(sc, dtype=torch.float64))
@@ -88,11 +91,16 @@ def _torch_target(spec, theta, eta, X, Y):
         if spec.likelihood == o.LIK_BERNOULLI:
             p = torch.clamp(f, 1e-8, 1 - 1e-7)
             y = Yt.reshape(-1, f.shape[0]).T
-            return (torch.xlogy(y, p) + torch.xlogy(1 - y, 1 - p)).sum()
-        s = torch.clamp(et[-1] ** 2, 1e-8, 1e8) if spec.likelihood == o.LIK_GAUSSIAN else torch.tensor(spec.fixed_sd, dtype=torch.float64)
+            return (wt * (torch.xlogy(y, p) + torch.xlogy(1 - y, 1 - p))).sum()
         y = Yt.reshape(f.shape[1], -1).T
-        n_el = f.numel()
-        return -0.5 * (2 * n_el * torch.log(s) + (((y - f) / s) ** 2).sum() + n_el * math.log(2 * math.pi))
+        if spec.likelihood == o.LIK_CATEGORICAL:
+            return (wt * y * torch.log_softmax(f, dim=0)).sum()
+        if spec.likelihood == o.LIK_POISSON:
+            return (wt * (y * f - torch.exp(f) - torch.lgamma(y + 1))).sum()
+        assert spec.likelihood in (o.LIK_GAUSSIAN, o.LIK_FIXED_GAUSSIAN)
+        s = torch.clamp(et[-1] ** 2, 1e-8, 1e8) if spec.likelihood == o.LIK_GAUSSIAN else torch.tensor(spec.fixed_sd, dtype=torch.float64)
+        n_el = wt.sum() * f.shape[0]                     # (unweighted: f.numel(), exactly)
+        return -0.5 * (2 * n_el * torch.log(s) + (wt * ((y - f) / s) ** 2).sum() + n_el * math.log(2 * math.pi))
 
     def run(hyper):
         a = Xt.T
@@ -179,6 +187,117 @@ def test_hand_coded_gradients_match_autograd_last_activation(case):
     hl, hg = o.hyper_log_prob_and_grad(spec, eta, theta, X, Y, np.float64)
     assert abs(hl - hl_t) <= 1e-10 * abs(hl_t)
     np.testing.assert_allclose(hg, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
+
+
+# the extensions beyond the reference (the categorical and Poisson likelihoods, per-row likelihood weights): autograd is all that pins them
+EXT_CASES = {
+    # dims, rows, hidden activation, prior, likelihood, targets, weighted
+    "cat_onehot": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "onehot", False),
+    "cat_soft": ([4, 12, 12, 3], 80, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_CATEGORICAL, "soft", False),
+    "cat_large_logits": ([4, 12, 12, 3], 80, o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "large", False),
+    "pois": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_POISSON, "counts", False),
+    "pois_gaussian_prior": ([3, 12, 9, 2], 60, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_POISSON, "counts", False),
+    "weighted_gauss": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_GAUSSIAN, None, True),
+    "weighted_fixed_gauss": ([3, 12, 9, 2], 60, o.ACT_RELU, o.PRIOR_GAUSSIAN, o.LIK_FIXED_GAUSSIAN, None, True),
+    "weighted_bern": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_BERNOULLI, None, True),
+    "weighted_cat": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "soft", True),
+    "weighted_pois": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_POISSON, "counts", True),
+}
+
+
+def _ext_problem(case):
+    dims, n, act, prior, lik, targets, weighted = EXT_CASES[case]
+    if lik in (o.LIK_CATEGORICAL, o.LIK_POISSON):
+        _g, X, Yr, theta, eta = o.synth_problem(dims, n, act, prior, o.LIK_GAUSSIAN)        # standardised teacher outputs [n, K]
+        spec = o.make_spec(dims, act, prior, lik, o.ACT_NONE)
+        eta = eta[:spec.n_hypers]                                                           # no likelihood hyper
+    else:
+        spec, X, Y, theta, eta = o.synth_problem(dims, n, act, prior, lik)
+    ow, _ob = spec.offsets()[-1]
+    theta = theta.astype(np.float64)
+    if lik == o.LIK_CATEGORICAL:
+        e = np.exp(2.0 * Yr - (2.0 * Yr).max(axis=1, keepdims=True))
+        Y = e / e.sum(axis=1, keepdims=True) if targets == "soft" else np.eye(dims[-1])[np.argmax(Yr, axis=1)]
+        if targets == "large":           # the last layer scaled until the logits pass +-70: exp(f) without the max shift overflows in fp32
+            theta[ow:] *= 80.0 / np.abs(o.forward(spec, theta, X, np.float64)).max()
+            assert np.abs(o.forward(spec, theta, X, np.float64)).max() > 70
+    if lik == o.LIK_POISSON:
+        Y = np.random.default_rng(11).poisson(np.exp(np.clip(1.5 + 1.5 * Yr, -3.0, 6.0))).astype(np.float64)
+        Y[::5] = 0.0                     # zero counts
+        Y[1::5] += 0.5                   # counts need not be integers: lgamma(y + 1)
+        f = o.forward(spec, theta, X, np.float64)
+        if np.abs(f).max() > 5.0:        # the state's own log-rates within [-5, 5]
+            theta[ow:] *= 5.0 / np.abs(f).max()
+        assert np.abs(o.forward(spec, theta, X, np.float64)).max() <= 5.0 + 1e-9 and (Y == 0).any() and (Y % 1 != 0).any()
+    return spec, X, np.asarray(Y, np.float64), theta, eta, (_real_weights(n) if weighted else None)
+
+
+def _real_weights(n, seed=3):
+    """the recipe of tests/test_gpu_row_weights.py: gamma-distributed, every seventh weight 0"""
+    w = np.random.default_rng(seed).gamma(0.7, 1.5, n).astype(np.float32)
+    w[::7] = 0.0
+    return w
+
+
+@pytest.mark.parametrize("case", list(EXT_CASES))
+def test_extension_gradients_match_autograd(case):
+    spec, X, Y, theta, eta, w = _ext_problem(case)
+    eta = (eta + 0.05 * np.random.default_rng(1).standard_normal(eta.size)).astype(np.float32)
+    lp_t, g_t, hl_t, hg_t = _torch_target(spec, theta, eta, X, Y, w)
+    lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64, w=w)
+    assert abs(lp - lp_t) <= 1e-10 * abs(lp_t)
+    assert lp == o.target_log_prob(spec, theta, eta, X, Y, np.float64, w=w)
+    np.testing.assert_allclose(g, g_t, rtol=1e-9, atol=1e-9 * np.abs(g_t).max())
+    hl, hg = o.hyper_log_prob_and_grad(spec, eta, theta, X, Y, np.float64, w=w)
+    assert abs(hl - hl_t) <= 1e-10 * abs(hl_t) and hl == o.hyper_log_prob(spec, eta, theta, X, Y, np.float64, w=w)
+    np.testing.assert_allclose(hg, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
+    if spec.likelihood == o.LIK_GAUSSIAN:        # the weighted closed form: S = sum_i w_i sum_k (y - f)^2, n = sum(w) d_out
+        f = o.forward(spec, theta, X, np.float64)
+        S = np.sum(w.astype(np.float64) * (Y.T - f) ** 2)
+        hl2, hg2 = o.hyper_log_prob_and_grad(spec, eta, theta, X, Y, np.float64, S=S, w=w)
+        assert abs(hl2 - hl_t) <= 1e-10 * abs(hl_t)
+        np.testing.assert_allclose(hg2, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
+
+
+@pytest.mark.parametrize("case", ["weighted_gauss", "weighted_fixed_gauss", "weighted_bern", "weighted_cat", "weighted_pois"])
+def test_integer_weights_are_repeated_rows(case):
+    spec, X, Y, theta, eta, _w = _ext_problem(case)
+    w = np.random.default_rng(11).integers(0, 4, len(X))
+    assert (w == 0).any() and (w == 3).any()
+    Xr, Yr = np.repeat(X, w, axis=0), np.repeat(Y, w, axis=0)
+    lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64, w=w)
+    lp_r, g_r = o.target_log_prob_and_grad(spec, theta, eta, Xr, Yr, np.float64)
+    assert abs(lp - lp_r) <= 1e-12 * abs(lp_r)
+    np.testing.assert_allclose(g, g_r, rtol=0, atol=1e-12 * np.abs(g_r).max())
+    hl, hg = o.hyper_log_prob_and_grad(spec, eta, theta, X, Y, np.float64, w=w)
+    hl_r, hg_r = o.hyper_log_prob_and_grad(spec, eta, theta, Xr, Yr, np.float64)
+    assert abs(hl - hl_r) <= 1e-12 * abs(hl_r)
+    np.testing.assert_allclose(hg, hg_r, rtol=0, atol=1e-12 * np.abs(hg_r).max())
+
+
+@pytest.mark.parametrize("case", ["weighted_cat", "weighted_pois"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_unit_weights_are_exactly_unweighted(case, dtype):
+    spec, X, Y, theta, eta, _w = _ext_problem(case)
+    lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, dtype)
+    lp1, g1 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, dtype, w=np.ones(len(X), np.float32))
+    assert lp1 == lp and np.array_equal(g1, g)
+
+
+@pytest.mark.parametrize("code", [4, 6, -1])
+def test_unknown_likelihood_code_raises(code):
+    """a code the oracle does not know is an error in every target, never another likelihood's chain"""
+    spec, X, Y, theta, eta = o.synth_problem([3, 5, 2], 10, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_FIXED_GAUSSIAN)
+    spec.likelihood = code
+    f = o.forward(spec, theta, X, np.float64)
+    for call in (lambda: o.log_likelihood(spec, eta, f, Y, np.float64),
+                 lambda: o.target_log_prob(spec, theta, eta, X, Y, np.float64),
+                 lambda: o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64),
+                 lambda: o.hyper_log_prob(spec, eta, theta, X, Y, np.float64),
+                 lambda: o.hyper_log_prob_and_grad(spec, eta, theta, X, Y, np.float64),
+                 lambda: o.weight_step(spec, theta, eta, X, Y, 1e-3, 2, np.zeros_like(theta), -1.0, np.float64)):
+        with pytest.raises(ValueError):
+            call()
 
 
 def _tie_problem(last):
