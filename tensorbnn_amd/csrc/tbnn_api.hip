@@ -78,6 +78,8 @@ struct Owned {
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 using Event = Owned<hipEvent_t, hipEventDestroy>;
 
+#include "backend.hpp"                    // the kernel families (it uses the kernel headers, Buf, fail and HIPCHK above)
+
 struct tbnn_comm {
     ncclComm_t comm = nullptr;
     int world = 1, rank = 0;
@@ -92,10 +94,7 @@ struct tbnn_ctx {
     uint32_t key0 = 0, key1 = 0, epoch = 0;
     int C = 1;                            // chains of this handle (tbnn_create_multi): every per-chain buffer is a [C][...] array, the per-chain
     uint32_t seed_hi = 0;                 // kernels run with gridDim.y = C; chain c draws from the Philox key (seed, chain_id + c)
-    const FusedOps* ops = nullptr;        // the fused kernels of this shape: an ahead-of-time table (aot_ops.hpp) or a registered library
-    bool lay = false; LayPlan lplan{}; Buf<float> lstore;   // kernels_layered.hpp: run-time-shape MFMA kernels, activations through HBM
-    Buf<float> lfwd;                      // its forward-only store (predict / metrics / ensembles): pooled, grown as needed
-    std::string kernel_name;
+    std::unique_ptr<Backend> be;          // the kernel family of this shape (backend.hpp: select_kernels), with its plan and private buffers
     // data: the rows tbnn_set_data staged (Xown / Yown), or the caller's (tbnn_set_data_device: borrowed)
     Buf<float> Xown, Yown; const float* dX = nullptr; const float* dY = nullptr; long n = 0;
     // row weights (tbnn_set_row_weights): [n x d_out targets | n weights] in one buffer -- what the kernels read as Y while weights are
@@ -113,16 +112,12 @@ struct tbnn_ctx {
     Buf<float> gd, gd_cur, eta_prev;      // data-term gradient of the proposal / current state; eta before a hyper step
     bool cur_valid = false;               // (logp, grad, stat) cached at q_cur for the current eta/data
     bool q_img_valid = false;             // h->qimg mirrors h->q (maintained by k_update)
-    // fused-pass workspace
-    int grid = 0, pitch = 0; Buf<float> slabs; Buf<double> pstat; Buf<float> scratch;
-    // wide-layer family (kernels_wide.hpp): its own workspace
-    WidePlan wplan; Buf<float> wstore, wslabA, wslabB;
-    int nslab = 0;                        // gradient slabs k_update reduces (wide: 1, already reduced)
+    // fused-pass workspace common to all families (alloc_workspace): grid = statistic entries in use, nslab = gradient slabs k_update reduces
+    int grid = 0, pitch = 0, nslab = 0; Buf<float> slabs; Buf<double> pstat;
     // row-sharded chain (tbnn_set_row_shard): all-reduce of the dense data-term gradient row + statistic
     tbnn_comm* shard = nullptr; long n_total = 0; Buf<float> grow; Buf<double> pstat_red;
     Buf<double> shard_buf;                // the all-reduce operand: P gradient values + the statistic, as doubles
-    Buf<int> imgmap; Buf<float> qimg, qimg_cur; int img_floats = 0;   // ops / layered: padded weight images
-    size_t scratchPerWG = 0;
+    Buf<int> imgmap; Buf<float> qimg, qimg_cur; int img_floats = 0;   // padded weight images of a backend that reads them (be->img_floats())
     float* pin_dev = nullptr;              // device-side address of pin
     PinBuf<float> pin;                     // pinned staging for the per-epoch state read-back (P + H floats): a 22-KB D2H copy
                                            // into pageable memory costs ~180 us, through pinned memory ~15 us
@@ -286,13 +281,12 @@ extern "C" int tbnn_create_multi(const tbnn_net_desc* desc, int device, uint64_t
     return create_impl(desc, device, seed, chain_id, n_chains, out);
 }
 extern "C" int tbnn_chain_count(tbnn_handle h) { NEED(h); return h->C; }
-// the handle's kernels: a FusedOps table (weighted: a registered weighted one), else the layered family (TBNN_KERNEL_AUTO), else the
-// thread-per-row kernel; with the weight image map and the padded images of the chosen kernels.  tbnn_create, and tbnn_set_row_weights /
+// the handle's backend: a FusedOps table (weighted: a registered weighted one), else the layered family (TBNN_KERNEL_AUTO), else the
+// thread-per-row kernel; with the weight image map and the padded images it reads.  tbnn_create, and tbnn_set_row_weights /
 // tbnn_set_data when the weights come or go (the caller re-allocates the fused-pass workspace when data are staged).  A refusal
-// (TBNN_KERNEL_FAST without a table) is decided before the handle is touched: it keeps its kernels, images and workspace.
+// (TBNN_KERNEL_FAST without a table) is decided before the handle is touched: it keeps its backend, images and workspace.
 static int select_kernels(tbnn_ctx* h, bool weighted) {
     const NetDev& nd = h->nd;
-    const size_t NC = (size_t)h->C;
     const int want = h->want;
     // TBNN_MID=0 (diagnostic / A-B runs): shapes both families cover take the wide path (two kernels through HBM)
     const FusedOps* ops = find_ops(nd, !env_off("TBNN_MID"), weighted);
@@ -300,28 +294,23 @@ static int select_kernels(tbnn_ctx* h, bool weighted) {
         return fail(-1, weighted ? "TBNN_KERNEL_FAST requested but no weighted kernel library is registered for this shape (jit.ensure_registered(..., weighted=True))"
                                  : "TBNN_KERNEL_FAST requested but no specialised kernel covers this shape");
     h->qimg.reset(); h->qimg_cur.reset(); h->imgmap.reset();
-    h->ops = nullptr; h->lay = false; h->img_floats = 0; h->q_img_valid = false; h->cur_valid = false;
-    h->kernel_name = "generic";
-    if (want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST) h->ops = ops;
-    // no shape-specialised kernel (and none registered at run time): the layered MFMA family takes any architecture
-    // (TBNN_LAYERED=0: the thread-per-row kernel, as before round 3)
-    h->lay = want == TBNN_KERNEL_AUTO && !ops && !env_off("TBNN_LAYERED");
-    if (h->ops) {
-        h->kernel_name = ops->name;
-        h->img_floats = ops->img_floats;
-    } else if (h->lay) {
-        lay_plan_shape(nd, h->lplan);
-        h->kernel_name = "layered<" + std::to_string(nd.in[0]);
-        for (int l = 0; l < nd.nl; ++l) h->kernel_name += "," + std::to_string(nd.out[l]);
-        h->kernel_name += weighted ? ",weighted>" : ">";
-        h->img_floats = h->lplan.img_floats;
-    } else if (weighted) {
-        h->kernel_name = "generic<weighted>";
+    h->be.reset();                                      // (with its workspace: never two backends' at once)
+    h->img_floats = 0; h->q_img_valid = false; h->cur_valid = false;
+    if (ops && (want == TBNN_KERNEL_AUTO || want == TBNN_KERNEL_FAST)) {
+        if (ops->family == TBNN_FAMILY_WIDE) h->be.reset(new (std::nothrow) WideBackend(nd, ops));
+        else h->be.reset(new (std::nothrow) FusedBackend(nd, ops));
+    } else if (want == TBNN_KERNEL_AUTO && !env_off("TBNN_LAYERED")) {
+        // no shape-specialised kernel (and none registered at run time): the layered MFMA family takes any architecture
+        h->be.reset(new (std::nothrow) LayeredBackend(nd, weighted));
+    } else {
+        h->be.reset(new (std::nothrow) GenericBackend(nd, weighted));     // TBNN_KERNEL_GENERIC, or TBNN_LAYERED=0
     }
-    if (h->ops || h->lay) {
+    if (!h->be) return fail(-4, "out of host memory");
+    h->img_floats = h->be->img_floats();
+    if (h->img_floats) {
         std::vector<int> map(2 * (size_t)nd.P);
-        if (h->ops) h->ops->image_map(map.data()); else lay_image_map(nd, h->lplan, map.data());
-        const size_t imgs = NC * (size_t)h->img_floats;
+        h->be->image_map(map.data());
+        const size_t imgs = (size_t)h->C * (size_t)h->img_floats;
         HIPCHK(h->imgmap.alloc(map.size()));
         HIPCHK(hipMemcpy(h->imgmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK(h->qimg.alloc(imgs));
@@ -395,7 +384,7 @@ static int create_impl(const tbnn_net_desc* desc, int device, uint64_t seed, uin
 
 extern "C" int tbnn_param_count(tbnn_handle h) { NEED(h); return h->nd.P; }
 extern "C" int tbnn_hyper_count(tbnn_handle h) { NEED(h); return h->nd.H; }
-extern "C" const char* tbnn_kernel_name(tbnn_handle h) { return h ? h->kernel_name.c_str() : ""; }
+extern "C" const char* tbnn_kernel_name(tbnn_handle h) { return h && h->be ? h->be->name() : ""; }
 extern "C" const char* tbnn_last_transition_path(tbnn_handle h) { return h ? h->last_path : ""; }
 extern "C" int tbnn_set_profiling(tbnn_handle h, int stride) {
     NEED(h);
@@ -409,52 +398,16 @@ extern "C" int tbnn_set_profiling(tbnn_handle h, int stride) {
 }
 extern "C" int tbnn_set_epoch(tbnn_handle h, uint32_t epoch) { NEED(h); h->epoch = epoch; return 0; }
 
-static inline bool is_wide(const tbnn_ctx* h) { return h->ops && h->ops->family == TBNN_FAMILY_WIDE; }
-
-// (re)allocate the fused-pass workspace for n rows
+// (re)allocate the fused-pass workspace for n rows: the backend's own, then what all families share
 static int alloc_workspace(tbnn_ctx* h, long n) {
     const NetDev& nd = h->nd;
-    h->slabs.reset(); h->pstat.reset(); h->scratch.reset();
-    h->wstore.reset(); h->wslabA.reset(); h->wslabB.reset();
-    int grid;
-    h->lstore.reset();
-    if (h->lay) {
-        lay_plan_rows(nd, n, h->lplan);
-        grid = h->lplan.NP;                       // entries of the statistic buffer in use; the gradient slabs: lplan.NS
-        h->scratchPerWG = 0;
-        HIPCHK(h->lstore.alloc((size_t)h->lplan.store_floats));
-        HIPCHK(hipMemsetAsync(h->lstore, 0, (size_t)h->lplan.store_floats * sizeof(float), h->stream));     // dz padding: written once, here
-        // a_0 = the rows in block form, once per data set
-        const long tot = h->lplan.ntiles * h->lplan.TK[0];
-        hipLaunchKernelGGL(k_lay_pack_x, dim3((int)std::min<long>(tot, 4096)), dim3(256), 0, h->stream, (const float*)h->dX, n, nd.d_in, h->lplan.TK[0],
-                           h->lplan.ntiles, h->lstore + h->lplan.aOff[0]);
-        HIPCHK(hipGetLastError());
-    } else if (is_wide(h)) {
-        h->ops->plan(n, &h->wplan);
-        grid = h->wplan.gridA;
-        h->scratchPerWG = 0;
-        HIPCHK(h->wstore.alloc(h->wplan.store_floats));
-        HIPCHK(h->wslabA.alloc(h->wplan.slabA_floats));
-        HIPCHK(h->wslabB.alloc(h->wplan.slabB_floats));
-    } else if (h->ops) {
-        grid = h->ops->grid(n);
-        // test hook: a smaller grid puts small row counts into the many-rounds + cooperative-tail regime of the big ones
-        if (const char* ge = getenv("TBNN_FAST_GRID")) { const int gg = atoi(ge); if (gg >= 1 && gg < grid) grid = gg; }
-        h->scratchPerWG = 0;
-    } else {
-        const long nblk = (n + GEN_RB - 1) / GEN_RB;
-        grid = (int)std::min<long>(nblk, 512);
-        h->scratchPerWG = generic_scratch_floats(nd);
-        HIPCHK(h->scratch.alloc(h->scratchPerWG * (size_t)grid));
-    }
-    // tbnn_forward always uses the generic forward kernel: keep a scratch for it
-    h->grid = grid;
+    h->slabs.reset(); h->pstat.reset();
+    if (const int rc = h->be->prepare(h->stream, h->dX, n, &h->grid, &h->nslab)) return rc;
     h->pitch = (nd.P + 3) & ~3;                  // float4-readable slabs
-    h->nslab = is_wide(h) ? 1 : (h->lay ? h->lplan.NS : grid);
     const size_t slab_floats = (size_t)h->C * h->nslab * h->pitch;
     HIPCHK(h->slabs.alloc(slab_floats));                                             // [C][nslab][pitch]
     HIPCHK(hipMemset(h->slabs, 0, slab_floats * sizeof(float)));
-    if (grid > PSTAT_CAP) return fail(-2, "grid exceeds PSTAT_CAP");
+    if (h->grid > PSTAT_CAP) return fail(-2, "grid exceeds PSTAT_CAP");
     HIPCHK(h->pstat.alloc((size_t)h->C * PSTAT_CAP));                                // [C][PSTAT_CAP]
     HIPCHK(hipMemset(h->pstat, 0, (size_t)h->C * PSTAT_CAP * sizeof(double)));      // entries >= grid stay zero
     HIPCHK(h->pstat_red.alloc(PSTAT_CAP));
@@ -745,10 +698,24 @@ static inline int stat_entries(const tbnn_ctx* h) { return h->shard ? 1 : h->gri
 // local statistic buffer: entries >= grid stay zero; the all-reduced copy is separate (ranks may have different grids)
 static inline const double* stat_ptr(const tbnn_ctx* h) { return h->shard ? h->pstat_red : h->pstat; }
 // the gradient slabs k_update reduces
-static inline const float* grad_slabs(const tbnn_ctx* h) { return (h->shard && !is_wide(h)) ? h->grow : h->slabs; }
+static inline const float* grad_slabs(const tbnn_ctx* h) { return (h->shard && !h->be->slab_is_grad_row()) ? h->grow : h->slabs; }
 static inline int grad_nslab(const tbnn_ctx* h) { return h->shard ? 1 : h->nslab; }
 
 // ---- launch helpers (all on h->stream, no sync) ----
+// an event pair from the pool around a launch, if this one is profiled (every h->profile-th): the opening event is recorded, the closing
+// one returned for the caller to record behind the launch (null: not profiled).  steps: leapfrog steps the launch covers
+static hipEvent_t profile_begin(tbnn_ctx* h, int steps) {
+    if (!(h->profile > 0 && (h->launch_no++ % h->profile) == 0)) return nullptr;
+    if (h->pev_used + 2 > h->pev.size()) {
+        hipEvent_t a = nullptr, b = nullptr;
+        hipEventCreate(&a); hipEventCreate(&b); h->pev.emplace_back(a); h->pev.emplace_back(b);
+    }
+    const hipEvent_t a = h->pev[h->pev_used], b = h->pev[h->pev_used + 1];
+    h->pev_used += 2;
+    h->pev_div.push_back(steps);
+    hipEventRecord(a, h->stream);
+    return b;
+}
 // q == h->q: the leapfrog position, whose padded image h->qimg is maintained by k_update;
 // any other q gets its image built here (h->qimg_cur).
 static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const StepCtl* ctl = nullptr, int t = 0) {
@@ -762,59 +729,28 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
             img = h->qimg_cur;
         }
     }
-    hipEvent_t a = nullptr, b = nullptr;
-    const bool prof = h->profile > 0 && (h->launch_no++ % h->profile) == 0;
-    if (prof) {
-        if (h->pev_used + 2 > h->pev.size()) {
-            hipEventCreate(&a); hipEventCreate(&b); h->pev.emplace_back(a); h->pev.emplace_back(b);
-        }
-        a = h->pev[h->pev_used]; b = h->pev[h->pev_used + 1]; h->pev_used += 2;
-        h->pev_div.push_back(1);
-        hipEventRecord(a, h->stream);
-    }
-    // the one-slab-per-workgroup families take all chains of a multi-chain handle in ONE launch (gridDim.y = chain); the others
-    // (two-kernel wide path, layered family, thread-per-row kernel: not what small problems run on) chain by chain through the
-    // same activation store
-    const ChainStride cs = {imgS, (long)h->nd.H, slabS, ctl, t};
-    // (the chain-by-chain families skip a chain past its own L on the host: ctl_host mirrors ctl)
-    auto done = [&](int c) { return ctl != nullptr && t > h->ctl_host[c].L; };
-    if (h->lay) {
-        for (int c = 0; c < C; ++c)
-            if (!done(c) && lay_launch(h->nd, h->lplan, h->stream, img + c * imgS, eta + (size_t)c * h->nd.H, pass_Y(h), h->n, h->lstore, h->slabs + c * slabS, h->pitch,
-                           h->pstat + (size_t)c * PSTAT_CAP, pass_w(h)))
-                return fail(-2, "layered kernel launch failed");
-    } else if (is_wide(h)) {
-        for (int c = 0; c < C; ++c) {
-            if (done(c)) continue;
-            const float* ic = img + c * imgS; const float* ec = eta + (size_t)c * h->nd.H;
-            double* pc = h->pstat + (size_t)c * PSTAT_CAP; float* sl = h->slabs + c * slabS;
-            if (h->ops->wlaunch(&h->wplan, h->stream, &h->nd, ic, ec, h->dX, pass_Y(h), h->n, h->wstore, h->wslabA, h->wslabB, pc, sl))
-                return fail(-2, h->kernel_name + ": launch failed");
-        }
-    } else if (h->ops) {
-        if (h->ops->launch(h->grid, h->stream, &h->nd, img, eta, h->dX, pass_Y(h), h->n, h->slabs, h->pitch, h->pstat, C, cs))
-            return fail(-2, h->kernel_name + ": launch failed");
-    } else {
-        for (int c = 0; c < C; ++c)
-            if (!done(c)) hipLaunchKernelGGL(k_fwd_bwd_generic, dim3(h->grid), dim3(GEN_RB), 0, h->stream, h->nd, q + (size_t)c * h->nd.P, eta + (size_t)c * h->nd.H, h->dX,
-                               pass_Y(h), h->n, h->scratch, h->scratchPerWG, h->slabs + c * slabS, h->pitch, h->pstat + (size_t)c * PSTAT_CAP, pass_w(h));
-    }
+    const hipEvent_t prof_end = profile_begin(h, 1);
+    // one gradient for all chains of the handle: the one-kernel fused tables in ONE launch (gridDim.y = chain), the other backends
+    // chain by chain through the same activation store (backend.hpp)
+    const PassArgs pa = {img, imgS, q, eta, (long)h->nd.H, h->dX, pass_Y(h), pass_w(h), h->n, h->slabs, slabS, h->pitch, h->pstat, C, ctl, t, h->ctl_host};
+    if (const int rc = h->be->fwd_bwd(h->stream, pa)) return rc;
     if (h->shard) {
         // ONE collective per fused pass: the dense data-term gradient row (P values; the wide path already has one) and the
         // statistic, summed to one value on the device, travel together as P + 1 doubles (the sum over the ranks is then
         // taken in double and rounded once; at configs[1]-class step times a second small all-reduce would cost as much as
         // the step), summed over the ranks in place, unpacked into the row k_update reads and pstat_red[0]
-        float* row = is_wide(h) ? h->slabs : h->grow;
+        const bool dense = h->be->slab_is_grad_row();
+        float* row = dense ? h->slabs : h->grow;
         const int P = h->nd.P;
-        if (!is_wide(h))
+        if (!dense)
             hipLaunchKernelGGL(k_slab_reduce, dim3((P + 63) / 64), dim3(64, 4), 0, h->stream, (const float*)h->slabs, h->nslab,
                                h->pitch, P, (float*)nullptr, h->shard_buf);
-        hipLaunchKernelGGL(k_shard_pack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, is_wide(h) ? (const float*)row : (const float*)nullptr,
+        hipLaunchKernelGGL(k_shard_pack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, dense ? (const float*)row : (const float*)nullptr,
                            (const double*)h->pstat, h->grid, h->shard_buf, h->lik_c);
         NCCLCHK(g_rccl.AllReduce(h->shard_buf, h->shard_buf, (size_t)P + 1, ncclDouble, ncclSum, h->shard->comm, h->stream));
         hipLaunchKernelGGL(k_shard_unpack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, (const double*)h->shard_buf, row, h->pstat_red);
     }
-    if (prof) hipEventRecord(b, h->stream);
+    if (prof_end) hipEventRecord(prof_end, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -861,6 +797,15 @@ static float drain_profile(tbnn_ctx* h) {
     return cnt ? (float)(tot / cnt) : 0.f;
 }
 
+// the weights a call evaluates at: the chain's own (theta == null), else theta copied into the proposal buffer h->q, whose image goes stale
+static int stage_theta(tbnn_ctx* h, const float* theta, const float** dq) {
+    *dq = h->q_cur;
+    if (!theta) return 0;
+    HIPCHK(hipMemcpyAsync(h->q, theta, (size_t)h->nd.P * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    *dq = h->q; h->q_img_valid = false;
+    return 0;
+}
+
 extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* eta, double* logp, float* grad,
                               double* stat) {
     NEED(h);
@@ -869,9 +814,9 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     HIPCHK(hipSetDevice(h->device));
     const NetDev& nd = h->nd;
     // evaluation happens on scratch copies (q, tmp-eta): the chain state is untouched
-    const float* dq = h->q_cur;
+    const float* dq = nullptr;
     const float* de = h->eta;
-    if (theta) { HIPCHK(hipMemcpyAsync(h->q, theta, (size_t)nd.P * sizeof(float), hipMemcpyHostToDevice, h->stream)); dq = h->q; h->q_img_valid = false; }
+    if (const int rc = stage_theta(h, theta, &dq)) return rc;
     if (eta) { HIPCHK(hipMemcpyAsync(h->tmp + nd.P, eta, (size_t)nd.H * sizeof(float), hipMemcpyHostToDevice, h->stream)); de = h->tmp + nd.P; }
     int rc = launch_fwd_bwd(h, dq, de);
     if (rc) return rc;
@@ -895,92 +840,19 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     return 0;
 }
 
-// the narrow family's forward-only kernel (fast3, mid and tall tables)
-static inline bool narrow_fwd_ok(const tbnn_ctx* h) { return h->ops && h->ops->nforward; }
-// `nets` networks whose images lie img_stride floats apart -> outputs out_stride floats apart
-static int narrow_forward(tbnn_ctx* h, int nets, const float* imgs, long img_stride, const float* dX, long n, float* dOut, long out_stride) {
-    const long ntiles = (n + 15) / 16, wgs = (ntiles + FAST_WAVES - 1) / FAST_WAVES;
-    // one network: fill the chip; an ensemble: the networks (grid.y) do that, fewer workgroups each re-use the image more
-    const long cap = nets >= 64 ? 16 : (nets >= 8 ? 64 : 256);
-    const int gx = (int)std::max<long>(1, std::min<long>(wgs, cap));
-    return h->ops->nforward(gx, nets, h->stream, imgs, img_stride, dX, n, dOut, out_stride);
-}
-
-// the layered family's forward chain (network.predict) on a store of its own: the rows are packed once, then any number of
-// networks run over them
-struct LayFwd { LayPlan pp{}; float* st = nullptr; long n = 0; };
-// (the store is pooled on the chain, like the record buffers of tbnn_hmc_run: network.train predicts and scores every displayed
-// epoch, and an allocation + a device synchronisation + a free per call is what that cost before round 4; everything runs in
-// order on the chain's one stream, so the next call may overwrite it)
-static int lay_fwd_prepare(tbnn_ctx* h, const float* dX, long n, LayFwd& lf) {
-    const NetDev& nd = h->nd;
-    lf.pp = h->lplan; lf.n = n;
-    lay_plan_rows(nd, n, lf.pp);
-    const size_t need = (size_t)(lf.pp.aOff[nd.nl] + lf.pp.ntiles * 256 * lf.pp.TM[nd.nl - 1]);
-    HIPCHK(h->lfwd.grow(need, need));
-    lf.st = h->lfwd;
-    hipLaunchKernelGGL(k_lay_pack_x, dim3((int)std::min<long>(lf.pp.ntiles * lf.pp.TK[0], 4096)), dim3(256), 0, h->stream, dX, n, nd.d_in, lf.pp.TK[0],
-                       lf.pp.ntiles, lf.st + lf.pp.aOff[0]);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-static int lay_fwd_run(tbnn_ctx* h, const LayFwd& lf, const float* q, float* dOut) {
-    const NetDev& nd = h->nd;
-    hipLaunchKernelGGL(k_make_image, dim3((nd.P + 255) / 256), dim3(256), 0, h->stream, nd.P, q, h->imgmap, h->qimg_cur, 0L, 0L);
-    lay_forward_chain(nd, lf.pp, h->stream, h->qimg_cur, lf.st);
-    hipLaunchKernelGGL(k_lay_unpack_f, dim3((int)std::min<long>(lf.pp.ntiles, 2048)), dim3(256), 0, h->stream, (const float*)(lf.st + lf.pp.aOff[nd.nl]), lf.n,
-                       lf.pp.ntiles, lf.pp.TM[nd.nl - 1], nd.d_out, dOut);
-    if (hipGetLastError() != hipSuccess) return fail(-2, "layered forward launch failed");
-    return 0;
-}
-
-// forward pass of the network at the weights q (device) over dX[n][d_in] -> dOut[d_out][n], on h->stream
-static int launch_forward(tbnn_ctx* h, const float* q, const float* dX, long n, float* dOut) {
-    const NetDev& nd = h->nd;
-    if (h->ops && h->ops->wforward) {
-        // MFMA forward (k_chain_wide<S, FWD>): needs the padded image of q
-        hipLaunchKernelGGL(k_make_image, dim3((nd.P + 255) / 256), dim3(256), 0, h->stream, nd.P, q, h->imgmap, h->qimg_cur);
-        if (h->ops->wforward(h->stream, &h->nd, h->qimg_cur, dX, n, dOut)) return fail(-2, "wide forward launch failed");
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (h->lay) {
-        LayFwd lf;
-        int rc = lay_fwd_prepare(h, dX, n, lf);
-        if (!rc) rc = lay_fwd_run(h, lf, q, dOut);
-        return rc;
-    }
-    if (narrow_fwd_ok(h)) {
-        // MFMA forward of the narrow family (k_forward_fast3): image of q, one network
-        hipLaunchKernelGGL(k_make_image, dim3((nd.P + 255) / 256), dim3(256), 0, h->stream, nd.P, q, h->imgmap, h->qimg_cur, 0L, 0L);
-        if (narrow_forward(h, 1, h->qimg_cur, 0, dX, n, dOut, 0)) return fail(-2, "fast3 forward launch failed");
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    const long nblk = (n + GEN_RB - 1) / GEN_RB;
-    const int grid = (int)std::min<long>(nblk, 512);
-    const size_t per = generic_scratch_floats(nd);
-    Buf<float> scr;
-    HIPCHK(scr.alloc(per * grid));
-    hipLaunchKernelGGL(k_forward_generic, dim3(grid), dim3(GEN_RB), 0, h->stream, nd, q, dX, n, scr, per, dOut);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
 extern "C" int tbnn_forward(tbnn_handle h, const float* theta, const float* X, int64_t n, float* out) {
     NEED(h);
     if (!theta) ONE_CHAIN(h, "tbnn_forward at the chain's own state");
     if (!X || !out || n < 1) return fail(-1, "forward: null pointer or n < 1");
     HIPCHK(hipSetDevice(h->device));
     const NetDev& nd = h->nd;
-    const float* dq = h->q_cur;
-    if (theta) { HIPCHK(hipMemcpyAsync(h->q, theta, (size_t)nd.P * sizeof(float), hipMemcpyHostToDevice, h->stream)); dq = h->q; h->q_img_valid = false; }
+    const float* dq = nullptr;
+    if (const int rc = stage_theta(h, theta, &dq)) return rc;
     Buf<float> dXf, dOut;
     HIPCHK(dXf.alloc((size_t)n * nd.d_in));
     HIPCHK(dOut.alloc((size_t)n * nd.d_out));
     HIPCHK(hipMemcpyAsync(dXf, X, (size_t)n * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (const int rc = launch_forward(h, dq, dXf, (long)n, dOut)) return rc;
+    if (const int rc = h->be->forward(h->stream, 1, dq, dXf, (long)n, dOut, h->imgmap, h->qimg_cur)) return rc;
     HIPCHK(hipMemcpyAsync(out, dOut, (size_t)n * nd.d_out * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
@@ -1007,12 +879,12 @@ static int predict_resident(tbnn_ctx* h, int which, const float* theta, long* n_
     const float* dX = which ? h->dXv : h->dX;
     const long n = which ? h->nv : h->n;
     if (!dX || n < 1) return fail(-1, which ? "tbnn_set_validation has not been called" : "tbnn_set_data has not been called");
-    const float* dq = h->q_cur;
-    if (theta) { HIPCHK(hipMemcpyAsync(h->q, theta, (size_t)nd.P * sizeof(float), hipMemcpyHostToDevice, h->stream)); dq = h->q; h->q_img_valid = false; }
+    const float* dq = nullptr;
+    if (const int rc = stage_theta(h, theta, &dq)) return rc;
     const size_t need = (size_t)n * nd.d_out;
     HIPCHK(h->fbuf.grow(need, need));
     *n_out = n;
-    return launch_forward(h, dq, dX, n, h->fbuf);
+    return h->be->forward(h->stream, 1, dq, dX, n, h->fbuf, h->imgmap, h->qimg_cur);
 }
 
 extern "C" int tbnn_predict(tbnn_handle h, int which, const float* theta, float* out) {
@@ -1059,7 +931,8 @@ static int ensemble_forward(tbnn_ctx* h, const std::string& who, const float* th
     if (rc) { hipStreamSynchronize(h->stream); return rc; }
     HIPCHK(dTh.alloc((size_t)chunk * nd.P));
     HIPCHK(dOut.alloc((size_t)chunk * per_net));
-    const bool batched = narrow_fwd_ok(h);
+    // one zeroed image per network of a chunk where the backend runs them as one launch, else the handle's one image in turn
+    const bool batched = h->be->forward_batched();
     if (batched) {
         HIPCHK(dImg.alloc((size_t)chunk * h->img_floats));
         HIPCHK(hipMemsetAsync(dImg, 0, (size_t)chunk * h->img_floats * sizeof(float), h->stream));
@@ -1068,18 +941,7 @@ static int ensemble_forward(tbnn_ctx* h, const std::string& who, const float* th
         const int c = std::min(chunk, m - i0);
         HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
                                 (size_t)nd.P * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
-        if (batched) {
-            hipLaunchKernelGGL(k_make_image, dim3((nd.P + 255) / 256, c), dim3(256), 0, h->stream, nd.P, (const float*)dTh, h->imgmap, dImg,
-                               (long)nd.P, (long)h->img_floats);
-            rc = narrow_forward(h, c, dImg, h->img_floats, dX, rows, dOut, (long)per_net);
-            if (rc) rc = fail(-2, "fast3 ensemble forward launch failed");
-        } else if (h->lay) {
-            LayFwd lf;
-            rc = lay_fwd_prepare(h, dX, rows, lf);
-            for (int i = 0; i < c && !rc; ++i) rc = lay_fwd_run(h, lf, dTh + (size_t)i * nd.P, dOut + (size_t)i * per_net);
-        } else {
-            for (int i = 0; i < c && !rc; ++i) rc = launch_forward(h, dTh + (size_t)i * nd.P, dX, rows, dOut + (size_t)i * per_net);
-        }
+        rc = h->be->forward(h->stream, c, dTh, dX, rows, dOut, h->imgmap, batched ? (float*)dImg : (float*)h->qimg_cur);
         if (!rc) {
             HIPCHK(hipGetLastError());
             rc = each(i0, c, (const float*)dOut, rows);
@@ -1303,21 +1165,13 @@ static int enqueue_transition(tbnn_ctx* h, float eps, int L, const float* d_p0, 
     // a small problem on an ahead-of-time narrow kernel: the L leapfrog steps in ONE launch, one workgroup per chain (kernels_traj.hpp).
     // Not for a traced transition (per-step energies) or a sharded gradient.  Profiling (tbnn_set_profiling) does NOT change the path (round 6;
     // ADVICE round 5): a profiled trajectory launch is bracketed by one event pair and reported per leapfrog step (its time / L).
-    const bool traj = h->traj && !d_trace && L >= 1 && h->ops && h->ops->family == TBNN_FAMILY_NARROW && h->ops->traj && h->n <= h->ops->traj_max_rows &&
-                      !h->shard;
+    const bool traj = h->traj && !d_trace && L >= 1 && h->n <= h->be->traj_max_rows() && !h->shard;
     h->last_path = traj ? "trajectory" : "per-step";
     if (traj) {
-        hipEvent_t ea = nullptr, eb = nullptr;
-        const bool prof = h->profile > 0 && (h->launch_no++ % h->profile) == 0;
-        if (prof) {
-            if (h->pev_used + 2 > h->pev.size()) { hipEventCreate(&ea); hipEventCreate(&eb); h->pev.emplace_back(ea); h->pev.emplace_back(eb); }
-            ea = h->pev[h->pev_used]; eb = h->pev[h->pev_used + 1]; h->pev_used += 2;
-            h->pev_div.push_back(L);
-            hipEventRecord(ea, h->stream);
-        }
-        const int trc = h->ops->traj(h->C, h->stream, &nd, h->qimg, (long)h->img_floats, h->eta, h->dX, h->dY, h->n, h->q, h->p, h->g, h->gd, h->imgmap,
-                                     h->pstat, stat_entries(h), eps, L, ctl);
-        if (prof) hipEventRecord(eb, h->stream);
+        const hipEvent_t prof_end = profile_begin(h, L);
+        const int trc = h->be->trajectory(h->stream, h->C, h->qimg, (long)h->img_floats, h->eta, h->dX, h->dY, h->n, h->q, h->p, h->g, h->gd, h->imgmap, h->pstat,
+                                          stat_entries(h), eps, L, ctl);
+        if (prof_end) hipEventRecord(prof_end, h->stream);
         if (trc)
             return fail(-2, "trajectory kernel launch failed");
         h->q_img_valid = false;            // the images the kernel advanced lived in LDS
@@ -1633,14 +1487,15 @@ extern "C" int tbnn_debug_draw(tbnn_handle h, uint32_t epoch, uint32_t purpose, 
 extern "C" int tbnn_debug_stamps(tbnn_handle h, uint64_t* out5) {
     if (!out5) return fail(-1, "null out16");
     NEED(h);
-    if (!h->ops || h->ops != narrow_find(h->nd) || !h->dX || h->C > 1) return fail(-1, "debug_stamps: narrow fast kernel + data required");
+    const FusedOps* ops = h->be->ops();
+    if (!ops || ops != narrow_find(h->nd) || !h->dX || h->C > 1) return fail(-1, "debug_stamps: narrow fast kernel + data required");
     HIPCHK(hipSetDevice(h->device));
     Buf<unsigned long long> d;
     HIPCHK(d.alloc(16));
     HIPCHK(hipMemset(d, 0, 16 * sizeof(unsigned long long)));
     hipLaunchKernelGGL(k_make_image, dim3((h->nd.P + 255) / 256), dim3(256), 0, h->stream, h->nd.P, h->q_cur, h->imgmap, h->qimg_cur);
     for (int rep = 0; rep < 3; ++rep)
-        if (narrow_launch_stamped(h->ops, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d))
+        if (narrow_launch_stamped(ops, h->grid, h->stream, h->nd, h->qimg_cur, h->eta, h->dX, h->dY, h->n, h->slabs, h->pitch, h->pstat, d))
             return fail(-2, "debug_stamps: launch failed");
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out5, d, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
