@@ -262,6 +262,27 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
 int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                          const float* net_w, int which, const float* X, const float* Y, int64_t n, double* per_net,
                          double* lppd_rows);
+/* Posterior-predictive quantiles (credible intervals) over the network axis.  Arguments up to `n` as tbnn_ensemble_moments'; the values
+ * ranked per (output, row) are the m values t_i = xform(f_i) * scale + shift, formed in fp32 BEFORE the ranking (a negative scale or the
+ * softmax need no special case).  probs: n_probs probabilities in [0, 1], 1 <= n_probs <= 64; out: host [n_probs][d_out][n] doubles.
+ *   TBNN_QUANT_LINEAR        NumPy's default: h = (m - 1) p, lo = floor(h), g = h - lo; t_(lo) + g (t_(lo+1) - t_(lo)) in fp64 from the two
+ *                            fp32 order statistics (g = 0: t_(lo) itself).  net_w must be NULL.
+ *   TBNN_QUANT_INVERTED_CDF  the smallest value v among the networks with w_i > 0 such that sum_{i: t_i <= v} w_i >= p W, W = sum_i w_i,
+ *                            both sums fp64 in network order (net_w NULL: every w_i = 1): one of the t_i, converted exactly --
+ *                            np.quantile(..., method="inverted_cdf", weights=w).  p W is one rounded fp64 product.  Without weights
+ *                            (W = m) that is NumPy's own index arithmetic at any p; with weights NumPy compares the partial sums
+ *                            divided by W with p instead, which is the same decision wherever p W is exact (dyadic p, integer
+ *                            weights) and may differ in the last bit of a tie between a partial sum and p W otherwise.
+ * An element with a NaN among its t_i gives NaN at every probability; +-inf rank as numbers.  The selection is exact (no sort: bisection on
+ * the order-preserving 32-bit key of an fp32 value, 32 passes over the element's m values) and the same bits from run to run.  All m
+ * networks of a row are needed at once, so the ROWS are cut into blocks (multiples of 64 rows whose m d_out rb predictions fit 2^28 floats;
+ * a block's n_probs d_out rb results are held beside them).
+ * Refused, with nothing written: NULL probs / out, n_probs outside 1 .. 64, a probability outside [0, 1] or NaN, an unknown method or
+ * transform, SOFTMAX with d_out < 2, weights breaking the rules above, weights with TBNN_QUANT_LINEAR, m d_out 64 > 2^28. */
+enum { TBNN_QUANT_LINEAR = 0, TBNN_QUANT_INVERTED_CDF = 1 };
+int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int method,
+                            int xform, float scale, float shift, int which, const float* X, int64_t n, const double* probs,
+                            int32_t n_probs, double* out);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)
  *   out3[0] = mean (p-r)^2            SquaredError

@@ -22,6 +22,7 @@ PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
 XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
+QUANT_LINEAR, QUANT_INVERTED_CDF = 0, 1
 MAX_LAYERS = 16
 ABI_VERSION = 3          # TBNN_ABI_VERSION of include/tbnn.h
 
@@ -94,6 +95,8 @@ SYMBOLS = [
     ("tbnn_predict", C.c_int, [_H, C.c_int, _fp, _fp]),
     ("tbnn_forward_many", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int64, _fp]),
     ("tbnn_ensemble_moments", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
+    ("tbnn_ensemble_quantiles", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp,
+                                          C.c_int32, _dp]),
     ("tbnn_ensemble_loglik", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
     ("tbnn_hyper_probs_many", C.c_int, [_H, C.POINTER(C.c_int32), _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _dp]),
@@ -440,6 +443,23 @@ class Chain:
         _check(lib.tbnn_ensemble_moments(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), float(shift), int(which),
                                          _p(xp), n, mean.ctypes.data_as(_dp), None if vr is None else vr.ctypes.data_as(_dp)))
         return mean, vr
+
+    _QUANT_METHODS = {"linear": QUANT_LINEAR, "inverted_cdf": QUANT_INVERTED_CDF}
+
+    def ensemble_quantiles(self, thetas, probs, X=None, which: int = 1, weights=None, method: str = "linear", xform: int = XFORM_NONE,
+                           scale: float = 1.0, shift: float = 0.0) -> np.ndarray:
+        """posterior-predictive quantiles over an ensemble, selected on the device (tbnn_ensemble_quantiles): thetas [m, P], probs in
+        [0, 1] -> float64 [n_probs, d_out, rows] of xform(f) * scale + shift.  method "linear" (np.quantile's default; no weights) or
+        "inverted_cdf" (np.quantile(method="inverted_cdf", weights=weights): one of the m values).  X None: the staged rows (0 train,
+        1 validation)"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        if method not in self._QUANT_METHODS:
+            raise ValueError(f"method must be one of {sorted(self._QUANT_METHODS)}")
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = np.empty((pr.size, self.d_out, n), dtype=np.float64)
+        _check(lib.tbnn_ensemble_quantiles(self._h, _p(th), th.shape[0], th.shape[1], _p(w), self._QUANT_METHODS[method], int(xform), float(scale),
+                                           float(shift), int(which), _p(xp), n, pr.ctypes.data_as(_dp), pr.size, out.ctypes.data_as(_dp)))
+        return out
 
     def ensemble_loglik(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None):
         """data log-likelihood of the rows under every network of an ensemble, reduced on the device (tbnn_ensemble_loglik): (per_net

@@ -13,6 +13,11 @@
 //             wavefront (shuffles), then over the four waves through LDS in a fixed order, into part[workgroup][network]; the host adds
 //             the workgroups in index order, so the per-network sums are the same from run to run.
 //
+//   quantiles the block [m][d_out][rb] of ALL m networks over a block of rows (a quantile needs every network's value of an element at once,
+//             so the host cuts the rows, not the networks).  k_ens_transform writes t_i over f_i in place; k_ens_quantiles selects order
+//             statistics exactly, without a sort: it fixes the bits of the order-preserving 32-bit key of the answer from the top, each
+//             pass re-reading the element's m values (stride tot, coalesced) and counting those at or below the trial key.
+//
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
 #pragma once
@@ -21,6 +26,7 @@
 #define ENS_TB 256      // threads per workgroup
 #define ENS_KT 8        // outputs of a row a softmax thread carries in registers at a time
 #define ENS_NT 64       // networks per LDS tile of the per-network reduction
+#define ENS_QP 8        // probabilities whose bisection states a quantile thread carries in registers at a time (k_ens_quantiles' QP: this or half)
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
 __device__ __forceinline__ float ens_xform(float f, int xform) {
@@ -191,4 +197,124 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_loglik(const float* __restrict__
 __global__ __launch_bounds__(ENS_TB) void k_ens_lppd_finish(double* __restrict__ lse, long n, double logW) {
     for (long row = (long)blockIdx.x * ENS_TB + threadIdx.x; row < n; row += (long)gridDim.x * ENS_TB)
         lse[row] = lse[row] + log(lse[n + row]) - logW;
+}
+
+// ---- quantiles ----
+// t = xform(f) * scale + shift over f, in place, by the expressions of k_ens_moments.  items = m tot
+__global__ __launch_bounds__(ENS_TB) void k_ens_transform(float* __restrict__ out, long items, int xform, float scale, float shift) {
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < items; e += (long)gridDim.x * ENS_TB)
+        out[e] = ens_xform(out[e], xform) * scale + shift;
+}
+
+// TBNN_XFORM_SOFTMAX: a thread owns one network's row (item = network * n + row) and walks its d_out logits as k_ens_moments_softmax does;
+// the third walk overwrites them, which nothing reads again
+__global__ __launch_bounds__(ENS_TB) void k_ens_transform_softmax(float* __restrict__ out, int m, long n, int d_out, float scale, float shift) {
+    const long items = (long)m * n;
+    for (long it = (long)blockIdx.x * ENS_TB + threadIdx.x; it < items; it += (long)gridDim.x * ENS_TB) {
+        float* __restrict__ f = out + (size_t)(it / n) * n * d_out + it % n;
+        float mx = -INFINITY, s = 0.f;
+        for (int k = 0; k < d_out; ++k) mx = fmaxf(mx, f[(size_t)k * n]);
+        for (int k = 0; k < d_out; ++k) s += ens_exp_diff(f[(size_t)k * n], mx);
+        for (int k = 0; k < d_out; ++k) f[(size_t)k * n] = ens_exp_diff(f[(size_t)k * n], mx) / s * scale + shift;
+    }
+}
+
+// the order-preserving key of an fp32 value: a < b as numbers <=> key(a) < key(b) as unsigned (-0 below +0; NaNs at both ends, past the
+// infinities: the caller counts them apart)
+__device__ __forceinline__ unsigned ens_key(float v) {
+    const unsigned b = __float_as_uint(v);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float ens_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+
+// t: the block [m][tot] of transformed values; w: m weights or null; probs[2][np]: the probabilities p and LINEAR's h = (m - 1) p, the
+// ROUNDED fp64 product NumPy forms (the host multiplies: here the compiler would fuse it with the subtraction of floor(h), and the fraction
+// g would differ from NumPy's by up to half an ulp of h, m 2^-54); res[np][tot].  Per element and probability
+// the smallest key K whose cumulative count (weights: fp64 sum in network order) reaches the target:
+//   LINEAR        count(key_i <= K) >= lo + 1, lo = floor((m - 1) p): K is t_(lo).  One more pass gives count(<= K) and the smallest key
+//                 above K: t_(lo+1) is t_(lo) itself when the count reaches lo + 2, else that key.  g = 0: t_(lo) as it is.
+//   INVERTED_CDF  sum_{key_i <= K} w_i >= p W and > 0 (the second: p = 0 does not stop below the first network with a weight).  Without
+//                 weights the count to reach is ceil(x), x the ROUNDED fp64 product p m -- NumPy's own index for any p, dyadic or not:
+//                 it forms the same product, subtracts 1 (exact for x >= 1/2: x and 1 are multiples of ulp(x) and the difference is
+//                 smaller than x) and takes floor(x - 1) + (x - 1 is no integer), which is ceil(x) - 1; below 1/2 both clamp to t_(0)
+// K is built from the top: with the bits above `bit` fixed, the trial key sets `bit` to 0 and all below it to 1; the target is reached
+// there <=> the bit is 0.  32 passes, whatever the values; a thread owns its element, so the result does not depend on the grid.
+// QP: the probabilities that share a read, ENS_QP or, for the interval call's three, half of it -- every slot is compared against every
+// value, live or not, and a slot's result does not depend on its neighbours.
+template <bool WEIGHTED, int QP>
+__global__ __launch_bounds__(ENS_TB) void k_ens_quantiles(const float* __restrict__ t, int m, long tot, const float* __restrict__ w, int method,
+                                                           const double* __restrict__ probs, int np, double W, double* __restrict__ res) {
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
+        const float* __restrict__ te = t + e;
+        int nans = 0;
+        for (int p0 = 0; p0 < np; p0 += QP) {
+            unsigned K[QP];
+            int need[QP];                          // the count to reach (no weights)
+            double target[QP], g[QP];          // p W, the sum to reach (weights); LINEAR's fraction h - lo
+#pragma unroll
+            for (int j = 0; j < QP; ++j) {
+                const double p = probs[min(p0 + j, np - 1)];       // (a slot past the last repeats it and is not written)
+                K[j] = 0u; g[j] = 0.0; target[j] = p * W;
+                if (method == TBNN_QUANT_LINEAR) {
+                    const double hh = probs[np + min(p0 + j, np - 1)], lo = floor(hh);
+                    g[j] = hh - lo; need[j] = (int)lo + 1;
+                } else {
+                    need[j] = max(1, (int)ceil(p * (double)m));     // unweighted: W = m
+                }
+            }
+            for (int bit = 31; bit >= 0; --bit) {
+                const unsigned low = (1u << bit) - 1u;
+                int cnt[QP];
+                double sum[QP];
+#pragma unroll
+                for (int j = 0; j < QP; ++j) { cnt[j] = 0; sum[j] = 0.0; }
+#pragma unroll 8
+                for (int i = 0; i < m; ++i) {
+                    const float v = te[(size_t)i * tot];
+                    const unsigned key = ens_key(v);
+                    if (p0 == 0 && bit == 31) nans += (v != v);
+                    if (WEIGHTED) {
+                        const double wi = (double)w[i];
+#pragma unroll
+                        for (int j = 0; j < QP; ++j) sum[j] += key <= (K[j] | low) ? wi : 0.0;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < QP; ++j) cnt[j] += key <= (K[j] | low);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < QP; ++j) {
+                    const bool reached = WEIGHTED ? (sum[j] >= target[j] && sum[j] > 0.0) : cnt[j] >= need[j];
+                    if (!reached) K[j] |= 1u << bit;
+                }
+            }
+            unsigned nxt[QP];
+            int cle[QP];
+#pragma unroll
+            for (int j = 0; j < QP; ++j) { nxt[j] = 0xFFFFFFFFu; cle[j] = 0; }
+            if (method == TBNN_QUANT_LINEAR) {
+#pragma unroll 4
+                for (int i = 0; i < m; ++i) {
+                    const unsigned key = ens_key(te[(size_t)i * tot]);
+#pragma unroll
+                    for (int j = 0; j < QP; ++j) {
+                        cle[j] += key <= K[j];
+                        nxt[j] = key > K[j] ? min(nxt[j], key) : nxt[j];
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < QP; ++j) {
+                if (p0 + j < np) {
+                    const double a = (double)ens_unkey(K[j]);
+                    double r = a;
+                    if (method == TBNN_QUANT_LINEAR && g[j] > 0.0) {
+                        const double b = cle[j] >= need[j] + 1 ? a : (double)ens_unkey(nxt[j]);
+                        r = a + g[j] * (b - a);
+                    }
+                    res[(size_t)(p0 + j) * tot + e] = nans ? (double)NAN : r;
+                }
+            }
+        }
+    }
 }

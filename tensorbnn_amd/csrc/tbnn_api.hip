@@ -899,6 +899,26 @@ extern "C" int tbnn_predict(tbnn_handle h, int which, const float* theta, float*
     return 0;
 }
 
+// the arguments every ensemble entry point checks alike, and the rows: *dX the staged rows, or the n host rows copied into dXown
+static int ensemble_rows(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X, int64_t n,
+                         Buf<float>& dXown, const float** dX, long* rows) {
+    const NetDev& nd = h->nd;
+    if (!thetas || m < 1 || theta_stride < nd.P) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    HIPCHK(hipSetDevice(h->device));
+    if (X) {
+        if (n < 1) return fail(-1, who + ": n < 1");
+        *rows = (long)n;
+        HIPCHK(dXown.alloc((size_t)*rows * nd.d_in));
+        HIPCHK(hipMemcpyAsync(dXown, X, (size_t)*rows * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        *dX = dXown;
+    } else {
+        if (which != 0 && which != 1) return fail(-1, "which must be 0 (training rows) or 1 (validation rows)");
+        *dX = which ? h->dXv : h->dX; *rows = which ? h->nv : h->n;
+        if (!*dX || *rows < 1) return fail(-1, which ? "tbnn_set_validation has not been called" : "tbnn_set_data has not been called");
+    }
+    return 0;
+}
+
 // The part tbnn_forward_many and the ensemble reductions share: m networks, theta_i = thetas + i * theta_stride, over the same rows.
 // X == null: the staged rows selected by `which` (0 training, 1 validation); else n host rows.  The rows are staged, the networks cut
 // into chunks whose predictions take at most chunk_floats floats, each chunk's weights (and, narrow shapes, images) built and its forward
@@ -908,22 +928,10 @@ template <class Begin, class Each>
 static int ensemble_forward(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
                             int64_t n, size_t chunk_floats, Begin&& begin, Each&& each) {
     const NetDev& nd = h->nd;
-    if (!thetas || m < 1 || theta_stride < nd.P) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    HIPCHK(hipSetDevice(h->device));
     const float* dX = nullptr;
     Buf<float> dXown;
     long rows = 0;
-    if (X) {
-        if (n < 1) return fail(-1, who + ": n < 1");
-        rows = (long)n;
-        HIPCHK(dXown.alloc((size_t)rows * nd.d_in));
-        HIPCHK(hipMemcpyAsync(dXown, X, (size_t)rows * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        dX = dXown;
-    } else {
-        if (which != 0 && which != 1) return fail(-1, "which must be 0 (training rows) or 1 (validation rows)");
-        dX = which ? h->dXv : h->dX; rows = which ? h->nv : h->n;
-        if (!dX || rows < 1) return fail(-1, which ? "tbnn_set_validation has not been called" : "tbnn_set_data has not been called");
-    }
+    if (const int rc = ensemble_rows(h, who, thetas, m, theta_stride, which, X, n, dXown, &dX, &rows)) return rc;
     const size_t per_net = (size_t)rows * nd.d_out;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, chunk_floats / std::max<size_t>(per_net, 1)));
     Buf<float> dTh, dOut, dImg;
@@ -955,6 +963,7 @@ static int ensemble_forward(tbnn_ctx* h, const std::string& who, const float* th
 static const size_t ENS_CHUNK_FLOATS = (size_t)1 << 28;
 // the ensemble reductions alone: TBNN_ENS_CHUNK_FLOATS (debug) cuts the chunks smaller, so that a test reaches the carry-over between
 // chunks with a small problem; tbnn_forward_many does not read it
+// (tbnn_ensemble_quantiles cuts rows with it, in multiples of 64: there the value may be exceeded by up to 64 rows' worth)
 static size_t ens_chunk_floats() {
     if (const char* e = getenv("TBNN_ENS_CHUNK_FLOATS")) { const long long v = atoll(e); if (v >= 1 && (size_t)v < ENS_CHUNK_FLOATS) return (size_t)v; }
     return ENS_CHUNK_FLOATS;
@@ -1032,6 +1041,89 @@ extern "C" int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t
     if (var_out) HIPCHK(hipMemcpyAsync(var_out, acc + tot, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// Quantiles need all m networks of an element at once, so this driver cuts the ROWS where ensemble_forward cuts the networks: blocks of rb
+// rows, every block's m forward passes into dOut[m][d_out][rb], then the transform and the selection (kernels_ensemble.hpp) and
+// n_probs d_out rb doubles into the strided host result.  rb: what keeps a block's predictions, m d_out rb floats, within
+// ens_chunk_floats(), rounded down to a multiple of 64 and never below 64 -- a block then starts as aligned within dX as dX itself is for
+// the forward kernels' vector loads; the debug override may therefore be exceeded by up to 64 rows' worth.  The block's results, n_probs
+// d_out rb doubles, are outside that budget: never more than the caller's own `out`.  Thetas, weights and probabilities are staged once;
+// be->forward builds a block's weight images into the one scratch allocated here.
+extern "C" int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int method,
+                                       int xform, float scale, float shift, int which, const float* X, int64_t n, const double* probs,
+                                       int32_t n_probs, double* out) {
+    NEED(h);
+    const std::string who = "ensemble_quantiles";
+    const NetDev& nd = h->nd;
+    const int d_out = nd.d_out;
+    if (!probs || !out) return fail(-1, who + ": null probs or out");
+    if (n_probs < 1 || n_probs > 64) return fail(-1, who + ": n_probs must be 1 .. 64");
+    for (int32_t j = 0; j < n_probs; ++j)
+        if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return fail(-1, who + ": probability " + std::to_string(j) + " is not in [0, 1]");
+    if (method != TBNN_QUANT_LINEAR && method != TBNN_QUANT_INVERTED_CDF) return fail(-1, who + ": unknown method");
+    if (xform < TBNN_XFORM_NONE || xform > TBNN_XFORM_SOFTMAX) return fail(-1, who + ": unknown transform");
+    if (xform == TBNN_XFORM_SOFTMAX && d_out < 2) return fail(-1, who + ": a softmax needs at least 2 outputs (one logit per class)");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (method == TBNN_QUANT_LINEAR && net_w) return fail(-1, who + ": TBNN_QUANT_LINEAR takes no weights (TBNN_QUANT_INVERTED_CDF does)");
+    double W = 0.0;
+    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
+    const size_t per_row = (size_t)m * (size_t)d_out;
+    if (per_row * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
+    const float* dX = nullptr;
+    Buf<float> dXown;
+    long rows = 0;
+    if (const int rc = ensemble_rows(h, who, thetas, m, theta_stride, which, X, n, dXown, &dX, &rows)) return rc;
+    const long rb = std::min<long>(rows, std::max<long>(64, (long)(ens_chunk_floats() / per_row) / 64 * 64));
+    Buf<float> dTh, dOut, dImg, dW;
+    Buf<double> dP, dQ;
+    HIPCHK(dTh.alloc((size_t)m * nd.P));
+    HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas, (size_t)theta_stride * sizeof(float), (size_t)nd.P * sizeof(float), (size_t)m,
+                            hipMemcpyHostToDevice, h->stream));
+    HIPCHK(dOut.alloc((size_t)m * d_out * rb));
+    HIPCHK(dQ.alloc((size_t)n_probs * d_out * rb));
+    // [2][n_probs]: p, and LINEAR's h = (m - 1) p as one rounded fp64 product (k_ens_quantiles)
+    std::vector<double> ph(2 * (size_t)n_probs);
+    for (int32_t j = 0; j < n_probs; ++j) { ph[j] = probs[j]; ph[n_probs + j] = (double)(m - 1) * probs[j]; }
+    HIPCHK(dP.alloc(ph.size()));
+    HIPCHK(hipMemcpyAsync(dP, ph.data(), ph.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (net_w) {
+        HIPCHK(dW.alloc((size_t)m));
+        HIPCHK(hipMemcpyAsync(dW, net_w, (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    const bool batched = h->be->forward_batched();
+    if (batched) {
+        HIPCHK(dImg.alloc((size_t)m * h->img_floats));
+        HIPCHK(hipMemsetAsync(dImg, 0, (size_t)m * h->img_floats * sizeof(float), h->stream));
+    }
+    int rc = 0;
+    for (long r0 = 0; r0 < rows && !rc; r0 += rb) {
+        const long r = std::min(rb, rows - r0), tot = r * d_out;
+        rc = h->be->forward(h->stream, m, dTh, dX + (size_t)r0 * nd.d_in, r, dOut, h->imgmap, batched ? (float*)dImg : (float*)h->qimg_cur);
+        if (rc) break;
+        HIPCHK(hipGetLastError());
+        if (xform == TBNN_XFORM_SOFTMAX)
+            hipLaunchKernelGGL(k_ens_transform_softmax, dim3(ens_grid((long)m * r)), dim3(ENS_TB), 0, h->stream, (float*)dOut, m, r, d_out, scale, shift);
+        else if (xform != TBNN_XFORM_NONE || scale != 1.f || shift != 0.f)
+            hipLaunchKernelGGL(k_ens_transform, dim3(ens_grid((long)m * tot)), dim3(ENS_TB), 0, h->stream, (float*)dOut, (long)m * tot, xform, scale, shift);
+        const dim3 grid(ens_grid(tot)), tb(ENS_TB);
+        const float* t = dOut;
+        const float* w = net_w ? (const float*)dW : nullptr;
+        const double* p = dP;
+        double* q = dQ;
+        // up to half of ENS_QP probabilities (an interval's three): the kernel that carries half the slots
+        if (net_w && n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+        else if (net_w) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+        else if (n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+        else hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+        HIPCHK(hipGetLastError());
+        // res[n_probs d_out][r] -> out[n_probs d_out][rows] at column r0
+        HIPCHK(hipMemcpy2DAsync(out + r0, (size_t)rows * sizeof(double), dQ, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                (size_t)n_probs * d_out, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    hipStreamSynchronize(h->stream);
+    return rc;
 }
 
 extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,

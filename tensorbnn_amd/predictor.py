@@ -15,6 +15,7 @@ the summed log-likelihood of the training rows under each saved network, compute
 (FFT autocorrelation; Sokal's automatic window with c = 5).
 """
 import math
+from decimal import Decimal
 
 import numpy as np
 
@@ -131,7 +132,7 @@ class predictor(object):
             out.append(np.float32(np.sum(_multivariate_log_prob(np.ones_like(cur) * sd, cur, real))))
         return out
 
-    # ---- reductions over the saved networks on the device (tbnn_ensemble_moments / tbnn_ensemble_loglik) ----
+    # ---- reductions over the saved networks on the device (tbnn_ensemble_moments / tbnn_ensemble_quantiles / tbnn_ensemble_loglik) ----
     _TRANSFORMS = {"none": nat.XFORM_NONE, "exp": nat.XFORM_EXP, "sigmoid": nat.XFORM_SIGMOID, "softmax": nat.XFORM_SOFTMAX}
 
     def _picked(self, n, weights):
@@ -162,6 +163,45 @@ class predictor(object):
         m, v = ch.ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=self._TRANSFORMS[transform],
                                    scale=float(sd), shift=float(mean))
         return (m, m + v) if countVariance else (m, v)
+
+    def predictQuantiles(self, inputMatrix, probs, n=1, weights=None, transform=None, sd=1.0, mean=0.0, method=None):
+        """Posterior quantiles of every n-th network's predictions at the probabilities `probs`, float64 [n_probs, d_out, rows] (a scalar
+        `probs`: [d_out, rows]), selected on the device: only the result crosses to the host.  Per value t = transform(f) * sd + mean,
+        transform None as in predictMoments (softmax under a CategoricalLikelihood, exp under a PoissonLikelihood, none otherwise) and
+        applied before the ranking.  method "linear" is np.quantile's default and takes no weights; "inverted_cdf" returns one of the
+        networks' values and takes weights (np.quantile(method="inverted_cdf", weights=weights)), e.g. what reweight returns.  method None:
+        "linear" without weights, "inverted_cdf" with them."""
+        from .likelihood import CategoricalLikelihood, PoissonLikelihood
+        if transform is None:
+            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
+                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
+        if transform not in self._TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
+        if method is None:
+            method = "linear" if weights is None else "inverted_cdf"
+        if method not in ("linear", "inverted_cdf"):
+            raise ValueError("method must be 'linear', 'inverted_cdf' or None")
+        if method == "linear" and weights is not None:
+            raise ValueError("method 'linear' takes no weights (np.quantile refuses them too): use 'inverted_cdf'")
+        picked, w = self._picked(n, weights)
+        pr = np.asarray(probs, dtype=np.float64)
+        ch = self._ensure_chain()
+        q = ch.ensemble_quantiles(picked, pr.reshape(-1), X=np.asarray(inputMatrix, dtype=np.float32), weights=w, method=method,
+                                  xform=self._TRANSFORMS[transform], scale=float(sd), shift=float(mean))
+        return q[0] if pr.ndim == 0 else q
+
+    def predictInterval(self, inputMatrix, level=0.9, **kwargs):
+        """(lower, median, upper), each float64 [d_out, rows]: the quantiles at (1 - level) / 2, 1 / 2 and (1 + level) / 2 from one call
+        of predictQuantiles, whose other arguments pass through.  This is the central CREDIBLE interval of the network's output -- the
+        rate, the class probability, the regression mean -- under the posterior the saved networks sample; it is not a predictive
+        interval for a new observation, which would add the observation noise (sigma, the Poisson or Bernoulli scatter)."""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        # in decimal, so that level = 0.9 asks for 0.05 and 0.95 themselves: (1 - 0.9) / 2 in binary is the double below 0.05
+        d = Decimal(repr(level))
+        q = self.predictQuantiles(inputMatrix, [float((1 - d) / 2), 0.5, float((1 + d) / 2)], **kwargs)
+        return q[0], q[1], q[2]
 
     def logPredictiveDensity(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
         """(per_network, per_row) under `likelihood` (None: the predictor's own): per_network[i] the summed log-likelihood of the rows

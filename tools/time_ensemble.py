@@ -1,10 +1,13 @@
-"""Times the two routes to an ensemble's predictive moments on the GPU:
+"""Times the routes to an ensemble's predictive moments and quantiles on the GPU:
   (a) Chain.forward_many, then np.mean / np.var in fp64 on the host (every prediction crosses to the host: 4 m d_out n bytes);
-  (b) Chain.ensemble_moments (the reduction on the device: 16 d_out n bytes cross).
+  (b) Chain.ensemble_moments (the reduction on the device: 16 d_out n bytes cross) -- also the forward-only floor of (d);
+  (c) Chain.forward_many, then np.quantile(axis=0) at probs = [0.05, 0.5, 0.95] on the host (on the fp32 array as it comes: the cheapest
+      form of that route; max_abs_diff_quantiles compares (d) with np.quantile of the fp64 cast, outside the timing);
+  (d) Chain.ensemble_quantiles at the same probabilities (the selection on the device: 24 d_out n bytes cross).
 Shapes: the headline 5-50-50-50-1 with m = 256 networks over n = 100,000 rows, and the tutorial 784-20-20-1 with m = 256, n = 12,000.
 Each route: one warm-up call, then the median of five calls on a host clock -- every call returns after its stream work has completed
-(include/tbnn.h), so the clock covers the forward passes, the copies and, for (a), the host's pass.  Prints one JSON line per shape with the
-library's build id.  Needs a gfx950 device; there is no fallback."""
+(include/tbnn.h), so the clock covers the forward passes, the copies and, for (a) and (c), the host's pass.  Prints one JSON line per shape
+with the library's build id.  Needs a gfx950 device; there is no fallback."""
 import json
 import os
 import statistics
@@ -48,9 +51,15 @@ def main():
 
         ta, (mean_a, var_a) = median_of(host_route)
         tb, (mean_b, var_b) = median_of(lambda: ch.ensemble_moments(thetas, X=X))
+        probs = [0.05, 0.5, 0.95]
+        tc, _ = median_of(lambda: np.quantile(ch.forward_many(thetas, X=X), probs, axis=0))
+        td, q_d = median_of(lambda: ch.ensemble_quantiles(thetas, probs, X=X))
+        q_c = np.quantile(ch.forward_many(thetas, X=X).astype(np.float64), probs, axis=0)
         print(json.dumps({"shape": name, "dims": dims, "kernel": ch.kernel_name, "m": m, "n": n, "build_id": nat.build_id(),
                           "forward_many_numpy_ms": round(ta * 1e3, 3), "ensemble_moments_ms": round(tb * 1e3, 3), "ratio": round(ta / tb, 2),
                           "bytes_to_host": {"forward_many": 4 * m * dims[-1] * n, "ensemble_moments": 16 * dims[-1] * n},
+                          "forward_many_np_quantile_ms": round(tc * 1e3, 3), "ensemble_quantiles_ms": round(td * 1e3, 3),
+                          "quantiles_ratio": round(tc / td, 2), "max_abs_diff_quantiles": float(np.abs(q_c - q_d).max()),
                           "max_abs_diff_mean": float(np.abs(mean_a - mean_b).max()), "max_abs_diff_var": float(np.abs(var_a - var_b).max())}),
               flush=True)
         ch.close()
