@@ -283,6 +283,35 @@ enum { TBNN_QUANT_LINEAR = 0, TBNN_QUANT_INVERTED_CDF = 1 };
 int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int method,
                             int xform, float scale, float shift, int which, const float* X, int64_t n, const double* probs,
                             int32_t n_probs, double* out);
+/* Convergence diagnostics over the network axis read as chains x draws: split-R-hat (Gelman-Rubin on split chains) and the effective
+ * sample size by Geyer's initial monotone sequence, the estimators Stan and ArviZ report (BDA3 section 11.4-11.5; Stan's ESS without its
+ * last-odd-lag correction).  Arguments as tbnn_ensemble_quantiles' without weights and probabilities; n_chains = C, 1 <= C <= 64, m = C S
+ * networks in chain-major order (network i = c S + s), S >= 8.  Per (output, row) the m values t[c][s] = xform(f) * scale + shift are formed
+ * in fp32 as the quantiles form them; everything below is fp64.
+ *   split     N = floor(S / 2); chain c gives split chains 2 c (draws 0 .. N-1) and 2 c + 1 (draws S-N .. S-1; an odd S drops the middle
+ *             draw): K = 2 C split chains x[k][0 .. N-1]
+ *   means     mu_k = mean of x[k], d[k][s] = x[k][s] - mu_k
+ *   autocov   a_k(l) = (1/N) sum_{s=0}^{N-1-l} d[k][s] d[k][s+l]  (biased; summed in s order; centred products, not raw second moments);
+ *             A(l) = mean over k of a_k(l), in k order
+ *   variances Wv = A(0) N / (N-1);  Bn = sample variance (ddof 1) of the K means;  Vp = Wv (N-1) / N + Bn
+ *   rhat      sqrt(Vp / Wv)
+ *   rho(l)    1 - (Wv - A(l)) / Vp, rho(0) = 1
+ *   ess       P_0 = 1 + rho(1); for k = 1, 2, ... while 2k+1 <= N-1: P_k = rho(2k) + rho(2k+1), stopping at the first P_k that is not > 0
+ *             (not used), else P'_k = min(P'_{k-1}, P_k);  tau = max(-1 + 2 sum P'_k, 1 / log10(K N));  ess = K N / tau
+ * An element with a NaN among its t, or with Wv not > 0 (every split chain constant), gives rhat = ess = NaN; +-inf among the t reach NaN
+ * through the arithmetic.  The same bits from run to run.  The autocovariances are computed 8 lags at a time from one read of the chain, and
+ * an element leaves the lag loop after the batch that holds its stop; the rows are cut into blocks as for the quantiles (the K means per
+ * element, 2 C d_out rb doubles, are held beside a block).  There is no importance-weight argument: the autocorrelation of a reweighted
+ * ensemble is not defined here.  rhat_out, ess_out: host [d_out][n] doubles; either may be NULL, not both (rhat alone stops after lag 0).
+ * Refused, with nothing written: both outputs NULL, n_chains outside 1 .. 64, m not divisible by n_chains, m / n_chains < 8, an unknown
+ * transform, SOFTMAX with d_out < 2, m d_out 64 > 2^28. */
+int tbnn_ensemble_diagnostics(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int32_t n_chains, int xform,
+                              float scale, float shift, int which, const float* X, int64_t n, double* rhat_out, double* ess_out);
+/* The same estimator over a caller's series, host [m][tot] floats in the same chain-major order (weights, hypers, any scalar per draw):
+ * rhat_out, ess_out host [tot] doubles, either may be NULL, not both.  No forward pass; nothing staged on the handle is read.  The columns
+ * are uploaded in blocks under the same budget.  Refused as above, and a NULL series, tot < 1 or m 64 > 2^28. */
+int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64_t tot, int32_t n_chains, double* rhat_out,
+                            double* ess_out);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)
  *   out3[0] = mean (p-r)^2            SquaredError

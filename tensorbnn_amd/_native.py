@@ -97,6 +97,8 @@ SYMBOLS = [
     ("tbnn_ensemble_moments", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_ensemble_quantiles", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp,
                                           C.c_int32, _dp]),
+    ("tbnn_ensemble_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
+    ("tbnn_series_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp]),
     ("tbnn_ensemble_loglik", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
     ("tbnn_hyper_probs_many", C.c_int, [_H, C.POINTER(C.c_int32), _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _dp]),
@@ -460,6 +462,30 @@ class Chain:
         _check(lib.tbnn_ensemble_quantiles(self._h, _p(th), th.shape[0], th.shape[1], _p(w), self._QUANT_METHODS[method], int(xform), float(scale),
                                            float(shift), int(which), _p(xp), n, pr.ctypes.data_as(_dp), pr.size, out.ctypes.data_as(_dp)))
         return out
+
+    def ensemble_diagnostics(self, thetas, chains: int = 1, X=None, which: int = 1, xform: int = XFORM_NONE, scale: float = 1.0,
+                             shift: float = 0.0):
+        """split-R-hat and effective sample size of xform(f) * scale + shift per (output, row), reduced on the device
+        (tbnn_ensemble_diagnostics): thetas [m, P] of `chains` chains with m / chains >= 8 draws each, chain-major (network i = c S + s)
+        -> (rhat, ess), each float64 [d_out, rows]; NaN where an element holds a NaN or is constant.  X None: the staged rows (0 train,
+        1 validation)"""
+        th, xp, n, _w = self._ensemble_args(thetas, X, which, None)
+        rhat = np.empty((self.d_out, n), dtype=np.float64)
+        ess = np.empty((self.d_out, n), dtype=np.float64)
+        _check(lib.tbnn_ensemble_diagnostics(self._h, _p(th), th.shape[0], th.shape[1], int(chains), int(xform), float(scale), float(shift),
+                                             int(which), _p(xp), n, rhat.ctypes.data_as(_dp), ess.ctypes.data_as(_dp)))
+        return rhat, ess
+
+    def series_diagnostics(self, series, chains: int = 1):
+        """the same estimator over any scalar series per draw (tbnn_series_diagnostics): series [m, tot] (or [m]), chain-major ->
+        (rhat, ess), each float64 [tot]"""
+        sr = np.ascontiguousarray(series, dtype=np.float32)
+        sr = sr.reshape(sr.shape[0], -1)
+        rhat = np.empty(sr.shape[1], dtype=np.float64)
+        ess = np.empty(sr.shape[1], dtype=np.float64)
+        _check(lib.tbnn_series_diagnostics(self._h, _p(sr), sr.shape[0], sr.shape[1], int(chains), rhat.ctypes.data_as(_dp),
+                                           ess.ctypes.data_as(_dp)))
+        return rhat, ess
 
     def ensemble_loglik(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None):
         """data log-likelihood of the rows under every network of an ensemble, reduced on the device (tbnn_ensemble_loglik): (per_net

@@ -17,6 +17,9 @@
 //             so the host cuts the rows, not the networks).  k_ens_transform writes t_i over f_i in place; k_ens_quantiles selects order
 //             statistics exactly, without a sort: it fixes the bits of the order-preserving 32-bit key of the answer from the top, each
 //             pass re-reading the element's m values (stride tot, coalesced) and counting those at or below the trial key.
+//   diagnostics the same block, its network axis read as chains x draws: k_ens_diagnostics forms split-R-hat and the effective sample size
+//             of every element (definition: include/tbnn.h, tbnn_ensemble_diagnostics) from centred fp64 sums, the autocovariances in
+//             batches of ENS_LB lags that share one read of the chain.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -26,6 +29,8 @@
 #define ENS_TB 256      // threads per workgroup
 #define ENS_KT 8        // outputs of a row a softmax thread carries in registers at a time
 #define ENS_NT 64       // networks per LDS tile of the per-network reduction
+#define ENS_LB 8        // lags whose autocovariance sums a diagnostics thread carries in registers at a time (k_ens_diagnostics)
+#define ENS_MAX_CHAINS 64   // chains of tbnn_ensemble_diagnostics / tbnn_series_diagnostics: 128 split-chain means per element in the scratch
 #define ENS_QP 8        // probabilities whose bisection states a quantile thread carries in registers at a time (k_ens_quantiles' QP: this or half)
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
@@ -315,6 +320,112 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_quantiles(const float* __restric
                     res[(size_t)(p0 + j) * tot + e] = nans ? (double)NAN : r;
                 }
             }
+        }
+    }
+}
+
+// ---- split-R-hat and effective sample size ----
+// t: the block [m][tot] of transformed values, m = C S, network i = c S + s (chain-major); mu: scratch [2 C][tot]; rhat, ess: [tot], either
+// may be null.  A thread owns its element (the result does not depend on the grid) and walks, all in fp64:
+//   means     split chain k = 2 c + h holds the N = S / 2 draws of chain c from s = 0 (h = 0) or from s = S - N (h = 1; an odd S drops the
+//             middle draw); mu_k = sum_s x[k][s] / N in s order, kept in mu[k][e]; a NaN among the m values is counted here.
+//   lags      ENS_LB at a time, l0 .. l0 + ENS_LB - 1: per split chain a window w[q] = d[s + l0 + q] (d = x - mu_k, 0 past the chain's end)
+//             slides along the chain, so one load of d[s] and one of the value entering the window feed ENS_LB sums
+//             acc[q] += d[s] w[q].  Every a_k(l) = acc / N is summed over s in order whatever ENS_LB is (a padded product adds 0 to a
+//             finished sum); A(l) = sum_k a_k(l) / K in k order.
+//   Geyer     the batch's pairs P = rho(2 j) + rho(2 j + 1) are consumed in order; the thread leaves the lag loop after the batch that
+//             holds the first P <= 0 (lanes of a wave diverge there); lags of that batch past the stop are not used.
+// Registers: acc, w and A are ENS_LB doubles each (48 VGPRs), indexed by unrolled constants only.
+__device__ __forceinline__ double ens_centred(const float* __restrict__ x, long tot, int idx, int N, double mu) {
+    return idx < N ? (double)x[(size_t)idx * tot] - mu : 0.0;
+}
+
+__global__ __launch_bounds__(ENS_TB) void k_ens_diagnostics(const float* __restrict__ t, int C, int S, long tot, double* __restrict__ mu,
+                                                             double* __restrict__ rhat, double* __restrict__ ess) {
+    const int N = S / 2, K = 2 * C;
+    const double dN = (double)N, dK = (double)K;
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
+        const float* __restrict__ te = t + e;
+        double* __restrict__ mue = mu + e;
+        int nans = 0;
+        double msum = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const float* __restrict__ x = te + (size_t)((k >> 1) * S + ((k & 1) ? S - N : 0)) * tot;
+            double s1 = 0.0;
+#pragma unroll 4
+            for (int s = 0; s < N; ++s) {
+                const float v = x[(size_t)s * tot];
+                nans += (v != v);
+                s1 += (double)v;
+            }
+            if ((S & 1) && (k & 1)) { const float v = te[(size_t)((k >> 1) * S + N) * tot]; nans += (v != v); }     // the dropped middle draw
+            s1 /= dN;
+            mue[(size_t)k * tot] = s1;
+            msum += s1;
+        }
+        // Bn: the sample variance (ddof = 1) of the K means, two passes
+        msum /= dK;
+        double Bn = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double d = mue[(size_t)k * tot] - msum;
+            Bn = fma(d, d, Bn);
+        }
+        Bn /= dK - 1.0;
+        double Wv = 0.0, Vp = 0.0, Pprev = 0.0, Psum = 0.0;
+        bool live = !nans;
+        for (int l0 = 0; l0 < N && live; l0 += ENS_LB) {
+            double A[ENS_LB];
+#pragma unroll
+            for (int q = 0; q < ENS_LB; ++q) A[q] = 0.0;
+            for (int k = 0; k < K; ++k) {
+                const float* __restrict__ x = te + (size_t)((k >> 1) * S + ((k & 1) ? S - N : 0)) * tot;
+                const double m = mue[(size_t)k * tot];
+                double acc[ENS_LB], w[ENS_LB];
+#pragma unroll
+                for (int q = 0; q < ENS_LB; ++q) { acc[q] = 0.0; w[q] = ens_centred(x, tot, l0 + q, N, m); }
+                // ENS_LB steps at a time, the window a ring with constant indices: at step s0 + j slot (j + q) % ENS_LB holds d[s + l0 + q], and
+                // slot j, used last as q = 0, takes the value that enters.  Steps past N - 1 - l0 multiply by the padding: they add 0.
+                for (int s0 = 0; s0 < N - l0; s0 += ENS_LB) {
+#pragma unroll
+                    for (int j = 0; j < ENS_LB; ++j) {
+                        const double ds = ens_centred(x, tot, s0 + j, N, m);
+#pragma unroll
+                        for (int q = 0; q < ENS_LB; ++q) acc[q] = fma(ds, w[(j + q) % ENS_LB], acc[q]);
+                        w[j] = ens_centred(x, tot, s0 + j + l0 + ENS_LB, N, m);
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < ENS_LB; ++q) A[q] += acc[q] / dN;
+            }
+#pragma unroll
+            for (int q = 0; q < ENS_LB; ++q) A[q] /= dK;
+            if (l0 == 0) {
+                Wv = A[0] * dN / (dN - 1.0);
+                Vp = Wv * (dN - 1.0) / dN + Bn;
+                live = Wv > 0.0;                    // (a NaN from an infinity among the values is not > 0 either)
+                if (!live || !ess) break;
+            }
+            // pairs (l0 + 2 j, l0 + 2 j + 1), 2 k + 1 <= N - 1; the first is P_0 = 1 + rho(1)
+#pragma unroll
+            for (int j = 0; j < ENS_LB / 2; ++j) {
+                if (live && l0 + 2 * j + 1 <= N - 1) {
+                    const double r1 = 1.0 - (Wv - A[2 * j + 1]) / Vp;
+                    if (l0 + j == 0) {
+                        Pprev = 1.0 + r1;
+                        Psum = Pprev;
+                    } else {
+                        const double P = (1.0 - (Wv - A[2 * j]) / Vp) + r1;
+                        if (P > 0.0) { Pprev = fmin(Pprev, P); Psum += Pprev; }
+                        else live = false;
+                    }
+                }
+            }
+        }
+        const bool defined = !nans && Wv > 0.0;
+        if (rhat) rhat[e] = defined ? sqrt(Vp / Wv) : (double)NAN;
+        if (ess) {
+            const double tau = fmax(2.0 * Psum - 1.0, 1.0 / log10(dK * dN));
+            ess[e] = defined ? dK * dN / tau : (double)NAN;
         }
     }
 }

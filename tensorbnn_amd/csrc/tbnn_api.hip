@@ -1043,20 +1043,60 @@ extern "C" int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t
     return 0;
 }
 
-// Quantiles need all m networks of an element at once, so this driver cuts the ROWS where ensemble_forward cuts the networks: blocks of rb
-// rows, every block's m forward passes into dOut[m][d_out][rb], then the transform and the selection (kernels_ensemble.hpp) and
-// n_probs d_out rb doubles into the strided host result.  rb: what keeps a block's predictions, m d_out rb floats, within
-// ens_chunk_floats(), rounded down to a multiple of 64 and never below 64 -- a block then starts as aligned within dX as dX itself is for
-// the forward kernels' vector loads; the debug override may therefore be exceeded by up to 64 rows' worth.  The block's results, n_probs
-// d_out rb doubles, are outside that budget: never more than the caller's own `out`.  Thetas, weights and probabilities are staged once;
-// be->forward builds a block's weight images into the one scratch allocated here.
+// Quantiles and chain diagnostics need all m networks of an element at once, so this driver cuts the ROWS where ensemble_forward cuts the
+// networks: blocks of rb rows, every block's m forward passes into dOut[m][d_out][rb], then the transform (kernels_ensemble.hpp) and
+// each(r0, r, rows, t): the consumer's kernels over t[m][d_out r] and its copies into the strided host result, on h->stream, which is
+// synchronised after every block.  rb: what keeps a block's predictions, m d_out rb floats, within ens_chunk_floats(), rounded down to a
+// multiple of 64 and never below 64 -- a block then starts as aligned within dX as dX itself is for the forward kernels' vector loads; the
+// debug override may therefore be exceeded by up to 64 rows' worth.  The consumer's per-block results are outside that budget: never more
+// than the caller's own output.  begin(rb) runs once before the first block (the consumer's buffers and staged arguments).  Thetas are
+// staged once; be->forward builds a block's weight images into the one scratch allocated here.
+template <class Begin, class Each>
+static int ensemble_row_blocks(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int xform, float scale,
+                               float shift, int which, const float* X, int64_t n, Begin&& begin, Each&& each) {
+    const NetDev& nd = h->nd;
+    const int d_out = nd.d_out;
+    const size_t per_row = (size_t)m * (size_t)d_out;
+    if (per_row * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
+    const float* dX = nullptr;
+    Buf<float> dXown;
+    long rows = 0;
+    if (const int rc = ensemble_rows(h, who, thetas, m, theta_stride, which, X, n, dXown, &dX, &rows)) return rc;
+    const long rb = std::min<long>(rows, std::max<long>(64, (long)(ens_chunk_floats() / per_row) / 64 * 64));
+    Buf<float> dTh, dOut, dImg;
+    HIPCHK(dTh.alloc((size_t)m * nd.P));
+    HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas, (size_t)theta_stride * sizeof(float), (size_t)nd.P * sizeof(float), (size_t)m,
+                            hipMemcpyHostToDevice, h->stream));
+    HIPCHK(dOut.alloc((size_t)m * d_out * rb));
+    int rc = begin(rb);
+    if (rc) { hipStreamSynchronize(h->stream); return rc; }
+    const bool batched = h->be->forward_batched();
+    if (batched) {
+        HIPCHK(dImg.alloc((size_t)m * h->img_floats));
+        HIPCHK(hipMemsetAsync(dImg, 0, (size_t)m * h->img_floats * sizeof(float), h->stream));
+    }
+    for (long r0 = 0; r0 < rows && !rc; r0 += rb) {
+        const long r = std::min(rb, rows - r0), tot = r * d_out;
+        rc = h->be->forward(h->stream, m, dTh, dX + (size_t)r0 * nd.d_in, r, dOut, h->imgmap, batched ? (float*)dImg : (float*)h->qimg_cur);
+        if (rc) break;
+        HIPCHK(hipGetLastError());
+        if (xform == TBNN_XFORM_SOFTMAX)
+            hipLaunchKernelGGL(k_ens_transform_softmax, dim3(ens_grid((long)m * r)), dim3(ENS_TB), 0, h->stream, (float*)dOut, m, r, d_out, scale, shift);
+        else if (xform != TBNN_XFORM_NONE || scale != 1.f || shift != 0.f)
+            hipLaunchKernelGGL(k_ens_transform, dim3(ens_grid((long)m * tot)), dim3(ENS_TB), 0, h->stream, (float*)dOut, (long)m * tot, xform, scale, shift);
+        rc = each(r0, r, rows, (const float*)dOut);
+        if (!rc) HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    hipStreamSynchronize(h->stream);
+    return rc;
+}
+
 extern "C" int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int method,
                                        int xform, float scale, float shift, int which, const float* X, int64_t n, const double* probs,
                                        int32_t n_probs, double* out) {
     NEED(h);
     const std::string who = "ensemble_quantiles";
-    const NetDev& nd = h->nd;
-    const int d_out = nd.d_out;
+    const int d_out = h->nd.d_out;
     if (!probs || !out) return fail(-1, who + ": null probs or out");
     if (n_probs < 1 || n_probs > 64) return fail(-1, who + ": n_probs must be 1 .. 64");
     for (int32_t j = 0; j < n_probs; ++j)
@@ -1068,62 +1108,112 @@ extern "C" int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32
     if (method == TBNN_QUANT_LINEAR && net_w) return fail(-1, who + ": TBNN_QUANT_LINEAR takes no weights (TBNN_QUANT_INVERTED_CDF does)");
     double W = 0.0;
     if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
-    const size_t per_row = (size_t)m * (size_t)d_out;
-    if (per_row * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
-    const float* dX = nullptr;
-    Buf<float> dXown;
-    long rows = 0;
-    if (const int rc = ensemble_rows(h, who, thetas, m, theta_stride, which, X, n, dXown, &dX, &rows)) return rc;
-    const long rb = std::min<long>(rows, std::max<long>(64, (long)(ens_chunk_floats() / per_row) / 64 * 64));
-    Buf<float> dTh, dOut, dImg, dW;
+    Buf<float> dW;
     Buf<double> dP, dQ;
-    HIPCHK(dTh.alloc((size_t)m * nd.P));
-    HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas, (size_t)theta_stride * sizeof(float), (size_t)nd.P * sizeof(float), (size_t)m,
-                            hipMemcpyHostToDevice, h->stream));
-    HIPCHK(dOut.alloc((size_t)m * d_out * rb));
-    HIPCHK(dQ.alloc((size_t)n_probs * d_out * rb));
     // [2][n_probs]: p, and LINEAR's h = (m - 1) p as one rounded fp64 product (k_ens_quantiles)
     std::vector<double> ph(2 * (size_t)n_probs);
     for (int32_t j = 0; j < n_probs; ++j) { ph[j] = probs[j]; ph[n_probs + j] = (double)(m - 1) * probs[j]; }
-    HIPCHK(dP.alloc(ph.size()));
-    HIPCHK(hipMemcpyAsync(dP, ph.data(), ph.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (net_w) {
-        HIPCHK(dW.alloc((size_t)m));
-        HIPCHK(hipMemcpyAsync(dW, net_w, (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
-    const bool batched = h->be->forward_batched();
-    if (batched) {
-        HIPCHK(dImg.alloc((size_t)m * h->img_floats));
-        HIPCHK(hipMemsetAsync(dImg, 0, (size_t)m * h->img_floats * sizeof(float), h->stream));
-    }
-    int rc = 0;
-    for (long r0 = 0; r0 < rows && !rc; r0 += rb) {
-        const long r = std::min(rb, rows - r0), tot = r * d_out;
-        rc = h->be->forward(h->stream, m, dTh, dX + (size_t)r0 * nd.d_in, r, dOut, h->imgmap, batched ? (float*)dImg : (float*)h->qimg_cur);
-        if (rc) break;
-        HIPCHK(hipGetLastError());
-        if (xform == TBNN_XFORM_SOFTMAX)
-            hipLaunchKernelGGL(k_ens_transform_softmax, dim3(ens_grid((long)m * r)), dim3(ENS_TB), 0, h->stream, (float*)dOut, m, r, d_out, scale, shift);
-        else if (xform != TBNN_XFORM_NONE || scale != 1.f || shift != 0.f)
-            hipLaunchKernelGGL(k_ens_transform, dim3(ens_grid((long)m * tot)), dim3(ENS_TB), 0, h->stream, (float*)dOut, (long)m * tot, xform, scale, shift);
-        const dim3 grid(ens_grid(tot)), tb(ENS_TB);
-        const float* t = dOut;
-        const float* w = net_w ? (const float*)dW : nullptr;
-        const double* p = dP;
-        double* q = dQ;
-        // up to half of ENS_QP probabilities (an interval's three): the kernel that carries half the slots
-        if (net_w && n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-        else if (net_w) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-        else if (n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-        else hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-        HIPCHK(hipGetLastError());
-        // res[n_probs d_out][r] -> out[n_probs d_out][rows] at column r0
-        HIPCHK(hipMemcpy2DAsync(out + r0, (size_t)rows * sizeof(double), dQ, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                (size_t)n_probs * d_out, hipMemcpyDeviceToHost, h->stream));
+    return ensemble_row_blocks(h, who, thetas, m, theta_stride, xform, scale, shift, which, X, n,
+        [&](long rb) -> int {
+            HIPCHK(dQ.alloc((size_t)n_probs * d_out * rb));
+            HIPCHK(dP.alloc(ph.size()));
+            HIPCHK(hipMemcpyAsync(dP, ph.data(), ph.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            if (net_w) {
+                HIPCHK(dW.alloc((size_t)m));
+                HIPCHK(hipMemcpyAsync(dW, net_w, (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            }
+            return 0;
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            const long tot = r * d_out;
+            const dim3 grid(ens_grid(tot)), tb(ENS_TB);
+            const float* w = net_w ? (const float*)dW : nullptr;
+            const double* p = dP;
+            double* q = dQ;
+            // up to half of ENS_QP probabilities (an interval's three): the kernel that carries half the slots
+            if (net_w && n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+            else if (net_w) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+            else if (n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+            else hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
+            HIPCHK(hipGetLastError());
+            // res[n_probs d_out][r] -> out[n_probs d_out][rows] at column r0
+            HIPCHK(hipMemcpy2DAsync(out + r0, (size_t)rows * sizeof(double), dQ, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                    (size_t)n_probs * d_out, hipMemcpyDeviceToHost, h->stream));
+            return 0;
+        });
+}
+
+// the checks of the chain structure both diagnostics entry points share: S = m / n_chains draws per chain
+static int diag_check(const std::string& who, int32_t m, int32_t n_chains, const double* rhat_out, const double* ess_out) {
+    if (!rhat_out && !ess_out) return fail(-1, who + ": rhat_out and ess_out are both null");
+    if (n_chains < 1 || n_chains > ENS_MAX_CHAINS) return fail(-1, who + ": n_chains must be 1 .. " + std::to_string(ENS_MAX_CHAINS));
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (m % n_chains) return fail(-1, who + ": m is not divisible by n_chains");
+    if (m / n_chains < 8) return fail(-1, who + ": fewer than 8 draws per chain");
+    return 0;
+}
+
+// k_ens_diagnostics over one block t[m][tot]; dR / dE: [tot] each, null where the result is not wanted
+static int diag_launch(tbnn_ctx* h, const float* t, int32_t m, int32_t n_chains, long tot, double* dMu, double* dR, double* dE) {
+    hipLaunchKernelGGL(k_ens_diagnostics, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, t, (int)n_chains, (int)(m / n_chains), tot, dMu, dR, dE);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int tbnn_ensemble_diagnostics(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int32_t n_chains, int xform,
+                                         float scale, float shift, int which, const float* X, int64_t n, double* rhat_out, double* ess_out) {
+    NEED(h);
+    const std::string who = "ensemble_diagnostics";
+    const int d_out = h->nd.d_out;
+    if (const int rc = diag_check(who, m, n_chains, rhat_out, ess_out)) return rc;
+    if (xform < TBNN_XFORM_NONE || xform > TBNN_XFORM_SOFTMAX) return fail(-1, who + ": unknown transform");
+    if (xform == TBNN_XFORM_SOFTMAX && d_out < 2) return fail(-1, who + ": a softmax needs at least 2 outputs (one logit per class)");
+    Buf<double> dMu, dRE;
+    long rbk = 0;
+    return ensemble_row_blocks(h, who, thetas, m, theta_stride, xform, scale, shift, which, X, n,
+        [&](long rb) -> int {
+            rbk = rb * d_out;
+            HIPCHK(dMu.alloc(2 * (size_t)n_chains * rbk));
+            HIPCHK(dRE.alloc(2 * (size_t)rbk));
+            return 0;
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            if (const int rc = diag_launch(h, t, m, n_chains, r * d_out, dMu, rhat_out ? (double*)dRE : nullptr, ess_out ? dRE + rbk : nullptr)) return rc;
+            // res[d_out][r] -> out[d_out][rows] at column r0
+            if (rhat_out) HIPCHK(hipMemcpy2DAsync(rhat_out + r0, (size_t)rows * sizeof(double), dRE, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                                  (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
+            if (ess_out) HIPCHK(hipMemcpy2DAsync(ess_out + r0, (size_t)rows * sizeof(double), dRE + rbk, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                                 (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
+            return 0;
+        });
+}
+
+// The same kernel over a caller's series: no forward pass, nothing staged on the handle is read.  The columns are cut into blocks of cb
+// (the rule of ensemble_row_blocks: m cb floats within ens_chunk_floats(), a multiple of 64, never below 64), each uploaded as [m][cb].
+extern "C" int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64_t tot, int32_t n_chains, double* rhat_out,
+                                       double* ess_out) {
+    NEED(h);
+    const std::string who = "series_diagnostics";
+    if (const int rc = diag_check(who, m, n_chains, rhat_out, ess_out)) return rc;
+    if (!series || tot < 1) return fail(-1, who + ": null series or tot < 1");
+    if ((size_t)m * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 columns of all m draws exceed the block budget of 2^28 floats");
+    HIPCHK(hipSetDevice(h->device));
+    const long cb = std::min<long>((long)tot, std::max<long>(64, (long)(ens_chunk_floats() / (size_t)m) / 64 * 64));
+    Buf<float> dT;
+    Buf<double> dMu, dRE;
+    HIPCHK(dT.alloc((size_t)m * cb));
+    HIPCHK(dMu.alloc(2 * (size_t)n_chains * cb));
+    HIPCHK(dRE.alloc(2 * (size_t)cb));
+    for (long c0 = 0; c0 < (long)tot; c0 += cb) {
+        const long c = std::min(cb, (long)tot - c0);
+        HIPCHK(hipMemcpy2DAsync(dT, (size_t)c * sizeof(float), series + c0, (size_t)tot * sizeof(float), (size_t)c * sizeof(float), (size_t)m,
+                                hipMemcpyHostToDevice, h->stream));
+        if (const int rc = diag_launch(h, dT, m, n_chains, c, dMu, rhat_out ? (double*)dRE : nullptr, ess_out ? dRE + cb : nullptr)) return rc;
+        if (rhat_out) HIPCHK(hipMemcpyAsync(rhat_out + c0, dRE, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (ess_out) HIPCHK(hipMemcpyAsync(ess_out + c0, dRE + cb, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    hipStreamSynchronize(h->stream);
-    return rc;
+    return 0;
 }
 
 extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,

@@ -15,6 +15,7 @@ the summed log-likelihood of the training rows under each saved network, compute
 (FFT autocorrelation; Sokal's automatic window with c = 5).
 """
 import math
+import os
 from decimal import Decimal
 
 import numpy as np
@@ -37,8 +38,35 @@ class predictor(object):
         self.loadArchitecture()
         self.likelihood = likelihood if likelihood is not None else GaussianLikelihood(sd=0.1)
         self._chain = None
+        self.numChains = 1                                                      # fromChains: the networks are chains x draws, chain-major
         self.weightsTrain = []                                                  # predictor.py:40
         self.weights = []
+
+    @classmethod
+    def fromChains(cls, folderName, **kwargs):
+        """The ensemble network.trainChains wrote: folderName/chain0 ... chain<C-1>, each a directory predictor(dir) reads.  The chains'
+        networks are concatenated chain-major (network i = c S + s, S saved networks per chain) and numChains = C, which is what
+        predictDiagnostics / parameterDiagnostics split by; every other method sees one ensemble of C S networks.  Chains with different
+        numbers of saved networks or different architectures are refused."""
+        dirs = []
+        while os.path.isdir(os.path.join(folderName, "chain%d" % len(dirs))):
+            dirs.append(os.path.join(folderName, "chain%d" % len(dirs)))
+        if not dirs:
+            raise ValueError(f"no chain0 directory under {folderName}")
+        parts = [cls(d, **kwargs) for d in dirs]
+        p = parts[0]
+        shape = lambda q: ([type(l).__name__ for l in q.layers], [m.shape[1:] for m in q.matrices], len(q.hypers[0]) if len(q.hypers) else 0)
+        for c, q in enumerate(parts[1:], 1):
+            if q.numNetworks != p.numNetworks:
+                raise ValueError(f"chain{c} holds {q.numNetworks} saved networks, chain0 {p.numNetworks}")
+            if shape(q) != shape(p):
+                raise ValueError(f"chain{c} has another architecture than chain0")
+        p.matrices = [np.concatenate([q.matrices[i] for q in parts]) for i in range(p.numMatrices)]
+        p.hypers = [h for q in parts for h in q.hypers]
+        p.vectors = [v for q in parts for v in q.vectors]
+        p.numChains = len(parts)
+        p.numNetworks = p.numChains * p.numNetworks
+        return p
 
     def loadNetworks(self):
         """predictor.py:43-113"""
@@ -203,6 +231,53 @@ class predictor(object):
         q = self.predictQuantiles(inputMatrix, [float((1 - d) / 2), 0.5, float((1 + d) / 2)], **kwargs)
         return q[0], q[1], q[2]
 
+    # ---- convergence diagnostics on the device (tbnn_ensemble_diagnostics / tbnn_series_diagnostics) ----
+    @staticmethod
+    def _diagnostics(rhat, ess):
+        bad = np.isnan(rhat) | np.isnan(ess)
+        ok = ~bad
+        return {"rhat": rhat, "ess": ess, "max_rhat": float(rhat[ok].max()) if ok.any() else float("nan"),
+                "min_ess": float(ess[ok].min()) if ok.any() else float("nan"), "undefined": int(bad.sum())}
+
+    def _chain_draws(self, n=1):
+        """network indices of every n-th draw of each chain, chain-major, and the draws per chain"""
+        C = getattr(self, "numChains", 1)
+        if self.numNetworks % C:
+            raise ValueError(f"{self.numNetworks} networks do not divide into {C} chains")
+        S = self.numNetworks // C
+        picked = [c * S + s for c in range(C) for s in range(0, S, n)]
+        if len(picked) // C < 8:
+            raise ValueError(f"{len(picked) // C} draws per chain: the diagnostics need at least 8")
+        return picked, C
+
+    def predictDiagnostics(self, inputMatrix, n=1, transform=None, sd=1.0, mean=0.0):
+        """Have the chains converged, and how many independent draws are the saved networks worth?  Split-R-hat and the effective sample
+        size (Geyer's initial monotone sequence; the definition is in include/tbnn.h) of t = transform(f) * sd + mean per (output, row),
+        over the numChains chains of fromChains (a plain predictor: one chain, split in two), reduced on the device.  Returns a dict:
+        rhat, ess float64 [d_out, rows] (NaN where an element is constant or holds a NaN), max_rhat and min_ess over the defined
+        elements, undefined: the number of NaN elements.  transform None resolves as in predictMoments; n thins WITHIN each chain (every
+        n-th draw of each), which needs at least 8 draws left per chain."""
+        from .likelihood import CategoricalLikelihood, PoissonLikelihood
+        if transform is None:
+            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
+                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
+        if transform not in self._TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
+        picked, C = self._chain_draws(n)
+        ch = self._ensure_chain()
+        rhat, ess = ch.ensemble_diagnostics(np.stack([self.vectors[i] for i in picked]), chains=C, X=np.asarray(inputMatrix, dtype=np.float32),
+                                            xform=self._TRANSFORMS[transform], scale=float(sd), shift=float(mean))
+        return self._diagnostics(rhat, ess)
+
+    def parameterDiagnostics(self):
+        """The dict of predictDiagnostics over the parameters themselves: every weight and bias coordinate in the order of the flattened
+        networks, followed by the hypers where any were saved -- rhat, ess float64 [P + H]."""
+        _picked, C = self._chain_draws()
+        series = np.stack(self.vectors)
+        if len(self.hypers):
+            series = np.concatenate([series, np.stack([np.asarray(h, dtype=np.float32).reshape(-1) for h in self.hypers])], axis=1)
+        return self._diagnostics(*self._ensure_chain().series_diagnostics(series, chains=C))
+
     def logPredictiveDensity(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
         """(per_network, per_row) under `likelihood` (None: the predictor's own): per_network[i] the summed log-likelihood of the rows
         under the i-th picked network (the data term of trainProbs / reweight, in fp64), per_row[r] the log of the weighted mixture of
@@ -306,6 +381,20 @@ class predictor(object):
     def extractParameters(self):
         """predictor.py:314-319: the parameter matrices, first axis = network"""
         return self.matrices
+
+    def extractHyperParameters(self):
+        """predictor.py:321-326: the hyper parameters, first axis = network"""
+        return np.array(self.hypers)
+
+    def parameterStatistics(self):
+        """predictor.py:328-339: per parameter matrix, its mean and its standard deviation over the networks"""
+        return [np.mean(m, axis=0) for m in self.matrices], [np.std(m, axis=0) for m in self.matrices]
+
+    def hyperStatistics(self):
+        """predictor.py:341-351: mean and standard deviation of every hyper parameter over the networks"""
+        hypers = np.array(self.hypers)
+        return np.mean(hypers, axis=0), np.std(hypers, axis=0)
+
 
 
 def function_1d(x):
