@@ -312,6 +312,43 @@ int tbnn_ensemble_diagnostics(tbnn_handle h, const float* thetas, int32_t m, int
  * are uploaded in blocks under the same budget.  Refused as above, and a NULL series, tot < 1 or m 64 > 2^28. */
 int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64_t tot, int32_t n_chains, double* rhat_out,
                             double* ess_out);
+/* Posterior-predictive distribution of a NEW observation: the mixture over the networks of the observation model around each network's
+ * prediction -- what tbnn_ensemble_quantiles leaves out (it ranks the networks' outputs: credible intervals).  Its quantiles are predictive
+ * intervals, its CDF at an observed target is the PIT value that checks them against held-out data.  Arguments up to `n` as
+ * tbnn_ensemble_loglik's (likelihood, sd, net_w, rows, targets), probs and the [n_probs][d_out][n] layout as tbnn_ensemble_quantiles'.
+ * Per (output j, row r), over the m networks with weights w_i (NULL: 1), W = sum_i w_i; f_i is the fp32 forward output promoted exactly to
+ * fp64 and everything below is fp64; no transform is applied.
+ *   Gaussian kinds   s_i = sd[i], or NULL = the descriptor's fixed_sd, clipped to [1e-8, 1e8] as tbnn_ensemble_loglik clips it.
+ *                    F(y) = (1/W) sum_i w_i Phi((y - f_i) / s_i), Phi(z) = erfc(-z / sqrt 2) / 2, summed in network order (the host stages
+ *                    w_i / W and 1 / (s_i sqrt 2) once per call).  Quantile at p: a point q where F crosses p -- the device returns the upper
+ *                    end b of a bracket a < b at most 2 ulp64 wide with F(a) < p <= F(b) AS EVALUATED (or a point with F == p), so q is a
+ *                    crossing within the evaluation error of F whatever the slope there, also where the mixture is flat between separated
+ *                    modes.  Found from the bracket [min_i, max_i] of f_i + s_i Phi^-1(p) (Phi^-1 on the host: Wichura's AS 241), widened,
+ *                    verified on the device and pushed outward where F does not straddle p, by Newton steps (F' is the mixture density)
+ *                    that fall back to bisection whenever a step leaves the bracket or fails to shrink it.
+ *   TBNN_LIK_POISSON lambda_i = exp((double)f_i).  For an integer k >= 0, F(k) = (1/W) sum_i w_i Q(k + 1, lambda_i), Q the regularised upper
+ *                    incomplete gamma function (k + 1 < 2^16: series below lambda < k + 2, continued fraction above, the prefactor formed
+ *                    around the peak from k + 1 = 32 on so that it does not cancel; from 2^16 on Temme's uniform expansion); F(k) = 0 for k < 0.  Quantile at p: the smallest
+ *                    integer k >= 0 with F(k) >= p, as a double (searched outward from the weighted mean rate, then by bisection).  The CDF
+ *                    at a target y is taken at floor(y).  One evaluation of Q costs a few sqrt(k) terms near k = lambda, 2,660 at the most
+ *                    (k just below 2^16), and no loop beyond: the cost does not grow with the rate up to the ceiling of 2^30.
+ * q_out: host [n_probs][d_out][n] doubles, or NULL (then probs may be NULL too); probs: n_probs probabilities in the OPEN interval (0, 1)
+ * (the Gaussian quantile at 0 or 1 is infinite), 1 <= n_probs <= 64.  cdf_out: host [d_out][n] doubles = F(y) at the targets, or NULL; Y is
+ * then needed by tbnn_ensemble_loglik's rules (host targets [n, d_out]; NULL with X NULL = the staged targets of `which`; X without Y is
+ * refused).  cdf_below_out (TBNN_LIK_POISSON only, with cdf_out; or NULL): [d_out][n] doubles = F(y - 1), the lower end of the target's step
+ * (a discrete PIT value lies anywhere in [F(y - 1), F(y)]).  At least one of q_out and cdf_out must be given.
+ * NaN: an element with a NaN among its f_i (any weight) gives NaN in every output; so does, among the networks with w_i > 0, a lambda_i
+ * that is not finite or exceeds 2^30 (Poisson) or, for the quantiles alone, an infinite f_i (Gaussian).  A NaN target gives a NaN CDF;
+ * under Poisson so does any target that is not finite, and a negative one gives 0.  Networks of weight 0 add nothing.  The results are the
+ * same bits from run to run, and a probability's result does not depend on the others asked with it.  The rows are cut into blocks as for
+ * tbnn_ensemble_quantiles (a block's (n_probs + 2) d_out rb results are held beside it).
+ * Refused, with nothing written: q_out and cdf_out both NULL, q_out without probs, cdf_below_out without cdf_out or with a Gaussian kind,
+ * X without Y when cdf_out is given, n not matching the staged rows, n_probs outside 1 .. 64, a probability outside (0, 1) or NaN,
+ * TBNN_LIK_BERNOULLI / TBNN_LIK_CATEGORICAL (the predictive distribution of a label is its posterior-mean probability:
+ * tbnn_ensemble_moments returns it), any other likelihood code, a NaN sd, weights breaking the rules above, m d_out 64 > 2^28. */
+int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                             const float* net_w, int which, const float* X, const float* Y, int64_t n, const double* probs,
+                             int32_t n_probs, double* q_out, double* cdf_out, double* cdf_below_out);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)
  *   out3[0] = mean (p-r)^2            SquaredError

@@ -100,6 +100,8 @@ SYMBOLS = [
     ("tbnn_ensemble_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_series_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp]),
     ("tbnn_ensemble_loglik", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp]),
+    ("tbnn_ensemble_predictive", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp,
+                                           _dp]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
     ("tbnn_hyper_probs_many", C.c_int, [_H, C.POINTER(C.c_int32), _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _dp]),
     ("tbnn_register_kernel_lib", C.c_int, [C.c_char_p]),
@@ -505,6 +507,31 @@ class Chain:
         _check(lib.tbnn_ensemble_loglik(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
                                         per_net.ctypes.data_as(_dp), rows.ctypes.data_as(_dp)))
         return per_net, rows
+
+    def ensemble_predictive(self, thetas, probs=None, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None, cdf=None):
+        """posterior-predictive distribution of a NEW observation -- the mixture over the networks of the observation model around each
+        prediction -- inverted and evaluated on the device (tbnn_ensemble_predictive): (q, F, F_below).  q float64 [n_probs, d_out, rows]: the
+        quantiles at probs, each in (0, 1) (None: no probs).  F float64 [d_out, rows]: the mixture CDF at the targets, the PIT values; asked
+        for by cdf=True, or cdf=None and Y given (Y None with X None: the staged targets); else None.  F_below: under LIK_POISSON the CDF at
+        target - 1 (a count's PIT lies in [F_below, F]), else None.  likelihood: LIK_GAUSSIAN / LIK_FIXED_GAUSSIAN / LIK_POISSON (None: the
+        chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd)"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        want_cdf = (Y is not None) if cdf is None else bool(cdf)
+        if want_cdf and xp is not None and Y is None:
+            raise ValueError("rows X need their targets Y")
+        yp = None if (Y is None or not want_cdf) else _f32(Y).reshape(-1, self.d_out)
+        if yp is not None and yp.shape[0] != n:
+            raise ValueError(f"Y must hold {n} rows")
+        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (th.shape[0],)))
+        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        pr = None if probs is None else np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        q = None if pr is None else np.empty((pr.size, self.d_out, n), dtype=np.float64)
+        F = np.empty((self.d_out, n), dtype=np.float64) if want_cdf else None
+        Fb = np.empty((self.d_out, n), dtype=np.float64) if want_cdf and lik == LIK_POISSON else None
+        dpp = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        _check(lib.tbnn_ensemble_predictive(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
+                                            dpp(pr), 0 if pr is None else pr.size, dpp(q), dpp(F), dpp(Fb)))
+        return q, F, Fb
 
     def hyper_probs_many(self, thetas, etas, priors=None) -> np.ndarray:
         """sum over the dense layers of calculateHyperProbs for m saved networks (predictor.trainProbs / reweight):

@@ -20,6 +20,12 @@
 //   diagnostics the same block, its network axis read as chains x draws: k_ens_diagnostics forms split-R-hat and the effective sample size
 //             of every element (definition: include/tbnn.h, tbnn_ensemble_diagnostics) from centred fp64 sums, the autocovariances in
 //             batches of ENS_LB lags that share one read of the chain.
+//   predictive  the same block, untransformed: the posterior-predictive distribution of a NEW observation, the mixture over the networks of
+//             the observation model around each prediction (definition: include/tbnn.h, tbnn_ensemble_predictive).  k_ens_pred_cdf
+//             evaluates the mixture CDF at each element's target in one pass; k_ens_pred_quantiles inverts it per element and
+//             probability -- Gaussian kinds: a verified bracket, then Newton steps safeguarded by bisection; Poisson: a search over the
+//             integers -- every trial one pass over the element's m predictions.  All fp64, contraction off: a slot's result does not
+//             depend on its neighbours or on the grid.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -32,6 +38,9 @@
 #define ENS_LB 8        // lags whose autocovariance sums a diagnostics thread carries in registers at a time (k_ens_diagnostics)
 #define ENS_MAX_CHAINS 64   // chains of tbnn_ensemble_diagnostics / tbnn_series_diagnostics: 128 split-chain means per element in the scratch
 #define ENS_QP 8        // probabilities whose bisection states a quantile thread carries in registers at a time (k_ens_quantiles' QP: this or half)
+#define ENS_PQ 4        // probabilities whose root-search states a predictive-quantile thread carries in registers at a time (k_ens_pred_quantiles' QP)
+#define ENS_PRED_PASSES 256   // trial points per probability at the most (Gaussian: the moves at least halve, a bisection at the worst; Poisson: <= 2 log2 of the count)
+#define ENS_POIS_MAX_RATE 1073741824.0   // 2^30: a larger (or non-finite) rate makes the element NaN
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
 __device__ __forceinline__ float ens_xform(float f, int xform) {
@@ -426,6 +435,270 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_diagnostics(const float* __restr
         if (ess) {
             const double tau = fmax(2.0 * Psum - 1.0, 1.0 / log10(dK * dN));
             ess[e] = defined ? dK * dN / tau : (double)NAN;
+        }
+    }
+}
+
+// ---- posterior-predictive CDF and quantiles with observation noise ----
+// Phi((y - f) / s) as erfc(-(y - f) c) / 2, c = 1 / (s sqrt 2) staged by the host
+__device__ __forceinline__ double ens_phi(double y, double f, double c) {
+#pragma clang fp contract(off)
+    return 0.5 * erfc(-((y - f) * c));
+}
+
+// log1p(mu) - mu.  Below |mu| < 1/32 the difference of the two would lose |mu| 2^-53 / (mu^2 / 2) of itself, so the series
+// -mu^2/2 + mu^3/3 - ... is summed there (14 terms: the first left out is below 2^-57 of the result)
+__device__ __forceinline__ double ens_log1pmx(double mu) {
+#pragma clang fp contract(off)
+    if (fabs(mu) >= 0.03125) return log1p(mu) - mu;
+    double t = 0.0;
+#pragma unroll
+    for (int k = 15; k >= 2; --k) t = ((k & 1) ? 1.0 : -1.0) / (double)k + mu * t;
+    return mu * mu * t;
+}
+
+// log of x^a e^-x / Gamma(a + 1), a >= 1, x > 0.  Written out, a log x - x - lgamma(a + 1) cancels terms of size a log a, so from a = 32 on
+// it is formed around the peak instead: with mu = (x - a) / a and Stirling's series for lgamma,
+//   a (log1p(mu) - mu) - 1/2 log(2 pi a) - (1/(12 a) - 1/(360 a^3) + 1/(1260 a^5))        (next term 1/(1680 a^7) < 3e-14)
+__device__ __forceinline__ double ens_pois_logpref(double a, double x) {
+#pragma clang fp contract(off)
+    if (a < 32.0) return a * log(x) - x - lgamma(a + 1.0);
+    const double r = 1.0 / a, r2 = r * r;
+    const double stirling = r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0)));
+    return a * ens_log1pmx((x - a) / a) - 0.5 * log(6.283185307179586477 * a) - stirling;
+}
+
+#define ENS_Q_TEMME_A 65536.0    // from this a on Q(a, x) is Temme's expansion: no loop.  Below it a series or fraction of at most 10 sqrt(a) + 100 terms
+
+// Q(a, x), the regularised upper incomplete gamma function, for a >= 1 (here an integer, k + 1) and finite x >= 0: Pr[Poisson(x) <= a - 1].
+// Where x^a e^-x / Gamma(a + 1) is below e^-80 the answer is 1 or 0 to more than 1e-25 and nothing is summed.  Else, a < 2^16: below
+// x < a + 1 the series P = pref sum_n x^n / ((a + 1) .. (a + n)), Q = 1 - P; from there on the continued fraction
+// Q = pref a / (x + 1 - a - 1 (1 - a) / (x + 3 - a - 2 (2 - a) / (x + 5 - a - ...))) by the modified Lentz recurrence (Numerical Recipes
+// section 6.2; for an integer a it ends by itself at term a); either needs a few sqrt(a) terms near x = a, fewer away from it, 2,660 at
+// the most.  a >= 2^16: Temme's uniform expansion (N. M. Temme, SIAM J. Math. Anal. 10 (1979) 757; the coefficients' series in eta are those of
+// DiDonato and Morris, ACM TOMS 12 (1986) 377): with eta^2 / 2 = mu - log1p(mu), eta of the sign of mu = (x - a) / a,
+//   Q = erfc(eta sqrt(a / 2)) / 2 + exp(-a eta^2 / 2) / sqrt(2 pi a) (c0 + c1 / a + c2 / a^2),   c0 = 1 / mu - 1 / eta, ...
+// Past the e^-80 exit |eta| < 0.05 there, where the c_k are summed from their Taylor series (the closed forms cancel); what is left out is
+// below 1e-16 of Q.  So the cost of one evaluation does not grow with the rate beyond 2^16.
+__device__ __forceinline__ double ens_gamma_q(double a, double x) {
+#pragma clang fp contract(off)
+    if (x <= 0.0) return 1.0;
+    const double lp = ens_pois_logpref(a, x);
+    const bool series = x < a + 1.0;
+    if (lp < -80.0) return series ? 1.0 : 0.0;
+    if (a >= ENS_Q_TEMME_A) {
+        const double mu = (x - a) / a, h = -ens_log1pmx(mu);                // eta^2 / 2
+        const double eta = copysign(sqrt(2.0 * h), mu), r = 1.0 / a;
+        const double c0 = -1.0 / 3.0 + eta * (1.0 / 12.0 + eta * (-2.0 / 135.0 + eta * (1.0 / 864.0 + eta * (1.0 / 2835.0 + eta * (-139.0 / 777600.0)))));
+        const double c1 = -1.0 / 540.0 + eta * (-1.0 / 288.0 + eta * (1.0 / 378.0 + eta * (-77.0 / 77760.0)));
+        const double c2 = 25.0 / 6048.0 + eta * (-139.0 / 51840.0);
+        const double q = 0.5 * erfc(eta * sqrt(0.5 * a)) + exp(-a * h) / sqrt(6.283185307179586477 * a) * (c0 + r * (c1 + r * c2));
+        return fmin(fmax(q, 0.0), 1.0);
+    }
+    const double pref = exp(lp);
+    const int itmax = (int)(10.0 * sqrt(fmax(a, x))) + 100;
+    if (series) {
+        double ap = a, del = 1.0, sum = 1.0;
+        for (int it = 0; it < itmax; ++it) {
+            ap += 1.0;
+            del *= x / ap;
+            sum += del;
+            if (del < sum * 1e-17) break;
+        }
+        return fmax(1.0 - pref * sum, 0.0);
+    }
+    const double tiny = 1e-300;
+    double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
+    for (int it = 1; it <= itmax; ++it) {
+        const double an = -(double)it * ((double)it - a);
+        b += 2.0;
+        d = an * d + b;
+        if (fabs(d) < tiny) d = tiny;
+        c = b + an / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) < 2.3e-16) break;
+    }
+    return fmin(pref * a * h, 1.0);
+}
+
+// the spacing of fp64 at |v| (v finite)
+__device__ __forceinline__ double ens_ulp64(double v) {
+    const double av = fabs(v);
+    return __longlong_as_double(__double_as_longlong(av) + 1) - av;
+}
+
+// t: the block [m][tot] of untransformed predictions, tot = d_out r; Y: the block's targets [r][d_out]; cst[2][m]: w_i / W and, Gaussian
+// kinds, 1 / (s_i sqrt 2).  cdf[tot] = F(y); below[tot] (Poisson, or null) = F(y - 1).  Networks of weight 0 add nothing; a NaN among an
+// element's f_i or a NaN target (Poisson: any target that is not finite) gives NaN.  Poisson: the target is read at k = floor(y), F = 0 for k < 0, and a non-finite rate or one
+// above 2^30 among the networks that count gives NaN.
+template <int LIK>
+__global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict__ t, int m, long tot, long r, int d_out, const float* __restrict__ Y,
+                                                          const double* __restrict__ cst, double* __restrict__ cdf, double* __restrict__ below) {
+#pragma clang fp contract(off)
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
+        const float* __restrict__ te = t + e;
+        const float yf = Y[(size_t)(e % r) * d_out + e / r];
+        const double y = (double)yf, k = floor(y);
+        int bad = LIK == TBNN_LIK_POISSON ? !(fabsf(yf) < INFINITY) : yf != yf;
+        double F = 0.0, Fb = 0.0;
+        for (int i = 0; i < m; ++i) {
+            const float fv = te[(size_t)i * tot];
+            const double wn = cst[i];
+            bad += fv != fv;
+            if (!(wn > 0.0)) continue;
+            if (LIK == TBNN_LIK_POISSON) {
+                const double lam = exp((double)fv);
+                if (!(lam <= ENS_POIS_MAX_RATE)) { bad += 1; continue; }
+                if (k >= 0.0) F += wn * ens_gamma_q(k + 1.0, lam);
+                if (below && k >= 1.0) Fb += wn * ens_gamma_q(k, lam);
+            } else {
+                F += wn * ens_phi(y, (double)fv, cst[m + i]);
+            }
+        }
+        cdf[e] = bad ? (double)NAN : F;
+        if (below) below[e] = bad ? (double)NAN : Fb;
+    }
+}
+
+// Quantiles of the same mixtures.  cst[3][m]: w_i / W, 1 / (s_i sqrt 2), s_i (Gaussian kinds; Poisson reads the first row only);
+// probs[2][np]: p and, Gaussian kinds, z_p = Phi^-1(p) from the host; smax: the largest s_i that counts; res[np][tot].  A thread owns its
+// element and carries QP probabilities' search states; every trial is one pass over the element's m predictions (stride tot, coalesced;
+// the constants are uniform), shared by the slots still searching, and the thread leaves when all are done.
+//   Gaussian  bracket [min_i, max_i] of f_i + s_i z_p (each component's own p-quantile: F <= p at the lower end and >= p at the upper),
+//             widened by 2^-44 (max(|a|, |b|) + smax), then VERIFIED: an end whose F is on the wrong side becomes the other end and is pushed
+//             out by twice the width, up to 16 times.  From there F(a) < p <= F(b) as evaluated.  Trial: the Newton step from the last
+//             point (F' = sum_i w_i / W c_i exp(-z_i^2) / sqrt pi), carried 2^-20 of its length and 2 ulp further so that converged steps land
+//             across the root and the OTHER end closes in too; the midpoint instead when that leaves the bracket or is more than half
+//             as long as the last move (the moves then shrink at least as a bisection's: Numerical Recipes' rtsafe).  Ends at F(x) == p or a bracket of at most 2 ulp64; the result is the upper end b.
+//   Poisson   the smallest integer k >= 0 with F(k) >= p, F(k) = sum_i w_i / W Q(k + 1, exp(f_i)): from k = floor(mean rate) outward in steps
+//             that double, starting at floor(sqrt(mean rate)) + 1 (F(-1) = 0 < p is known), until bracketed; then bisection.
+// An element with a NaN among its f_i gives NaN at every probability; so does, among the networks that count, an infinite f_i (Gaussian: the
+// bracket is unbounded) or a rate that is not finite or above 2^30 (Poisson).
+template <int LIK, int QP>
+__global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __restrict__ t, int m, long tot, const double* __restrict__ cst,
+                                                                const double* __restrict__ probs, int np, double smax, double* __restrict__ res) {
+#pragma clang fp contract(off)
+    const bool gauss = LIK != TBNN_LIK_POISSON;
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
+        const float* __restrict__ te = t + e;
+        for (int p0 = 0; p0 < np; p0 += QP) {
+            // a, b: Gaussian the bracket's ends; Poisson the largest k known with F < p and the smallest with F >= p (or +inf: none yet).
+            // x: the trial; wd: Gaussian the bracket's width while it is verified, then the length of the last move; Poisson the next step outward
+            double pj[QP], a[QP], b[QP], x[QP], wd[QP];
+            int ph[QP];                                // Gaussian: 0 verifying a, 1 verifying b, 2 searching; + 8 per push outward.  -1: done
+            int bad = 0;
+            double mean = 0.0;
+#pragma unroll
+            for (int j = 0; j < QP; ++j) {
+                pj[j] = probs[min(p0 + j, np - 1)];
+                a[j] = gauss ? (double)INFINITY : -1.0; b[j] = gauss ? -(double)INFINITY : (double)INFINITY;
+                ph[j] = p0 + j < np ? 0 : -1;              // (a slot past the last is never evaluated)
+            }
+            for (int i = 0; i < m; ++i) {
+                const float fv = te[(size_t)i * tot];
+                const double wn = cst[i];
+                bad += fv != fv;
+                if (!(wn > 0.0)) continue;
+                if (gauss) {
+                    bad += fabsf(fv) == INFINITY;
+                    const double s = cst[2 * m + i];
+#pragma unroll
+                    for (int j = 0; j < QP; ++j) {
+                        const double v = fma(s, probs[np + min(p0 + j, np - 1)], (double)fv);
+                        a[j] = fmin(a[j], v); b[j] = fmax(b[j], v);
+                    }
+                } else {
+                    const double lam = exp((double)fv);
+                    if (!(lam <= ENS_POIS_MAX_RATE)) bad += 1;
+                    mean += wn * lam;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < QP; ++j) {
+                if (gauss) {
+                    const double d = 0x1p-44 * (fmax(fabs(a[j]), fabs(b[j])) + smax);
+                    a[j] -= d; b[j] += d;
+                    x[j] = a[j]; wd[j] = b[j] - a[j];
+                } else {
+                    x[j] = floor(mean); wd[j] = floor(sqrt(mean)) + 1.0;
+                }
+            }
+            for (int pass = 0; pass < ENS_PRED_PASSES && !bad; ++pass) {
+                bool live = false;
+#pragma unroll
+                for (int j = 0; j < QP; ++j) live = live || ph[j] >= 0;
+                if (!live) break;
+                double F[QP], D[QP];
+#pragma unroll
+                for (int j = 0; j < QP; ++j) { F[j] = 0.0; D[j] = 0.0; }
+                for (int i = 0; i < m; ++i) {
+                    const double wn = cst[i];
+                    if (!(wn > 0.0)) continue;
+                    const double f = (double)te[(size_t)i * tot];
+                    if (gauss) {
+                        const double c = cst[m + i], wc = wn * c;
+#pragma unroll
+                        for (int j = 0; j < QP; ++j) {
+                            if (ph[j] >= 0) {
+                                const double z = (x[j] - f) * c;
+                                F[j] += wn * (0.5 * erfc(-z));
+                                D[j] += wc * exp(-(z * z));
+                            }
+                        }
+                    } else {
+                        const double lam = exp(f);
+#pragma unroll
+                        for (int j = 0; j < QP; ++j)
+                            if (ph[j] >= 0) F[j] += wn * ens_gamma_q(x[j] + 1.0, lam);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < QP; ++j) {
+                    if (ph[j] < 0) continue;
+                    const double p = pj[j];
+                    if (!gauss) {
+                        if (F[j] >= p) b[j] = x[j]; else a[j] = x[j];
+                        if (b[j] == (double)INFINITY) {                                       // still below: outward, unless the count is absurd
+                            if (a[j] > 0x1p40) { b[j] = a[j]; ph[j] = -1; continue; }
+                            x[j] = a[j] + wd[j]; wd[j] *= 2.0;
+                        } else if (ph[j] == 0 && a[j] < 0.0 && b[j] - wd[j] > 0.0) {           // above, and nothing below it tried yet: outward and down
+                            x[j] = b[j] - wd[j]; wd[j] *= 2.0;
+                        } else {
+                            ph[j] = 1;
+                            if (b[j] - a[j] <= 1.0) { ph[j] = -1; continue; }
+                            x[j] = a[j] + floor(0.5 * (b[j] - a[j]));
+                        }
+                        continue;
+                    }
+                    const int stage = ph[j] & 7, pushes = ph[j] >> 3;
+                    if (stage == 0) {                                                       // x == a: F(a) < p wanted
+                        if (F[j] < p || pushes >= 16) { ph[j] = 1; x[j] = b[j]; }
+                        else { b[j] = a[j]; a[j] -= 2.0 * wd[j]; wd[j] = b[j] - a[j]; x[j] = a[j]; ph[j] += 8; }
+                        continue;
+                    }
+                    if (stage == 1) {                                                       // x == b: F(b) >= p wanted
+                        if (!(F[j] >= p) && pushes < 16) { a[j] = b[j]; b[j] += 2.0 * wd[j]; wd[j] = b[j] - a[j]; x[j] = b[j]; ph[j] += 8; continue; }
+                        ph[j] = 2;
+                        wd[j] = 4.0 * (b[j] - a[j]);                                        // (the first trial may be a Newton step)
+                    } else if (F[j] >= p) b[j] = x[j];
+                    else a[j] = x[j];
+                    const double w = b[j] - a[j];
+                    if (F[j] == p || !(w > 2.0 * ens_ulp64(b[j]))) { ph[j] = -1; continue; }
+                    // F' = D / sqrt pi
+                    const double step = (p - F[j]) * 1.7724538509055160273 / D[j];
+                    const double xn = x[j] + step + (0x1p-20 * step + copysign(2.0 * ens_ulp64(x[j]), step));
+                    const bool newton = xn > a[j] && xn < b[j] && fabs(xn - x[j]) <= 0.5 * wd[j];
+                    const double xt = newton ? xn : a[j] + 0.5 * w;
+                    wd[j] = fabs(xt - x[j]);
+                    x[j] = xt;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < QP; ++j)
+                if (p0 + j < np) res[(size_t)(p0 + j) * tot + e] = bad ? (double)NAN : b[j];
         }
     }
 }

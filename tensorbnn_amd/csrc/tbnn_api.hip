@@ -1305,6 +1305,144 @@ extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t 
     return 0;
 }
 
+// Phi^-1(p), 0 < p < 1: Wichura's algorithm AS 241 (Applied Statistics 37 (1988) 477-484), routine PPND16, about 1e-16 relative
+static double ens_norm_ppf(double p) {
+    const double q = p - 0.5;
+    if (std::fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        return q * (((((((2.5090809287301226727e3 * r + 3.3430575583588128105e4) * r + 6.7265770927008700853e4) * r + 4.5921953931549871457e4) * r +
+                        1.3731693765509461125e4) * r + 1.9715909503065514427e3) * r + 1.3314166789178437745e2) * r + 3.3871328727963666080e0) /
+               (((((((5.2264952788528545610e3 * r + 2.8729085735721942674e4) * r + 3.9307895800092710610e4) * r + 2.1213794301586595867e4) * r +
+                    5.3941960214247511077e3) * r + 6.8718700749205790830e2) * r + 4.2313330701600911252e1) * r + 1.0);
+    }
+    double r = std::sqrt(-std::log(q < 0.0 ? p : 1.0 - p)), v;
+    if (r <= 5.0) {
+        r -= 1.6;
+        v = (((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r + 1.27045825245236838258e0) * r +
+                3.64784832476320460504e0) * r + 5.76949722146069140550e0) * r + 4.63033784615654529590e0) * r + 1.42343711074968357734e0) /
+            (((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r + 1.48103976427480074590e-1) * r +
+                6.89767334985100004550e-1) * r + 1.67638483018380384940e0) * r + 2.05319162663775882187e0) * r + 1.0);
+    } else {
+        r -= 5.0;
+        v = (((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r + 2.65321895265761230930e-2) * r +
+                2.96560571828504891230e-1) * r + 1.78482653991729133580e0) * r + 5.46378491116411436990e0) * r + 6.65790464350110377720e0) /
+            (((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-7) * r + 1.84631831751005468180e-5) * r + 7.86869131145613259100e-4) * r +
+                1.48753612908506148525e-2) * r + 1.36929880922735805310e-1) * r + 5.99832206555887937690e-1) * r + 1.0);
+    }
+    return q < 0.0 ? -v : v;
+}
+
+// what tbnn_ensemble_predictive refuses before it touches a device, and the per-network constants it stages: cst[3][m] = w_i / W,
+// 1 / (s_i sqrt 2), s_i (the last two: Gaussian kinds); pz[2][n_probs] = p, Phi^-1(p); *smax = the largest s_i among the networks that count
+static int pred_check(const std::string& who, int likelihood, float fixed_sd, int d_out, const float* sd, const float* net_w, int32_t m, const float* X,
+                      const float* Y, const double* probs, int32_t n_probs, const double* q_out, const double* cdf_out, const double* cdf_below_out,
+                      std::vector<double>& cst, std::vector<double>& pz, double* smax) {
+    if (!q_out && !cdf_out) return fail(-1, who + ": q_out and cdf_out are both null");
+    if (q_out && !probs) return fail(-1, who + ": null probs with q_out");
+    if (cdf_below_out && !cdf_out) return fail(-1, who + ": cdf_below_out without cdf_out");
+    if (cdf_out && X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (q_out) {
+        if (n_probs < 1 || n_probs > 64) return fail(-1, who + ": n_probs must be 1 .. 64");
+        for (int32_t j = 0; j < n_probs; ++j)
+            if (!(probs[j] > 0.0 && probs[j] < 1.0)) return fail(-1, who + ": probability " + std::to_string(j) + " is not in (0, 1)");
+    }
+    if (likelihood == TBNN_LIK_BERNOULLI || likelihood == TBNN_LIK_CATEGORICAL)
+        return fail(-1, who + ": the predictive distribution of a label is its posterior-mean probability: tbnn_ensemble_moments returns it");
+    const bool gauss = likelihood == TBNN_LIK_GAUSSIAN || likelihood == TBNN_LIK_FIXED_GAUSSIAN;
+    if (!gauss && likelihood != TBNN_LIK_POISSON) return fail(-1, who + ": unknown likelihood");
+    if (cdf_below_out && gauss) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    // the budget of ensemble_row_blocks, judged here before m values of sd and net_w are read and 3 m doubles staged
+    if ((size_t)m * (size_t)d_out * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
+    if (!q_out) n_probs = 0;                                                          // (not read, whatever the caller left there)
+    double W = 0.0;
+    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
+    cst.assign(3 * (size_t)m, 0.0);
+    *smax = 0.0;
+    for (int32_t i = 0; i < m; ++i) {
+        cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
+        if (!gauss) continue;
+        const float s = sd ? sd[i] : fixed_sd;
+        if (std::isnan(s)) return fail(-1, who + ": sd " + std::to_string(i) + " is not a number");
+        const double sc = (double)std::min(std::max(s, 1e-8f), 1e8f);                  // the clip of tbnn_ensemble_loglik (layer.py:62)
+        cst[(size_t)m + i] = 1.0 / (sc * std::sqrt(2.0));
+        cst[2 * (size_t)m + i] = sc;
+        if (cst[i] > 0.0) *smax = std::max(*smax, sc);
+    }
+    pz.assign(2 * (size_t)std::max(n_probs, 1), 0.0);
+    for (int32_t j = 0; j < n_probs; ++j) { pz[j] = probs[j]; pz[(size_t)n_probs + j] = ens_norm_ppf(probs[j]); }
+    return 0;
+}
+
+extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                                        const float* net_w, int which, const float* X, const float* Y, int64_t n, const double* probs,
+                                        int32_t n_probs, double* q_out, double* cdf_out, double* cdf_below_out) {
+    NEED(h);
+    const std::string who = "ensemble_predictive";
+    const int d_out = h->nd.d_out;
+    std::vector<double> cst, pz;
+    double smax = 0.0;
+    if (const int rc = pred_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, probs, n_probs, q_out, cdf_out, cdf_below_out, cst, pz, &smax)) return rc;
+    if (!q_out) n_probs = 0;
+    const bool pois = likelihood == TBNN_LIK_POISSON;
+    const float* dYrows = nullptr;
+    if (cdf_out && Y && !X && (which == 0 || which == 1)) {
+        const long staged = which ? h->nv : h->n;
+        if (staged >= 1 && n != staged) return fail(-1, who + ": n = " + std::to_string((long long)n) + " does not match the " + std::to_string(staged) + " staged rows");
+    }
+    if (cdf_out && !Y) {
+        dYrows = which == 0 ? h->dY : which == 1 ? h->dYv : nullptr;
+        if ((which == 0 || which == 1) && (which ? h->nv : h->n) >= 1 && !dYrows) return fail(-1, who + ": no staged targets");
+    }
+    Buf<float> dY;
+    Buf<double> dCst, dP, dRes;
+    long rbk = 0;
+    return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
+        [&](long rb) -> int {
+            rbk = rb * d_out;
+            // a block's results: n_probs quantile planes, then the CDF and the CDF below
+            HIPCHK(dRes.alloc(((size_t)n_probs + 2) * rbk));
+            HIPCHK(dCst.alloc(cst.size()));
+            HIPCHK(hipMemcpyAsync(dCst, cst.data(), cst.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(dP.alloc(pz.size()));
+            HIPCHK(hipMemcpyAsync(dP, pz.data(), pz.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            if (cdf_out && Y) {
+                HIPCHK(dY.alloc((size_t)n * d_out));
+                HIPCHK(hipMemcpyAsync(dY, Y, (size_t)n * d_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                dYrows = dY;
+            }
+            return 0;
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            const long tot = r * d_out;
+            const dim3 grid(ens_grid(tot)), tb(ENS_TB);
+            const double* c = dCst;
+            const double* p = dP;
+            double* q = dRes;
+            double* F = dRes + (size_t)n_probs * rbk;
+            double* Fb = cdf_below_out ? F + rbk : nullptr;
+            if (q_out) {
+                if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q);
+                else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q);
+                HIPCHK(hipGetLastError());
+                // res[n_probs d_out][r] -> q_out[n_probs d_out][rows] at column r0
+                HIPCHK(hipMemcpy2DAsync(q_out + r0, (size_t)rows * sizeof(double), q, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                        (size_t)n_probs * d_out, hipMemcpyDeviceToHost, h->stream));
+            }
+            if (cdf_out) {
+                const float* y = dYrows + (size_t)r0 * d_out;
+                if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb);
+                else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy2DAsync(cdf_out + r0, (size_t)rows * sizeof(double), F, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                        (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
+                if (Fb) HIPCHK(hipMemcpy2DAsync(cdf_below_out + r0, (size_t)rows * sizeof(double), Fb, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                                (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
+            }
+            return 0;
+        });
+}
+
 extern "C" int tbnn_metrics(tbnn_handle h, int which, const float* theta, float mean, float sd, int exp_pred, int exp_real,
                             double out3[3]) {
     NEED(h);

@@ -221,8 +221,8 @@ class predictor(object):
     def predictInterval(self, inputMatrix, level=0.9, **kwargs):
         """(lower, median, upper), each float64 [d_out, rows]: the quantiles at (1 - level) / 2, 1 / 2 and (1 + level) / 2 from one call
         of predictQuantiles, whose other arguments pass through.  This is the central CREDIBLE interval of the network's output -- the
-        rate, the class probability, the regression mean -- under the posterior the saved networks sample; it is not a predictive
-        interval for a new observation, which would add the observation noise (sigma, the Poisson or Bernoulli scatter)."""
+        rate, the class probability, the regression mean -- under the posterior the saved networks sample; the predictive interval
+        for a new observation, which adds the observation noise (sigma, the Poisson scatter), is predictiveInterval's."""
         level = float(level)
         if not 0.0 < level < 1.0:
             raise ValueError("level must lie in (0, 1)")
@@ -283,18 +283,80 @@ class predictor(object):
         under the i-th picked network (the data term of trainProbs / reweight, in fp64), per_row[r] the log of the weighted mixture of
         the networks' likelihoods of row r, whose sum is the log predictive density of held-out rows.  Under a GaussianLikelihood the
         standard deviation of each network is its saved last hyper, read as _data_logprob reads it."""
-        from .likelihood import FixedGaussianLikelihood
         lik = self.likelihood if likelihood is None else likelihood
         picked, w = self._picked(n, weights)
-        sd = None
-        if isinstance(lik, FixedGaussianLikelihood):
-            sd = np.full(picked.shape[0], np.float32(lik.sd), dtype=np.float32)                 # likelihood.py:195 (not squared)
-        elif isinstance(lik, GaussianLikelihood):
-            sd = np.array([np.float32(self.hypers[m][-1]) if len(self.hypers) else np.float32(0.1)
-                           for m in range(0, self.numNetworks, n)], dtype=np.float32)           # likelihood.py:116-117
+        sd = self._network_sd(lik, n)
         ch = self._ensure_chain()
         return ch.ensemble_loglik(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
                                   likelihood=lik.kind, sd=sd, weights=w)
+
+    def _network_sd(self, lik, n):
+        """the standard deviation of every n-th network under a Gaussian kind of likelihood, float32 [picked]: the fixed sd, or each
+        network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; None for the other likelihoods"""
+        from .likelihood import FixedGaussianLikelihood
+        picked = len(range(0, self.numNetworks, n))
+        if isinstance(lik, FixedGaussianLikelihood):
+            return np.full(picked, np.float32(lik.sd), dtype=np.float32)                        # likelihood.py:195 (not squared)
+        if isinstance(lik, GaussianLikelihood):
+            return np.array([np.float32(self.hypers[m][-1]) if len(self.hypers) else np.float32(0.1)
+                             for m in range(0, self.numNetworks, n)], dtype=np.float32)         # likelihood.py:116-117
+        return None
+
+    # ---- the predictive distribution of a new observation: observation noise included (tbnn_ensemble_predictive) ----
+    def _predictive_likelihood(self, likelihood):
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if isinstance(lik, (BernoulliLikelihood, CategoricalLikelihood)):
+            raise ValueError("the predictive distribution of a label is its posterior-mean probability: predictMoments returns it")
+        return lik
+
+    def predictiveQuantiles(self, inputMatrix, probs, n=1, weights=None, likelihood=None, sd=1.0, mean=0.0):
+        """Quantiles of the PREDICTIVE distribution of a new observation at the probabilities `probs` (each in (0, 1)), float64
+        [n_probs, d_out, rows] (a scalar `probs`: [d_out, rows]): the mixture over every n-th network of the observation model around
+        its prediction, inverted on the device -- under a Gaussian kind of likelihood N(f_i, s_i^2) with s_i the network's own standard
+        deviation (its saved last hyper as logPredictiveDensity reads it, or the fixed sd), under a PoissonLikelihood the counts'
+        Poisson(exp(f_i)), whose quantile is the smallest count k with F(k) >= p.  likelihood None: the predictor's own.  weights: one
+        per picked network, e.g. what reweight returns.  The result is q * sd + mean, the de-normalisation of the metrics, applied on
+        the host in fp64: sd > 0, and counts take none (sd = 1, mean = 0).  predictQuantiles gives the credible quantiles of the
+        network's output instead; Bernoulli and categorical likelihoods are refused (predictMoments returns a label's probability)."""
+        from .likelihood import PoissonLikelihood
+        lik = self._predictive_likelihood(likelihood)
+        sd, mean = float(sd), float(mean)
+        if not sd > 0.0:
+            raise ValueError("sd must be > 0 (a negative scale would turn the quantiles round)")
+        if isinstance(lik, PoissonLikelihood) and (sd != 1.0 or mean != 0.0):
+            raise ValueError("counts are not de-normalised: sd = 1, mean = 0 under a PoissonLikelihood")
+        picked, w = self._picked(n, weights)
+        pr = np.asarray(probs, dtype=np.float64)
+        ch = self._ensure_chain()
+        q, _F, _Fb = ch.ensemble_predictive(picked, probs=pr.reshape(-1), X=np.asarray(inputMatrix, dtype=np.float32), likelihood=lik.kind,
+                                            sd=self._network_sd(lik, n), weights=w)
+        if sd != 1.0 or mean != 0.0:
+            q = q * sd + mean
+        return q[0] if pr.ndim == 0 else q
+
+    def predictiveInterval(self, inputMatrix, level=0.9, **kwargs):
+        """(lower, median, upper), each float64 [d_out, rows]: the predictive quantiles at (1 - level) / 2, 1 / 2 and (1 + level) / 2 from
+        one call of predictiveQuantiles, whose other arguments pass through -- the central PREDICTIVE interval, which a new observation
+        falls into with probability `level` (predictInterval's credible interval covers the network's output only)."""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        d = Decimal(repr(level))                       # in decimal, as predictInterval: level = 0.9 asks for 0.05 and 0.95 themselves
+        q = self.predictiveQuantiles(inputMatrix, [float((1 - d) / 2), 0.5, float((1 + d) / 2)], **kwargs)
+        return q[0], q[1], q[2]
+
+    def predictiveCDF(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
+        """The PIT values of the rows: the predictive CDF of predictiveQuantiles at the observed targets realVals, float64 [d_out, rows]
+        -- uniform on (0, 1) over held-out rows when the predictive distribution is calibrated.  Targets in the networks' own
+        (normalised) units.  Under a PoissonLikelihood the pair (F(y - 1), F(y)): a count's PIT value lies anywhere on its step."""
+        from .likelihood import PoissonLikelihood
+        lik = self._predictive_likelihood(likelihood)
+        picked, w = self._picked(n, weights)
+        ch = self._ensure_chain()
+        _q, F, Fb = ch.ensemble_predictive(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
+                                           likelihood=lik.kind, sd=self._network_sd(lik, n), weights=w)
+        return (Fb, F) if isinstance(lik, PoissonLikelihood) else F
 
     def _ensure_chain(self):
         if self._chain is None:
