@@ -349,6 +349,38 @@ int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64
 int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                              const float* net_w, int which, const float* X, const float* Y, int64_t n, const double* probs,
                              int32_t n_probs, double* q_out, double* cdf_out, double* cdf_below_out);
+/* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
+ * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
+ * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).
+ * Arguments up to `n` as tbnn_ensemble_loglik's (likelihood, sd, rows, targets), without net_w: smoothing the ratios of an ensemble that is
+ * already importance-weighted is not defined here.  r_eff: the relative efficiency of the draws (1: independent), one number for all rows.
+ * l_i is the row's log-likelihood under network i, summed over its outputs: the terms of tbnn_ensemble_loglik, the same bits.  Everything
+ * after l_i is fp64, not contracted.  Per row:
+ *   lppd      logsumexp_i(l_i) - log m                                  (the bits of tbnn_ensemble_loglik's lppd_rows without weights)
+ *   p_waic    sum_i (l_i - mean l)^2 / (m - 1), centred; elpd_waic = lppd - p_waic is left to the caller
+ *   ratios    x_i = -l_i - max_j(-l_j): the largest is exactly 0
+ *   tail      M = ceil(min(0.2 m, 3 sqrt(m / r_eff))); with v_(1) <= ... <= v_(m) the sorted x, the tail is v_(m-M+1 .. m) and the cutoff
+ *             c = v_(m-M).  Only the multiset of values counts, so ties need no rule
+ *   no smoothing if M < 5, or the tail's range v_(m) - v_(m-M+1) is 0, or y_(q) below is not > 0: k = +inf and the raw x_i are used
+ *   fit       (Zhang and Stephens 2009, with loo's priors)  y_j = exp(v_(m-M+j)) - exp(c), j = 1 .. M; q = floor(M / 4 + 1/2),
+ *             G = 30 + floor(sqrt M); for g = 1 .. G: b_g = 1 / y_(M) + (1 - sqrt(G / (g - 1/2))) / (3 y_(q)),
+ *             kappa_g = (1/M) sum_j log1p(-b_g y_j), L_g = M (log(-b_g / kappa_g) - kappa_g - 1), w_g = exp(L_g - logsumexp_g L), all G kept;
+ *             b = sum_g b_g w_g, kappa = (1/M) sum_j log1p(-b y_j), sigma = -kappa / b, k = (M kappa + 5) / (M + 10)
+ *   smoothing the j-th smallest tail value becomes log(exp(c) + sigma expm1(-k log1p(-p_j)) / k), p_j = (j - 1/2) / M (|k| < 2^-52:
+ *             -sigma log1p(-p_j) for the quotient), then at most 0.  A k or sigma that is not finite: the raw x_i, and the k obtained
+ *   loo       with the final lw_i: elpd_loo = logsumexp_i(lw_i + l_i) - logsumexp_i(lw_i)
+ * A NaN or infinity among a row's l_i gives NaN in every row output of that row; its neighbours are unaffected.  pareto_k says where
+ * elpd_loo can be trusted (below min(1 - 1 / log10 m, 0.7)).  elpd_loo_rows, pareto_k_rows, lppd_rows, p_waic_rows: n doubles each, or
+ * NULL; pointwise: host [m][n] doubles = l_i per row (ArviZ's log_likelihood group), or NULL; at least one of the five.  Without
+ * elpd_loo_rows and pareto_k_rows the smoothing kernel is not launched.  The device finds c without a sort (bisection on the order-preserving
+ * 64-bit key of an fp64 value, 64 passes over the row's m values), ranks the tail by counting and carries the fit's weights as running sums;
+ * one thread per row, the same bits from run to run and whatever the blocks.  The rows are cut into blocks as for tbnn_ensemble_quantiles,
+ * the matrix column and the tail, 8 m + 16 M bytes per row, counted into the same budget beside the 4 m d_out of the predictions.
+ * Refused, with nothing written: every output NULL, r_eff not finite or not > 0, m < 2, X without Y, n not matching the staged rows, an
+ * unknown likelihood code, TBNN_LIK_CATEGORICAL with d_out < 2, a NaN sd, (m d_out + 2 m + 4 M) 64 > 2^28. */
+int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                      int which, const float* X, const float* Y, int64_t n, double r_eff, double* elpd_loo_rows, double* pareto_k_rows,
+                      double* lppd_rows, double* p_waic_rows, double* pointwise);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)
  *   out3[0] = mean (p-r)^2            SquaredError

@@ -102,6 +102,7 @@ SYMBOLS = [
     ("tbnn_ensemble_loglik", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_ensemble_predictive", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp,
                                            _dp]),
+    ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
     ("tbnn_hyper_probs_many", C.c_int, [_H, C.POINTER(C.c_int32), _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _dp]),
     ("tbnn_register_kernel_lib", C.c_int, [C.c_char_p]),
@@ -532,6 +533,29 @@ class Chain:
         _check(lib.tbnn_ensemble_predictive(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
                                             dpp(pr), 0 if pr is None else pr.size, dpp(q), dpp(F), dpp(Fb)))
         return q, F, Fb
+
+    def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,
+                     psis: bool = True):
+        """Pareto-smoothed importance-sampling leave-one-out cross-validation and WAIC of an ensemble, reduced on the device
+        (tbnn_ensemble_loo; the definition is in include/tbnn.h): a dict of float64 arrays over the rows -- elpd_loo, pareto_k (+inf where
+        the row's ratios were not smoothed), lppd, p_waic -- and, with pointwise=True, pointwise [m, rows]: the log-likelihood of every row
+        under every network.  A row with a log-likelihood that is not finite is NaN in all four.  likelihood, sd, Y, X, which: as
+        ensemble_loglik's; r_eff: the relative efficiency of the draws (1: independent).  There are no network weights.  psis=False (WAIC
+        alone): elpd_loo and pareto_k are left out and the smoothing kernel is not launched."""
+        th, xp, n, _w = self._ensemble_args(thetas, X, which, None)
+        if xp is not None and Y is None:
+            raise ValueError("rows X need their targets Y")
+        yp = None if Y is None else _f32(Y).reshape(-1, self.d_out)
+        if yp is not None and yp.shape[0] != n:
+            raise ValueError(f"Y must hold {n} rows")
+        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (th.shape[0],)))
+        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        out = {k: np.empty(n, dtype=np.float64) for k in (("elpd_loo", "pareto_k") if psis else ()) + ("lppd", "p_waic")}
+        if pointwise:
+            out["pointwise"] = np.empty((th.shape[0], n), dtype=np.float64)
+        _check(lib.tbnn_ensemble_loo(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), int(which), _p(xp), _p(yp), n, float(r_eff),
+                                     *[out[k].ctypes.data_as(_dp) if k in out else None for k in ("elpd_loo", "pareto_k", "lppd", "p_waic", "pointwise")]))
+        return out
 
     def hyper_probs_many(self, thetas, etas, priors=None) -> np.ndarray:
         """sum over the dense layers of calculateHyperProbs for m saved networks (predictor.trainProbs / reweight):

@@ -26,6 +26,10 @@
 //             probability -- Gaussian kinds: a verified bracket, then Newton steps safeguarded by bisection; Poisson: a search over the
 //             integers -- every trial one pass over the element's m predictions.  All fp64, contraction off: a slot's result does not
 //             depend on its neighbours or on the grid.
+//   loo         the same block, untransformed: k_ens_pointwise writes the matrix l[m][rb] of row log-likelihoods (ens_row_loglik, the terms of
+//             k_ens_loglik) with the rows' lppd and p_waic; k_ens_psis smooths each row's importance ratios (definition: include/tbnn.h,
+//             tbnn_ensemble_loo): the cutoff by bisection on the order-preserving 64-bit key, the tail gathered into a scratch [M][rb] and
+//             ranked there by counting, the generalised Pareto fit in one sweep over the G candidates.  All fp64, contraction off.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -168,6 +172,12 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
     return l;
 }
 
+// one more term a of a running log-sum-exp: M the maximum so far, S = sum exp(a_i - M)
+__device__ __forceinline__ void ens_lse_step(double a, double& M, double& S) {
+    if (a > M) { S = fma(S, exp(M - a), 1.0); M = a; }            // (M = -inf: S = 0, exp(-inf) = 0)
+    else if (a != -INFINITY) S += exp(a - M);                    // (a NaN prediction stays visible)
+}
+
 // One row per thread (the grid covers n).  sig / cst: the chunk's c sigmas and constants (Gaussian kinds; else unused); lw: the chunk's c
 // log weights, -inf for a weight of 0, or null (equal: log 1); lse: [2][n] or null (no row-wise mixture wanted); part: [gridDim.x][c] or null
 __global__ __launch_bounds__(ENS_TB) void k_ens_loglik(const float* __restrict__ out, int c, long n, int d_out, int lik, const float* __restrict__ Y,
@@ -188,9 +198,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_loglik(const float* __restrict__
             if (valid) {
                 l = ens_row_loglik(lik, out + (size_t)i * tot + row, n, Y + (size_t)row * d_out, d_out, sig ? sig[i] : 1.f, cst ? cst[i] : 0.0);
                 if (lse) {
-                    const double a = (lw ? lw[i] : 0.0) + l;
-                    if (a > M) { S = fma(S, exp(M - a), 1.0); M = a; }            // (M = -inf: S = 0, exp(-inf) = 0)
-                    else if (a != -INFINITY) S += exp(a - M);                    // (a NaN prediction stays visible)
+                    ens_lse_step((lw ? lw[i] : 0.0) + l, M, S);
                 }
             }
             if (part) {
@@ -700,5 +708,189 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
             for (int j = 0; j < QP; ++j)
                 if (p0 + j < np) res[(size_t)(p0 + j) * tot + e] = bad ? (double)NAN : b[j];
         }
+    }
+}
+
+// ---- Pareto-smoothed leave-one-out cross-validation and WAIC ----
+// out: the block [m][d_out][r] of untransformed predictions; Y: the block's targets [r][d_out]; sig / cst: the m sigmas and constants of
+// k_ens_loglik (Gaussian kinds; else null).  L[m][r] = l_i of every row, by ens_row_loglik: the bits k_ens_loglik sums.  lppd[r] (or null) =
+// logsumexp_i l_i - log m, by the steps and in the order of k_ens_loglik / k_ens_lppd_finish: the same bits; pwaic[r] (or null) = the
+// centred sum of squares of the row's l_i over m - 1, the l_i read back from L.  A row with an l_i that is not finite gives NaN in both.
+__global__ __launch_bounds__(ENS_TB) void k_ens_pointwise(const float* __restrict__ out, int m, long r, int d_out, int lik, const float* __restrict__ Y,
+                                                           const float* __restrict__ sig, const double* __restrict__ cst, double logm,
+                                                           double* L, double* __restrict__ lppd, double* __restrict__ pwaic) {
+#pragma clang fp contract(off)
+    const long tot = r * d_out;
+    for (long row = (long)blockIdx.x * ENS_TB + threadIdx.x; row < r; row += (long)gridDim.x * ENS_TB) {
+        double Mx = -INFINITY, S = 0.0, sum = 0.0;
+        int bad = 0;
+        for (int i = 0; i < m; ++i) {
+            const double l = ens_row_loglik(lik, out + (size_t)i * tot + row, r, Y + (size_t)row * d_out, d_out, sig ? sig[i] : 1.f, cst ? cst[i] : 0.0);
+            L[(size_t)i * r + row] = l;
+            bad += !(fabs(l) < INFINITY);
+            ens_lse_step(l, Mx, S);
+            sum += l;
+        }
+        if (lppd) lppd[row] = bad ? (double)NAN : Mx + log(S) - logm;
+        if (pwaic) {
+            const double mean = sum / (double)m;
+            double ss = 0.0;
+#pragma unroll 4
+            for (int i = 0; i < m; ++i) {
+                const double d = L[(size_t)i * r + row] - mean;
+                ss += d * d;
+            }
+            pwaic[row] = bad ? (double)NAN : ss / (double)(m - 1);
+        }
+    }
+}
+
+// the order-preserving key of an fp64 value (ens_key's rule)
+__device__ __forceinline__ unsigned long long ens_key64(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return b ^ ((b >> 63) ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ens_unkey64(unsigned long long k) {
+    return __longlong_as_double((long long)(k ^ ((k >> 63) ? 0x8000000000000000ull : 0xFFFFFFFFFFFFFFFFull)));
+}
+
+// the raw log ratio x_i = -l_i - max_j(-l_j); adding 0 turns a -0 into +0, so that equal values have equal keys
+__device__ __forceinline__ double ens_psis_x(double l, double mx) {
+#pragma clang fp contract(off)
+    return (-l - mx) + 0.0;
+}
+
+// L: the block's matrix [m][r]; M, G, q: the tail length, the number of candidates and the quartile index of tbnn_ensemble_loo, from the
+// host; ta, tb: scratch [M][r] each; elpd, pk: [r].  A thread owns its row (the result does not depend on the grid) and walks, all in fp64:
+//   maximum   mx = max_i(-l_i), and the check that every l_i is finite (else NaN, NaN)
+//   cutoff    c = v_(m-M), the smallest key K with count(key(x_i) <= K) >= m - M, its 64 bits fixed from the top as k_ens_quantiles fixes 32
+//   tail      the x_i > c and, of those equal to c, the last M - count(x_i > c) in network order (the members a stable sort puts last; the
+//             values are what counts), written to ta in network order; their rank among the M -- the count of smaller values, and of equal
+//             ones earlier in ta -- goes to tb, then y_j = exp(x_j) - exp(c) over x_j in ta.  M^2 comparisons: below the fit's M G log1p up
+//             to M of a few thousand
+//   fit       one sweep over g = 1 .. G: the weights exp(L_g - logsumexp L) and b = sum_g b_g w_g are carried as a running maximum of L_g
+//             and the two sums S = sum exp(L_g - max), B = sum b_g exp(L_g - max), rescaled when the maximum moves; b = B / S.  No L_g is
+//             kept and none recomputed
+//   closing   a second walk over the networks finds the tail's members by the same rule and gives each the quantile of its rank; the two
+//             log-sum-exps run in network order
+// No per-thread array: ta and tb are read at stride r (coalesced: the lanes of a wave ask for the same j).
+__global__ __launch_bounds__(ENS_TB) void k_ens_psis(const double* __restrict__ L, int m, long r, int M, int G, int q, double* ta, double* tb,
+                                                      double* __restrict__ elpd, double* __restrict__ pk) {
+#pragma clang fp contract(off)
+    const double dM = (double)M, dG = (double)G;
+    for (long row = (long)blockIdx.x * ENS_TB + threadIdx.x; row < r; row += (long)gridDim.x * ENS_TB) {
+        const double* __restrict__ Lr = L + row;
+        double* A = ta + row;
+        double* B = tb + row;
+        double mx = -INFINITY;
+        int bad = 0;
+#pragma unroll 4
+        for (int i = 0; i < m; ++i) {
+            const double l = Lr[(size_t)i * r];
+            bad += !(fabs(l) < INFINITY);
+            mx = fmax(mx, -l);
+        }
+        if (bad) {
+            if (elpd) elpd[row] = (double)NAN;
+            if (pk) pk[row] = (double)NAN;
+            continue;
+        }
+        const int need = m - M;
+        unsigned long long K = 0ull;
+        for (int bit = 63; bit >= 0; --bit) {
+            const unsigned long long trial = K | ((1ull << bit) - 1ull);
+            int cnt = 0;
+#pragma unroll 8
+            for (int i = 0; i < m; ++i) cnt += ens_key64(ens_psis_x(Lr[(size_t)i * r], mx)) <= trial;
+            if (cnt < need) K |= 1ull << bit;
+        }
+        const double c = ens_unkey64(K);
+        int above = 0, ties = 0;
+#pragma unroll 4
+        for (int i = 0; i < m; ++i) {
+            const double x = ens_psis_x(Lr[(size_t)i * r], mx);
+            above += x > c;
+            ties += x == c;
+        }
+        const int first_tie = ties - (M - above);          // ties before this one (network order) stay below the tail
+        int pos = 0, seen = 0;
+        double tmin = 0.0;
+        for (int i = 0; i < m; ++i) {
+            const double x = ens_psis_x(Lr[(size_t)i * r], mx);
+            bool in = x > c;
+            if (x == c) { in = seen >= first_tie; ++seen; }
+            if (in && pos < M) { A[(size_t)pos * r] = x; tmin = fmin(tmin, x); ++pos; }
+        }
+        double kk = (double)INFINITY, sigma = 0.0, ec = 0.0;
+        bool smooth = M >= 5 && pos == M && tmin < 0.0;         // (the largest x is 0 and is in the tail: the range is -tmin)
+        if (smooth) {
+            for (int j = 0; j < M; ++j) {
+                const double xj = A[(size_t)j * r];
+                int cnt = 0;
+#pragma unroll 8
+                for (int jj = 0; jj < M; ++jj) {
+                    const double v = A[(size_t)jj * r];
+                    cnt += (v < xj) || (v == xj && jj < j);
+                }
+                B[(size_t)j * r] = (double)cnt;
+            }
+            ec = exp(c);
+            double yq = 0.0, yM = 0.0;
+            for (int j = 0; j < M; ++j) {
+                const double y = exp(A[(size_t)j * r]) - ec;
+                if ((int)B[(size_t)j * r] == q - 1) yq = y;
+                yM = fmax(yM, y);
+                A[(size_t)j * r] = y;
+            }
+            smooth = yq > 0.0;
+            if (smooth) {
+                double Lmax = -INFINITY, S = 0.0, Bs = 0.0;
+                for (int g = 1; g <= G; ++g) {
+                    const double b = 1.0 / yM + (1.0 - sqrt(dG / ((double)g - 0.5))) / (3.0 * yq);
+                    double ks = 0.0;
+#pragma unroll 4
+                    for (int j = 0; j < M; ++j) ks += log1p(-b * A[(size_t)j * r]);
+                    const double kap = ks / dM;
+                    const double Lg = dM * (log(-b / kap) - kap - 1.0);
+                    if (Lg > Lmax) {
+                        const double e = exp(Lmax - Lg);
+                        S = S * e + 1.0; Bs = Bs * e + b; Lmax = Lg;
+                    } else {
+                        const double e = exp(Lg - Lmax);            // (a NaN L_g reaches b, and k with it)
+                        S += e; Bs += b * e;
+                    }
+                }
+                const double b = Bs / S;
+                double ks = 0.0;
+#pragma unroll 4
+                for (int j = 0; j < M; ++j) ks += log1p(-b * A[(size_t)j * r]);
+                const double kap = ks / dM;
+                sigma = -kap / b;
+                kk = (dM * kap + 5.0) / (dM + 10.0);
+                smooth = fabs(kk) < INFINITY && fabs(sigma) < INFINITY;      // else the raw ratios, and the k obtained
+            }
+        }
+        if (pk) pk[row] = kk;
+        if (!elpd) continue;
+        double M1 = -INFINITY, S1 = 0.0, M2 = -INFINITY, S2 = 0.0;
+        pos = 0; seen = 0;
+        for (int i = 0; i < m; ++i) {
+            const double l = Lr[(size_t)i * r];
+            const double x = ens_psis_x(l, mx);
+            bool in = x > c;
+            if (x == c) { in = seen >= first_tie; ++seen; }
+            double lw = x;
+            if (in && pos < M) {
+                if (smooth) {
+                    const double z = log1p(-((B[(size_t)pos * r] + 0.5) / dM));
+                    const double qv = fabs(kk) < 0x1p-52 ? -sigma * z : sigma * expm1(-kk * z) / kk;
+                    lw = fmin(log(ec + qv), 0.0);
+                }
+                ++pos;
+            }
+            ens_lse_step(lw + l, M1, S1);
+            ens_lse_step(lw, M2, S2);
+        }
+        elpd[row] = (M1 + log(S1)) - (M2 + log(S2));
     }
 }

@@ -1049,14 +1049,15 @@ extern "C" int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t
 // synchronised after every block.  rb: what keeps a block's predictions, m d_out rb floats, within ens_chunk_floats(), rounded down to a
 // multiple of 64 and never below 64 -- a block then starts as aligned within dX as dX itself is for the forward kernels' vector loads; the
 // debug override may therefore be exceeded by up to 64 rows' worth.  The consumer's per-block results are outside that budget: never more
-// than the caller's own output.  begin(rb) runs once before the first block (the consumer's buffers and staged arguments).  Thetas are
-// staged once; be->forward builds a block's weight images into the one scratch allocated here.
+// than the caller's own output.  extra_row_bytes: what a consumer keeps per row BESIDE the predictions in proportion to m (tbnn_ensemble_loo's
+// matrix and tail), counted into the budget in floats; 0 for the others.  begin(rb) runs once before the first block (the consumer's
+// buffers and staged arguments).  Thetas are staged once; be->forward builds a block's weight images into the one scratch allocated here.
 template <class Begin, class Each>
 static int ensemble_row_blocks(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int xform, float scale,
-                               float shift, int which, const float* X, int64_t n, Begin&& begin, Each&& each) {
+                               float shift, int which, const float* X, int64_t n, Begin&& begin, Each&& each, size_t extra_row_bytes = 0) {
     const NetDev& nd = h->nd;
     const int d_out = nd.d_out;
-    const size_t per_row = (size_t)m * (size_t)d_out;
+    const size_t per_row = (size_t)m * (size_t)d_out + (extra_row_bytes + sizeof(float) - 1) / sizeof(float);
     if (per_row * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
     const float* dX = nullptr;
     Buf<float> dXown;
@@ -1441,6 +1442,100 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
             }
             return 0;
         });
+}
+
+// M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)
+static void psis_sizes(int32_t m, double r_eff, int* M, int* G, int* q) {
+    *M = (int)std::ceil(std::min(0.2 * (double)m, 3.0 * std::sqrt((double)m / r_eff)));
+    *G = 30 + (int)std::floor(std::sqrt((double)*M));
+    *q = (int)std::floor((double)*M / 4.0 + 0.5);
+}
+// what tbnn_ensemble_loo keeps per row beside the predictions: the matrix column (m doubles) and the tail's two planes (2 M doubles)
+static size_t psis_row_bytes(int32_t m, int M) { return sizeof(double) * ((size_t)m + 2 * (size_t)M); }
+
+extern "C" int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                                 int which, const float* X, const float* Y, int64_t n, double r_eff, double* elpd_loo_rows,
+                                 double* pareto_k_rows, double* lppd_rows, double* p_waic_rows, double* pointwise) {
+    NEED(h);
+    const std::string who = "ensemble_loo";
+    const int d_out = h->nd.d_out;
+    if (!elpd_loo_rows && !pareto_k_rows && !lppd_rows && !p_waic_rows && !pointwise) return fail(-1, who + ": every output is null");
+    if (!(r_eff > 0.0) || !std::isfinite(r_eff)) return fail(-1, who + ": r_eff must be finite and > 0");
+    if (!lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
+    if (likelihood == TBNN_LIK_CATEGORICAL && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (m < 2) return fail(-1, who + ": fewer than 2 networks");
+    int M = 0, G = 0, q = 0;
+    psis_sizes(m, r_eff, &M, &G, &q);
+    const size_t extra = psis_row_bytes(m, M);
+    if (((size_t)m * (size_t)d_out + extra / sizeof(float)) * 64 > ENS_CHUNK_FLOATS)
+        return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
+    const float* dYrows = nullptr;
+    if (Y && !X && (which == 0 || which == 1)) {
+        const long staged = which ? h->nv : h->n;
+        if (staged >= 1 && n != staged) return fail(-1, who + ": n = " + std::to_string((long long)n) + " does not match the " + std::to_string(staged) + " staged rows");
+    }
+    if (!Y) {
+        dYrows = which == 0 ? h->dY : which == 1 ? h->dYv : nullptr;
+        if ((which == 0 || which == 1) && (which ? h->nv : h->n) >= 1 && !dYrows) return fail(-1, who + ": no staged targets");
+    }
+    const bool gauss = likelihood == TBNN_LIK_GAUSSIAN || likelihood == TBNN_LIK_FIXED_GAUSSIAN;
+    // per network: sigma and -log sigma - 1/2 log 2 pi, as tbnn_ensemble_loglik stages them
+    std::vector<float> sig;
+    std::vector<double> cst;
+    if (gauss) {
+        sig.resize((size_t)m); cst.resize((size_t)m);
+        for (int32_t i = 0; i < m; ++i) {
+            const float s = sd ? sd[i] : h->nd.fixed_sd;
+            if (std::isnan(s)) return fail(-1, who + ": sd " + std::to_string(i) + " is not a number");
+            sig[i] = std::min(std::max(s, 1e-8f), 1e8f);
+            cst[i] = -std::log((double)sig[i]) - 0.5 * std::log(2.0 * M_PI);
+        }
+    }
+    const bool psis = elpd_loo_rows || pareto_k_rows;
+    const double logm = std::log((double)m);
+    Buf<float> dSig, dY;
+    Buf<double> dCst, dL, dTail, dRes;
+    long rbk = 0;
+    return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
+        [&](long rb) -> int {
+            rbk = rb;
+            HIPCHK(dL.alloc((size_t)m * rb));
+            if (psis) HIPCHK(dTail.alloc(2 * (size_t)M * rb));
+            // a block's row results: elpd_loo, pareto_k, lppd, p_waic
+            HIPCHK(dRes.alloc(4 * (size_t)rb));
+            if (gauss) {
+                HIPCHK(dSig.alloc((size_t)m)); HIPCHK(dCst.alloc((size_t)m));
+                HIPCHK(hipMemcpyAsync(dSig, sig.data(), (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(hipMemcpyAsync(dCst, cst.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            }
+            if (Y) {
+                HIPCHK(dY.alloc((size_t)n * d_out));
+                HIPCHK(hipMemcpyAsync(dY, Y, (size_t)n * d_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                dYrows = dY;
+            }
+            return 0;
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            const dim3 grid(ens_grid(r)), tb(ENS_TB);
+            double* res = dRes;
+            hipLaunchKernelGGL(k_ens_pointwise, grid, tb, 0, h->stream, t, (int)m, r, d_out, likelihood, dYrows + (size_t)r0 * d_out,
+                               gauss ? (const float*)dSig : nullptr, gauss ? (const double*)dCst : nullptr, logm, (double*)dL,
+                               lppd_rows ? res + 2 * rbk : nullptr, p_waic_rows ? res + 3 * rbk : nullptr);
+            HIPCHK(hipGetLastError());
+            if (psis) {
+                hipLaunchKernelGGL(k_ens_psis, grid, tb, 0, h->stream, (const double*)dL, (int)m, r, M, G, q, (double*)dTail, dTail + (size_t)M * rbk,
+                                   elpd_loo_rows ? res : nullptr, pareto_k_rows ? res + rbk : nullptr);
+                HIPCHK(hipGetLastError());
+            }
+            double* const outs[4] = {elpd_loo_rows, pareto_k_rows, lppd_rows, p_waic_rows};
+            for (int k = 0; k < 4; ++k)
+                if (outs[k]) HIPCHK(hipMemcpyAsync(outs[k] + r0, res + (size_t)k * rbk, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            // l[m][r] -> pointwise[m][rows] at column r0
+            if (pointwise) HIPCHK(hipMemcpy2DAsync(pointwise + r0, (size_t)rows * sizeof(double), dL, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                                    (size_t)m, hipMemcpyDeviceToHost, h->stream));
+            return 0;
+        }, extra);
 }
 
 extern "C" int tbnn_metrics(tbnn_handle h, int which, const float* theta, float mean, float sd, int exp_pred, int exp_real,

@@ -290,6 +290,68 @@ class predictor(object):
         return ch.ensemble_loglik(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
                                   likelihood=lik.kind, sd=sd, weights=w)
 
+    # ---- out-of-sample model comparison on the device: PSIS-LOO and WAIC (tbnn_ensemble_loo) ----
+    def _loo_rows(self, inputMatrix, realVals, n, likelihood, r_eff, pointwise, psis=True):
+        lik = self.likelihood if likelihood is None else likelihood
+        picked, _w = self._picked(n, None)
+        ch = self._ensure_chain()
+        return ch.ensemble_loo(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
+                               likelihood=lik.kind, sd=self._network_sd(lik, n), r_eff=float(r_eff), pointwise=pointwise, psis=psis), picked.shape[0]
+
+    @staticmethod
+    def _elpd_summary(name, ic, rows, lppd):
+        """the sum of the rows, its standard error sqrt(n var(rows, ddof=1)) and the effective number of parameters sum(lppd - rows)"""
+        rows = np.asarray(rows, dtype=np.float64)
+        total = float(rows.sum())
+        se = float(np.sqrt(rows.size * np.var(rows, ddof=1))) if rows.size > 1 else float("nan")
+        return {"elpd_" + name: total, "se": se, "p_" + name: float(np.sum(lppd - rows)), ic: -2.0 * total}
+
+    def loo(self, inputMatrix, realVals, n=1, likelihood=None, r_eff=1.0, pointwise=False):
+        """Which model predicts better out of sample?  Pareto-smoothed importance-sampling leave-one-out cross-validation of every n-th
+        network over the rows (Vehtari, Gelman, Gabry 2017; the R package loo's algorithm, stated in include/tbnn.h), formed and smoothed
+        on the device.  Returns a dict: elpd_loo (the sum over the rows), se = sqrt(rows var(elpd_loo_rows, ddof=1)),
+        p_loo = sum(lppd_rows - elpd_loo_rows), looic = -2 elpd_loo; the row arrays elpd_loo_rows, lppd_rows and pareto_k (float64 [rows];
+        +inf where a row's ratios were not smoothed), k_threshold = min(1 - 1 / log10(m), 0.7) and n_bad_k, the number of rows above it,
+        where the estimate cannot be trusted; with pointwise=True also pointwise, float64 [m, rows]: the log-likelihood matrix (ArviZ's
+        log_likelihood group).  likelihood None: the predictor's own; under a GaussianLikelihood each network's standard deviation is its
+        saved last hyper, as in logPredictiveDensity.  r_eff: the relative efficiency of the draws (1: independent; predictDiagnostics'
+        ess over the number of draws is an estimate).  compareLoo compares two results over the same rows."""
+        res, m = self._loo_rows(inputMatrix, realVals, n, likelihood, r_eff, pointwise)
+        out = self._elpd_summary("loo", "looic", res["elpd_loo"], res["lppd"])
+        thr = min(1.0 - 1.0 / np.log10(m), 0.7)
+        k = res["pareto_k"]
+        out.update(elpd_loo_rows=res["elpd_loo"], lppd_rows=res["lppd"], pareto_k=k, k_threshold=float(thr), n_bad_k=int(np.sum(k > thr)))
+        if pointwise:
+            out["pointwise"] = res["pointwise"]
+        return out
+
+    def waic(self, inputMatrix, realVals, n=1, likelihood=None, pointwise=False):
+        """The widely applicable information criterion over the same matrix: elpd_waic (the sum over the rows of lppd - p_waic), se, p_waic
+        (the sum of the rows' centred variances of the log-likelihood over the networks), waic = -2 elpd_waic, and the row arrays
+        elpd_waic_rows, lppd_rows, p_waic_rows; with pointwise=True also the matrix.  Arguments as loo's."""
+        res, _m = self._loo_rows(inputMatrix, realVals, n, likelihood, 1.0, pointwise, psis=False)      # (the smoothing kernel is not launched)
+        rows = res["lppd"] - res["p_waic"]
+        out = self._elpd_summary("waic", "waic", rows, res["lppd"])
+        out.update(elpd_waic_rows=rows, lppd_rows=res["lppd"], p_waic_rows=res["p_waic"])
+        if pointwise:
+            out["pointwise"] = res["pointwise"]
+        return out
+
+    @staticmethod
+    def compareLoo(a, b):
+        """Two results of loo (or of waic) over the SAME rows, possibly of two predictors: elpd_diff = elpd(a) - elpd(b), the sum of the
+        rows' differences, and se_diff = sqrt(rows var(a_rows - b_rows, ddof=1)), the paired standard error.  Host only."""
+        def rows(r):
+            for key in ("elpd_loo_rows", "elpd_waic_rows"):
+                if key in r:
+                    return np.asarray(r[key], dtype=np.float64).reshape(-1)
+            raise ValueError("compareLoo takes the dicts loo or waic return")
+        ra, rb = rows(a), rows(b)
+        if ra.size != rb.size:
+            raise ValueError(f"the results cover {ra.size} and {rb.size} rows: a comparison needs the same rows")
+        d = ra - rb
+        return {"elpd_diff": float(d.sum()), "se_diff": float(np.sqrt(d.size * np.var(d, ddof=1))) if d.size > 1 else float("nan")}
+
     def _network_sd(self, lik, n):
         """the standard deviation of every n-th network under a Gaussian kind of likelihood, float32 [picked]: the fixed sd, or each
         network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; None for the other likelihoods"""
