@@ -198,6 +198,11 @@ def _p(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_fp)
 
 
+def _pd(a: Optional[np.ndarray]):
+    """the same for a float64 array"""
+    return None if a is None else a.ctypes.data_as(_dp)
+
+
 def build_id() -> str:
     """hash of the sources the loaded libtbnn.so was built from (tbnn_build_id)"""
     return lib.tbnn_build_id().decode()
@@ -362,7 +367,7 @@ class Chain:
         out = StepOut()
         tr = np.empty(L + 1, dtype=np.float64) if trace else None
         _check(lib.tbnn_hmc_step(self._h, float(eps), int(L), _p(p0a), _p(lua), C.byref(out),
-                                 None if tr is None else tr.ctypes.data_as(_dp)))
+                                 _pd(tr)))
         d = out.as_dict()
         if trace:
             d["trace_logp"] = tr
@@ -411,14 +416,7 @@ class Chain:
 
     def forward_many(self, thetas, X=None, which: int = 1) -> np.ndarray:
         """predictions of an ensemble: thetas [m, P] -> [m, d_out, rows]; X None: the staged rows (0 train, 1 validation)"""
-        th = np.ascontiguousarray(thetas, dtype=np.float32)
-        if th.ndim != 2 or th.shape[1] != self.P:
-            raise ValueError(f"thetas must be [m, {self.P}]")
-        if X is None:
-            n, xp = (self.nv if which else self.n), None
-        else:
-            xp = _f32(X).reshape(-1, self.d_in)
-            n = xp.shape[0]
+        th, xp, n, _w = self._ensemble_args(thetas, X, which, None)
         out = np.empty((th.shape[0], self.d_out, n), dtype=np.float32)
         _check(lib.tbnn_forward_many(self._h, _p(th), th.shape[0], th.shape[1], int(which), _p(xp), n, _p(out)))
         return out
@@ -437,6 +435,17 @@ class Chain:
             raise ValueError(f"weights must be one per network ({th.shape[0]})")
         return th, xp, n, w
 
+    def _ensemble_targets(self, m, xp, n, Y, sd, likelihood, want=True):
+        """(targets [n, d_out] or None, one sd per network or None, the LIK_* to judge under) as the entry points that read targets take
+        them; want=False: the targets are not asked for"""
+        if want and xp is not None and Y is None:
+            raise ValueError("rows X need their targets Y")
+        yp = None if (Y is None or not want) else _f32(Y).reshape(-1, self.d_out)
+        if yp is not None and yp.shape[0] != n:
+            raise ValueError(f"Y must hold {n} rows")
+        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (m,)))
+        return yp, sdp, self._jit_args[1] if likelihood is None else int(likelihood)
+
     def ensemble_moments(self, thetas, X=None, which: int = 1, weights=None, xform: int = XFORM_NONE, scale: float = 1.0,
                          shift: float = 0.0, var: bool = True):
         """posterior-predictive mean and population variance over an ensemble, reduced on the device (tbnn_ensemble_moments):
@@ -446,7 +455,7 @@ class Chain:
         mean = np.empty((self.d_out, n), dtype=np.float64)
         vr = np.empty((self.d_out, n), dtype=np.float64) if var else None
         _check(lib.tbnn_ensemble_moments(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), float(shift), int(which),
-                                         _p(xp), n, mean.ctypes.data_as(_dp), None if vr is None else vr.ctypes.data_as(_dp)))
+                                         _p(xp), n, _pd(mean), _pd(vr)))
         return mean, vr
 
     _QUANT_METHODS = {"linear": QUANT_LINEAR, "inverted_cdf": QUANT_INVERTED_CDF}
@@ -463,7 +472,7 @@ class Chain:
         pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
         out = np.empty((pr.size, self.d_out, n), dtype=np.float64)
         _check(lib.tbnn_ensemble_quantiles(self._h, _p(th), th.shape[0], th.shape[1], _p(w), self._QUANT_METHODS[method], int(xform), float(scale),
-                                           float(shift), int(which), _p(xp), n, pr.ctypes.data_as(_dp), pr.size, out.ctypes.data_as(_dp)))
+                                           float(shift), int(which), _p(xp), n, _pd(pr), pr.size, _pd(out)))
         return out
 
     def ensemble_diagnostics(self, thetas, chains: int = 1, X=None, which: int = 1, xform: int = XFORM_NONE, scale: float = 1.0,
@@ -476,7 +485,7 @@ class Chain:
         rhat = np.empty((self.d_out, n), dtype=np.float64)
         ess = np.empty((self.d_out, n), dtype=np.float64)
         _check(lib.tbnn_ensemble_diagnostics(self._h, _p(th), th.shape[0], th.shape[1], int(chains), int(xform), float(scale), float(shift),
-                                             int(which), _p(xp), n, rhat.ctypes.data_as(_dp), ess.ctypes.data_as(_dp)))
+                                             int(which), _p(xp), n, _pd(rhat), _pd(ess)))
         return rhat, ess
 
     def series_diagnostics(self, series, chains: int = 1):
@@ -486,8 +495,7 @@ class Chain:
         sr = sr.reshape(sr.shape[0], -1)
         rhat = np.empty(sr.shape[1], dtype=np.float64)
         ess = np.empty(sr.shape[1], dtype=np.float64)
-        _check(lib.tbnn_series_diagnostics(self._h, _p(sr), sr.shape[0], sr.shape[1], int(chains), rhat.ctypes.data_as(_dp),
-                                           ess.ctypes.data_as(_dp)))
+        _check(lib.tbnn_series_diagnostics(self._h, _p(sr), sr.shape[0], sr.shape[1], int(chains), _pd(rhat), _pd(ess)))
         return rhat, ess
 
     def ensemble_loglik(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None):
@@ -496,17 +504,11 @@ class Chain:
         likelihood: the LIK_* to judge under (None: the chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd);
         Y None with X None: the staged targets"""
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
-        if xp is not None and Y is None:
-            raise ValueError("rows X need their targets Y")
-        yp = None if Y is None else _f32(Y).reshape(-1, self.d_out)
-        if yp is not None and yp.shape[0] != n:
-            raise ValueError(f"Y must hold {n} rows")
-        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (th.shape[0],)))
-        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        yp, sdp, lik = self._ensemble_targets(th.shape[0], xp, n, Y, sd, likelihood)
         per_net = np.empty(th.shape[0], dtype=np.float64)
         rows = np.empty(n, dtype=np.float64)
         _check(lib.tbnn_ensemble_loglik(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
-                                        per_net.ctypes.data_as(_dp), rows.ctypes.data_as(_dp)))
+                                        _pd(per_net), _pd(rows)))
         return per_net, rows
 
     def ensemble_predictive(self, thetas, probs=None, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None, cdf=None):
@@ -518,20 +520,13 @@ class Chain:
         chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd)"""
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
         want_cdf = (Y is not None) if cdf is None else bool(cdf)
-        if want_cdf and xp is not None and Y is None:
-            raise ValueError("rows X need their targets Y")
-        yp = None if (Y is None or not want_cdf) else _f32(Y).reshape(-1, self.d_out)
-        if yp is not None and yp.shape[0] != n:
-            raise ValueError(f"Y must hold {n} rows")
-        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (th.shape[0],)))
-        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        yp, sdp, lik = self._ensemble_targets(th.shape[0], xp, n, Y, sd, likelihood, want=want_cdf)
         pr = None if probs is None else np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
         q = None if pr is None else np.empty((pr.size, self.d_out, n), dtype=np.float64)
         F = np.empty((self.d_out, n), dtype=np.float64) if want_cdf else None
         Fb = np.empty((self.d_out, n), dtype=np.float64) if want_cdf and lik == LIK_POISSON else None
-        dpp = lambda a: None if a is None else a.ctypes.data_as(_dp)
         _check(lib.tbnn_ensemble_predictive(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
-                                            dpp(pr), 0 if pr is None else pr.size, dpp(q), dpp(F), dpp(Fb)))
+                                            _pd(pr), 0 if pr is None else pr.size, _pd(q), _pd(F), _pd(Fb)))
         return q, F, Fb
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,
@@ -543,18 +538,12 @@ class Chain:
         ensemble_loglik's; r_eff: the relative efficiency of the draws (1: independent).  There are no network weights.  psis=False (WAIC
         alone): elpd_loo and pareto_k are left out and the smoothing kernel is not launched."""
         th, xp, n, _w = self._ensemble_args(thetas, X, which, None)
-        if xp is not None and Y is None:
-            raise ValueError("rows X need their targets Y")
-        yp = None if Y is None else _f32(Y).reshape(-1, self.d_out)
-        if yp is not None and yp.shape[0] != n:
-            raise ValueError(f"Y must hold {n} rows")
-        sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (th.shape[0],)))
-        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        yp, sdp, lik = self._ensemble_targets(th.shape[0], xp, n, Y, sd, likelihood)
         out = {k: np.empty(n, dtype=np.float64) for k in (("elpd_loo", "pareto_k") if psis else ()) + ("lppd", "p_waic")}
         if pointwise:
             out["pointwise"] = np.empty((th.shape[0], n), dtype=np.float64)
         _check(lib.tbnn_ensemble_loo(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), int(which), _p(xp), _p(yp), n, float(r_eff),
-                                     *[out[k].ctypes.data_as(_dp) if k in out else None for k in ("elpd_loo", "pareto_k", "lppd", "p_waic", "pointwise")]))
+                                     *[_pd(out.get(k)) for k in ("elpd_loo", "pareto_k", "lppd", "p_waic", "pointwise")]))
         return out
 
     def hyper_probs_many(self, thetas, etas, priors=None) -> np.ndarray:

@@ -3,6 +3,7 @@
 // forward passes and (where it has one) whole trajectories.  Each backend owns its plan and its private device buffers.
 // Host only, included by tbnn_api.hip alone, after the kernel headers and its owners and error helpers (Buf, fail, HIPCHK): nothing here
 // crosses the dlopen boundary -- a kernel library still registers a FusedOps table (fused_ops.hpp), which FusedBackend / WideBackend wrap.
+// tbnn_api.hip's include order: kernel headers, owners and error helpers, this file, tbnn_ctx and the launch helpers, ensemble_api.hpp.
 #pragma once
 
 // one gradient (forward + backward pass over the rows) for all chains of a handle

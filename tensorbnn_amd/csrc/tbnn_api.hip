@@ -899,644 +899,7 @@ extern "C" int tbnn_predict(tbnn_handle h, int which, const float* theta, float*
     return 0;
 }
 
-// the arguments every ensemble entry point checks alike, and the rows: *dX the staged rows, or the n host rows copied into dXown
-static int ensemble_rows(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X, int64_t n,
-                         Buf<float>& dXown, const float** dX, long* rows) {
-    const NetDev& nd = h->nd;
-    if (!thetas || m < 1 || theta_stride < nd.P) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    HIPCHK(hipSetDevice(h->device));
-    if (X) {
-        if (n < 1) return fail(-1, who + ": n < 1");
-        *rows = (long)n;
-        HIPCHK(dXown.alloc((size_t)*rows * nd.d_in));
-        HIPCHK(hipMemcpyAsync(dXown, X, (size_t)*rows * nd.d_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        *dX = dXown;
-    } else {
-        if (which != 0 && which != 1) return fail(-1, "which must be 0 (training rows) or 1 (validation rows)");
-        *dX = which ? h->dXv : h->dX; *rows = which ? h->nv : h->n;
-        if (!*dX || *rows < 1) return fail(-1, which ? "tbnn_set_validation has not been called" : "tbnn_set_data has not been called");
-    }
-    return 0;
-}
-
-// The part tbnn_forward_many and the ensemble reductions share: m networks, theta_i = thetas + i * theta_stride, over the same rows.
-// X == null: the staged rows selected by `which` (0 training, 1 validation); else n host rows.  The rows are staged, the networks cut
-// into chunks whose predictions take at most chunk_floats floats, each chunk's weights (and, narrow shapes, images) built and its forward
-// passes run into dOut[c][d_out][rows] on h->stream.  begin(rows, chunk) runs once before the first chunk (the consumer's buffers),
-// each(i0, c, dOut, rows) after every chunk's forward passes are enqueued; the stream is synchronised after each chunk.
-template <class Begin, class Each>
-static int ensemble_forward(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
-                            int64_t n, size_t chunk_floats, Begin&& begin, Each&& each) {
-    const NetDev& nd = h->nd;
-    const float* dX = nullptr;
-    Buf<float> dXown;
-    long rows = 0;
-    if (const int rc = ensemble_rows(h, who, thetas, m, theta_stride, which, X, n, dXown, &dX, &rows)) return rc;
-    const size_t per_net = (size_t)rows * nd.d_out;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, chunk_floats / std::max<size_t>(per_net, 1)));
-    Buf<float> dTh, dOut, dImg;
-    int rc = begin(rows, chunk);
-    if (rc) { hipStreamSynchronize(h->stream); return rc; }
-    HIPCHK(dTh.alloc((size_t)chunk * nd.P));
-    HIPCHK(dOut.alloc((size_t)chunk * per_net));
-    // one zeroed image per network of a chunk where the backend runs them as one launch, else the handle's one image in turn
-    const bool batched = h->be->forward_batched();
-    if (batched) {
-        HIPCHK(dImg.alloc((size_t)chunk * h->img_floats));
-        HIPCHK(hipMemsetAsync(dImg, 0, (size_t)chunk * h->img_floats * sizeof(float), h->stream));
-    }
-    for (int i0 = 0; i0 < m && !rc; i0 += chunk) {
-        const int c = std::min(chunk, m - i0);
-        HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
-                                (size_t)nd.P * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
-        rc = h->be->forward(h->stream, c, dTh, dX, rows, dOut, h->imgmap, batched ? (float*)dImg : (float*)h->qimg_cur);
-        if (!rc) {
-            HIPCHK(hipGetLastError());
-            rc = each(i0, c, (const float*)dOut, rows);
-            if (!rc) HIPCHK(hipStreamSynchronize(h->stream));
-        }
-    }
-    hipStreamSynchronize(h->stream);
-    return rc;
-}
-// networks per pass: the chunk of predictions stays below 1 GiB
-static const size_t ENS_CHUNK_FLOATS = (size_t)1 << 28;
-// the ensemble reductions alone: TBNN_ENS_CHUNK_FLOATS (debug) cuts the chunks smaller, so that a test reaches the carry-over between
-// chunks with a small problem; tbnn_forward_many does not read it
-// (tbnn_ensemble_quantiles cuts rows with it, in multiples of 64: there the value may be exceeded by up to 64 rows' worth)
-static size_t ens_chunk_floats() {
-    if (const char* e = getenv("TBNN_ENS_CHUNK_FLOATS")) { const long long v = atoll(e); if (v >= 1 && (size_t)v < ENS_CHUNK_FLOATS) return (size_t)v; }
-    return ENS_CHUNK_FLOATS;
-}
-
-// Ensemble prediction (predictor.py:132-155).  out[m][d_out][n].
-extern "C" int tbnn_forward_many(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int which, const float* X,
-                                 int64_t n, float* out) {
-    NEED(h);
-    if (!out) return fail(-1, "forward_many: null pointer, m < 1 or theta_stride < P");
-    const size_t d_out = (size_t)h->nd.d_out;
-    return ensemble_forward(h, "forward_many", thetas, m, theta_stride, which, X, n, ENS_CHUNK_FLOATS, [](long, int) { return 0; },
-                            [&](int i0, int c, const float* dOut, long rows) -> int {
-                                const size_t per_net = (size_t)rows * d_out;
-                                HIPCHK(hipMemcpyAsync(out + (size_t)i0 * per_net, dOut, (size_t)c * per_net * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-                                return 0;
-                            });
-}
-
-// importance weights of the networks: the rules of tbnn_set_row_weights.  W = their sum (fp64, network order); null: equal, W = m
-static int ens_check_weights(const std::string& who, const float* net_w, int32_t m, double* W) {
-    double s = 0.0;
-    for (int32_t i = 0; i < m; ++i) {
-        if (!net_w) { s += 1.0; continue; }
-        if (!std::isfinite(net_w[i])) return fail(-1, who + ": weight " + std::to_string(i) + " is not finite");
-        if (net_w[i] < 0.f) return fail(-1, who + ": weight " + std::to_string(i) + " is negative");
-        s += (double)net_w[i];
-    }
-    if (!(s > 0.0)) return fail(-1, who + ": all weights are zero");
-    *W = s;
-    return 0;
-}
-
-static int ens_grid(long items) { return (int)std::max<long>(1, std::min<long>((items + ENS_TB - 1) / ENS_TB, 4096)); }
-
-extern "C" int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
-                                     float scale, float shift, int which, const float* X, int64_t n, double* mean_out, double* var_out) {
-    NEED(h);
-    const std::string who = "ensemble_moments";
-    const int d_out = h->nd.d_out;
-    if (!mean_out) return fail(-1, who + ": null mean_out");
-    if (xform < TBNN_XFORM_NONE || xform > TBNN_XFORM_SOFTMAX) return fail(-1, who + ": unknown transform");
-    if (xform == TBNN_XFORM_SOFTMAX && d_out < 2) return fail(-1, who + ": a softmax needs at least 2 outputs (one logit per class)");
-    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    double W = 0.0;
-    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
-    Buf<double> acc;
-    Buf<float> dW;
-    long tot = 0;
-    int rc = ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, ens_chunk_floats(),
-        [&](long rows, int) -> int {
-            tot = rows * d_out;
-            HIPCHK(acc.alloc(3 * (size_t)tot));
-            if (net_w) {
-                HIPCHK(dW.alloc((size_t)m));
-                HIPCHK(hipMemcpyAsync(dW, net_w, (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            }
-            return 0;
-        },
-        [&](int i0, int c, const float* dOut, long rows) -> int {
-            const float* w = net_w ? dW + i0 : nullptr;
-            if (xform == TBNN_XFORM_SOFTMAX)
-                hipLaunchKernelGGL(k_ens_moments_softmax, dim3(ens_grid(rows)), dim3(ENS_TB), 0, h->stream, dOut, c, rows, d_out, scale, shift, w,
-                                   (int)(i0 == 0), (double*)acc);
-            else
-                hipLaunchKernelGGL(k_ens_moments, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, dOut, c, tot, xform, scale, shift, w, (int)(i0 == 0),
-                                   (double*)acc);
-            HIPCHK(hipGetLastError());
-            return 0;
-        });
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_ens_moments_finish, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, tot, W);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(mean_out, acc, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (var_out) HIPCHK(hipMemcpyAsync(var_out, acc + tot, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// Quantiles and chain diagnostics need all m networks of an element at once, so this driver cuts the ROWS where ensemble_forward cuts the
-// networks: blocks of rb rows, every block's m forward passes into dOut[m][d_out][rb], then the transform (kernels_ensemble.hpp) and
-// each(r0, r, rows, t): the consumer's kernels over t[m][d_out r] and its copies into the strided host result, on h->stream, which is
-// synchronised after every block.  rb: what keeps a block's predictions, m d_out rb floats, within ens_chunk_floats(), rounded down to a
-// multiple of 64 and never below 64 -- a block then starts as aligned within dX as dX itself is for the forward kernels' vector loads; the
-// debug override may therefore be exceeded by up to 64 rows' worth.  The consumer's per-block results are outside that budget: never more
-// than the caller's own output.  extra_row_bytes: what a consumer keeps per row BESIDE the predictions in proportion to m (tbnn_ensemble_loo's
-// matrix and tail), counted into the budget in floats; 0 for the others.  begin(rb) runs once before the first block (the consumer's
-// buffers and staged arguments).  Thetas are staged once; be->forward builds a block's weight images into the one scratch allocated here.
-template <class Begin, class Each>
-static int ensemble_row_blocks(tbnn_ctx* h, const std::string& who, const float* thetas, int32_t m, int64_t theta_stride, int xform, float scale,
-                               float shift, int which, const float* X, int64_t n, Begin&& begin, Each&& each, size_t extra_row_bytes = 0) {
-    const NetDev& nd = h->nd;
-    const int d_out = nd.d_out;
-    const size_t per_row = (size_t)m * (size_t)d_out + (extra_row_bytes + sizeof(float) - 1) / sizeof(float);
-    if (per_row * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
-    const float* dX = nullptr;
-    Buf<float> dXown;
-    long rows = 0;
-    if (const int rc = ensemble_rows(h, who, thetas, m, theta_stride, which, X, n, dXown, &dX, &rows)) return rc;
-    const long rb = std::min<long>(rows, std::max<long>(64, (long)(ens_chunk_floats() / per_row) / 64 * 64));
-    Buf<float> dTh, dOut, dImg;
-    HIPCHK(dTh.alloc((size_t)m * nd.P));
-    HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas, (size_t)theta_stride * sizeof(float), (size_t)nd.P * sizeof(float), (size_t)m,
-                            hipMemcpyHostToDevice, h->stream));
-    HIPCHK(dOut.alloc((size_t)m * d_out * rb));
-    int rc = begin(rb);
-    if (rc) { hipStreamSynchronize(h->stream); return rc; }
-    const bool batched = h->be->forward_batched();
-    if (batched) {
-        HIPCHK(dImg.alloc((size_t)m * h->img_floats));
-        HIPCHK(hipMemsetAsync(dImg, 0, (size_t)m * h->img_floats * sizeof(float), h->stream));
-    }
-    for (long r0 = 0; r0 < rows && !rc; r0 += rb) {
-        const long r = std::min(rb, rows - r0), tot = r * d_out;
-        rc = h->be->forward(h->stream, m, dTh, dX + (size_t)r0 * nd.d_in, r, dOut, h->imgmap, batched ? (float*)dImg : (float*)h->qimg_cur);
-        if (rc) break;
-        HIPCHK(hipGetLastError());
-        if (xform == TBNN_XFORM_SOFTMAX)
-            hipLaunchKernelGGL(k_ens_transform_softmax, dim3(ens_grid((long)m * r)), dim3(ENS_TB), 0, h->stream, (float*)dOut, m, r, d_out, scale, shift);
-        else if (xform != TBNN_XFORM_NONE || scale != 1.f || shift != 0.f)
-            hipLaunchKernelGGL(k_ens_transform, dim3(ens_grid((long)m * tot)), dim3(ENS_TB), 0, h->stream, (float*)dOut, (long)m * tot, xform, scale, shift);
-        rc = each(r0, r, rows, (const float*)dOut);
-        if (!rc) HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    hipStreamSynchronize(h->stream);
-    return rc;
-}
-
-extern "C" int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int method,
-                                       int xform, float scale, float shift, int which, const float* X, int64_t n, const double* probs,
-                                       int32_t n_probs, double* out) {
-    NEED(h);
-    const std::string who = "ensemble_quantiles";
-    const int d_out = h->nd.d_out;
-    if (!probs || !out) return fail(-1, who + ": null probs or out");
-    if (n_probs < 1 || n_probs > 64) return fail(-1, who + ": n_probs must be 1 .. 64");
-    for (int32_t j = 0; j < n_probs; ++j)
-        if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return fail(-1, who + ": probability " + std::to_string(j) + " is not in [0, 1]");
-    if (method != TBNN_QUANT_LINEAR && method != TBNN_QUANT_INVERTED_CDF) return fail(-1, who + ": unknown method");
-    if (xform < TBNN_XFORM_NONE || xform > TBNN_XFORM_SOFTMAX) return fail(-1, who + ": unknown transform");
-    if (xform == TBNN_XFORM_SOFTMAX && d_out < 2) return fail(-1, who + ": a softmax needs at least 2 outputs (one logit per class)");
-    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    if (method == TBNN_QUANT_LINEAR && net_w) return fail(-1, who + ": TBNN_QUANT_LINEAR takes no weights (TBNN_QUANT_INVERTED_CDF does)");
-    double W = 0.0;
-    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
-    Buf<float> dW;
-    Buf<double> dP, dQ;
-    // [2][n_probs]: p, and LINEAR's h = (m - 1) p as one rounded fp64 product (k_ens_quantiles)
-    std::vector<double> ph(2 * (size_t)n_probs);
-    for (int32_t j = 0; j < n_probs; ++j) { ph[j] = probs[j]; ph[n_probs + j] = (double)(m - 1) * probs[j]; }
-    return ensemble_row_blocks(h, who, thetas, m, theta_stride, xform, scale, shift, which, X, n,
-        [&](long rb) -> int {
-            HIPCHK(dQ.alloc((size_t)n_probs * d_out * rb));
-            HIPCHK(dP.alloc(ph.size()));
-            HIPCHK(hipMemcpyAsync(dP, ph.data(), ph.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            if (net_w) {
-                HIPCHK(dW.alloc((size_t)m));
-                HIPCHK(hipMemcpyAsync(dW, net_w, (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            }
-            return 0;
-        },
-        [&](long r0, long r, long rows, const float* t) -> int {
-            const long tot = r * d_out;
-            const dim3 grid(ens_grid(tot)), tb(ENS_TB);
-            const float* w = net_w ? (const float*)dW : nullptr;
-            const double* p = dP;
-            double* q = dQ;
-            // up to half of ENS_QP probabilities (an interval's three): the kernel that carries half the slots
-            if (net_w && n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-            else if (net_w) hipLaunchKernelGGL((k_ens_quantiles<true, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-            else if (n_probs <= ENS_QP / 2) hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP / 2>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-            else hipLaunchKernelGGL((k_ens_quantiles<false, ENS_QP>), grid, tb, 0, h->stream, t, m, tot, w, method, p, n_probs, W, q);
-            HIPCHK(hipGetLastError());
-            // res[n_probs d_out][r] -> out[n_probs d_out][rows] at column r0
-            HIPCHK(hipMemcpy2DAsync(out + r0, (size_t)rows * sizeof(double), dQ, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                    (size_t)n_probs * d_out, hipMemcpyDeviceToHost, h->stream));
-            return 0;
-        });
-}
-
-// the checks of the chain structure both diagnostics entry points share: S = m / n_chains draws per chain
-static int diag_check(const std::string& who, int32_t m, int32_t n_chains, const double* rhat_out, const double* ess_out) {
-    if (!rhat_out && !ess_out) return fail(-1, who + ": rhat_out and ess_out are both null");
-    if (n_chains < 1 || n_chains > ENS_MAX_CHAINS) return fail(-1, who + ": n_chains must be 1 .. " + std::to_string(ENS_MAX_CHAINS));
-    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    if (m % n_chains) return fail(-1, who + ": m is not divisible by n_chains");
-    if (m / n_chains < 8) return fail(-1, who + ": fewer than 8 draws per chain");
-    return 0;
-}
-
-// k_ens_diagnostics over one block t[m][tot]; dR / dE: [tot] each, null where the result is not wanted
-static int diag_launch(tbnn_ctx* h, const float* t, int32_t m, int32_t n_chains, long tot, double* dMu, double* dR, double* dE) {
-    hipLaunchKernelGGL(k_ens_diagnostics, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, t, (int)n_chains, (int)(m / n_chains), tot, dMu, dR, dE);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int tbnn_ensemble_diagnostics(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int32_t n_chains, int xform,
-                                         float scale, float shift, int which, const float* X, int64_t n, double* rhat_out, double* ess_out) {
-    NEED(h);
-    const std::string who = "ensemble_diagnostics";
-    const int d_out = h->nd.d_out;
-    if (const int rc = diag_check(who, m, n_chains, rhat_out, ess_out)) return rc;
-    if (xform < TBNN_XFORM_NONE || xform > TBNN_XFORM_SOFTMAX) return fail(-1, who + ": unknown transform");
-    if (xform == TBNN_XFORM_SOFTMAX && d_out < 2) return fail(-1, who + ": a softmax needs at least 2 outputs (one logit per class)");
-    Buf<double> dMu, dRE;
-    long rbk = 0;
-    return ensemble_row_blocks(h, who, thetas, m, theta_stride, xform, scale, shift, which, X, n,
-        [&](long rb) -> int {
-            rbk = rb * d_out;
-            HIPCHK(dMu.alloc(2 * (size_t)n_chains * rbk));
-            HIPCHK(dRE.alloc(2 * (size_t)rbk));
-            return 0;
-        },
-        [&](long r0, long r, long rows, const float* t) -> int {
-            if (const int rc = diag_launch(h, t, m, n_chains, r * d_out, dMu, rhat_out ? (double*)dRE : nullptr, ess_out ? dRE + rbk : nullptr)) return rc;
-            // res[d_out][r] -> out[d_out][rows] at column r0
-            if (rhat_out) HIPCHK(hipMemcpy2DAsync(rhat_out + r0, (size_t)rows * sizeof(double), dRE, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                                  (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
-            if (ess_out) HIPCHK(hipMemcpy2DAsync(ess_out + r0, (size_t)rows * sizeof(double), dRE + rbk, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                                 (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
-            return 0;
-        });
-}
-
-// The same kernel over a caller's series: no forward pass, nothing staged on the handle is read.  The columns are cut into blocks of cb
-// (the rule of ensemble_row_blocks: m cb floats within ens_chunk_floats(), a multiple of 64, never below 64), each uploaded as [m][cb].
-extern "C" int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64_t tot, int32_t n_chains, double* rhat_out,
-                                       double* ess_out) {
-    NEED(h);
-    const std::string who = "series_diagnostics";
-    if (const int rc = diag_check(who, m, n_chains, rhat_out, ess_out)) return rc;
-    if (!series || tot < 1) return fail(-1, who + ": null series or tot < 1");
-    if ((size_t)m * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 columns of all m draws exceed the block budget of 2^28 floats");
-    HIPCHK(hipSetDevice(h->device));
-    const long cb = std::min<long>((long)tot, std::max<long>(64, (long)(ens_chunk_floats() / (size_t)m) / 64 * 64));
-    Buf<float> dT;
-    Buf<double> dMu, dRE;
-    HIPCHK(dT.alloc((size_t)m * cb));
-    HIPCHK(dMu.alloc(2 * (size_t)n_chains * cb));
-    HIPCHK(dRE.alloc(2 * (size_t)cb));
-    for (long c0 = 0; c0 < (long)tot; c0 += cb) {
-        const long c = std::min(cb, (long)tot - c0);
-        HIPCHK(hipMemcpy2DAsync(dT, (size_t)c * sizeof(float), series + c0, (size_t)tot * sizeof(float), (size_t)c * sizeof(float), (size_t)m,
-                                hipMemcpyHostToDevice, h->stream));
-        if (const int rc = diag_launch(h, dT, m, n_chains, c, dMu, rhat_out ? (double*)dRE : nullptr, ess_out ? dRE + cb : nullptr)) return rc;
-        if (rhat_out) HIPCHK(hipMemcpyAsync(rhat_out + c0, dRE, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (ess_out) HIPCHK(hipMemcpyAsync(ess_out + c0, dRE + cb, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return 0;
-}
-
-extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
-                                    const float* net_w, int which, const float* X, const float* Y, int64_t n, double* per_net,
-                                    double* lppd_rows) {
-    NEED(h);
-    const std::string who = "ensemble_loglik";
-    const int d_out = h->nd.d_out;
-    if (!per_net && !lppd_rows) return fail(-1, who + ": per_net and lppd_rows are both null");
-    if (!lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
-    if (likelihood == TBNN_LIK_CATEGORICAL && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
-    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
-    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    double W = 0.0;
-    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
-    const bool gauss = likelihood == TBNN_LIK_GAUSSIAN || likelihood == TBNN_LIK_FIXED_GAUSSIAN;
-    // per network: sigma clipped to [1e-8, 1e8] (layer.py:62), -log sigma - 1/2 log 2 pi, log w
-    std::vector<float> sig;
-    std::vector<double> cst, lw;
-    if (gauss) {
-        sig.resize((size_t)m); cst.resize((size_t)m);
-        for (int32_t i = 0; i < m; ++i) {
-            const float s = sd ? sd[i] : h->nd.fixed_sd;
-            if (std::isnan(s)) return fail(-1, who + ": sd " + std::to_string(i) + " is not a number");
-            sig[i] = std::min(std::max(s, 1e-8f), 1e8f);
-            cst[i] = -std::log((double)sig[i]) - 0.5 * std::log(2.0 * M_PI);
-        }
-    }
-    if (net_w && lppd_rows) {
-        lw.resize((size_t)m);
-        for (int32_t i = 0; i < m; ++i) lw[i] = std::log((double)net_w[i]);          // (log 0 = -inf: the network drops out of the mixture)
-    }
-    Buf<float> dSig, dY;
-    Buf<double> dCst, dLw, lse, part;
-    std::vector<double> hpart;
-    const float* dYrows = nullptr;
-    int nblk = 0;
-    long nrows = 0;
-    int rc = ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, ens_chunk_floats(),
-        [&](long rows, int chunk) -> int {
-            nrows = rows;
-            if (Y) {
-                if (n != rows) return fail(-1, who + ": n = " + std::to_string((long long)n) + " does not match the " + std::to_string(rows) + " staged rows");
-                HIPCHK(dY.alloc((size_t)rows * d_out));
-                HIPCHK(hipMemcpyAsync(dY, Y, (size_t)rows * d_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                dYrows = dY;
-            } else {
-                dYrows = which ? h->dYv : h->dY;
-                if (!dYrows) return fail(-1, who + ": no staged targets");
-            }
-            nblk = (int)((rows + ENS_TB - 1) / ENS_TB);
-            if (gauss) {
-                HIPCHK(dSig.alloc((size_t)m)); HIPCHK(dCst.alloc((size_t)m));
-                HIPCHK(hipMemcpyAsync(dSig, sig.data(), (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                HIPCHK(hipMemcpyAsync(dCst, cst.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            }
-            if (!lw.empty()) {
-                HIPCHK(dLw.alloc((size_t)m));
-                HIPCHK(hipMemcpyAsync(dLw, lw.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            }
-            if (lppd_rows) HIPCHK(lse.alloc(2 * (size_t)rows));
-            if (per_net) {
-                HIPCHK(part.alloc((size_t)nblk * chunk));
-                hpart.resize((size_t)nblk * chunk);
-                for (int32_t i = 0; i < m; ++i) per_net[i] = 0.0;
-            }
-            return 0;
-        },
-        [&](int i0, int c, const float* dOut, long rows) -> int {
-            hipLaunchKernelGGL(k_ens_loglik, dim3(nblk), dim3(ENS_TB), 0, h->stream, dOut, c, rows, d_out, likelihood, dYrows,
-                               gauss ? (const float*)(dSig + i0) : nullptr, gauss ? (const double*)(dCst + i0) : nullptr,
-                               lw.empty() ? nullptr : (const double*)(dLw + i0), (int)(i0 == 0), (double*)lse, (double*)part);
-            HIPCHK(hipGetLastError());
-            if (per_net) {
-                // the workgroups' partial sums of this chunk, added in index order: the same bits from run to run
-                HIPCHK(hipMemcpyAsync(hpart.data(), part, (size_t)nblk * c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                for (int b = 0; b < nblk; ++b) for (int i = 0; i < c; ++i) per_net[i0 + i] += hpart[(size_t)b * c + i];
-            }
-            return 0;
-        });
-    if (rc) return rc;
-    if (lppd_rows) {
-        hipLaunchKernelGGL(k_ens_lppd_finish, dim3(ens_grid(nrows)), dim3(ENS_TB), 0, h->stream, (double*)lse, nrows, std::log(W));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(lppd_rows, lse, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return 0;
-}
-
-// Phi^-1(p), 0 < p < 1: Wichura's algorithm AS 241 (Applied Statistics 37 (1988) 477-484), routine PPND16, about 1e-16 relative
-static double ens_norm_ppf(double p) {
-    const double q = p - 0.5;
-    if (std::fabs(q) <= 0.425) {
-        const double r = 0.180625 - q * q;
-        return q * (((((((2.5090809287301226727e3 * r + 3.3430575583588128105e4) * r + 6.7265770927008700853e4) * r + 4.5921953931549871457e4) * r +
-                        1.3731693765509461125e4) * r + 1.9715909503065514427e3) * r + 1.3314166789178437745e2) * r + 3.3871328727963666080e0) /
-               (((((((5.2264952788528545610e3 * r + 2.8729085735721942674e4) * r + 3.9307895800092710610e4) * r + 2.1213794301586595867e4) * r +
-                    5.3941960214247511077e3) * r + 6.8718700749205790830e2) * r + 4.2313330701600911252e1) * r + 1.0);
-    }
-    double r = std::sqrt(-std::log(q < 0.0 ? p : 1.0 - p)), v;
-    if (r <= 5.0) {
-        r -= 1.6;
-        v = (((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r + 1.27045825245236838258e0) * r +
-                3.64784832476320460504e0) * r + 5.76949722146069140550e0) * r + 4.63033784615654529590e0) * r + 1.42343711074968357734e0) /
-            (((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r + 1.48103976427480074590e-1) * r +
-                6.89767334985100004550e-1) * r + 1.67638483018380384940e0) * r + 2.05319162663775882187e0) * r + 1.0);
-    } else {
-        r -= 5.0;
-        v = (((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r + 2.65321895265761230930e-2) * r +
-                2.96560571828504891230e-1) * r + 1.78482653991729133580e0) * r + 5.46378491116411436990e0) * r + 6.65790464350110377720e0) /
-            (((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-7) * r + 1.84631831751005468180e-5) * r + 7.86869131145613259100e-4) * r +
-                1.48753612908506148525e-2) * r + 1.36929880922735805310e-1) * r + 5.99832206555887937690e-1) * r + 1.0);
-    }
-    return q < 0.0 ? -v : v;
-}
-
-// what tbnn_ensemble_predictive refuses before it touches a device, and the per-network constants it stages: cst[3][m] = w_i / W,
-// 1 / (s_i sqrt 2), s_i (the last two: Gaussian kinds); pz[2][n_probs] = p, Phi^-1(p); *smax = the largest s_i among the networks that count
-static int pred_check(const std::string& who, int likelihood, float fixed_sd, int d_out, const float* sd, const float* net_w, int32_t m, const float* X,
-                      const float* Y, const double* probs, int32_t n_probs, const double* q_out, const double* cdf_out, const double* cdf_below_out,
-                      std::vector<double>& cst, std::vector<double>& pz, double* smax) {
-    if (!q_out && !cdf_out) return fail(-1, who + ": q_out and cdf_out are both null");
-    if (q_out && !probs) return fail(-1, who + ": null probs with q_out");
-    if (cdf_below_out && !cdf_out) return fail(-1, who + ": cdf_below_out without cdf_out");
-    if (cdf_out && X && !Y) return fail(-1, who + ": rows X without their targets Y");
-    if (q_out) {
-        if (n_probs < 1 || n_probs > 64) return fail(-1, who + ": n_probs must be 1 .. 64");
-        for (int32_t j = 0; j < n_probs; ++j)
-            if (!(probs[j] > 0.0 && probs[j] < 1.0)) return fail(-1, who + ": probability " + std::to_string(j) + " is not in (0, 1)");
-    }
-    if (likelihood == TBNN_LIK_BERNOULLI || likelihood == TBNN_LIK_CATEGORICAL)
-        return fail(-1, who + ": the predictive distribution of a label is its posterior-mean probability: tbnn_ensemble_moments returns it");
-    const bool gauss = likelihood == TBNN_LIK_GAUSSIAN || likelihood == TBNN_LIK_FIXED_GAUSSIAN;
-    if (!gauss && likelihood != TBNN_LIK_POISSON) return fail(-1, who + ": unknown likelihood");
-    if (cdf_below_out && gauss) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
-    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
-    // the budget of ensemble_row_blocks, judged here before m values of sd and net_w are read and 3 m doubles staged
-    if ((size_t)m * (size_t)d_out * 64 > ENS_CHUNK_FLOATS) return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
-    if (!q_out) n_probs = 0;                                                          // (not read, whatever the caller left there)
-    double W = 0.0;
-    if (const int rc = ens_check_weights(who, net_w, m, &W)) return rc;
-    cst.assign(3 * (size_t)m, 0.0);
-    *smax = 0.0;
-    for (int32_t i = 0; i < m; ++i) {
-        cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
-        if (!gauss) continue;
-        const float s = sd ? sd[i] : fixed_sd;
-        if (std::isnan(s)) return fail(-1, who + ": sd " + std::to_string(i) + " is not a number");
-        const double sc = (double)std::min(std::max(s, 1e-8f), 1e8f);                  // the clip of tbnn_ensemble_loglik (layer.py:62)
-        cst[(size_t)m + i] = 1.0 / (sc * std::sqrt(2.0));
-        cst[2 * (size_t)m + i] = sc;
-        if (cst[i] > 0.0) *smax = std::max(*smax, sc);
-    }
-    pz.assign(2 * (size_t)std::max(n_probs, 1), 0.0);
-    for (int32_t j = 0; j < n_probs; ++j) { pz[j] = probs[j]; pz[(size_t)n_probs + j] = ens_norm_ppf(probs[j]); }
-    return 0;
-}
-
-extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
-                                        const float* net_w, int which, const float* X, const float* Y, int64_t n, const double* probs,
-                                        int32_t n_probs, double* q_out, double* cdf_out, double* cdf_below_out) {
-    NEED(h);
-    const std::string who = "ensemble_predictive";
-    const int d_out = h->nd.d_out;
-    std::vector<double> cst, pz;
-    double smax = 0.0;
-    if (const int rc = pred_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, probs, n_probs, q_out, cdf_out, cdf_below_out, cst, pz, &smax)) return rc;
-    if (!q_out) n_probs = 0;
-    const bool pois = likelihood == TBNN_LIK_POISSON;
-    const float* dYrows = nullptr;
-    if (cdf_out && Y && !X && (which == 0 || which == 1)) {
-        const long staged = which ? h->nv : h->n;
-        if (staged >= 1 && n != staged) return fail(-1, who + ": n = " + std::to_string((long long)n) + " does not match the " + std::to_string(staged) + " staged rows");
-    }
-    if (cdf_out && !Y) {
-        dYrows = which == 0 ? h->dY : which == 1 ? h->dYv : nullptr;
-        if ((which == 0 || which == 1) && (which ? h->nv : h->n) >= 1 && !dYrows) return fail(-1, who + ": no staged targets");
-    }
-    Buf<float> dY;
-    Buf<double> dCst, dP, dRes;
-    long rbk = 0;
-    return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
-        [&](long rb) -> int {
-            rbk = rb * d_out;
-            // a block's results: n_probs quantile planes, then the CDF and the CDF below
-            HIPCHK(dRes.alloc(((size_t)n_probs + 2) * rbk));
-            HIPCHK(dCst.alloc(cst.size()));
-            HIPCHK(hipMemcpyAsync(dCst, cst.data(), cst.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(dP.alloc(pz.size()));
-            HIPCHK(hipMemcpyAsync(dP, pz.data(), pz.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            if (cdf_out && Y) {
-                HIPCHK(dY.alloc((size_t)n * d_out));
-                HIPCHK(hipMemcpyAsync(dY, Y, (size_t)n * d_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                dYrows = dY;
-            }
-            return 0;
-        },
-        [&](long r0, long r, long rows, const float* t) -> int {
-            const long tot = r * d_out;
-            const dim3 grid(ens_grid(tot)), tb(ENS_TB);
-            const double* c = dCst;
-            const double* p = dP;
-            double* q = dRes;
-            double* F = dRes + (size_t)n_probs * rbk;
-            double* Fb = cdf_below_out ? F + rbk : nullptr;
-            if (q_out) {
-                if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q);
-                else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q);
-                HIPCHK(hipGetLastError());
-                // res[n_probs d_out][r] -> q_out[n_probs d_out][rows] at column r0
-                HIPCHK(hipMemcpy2DAsync(q_out + r0, (size_t)rows * sizeof(double), q, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                        (size_t)n_probs * d_out, hipMemcpyDeviceToHost, h->stream));
-            }
-            if (cdf_out) {
-                const float* y = dYrows + (size_t)r0 * d_out;
-                if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb);
-                else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy2DAsync(cdf_out + r0, (size_t)rows * sizeof(double), F, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                        (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
-                if (Fb) HIPCHK(hipMemcpy2DAsync(cdf_below_out + r0, (size_t)rows * sizeof(double), Fb, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                                (size_t)d_out, hipMemcpyDeviceToHost, h->stream));
-            }
-            return 0;
-        });
-}
-
-// M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)
-static void psis_sizes(int32_t m, double r_eff, int* M, int* G, int* q) {
-    *M = (int)std::ceil(std::min(0.2 * (double)m, 3.0 * std::sqrt((double)m / r_eff)));
-    *G = 30 + (int)std::floor(std::sqrt((double)*M));
-    *q = (int)std::floor((double)*M / 4.0 + 0.5);
-}
-// what tbnn_ensemble_loo keeps per row beside the predictions: the matrix column (m doubles) and the tail's two planes (2 M doubles)
-static size_t psis_row_bytes(int32_t m, int M) { return sizeof(double) * ((size_t)m + 2 * (size_t)M); }
-
-extern "C" int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
-                                 int which, const float* X, const float* Y, int64_t n, double r_eff, double* elpd_loo_rows,
-                                 double* pareto_k_rows, double* lppd_rows, double* p_waic_rows, double* pointwise) {
-    NEED(h);
-    const std::string who = "ensemble_loo";
-    const int d_out = h->nd.d_out;
-    if (!elpd_loo_rows && !pareto_k_rows && !lppd_rows && !p_waic_rows && !pointwise) return fail(-1, who + ": every output is null");
-    if (!(r_eff > 0.0) || !std::isfinite(r_eff)) return fail(-1, who + ": r_eff must be finite and > 0");
-    if (!lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
-    if (likelihood == TBNN_LIK_CATEGORICAL && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
-    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
-    if (m < 2) return fail(-1, who + ": fewer than 2 networks");
-    int M = 0, G = 0, q = 0;
-    psis_sizes(m, r_eff, &M, &G, &q);
-    const size_t extra = psis_row_bytes(m, M);
-    if (((size_t)m * (size_t)d_out + extra / sizeof(float)) * 64 > ENS_CHUNK_FLOATS)
-        return fail(-1, who + ": 64 rows of all m networks exceed the block budget of 2^28 floats");
-    const float* dYrows = nullptr;
-    if (Y && !X && (which == 0 || which == 1)) {
-        const long staged = which ? h->nv : h->n;
-        if (staged >= 1 && n != staged) return fail(-1, who + ": n = " + std::to_string((long long)n) + " does not match the " + std::to_string(staged) + " staged rows");
-    }
-    if (!Y) {
-        dYrows = which == 0 ? h->dY : which == 1 ? h->dYv : nullptr;
-        if ((which == 0 || which == 1) && (which ? h->nv : h->n) >= 1 && !dYrows) return fail(-1, who + ": no staged targets");
-    }
-    const bool gauss = likelihood == TBNN_LIK_GAUSSIAN || likelihood == TBNN_LIK_FIXED_GAUSSIAN;
-    // per network: sigma and -log sigma - 1/2 log 2 pi, as tbnn_ensemble_loglik stages them
-    std::vector<float> sig;
-    std::vector<double> cst;
-    if (gauss) {
-        sig.resize((size_t)m); cst.resize((size_t)m);
-        for (int32_t i = 0; i < m; ++i) {
-            const float s = sd ? sd[i] : h->nd.fixed_sd;
-            if (std::isnan(s)) return fail(-1, who + ": sd " + std::to_string(i) + " is not a number");
-            sig[i] = std::min(std::max(s, 1e-8f), 1e8f);
-            cst[i] = -std::log((double)sig[i]) - 0.5 * std::log(2.0 * M_PI);
-        }
-    }
-    const bool psis = elpd_loo_rows || pareto_k_rows;
-    const double logm = std::log((double)m);
-    Buf<float> dSig, dY;
-    Buf<double> dCst, dL, dTail, dRes;
-    long rbk = 0;
-    return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
-        [&](long rb) -> int {
-            rbk = rb;
-            HIPCHK(dL.alloc((size_t)m * rb));
-            if (psis) HIPCHK(dTail.alloc(2 * (size_t)M * rb));
-            // a block's row results: elpd_loo, pareto_k, lppd, p_waic
-            HIPCHK(dRes.alloc(4 * (size_t)rb));
-            if (gauss) {
-                HIPCHK(dSig.alloc((size_t)m)); HIPCHK(dCst.alloc((size_t)m));
-                HIPCHK(hipMemcpyAsync(dSig, sig.data(), (size_t)m * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                HIPCHK(hipMemcpyAsync(dCst, cst.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            }
-            if (Y) {
-                HIPCHK(dY.alloc((size_t)n * d_out));
-                HIPCHK(hipMemcpyAsync(dY, Y, (size_t)n * d_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                dYrows = dY;
-            }
-            return 0;
-        },
-        [&](long r0, long r, long rows, const float* t) -> int {
-            const dim3 grid(ens_grid(r)), tb(ENS_TB);
-            double* res = dRes;
-            hipLaunchKernelGGL(k_ens_pointwise, grid, tb, 0, h->stream, t, (int)m, r, d_out, likelihood, dYrows + (size_t)r0 * d_out,
-                               gauss ? (const float*)dSig : nullptr, gauss ? (const double*)dCst : nullptr, logm, (double*)dL,
-                               lppd_rows ? res + 2 * rbk : nullptr, p_waic_rows ? res + 3 * rbk : nullptr);
-            HIPCHK(hipGetLastError());
-            if (psis) {
-                hipLaunchKernelGGL(k_ens_psis, grid, tb, 0, h->stream, (const double*)dL, (int)m, r, M, G, q, (double*)dTail, dTail + (size_t)M * rbk,
-                                   elpd_loo_rows ? res : nullptr, pareto_k_rows ? res + rbk : nullptr);
-                HIPCHK(hipGetLastError());
-            }
-            double* const outs[4] = {elpd_loo_rows, pareto_k_rows, lppd_rows, p_waic_rows};
-            for (int k = 0; k < 4; ++k)
-                if (outs[k]) HIPCHK(hipMemcpyAsync(outs[k] + r0, res + (size_t)k * rbk, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            // l[m][r] -> pointwise[m][rows] at column r0
-            if (pointwise) HIPCHK(hipMemcpy2DAsync(pointwise + r0, (size_t)rows * sizeof(double), dL, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
-                                                    (size_t)m, hipMemcpyDeviceToHost, h->stream));
-            return 0;
-        }, extra);
-}
+#include "ensemble_api.hpp"               // tbnn_forward_many and the ensemble reductions (it uses tbnn_ctx, lik_known, Buf, fail, HIPCHK and NEED above)
 
 extern "C" int tbnn_metrics(tbnn_handle h, int which, const float* theta, float mean, float sd, int exp_pred, int exp_real,
                             double out3[3]) {

@@ -163,6 +163,26 @@ class predictor(object):
     # ---- reductions over the saved networks on the device (tbnn_ensemble_moments / tbnn_ensemble_quantiles / tbnn_ensemble_loglik) ----
     _TRANSFORMS = {"none": nat.XFORM_NONE, "exp": nat.XFORM_EXP, "sigmoid": nat.XFORM_SIGMOID, "softmax": nat.XFORM_SOFTMAX}
 
+    def _transform(self, transform):
+        """the name of the transform asked for; None: the one the predictor's likelihood implies"""
+        from .likelihood import CategoricalLikelihood, PoissonLikelihood
+        if transform is None:
+            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
+                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
+        if transform not in self._TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
+        return transform
+
+    @staticmethod
+    def _central_probs(level):
+        """(1 - level) / 2, 1 / 2, (1 + level) / 2 -- in decimal, so that level = 0.9 asks for 0.05 and 0.95 themselves: (1 - 0.9) / 2 in
+        binary is the double below 0.05"""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        d = Decimal(repr(level))
+        return [float((1 - d) / 2), 0.5, float((1 + d) / 2)]
+
     def _picked(self, n, weights):
         picked = np.stack([self.vectors[m] for m in range(0, self.numNetworks, n)])
         w = None if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1)
@@ -178,14 +198,9 @@ class predictor(object):
         "sigmoid" / "softmax" / "none" override.  weights: one per picked network, e.g. what reweight returns.  countVariance (with the
         exp transform, sd = 1, mean = 0): the second array is the total predictive variance of a COUNT, E[rate] + Var[rate] (the Poisson
         noise plus the posterior spread of the rate), added on the host to the two arrays the device returns."""
-        from .likelihood import CategoricalLikelihood, PoissonLikelihood
-        if transform is None:
-            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
-                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
+        transform = self._transform(transform)
         if countVariance and (transform != "exp" or float(sd) != 1.0 or float(mean) != 0.0):
             raise ValueError("countVariance needs the rate itself: transform 'exp' (the default under a PoissonLikelihood), sd = 1, mean = 0")
-        if transform not in self._TRANSFORMS:
-            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
         picked, w = self._picked(n, weights)
         ch = self._ensure_chain()
         m, v = ch.ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=self._TRANSFORMS[transform],
@@ -199,12 +214,7 @@ class predictor(object):
         applied before the ranking.  method "linear" is np.quantile's default and takes no weights; "inverted_cdf" returns one of the
         networks' values and takes weights (np.quantile(method="inverted_cdf", weights=weights)), e.g. what reweight returns.  method None:
         "linear" without weights, "inverted_cdf" with them."""
-        from .likelihood import CategoricalLikelihood, PoissonLikelihood
-        if transform is None:
-            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
-                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
-        if transform not in self._TRANSFORMS:
-            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
+        transform = self._transform(transform)
         if method is None:
             method = "linear" if weights is None else "inverted_cdf"
         if method not in ("linear", "inverted_cdf"):
@@ -223,12 +233,7 @@ class predictor(object):
         of predictQuantiles, whose other arguments pass through.  This is the central CREDIBLE interval of the network's output -- the
         rate, the class probability, the regression mean -- under the posterior the saved networks sample; the predictive interval
         for a new observation, which adds the observation noise (sigma, the Poisson scatter), is predictiveInterval's."""
-        level = float(level)
-        if not 0.0 < level < 1.0:
-            raise ValueError("level must lie in (0, 1)")
-        # in decimal, so that level = 0.9 asks for 0.05 and 0.95 themselves: (1 - 0.9) / 2 in binary is the double below 0.05
-        d = Decimal(repr(level))
-        q = self.predictQuantiles(inputMatrix, [float((1 - d) / 2), 0.5, float((1 + d) / 2)], **kwargs)
+        q = self.predictQuantiles(inputMatrix, self._central_probs(level), **kwargs)
         return q[0], q[1], q[2]
 
     # ---- convergence diagnostics on the device (tbnn_ensemble_diagnostics / tbnn_series_diagnostics) ----
@@ -257,12 +262,7 @@ class predictor(object):
         rhat, ess float64 [d_out, rows] (NaN where an element is constant or holds a NaN), max_rhat and min_ess over the defined
         elements, undefined: the number of NaN elements.  transform None resolves as in predictMoments; n thins WITHIN each chain (every
         n-th draw of each), which needs at least 8 draws left per chain."""
-        from .likelihood import CategoricalLikelihood, PoissonLikelihood
-        if transform is None:
-            transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
-                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
-        if transform not in self._TRANSFORMS:
-            raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
+        transform = self._transform(transform)
         picked, C = self._chain_draws(n)
         ch = self._ensure_chain()
         rhat, ess = ch.ensemble_diagnostics(np.stack([self.vectors[i] for i in picked]), chains=C, X=np.asarray(inputMatrix, dtype=np.float32),
@@ -401,11 +401,7 @@ class predictor(object):
         """(lower, median, upper), each float64 [d_out, rows]: the predictive quantiles at (1 - level) / 2, 1 / 2 and (1 + level) / 2 from
         one call of predictiveQuantiles, whose other arguments pass through -- the central PREDICTIVE interval, which a new observation
         falls into with probability `level` (predictInterval's credible interval covers the network's output only)."""
-        level = float(level)
-        if not 0.0 < level < 1.0:
-            raise ValueError("level must lie in (0, 1)")
-        d = Decimal(repr(level))                       # in decimal, as predictInterval: level = 0.9 asks for 0.05 and 0.95 themselves
-        q = self.predictiveQuantiles(inputMatrix, [float((1 - d) / 2), 0.5, float((1 + d) / 2)], **kwargs)
+        q = self.predictiveQuantiles(inputMatrix, self._central_probs(level), **kwargs)
         return q[0], q[1], q[2]
 
     def predictiveCDF(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
