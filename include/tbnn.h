@@ -445,6 +445,44 @@ int tbnn_adapter_update(tbnn_adapter_handle a, const float* state, int32_t P, fl
                         int32_t inject_e, int32_t inject_l, float* eps_out, int32_t* L_out,
                         float* sjd_out);
 
+/* ---- pre-training on the device: BNN_functions.trainBasicRegression / trainBasicClassification (BNN_functions.py:60-180, :183-297;
+ * docs/ClassificationExample.md, Examples/extendedRegression.py start every chain from their result) are Keras Adam with amsgrad=True;
+ * here the same update rule ascends the chain's OWN target -- its activations, priors, likelihood, row weights -- with the fused
+ * forward+backward pass of whichever kernel family the handle runs.  Added without a new ABI version: the symbols are additions. ----
+ *
+ * tbnn_optimize runs n_steps >= 0 full-batch steps back to back on the chain's stream (no host round trip), from theta_0 = the
+ * chain's state.  With g_t the gradient at theta_t of the objective (TBNN_OPT_POSTERIOR: the target log-probability tbnn_logp_grad
+ * returns, priors included; TBNN_OPT_LIKELIHOOD: the data log-likelihood alone, row weights included) and t counting from 1 since the
+ * last reset, one step is torch.optim.Adam(lr, betas, eps, amsgrad, maximize=True)'s, in fp32:
+ *   m = beta1 m + (1 - beta1) g_t ;  v = beta2 v + (1 - beta2) g_t^2 ;  vhat = amsgrad ? max(vhat, v) : v
+ *   theta_{t+1} = theta_t + a_t m / (sqrt(vhat) r_t + epsilon),   a_t = lr / (1 - beta1^t),   r_t = 1 / sqrt(1 - beta2^t)
+ * (a_t, r_t and 1 - beta formed in fp64 from the fp32 arguments and rounded once).
+ * Checks: the objective is evaluated at theta_t for the call's steps t = 0, k, 2k, .. < n_steps (k = check_every) and once more at
+ * theta_{n_steps}: n_checks = ceil(n_steps / k) + 1 values per chain, in step order (n_steps = 0: one evaluation, no step).  The value is
+ * the true log-density (Poisson with its constant), summed in fp64.  A check whose value is finite and above every earlier one since the
+ * last reset records theta_t as the best weights; a check whose value is NOT finite freezes the chain: it makes no further update, in this
+ * call or a later one without reset (diverged = 1).  Between two checks nothing is judged.
+ * After the call the chain's state is the best weights when keep_best is set or the chain froze, else theta_{n_steps}; the cached
+ * (log-prob, gradient) of the state is dropped, so the next transition or tbnn_logp_grad evaluates afresh.  Hypers, the epoch counter
+ * and the random stream are untouched: the call draws nothing.
+ * reset != 0 zeroes m, v, vhat, t and the best record (best weights = the start state) first; reset == 0 continues them, so that a run
+ * cut into blocks with keep_best = 0 takes the same steps as one call (the first call on a handle always resets).
+ * Multi-chain handle: every chain is optimised from its own state in the same launches; out[chains], trace[chains][n_checks]; a frozen
+ * chain does not hold up the others.
+ * out (per chain): steps_done = n_steps, or for a chain that froze the step of the check that froze it (0: frozen before the call);
+ * diverged; best_step: the step counter t (since the last reset) of the best check; n_checks; obj_first / obj_last: the first and last
+ * check of this call; obj_best: the best since the last reset (-inf: none was finite); device_us: hipEvent time of the whole run.
+ * Errors (the handle is left as it was): no data staged; a row-sharded handle (tbnn_set_row_shard); NULL cfg or out; n_steps < 0;
+ * check_every < 1; lr or epsilon not finite or not > 0; a beta outside [0, 1); an unknown objective. */
+enum { TBNN_OPT_POSTERIOR = 0, TBNN_OPT_LIKELIHOOD = 1 };
+typedef struct tbnn_optim_cfg { float lr, beta1, beta2, epsilon; int32_t amsgrad, objective, check_every, keep_best; } tbnn_optim_cfg;
+typedef struct tbnn_optim_out { int32_t steps_done, diverged, best_step, n_checks; double obj_first, obj_last, obj_best; float device_us; } tbnn_optim_out;
+int tbnn_optimize(tbnn_handle h, const tbnn_optim_cfg* cfg, int32_t n_steps, int32_t reset, tbnn_optim_out* out /* [chains] */,
+                  double* trace /* [chains][n_checks] or NULL */);
+/* diagnostic: the optimiser's moments, the total gradient g of its last step ([chains][P] floats each) and its step counter t; any
+ * pointer may be NULL.  An error before the first tbnn_optimize. */
+int tbnn_optim_state(tbnn_handle h, float* m, float* v, float* vhat, float* g, int32_t* t);
+
 #ifdef __cplusplus
 }
 #endif

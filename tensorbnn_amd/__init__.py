@@ -6,3 +6,6 @@ surface, with the transition running in hand-written gfx950 HIP kernels behind
 the C ABI of ``include/tbnn.h`` (bound in ``_native.py``).  No CPU fallback.
 """
 __version__ = "0.1.0"
+
+# the reference's pre-training helpers (they load the native library on their first call, not here: `tensorbnn_amd.build` must import without it)
+from .BNN_functions import trainBasicClassification, trainBasicRegression  # noqa: E402,F401

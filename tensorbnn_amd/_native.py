@@ -21,6 +21,7 @@ ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
+OPT_POSTERIOR, OPT_LIKELIHOOD = 0, 1
 XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
 QUANT_LINEAR, QUANT_INVERTED_CDF = 0, 1
 MAX_LAYERS = 16
@@ -45,6 +46,19 @@ class StepOut(C.Structure):
                 ("accept_prob", C.c_float), ("logp_old", C.c_double), ("logp_new", C.c_double),
                 ("kinetic_old", C.c_double), ("kinetic_new", C.c_double), ("sjd", C.c_double),
                 ("device_us", C.c_float), ("fwdbwd_us", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OptimCfg(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("amsgrad", C.c_int32),
+                ("objective", C.c_int32), ("check_every", C.c_int32), ("keep_best", C.c_int32)]
+
+
+class OptimOut(C.Structure):
+    _fields_ = [("steps_done", C.c_int32), ("diverged", C.c_int32), ("best_step", C.c_int32), ("n_checks", C.c_int32),
+                ("obj_first", C.c_double), ("obj_last", C.c_double), ("obj_best", C.c_double), ("device_us", C.c_float)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -84,6 +98,8 @@ SYMBOLS = [
     ("tbnn_hyper_step_each", C.c_int, [_H, _fp, C.c_int32, C.POINTER(StepOut)]),
     ("tbnn_hyper_step", C.c_int, [_H, C.c_float, C.c_int32, _fp, _fp, C.POINTER(StepOut)]),
     ("tbnn_hyper_logp_grad", C.c_int, [_H, _fp, _dp, _fp]),
+    ("tbnn_optimize", C.c_int, [_H, C.POINTER(OptimCfg), C.c_int32, C.c_int32, C.POINTER(OptimOut), _dp]),
+    ("tbnn_optim_state", C.c_int, [_H, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
     ("tbnn_export_sample_device", C.c_int, [_H, C.c_void_p]),
     ("tbnn_debug_draw", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_int32, _fp, _fp]),
     ("tbnn_set_epoch", C.c_int, [_H, C.c_uint32]),
@@ -216,6 +232,37 @@ def lint_status() -> str:
 def device_count() -> int:
     rc = lib.tbnn_device_count()
     return max(rc, 0)
+
+
+_OBJECTIVES = {"posterior": OPT_POSTERIOR, "likelihood": OPT_LIKELIHOOD}
+
+
+def _optimize(chain, n_chains, steps, lr, beta1, beta2, epsilon, amsgrad, objective, check_every, keep, reset):
+    """Chain / ChainGroup.optimize: tbnn_optimize -> one dict per chain: the fields of tbnn_optim_out and the objective trace"""
+    if keep not in ("best", "last"):
+        raise ValueError('keep must be "best" or "last"')
+    obj = _OBJECTIVES.get(objective, objective)
+    if isinstance(obj, str):
+        raise ValueError(f"objective must be one of {sorted(_OBJECTIVES)}")
+    cfg = OptimCfg(float(lr), float(beta1), float(beta2), float(epsilon), int(bool(amsgrad)), int(obj), int(check_every), int(keep == "best"))
+    steps, every = int(steps), int(check_every)
+    n_checks = (max(steps, 0) + every - 1) // every + 1 if every >= 1 else 1
+    outs = (OptimOut * n_chains)()
+    tr = np.empty((n_chains, n_checks), dtype=np.float64)
+    _check(lib.tbnn_optimize(chain._h, C.byref(cfg), steps, int(bool(reset)), outs, _pd(tr)))
+    res = []
+    for c in range(n_chains):
+        d = outs[c].as_dict()
+        d["trace"] = tr[c].copy()
+        res.append(d)
+    return res
+
+
+def _optim_state(chain, shape):
+    m, v, vhat, g = (np.empty(shape, dtype=np.float32) for _ in range(4))
+    t = C.c_int32()
+    _check(lib.tbnn_optim_state(chain._h, _p(m), _p(v), _p(vhat), _p(g), C.byref(t)))
+    return {"m": m, "v": v, "vhat": vhat, "g": g, "t": int(t.value)}
 
 
 def _set_row_weights(chain, w):
@@ -377,6 +424,19 @@ class Chain:
         outs = (StepOut * n_epochs)()
         _check(lib.tbnn_hmc_run(self._h, float(eps), int(L), int(n_epochs), outs))
         return [o.as_dict() for o in outs]
+
+    def optimize(self, steps: int, lr: float = 1e-2, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, amsgrad: bool = True,
+                 objective: str = "posterior", check_every: int = 10, keep: str = "best", reset: bool = True):
+        """`steps` full-batch Adam / AMSGrad steps up the chain's own target from its state, all on the device (tbnn_optimize; the
+        definition is in include/tbnn.h).  objective "posterior" (log-likelihood + priors) or "likelihood"; the objective is checked every
+        `check_every` steps and once at the end; keep "best": the state becomes the best checked weights, "last": the last step's (a chain
+        whose objective stopped being finite goes back to its best either way: diverged = 1); reset=False continues the moments, the step
+        counter and the best record of the previous call.  -> the fields of tbnn_optim_out and "trace" (the checked objectives)"""
+        return _optimize(self, 1, steps, lr, beta1, beta2, epsilon, amsgrad, objective, check_every, keep, reset)[0]
+
+    def optim_state(self):
+        """diagnostic: the optimiser's moments m, v, vhat and the total gradient g of its last step ([P] each) and its step counter t"""
+        return _optim_state(self, (self.P,))
 
     def hyper_step(self, eps_h: float, L_h: int, p0=None, log_u=None):
         p0a = None if p0 is None else _f32(p0).reshape(-1)
@@ -667,6 +727,15 @@ class ChainGroup:
         outs = (StepOut * self.C)()
         _check(lib.tbnn_hmc_step(self._h, float(eps), int(L), None, None, outs, None))
         return [o.as_dict() for o in outs]
+
+    def optimize(self, steps: int, lr: float = 1e-2, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, amsgrad: bool = True,
+                 objective: str = "posterior", check_every: int = 10, keep: str = "best", reset: bool = True):
+        """Chain.optimize for every chain of the group, each from its own state, in the same launches: a list of its dicts, one per chain"""
+        return _optimize(self, self.C, steps, lr, beta1, beta2, epsilon, amsgrad, objective, check_every, keep, reset)
+
+    def optim_state(self):
+        """Chain.optim_state with [n_chains, P] arrays"""
+        return _optim_state(self, (self.C, self.P))
 
     def hyper_step(self, eps_h: float, L_h: int):
         outs = (StepOut * self.C)()

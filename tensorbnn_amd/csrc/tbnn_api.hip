@@ -20,6 +20,7 @@
 #include "kernels_hyper.hpp"
 #include "kernels_layered.hpp"
 #include "kernels_ensemble.hpp"
+#include "kernels_optim.hpp"
 #include "aot_ops.hpp"
 #include <mutex>
 
@@ -133,6 +134,10 @@ struct tbnn_ctx {
     Buf<float> hyp_ws;
     // per-chain step control (tbnn_hmc_step_each / tbnn_hyper_step_each): [C] on the device, staged through pinned memory
     Buf<StepCtl> ctl; PinBuf<StepCtl> ctl_host; Buf<float> epsh; PinBuf<float> epsh_host;
+    // optimiser state (tbnn_optimize; allocated on its first call): Adam moments, the last total gradient and the best weights as [C][P],
+    // the per-chain record k_optim_logp keeps, the objective trace [C][n_checks] (pooled), and the step counter t since the last reset
+    Buf<float> opt_m, opt_v, opt_vhat, opt_g, opt_qbest; Buf<OptChain> opt_oc; PinBuf<OptChain> opt_oc_host; Buf<double> opt_trace;
+    long opt_t = 0; bool opt_live = false;
     bool merge_ends = true;                // TBNN_MERGE_ENDS (read at tbnn_create): decision + record + commit in one k_energy launch
     bool traj = true;                      // TBNN_TRAJ (read at tbnn_create; 0: off): whole trajectories of small problems in one launch (kernels_traj.hpp)
 };
@@ -1096,6 +1101,120 @@ extern "C" int tbnn_hmc_run_each(tbnn_handle h, const float* eps, const int32_t*
 }
 extern "C" int tbnn_hmc_step_each(tbnn_handle h, const float* eps, const int32_t* L, tbnn_step_out* out) {
     return tbnn_hmc_run_each(h, eps, L, 1, out);
+}
+
+// ---- pre-training (include/tbnn.h: tbnn_optimize): Adam / AMSGrad ascent of the target log-probability, the whole run queued on the
+// chain's stream.  Replaces BNN_functions.trainBasicRegression / trainBasicClassification's Keras loop (BNN_functions.py:136-161, :255-279).
+static void launch_optim_logp(tbnn_ctx* h, int lik_only, int step, int n_checks, int k) {
+    hipLaunchKernelGGL(k_optim_logp, dim3(1, h->C), dim3(1024), 0, h->stream, h->nd, lik_only, (const float*)h->eta, (const float*)h->q, stat_ptr(h),
+                       stat_entries(h), rows_total(h), lik_const(h), (OptChain*)h->opt_oc, step, (double*)h->opt_trace, n_checks, k);
+}
+static void launch_optim(tbnn_ctx* h, int lik_only, const OptStep& s, int checked) {
+    const bool big = h->nd.P >= UPD_BIG_P;             // k_update's choice of block geometry (update_ops.hpp)
+    const int ucols = big ? UPD_COLS_BIG : UPD_COLS;
+    const int gx = (h->pitch / 4 + ucols - 1) / ucols;
+    const int* map = h->imgmap;
+    if (big)
+        hipLaunchKernelGGL((k_optim<UPD_COLS_BIG, UPD_GROUPS_BIG>), dim3(gx, h->C), dim3(UPD_COLS_BIG, UPD_GROUPS_BIG), 0, h->stream, h->nd, lik_only, s, checked,
+                           (const float*)h->eta, grad_slabs(h), grad_nslab(h), h->pitch, (float*)h->q, (float*)h->opt_g, (float*)h->opt_m, (float*)h->opt_v,
+                           (float*)h->opt_vhat, (float*)h->opt_qbest, (const OptChain*)h->opt_oc, map, (float*)h->qimg, h->img_floats);
+    else
+        hipLaunchKernelGGL((k_optim<UPD_COLS, UPD_GROUPS>), dim3(gx, h->C), dim3(UPD_COLS, UPD_GROUPS), 0, h->stream, h->nd, lik_only, s, checked,
+                           (const float*)h->eta, grad_slabs(h), grad_nslab(h), h->pitch, (float*)h->q, (float*)h->opt_g, (float*)h->opt_m, (float*)h->opt_v,
+                           (float*)h->opt_vhat, (float*)h->opt_qbest, (const OptChain*)h->opt_oc, map, (float*)h->qimg, h->img_floats);
+}
+extern "C" int tbnn_optimize(tbnn_handle h, const tbnn_optim_cfg* cfg, int32_t n_steps, int32_t reset, tbnn_optim_out* out, double* trace) {
+    NEED(h);
+    // every refusal comes before the handle is touched
+    if (!cfg || !out) return fail(-1, "tbnn_optimize: null cfg or out");
+    if (!h->dX) return fail(-1, "tbnn_optimize: tbnn_set_data has not been called");
+    if (h->shard) return fail(-1, "tbnn_optimize: not on a row-sharded handle (tbnn_set_row_shard): the optimiser runs on unsharded handles only");
+    if (n_steps < 0) return fail(-1, "tbnn_optimize: n_steps must be >= 0");
+    if (cfg->check_every < 1) return fail(-1, "tbnn_optimize: check_every must be >= 1");
+    if (!std::isfinite(cfg->lr) || !(cfg->lr > 0.f)) return fail(-1, "tbnn_optimize: lr must be finite and > 0");
+    if (!std::isfinite(cfg->epsilon) || !(cfg->epsilon > 0.f)) return fail(-1, "tbnn_optimize: epsilon must be finite and > 0");
+    if (!(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) || !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f)) return fail(-1, "tbnn_optimize: beta1 and beta2 must be in [0, 1)");
+    if (cfg->objective != TBNN_OPT_POSTERIOR && cfg->objective != TBNN_OPT_LIKELIHOOD) return fail(-1, "tbnn_optimize: unknown objective");
+    HIPCHK(hipSetDevice(h->device));
+    const NetDev& nd = h->nd;
+    const int C = h->C, T = n_steps, every = cfg->check_every;
+    const int n_checks = (T + every - 1) / every + 1;            // t in {0, k, 2k, .. < T}, and T
+    const size_t PN = (size_t)C * nd.P;
+    const dim3 pgrid((nd.P + 255) / 256, C);
+    if (!h->opt_live) {
+        HIPCHK(h->opt_m.alloc(PN)); HIPCHK(h->opt_v.alloc(PN)); HIPCHK(h->opt_vhat.alloc(PN)); HIPCHK(h->opt_g.alloc(PN)); HIPCHK(h->opt_qbest.alloc(PN));
+        HIPCHK(h->opt_oc.alloc((size_t)C)); HIPCHK(h->opt_oc_host.alloc((size_t)C));
+    }
+    HIPCHK(h->opt_trace.grow((size_t)C * n_checks, (size_t)C * n_checks + 1024));
+    if (reset || !h->opt_live) {
+        hipLaunchKernelGGL(k_optim_reset, pgrid, dim3(256), 0, h->stream, nd.P, C, (const float*)h->q_cur, (float*)h->opt_m, (float*)h->opt_v, (float*)h->opt_vhat,
+                           (float*)h->opt_g, (float*)h->opt_qbest, (OptChain*)h->opt_oc);
+        h->opt_t = 0; h->opt_live = true;
+    }
+    const int lik_only = cfg->objective == TBNN_OPT_LIKELIHOOD;
+    // theta_0 = the chain's state, in the proposal buffer with its padded image: k_optim keeps both current from here on
+    HIPCHK(hipMemcpyAsync(h->q, h->q_cur, PN * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    h->q_img_valid = false; h->cur_valid = false;
+    if (h->imgmap) {
+        hipLaunchKernelGGL(k_make_image, pgrid, dim3(256), 0, h->stream, nd.P, (const float*)h->q, h->imgmap, h->qimg, (long)nd.P, (long)h->img_floats);
+        h->q_img_valid = true;
+    }
+    struct ImageStale {                                        // on EVERY exit: the proposal buffer no longer mirrors a leapfrog position
+        tbnn_ctx* h;
+        ~ImageStale() { h->q_img_valid = false; h->cur_valid = false; }
+    } guard{h};
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    const double b1 = (double)cfg->beta1, b2 = (double)cfg->beta2;
+    OptStep s;
+    s.b1 = cfg->beta1; s.b2 = cfg->beta2; s.omb1 = (float)(1.0 - b1); s.omb2 = (float)(1.0 - b2); s.epsilon = cfg->epsilon; s.amsgrad = cfg->amsgrad != 0;
+    int k = 0;
+    for (int i = 0; i < T; ++i) {
+        if (const int rc = launch_fwd_bwd(h, h->q, h->eta)) return rc;
+        const int checked = i % every == 0;
+        if (checked) launch_optim_logp(h, lik_only, (int)(h->opt_t + i), n_checks, k++);
+        const double t = (double)(h->opt_t + i + 1);
+        s.a_t = (float)((double)cfg->lr / (1.0 - std::pow(b1, t)));
+        s.r_t = (float)(1.0 / std::sqrt(1.0 - std::pow(b2, t)));
+        launch_optim(h, lik_only, s, checked);
+    }
+    if (const int rc = launch_fwd_bwd(h, h->q, h->eta)) return rc;
+    launch_optim_logp(h, lik_only, (int)(h->opt_t + T), n_checks, k++);
+    hipLaunchKernelGGL(k_optim_finish, pgrid, dim3(256), 0, h->stream, nd.P, cfg->keep_best != 0, (const OptChain*)h->opt_oc, (const float*)h->q,
+                       (float*)h->opt_qbest, (float*)h->q_cur);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->opt_t += T;
+    std::vector<double> tr((size_t)C * n_checks);
+    HIPCHK(hipMemcpyAsync(tr.data(), h->opt_trace, tr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->opt_oc_host, h->opt_oc, (size_t)C * sizeof(OptChain), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float ms = 0.f; hipEventElapsedTime(&ms, h->ev0, h->ev1);
+    if (h->profile) drain_profile(h);
+    for (int c = 0; c < C; ++c) {
+        const OptChain& oc = h->opt_oc_host[c];
+        const double* tc = tr.data() + (size_t)c * n_checks;
+        tbnn_optim_out& o = out[c];
+        o.steps_done = T; o.diverged = oc.frozen; o.best_step = oc.best_step; o.n_checks = n_checks;
+        if (oc.frozen)                                        // the step whose check froze the chain (0: it was frozen when the call began)
+            for (int j = 0; j < n_checks; ++j)
+                if (!std::isfinite(tc[j])) { o.steps_done = std::min(T, j * every); break; }
+        o.obj_first = tc[0]; o.obj_last = tc[n_checks - 1]; o.obj_best = oc.best; o.device_us = ms * 1000.f;
+    }
+    if (trace) memcpy(trace, tr.data(), tr.size() * sizeof(double));
+    return 0;
+}
+extern "C" int tbnn_optim_state(tbnn_handle h, float* m, float* v, float* vhat, float* g, int32_t* t) {
+    NEED(h);
+    if (!h->opt_live) return fail(-1, "tbnn_optim_state: tbnn_optimize has not been called on this handle");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = (size_t)h->C * h->nd.P * sizeof(float);
+    if (m) HIPCHK(hipMemcpyAsync(m, h->opt_m, B, hipMemcpyDeviceToHost, h->stream));
+    if (v) HIPCHK(hipMemcpyAsync(v, h->opt_v, B, hipMemcpyDeviceToHost, h->stream));
+    if (vhat) HIPCHK(hipMemcpyAsync(vhat, h->opt_vhat, B, hipMemcpyDeviceToHost, h->stream));
+    if (g) HIPCHK(hipMemcpyAsync(g, h->opt_g, B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (t) *t = (int32_t)h->opt_t;
+    return 0;
 }
 
 extern "C" int tbnn_hyper_logp_grad(tbnn_handle h, const float* eta, double* logp, float* grad) {

@@ -227,6 +227,77 @@ class network(object):
             metric.calculate(trainPredict, validatePredict, trainReal, validateReal)
             metric.display()
 
+    # ------------------------------------------------------------------ pre-training
+    def pretrain(self, likelihood, cycles=3, epochs=1000, learningRate=0.01, decay=10.0, objective="posterior", patience=10,
+                 checkEvery=10, verbose=True):
+        """NEW: the pre-training every tutorial of the reference starts with (BNN_functions.trainBasicRegression /
+        trainBasicClassification, BNN_functions.py:60-297: Adam with amsgrad=True in `cycles` cycles whose learning rate falls by
+        `decay`, early stopping on the validation loss, best weights restored) -- on THIS network as it was built: its own
+        activations, priors and `likelihood`, its row weights, on the device (Chain.optimize; include/tbnn.h: tbnn_optimize).
+
+        Cycle x runs at learningRate * decay**-x from a fresh optimiser state (the reference re-compiles its model every cycle) for
+        at most `epochs` epochs.  ONE EPOCH HERE IS ONE FULL-BATCH STEP: the gradient of the whole training set, one Adam update --
+        not Keras' pass over mini-batches of 32 rows (n / 32 updates).  objective: "posterior" (log-likelihood + the layers' priors at
+        the current hyper-parameters) or "likelihood".  After every block of `checkEvery` steps the validation log-likelihood of the
+        current weights is evaluated on the device (Chain.ensemble_loglik over the staged validation rows); without validation rows
+        the training objective is monitored instead.  `patience` blocks in a row without improvement end the run -- like the
+        reference's one EarlyStopping callback, whose best record carries over the cycles -- and the best weights by that
+        monitor are restored.  A block whose objective stops being finite ends its cycle (the weights go back to the best).
+
+        Writes the result into self.states, so that a following train() / trainChains() starts there; the hyper-parameters stay as
+        they are.  Returns the history: a dict with "monitor" ("validation" | "training"), "blocks" (one record per block: cycle,
+        step, lr, objective, monitor), "start", "best", "best_step", "steps" and "stopped_early"."""
+        self.likelihood = likelihood
+        hyp = [np.asarray(h, dtype=np.float32).reshape(1) for h in self.hyperStates]
+        if self._lik_hypers:
+            hyp = hyp[:-self._lik_hypers]
+        hyp += [np.asarray(v, dtype=np.float32).reshape(1) for v in likelihood.hypers]
+        ch = self._ensure_chain(likelihood)
+        if verbose:
+            print("tensorbnn_amd: pre-training on", ch.kernel_name)
+        ch.set_state(self._theta())
+        ch.set_hypers(np.concatenate(hyp) if hyp else np.zeros(0, np.float32))
+        validate = bool(getattr(ch, "nv", 0))
+        sd = float(np.asarray(likelihood.hypers[-1]).reshape(-1)[0]) ** 2 if likelihood.kind == nat.LIK_GAUSSIAN else None
+
+        def monitor(theta, out):
+            if not validate:
+                return float(out["obj_last"])
+            return float(ch.ensemble_loglik(theta[None, :], which=1, sd=sd)[0][0])
+
+        theta = ch.get_state()
+        start = monitor(theta, ch.optimize(0, objective=objective))
+        best, best_theta, best_step = start, theta.copy(), 0
+        if not np.isfinite(best):
+            best = -np.inf
+        blocks, stale, steps, stopped = [], 0, 0, False
+        for x in range(int(cycles)):
+            lr = float(learningRate) * float(decay) ** (-x)
+            done = 0
+            while done < int(epochs) and not stopped:
+                k = min(int(checkEvery), int(epochs) - done)
+                out = ch.optimize(k, lr=lr, objective=objective, check_every=k, keep="last", reset=(done == 0))
+                done += k
+                steps += k
+                theta = ch.get_state()
+                mon = monitor(theta, out)
+                blocks.append({"cycle": x, "step": steps, "lr": lr, "objective": float(out["obj_last"]), "monitor": mon})
+                if verbose:
+                    print(f"cycle {x} step {steps} lr {lr:g} objective {out['obj_last']:.6g} monitor {mon:.6g}")
+                if np.isfinite(mon) and mon > best:
+                    best, best_theta, best_step, stale = mon, theta.copy(), steps, 0
+                else:
+                    stale += 1
+                if out["diverged"]:
+                    break
+                stopped = stale >= int(patience)
+            if stopped:
+                break
+        ch.set_state(best_theta)
+        self._set_states_from(best_theta)
+        return {"monitor": "validation" if validate else "training", "blocks": blocks, "start": start, "best": best,
+                "best_step": best_step, "steps": steps, "stopped_early": stopped}
+
     # ------------------------------------------------------------------ MCMC
     def setupMCMC(self, stepSizeStart=1e-3, stepSizeMin=1e-4, stepSizeMax=1e-2, stepSizeOptions=40,
                   leapfrogStart=1000, leapfogMin=100, leapFrogMax=10000, leapfrogIncrement=1, hyperStepSize=1e-2,
