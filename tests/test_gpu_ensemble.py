@@ -35,6 +35,8 @@ import math
 import numpy as np
 import pytest
 
+import forward_ref as fr
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -53
@@ -197,6 +199,11 @@ def test_two_real_chunks(native):
     ch = make_chain(native, "layered10")
     assert (1 << 28) // (10 * n) == 26 < m
     f = ch.forward_many(thetas, X=X)
+    # f is cut at the same boundary as everything below: the last network of the first chunk and both of the second against the fp64
+    # oracle (tests/forward_ref.py; this problem's fp32 oracle sits at 0.03 of that tolerance, tests/test_forward_ref_host.py)
+    nets = [0, 25, 26, 27]
+    rows = np.unique(np.concatenate([np.arange(0, n, 97), np.arange(64), np.arange(n - 64, n)]))
+    fr.check(f[nets][:, :, rows], fr.reference(fr.spec_of(*CASES["layered10"][:3]), thetas[nets], X, rows), "two real chunks, networks 0, 25 | 26, 27")
     w = net_weights(m, seed=5)
     mean, var = ch.ensemble_moments(thetas, X=X, weights=w)
     for k in range(10):                                                  # one output at a time: the extended-precision copies stay small
