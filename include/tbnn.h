@@ -52,8 +52,18 @@ enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
  * and C is subtracted where the log-probability is formed.  After tbnn_set_data_device C does not follow later in-place changes of the
  * caller's Y (stage the data again).  A log-rate beyond the fp32 range of exp gives a non-finite log-probability: such a proposal is
  * rejected (log_accept_ratio -inf) and the chain keeps its state.  Code 4 is not assigned: it is refused as an unknown likelihood, as
- * before TBNN_LIK_POISSON existed. */
-enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5 };
+ * before TBNN_LIK_POISSON existed;
+ * STUDENT_T: robust regression, any d_out >= 1 independent outputs, the last layer with any activation the Gaussian kinds accept.  With
+ * the scale s = the descriptor's fixed_sd (> 0), the degrees of freedom nu = the descriptor's lik_df (finite, > 0) and r = y - f, per
+ * (row, output):  log p = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log s - (nu+1)/2 log1p(r^2 / (nu s^2)),
+ * dL/df = (nu+1) r / (nu s^2 + r^2): a row's pull is bounded (largest at |r| = s sqrt nu) and falls off as 1/r beyond.  No likelihood
+ * hyper (H = 4 n_layers; the hyper transition touches no data).  The kernels accumulate sum_i w_i log1p(r^2 / (nu s^2)) (stat of
+ * tbnn_logp_grad) and the constant, W d_out times the first four terms with W the rows that normalise the Gaussian kinds too (their
+ * count, the sum of the row weights, n_total of a row-sharded chain), is added in fp64 where the log-probability is formed.  Codes 4, 6,
+ * 7 and every other value are not assigned: refused as an unknown likelihood.  Under TBNN_LIK_STUDENT_T tbnn_create,
+ * tbnn_create_multi and tbnn_fused_kernel_available refuse a lik_df that is not finite and > 0 and a fixed_sd that is not > 0. */
+enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5,
+       TBNN_LIK_STUDENT_T = 8 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or
@@ -71,9 +81,10 @@ typedef struct tbnn_net_desc {
     int32_t n_layers;
     const tbnn_layer_desc* layers;
     int32_t likelihood;  /* TBNN_LIK_* */
-    float fixed_sd;      /* FixedGaussianLikelihood(sd=) likelihood.py:138-141 */
+    float fixed_sd;      /* FixedGaussianLikelihood(sd=) likelihood.py:138-141; the scale s of TBNN_LIK_STUDENT_T */
     int32_t kernel;      /* TBNN_KERNEL_* */
-    int32_t reserved;
+    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; ignored under every other likelihood (this was `int32_t reserved`:
+                          * the same size and offset, and the all-zero bits callers passed there are 0.0) */
 } tbnn_net_desc;
 
 /* per-transition results: what network.train prints/threads through
@@ -255,7 +266,9 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
  * (Y with X NULL: targets for the staged rows, n must match); X without Y is refused.  Terms: the Gaussian log density per output;
  * Bernoulli with p clipped to [1e-8, 1 - 1e-7] (likelihood.py:78-80); categorical sum_k y_k log softmax_k(f) (likelihood.py:86-107);
  * Poisson y f - exp(f) - lgamma(y + 1) per output in fp64, f the log-rate (the posterior mean and variance of the rate itself:
- * tbnn_ensemble_moments with TBNN_XFORM_EXP).
+ * tbnn_ensemble_moments with TBNN_XFORM_EXP); Student-t: the density of TBNN_LIK_STUDENT_T per output in fp64, its scale s_i = sd[i] or
+ * NULL = fixed_sd, clipped as the Gaussian kinds', its nu the handle's lik_df -- the descriptor's on a Student-t handle, what
+ * tbnn_set_lik_df set on any other (0, never set: refused).
  *   per_net[i]   = sum over rows and outputs of the terms under network i          (m doubles, or NULL)
  *   lppd_rows[r] = log sum_i w_i p(y_r | theta_i) - log W, p the product over the row's outputs   (n doubles, or NULL)
  * Both are the same bits from run to run. */
@@ -345,7 +358,8 @@ int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64
  * Refused, with nothing written: q_out and cdf_out both NULL, q_out without probs, cdf_below_out without cdf_out or with a Gaussian kind,
  * X without Y when cdf_out is given, n not matching the staged rows, n_probs outside 1 .. 64, a probability outside (0, 1) or NaN,
  * TBNN_LIK_BERNOULLI / TBNN_LIK_CATEGORICAL (the predictive distribution of a label is its posterior-mean probability:
- * tbnn_ensemble_moments returns it), any other likelihood code, a NaN sd, weights breaking the rules above, m d_out 64 > 2^28. */
+ * tbnn_ensemble_moments returns it), TBNN_LIK_STUDENT_T (the mixture of t CDFs needs the regularised incomplete beta function on the
+ * device: not built), any other likelihood code, a NaN sd, weights breaking the rules above, m d_out 64 > 2^28. */
 int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                              const float* net_w, int which, const float* X, const float* Y, int64_t n, const double* probs,
                              int32_t n_probs, double* q_out, double* cdf_out, double* cdf_below_out);
@@ -381,6 +395,10 @@ int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int6
 int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                       int which, const float* X, const float* Y, int64_t n, double r_eff, double* elpd_loo_rows, double* pareto_k_rows,
                       double* lppd_rows, double* p_waic_rows, double* pointwise);
+/* The degrees of freedom nu that tbnn_ensemble_loglik and tbnn_ensemble_loo use when they judge under TBNN_LIK_STUDENT_T on a handle whose
+ * OWN likelihood is another one (a forward handle for saved networks is usually a fixed-sd Gaussian one).  Nothing else reads it.  Refused
+ * (-1): a TBNN_LIK_STUDENT_T handle (its nu is the descriptor's lik_df), a df that is not finite and > 0. */
+int tbnn_set_lik_df(tbnn_handle h, float df);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)
  *   out3[0] = mean (p-r)^2            SquaredError

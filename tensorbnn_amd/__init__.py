@@ -9,3 +9,11 @@ __version__ = "0.1.0"
 
 # the reference's pre-training helpers (they load the native library on their first call, not here: `tensorbnn_amd.build` must import without it)
 from .BNN_functions import trainBasicClassification, trainBasicRegression  # noqa: E402,F401
+
+
+def __getattr__(name):
+    # the likelihood plug-ins bind the native library when their module is imported: resolved on first use, for the same reason
+    if name == "StudentTLikelihood":
+        from .likelihood import StudentTLikelihood
+        return StudentTLikelihood
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("TBNN_LIB") or os.path.join(_HERE, "libtbnn.so")
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
+LIK_STUDENT_T = 8                                                                                  # (nor are 6 and 7)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
 OPT_POSTERIOR, OPT_LIKELIHOOD = 0, 1
 XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
@@ -38,7 +39,7 @@ class LayerDesc(C.Structure):
 
 class NetDesc(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("layers", C.POINTER(LayerDesc)), ("likelihood", C.c_int32),
-                ("fixed_sd", C.c_float), ("kernel", C.c_int32), ("reserved", C.c_int32)]
+                ("fixed_sd", C.c_float), ("kernel", C.c_int32), ("lik_df", C.c_float)]
 
 
 class StepOut(C.Structure):
@@ -119,6 +120,7 @@ SYMBOLS = [
     ("tbnn_ensemble_predictive", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp,
                                            _dp]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
+    ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
     ("tbnn_hyper_probs_many", C.c_int, [_H, C.POINTER(C.c_int32), _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _dp]),
     ("tbnn_register_kernel_lib", C.c_int, [C.c_char_p]),
@@ -287,12 +289,13 @@ class Chain:
 
     def __init__(self, layers: Sequence[tuple], likelihood: int = LIK_GAUSSIAN, fixed_sd: float = 0.1,
                  device: int = 0, seed: int = 50, chain_id: int = 0, kernel: int = KERNEL_AUTO,
-                 jit: Optional[bool] = None):
+                 jit: Optional[bool] = None, lik_df: float = 0.0):
         """jit: compile + register MFMA kernels for a shape outside the ahead-of-time registries (jit.py);
-        None -> the TBNN_JIT environment switch (default on); only consulted for KERNEL_AUTO / KERNEL_FAST."""
+        None -> the TBNN_JIT environment switch (default on); only consulted for KERNEL_AUTO / KERNEL_FAST.
+        lik_df: the degrees of freedom of LIK_STUDENT_T (its scale is fixed_sd); ignored under every other likelihood."""
         arr = (LayerDesc * len(layers))(*[LayerDesc(*map(int, l)) for l in layers])
         self._layers_keepalive = arr
-        desc = NetDesc(len(layers), arr, int(likelihood), float(fixed_sd), int(kernel), 0)
+        desc = NetDesc(len(layers), arr, int(likelihood), float(fixed_sd), int(kernel), float(lik_df))
         self._jit_args = (list(layers), int(likelihood), int(kernel), jit)          # (set_row_weights: the weighted kernels of the shape)
         if kernel != KERNEL_GENERIC:
             from . import jit as _jit
@@ -561,8 +564,9 @@ class Chain:
     def ensemble_loglik(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None):
         """data log-likelihood of the rows under every network of an ensemble, reduced on the device (tbnn_ensemble_loglik): (per_net
         float64 [m]: summed over rows and outputs; lppd_rows float64 [rows]: log of the weighted mixture of the networks' row likelihoods).
-        likelihood: the LIK_* to judge under (None: the chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd);
-        Y None with X None: the staged targets"""
+        likelihood: the LIK_* to judge under (None: the chain's own); sd: one per network for the Gaussian kinds and the scale of
+        LIK_STUDENT_T (None: the chain's fixed_sd; its degrees of freedom: the chain's lik_df, or set_lik_df); Y None with X None: the
+        staged targets"""
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
         yp, sdp, lik = self._ensemble_targets(th.shape[0], xp, n, Y, sd, likelihood)
         per_net = np.empty(th.shape[0], dtype=np.float64)
@@ -633,6 +637,11 @@ class Chain:
         _check(lib.tbnn_gather_samples(self._h, comm._c, C.c_void_p(d_out_ptr) if d_out_ptr else None, _p(out)))
         return out
 
+    def set_lik_df(self, df: float):
+        """the degrees of freedom ensemble_loglik / ensemble_loo use when they judge under LIK_STUDENT_T on a chain whose own likelihood is
+        another one (tbnn_set_lik_df); a LIK_STUDENT_T chain takes them from its constructor's lik_df and refuses this call"""
+        _check(lib.tbnn_set_lik_df(self._h, float(df)))
+
     def set_row_shard(self, comm: Optional["Comm"], n_total: int = 0):
         """row-sharded single chain: this rank's set_data rows are one block of n_total rows (None: back to unsharded)"""
         _check(lib.tbnn_set_row_shard(self._h, comm._c if comm is not None else None, int(n_total)))
@@ -644,10 +653,11 @@ class ChainGroup:
     small problems -- bound by launch latency, most of the GPU idle -- advance n_chains chains in the time of one."""
 
     def __init__(self, layers: Sequence[tuple], n_chains: int, likelihood: int = LIK_GAUSSIAN, fixed_sd: float = 0.1,
-                 device: int = 0, seed: int = 50, chain_id: int = 0, kernel: int = KERNEL_AUTO, jit: Optional[bool] = None):
+                 device: int = 0, seed: int = 50, chain_id: int = 0, kernel: int = KERNEL_AUTO, jit: Optional[bool] = None,
+                 lik_df: float = 0.0):
         arr = (LayerDesc * len(layers))(*[LayerDesc(*map(int, l)) for l in layers])
         self._layers_keepalive = arr
-        desc = NetDesc(len(layers), arr, int(likelihood), float(fixed_sd), int(kernel), 0)
+        desc = NetDesc(len(layers), arr, int(likelihood), float(fixed_sd), int(kernel), float(lik_df))
         self._jit_args = (list(layers), int(likelihood), int(kernel), jit)
         if kernel != KERNEL_GENERIC:
             from . import jit as _jit

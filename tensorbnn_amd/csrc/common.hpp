@@ -12,9 +12,13 @@
 enum { SHAPE_LIK_GAUSS = 0, SHAPE_LIK_BERN = 1, SHAPE_LIK_CAT = 2, SHAPE_LIK_POIS = 3 };
 // flag bit of the code: the kernel scales each row's data term by its weight (tbnn_set_row_weights; kernels_fast.hpp: row_weight)
 enum { SHAPE_LIK_WEIGHTED = 4 };
+// flag bit on the Gaussian family (the low two bits are full): the Student-t data term of TBNN_LIK_STUDENT_T, the residual y - f of the
+// Gaussian kinds under another loss (kernels_fast.hpp: lik_delta); weighted: SHAPE_LIK_STUDENT | SHAPE_LIK_WEIGHTED
+enum { SHAPE_LIK_STUDENT = 8 };
 // ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
 __host__ __device__ constexpr int shape_lik(int lik) {
-    return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS : SHAPE_LIK_GAUSS;
+    return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS :
+           lik == TBNN_LIK_STUDENT_T ? (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS) : SHAPE_LIK_GAUSS;
 }
 
 #define TBNN_WAVE 64
@@ -38,6 +42,7 @@ struct NetDev {
     int maxW;                     // widest layer (in or out)
     float fixed_sd;
     int reserved_flags;           // bit 0: fast kernel processes one tile at a time (diagnostic)
+    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu (0 otherwise)
 };
 
 // Gradient-slab stores of the narrow family: WRITE-THROUGH (global_store ... sc1: a relaxed agent-scope atomic store) when the slabs
@@ -97,6 +102,31 @@ __device__ __forceinline__ float lik_sigma(const NetDev& nd, const float* __rest
     s = fmaxf(s, 1e-8f);
     s = fminf(s, 1e8f);
     return s;
+}
+
+// Student-t (TBNN_LIK_STUDENT_T).  A kernel derives two constants once in its prologue: k = 1 / (nu s^2), which scales the squared residual
+// (the fused kernels: in the place of the Gaussian 1 / s^2, lik_inv_var of kernels_fast.hpp), and nu + 1, the factor of the delta.
+// log1p(u) for u >= 0 accurate RELATIVE TO ITSELF: the term is multiplied by (nu + 1) / 2 afterwards, and a bare __logf(1 + u) carries
+// the rounding of 1 + u, ~6e-8 ABSOLUTE, into a term that may itself be 1e-6 (nu = 1e4: 3e-4 per element after scaling).  Below 1/4 the
+// series 2 atanh(z) = 2 z (1 + z^2/3 + z^4/5 + z^6/7), z = u / (2 + u) <= 1/9 (the next term is 3e-9 of the sum); from 1/4 on the hardware
+// log2 of 1 + u, whose value is then >= 0.22 and takes the sum's rounding as ~3e-7 of itself.  Both are computed and one selected: no
+// branch in the tile body.  u = inf (a residual past the fp32 range) gives inf, NaN gives NaN: the statistic is not finite and k_energy
+// rejects the proposal.  No contraction beyond the fmaf written out (here, in student_elem and in lik_delta's branch): which product the
+// compiler fuses into which sum (2 + u, z + z, 1 + u of u = r r k) is its choice per instantiation, and a weighted kernel at weight 1 must
+// give the unweighted kernel's bits
+__device__ __forceinline__ float log1p_fast(float u) {
+#pragma clang fp contract(off)
+    const float z = u * __builtin_amdgcn_rcpf(2.f + u), z2 = z * z;
+    const float ser = (2.f * z) * fmaf(z2, fmaf(z2, fmaf(z2, 1.f / 7.f, 0.2f), 1.f / 3.f), 1.f);
+    return u < 0.25f ? ser : __logf(1.f + u);
+}
+// one (row, output) element of the Student-t data term for the kernels that branch at run time (layered, generic): adds
+// wt log1p(r^2 k) to stat and returns dL/df = wt (nu + 1) r k / (1 + r^2 k), k = 1 / (nu s^2) -- the arithmetic of lik_delta's branch
+__device__ __forceinline__ float student_elem(float fi, float y, double& stat, float wt, float k, float np1) {
+#pragma clang fp contract(off)
+    const float r = y - fi, u = r * r * k;
+    stat += (double)(wt * log1p_fast(u));
+    return wt * (np1 * (r * k) * __builtin_amdgcn_rcpf(1.f + u));
 }
 
 __device__ __forceinline__ float act_fwd(float z, int act) {

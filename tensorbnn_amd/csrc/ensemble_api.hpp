@@ -57,6 +57,27 @@ static int ens_sigmas(const std::string& who, const float* sd, float fixed_sd, i
     return 0;
 }
 
+// what tbnn_ensemble_loglik and tbnn_ensemble_loo stage per network: *scaled = the likelihood has a scale (the Gaussian kinds, Student-t) -- sig
+// and cst as ens_sigmas forms them; under TBNN_LIK_STUDENT_T *nu = the handle's degrees of freedom (its descriptor's, or what
+// tbnn_set_lik_df set on a handle of another likelihood) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
+static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, const float* sd, int32_t m, bool* scaled, std::vector<float>& sig,
+                          std::vector<double>& cst, double* nu) {
+    const bool student = likelihood == TBNN_LIK_STUDENT_T;
+    *scaled = ens_gaussian(likelihood) || student;
+    *nu = 0.0;
+    if (student) {
+        const float df = h->nd.lik == TBNN_LIK_STUDENT_T ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(df)) return fail(-1, who + ": judging under TBNN_LIK_STUDENT_T needs the degrees of freedom: call tbnn_set_lik_df on this handle first");
+        *nu = (double)df;
+    }
+    if (*scaled) ENS_TRY(ens_sigmas(who, sd, h->nd.fixed_sd, m, sig, &cst));
+    if (student) {
+        const double c0 = std::lgamma(0.5 * (*nu + 1.0)) - std::lgamma(0.5 * *nu) - 0.5 * std::log(*nu * M_PI);
+        for (int32_t i = 0; i < m; ++i) cst[i] = c0 - std::log((double)sig[i]);
+    }
+    return 0;
+}
+
 // The targets of the rows an entry point judges: the caller's Y (n rows), or the ones staged with the rows `which` selects.  What can be
 // refused before the driver touches the device is refused here; a `which` that selects nothing is left to EnsStage::stage_rows.
 static int ens_check_targets(tbnn_ctx* h, const std::string& who, int which, const float* X, const float* Y, int64_t n) {
@@ -388,11 +409,12 @@ extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t 
     if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     double W = 0.0;
     ENS_TRY(ens_check_weights(who, net_w, m, &W));
-    const bool gauss = ens_gaussian(likelihood);
-    // per network: sigma, -log sigma - 1/2 log 2 pi, log w
+    // per network: sigma, the constant of the density (Gaussian kinds: -log sigma - 1/2 log 2 pi; Student-t: ens_lik_consts), log w
+    bool gauss = false;                  // (the likelihood has a scale: the Gaussian kinds and Student-t)
+    double nu = 0.0;
     std::vector<float> sig;
     std::vector<double> cst, lw;
-    if (gauss) ENS_TRY(ens_sigmas(who, sd, h->nd.fixed_sd, m, sig, &cst));
+    ENS_TRY(ens_lik_consts(h, who, likelihood, sd, m, &gauss, sig, cst, &nu));
     if (net_w && lppd_rows) {
         lw.resize((size_t)m);
         for (int32_t i = 0; i < m; ++i) lw[i] = std::log((double)net_w[i]);          // (log 0 = -inf: the network drops out of the mixture)
@@ -425,7 +447,7 @@ extern "C" int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t 
         [&](int i0, int c, const float* dOut, long rows) -> int {
             hipLaunchKernelGGL(k_ens_loglik, dim3(nblk), dim3(ENS_TB), 0, h->stream, dOut, c, rows, d_out, likelihood, dYrows,
                                gauss ? (const float*)(dSig + i0) : nullptr, gauss ? (const double*)(dCst + i0) : nullptr,
-                               lw.empty() ? nullptr : (const double*)(dLw + i0), (int)(i0 == 0), (double*)lse, (double*)part);
+                               lw.empty() ? nullptr : (const double*)(dLw + i0), (int)(i0 == 0), (double*)lse, (double*)part, nu);
             HIPCHK(hipGetLastError());
             if (per_net) {
                 // the workgroups' partial sums of this chunk, added in index order: the same bits from run to run
@@ -487,6 +509,8 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
     }
     if (likelihood == TBNN_LIK_BERNOULLI || likelihood == TBNN_LIK_CATEGORICAL)
         return fail(-1, who + ": the predictive distribution of a label is its posterior-mean probability: tbnn_ensemble_moments returns it");
+    if (likelihood == TBNN_LIK_STUDENT_T)
+        return fail(-1, who + ": the Student-t predictive distribution (a mixture of t CDFs: the incomplete beta function on the device) is not built");
     const bool gauss = ens_gaussian(likelihood);
     if (!gauss && likelihood != TBNN_LIK_POISSON) return fail(-1, who + ": unknown likelihood");
     if (cdf_below_out && gauss) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
@@ -590,11 +614,12 @@ extern "C" int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, 
     // the budget of ensemble_row_blocks, judged here before m values of sd are read
     ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out + extra / sizeof(float), nullptr));
     ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
-    const bool gauss = ens_gaussian(likelihood);
-    // per network: sigma and -log sigma - 1/2 log 2 pi
+    // per network: sigma and the constant of the density, as tbnn_ensemble_loglik's
+    bool gauss = false;
+    double nu = 0.0;
     std::vector<float> sig;
     std::vector<double> cst;
-    if (gauss) ENS_TRY(ens_sigmas(who, sd, h->nd.fixed_sd, m, sig, &cst));
+    ENS_TRY(ens_lik_consts(h, who, likelihood, sd, m, &gauss, sig, cst, &nu));
     const bool psis = elpd_loo_rows || pareto_k_rows;
     const double logm = std::log((double)m);
     const float* dYrows = nullptr;
@@ -619,7 +644,7 @@ extern "C" int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, 
             double* res = dRes;
             hipLaunchKernelGGL(k_ens_pointwise, grid, tb, 0, h->stream, t, (int)m, r, d_out, likelihood, dYrows + (size_t)r0 * d_out,
                                gauss ? (const float*)dSig : nullptr, gauss ? (const double*)dCst : nullptr, logm, (double*)dL,
-                               lppd_rows ? res + 2 * rbk : nullptr, p_waic_rows ? res + 3 * rbk : nullptr);
+                               lppd_rows ? res + 2 * rbk : nullptr, p_waic_rows ? res + 3 * rbk : nullptr, nu);
             HIPCHK(hipGetLastError());
             if (psis) {
                 hipLaunchKernelGGL(k_ens_psis, grid, tb, 0, h->stream, (const double*)dL, (int)m, r, M, G, q, (double*)dTail, dTail + (size_t)M * rbk,

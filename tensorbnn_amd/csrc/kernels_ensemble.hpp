@@ -137,8 +137,10 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_moments_finish(double* __restric
 //   Bernoulli        xlogy(y, p) + xlog1py(1 - y, -p), p = clip(f, 1e-8, 1 - 1e-7) (likelihood.py:78-80; kernels_generic.hpp)
 //   categorical      sum_k y_k (f_k - max - log sum_j exp(f_j - max)) (likelihood.py:86-107)
 //   Poisson          y f - exp(f) - lgamma(y + 1) per output, f the log-rate, in fp64 (include/tbnn.h TBNN_LIK_POISSON)
+//   Student-t        cst - (nu + 1) / 2 log1p(((y - f) / sigma)^2 / nu) per output in fp64 (include/tbnn.h TBNN_LIK_STUDENT_T; sigma clipped by
+//                    the host, cst = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma: ensemble_api.hpp ens_lik_consts)
 __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restrict__ f, long n, const float* __restrict__ y, int d_out, float sigma,
-                                                 double cst) {
+                                                 double cst, double nu) {
     double l = 0.0;
     if (lik == TBNN_LIK_CATEGORICAL) {
         float mx = -INFINITY, s = 0.f;
@@ -155,6 +157,11 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
         for (int k = 0; k < d_out; ++k) {
             const double fk = (double)f[(size_t)k * n], yk = (double)y[k];
             l += fma(yk, fk, -exp(fk)) - lgamma(yk + 1.0);
+        }
+    } else if (lik == TBNN_LIK_STUDENT_T) {
+        for (int k = 0; k < d_out; ++k) {
+            const double d = ((double)y[k] - (double)f[(size_t)k * n]) / (double)sigma;
+            l += cst - 0.5 * (nu + 1.0) * log1p(d * d / nu);
         }
     } else if (lik == TBNN_LIK_BERNOULLI) {
         for (int k = 0; k < d_out; ++k) {
@@ -178,11 +185,11 @@ __device__ __forceinline__ void ens_lse_step(double a, double& M, double& S) {
     else if (a != -INFINITY) S += exp(a - M);                    // (a NaN prediction stays visible)
 }
 
-// One row per thread (the grid covers n).  sig / cst: the chunk's c sigmas and constants (Gaussian kinds; else unused); lw: the chunk's c
+// One row per thread (the grid covers n).  sig / cst: the chunk's c sigmas and constants (Gaussian kinds, Student-t with its nu; else unused); lw: the chunk's c
 // log weights, -inf for a weight of 0, or null (equal: log 1); lse: [2][n] or null (no row-wise mixture wanted); part: [gridDim.x][c] or null
 __global__ __launch_bounds__(ENS_TB) void k_ens_loglik(const float* __restrict__ out, int c, long n, int d_out, int lik, const float* __restrict__ Y,
                                                         const float* __restrict__ sig, const double* __restrict__ cst, const double* __restrict__ lw,
-                                                        int first, double* __restrict__ lse, double* __restrict__ part) {
+                                                        int first, double* __restrict__ lse, double* __restrict__ part, double nu) {
     __shared__ double red[ENS_NT][ENS_TB / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long row = (long)blockIdx.x * ENS_TB + tid;
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_loglik(const float* __restrict__
             const int i = i0 + ii;
             double l = 0.0;
             if (valid) {
-                l = ens_row_loglik(lik, out + (size_t)i * tot + row, n, Y + (size_t)row * d_out, d_out, sig ? sig[i] : 1.f, cst ? cst[i] : 0.0);
+                l = ens_row_loglik(lik, out + (size_t)i * tot + row, n, Y + (size_t)row * d_out, d_out, sig ? sig[i] : 1.f, cst ? cst[i] : 0.0, nu);
                 if (lse) {
                     ens_lse_step((lw ? lw[i] : 0.0) + l, M, S);
                 }
@@ -718,14 +725,14 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
 // centred sum of squares of the row's l_i over m - 1, the l_i read back from L.  A row with an l_i that is not finite gives NaN in both.
 __global__ __launch_bounds__(ENS_TB) void k_ens_pointwise(const float* __restrict__ out, int m, long r, int d_out, int lik, const float* __restrict__ Y,
                                                            const float* __restrict__ sig, const double* __restrict__ cst, double logm,
-                                                           double* L, double* __restrict__ lppd, double* __restrict__ pwaic) {
+                                                           double* L, double* __restrict__ lppd, double* __restrict__ pwaic, double nu) {
 #pragma clang fp contract(off)
     const long tot = r * d_out;
     for (long row = (long)blockIdx.x * ENS_TB + threadIdx.x; row < r; row += (long)gridDim.x * ENS_TB) {
         double Mx = -INFINITY, S = 0.0, sum = 0.0;
         int bad = 0;
         for (int i = 0; i < m; ++i) {
-            const double l = ens_row_loglik(lik, out + (size_t)i * tot + row, r, Y + (size_t)row * d_out, d_out, sig ? sig[i] : 1.f, cst ? cst[i] : 0.0);
+            const double l = ens_row_loglik(lik, out + (size_t)i * tot + row, r, Y + (size_t)row * d_out, d_out, sig ? sig[i] : 1.f, cst ? cst[i] : 0.0, nu);
             L[(size_t)i * r + row] = l;
             bad += !(fabs(l) < INFINITY);
             ens_lse_step(l, Mx, S);

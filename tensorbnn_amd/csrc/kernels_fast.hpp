@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FAST_THREADS (FAST_WAVES * 64)
 
 // HACT: activation after every hidden layer, LACT: after the last layer,
-// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson; `false` / `true` still spell the first two) -- all
+// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT; `false` / `true` still spell the first two) -- all
 // compile-time so the tile body is one straight-line block the scheduler can interleave.
 // Round 6: network.add takes any sequence of layers and activations (tensorBNN/network.py:173-191) -- a stack whose hidden layers do NOT all
 // carry the same activation has HACT = TBNN_ACT_PACKED | sum_l act_l << 3 l (hidden layer l = 0 .. NL - 2; at most 9 of them: fused_ops.hpp,
@@ -41,8 +41,9 @@ struct Shape {
     static constexpr int D[sizeof...(Ds)] = {Ds...};
     static constexpr int HCODE = HACT_, LACT = LACT_, LIK = LIK_;
     static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT, POIS = (LIK_ & 3) == SHAPE_LIK_POIS,
-                          WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0;
-    static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & 3) <= SHAPE_LIK_POIS && LIK_ < 2 * SHAPE_LIK_WEIGHTED, "unknown likelihood code");
+                          WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0, STUD = (LIK_ & SHAPE_LIK_STUDENT) != 0;
+    static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & ~(3 | SHAPE_LIK_WEIGHTED | SHAPE_LIK_STUDENT)) == 0, "unknown likelihood code");
+    static_assert(!STUD || (LIK_ & 3) == SHAPE_LIK_GAUSS, "Student-t is a flag on the Gaussian family (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS)");
     static_assert(!POIS || LACT_ == TBNN_ACT_NONE, "Poisson: the last layer's output is the log-rate (no last activation)");
     static_assert(!CAT || (LACT_ == TBNN_ACT_NONE && D[NL] >= 2), "categorical: logits (no last activation), at least 2 outputs");
     static_assert((HACT_ & TBNN_ACT_PACKED) == 0 || NL - 1 <= 9, "a packed activation code holds 9 hidden layers");
@@ -591,10 +592,18 @@ struct LastRegs {
     float accb[O];
 };
 
+// the scale of the squared residual a kernel derives in its prologue: 1 / s^2 of the Gaussian kinds; a Student-t instantiation: 1 / (nu s^2)
+template <class S>
+__device__ __forceinline__ float lik_inv_var(const NetDev& nd, float sigma) {
+    if constexpr (S::STUD) return 1.f / (nd.lik_df * sigma * sigma);
+    else return 1.f / (sigma * sigma);
+}
+
 // likelihood for one output value: statistic (counted when `count`), returns dL/df * act'.  A weighted instantiation scales the
 // residual / the row's term and its derivative by the row weight `wt` before either enters a sum: weight 1 gives the unweighted bits.
+// inv_var: lik_inv_var; np1: nu + 1, read by a Student-t instantiation only.
 template <class S>
-__device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat, float wt = 1.f) {
+__device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat, float wt = 1.f, float np1 = 0.f) {
     static_assert(!S::CAT, "the categorical likelihood couples a row's outputs: cat_delta4 on the MFMA output tile, no per-element path");
     float da;
     if constexpr (S::BERN) {
@@ -624,6 +633,20 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
         } else {
             if (count) stat += (double)term;
             da = res;
+        }
+    } else if constexpr (S::STUD) {
+        // TBNN_LIK_STUDENT_T: u = r^2 / (nu s^2); the term log1p(u) (its factor -(nu + 1) / 2 and the constant: data_logp, kernels_hmc.hpp) and
+        // dL/df = (nu + 1) r / (nu s^2 + r^2) = (nu + 1) (r k) / (1 + u), k = inv_var, by the hardware reciprocal as the Bernoulli path's
+        // (not contracted: common.hpp log1p_fast)
+#pragma clang fp contract(off)
+        const float res = yy - fi, u = res * res * inv_var;
+        const float term = log1p_fast(u), d = np1 * (res * inv_var) * __builtin_amdgcn_rcpf(1.f + u);
+        if constexpr (S::WTD) {
+            if (count) stat += (double)(wt * term);
+            da = wt * d;
+        } else {
+            if (count) stat += (double)term;
+            da = d;
         }
     } else {
         const float res = yy - fi;
@@ -709,7 +732,7 @@ struct TileStep {
     using C = FastCfg<S>;
     static constexpr int YN = C::VL ? C::out(C::NL - 1) : 4 * C::MTL;
     static __device__ __forceinline__ void run(f32x4 (&dW)[C::DW_TILES], LastRegs<S>& LR, double& stat, const float* __restrict__ lds,
-                                                float* wl, int i16, int g, float inv_var, const float (&x)[C::KS0],
+                                                float* wl, int i16, int g, float inv_var, float np1, const float (&x)[C::KS0],
                                                 const float (&y)[YN], bool rvalid,
                                                 const f32x4 (&A0)[C::MT(0)], const f32x4 (&B0)[C::MT(0)], float wt = 1.f) {
         constexpr int d_out = C::out(C::NL - 1), d_in = C::in(0), L = C::NL - 1, LM = C::NLM - 1;
@@ -737,7 +760,7 @@ struct TileStep {
                 p += __shfl_xor(p, 16, 64);
                 p += __shfl_xor(p, 32, 64);
                 const float fi = actc_fwd<S::LACT>(p + LR.b[o]);
-                dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt) : 0.f;
+                dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
             }
             TSTAMP(9);
             // dW_L / db_L partial sums, delta_{L-1}
@@ -763,7 +786,7 @@ struct TileStep {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int u = unit_of(d_out, 16 * mt + 4 * g + r, false);
-                    dz[mt][r] = (rvalid && u >= 0) ? lik_delta<S>(T.a[C::aroff(L) + mt][r], y[4 * mt + r], inv_var, true, stat, wt) : 0.f;
+                    dz[mt][r] = (rvalid && u >= 0) ? lik_delta<S>(T.a[C::aroff(L) + mt][r], y[4 * mt + r], inv_var, true, stat, wt, np1) : 0.f;
                 }
             TSTAMP(9);
         }
@@ -880,7 +903,8 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int t = 0; t < C::DW_TILES; ++t) dW[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float sigma = lik_sigma(nd, eta);
-    const float inv_var = 1.f / (sigma * sigma);
+    const float inv_var = lik_inv_var<S>(nd, sigma);
+    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
     double stat = 0.0;
     constexpr int d_in = C::in(0), d_out = C::out(C::NL - 1);
     const long ntiles = (n + 15) / 16;
@@ -946,7 +970,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         for (int k = 0; k < YN; ++k) y[k] = yn[k];
         const float wt = wn;
         fetch(tile + W);
-        TileStep<S>::run(dW, LR, stat, lds, wl, i16, g, inv_var, x, y, rv, A0, B0, wt);
+        TileStep<S>::run(dW, LR, stat, lds, wl, i16, g, inv_var, np1, x, y, rv, A0, B0, wt);
         if (first) { TB_STAMP(2); first = false; }
     }
     TB_STAMP(3);

@@ -1063,7 +1063,7 @@ struct Coop3 {
 
     // one 16-row tile on the four waves of the workgroup (every wave holds the tile's x / y of row i16)
     static __device__ __forceinline__ void tile(f32x4 (&dWc)[DWC], float (&FP)[FPd], double& stat, const float* __restrict__ lds, float* wl,
-                                                 float* xch, int wave, int lane, int i16, int g, float inv_var,
+                                                 float* xch, int wave, int lane, int i16, int g, float inv_var, float np1,
                                                  const float (&x)[C::KS0], const float (&y)[C::out(C::NL - 1)], bool rvalid, float wt = 1.f) {
         constexpr int d_in = C::in(0), d_out = C::out(C::NL - 1);
         Tile3<S> T;
@@ -1086,7 +1086,7 @@ struct Coop3 {
 #pragma unroll
         for (int o = 0; o < NFd; ++o) dzf[o] = 0.f;
 #pragma unroll
-        for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0 && wave == 0, stat, wt) : 0.f;
+        for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0 && wave == 0, stat, wt, np1) : 0.f;
         if (wave == 0) FringeDW<S, L>::run(FP, T, dzf, g);
         f32x4 dzL[C::MT(L)];
 #pragma unroll
@@ -1513,7 +1513,8 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int t = 0; t < C::FP_REGS; ++t) FP[t] = 0.f;
     const float sigma = lik_sigma(nd, eta);
-    const float inv_var = 1.f / (sigma * sigma);
+    const float inv_var = lik_inv_var<S>(nd, sigma);
+    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
     double stat = 0.0;
 
     if (g == 0) wl[C::aoff3(0) + d_in * C::PR + i16] = 1.f;
@@ -1556,7 +1557,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         // likelihood on the all-fringe last layer
         float dzf[NFd];
 #pragma unroll
-        for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0, stat, wt) : 0.f;
+        for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
         TSTAMP(30);
         // (the last layer's fringe sums -- a dozen packed FMAs -- wait until the N-fringe operands of layer L-1 are on their way: NCF)
         if constexpr (!C::NCF(L > 0 ? L - 1 : 0)) FringeDW<S, L>::run(FP, T, dzf, g);
@@ -1603,9 +1604,9 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             // the barriers inside are met by all 4 waves).  Small networks keep the loop: their launch is fetch- and launch-bound, the second
             // copy costs configs[0] 1 %
             const long ct0 = main_end + blockIdx.x, ct1 = ct0 + gridDim.x;
-            if (ncoop > 0 && ct0 < ntiles) CO::tile(dWc, FP, stat, lds, wl, xch, wave, lane, i16, g, inv_var, xc[0], yc[0], ct0 * 16 + i16 < n, wc[0]);
+            if (ncoop > 0 && ct0 < ntiles) CO::tile(dWc, FP, stat, lds, wl, xch, wave, lane, i16, g, inv_var, np1, xc[0], yc[0], ct0 * 16 + i16 < n, wc[0]);
             if (ncoop > 1 && ct1 < ntiles) {
-                CO::tile(dWc, FP, stat, lds, wl, xch, wave, lane, i16, g, inv_var, xc[1], yc[1], ct1 * 16 + i16 < n, wc[1]);
+                CO::tile(dWc, FP, stat, lds, wl, xch, wave, lane, i16, g, inv_var, np1, xc[1], yc[1], ct1 * 16 + i16 < n, wc[1]);
             }
         } else {
 #pragma unroll 1
@@ -1617,7 +1618,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
                 for (int t = 0; t < C::KS0; ++t) xj[t] = j == 0 ? xc[0][t] : xc[1][t];
 #pragma unroll
                 for (int o = 0; o < d_out; ++o) yj[o] = j == 0 ? yc[0][o] : yc[1][o];
-                CO::tile(dWc, FP, stat, lds, wl, xch, wave, lane, i16, g, inv_var, xj, yj, ct * 16 + i16 < n, j == 0 ? wc[0] : wc[1]);
+                CO::tile(dWc, FP, stat, lds, wl, xch, wave, lane, i16, g, inv_var, np1, xj, yj, ct * 16 + i16 < n, j == 0 ? wc[0] : wc[1]);
             }
         }
     }

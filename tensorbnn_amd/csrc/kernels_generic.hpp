@@ -14,7 +14,7 @@
 // Math restated from the reference: dense W@a+b layer.py:278, activations
 // activationFunctions.py:36/49/62, Gaussian residual likelihood.py:88-94 +
 // BNN_functions.py:23-32, Bernoulli likelihood.py:226-236, categorical (softmax over a row's outputs:
-// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON); reverse mode per
+// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T); reverse mode per
 // SURVEY.md A12 (TF autodiff has no source in the tree).
 #pragma once
 #include "common.hpp"
@@ -113,6 +113,11 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
                     // fi is the log-rate: y f - e^f (the constant -lgamma(y + 1) is the handle's: data_logp), dL/df = y - e^f; library expf
                     const float mu = expf(fi);
                     if (valid) { stat += (double)(wt * (y * fi - mu)); da = wt * (y - mu); }
+                } else if (nd.lik == TBNN_LIK_STUDENT_T) {
+                    // log1p(r^2 / (nu s^2)) (its factor -(nu + 1) / 2 and the constant: data_logp), dL/df = (nu + 1) r / (nu s^2 + r^2); library
+                    // log1pf and IEEE division
+                    const float r = y - fi, ns2 = nd.lik_df * sigma * sigma;
+                    if (valid) { stat += (double)(wt * log1pf(r * r / ns2)); da = wt * ((nd.lik_df + 1.f) * r / (ns2 + r * r)); }
                 } else {
                     const float r = y - fi;
                     const float wr = wt * r;

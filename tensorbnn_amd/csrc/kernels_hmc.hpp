@@ -159,6 +159,13 @@ __global__ __launch_bounds__(256) void k_make_image(int P, const float* __restri
 __device__ __forceinline__ double data_logp(const NetDev& nd, const float* __restrict__ eta, double stat, double n, double lik_c) {
     if (nd.lik == TBNN_LIK_POISSON) return stat - lik_c;                                   // the statistic is sum w (y f - e^f)
     if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
+    if (nd.lik == TBNN_LIK_STUDENT_T) {
+        // the statistic is sum w log1p(r^2 / (nu s^2)): n d_out c(nu, s) - (nu + 1) / 2 stat,
+        // c = lgamma((nu + 1) / 2) - lgamma(nu / 2) - 1/2 log(nu pi) - log s (include/tbnn.h TBNN_LIK_STUDENT_T)
+        const double nu = (double)nd.lik_df, s = (double)lik_sigma(nd, eta);
+        const double c = lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.14159265358979323846) - log(s);
+        return n * (double)nd.d_out * c - 0.5 * (nu + 1.0) * stat;
+    }
     // multivariateLogProb with sigma broadcast to [n, d_out] (likelihood.py:92, BNN_functions.py:25-32)
     const double s = (double)lik_sigma(nd, eta);
     const double nel = (double)n * (double)nd.d_out;

@@ -249,7 +249,8 @@ __global__ __launch_bounds__(MID_THREADS, 1) __attribute__((amdgpu_waves_per_eu(
     __syncthreads();
 
     const float sigma = FWD ? 1.f : lik_sigma(nd, eta);
-    const float inv_var = 1.f / (sigma * sigma);
+    const float inv_var = lik_inv_var<S>(nd, sigma);
+    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
     double stat = 0.0;
     f32x4 dW[FWD ? 1 : C::DW_TILES];
 #pragma unroll
@@ -452,7 +453,7 @@ __global__ __launch_bounds__(MID_THREADS, 1) __attribute__((amdgpu_waves_per_eu(
                     if (rvalid && g == 0) fout[(size_t)o * n + tile * 16 + i16] = fi;      // [d_out][n]
                     dzl[o] = 0.f;
                 } else {
-                    dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt) : 0.f;
+                    dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
                     LR.accb[o] += dzl[o];
                 }
                 MSTAMP(18 + 3 * o);
@@ -468,7 +469,7 @@ __global__ __launch_bounds__(MID_THREADS, 1) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int u = unit_of(d_out, 4 * g + r, false);
-                    dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(a[0][r], y[r], inv_var, true, stat, wt) : 0.f;
+                    dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(a[0][r], y[r], inv_var, true, stat, wt, np1) : 0.f;
                 }
             }
         } else {

@@ -274,7 +274,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
 
     TALL_STAMP(17);
     const float sigma = FWD ? 1.f : lik_sigma(nd, eta);
-    const float inv_var = 1.f / (sigma * sigma);
+    const float inv_var = lik_inv_var<S>(nd, sigma);
+    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
     double stat = 0.0;
     f32x4 dW0[FWD ? 1 : MT0 * CH];
     f32x4 dWm[(FWD || C::DWM_TILES == 0) ? 1 : C::DWM_TILES];
@@ -460,7 +461,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
                 if (rvalid && g == 0) fout[(size_t)o * n + tile * 16 + i16] = fi;      // [d_out][n]
                 dzl[o] = 0.f;
             } else {
-                dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt) : 0.f;
+                dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
             }
         }
         }
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int u = unit_of(d_out, 4 * g + r, false);
-                    dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(a[0][r], y[r], inv_var, true, stat, wt) : 0.f;
+                    dz[0][r] = (rvalid && u >= 0) ? lik_delta<S>(a[0][r], y[r], inv_var, true, stat, wt, np1) : 0.f;
                 }
             }
         } else {

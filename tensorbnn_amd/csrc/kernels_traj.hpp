@@ -103,7 +103,8 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
         }
     }
     const float sigma = lik_sigma(nd, eta);
-    const float inv_var = 1.f / (sigma * sigma);
+    const float inv_var = lik_inv_var<S>(nd, sigma);
+    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
     const float sg = nd.lik == TBNN_LIK_GAUSSIAN ? sigma : 1.f;
     __syncthreads();
     if (gq == 0) wl[C::aoff3(0) + d_in * C::PR + i16] = 1.f;
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
 #pragma unroll
             for (int o = 0; o < NFd; ++o) dzf[o] = 0.f;
 #pragma unroll
-            for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[LL][o], y[o], inv_var, gq == 0, stat) : 0.f;
+            for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[LL][o], y[o], inv_var, gq == 0, stat, 1.f, np1) : 0.f;
             if constexpr (!C::NCF(LL > 0 ? LL - 1 : 0)) FringeDW<S, LL>::run(FP, T, dzf, gq);
             f32x4 dzL[C::MT(LL)];
             f32x4 dzp[C::MT(LL - 1)];

@@ -101,6 +101,9 @@ struct tbnn_ctx {
     // row weights (tbnn_set_row_weights): [n x d_out targets | n weights] in one buffer -- what the kernels read as Y while weights are
     // set (kernels_fast.hpp: row_weight) -- and W = their sum in fp64; null / 0: none
     Buf<float> dYw; double wsum = 0.0;
+    // the degrees of freedom tbnn_ensemble_loglik / tbnn_ensemble_loo judge under TBNN_LIK_STUDENT_T with on a handle of another likelihood
+    // (tbnn_set_lik_df; 0: not set -- a Student-t handle's own are nd.lik_df)
+    float ens_df = 0.f;
     // TBNN_LIK_POISSON: C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (stage_lik_const; all chains share it); 0 otherwise
     double lik_c = 0.0;
     int want = TBNN_KERNEL_AUTO;          // tbnn_net_desc::kernel (the re-selection of tbnn_set_row_weights follows it)
@@ -157,8 +160,10 @@ extern "C" int tbnn_device_count(void) {
     return n;
 }
 
-// the TBNN_LIK_* values (4 is not one of them: include/tbnn.h)
-static bool lik_known(int lik) { return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON; }
+// the TBNN_LIK_* values (4, 6 and 7 are not among them: include/tbnn.h)
+static bool lik_known(int lik) { return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON || lik == TBNN_LIK_STUDENT_T; }
+// degrees of freedom a Student-t term can be formed with
+static bool df_ok(float df) { return df > 0.f && df < INFINITY; }
 
 static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
     if (!d || !d->layers) return fail(-1, "null descriptor");
@@ -193,6 +198,11 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
     nd.sumOut = so; nd.maxW = mw;
     nd.fixed_sd = d->fixed_sd;
     if (nd.lik == TBNN_LIK_FIXED_GAUSSIAN && !(d->fixed_sd > 0.f)) return fail(-1, "fixed_sd must be > 0");
+    if (nd.lik == TBNN_LIK_STUDENT_T) {
+        if (!(d->fixed_sd > 0.f)) return fail(-1, "the Student-t likelihood takes its scale from fixed_sd, which must be > 0");
+        if (!df_ok(d->lik_df)) return fail(-1, "the Student-t likelihood needs lik_df (its degrees of freedom) finite and > 0");
+        nd.lik_df = d->lik_df;
+    }
     return 0;
 }
 
@@ -1101,6 +1111,14 @@ extern "C" int tbnn_hmc_run_each(tbnn_handle h, const float* eps, const int32_t*
 }
 extern "C" int tbnn_hmc_step_each(tbnn_handle h, const float* eps, const int32_t* L, tbnn_step_out* out) {
     return tbnn_hmc_run_each(h, eps, L, 1, out);
+}
+
+extern "C" int tbnn_set_lik_df(tbnn_handle h, float df) {
+    NEED(h);
+    if (h->nd.lik == TBNN_LIK_STUDENT_T) return fail(-1, "set_lik_df: a Student-t handle takes its degrees of freedom from the descriptor's lik_df");
+    if (!df_ok(df)) return fail(-1, "set_lik_df: df must be finite and > 0");
+    h->ens_df = df;
+    return 0;
 }
 
 // ---- pre-training (include/tbnn.h: tbnn_optimize): Adam / AMSGrad ascent of the target log-probability, the whole run queued on the

@@ -128,3 +128,38 @@ class PoissonLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+class StudentTLikelihood(Likelihood):
+    """Robust regression: independent Student-t noise of fixed scale `sd` and `df` degrees of freedom around each output (any
+    activation the Gaussian kinds take).  Per (row, output), r = y - f:
+    log p = lgamma((df+1)/2) - lgamma(df/2) - 1/2 log(df pi) - log sd - (df+1)/2 log1p(r^2 / (df sd^2))  (include/tbnn.h
+    TBNN_LIK_STUDENT_T).  A row's pull on the fit, (df+1) r / (df sd^2 + r^2), is bounded: a few gross outliers do not decide the
+    posterior as they do under FixedGaussianLikelihood, which this likelihood approaches as df grows.  No hyper-parameter."""
+    kind = nat.LIK_STUDENT_T
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.sd = kwargs["sd"]
+        self.fixed_sd = float(kwargs["sd"])
+        self.df = float(kwargs["df"])
+        if not (self.fixed_sd > 0 and math.isfinite(self.fixed_sd)) or not (self.df > 0 and math.isfinite(self.df)):
+            raise ValueError("StudentTLikelihood needs sd > 0 and df > 0, both finite")
+        self.mainProbsInHypers = False
+
+    def logDensity(self, f, y, sd=None):
+        """the log density of y around f, element by element in float64 (sd: the scale, default the likelihood's own)"""
+        s = np.clip(np.float64(self.fixed_sd if sd is None else sd), 1e-8, 1e8)          # (clipped as the Gaussian kinds clip theirs)
+        nu = self.df
+        c = math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi) - np.log(s)
+        r = (np.asarray(y, dtype=np.float64) - np.asarray(f, dtype=np.float64)) / s
+        return c - 0.5 * (nu + 1.0) * np.log1p(r * r / nu)
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """the log density per (output, row) in float64, [d_out, rows] as PoissonLikelihood's; the sum is the data term"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [d_out, rows]
+        y = np.asarray(kwargs["realVals"], dtype=np.float64).reshape(-1, f.shape[0]).T
+        return self.logDensity(f, y)
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

@@ -168,15 +168,16 @@ class network(object):
         lik = likelihood if likelihood is not None else getattr(self, "likelihood", None)
         kind = lik.kind if lik is not None else nat.LIK_FIXED_GAUSSIAN
         sd = float(getattr(lik, "fixed_sd", 0.1)) if lik is not None else 0.1
+        df = float(getattr(lik, "df", 0.0)) if kind == nat.LIK_STUDENT_T else 0.0          # StudentTLikelihood: its degrees of freedom
         w = self.trainWeights
-        key = (tuple(map(tuple, self._dense)), kind, sd, None if w is None else hash(np.asarray(w, np.float32).tobytes()))
+        key = (tuple(map(tuple, self._dense)), kind, sd, df, None if w is None else hash(np.asarray(w, np.float32).tobytes()))
         if self._chain is None or self._chain_key != key:
             if self._chain is not None:
                 self._chain.close()
                 self._chain = None
             # staged completely before it is kept: a chain whose weights were refused is not reused by the next train()
             ch = nat.Chain(self._dense, likelihood=kind, fixed_sd=sd, device=self.device, seed=self.seed,
-                           chain_id=self.chain_id, kernel=self.kernel)
+                           chain_id=self.chain_id, kernel=self.kernel, lik_df=df)
             try:
                 y = self.trainY.reshape(len(self.trainX), -1)
                 ch.set_data(self.trainX, y)
@@ -431,7 +432,8 @@ class network(object):
             self.hyperStates.append(np.asarray(val, dtype=np.float32).reshape(1))
         self._lik_hypers = len(likelihood.hypers)
         grp = nat.ChainGroup(self._dense, int(chains), likelihood=likelihood.kind, fixed_sd=float(getattr(likelihood, "fixed_sd", 0.1)),
-                             device=self.device, seed=self.seed, chain_id=self.chain_id, kernel=self.kernel)
+                             device=self.device, seed=self.seed, chain_id=self.chain_id, kernel=self.kernel,
+                             lik_df=float(getattr(likelihood, "df", 0.0)) if likelihood.kind == nat.LIK_STUDENT_T else 0.0)
         C = grp.C
         if verbose:
             print("tensorbnn_amd: fused kernel", grp.kernel_name, "x", C, "chains")

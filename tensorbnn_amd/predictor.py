@@ -135,7 +135,8 @@ class predictor(object):
     def _data_logprob(self, likelihood, trainX, trainY, n):
         """summed log-likelihood of the training rows under every n-th network (see the module docstring)"""
         from .layer import _multivariate_log_prob
-        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, PoissonLikelihood, log_softmax
+        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, PoissonLikelihood, StudentTLikelihood,
+                                 log_softmax)
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
@@ -145,9 +146,9 @@ class predictor(object):
             if isinstance(likelihood, CategoricalLikelihood):
                 out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
                 continue
-            if isinstance(likelihood, PoissonLikelihood):
+            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood)):
                 terms = likelihood.makeResponseLikelihood(None, predict=lambda *_a, _f=cur.T: _f, realVals=real)
-                out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1)
+                out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1) / of the t log densities
                 continue
             if isinstance(likelihood, BernoulliLikelihood):
                 out.append(np.float32(0))                                       # likelihood.py:239-243
@@ -354,9 +355,15 @@ class predictor(object):
 
     def _network_sd(self, lik, n):
         """the standard deviation of every n-th network under a Gaussian kind of likelihood, float32 [picked]: the fixed sd, or each
-        network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; None for the other likelihoods"""
-        from .likelihood import FixedGaussianLikelihood
+        network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; the scale of a StudentTLikelihood; None
+        for the other likelihoods"""
+        from .likelihood import FixedGaussianLikelihood, StudentTLikelihood
         picked = len(range(0, self.numNetworks, n))
+        if isinstance(lik, StudentTLikelihood):
+            # its scale, one per network as the fixed sd -- and its degrees of freedom set on the forward chain (a fixed-sd Gaussian handle)
+            # before the reduction that judges under it
+            self._ensure_chain().set_lik_df(lik.df)
+            return np.full(picked, np.float32(lik.sd), dtype=np.float32)
         if isinstance(lik, FixedGaussianLikelihood):
             return np.full(picked, np.float32(lik.sd), dtype=np.float32)                        # likelihood.py:195 (not squared)
         if isinstance(lik, GaussianLikelihood):
@@ -366,10 +373,13 @@ class predictor(object):
 
     # ---- the predictive distribution of a new observation: observation noise included (tbnn_ensemble_predictive) ----
     def _predictive_likelihood(self, likelihood):
-        from .likelihood import BernoulliLikelihood, CategoricalLikelihood
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, StudentTLikelihood
         lik = self.likelihood if likelihood is None else likelihood
         if isinstance(lik, (BernoulliLikelihood, CategoricalLikelihood)):
             raise ValueError("the predictive distribution of a label is its posterior-mean probability: predictMoments returns it")
+        if isinstance(lik, StudentTLikelihood):
+            raise ValueError("predictive quantiles, intervals and the predictive CDF are not built for a StudentTLikelihood (the mixture of t "
+                             "CDFs needs the incomplete beta function on the device); logPredictiveDensity, loo and waic are")
         return lik
 
     def predictiveQuantiles(self, inputMatrix, probs, n=1, weights=None, likelihood=None, sd=1.0, mean=0.0):
