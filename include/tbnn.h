@@ -61,9 +61,19 @@ enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
  * tbnn_logp_grad) and the constant, W d_out times the first four terms with W the rows that normalise the Gaussian kinds too (their
  * count, the sum of the row weights, n_total of a row-sharded chain), is added in fp64 where the log-probability is formed.  Codes 4, 6,
  * 7 and every other value are not assigned: refused as an unknown likelihood.  Under TBNN_LIK_STUDENT_T tbnn_create,
- * tbnn_create_multi and tbnn_fused_kernel_available refuse a lik_df that is not finite and > 0 and a fixed_sd that is not > 0. */
+ * tbnn_create_multi and tbnn_fused_kernel_available refuse a lik_df that is not finite and > 0 and a fixed_sd that is not > 0;
+ * NEG_BINOMIAL: over-dispersed counts, any d_out >= 1 independent outputs; Poisson's admission rules (no last activation, f the LOG of the
+ * mean, Y finite and >= 0, non-integers allowed, no likelihood hyper).  The dispersion r = the descriptor's lik_df (finite, > 0: tbnn_create,
+ * tbnn_create_multi and tbnn_fused_kernel_available refuse any other lik_df); mean mu = exp(f), variance mu + mu^2 / r, r -> inf the Poisson
+ * model.  With t = f - log r, p = sigmoid(t) = mu / (r + mu), q = 1 - p, per (row, output):
+ * log p(y | f) = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y log p + r log q,  dL/df = y q - r p = r (y - mu) / (r + mu): a row's pull is
+ * bounded by r from below, however large the rate.  The kernels form -log p = max(-t, 0) + log1p(e^-|t|) and -log q = max(t, 0) +
+ * log1p(e^-|t|) and never exp(f): every finite f gives a finite term (Poisson's overflow past the fp32 range of exp does not occur).  They
+ * accumulate y log p + r log q; the constant C = sum_i w_i sum_k (lgamma(y + 1) + lgamma(r) - lgamma(y + r)) is computed with the data (or
+ * row weights), in fp64 and bit for bit the same from run to run, and subtracted where the log-probability is formed -- Poisson's rules for
+ * tbnn_set_data_device and row shards hold.  Code 9 and every other value are not assigned. */
 enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5,
-       TBNN_LIK_STUDENT_T = 8 };
+       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or
@@ -83,7 +93,7 @@ typedef struct tbnn_net_desc {
     int32_t likelihood;  /* TBNN_LIK_* */
     float fixed_sd;      /* FixedGaussianLikelihood(sd=) likelihood.py:138-141; the scale s of TBNN_LIK_STUDENT_T */
     int32_t kernel;      /* TBNN_KERNEL_* */
-    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; ignored under every other likelihood (this was `int32_t reserved`:
+    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; ignored under every other likelihood (this was `int32_t reserved`:
                           * the same size and offset, and the all-zero bits callers passed there are 0.0) */
 } tbnn_net_desc;
 
@@ -268,7 +278,8 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
  * Poisson y f - exp(f) - lgamma(y + 1) per output in fp64, f the log-rate (the posterior mean and variance of the rate itself:
  * tbnn_ensemble_moments with TBNN_XFORM_EXP); Student-t: the density of TBNN_LIK_STUDENT_T per output in fp64, its scale s_i = sd[i] or
  * NULL = fixed_sd, clipped as the Gaussian kinds', its nu the handle's lik_df -- the descriptor's on a Student-t handle, what
- * tbnn_set_lik_df set on any other (0, never set: refused).
+ * tbnn_set_lik_df set on any other (0, never set: refused); negative binomial: the density of TBNN_LIK_NEG_BINOMIAL per output in fp64 in
+ * its stable form, its dispersion r the handle's lik_df by the same rule.
  *   per_net[i]   = sum over rows and outputs of the terms under network i          (m doubles, or NULL)
  *   lppd_rows[r] = log sum_i w_i p(y_r | theta_i) - log W, p the product over the row's outputs   (n doubles, or NULL)
  * Both are the same bits from run to run. */
@@ -345,14 +356,24 @@ int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64
  *                    integer k >= 0 with F(k) >= p, as a double (searched outward from the weighted mean rate, then by bisection).  The CDF
  *                    at a target y is taken at floor(y).  One evaluation of Q costs a few sqrt(k) terms near k = lambda, 2,660 at the most
  *                    (k just below 2^16), and no loop beyond: the cost does not grow with the rate up to the ceiling of 2^30.
+ *   TBNN_LIK_NEG_BINOMIAL   r = the handle's dispersion (the descriptor's lik_df on a negative-binomial handle, else what tbnn_set_lik_df set;
+ *                    never set: refused), q_i = r / (r + exp(f_i)) = sigmoid(log r - (double)f_i), formed directly and not as 1 - p_i.  For an
+ *                    integer k >= 0, F(k) = (1/W) sum_i w_i I_{q_i}(r, k + 1), I the regularised incomplete beta function: its continued
+ *                    fraction by the modified Lentz recurrence, the side I_x(a, b) / 1 - I_{1-x}(b, a) by x < (a + 1) / (a + b + 2), the
+ *                    prefactor formed around the peak (Stirling's series for every argument from 16 on) so that it does not cancel for large
+ *                    k, never more than 10 sqrt(max(r, k + 1)) + 100 double steps; F(k) = 0 for k < 0.  Quantile at p: the smallest integer
+ *                    k >= 0 with F(k) >= p, searched as Poisson's from the weighted mean rate, the first step floor(sqrt(mean + mean^2 / r))
+ *                    + 1.  The CDF at a target y is taken at floor(y).  Ceilings: 2^20 on the rate exp(f_i) and on k (below).
  * q_out: host [n_probs][d_out][n] doubles, or NULL (then probs may be NULL too); probs: n_probs probabilities in the OPEN interval (0, 1)
  * (the Gaussian quantile at 0 or 1 is infinite), 1 <= n_probs <= 64.  cdf_out: host [d_out][n] doubles = F(y) at the targets, or NULL; Y is
  * then needed by tbnn_ensemble_loglik's rules (host targets [n, d_out]; NULL with X NULL = the staged targets of `which`; X without Y is
- * refused).  cdf_below_out (TBNN_LIK_POISSON only, with cdf_out; or NULL): [d_out][n] doubles = F(y - 1), the lower end of the target's step
+ * refused).  cdf_below_out (TBNN_LIK_POISSON and TBNN_LIK_NEG_BINOMIAL only, with cdf_out; or NULL): [d_out][n] doubles = F(y - 1), the lower end of the target's step
  * (a discrete PIT value lies anywhere in [F(y - 1), F(y)]).  At least one of q_out and cdf_out must be given.
  * NaN: an element with a NaN among its f_i (any weight) gives NaN in every output; so does, among the networks with w_i > 0, a lambda_i
- * that is not finite or exceeds 2^30 (Poisson) or, for the quantiles alone, an infinite f_i (Gaussian).  A NaN target gives a NaN CDF;
- * under Poisson so does any target that is not finite, and a negative one gives 0.  Networks of weight 0 add nothing.  The results are the
+ * that is not finite or exceeds 2^30 (Poisson; negative binomial: 2^20) or, for the quantiles alone, an infinite f_i (Gaussian).  A NaN
+ * target gives a NaN CDF; under Poisson and the negative binomial so does any target that is not finite, and a negative one gives 0.  Under
+ * the negative binomial a target with floor(y) > 2^20 gives a NaN CDF too, no trial of the quantile search goes past k = 2^20, and a
+ * probability whose F(2^20) is still below it gives NaN for that probability alone.  Networks of weight 0 add nothing.  The results are the
  * same bits from run to run, and a probability's result does not depend on the others asked with it.  The rows are cut into blocks as for
  * tbnn_ensemble_quantiles (a block's (n_probs + 2) d_out rb results are held beside it).
  * Refused, with nothing written: q_out and cdf_out both NULL, q_out without probs, cdf_below_out without cdf_out or with a Gaussian kind,
@@ -397,7 +418,8 @@ int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t the
                       double* lppd_rows, double* p_waic_rows, double* pointwise);
 /* The degrees of freedom nu that tbnn_ensemble_loglik and tbnn_ensemble_loo use when they judge under TBNN_LIK_STUDENT_T on a handle whose
  * OWN likelihood is another one (a forward handle for saved networks is usually a fixed-sd Gaussian one).  Nothing else reads it.  Refused
- * (-1): a TBNN_LIK_STUDENT_T handle (its nu is the descriptor's lik_df), a df that is not finite and > 0. */
+ * (-1): a TBNN_LIK_STUDENT_T handle (its nu is the descriptor's lik_df), a df that is not finite and > 0.  The same value is the dispersion r
+ * when they judge under TBNN_LIK_NEG_BINOMIAL; a TBNN_LIK_NEG_BINOMIAL handle (its r is the descriptor's lik_df) is refused too. */
 int tbnn_set_lik_df(tbnn_handle h, float df);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)

@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "StudentTLikelihood":
         from .likelihood import StudentTLikelihood
         return StudentTLikelihood
+    if name == "NegativeBinomialLikelihood":
+        from .likelihood import NegativeBinomialLikelihood
+        return NegativeBinomialLikelihood
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,6 +21,7 @@ ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
 LIK_STUDENT_T = 8                                                                                  # (nor are 6 and 7)
+LIK_NEG_BINOMIAL = 10                                                                              # (nor is 9)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
 OPT_POSTERIOR, OPT_LIKELIHOOD = 0, 1
 XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
@@ -292,7 +293,8 @@ class Chain:
                  jit: Optional[bool] = None, lik_df: float = 0.0):
         """jit: compile + register MFMA kernels for a shape outside the ahead-of-time registries (jit.py);
         None -> the TBNN_JIT environment switch (default on); only consulted for KERNEL_AUTO / KERNEL_FAST.
-        lik_df: the degrees of freedom of LIK_STUDENT_T (its scale is fixed_sd); ignored under every other likelihood."""
+        lik_df: the degrees of freedom of LIK_STUDENT_T (its scale is fixed_sd), the dispersion r of LIK_NEG_BINOMIAL; ignored under every
+        other likelihood."""
         arr = (LayerDesc * len(layers))(*[LayerDesc(*map(int, l)) for l in layers])
         self._layers_keepalive = arr
         desc = NetDesc(len(layers), arr, int(likelihood), float(fixed_sd), int(kernel), float(lik_df))
@@ -579,8 +581,8 @@ class Chain:
         """posterior-predictive distribution of a NEW observation -- the mixture over the networks of the observation model around each
         prediction -- inverted and evaluated on the device (tbnn_ensemble_predictive): (q, F, F_below).  q float64 [n_probs, d_out, rows]: the
         quantiles at probs, each in (0, 1) (None: no probs).  F float64 [d_out, rows]: the mixture CDF at the targets, the PIT values; asked
-        for by cdf=True, or cdf=None and Y given (Y None with X None: the staged targets); else None.  F_below: under LIK_POISSON the CDF at
-        target - 1 (a count's PIT lies in [F_below, F]), else None.  likelihood: LIK_GAUSSIAN / LIK_FIXED_GAUSSIAN / LIK_POISSON (None: the
+        for by cdf=True, or cdf=None and Y given (Y None with X None: the staged targets); else None.  F_below: under LIK_POISSON / LIK_NEG_BINOMIAL the CDF at
+        target - 1 (a count's PIT lies in [F_below, F]), else None.  likelihood: LIK_GAUSSIAN / LIK_FIXED_GAUSSIAN / LIK_POISSON / LIK_NEG_BINOMIAL (None: the
         chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd)"""
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
         want_cdf = (Y is not None) if cdf is None else bool(cdf)
@@ -588,7 +590,7 @@ class Chain:
         pr = None if probs is None else np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
         q = None if pr is None else np.empty((pr.size, self.d_out, n), dtype=np.float64)
         F = np.empty((self.d_out, n), dtype=np.float64) if want_cdf else None
-        Fb = np.empty((self.d_out, n), dtype=np.float64) if want_cdf and lik == LIK_POISSON else None
+        Fb = np.empty((self.d_out, n), dtype=np.float64) if want_cdf and lik in (LIK_POISSON, LIK_NEG_BINOMIAL) else None
         _check(lib.tbnn_ensemble_predictive(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
                                             _pd(pr), 0 if pr is None else pr.size, _pd(q), _pd(F), _pd(Fb)))
         return q, F, Fb
@@ -639,7 +641,9 @@ class Chain:
 
     def set_lik_df(self, df: float):
         """the degrees of freedom ensemble_loglik / ensemble_loo use when they judge under LIK_STUDENT_T on a chain whose own likelihood is
-        another one (tbnn_set_lik_df); a LIK_STUDENT_T chain takes them from its constructor's lik_df and refuses this call"""
+        another one (tbnn_set_lik_df); a LIK_STUDENT_T chain takes them from its constructor's lik_df and refuses this call.  The same
+        value is the dispersion r when they -- and ensemble_predictive -- judge under LIK_NEG_BINOMIAL; a LIK_NEG_BINOMIAL chain refuses
+        the call too"""
         _check(lib.tbnn_set_lik_df(self._h, float(df)))
 
     def set_row_shard(self, comm: Optional["Comm"], n_total: int = 0):

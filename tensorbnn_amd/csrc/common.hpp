@@ -15,10 +15,14 @@ enum { SHAPE_LIK_WEIGHTED = 4 };
 // flag bit on the Gaussian family (the low two bits are full): the Student-t data term of TBNN_LIK_STUDENT_T, the residual y - f of the
 // Gaussian kinds under another loss (kernels_fast.hpp: lik_delta); weighted: SHAPE_LIK_STUDENT | SHAPE_LIK_WEIGHTED
 enum { SHAPE_LIK_STUDENT = 8 };
+// the same bit on the Poisson code: the negative-binomial data term of TBNN_LIK_NEG_BINOMIAL, the log-rate f of the Poisson kind under
+// another loss; weighted: SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN | SHAPE_LIK_WEIGHTED.  (The bit is not defined on the other two codes.)
+enum { SHAPE_LIK_NEGBIN = 8 };
 // ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
 __host__ __device__ constexpr int shape_lik(int lik) {
     return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS :
-           lik == TBNN_LIK_STUDENT_T ? (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS) : SHAPE_LIK_GAUSS;
+           lik == TBNN_LIK_STUDENT_T ? (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS) :
+           lik == TBNN_LIK_NEG_BINOMIAL ? (SHAPE_LIK_NEGBIN | SHAPE_LIK_POIS) : SHAPE_LIK_GAUSS;
 }
 
 #define TBNN_WAVE 64
@@ -42,7 +46,7 @@ struct NetDev {
     int maxW;                     // widest layer (in or out)
     float fixed_sd;
     int reserved_flags;           // bit 0: fast kernel processes one tile at a time (diagnostic)
-    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu (0 otherwise)
+    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r (0 otherwise)
 };
 
 // Gradient-slab stores of the narrow family: WRITE-THROUGH (global_store ... sc1: a relaxed agent-scope atomic store) when the slabs
@@ -127,6 +131,35 @@ __device__ __forceinline__ float student_elem(float fi, float y, double& stat, f
     const float r = y - fi, u = r * r * k;
     stat += (double)(wt * log1p_fast(u));
     return wt * (np1 * (r * k) * __builtin_amdgcn_rcpf(1.f + u));
+}
+
+// Negative binomial with log link (TBNN_LIK_NEG_BINOMIAL), fi the log of the mean, r the dispersion, lr = log r derived once in the
+// kernel's prologue.  With t = f - log r, p = sigmoid(t) = mu / (r + mu), q = 1 - p: the term y log p + r log q and dL/df = y q - r p.
+// Neither e^f nor r + e^f is formed: a = |t|, e = e^-a in (0, 1] by the hardware exp2, l = log1p(e) (log1p_fast: accurate relative to
+// itself, which the small side needs -- r log q ~ -mu when r is large), -log p = max(-t, 0) + l, -log q = max(t, 0) + l; p and q from e
+// and ONE hardware reciprocal of 1 + e, picked by the sign of t.  y (-log p) and r (-log q) are both >= 0: nothing cancels in the term,
+// and y q - r p is the difference of two bounded products.  Every finite f gives a finite term (f past the fp32 range of exp: e = 0,
+// the term ~ -y |t| or -r t, finite while that product is: |f| to 1e30 at counts to 1e8); NaN gives NaN and k_energy rejects the proposal.  Not contracted, for the reason given at log1p_fast.
+// *term: the element's part of the statistic (the constant lgamma(y + r) - lgamma(r) - lgamma(y + 1) is the handle's: data_logp,
+// kernels_hmc.hpp); returns dL/df.  One function for lik_delta's compile-time branch and the kernels that branch at run time.
+__device__ __forceinline__ float negbin_term(float fi, float y, float r, float lr, float* term) {
+#pragma clang fp contract(off)
+    const float t = fi - lr, a = fabsf(t);
+    const float e = __expf(-a), l = log1p_fast(e);
+    const float nlp = fmaxf(-t, 0.f) + l, nlq = fmaxf(t, 0.f) + l;
+    const float rc = __builtin_amdgcn_rcpf(1.f + e), s = e * rc;
+    const bool pos = t >= 0.f;
+    const float p = pos ? rc : s, q = pos ? s : rc;
+    *term = -(y * nlp + r * nlq);
+    return y * q - r * p;
+}
+// ... for the kernels that branch at run time (layered, generic): adds wt term to stat, returns wt dL/df
+__device__ __forceinline__ float negbin_elem(float fi, float y, double& stat, float wt, float r, float lr) {
+#pragma clang fp contract(off)
+    float term;
+    const float d = negbin_term(fi, y, r, lr, &term);
+    stat += (double)(wt * term);
+    return wt * d;
 }
 
 __device__ __forceinline__ float act_fwd(float z, int act) {

@@ -59,7 +59,7 @@ static int ens_sigmas(const std::string& who, const float* sd, float fixed_sd, i
 
 // what tbnn_ensemble_loglik and tbnn_ensemble_loo stage per network: *scaled = the likelihood has a scale (the Gaussian kinds, Student-t) -- sig
 // and cst as ens_sigmas forms them; under TBNN_LIK_STUDENT_T *nu = the handle's degrees of freedom (its descriptor's, or what
-// tbnn_set_lik_df set on a handle of another likelihood) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
+// tbnn_set_lik_df set on a handle of another likelihood; under TBNN_LIK_NEG_BINOMIAL the dispersion r, by the same rule) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
 static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, const float* sd, int32_t m, bool* scaled, std::vector<float>& sig,
                           std::vector<double>& cst, double* nu) {
     const bool student = likelihood == TBNN_LIK_STUDENT_T;
@@ -69,6 +69,12 @@ static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, c
         const float df = h->nd.lik == TBNN_LIK_STUDENT_T ? h->nd.lik_df : h->ens_df;
         if (!df_ok(df)) return fail(-1, who + ": judging under TBNN_LIK_STUDENT_T needs the degrees of freedom: call tbnn_set_lik_df on this handle first");
         *nu = (double)df;
+    }
+    if (likelihood == TBNN_LIK_NEG_BINOMIAL) {
+        // the dispersion r travels where nu does: the descriptor's lik_df on a negative-binomial handle, else what tbnn_set_lik_df set
+        const float r = h->nd.lik == TBNN_LIK_NEG_BINOMIAL ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(r)) return fail(-1, who + ": judging under TBNN_LIK_NEG_BINOMIAL needs the dispersion: call tbnn_set_lik_df on this handle first");
+        *nu = (double)r;
     }
     if (*scaled) ENS_TRY(ens_sigmas(who, sd, h->nd.fixed_sd, m, sig, &cst));
     if (student) {
@@ -512,7 +518,8 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
     if (likelihood == TBNN_LIK_STUDENT_T)
         return fail(-1, who + ": the Student-t predictive distribution (a mixture of t CDFs: the incomplete beta function on the device) is not built");
     const bool gauss = ens_gaussian(likelihood);
-    if (!gauss && likelihood != TBNN_LIK_POISSON) return fail(-1, who + ": unknown likelihood");
+    if (!gauss && likelihood != TBNN_LIK_POISSON && likelihood != TBNN_LIK_NEG_BINOMIAL) return fail(-1, who + ": unknown likelihood");
+    // (the wording predates the negative binomial, which takes cdf_below_out too; tests match on it)
     if (cdf_below_out && gauss) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
     if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     // the budget of ensemble_row_blocks, judged here before m values of sd and net_w are read and 3 m doubles staged
@@ -547,7 +554,14 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
     double smax = 0.0;
     ENS_TRY(pred_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, probs, n_probs, q_out, cdf_out, cdf_below_out, cst, pz, &smax));
     if (!q_out) n_probs = 0;
-    const bool pois = likelihood == TBNN_LIK_POISSON;
+    const bool pois = likelihood == TBNN_LIK_POISSON, negb = likelihood == TBNN_LIK_NEG_BINOMIAL;
+    // the dispersion of the negative binomial: the descriptor's lik_df on such a handle, what tbnn_set_lik_df set on any other
+    double disp = 0.0;
+    if (negb) {
+        const float r = h->nd.lik == TBNN_LIK_NEG_BINOMIAL ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(r)) return fail(-1, who + ": the predictive distribution under TBNN_LIK_NEG_BINOMIAL needs the dispersion: call tbnn_set_lik_df on this handle first");
+        disp = (double)r;
+    }
     if (cdf_out) ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
     const float* dYrows = nullptr;
     Buf<float> dY;
@@ -572,15 +586,17 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
             double* F = dRes + (size_t)n_probs * rbk;
             double* Fb = cdf_below_out ? F + rbk : nullptr;
             if (q_out) {
-                if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q);
-                else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q);
+                if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
+                else if (negb) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_NEG_BINOMIAL, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
+                else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 HIPCHK(hipGetLastError());
                 ENS_TRY(ens_copy_planes(h, q_out, r0, rows, q, r, (size_t)n_probs * d_out));
             }
             if (cdf_out) {
                 const float* y = dYrows + (size_t)r0 * d_out;
-                if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb);
-                else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb);
+                if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
+                else if (negb) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_NEG_BINOMIAL>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
+                else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 HIPCHK(hipGetLastError());
                 ENS_TRY(ens_copy_planes(h, cdf_out, r0, rows, F, r, (size_t)d_out));
                 if (Fb) ENS_TRY(ens_copy_planes(h, cdf_below_out, r0, rows, Fb, r, (size_t)d_out));

@@ -45,6 +45,7 @@
 #define ENS_PQ 4        // probabilities whose root-search states a predictive-quantile thread carries in registers at a time (k_ens_pred_quantiles' QP)
 #define ENS_PRED_PASSES 256   // trial points per probability at the most (Gaussian: the moves at least halve, a bisection at the worst; Poisson: <= 2 log2 of the count)
 #define ENS_POIS_MAX_RATE 1073741824.0   // 2^30: a larger (or non-finite) rate makes the element NaN
+#define ENS_NB_MAX 1048576.0             // 2^20: the negative binomial's ceiling on the rate AND on the count k; beyond either the element is NaN
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
 __device__ __forceinline__ float ens_xform(float f, int xform) {
@@ -137,6 +138,8 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_moments_finish(double* __restric
 //   Bernoulli        xlogy(y, p) + xlog1py(1 - y, -p), p = clip(f, 1e-8, 1 - 1e-7) (likelihood.py:78-80; kernels_generic.hpp)
 //   categorical      sum_k y_k (f_k - max - log sum_j exp(f_j - max)) (likelihood.py:86-107)
 //   Poisson          y f - exp(f) - lgamma(y + 1) per output, f the log-rate, in fp64 (include/tbnn.h TBNN_LIK_POISSON)
+//   neg. binomial    lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y log p + r log q per output in fp64, p = sigmoid(f - log r), the logs in
+//                    the stable form of negbin_term (common.hpp); r arrives in `nu` (ensemble_api.hpp ens_lik_consts)
 //   Student-t        cst - (nu + 1) / 2 log1p(((y - f) / sigma)^2 / nu) per output in fp64 (include/tbnn.h TBNN_LIK_STUDENT_T; sigma clipped by
 //                    the host, cst = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma: ensemble_api.hpp ens_lik_consts)
 __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restrict__ f, long n, const float* __restrict__ y, int d_out, float sigma,
@@ -157,6 +160,13 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
         for (int k = 0; k < d_out; ++k) {
             const double fk = (double)f[(size_t)k * n], yk = (double)y[k];
             l += fma(yk, fk, -exp(fk)) - lgamma(yk + 1.0);
+        }
+    } else if (lik == TBNN_LIK_NEG_BINOMIAL) {
+        const double lr = log(nu), lgr = lgamma(nu);
+        for (int k = 0; k < d_out; ++k) {
+            const double yk = (double)y[k], t = (double)f[(size_t)k * n] - lr;
+            const double lp1 = log1p(exp(-fabs(t)));
+            l += (lgamma(yk + nu) - lgr - lgamma(yk + 1.0)) - (yk * (fmax(-t, 0.0) + lp1) + nu * (fmax(t, 0.0) + lp1));
         }
     } else if (lik == TBNN_LIK_STUDENT_T) {
         for (int k = 0; k < d_out; ++k) {
@@ -539,6 +549,97 @@ __device__ __forceinline__ double ens_gamma_q(double a, double x) {
     return fmin(pref * a * h, 1.0);
 }
 
+// ---- the regularised incomplete beta function I_x(a, b), fp64 (the negative-binomial CDF: Pr[Y <= k] = I_q(r, k + 1), q = r / (r + mu)) ----
+// Stirling's correction: lgamma(z) = (z - 1/2) log z - z + 1/2 log 2 pi + ens_stirling(z); from z = 16 on the next term, 1 / (1680 z^7), is < 3e-12
+__device__ __forceinline__ double ens_stirling(double z) {
+#pragma clang fp contract(off)
+    const double r = 1.0 / z, r2 = r * r;
+    return r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0)));
+}
+
+// log of x^a y^b / B(a, b), y = 1 - x given by the caller (formed on its own, not as 1 - x).  Written out, lgamma(a + b) - lgamma(a) - lgamma(b)
+// + a log x + b log y differences terms of size n log n, n = a + b: 1.4e7 at a count of 2^20, 3e-9 of the result.  So, as ens_pois_logpref
+// forms its prefactor around the peak: every argument >= 16 takes Stirling's series, whose leading parts cancel in closed form --
+//   a, b >= 16   1/2 log(a b / (2 pi n)) + a log1pmx(u) + b log1pmx(v) + S(n) - S(a) - S(b),  u = (x - a/n) / (a/n), v = (y - b/n) / (b/n)
+//                (a u + b v = 0: the first-order parts are gone, both log1pmx terms are <= 0; x - a/n as (x b - y a) / n)
+//   one < 16     with s the small and L the large one: lgamma(n) - lgamma(L) = L log1pmx(s/L) - 1/2 log1p(s/L) + s log n + S(n) - S(L),
+//                then - lgamma(s) + a log x + b log y: where the result is not negligible every term is of modest size
+//   both < 16    written out: no term exceeds ~50
+// log x and log y through log1p of the other where they are near 1
+__device__ __forceinline__ double ens_beta_logpref(double a, double b, double x, double y) {
+#pragma clang fp contract(off)
+    const double n = a + b;
+    if (a >= 16.0 && b >= 16.0) {
+        const double d = (x * b - y * a) / n;
+        return 0.5 * log(a * b / (6.283185307179586477 * n)) + a * ens_log1pmx(d * n / a) + b * ens_log1pmx(-d * n / b) +
+               (ens_stirling(n) - ens_stirling(a) - ens_stirling(b));
+    }
+    const double lx = x < 0.5 ? log(x) : log1p(-y), ly = y < 0.5 ? log(y) : log1p(-x);
+    if (a < 16.0 && b < 16.0) return lgamma(n) - lgamma(a) - lgamma(b) + a * lx + b * ly;
+    const double sm = fmin(a, b), lg = fmax(a, b), z = sm / lg;
+    const double gr = lg * ens_log1pmx(z) - 0.5 * log1p(z) + sm * log(n) + (ens_stirling(n) - ens_stirling(lg)) - lgamma(sm);
+    return gr + a * lx + b * ly;
+}
+
+// the continued fraction of I_x(a, b) a B(a, b) / (x^a y^b) by the modified Lentz recurrence (Numerical Recipes section 6.4, betacf): it
+// converges in O(sqrt(max(a, b))) double steps for x < (a + 1) / (a + b + 2); never more than 10 sqrt(max(a, b)) + 100 are taken (10,340 at
+// the ceiling; the grid of tests/test_gpu_negbin_predictive.py needs 129 at the most)
+__device__ __forceinline__ double ens_beta_cf(double a, double b, double x) {
+#pragma clang fp contract(off)
+    const double tiny = 1e-300;
+    const int itmax = (int)(10.0 * sqrt(fmax(a, b))) + 100;
+    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * x / qap;
+    if (fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double h = d;
+    for (int it = 1; it <= itmax; ++it) {
+        const double m = (double)it, m2 = 2.0 * m;
+        double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        h *= d * c;
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) < 2.3e-16) break;
+    }
+    return h;
+}
+
+// I_x(a, b) for a, b > 0 and x, y = 1 - x in [0, 1], both given.  The side by the usual rule: x < (a + 1) / (a + b + 2) the fraction of
+// (a, b, x), else 1 minus the fraction of (b, a, y).  Where the prefactor is below e^-80 the answer is 0 or 1 to more than 1e-25 (the
+// fraction over its first argument stays below ~1e7 here) and nothing is summed.  A NaN among the arguments gives NaN.
+__device__ __forceinline__ double ens_betainc(double a, double b, double x, double y) {
+#pragma clang fp contract(off)
+    if (x != x || y != y) return (double)NAN;
+    if (!(x > 0.0)) return 0.0;
+    if (!(y > 0.0)) return 1.0;
+    const double lp = ens_beta_logpref(a, b, x, y);
+    const bool left = x < (a + 1.0) / (a + b + 2.0);
+    if (lp < -80.0) return left ? 0.0 : 1.0;
+    const double pref = exp(lp);
+    if (left) return fmin(pref * ens_beta_cf(a, b, x) / a, 1.0);
+    return fmax(1.0 - pref * ens_beta_cf(b, a, y) / b, 0.0);
+}
+
+// the negative binomial's q = r / (r + mu) = sigmoid(log r - f) and p = 1 - q = sigmoid(f - log r), each formed directly from
+// e = exp(-|log r - f|): neither is a difference from 1
+__device__ __forceinline__ void ens_nb_qp(double lr, double f, double& q, double& p) {
+#pragma clang fp contract(off)
+    const double s = lr - f, e = exp(-fabs(s)), big = 1.0 / (1.0 + e), small = e / (1.0 + e);
+    q = s >= 0.0 ? big : small;
+    p = s >= 0.0 ? small : big;
+}
+
 // the spacing of fp64 at |v| (v finite)
 __device__ __forceinline__ double ens_ulp64(double v) {
     const double av = fabs(v);
@@ -548,16 +649,22 @@ __device__ __forceinline__ double ens_ulp64(double v) {
 // t: the block [m][tot] of untransformed predictions, tot = d_out r; Y: the block's targets [r][d_out]; cst[2][m]: w_i / W and, Gaussian
 // kinds, 1 / (s_i sqrt 2).  cdf[tot] = F(y); below[tot] (Poisson, or null) = F(y - 1).  Networks of weight 0 add nothing; a NaN among an
 // element's f_i or a NaN target (Poisson: any target that is not finite) gives NaN.  Poisson: the target is read at k = floor(y), F = 0 for k < 0, and a non-finite rate or one
-// above 2^30 among the networks that count gives NaN.
+// above 2^30 among the networks that count gives NaN.  Negative binomial (disp = r, the dispersion; not read otherwise): as Poisson with
+// F(k) = sum_i w_i / W I_{q_i}(r, k + 1), q_i = sigmoid(log r - f_i); its ceilings are 2^20 on the rate AND on k = floor(y): beyond either
+// the element is NaN (ENS_NB_MAX).
 template <int LIK>
 __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict__ t, int m, long tot, long r, int d_out, const float* __restrict__ Y,
-                                                          const double* __restrict__ cst, double* __restrict__ cdf, double* __restrict__ below) {
+                                                          const double* __restrict__ cst, double* __restrict__ cdf, double* __restrict__ below,
+                                                          double disp) {
 #pragma clang fp contract(off)
+    constexpr bool COUNTS = LIK == TBNN_LIK_POISSON || LIK == TBNN_LIK_NEG_BINOMIAL;
+    const double lr = LIK == TBNN_LIK_NEG_BINOMIAL ? log(disp) : 0.0;
     for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
         const float* __restrict__ te = t + e;
         const float yf = Y[(size_t)(e % r) * d_out + e / r];
         const double y = (double)yf, k = floor(y);
-        int bad = LIK == TBNN_LIK_POISSON ? !(fabsf(yf) < INFINITY) : yf != yf;
+        int bad = COUNTS ? !(fabsf(yf) < INFINITY) : yf != yf;
+        if (LIK == TBNN_LIK_NEG_BINOMIAL) bad += k > ENS_NB_MAX;
         double F = 0.0, Fb = 0.0;
         for (int i = 0; i < m; ++i) {
             const float fv = te[(size_t)i * tot];
@@ -569,6 +676,14 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
                 if (!(lam <= ENS_POIS_MAX_RATE)) { bad += 1; continue; }
                 if (k >= 0.0) F += wn * ens_gamma_q(k + 1.0, lam);
                 if (below && k >= 1.0) Fb += wn * ens_gamma_q(k, lam);
+            } else if (LIK == TBNN_LIK_NEG_BINOMIAL) {
+                const double lam = exp((double)fv);
+                if (!(lam <= ENS_NB_MAX)) { bad += 1; continue; }
+                if (bad) continue;                                                      // (a count past the ceiling: nothing is summed)
+                double q, p;
+                ens_nb_qp(lr, (double)fv, q, p);
+                if (k >= 0.0) F += wn * ens_betainc(disp, k + 1.0, q, p);
+                if (below && k >= 1.0) Fb += wn * ens_betainc(disp, k, q, p);
             } else {
                 F += wn * ens_phi(y, (double)fv, cst[m + i]);
             }
@@ -592,11 +707,17 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
 //             that double, starting at floor(sqrt(mean rate)) + 1 (F(-1) = 0 < p is known), until bracketed; then bisection.
 // An element with a NaN among its f_i gives NaN at every probability; so does, among the networks that count, an infinite f_i (Gaussian: the
 // bracket is unbounded) or a rate that is not finite or above 2^30 (Poisson).
+//   neg. binomial (disp = r; not read otherwise) Poisson's slots with F(k) = sum_i w_i / W I_{q_i}(r, k + 1): from k = floor(mean rate), the first
+//             step floor(sqrt(mean + mean^2 / r)) + 1.  No trial goes past k = 2^20 (ENS_NB_MAX): a probability whose F(2^20) is still below it
+//             gives NaN, and so does a rate that is not finite or above 2^20 among the networks that count.
 template <int LIK, int QP>
 __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __restrict__ t, int m, long tot, const double* __restrict__ cst,
-                                                                const double* __restrict__ probs, int np, double smax, double* __restrict__ res) {
+                                                                const double* __restrict__ probs, int np, double smax, double* __restrict__ res,
+                                                                double disp) {
 #pragma clang fp contract(off)
-    const bool gauss = LIK != TBNN_LIK_POISSON;
+    constexpr bool NEGB = LIK == TBNN_LIK_NEG_BINOMIAL;
+    const bool gauss = LIK != TBNN_LIK_POISSON && !NEGB;
+    const double lr = NEGB ? log(disp) : 0.0;
     for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
         const float* __restrict__ te = t + e;
         for (int p0 = 0; p0 < np; p0 += QP) {
@@ -627,7 +748,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     }
                 } else {
                     const double lam = exp((double)fv);
-                    if (!(lam <= ENS_POIS_MAX_RATE)) bad += 1;
+                    if (!(lam <= (NEGB ? ENS_NB_MAX : ENS_POIS_MAX_RATE))) bad += 1;
                     mean += wn * lam;
                 }
             }
@@ -638,7 +759,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     a[j] -= d; b[j] += d;
                     x[j] = a[j]; wd[j] = b[j] - a[j];
                 } else {
-                    x[j] = floor(mean); wd[j] = floor(sqrt(mean)) + 1.0;
+                    x[j] = floor(mean); wd[j] = floor(sqrt(NEGB ? mean + mean * mean / disp : mean)) + 1.0;
                 }
             }
             for (int pass = 0; pass < ENS_PRED_PASSES && !bad; ++pass) {
@@ -663,6 +784,12 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                                 D[j] += wc * exp(-(z * z));
                             }
                         }
+                    } else if (NEGB) {
+                        double q, p;
+                        ens_nb_qp(lr, f, q, p);
+#pragma unroll
+                        for (int j = 0; j < QP; ++j)
+                            if (ph[j] >= 0) F[j] += wn * ens_betainc(disp, x[j] + 1.0, q, p);
                     } else {
                         const double lam = exp(f);
 #pragma unroll
@@ -677,8 +804,10 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     if (!gauss) {
                         if (F[j] >= p) b[j] = x[j]; else a[j] = x[j];
                         if (b[j] == (double)INFINITY) {                                       // still below: outward, unless the count is absurd
+                            if (NEGB && a[j] >= ENS_NB_MAX) { b[j] = (double)NAN; ph[j] = -1; continue; }      // (F at the ceiling is below p)
                             if (a[j] > 0x1p40) { b[j] = a[j]; ph[j] = -1; continue; }
                             x[j] = a[j] + wd[j]; wd[j] *= 2.0;
+                            if (NEGB) x[j] = fmin(x[j], ENS_NB_MAX);
                         } else if (ph[j] == 0 && a[j] < 0.0 && b[j] - wd[j] > 0.0) {           // above, and nothing below it tried yet: outward and down
                             x[j] = b[j] - wd[j]; wd[j] *= 2.0;
                         } else {

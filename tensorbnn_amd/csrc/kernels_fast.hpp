@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FAST_THREADS (FAST_WAVES * 64)
 
 // HACT: activation after every hidden layer, LACT: after the last layer,
-// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT; `false` / `true` still spell the first two) -- all
+// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT / SHAPE_LIK_NEGBIN; `false` / `true` still spell the first two) -- all
 // compile-time so the tile body is one straight-line block the scheduler can interleave.
 // Round 6: network.add takes any sequence of layers and activations (tensorBNN/network.py:173-191) -- a stack whose hidden layers do NOT all
 // carry the same activation has HACT = TBNN_ACT_PACKED | sum_l act_l << 3 l (hidden layer l = 0 .. NL - 2; at most 9 of them: fused_ops.hpp,
@@ -40,11 +40,14 @@ struct Shape {
     static constexpr int NL = sizeof...(Ds) - 1;
     static constexpr int D[sizeof...(Ds)] = {Ds...};
     static constexpr int HCODE = HACT_, LACT = LACT_, LIK = LIK_;
-    static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT, POIS = (LIK_ & 3) == SHAPE_LIK_POIS,
-                          WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0, STUD = (LIK_ & SHAPE_LIK_STUDENT) != 0;
+    // (bit 8 is SHAPE_LIK_STUDENT on the Gaussian code and SHAPE_LIK_NEGBIN on the Poisson code: POIS is the plain Poisson term only)
+    static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT,
+                          POIS = (LIK_ & (3 | SHAPE_LIK_NEGBIN)) == SHAPE_LIK_POIS, NEGB = (LIK_ & (3 | SHAPE_LIK_NEGBIN)) == (SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN),
+                          WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0, STUD = (LIK_ & (3 | SHAPE_LIK_STUDENT)) == (SHAPE_LIK_GAUSS | SHAPE_LIK_STUDENT);
     static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & ~(3 | SHAPE_LIK_WEIGHTED | SHAPE_LIK_STUDENT)) == 0, "unknown likelihood code");
-    static_assert(!STUD || (LIK_ & 3) == SHAPE_LIK_GAUSS, "Student-t is a flag on the Gaussian family (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS)");
-    static_assert(!POIS || LACT_ == TBNN_ACT_NONE, "Poisson: the last layer's output is the log-rate (no last activation)");
+    static_assert((LIK_ & SHAPE_LIK_STUDENT) == 0 || STUD || NEGB,
+                  "bit 8 is a flag on the Gaussian code (Student-t: SHAPE_LIK_STUDENT) and on the Poisson code (negative binomial: SHAPE_LIK_NEGBIN)");
+    static_assert(!(POIS || NEGB) || LACT_ == TBNN_ACT_NONE, "Poisson, negative binomial: the last layer's output is the log-rate (no last activation)");
     static_assert(!CAT || (LACT_ == TBNN_ACT_NONE && D[NL] >= 2), "categorical: logits (no last activation), at least 2 outputs");
     static_assert((HACT_ & TBNN_ACT_PACKED) == 0 || NL - 1 <= 9, "a packed activation code holds 9 hidden layers");
     static constexpr int act(int l) { return l == NL - 1 ? LACT_ : ((HACT_ & TBNN_ACT_PACKED) ? (HACT_ >> (3 * l)) & 7 : HACT_); }
@@ -592,16 +595,25 @@ struct LastRegs {
     float accb[O];
 };
 
-// the scale of the squared residual a kernel derives in its prologue: 1 / s^2 of the Gaussian kinds; a Student-t instantiation: 1 / (nu s^2)
+// the scale of the squared residual a kernel derives in its prologue: 1 / s^2 of the Gaussian kinds; a Student-t instantiation: 1 / (nu s^2);
+// a negative-binomial one: log r, which it subtracts from the log-rate (common.hpp: negbin_term; the library logf, once per thread)
 template <class S>
 __device__ __forceinline__ float lik_inv_var(const NetDev& nd, float sigma) {
     if constexpr (S::STUD) return 1.f / (nd.lik_df * sigma * sigma);
+    else if constexpr (S::NEGB) return logf(nd.lik_df);
     else return 1.f / (sigma * sigma);
+}
+// the second constant of the prologue: nu + 1 (Student-t: the delta's factor; not read by the other kinds); a negative-binomial
+// instantiation: r itself
+template <class S>
+__device__ __forceinline__ float lik_np1(const NetDev& nd) {
+    if constexpr (S::NEGB) return nd.lik_df;
+    else return nd.lik_df + 1.f;
 }
 
 // likelihood for one output value: statistic (counted when `count`), returns dL/df * act'.  A weighted instantiation scales the
 // residual / the row's term and its derivative by the row weight `wt` before either enters a sum: weight 1 gives the unweighted bits.
-// inv_var: lik_inv_var; np1: nu + 1, read by a Student-t instantiation only.
+// inv_var: lik_inv_var; np1: lik_np1, read by a Student-t or negative-binomial instantiation only.
 template <class S>
 __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat, float wt = 1.f, float np1 = 0.f) {
     static_assert(!S::CAT, "the categorical likelihood couples a row's outputs: cat_delta4 on the MFMA output tile, no per-element path");
@@ -633,6 +645,19 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
         } else {
             if (count) stat += (double)term;
             da = res;
+        }
+    } else if constexpr (S::NEGB) {
+        // TBNN_LIK_NEG_BINOMIAL: fi is the log of the mean, inv_var holds log r and np1 holds r (lik_inv_var, lik_np1); the term
+        // y log p + r log q and dL/df = y q - r p in the stable form of negbin_term (common.hpp; not contracted)
+#pragma clang fp contract(off)
+        float term;
+        const float d = negbin_term(fi, yy, np1, inv_var, &term);
+        if constexpr (S::WTD) {
+            if (count) stat += (double)(wt * term);
+            da = wt * d;
+        } else {
+            if (count) stat += (double)term;
+            da = d;
         }
     } else if constexpr (S::STUD) {
         // TBNN_LIK_STUDENT_T: u = r^2 / (nu s^2); the term log1p(u) (its factor -(nu + 1) / 2 and the constant: data_logp, kernels_hmc.hpp) and
@@ -904,7 +929,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     for (int t = 0; t < C::DW_TILES; ++t) dW[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float sigma = lik_sigma(nd, eta);
     const float inv_var = lik_inv_var<S>(nd, sigma);
-    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
+    const float np1 = lik_np1<S>(nd);                     // (Student-t: the delta's factor; negative binomial: r; not read otherwise)
     double stat = 0.0;
     constexpr int d_in = C::in(0), d_out = C::out(C::NL - 1);
     const long ntiles = (n + 15) / 16;

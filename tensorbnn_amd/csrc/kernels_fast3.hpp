@@ -1514,7 +1514,7 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     for (int t = 0; t < C::FP_REGS; ++t) FP[t] = 0.f;
     const float sigma = lik_sigma(nd, eta);
     const float inv_var = lik_inv_var<S>(nd, sigma);
-    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
+    const float np1 = lik_np1<S>(nd);                     // (Student-t: the delta's factor; negative binomial: r; not read otherwise)
     double stat = 0.0;
 
     if (g == 0) wl[C::aoff3(0) + d_in * C::PR + i16] = 1.f;

@@ -14,7 +14,7 @@
 // Math restated from the reference: dense W@a+b layer.py:278, activations
 // activationFunctions.py:36/49/62, Gaussian residual likelihood.py:88-94 +
 // BNN_functions.py:23-32, Bernoulli likelihood.py:226-236, categorical (softmax over a row's outputs:
-// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T); reverse mode per
+// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T), negative binomial (TBNN_LIK_NEG_BINOMIAL); reverse mode per
 // SURVEY.md A12 (TF autodiff has no source in the tree).
 #pragma once
 #include "common.hpp"
@@ -118,6 +118,13 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
                     // log1pf and IEEE division
                     const float r = y - fi, ns2 = nd.lik_df * sigma * sigma;
                     if (valid) { stat += (double)(wt * log1pf(r * r / ns2)); da = wt * ((nd.lik_df + 1.f) * r / (ns2 + r * r)); }
+                } else if (nd.lik == TBNN_LIK_NEG_BINOMIAL) {
+                    // fi is the log of the mean, t = f - log r, p = sigmoid(t): y log p + r log q (the constant: data_logp), dL/df = y q - r p, in
+                    // the stable form of negbin_term (common.hpp) with the library expf / log1pf / logf and an IEEE division
+                    const float rr = nd.lik_df, t = fi - logf(rr), e = expf(-fabsf(t)), l = log1pf(e);
+                    const float big = 1.f / (1.f + e), small = e / (1.f + e);
+                    const float p = t >= 0.f ? big : small, qq = t >= 0.f ? small : big;
+                    if (valid) { stat += (double)(wt * -(y * (fmaxf(-t, 0.f) + l) + rr * (fmaxf(t, 0.f) + l))); da = wt * (y * qq - rr * p); }
                 } else {
                     const float r = y - fi;
                     const float wr = wt * r;

@@ -117,21 +117,25 @@ __global__ __launch_bounds__(256) void k_shard_unpack(int P, const double* __res
     if (j == 0) stat_red[0] = buf[P];
 }
 
-// Poisson targets at data staging (TBNN_LIK_POISSON): the constant C = sum_i w_i sum_k lgamma(y_ik + 1) of the log-probability, which the
-// fused kernels leave out of their statistic (no lgamma in the hot loop), and the count of targets that are not finite and >= 0 (the
-// staging call refuses the data then).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and counts out[2 b + 1]) the
-// host adds in block order: the same bits from run to run.  w: one weight per row, null: weight 1.
+// Count targets at data staging (TBNN_LIK_POISSON, TBNN_LIK_NEG_BINOMIAL): the constant C of the log-probability, which the fused kernels
+// leave out of their statistic (no lgamma in the hot loop) -- Poisson (r = 0): C = sum_i w_i sum_k lgamma(y_ik + 1); negative binomial
+// (r > 0, the dispersion): C = sum_i w_i sum_k (lgamma(y_ik + 1) + lgamma(r) - lgamma(y_ik + r)) -- and the count of targets that are not
+// finite and >= 0 (the staging call refuses the data then).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and
+// counts out[2 b + 1]) the host adds in block order: the same bits from run to run.  w: one weight per row, null: weight 1.
 #define LIKC_BLOCKS 64
 __global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y, const float* __restrict__ w, long n, int d_out,
-                                                     double* __restrict__ out) {
+                                                     double* __restrict__ out, double r) {
     __shared__ double red[4];
     double c = 0.0, bad = 0.0;
     const long nel = n * d_out;
+    const double lgr = r > 0.0 ? lgamma(r) : 0.0;
     for (long el = (long)blockIdx.x * 256 + threadIdx.x; el < nel; el += (long)LIKC_BLOCKS * 256) {
         const float y = Y[el];
         if (!(y >= 0.f && y < INFINITY)) { bad += 1.0; continue; }
         const double wt = w ? (double)w[el / d_out] : 1.0;
-        c += wt * lgamma((double)y + 1.0);
+        double t = lgamma((double)y + 1.0);
+        if (r > 0.0) t += lgr - lgamma((double)y + r);
+        c += wt * t;
     }
     c = block_sum(c, red);
     bad = block_sum(bad, red);
@@ -155,9 +159,11 @@ __global__ __launch_bounds__(256) void k_make_image(int P, const float* __restri
 }
 
 // data-term log-likelihood from the reduced statistic; n: the rows that normalise the Gaussian (their count, or W = sum of the row weights);
-// lik_c: Poisson's constant C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (tbnn_api.hip: stage_lik_const; 0 otherwise)
+// lik_c: the constant C of the Poisson / negative-binomial log-probability over the staged rows (k_pois_const; tbnn_api.hip:
+// stage_lik_const; 0 otherwise)
 __device__ __forceinline__ double data_logp(const NetDev& nd, const float* __restrict__ eta, double stat, double n, double lik_c) {
     if (nd.lik == TBNN_LIK_POISSON) return stat - lik_c;                                   // the statistic is sum w (y f - e^f)
+    if (nd.lik == TBNN_LIK_NEG_BINOMIAL) return stat - lik_c;                              // ... sum w (y log p + r log q)
     if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
     if (nd.lik == TBNN_LIK_STUDENT_T) {
         // the statistic is sum w log1p(r^2 / (nu s^2)): n d_out c(nu, s) - (nu + 1) / 2 stat,

@@ -365,7 +365,7 @@ __device__ __forceinline__ float lay_poisson(float fi, float y, double& stat, fl
 }
 
 // likelihood (restated as in kernels_generic.hpp): statistic (Gaussian: sum of squared residuals; Bernoulli, categorical, Poisson: log-prob;
-// Student-t: sum of log1p(r^2 / (nu s^2))) and
+// Student-t: sum of log1p(r^2 / (nu s^2)); negative binomial: sum of y log p + r log q) and
 // dz of the last layer = dL/df * act'(f).  f, dz: blocks [row tile][TMl][16][16]; one thread per data row.  Only the real
 // (row, output) entries of dz are written: the padding was zeroed when the store was allocated and nothing else writes it.
 // wrow: one weight per row (tbnn_set_row_weights), null: weight 1 -- a row's residual / term and its dz are scaled by it before any sum.
@@ -375,6 +375,7 @@ __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restr
     const float sigma = lik_sigma(nd, eta);
     const float inv_var = 1.f / (sigma * sigma);
     const float st_k = 1.f / (nd.lik_df * sigma * sigma), st_np1 = nd.lik_df + 1.f;      // Student-t alone reads them (common.hpp: student_elem)
+    const float nb_lr = nd.lik == TBNN_LIK_NEG_BINOMIAL ? logf(nd.lik_df) : 0.f;           // negative binomial: log r (common.hpp: negbin_elem)
     const int lact = nd.act[nd.nl - 1];
     double stat = 0.0;
     if (nd.lik == TBNN_LIK_CATEGORICAL) {
@@ -420,6 +421,8 @@ __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restr
                 da = lay_poisson(fi, y, stat, wt);
             } else if (nd.lik == TBNN_LIK_STUDENT_T) {
                 da = student_elem(fi, y, stat, wt, st_k, st_np1);
+            } else if (nd.lik == TBNN_LIK_NEG_BINOMIAL) {
+                da = negbin_elem(fi, y, stat, wt, nd.lik_df, nb_lr);
             } else {
                 const float res = y - fi;                                   // likelihood.py:88-94
                 const float wr = wt * res;
@@ -552,6 +555,7 @@ __global__ __launch_bounds__(256) void k_lay_tail(NetDev nd, LayPlan p, const fl
     const float sigma = lik_sigma(nd, eta);
     const float inv_var = 1.f / (sigma * sigma);
     const float st_k = 1.f / (nd.lik_df * sigma * sigma), st_np1 = nd.lik_df + 1.f;      // Student-t alone reads them (common.hpp: student_elem)
+    const float nb_lr = nd.lik == TBNN_LIK_NEG_BINOMIAL ? logf(nd.lik_df) : 0.f;           // negative binomial: log r (common.hpp: negbin_elem)
     const int nl = p.nl, l0 = p.l0, lact = nd.act[nl - 1], lane_off = i16 * 16 + 4 * g;
     double stat = 0.0;
     for (long rt = (long)blockIdx.x * 4 + wave; rt < p.ntiles; rt += (long)gridDim.x * 4) {
@@ -631,6 +635,8 @@ __global__ __launch_bounds__(256) void k_lay_tail(NetDev nd, LayPlan p, const fl
                             da = lay_poisson(fi, y, stat, wt);
                         } else if (nd.lik == TBNN_LIK_STUDENT_T) {
                             da = student_elem(fi, y, stat, wt, st_k, st_np1);
+                        } else if (nd.lik == TBNN_LIK_NEG_BINOMIAL) {
+                            da = negbin_elem(fi, y, stat, wt, nd.lik_df, nb_lr);
                         } else {
                             const float res = y - fi;                                  // likelihood.py:88-94
                             const float wr = wt * res;
@@ -699,6 +705,7 @@ __global__ __launch_bounds__(256) void k_lay_last(NetDev nd, LayPlan p, const fl
     const float sigma = lik_sigma(nd, eta);
     const float inv_var = 1.f / (sigma * sigma);
     const float st_k = 1.f / (nd.lik_df * sigma * sigma), st_np1 = nd.lik_df + 1.f;      // Student-t alone reads them (common.hpp: student_elem)
+    const float nb_lr = nd.lik == TBNN_LIK_NEG_BINOMIAL ? logf(nd.lik_df) : 0.f;           // negative binomial: log r (common.hpp: negbin_elem)
     const int L = p.nl - 1, lact = nd.act[L], lane_off = i16 * 16 + 4 * g;
     const int KG = p.TK[L], wp = 16 * KG, MTp = p.TM[L - 1], outp = nd.out[L - 1], actp = nd.act[L - 1];
     // the weights, once per wave: W_L rows (A operand of the forward tile) and W_L^T (A operand of the delta step; its k dimension is the
@@ -764,6 +771,8 @@ __global__ __launch_bounds__(256) void k_lay_last(NetDev nd, LayPlan p, const fl
                         da = lay_poisson(fi, y, stat, wt);
                     } else if (nd.lik == TBNN_LIK_STUDENT_T) {
                         da = student_elem(fi, y, stat, wt, st_k, st_np1);
+                    } else if (nd.lik == TBNN_LIK_NEG_BINOMIAL) {
+                        da = negbin_elem(fi, y, stat, wt, nd.lik_df, nb_lr);
                     } else {
                         const float res = y - fi;                                  // likelihood.py:88-94
                         const float wr = wt * res;

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
     TALL_STAMP(17);
     const float sigma = FWD ? 1.f : lik_sigma(nd, eta);
     const float inv_var = lik_inv_var<S>(nd, sigma);
-    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
+    const float np1 = lik_np1<S>(nd);                     // (Student-t: the delta's factor; negative binomial: r; not read otherwise)
     double stat = 0.0;
     f32x4 dW0[FWD ? 1 : MT0 * CH];
     f32x4 dWm[(FWD || C::DWM_TILES == 0) ? 1 : C::DWM_TILES];

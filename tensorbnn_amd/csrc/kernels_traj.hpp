@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
     }
     const float sigma = lik_sigma(nd, eta);
     const float inv_var = lik_inv_var<S>(nd, sigma);
-    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
+    const float np1 = lik_np1<S>(nd);                     // (Student-t: the delta's factor; negative binomial: r; not read otherwise)
     const float sg = nd.lik == TBNN_LIK_GAUSSIAN ? sigma : 1.f;
     __syncthreads();
     if (gq == 0) wl[C::aoff3(0) + d_in * C::PR + i16] = 1.f;

@@ -429,7 +429,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
 
     const float sigma = FWD ? 1.f : lik_sigma(nd, eta);
     const float inv_var = lik_inv_var<S>(nd, sigma);
-    const float np1 = nd.lik_df + 1.f;                    // (Student-t: the delta's factor; not read otherwise)
+    const float np1 = lik_np1<S>(nd);                     // (Student-t: the delta's factor; negative binomial: r; not read otherwise)
     double stat = 0.0;
     f32x4 dW0[C::DW0_TILES];
 #pragma unroll

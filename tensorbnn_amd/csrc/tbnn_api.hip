@@ -104,7 +104,8 @@ struct tbnn_ctx {
     // the degrees of freedom tbnn_ensemble_loglik / tbnn_ensemble_loo judge under TBNN_LIK_STUDENT_T with on a handle of another likelihood
     // (tbnn_set_lik_df; 0: not set -- a Student-t handle's own are nd.lik_df)
     float ens_df = 0.f;
-    // TBNN_LIK_POISSON: C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (stage_lik_const; all chains share it); 0 otherwise
+    // TBNN_LIK_POISSON: C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (stage_lik_const; all chains share it); TBNN_LIK_NEG_BINOMIAL:
+    // ... (lgamma(y_ik + 1) + lgamma(r) - lgamma(y_ik + r)); 0 otherwise
     double lik_c = 0.0;
     int want = TBNN_KERNEL_AUTO;          // tbnn_net_desc::kernel (the re-selection of tbnn_set_row_weights follows it)
     // validation data (network.py:47-51) and the prediction buffer of tbnn_predict / tbnn_metrics
@@ -161,8 +162,12 @@ extern "C" int tbnn_device_count(void) {
 }
 
 // the TBNN_LIK_* values (4, 6 and 7 are not among them: include/tbnn.h)
-static bool lik_known(int lik) { return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON || lik == TBNN_LIK_STUDENT_T; }
-// degrees of freedom a Student-t term can be formed with
+static bool lik_known(int lik) {
+    return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON || lik == TBNN_LIK_STUDENT_T || lik == TBNN_LIK_NEG_BINOMIAL;
+}
+// the count likelihoods: targets finite and >= 0, the last layer's output a log-rate, the constant of stage_lik_const
+static bool lik_counts(int lik) { return lik == TBNN_LIK_POISSON || lik == TBNN_LIK_NEG_BINOMIAL; }
+// degrees of freedom a Student-t term can be formed with (and a dispersion a negative-binomial one can)
 static bool df_ok(float df) { return df > 0.f && df < INFINITY; }
 
 static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
@@ -191,6 +196,11 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
         if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
             return fail(-1, "the categorical likelihood takes the last layer's outputs as logits: the last layer must carry no activation");
     }
+    if (d->likelihood == TBNN_LIK_NEG_BINOMIAL) {
+        if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
+            return fail(-1, "the negative-binomial likelihood takes the last layer's outputs as log-rates (log link): the last layer must carry no activation");
+        if (!df_ok(d->lik_df)) return fail(-1, "the negative-binomial likelihood needs lik_df (its dispersion r) finite and > 0");
+    }
     nd.P = off;
     nd.lik = d->likelihood;
     nd.H = 4 * nd.nl + (nd.lik == TBNN_LIK_GAUSSIAN ? 1 : 0);
@@ -203,6 +213,7 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
         if (!df_ok(d->lik_df)) return fail(-1, "the Student-t likelihood needs lik_df (its degrees of freedom) finite and > 0");
         nd.lik_df = d->lik_df;
     }
+    if (nd.lik == TBNN_LIK_NEG_BINOMIAL) nd.lik_df = d->lik_df;
     return 0;
 }
 
@@ -432,15 +443,16 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
     return 0;
 }
 
-// Poisson (TBNN_LIK_POISSON; any other likelihood: C = 0, nothing runs): the constant C of the n rows dY (device) under the row weights dw
+// Poisson and negative binomial (TBNN_LIK_POISSON, TBNN_LIK_NEG_BINOMIAL; any other likelihood: C = 0, nothing runs): the constant C of the n rows dY (device) under the row weights dw
 // (device, null: none) -- k_pois_const, its partials added here in block order -- and the refusal of targets that are not counts.  Called
 // by everything that stages rows or weights BEFORE it changes the handle: a refusal leaves the handle as it was.
 static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY, const float* dw, long n, double* C) {
     *C = 0.0;
-    if (h->nd.lik != TBNN_LIK_POISSON) return 0;
+    if (!lik_counts(h->nd.lik)) return 0;
+    const bool nb = h->nd.lik == TBNN_LIK_NEG_BINOMIAL;
     Buf<double> part;
     HIPCHK(part.alloc(2 * LIKC_BLOCKS));
-    hipLaunchKernelGGL(k_pois_const, dim3(LIKC_BLOCKS), dim3(256), 0, h->stream, dY, dw, n, h->nd.d_out, (double*)part);
+    hipLaunchKernelGGL(k_pois_const, dim3(LIKC_BLOCKS), dim3(256), 0, h->stream, dY, dw, n, h->nd.d_out, (double*)part, nb ? (double)h->nd.lik_df : 0.0);
     HIPCHK(hipGetLastError());
     double host[2 * LIKC_BLOCKS];
     HIPCHK(hipMemcpyAsync(host, part, sizeof(host), hipMemcpyDeviceToHost, h->stream));
@@ -448,7 +460,7 @@ static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY,
     double c = 0.0, bad = 0.0;
     for (int b = 0; b < LIKC_BLOCKS; ++b) { c += host[2 * b]; bad += host[2 * b + 1]; }
     if (bad > 0.0)
-        return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are negative or not finite: the Poisson likelihood takes counts (finite, >= 0)");
+        return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are negative or not finite: the " + (nb ? "negative-binomial" : "Poisson") + " likelihood takes counts (finite, >= 0)");
     *C = c;
     return 0;
 }
@@ -482,7 +494,7 @@ extern "C" int tbnn_set_data(tbnn_handle h, const float* X, const float* Y, int6
     const size_t nx = (size_t)n * h->nd.d_in, ny = (size_t)n * h->nd.d_out;
     double C = 0.0;
     Buf<float> newY;
-    if (h->nd.lik == TBNN_LIK_POISSON) {
+    if (lik_counts(h->nd.lik)) {
         // the targets are staged and judged first: refused ones leave the handle with the rows it had
         HIPCHK(newY.alloc(ny));
         HIPCHK(hipMemcpy(newY, Y, ny * sizeof(float), hipMemcpyHostToDevice));
@@ -1116,6 +1128,7 @@ extern "C" int tbnn_hmc_step_each(tbnn_handle h, const float* eps, const int32_t
 extern "C" int tbnn_set_lik_df(tbnn_handle h, float df) {
     NEED(h);
     if (h->nd.lik == TBNN_LIK_STUDENT_T) return fail(-1, "set_lik_df: a Student-t handle takes its degrees of freedom from the descriptor's lik_df");
+    if (h->nd.lik == TBNN_LIK_NEG_BINOMIAL) return fail(-1, "set_lik_df: a negative-binomial handle takes its dispersion from the descriptor's lik_df");
     if (!df_ok(df)) return fail(-1, "set_lik_df: df must be finite and > 0");
     h->ens_df = df;
     return 0;

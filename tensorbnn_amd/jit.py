@@ -73,6 +73,7 @@ ACT_PACKED = 0x40000000          # csrc/common.hpp: TBNN_ACT_PACKED
 LIK_GAUSS, LIK_BERN, LIK_CAT, LIK_POIS = 0, 1, 2, 3      # csrc/common.hpp: SHAPE_LIK_* (the Gaussian family, Bernoulli, categorical, Poisson)
 LIK_WEIGHTED = 4                            # csrc/common.hpp: SHAPE_LIK_WEIGHTED -- the flag bit of kernels that take row weights
 LIK_STUDENT = 8                             # csrc/common.hpp: SHAPE_LIK_STUDENT -- the flag bit, on LIK_GAUSS, of the Student-t data term
+LIK_NEGBIN = 8                              # csrc/common.hpp: SHAPE_LIK_NEGBIN -- the same bit on LIK_POIS: the negative-binomial data term
 
 
 def lik_code(likelihood: int, weighted: bool = False) -> int:
@@ -80,7 +81,7 @@ def lik_code(likelihood: int, weighted: bool = False) -> int:
     weighted: | LIK_WEIGHTED (the kernels of a chain with row weights, Chain.set_row_weights)"""
     from . import _native as nat
     code = {nat.LIK_BERNOULLI: LIK_BERN, nat.LIK_CATEGORICAL: LIK_CAT, nat.LIK_POISSON: LIK_POIS,
-            nat.LIK_STUDENT_T: LIK_STUDENT | LIK_GAUSS}.get(int(likelihood), LIK_GAUSS)
+            nat.LIK_STUDENT_T: LIK_STUDENT | LIK_GAUSS, nat.LIK_NEG_BINOMIAL: LIK_NEGBIN | LIK_POIS}.get(int(likelihood), LIK_GAUSS)
     return code | (LIK_WEIGHTED if weighted else 0)
 
 
@@ -109,7 +110,7 @@ def families(dims, lik: int = LIK_GAUSS) -> list:
         return []                       # tbnn_create refuses the network (TBNN_MAX_LAYERS)
     # (the weighted bit changes no family's reach: a weighted narrow table only goes without the trajectory kernel, jit_narrow.hpp; nor does
     # the Poisson likelihood, an element-wise term like the Gaussian's: lik_delta, csrc/kernels_fast.hpp)
-    # (nor the Student-t flag: the Gaussian residual under another element-wise loss)
+    # (nor the Student-t / negative-binomial flag: the Gaussian residual, the Poisson log-rate under another element-wise loss)
     if lik & ~(LIK_WEIGHTED | LIK_STUDENT) == LIK_CAT:
         # the categorical likelihood couples a row's outputs: only the MFMA output tile of the mid, tall and wide kernels carries it
         # (csrc/kernels_fast.hpp: cat_delta4) -- 3 .. 16 outputs; the narrow family, its trajectory kernel and the VALU last layer
@@ -276,7 +277,8 @@ def tall_usage(dims) -> dict:
 def source(dims, hact, lact, lik, family) -> str:
     # (the unweighted codes keep their spelling: the same source, the same library as before the weighted bit)
     lik_arg = {LIK_GAUSS: "false", LIK_BERN: "true", LIK_CAT: "SHAPE_LIK_CAT", LIK_POIS: "SHAPE_LIK_POIS", LIK_STUDENT: "SHAPE_LIK_STUDENT",
-               LIK_STUDENT | LIK_WEIGHTED: "SHAPE_LIK_STUDENT | SHAPE_LIK_WEIGHTED"}.get(int(lik), str(int(lik)))
+               LIK_STUDENT | LIK_WEIGHTED: "SHAPE_LIK_STUDENT | SHAPE_LIK_WEIGHTED", LIK_POIS | LIK_NEGBIN: "SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN",
+               LIK_POIS | LIK_NEGBIN | LIK_WEIGHTED: "SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN | SHAPE_LIK_WEIGHTED"}.get(int(lik), str(int(lik)))
     shape = f"Shape<{hact}, {lact}, {lik_arg}, {', '.join(map(str, dims))}>"
     if family == "wide":
         return (f'#include "{CSRC}/jit_wide.hpp"\nusing S = {shape};\n'

@@ -163,3 +163,40 @@ class StudentTLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+class NegativeBinomialLikelihood(Likelihood):
+    """Over-dispersed counts: as PoissonLikelihood, the last dense layer's outputs (no activation after it) are the LOGS of the means, and
+    each count is negative binomial with mean mu = exp(f) and variance mu + mu^2 / dispersion (dispersion -> inf: Poisson).  Per
+    (row, output), p = mu / (dispersion + mu):
+    log p(y | f) = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y log p + r log(1 - p)  (include/tbnn.h TBNN_LIK_NEG_BINOMIAL), targets
+    y >= 0 (non-integers allowed).  A row's pull on the fit, r (y - mu) / (r + mu), is bounded by r from below however large the rate.
+    No hyper-parameter: the dispersion is fixed (NegativeBinomialLikelihood(dispersion=r))."""
+    kind = nat.LIK_NEG_BINOMIAL
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.dispersion = float(kwargs["dispersion"])
+        if not (self.dispersion > 0 and math.isfinite(self.dispersion)):
+            raise ValueError("NegativeBinomialLikelihood needs dispersion > 0 and finite")
+        self.mainProbsInHypers = False
+
+    def logDensity(self, f, y):
+        """the log density of the counts y at log-means f, element by element in float64, in the form the kernels use: with
+        t = f - log r, -log p = max(-t, 0) + log1p(e^-|t|) and -log(1 - p) = max(t, 0) + log1p(e^-|t|)"""
+        r = self.dispersion
+        lg = np.vectorize(math.lgamma, otypes=[np.float64])
+        f = np.asarray(f, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        t = f - math.log(r)
+        l = np.log1p(np.exp(-np.abs(t)))
+        return (lg(y + r) - math.lgamma(r) - lg(y + 1.0)) - (y * (np.maximum(-t, 0.0) + l) + r * (np.maximum(t, 0.0) + l))
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """the log density per (output, row) in float64, [d_out, rows] as PoissonLikelihood's; the sum is the data term"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [d_out, rows]: log-means
+        y = np.asarray(kwargs["realVals"], dtype=np.float64).reshape(-1, f.shape[0]).T
+        return self.logDensity(f, y)
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

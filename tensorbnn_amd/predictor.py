@@ -135,8 +135,8 @@ class predictor(object):
     def _data_logprob(self, likelihood, trainX, trainY, n):
         """summed log-likelihood of the training rows under every n-th network (see the module docstring)"""
         from .layer import _multivariate_log_prob
-        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, PoissonLikelihood, StudentTLikelihood,
-                                 log_softmax)
+        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, NegativeBinomialLikelihood,
+                                 PoissonLikelihood, StudentTLikelihood, log_softmax)
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
@@ -146,9 +146,9 @@ class predictor(object):
             if isinstance(likelihood, CategoricalLikelihood):
                 out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
                 continue
-            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood)):
+            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood, NegativeBinomialLikelihood)):
                 terms = likelihood.makeResponseLikelihood(None, predict=lambda *_a, _f=cur.T: _f, realVals=real)
-                out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1) / of the t log densities
+                out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1) / of the t / negative-binomial log densities
                 continue
             if isinstance(likelihood, BernoulliLikelihood):
                 out.append(np.float32(0))                                       # likelihood.py:239-243
@@ -166,10 +166,10 @@ class predictor(object):
 
     def _transform(self, transform):
         """the name of the transform asked for; None: the one the predictor's likelihood implies"""
-        from .likelihood import CategoricalLikelihood, PoissonLikelihood
+        from .likelihood import CategoricalLikelihood, NegativeBinomialLikelihood, PoissonLikelihood
         if transform is None:
             transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
-                         "exp" if isinstance(self.likelihood, PoissonLikelihood) else "none")
+                         "exp" if isinstance(self.likelihood, (PoissonLikelihood, NegativeBinomialLikelihood)) else "none")
         if transform not in self._TRANSFORMS:
             raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
         return transform
@@ -195,10 +195,13 @@ class predictor(object):
         """Posterior-predictive mean and population variance of every n-th network's predictions, (mean, var) as float64 [d_out, rows],
         reduced on the device: only the two results cross to the host.  Per value t = transform(f) * sd + mean (the de-normalisation of
         the metrics).  transform None: softmax under a CategoricalLikelihood -- class probabilities averaged over the posterior, not
-        averaged logits --, exp under a PoissonLikelihood -- the posterior mean and variance of the RATE -- and none otherwise; "exp" /
-        "sigmoid" / "softmax" / "none" override.  weights: one per picked network, e.g. what reweight returns.  countVariance (with the
-        exp transform, sd = 1, mean = 0): the second array is the total predictive variance of a COUNT, E[rate] + Var[rate] (the Poisson
-        noise plus the posterior spread of the rate), added on the host to the two arrays the device returns."""
+        averaged logits --, exp under a PoissonLikelihood or NegativeBinomialLikelihood -- the posterior mean and variance of the RATE --
+        and none otherwise; "exp" / "sigmoid" / "softmax" / "none" override.  weights: one per picked network, e.g. what reweight
+        returns.  countVariance (with the exp transform, sd = 1, mean = 0): the second array is the total predictive variance of a
+        COUNT, E[rate] + Var[rate] (the Poisson noise plus the posterior spread of the rate) -- under a NegativeBinomialLikelihood
+        E[rate] + Var[rate] + E[rate^2] / dispersion, E[rate^2] = Var[rate] + E[rate]^2 --, added on the host to the two arrays the
+        device returns."""
+        from .likelihood import NegativeBinomialLikelihood
         transform = self._transform(transform)
         if countVariance and (transform != "exp" or float(sd) != 1.0 or float(mean) != 0.0):
             raise ValueError("countVariance needs the rate itself: transform 'exp' (the default under a PoissonLikelihood), sd = 1, mean = 0")
@@ -206,6 +209,8 @@ class predictor(object):
         ch = self._ensure_chain()
         m, v = ch.ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=self._TRANSFORMS[transform],
                                    scale=float(sd), shift=float(mean))
+        if countVariance and isinstance(self.likelihood, NegativeBinomialLikelihood):
+            return m, m + v + (v + m * m) / self.likelihood.dispersion
         return (m, m + v) if countVariance else (m, v)
 
     def predictQuantiles(self, inputMatrix, probs, n=1, weights=None, transform=None, sd=1.0, mean=0.0, method=None):
@@ -357,8 +362,12 @@ class predictor(object):
         """the standard deviation of every n-th network under a Gaussian kind of likelihood, float32 [picked]: the fixed sd, or each
         network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; the scale of a StudentTLikelihood; None
         for the other likelihoods"""
-        from .likelihood import FixedGaussianLikelihood, StudentTLikelihood
+        from .likelihood import FixedGaussianLikelihood, NegativeBinomialLikelihood, StudentTLikelihood
         picked = len(range(0, self.numNetworks, n))
+        if isinstance(lik, NegativeBinomialLikelihood):
+            # no scale; its dispersion set on the forward chain (a fixed-sd Gaussian handle) before the reduction that judges under it
+            self._ensure_chain().set_lik_df(lik.dispersion)
+            return None
         if isinstance(lik, StudentTLikelihood):
             # its scale, one per network as the fixed sd -- and its degrees of freedom set on the forward chain (a fixed-sd Gaussian handle)
             # before the reduction that judges under it
@@ -387,17 +396,18 @@ class predictor(object):
         [n_probs, d_out, rows] (a scalar `probs`: [d_out, rows]): the mixture over every n-th network of the observation model around
         its prediction, inverted on the device -- under a Gaussian kind of likelihood N(f_i, s_i^2) with s_i the network's own standard
         deviation (its saved last hyper as logPredictiveDensity reads it, or the fixed sd), under a PoissonLikelihood the counts'
-        Poisson(exp(f_i)), whose quantile is the smallest count k with F(k) >= p.  likelihood None: the predictor's own.  weights: one
+        Poisson(exp(f_i)) and under a NegativeBinomialLikelihood their negative binomial of mean exp(f_i) and the likelihood's
+        dispersion, whose quantile is the smallest count k with F(k) >= p.  likelihood None: the predictor's own.  weights: one
         per picked network, e.g. what reweight returns.  The result is q * sd + mean, the de-normalisation of the metrics, applied on
         the host in fp64: sd > 0, and counts take none (sd = 1, mean = 0).  predictQuantiles gives the credible quantiles of the
         network's output instead; Bernoulli and categorical likelihoods are refused (predictMoments returns a label's probability)."""
-        from .likelihood import PoissonLikelihood
+        from .likelihood import NegativeBinomialLikelihood, PoissonLikelihood
         lik = self._predictive_likelihood(likelihood)
         sd, mean = float(sd), float(mean)
         if not sd > 0.0:
             raise ValueError("sd must be > 0 (a negative scale would turn the quantiles round)")
-        if isinstance(lik, PoissonLikelihood) and (sd != 1.0 or mean != 0.0):
-            raise ValueError("counts are not de-normalised: sd = 1, mean = 0 under a PoissonLikelihood")
+        if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) and (sd != 1.0 or mean != 0.0):
+            raise ValueError("counts are not de-normalised: sd = 1, mean = 0 under a PoissonLikelihood or NegativeBinomialLikelihood")
         picked, w = self._picked(n, weights)
         pr = np.asarray(probs, dtype=np.float64)
         ch = self._ensure_chain()
@@ -417,14 +427,15 @@ class predictor(object):
     def predictiveCDF(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
         """The PIT values of the rows: the predictive CDF of predictiveQuantiles at the observed targets realVals, float64 [d_out, rows]
         -- uniform on (0, 1) over held-out rows when the predictive distribution is calibrated.  Targets in the networks' own
-        (normalised) units.  Under a PoissonLikelihood the pair (F(y - 1), F(y)): a count's PIT value lies anywhere on its step."""
-        from .likelihood import PoissonLikelihood
+        (normalised) units.  Under a PoissonLikelihood or NegativeBinomialLikelihood the pair (F(y - 1), F(y)): a count's PIT value lies
+        anywhere on its step."""
+        from .likelihood import NegativeBinomialLikelihood, PoissonLikelihood
         lik = self._predictive_likelihood(likelihood)
         picked, w = self._picked(n, weights)
         ch = self._ensure_chain()
         _q, F, Fb = ch.ensemble_predictive(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
                                            likelihood=lik.kind, sd=self._network_sd(lik, n), weights=w)
-        return (Fb, F) if isinstance(lik, PoissonLikelihood) else F
+        return (Fb, F) if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) else F
 
     def _ensure_chain(self):
         if self._chain is None:
