@@ -1398,12 +1398,31 @@ struct Epi3 {
 };
 
 // 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4: lane i lands at lbase + 16 i; lbase is
-// wave-uniform).  The builtin exists in the device pass only; the host pass needs just the kernel's stub.
-__device__ __forceinline__ void lds_dma16(const float* gsrc, float* lbase) {
+// wave-uniform), for a transfer that stays in flight across LDS reads of OTHER addresses.  An asm statement, not
+// __builtin_amdgcn_global_load_lds: the compiler keeps no address ranges for an LDS transfer it can see and puts `s_waitcnt vmcnt(0)`
+// in front of the first LDS read that follows one, whatever that read's address (here: the first forward pass's operands, while the
+// W^T images are still on their way).  This form it does not see, so the CALLER owns the wait: `s_waitcnt vmcnt(0)` and a barrier
+// before anything reads the destination.  The compiler's own vmcnt waits stay correct, only later than needed: loads return in order,
+// and a count that leaves these out is reached after they have come back.
+// (m0 = the LDS byte address, as the builtin sets it; one wait state between the write of m0 and the transfer that reads it.  m0 is
+// the compiler's own register and cannot be named as clobbered: the statement puts back what it found.  The instruction exists in the
+// device pass only; the host pass needs just the kernel's stub.)
+__device__ __forceinline__ void lds_dma16_unseen(const float* gsrc, float* lbase) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(gsrc, lbase, 16, 0, 0);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"((unsigned)(size_t)lbase) : "memory");
 #else
     (void)gsrc; (void)lbase;
+#endif
+}
+// `s_waitcnt vmcnt(0)` as the builtin (gfx9 encoding: vmcnt 0, expcnt and lgkmcnt left at their maxima), not as an asm statement: the
+// compiler's own count of what is in flight takes it in.  An asm wait it does not see: a load it still held for pending on one path
+// (the last image piece is stored under a predicate) made it drain everything in front of the first MFMA that reuses the registers --
+// inside the tile loop, on every tile.
+__device__ __forceinline__ void wait_vmem_all() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
 #endif
 }
 
@@ -1414,6 +1433,9 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     float* __restrict__ slabs, int pitch, double* __restrict__ pstat, unsigned long long* __restrict__ stamps, ChainStride cs)
 {
     using C = F3Cfg<S>;
+    // every argument the prologue's requests are made from, read here: one batch of scalar loads with one wait, in front of the
+    // branches below (the early exit, the stamp), each of which otherwise gets a group of loads and a wait of its own
+    asm volatile("" :: "s"(cs.ctl), "s"(cs.t), "s"(cs.img), "s"(stamps), "s"(qimg), "s"(X), "s"(Y), "s"(n), "s"(gridDim.x));
     // gridDim.y = chains of a multi-chain handle (tbnn_create_multi): this workgroup's chain
     if (chain_done(cs.ctl, cs.t, blockIdx.y)) return;           // a chain past its own L (per-chain step control)
     qimg += (size_t)blockIdx.y * cs.img; eta += (size_t)blockIdx.y * cs.eta; slabs += (size_t)blockIdx.y * cs.slab; pstat += (size_t)blockIdx.y * PSTAT_CAP;
@@ -1433,8 +1455,8 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     const long ntiles = (n + 15) / 16;
     const long W = (long)gridDim.x * FAST_WAVES;
     const long wg = (long)blockIdx.x * FAST_WAVES + wave;
-    // the rows of this wave's first tile (and of the cooperative tiles) are requested before anything else: their HBM
-    // latency (the first tile took 7.5 us instead of 6.1) hides under the prologue's image loads
+    // the rows of this wave's first tile are requested before anything else: their HBM latency (the first tile took 7.5 us
+    // instead of 6.1) hides under the prologue's image loads
     float xn[C::KS0], yn[d_out], wn = 1.f;
     auto fetch = [&](long tile) {
         const long row = tile * 16 + i16;
@@ -1448,6 +1470,20 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         for (int o = 0; o < d_out; ++o) yn[o] = ok ? Y[row * d_out + o] : 0.f;
         wn = row_weight<S>(Y, n, row, ok);
     };
+    // Request order of the prologue: what needs no arithmetic first -- this wave's first tile, then the W / bias images (needed at the
+    // first forward pass) -- and only then the tile split below, whose division used to run before a single request had left.
+    long tile = wg;
+    fetch(tile);
+    constexpr bool WTDMA = C::STATIC_FLOATS > C::WB_FLOATS;
+    // (the image is read with a clamped index, not a predicated load: a predicate made the compiler copy a register the loads in
+    // flight were still writing, and wait for all of them in the middle of the group; the store below keeps its bound)
+    constexpr int IMG_N4 = (WTDMA ? C::WB_FLOATS : C::STATIC_FLOATS) / 4, IMG_IT = (IMG_N4 + FAST_THREADS - 1) / FAST_THREADS;
+    f32x4 imgv[IMG_IT];
+#pragma unroll
+    for (int k = 0; k < IMG_IT; ++k) {
+        const int e = tid + k * FAST_THREADS;
+        imgv[k] = *reinterpret_cast<const f32x4*>(qimg + 4 * (e < IMG_N4 ? e : 0));
+    }
     // full rounds of W tiles run on the tile loop; a remainder of at most 2 tiles per workgroup runs as cooperative rounds
     // (Coop3), tile = main_end + round * gridDim.x + blockIdx.x
     long main_end = ntiles;
@@ -1457,6 +1493,33 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         if (rem > 0 && rem <= 2 * G) { main_end = ntiles - rem; ncoop = rem <= G ? 1 : 2; }
     }
     if constexpr ((TBNN_SKEL & 1) != 0) { main_end = 0; ncoop = 0; }       // diagnostic: the launch's fixed cost
+    {
+        // the zero fill of the per-wave images runs under the image loads' latency, then the LDS stores
+        __builtin_amdgcn_sched_barrier(0);
+        float4* z = reinterpret_cast<float4*>(wl);
+        for (int e = lane; e < C::WAVE3_FLOATS / 4; e += 64) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < IMG_IT; ++k) { const int e = tid + k * FAST_THREADS; if (e < IMG_N4) *reinterpret_cast<f32x4*>(lds + 4 * e) = imgv[k]; }
+        // every path meets a full wait here (the last piece's store, and with it its wait, is predicated): nothing is in flight but
+        // that piece, and the compiler enters the tile loop knowing so
+        wait_vmem_all();
+    }
+    __syncthreads();
+    // The W^T images (delta chain: needed from the first BACKWARD pass on) do not go through registers: each wave sends its
+    // share straight to LDS with global_load_lds (1 KB per instruction, no VGPRs held).  They leave HERE, behind the prologue's
+    // wait and barrier, so that no wait of the prologue covers them: the first tile's forward pass runs under them, and the wait +
+    // barrier that makes them visible sits behind it (wt_pending).  (Sent in front of the W / bias loads, as they were, their
+    // 34.8 KB came back first -- loads return in order -- and the prologue's wait for the W / bias image was a wait for them as
+    // well; and sent through the builtin they made the compiler wait for them before the first LDS read: lds_dma16_unseen.)
+    if constexpr (WTDMA) {
+        constexpr int WT = C::STATIC_FLOATS - C::WB_FLOATS, NCHUNK = (WT + 255) / 256;
+        static_assert(C::WB_FLOATS % 4 == 0 && WT % 4 == 0, "16-B pieces");
+        for (int c = wave; c < NCHUNK; c += FAST_WAVES) {
+            const int off = C::WB_FLOATS + c * 256;
+            if (c * 256 + lane * 4 < WT) lds_dma16_unseen(qimg + off + lane * 4, lds + off);
+        }
+    }
     // the cooperative tiles' rows are fetched now: their latency hides under the whole tile loop
     float xc[2][C::KS0], yc[2][d_out], wc[2];
 #pragma unroll
@@ -1473,36 +1536,6 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         for (int o = 0; o < d_out; ++o) yc[j][o] = ok ? Y[row * d_out + o] : 0.f;
         wc[j] = row_weight<S>(Y, n, row, ok);
     }
-    long tile = wg;
-    fetch(tile);
-    // The W^T images (delta chain: needed from the first BACKWARD pass on) do not go through registers: each wave sends its
-    // share straight to LDS with global_load_lds (1 KB per instruction, no VGPRs held), and the wait + barrier that makes
-    // them visible sits behind the first tile's forward pass -- the prologue proper stages the W / bias images only.
-    constexpr bool WTDMA = C::STATIC_FLOATS > C::WB_FLOATS;
-    if constexpr (WTDMA) {
-        constexpr int WT = C::STATIC_FLOATS - C::WB_FLOATS, NCHUNK = (WT + 255) / 256;
-        static_assert(C::WB_FLOATS % 4 == 0 && WT % 4 == 0, "16-B pieces");
-        for (int c = wave; c < NCHUNK; c += FAST_WAVES) {
-            const int off = C::WB_FLOATS + c * 256;
-            if (c * 256 + lane * 4 < WT) lds_dma16(qimg + off + lane * 4, lds + off);
-        }
-    }
-    {
-        // all image loads in flight first, the zero fill of the per-wave images under their latency, then the LDS stores
-        constexpr int N4 = (WTDMA ? C::WB_FLOATS : C::STATIC_FLOATS) / 4, IT = (N4 + FAST_THREADS - 1) / FAST_THREADS;
-        const float4* src = reinterpret_cast<const float4*>(qimg);
-        float4* dst = reinterpret_cast<float4*>(lds);
-        float4 v[IT];
-#pragma unroll
-        for (int k = 0; k < IT; ++k) { const int e = tid + k * FAST_THREADS; v[k] = e < N4 ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f); }
-        __builtin_amdgcn_sched_barrier(0);
-        float4* z = reinterpret_cast<float4*>(wl);
-        for (int e = lane; e < C::WAVE3_FLOATS / 4; e += 64) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < IT; ++k) { const int e = tid + k * FAST_THREADS; if (e < N4) dst[e] = v[k]; }
-    }
-    __syncthreads();
     TB_STAMP(1); TSTAMPO(58);
 
     constexpr int NFd = C::maxNF() > 0 ? C::maxNF() : 1;

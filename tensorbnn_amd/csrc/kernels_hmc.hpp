@@ -22,6 +22,9 @@ __global__ __launch_bounds__(UC * UG) void k_update(
     // kick + drift, t = 1 .. max L: the step index.  (mode UPD_GRAD_ONLY -- the bootstrap evaluation -- is the same for every chain)
     const StepCtl* __restrict__ ctl = nullptr, int t = 0)
 {
+    // the arguments the first requests are made from, read here: one batch of scalar loads and one wait in front of the branches below
+    // (each of which otherwise gets its own group of loads, and its own wait)
+    asm volatile("" :: "s"(mode), "s"(ctl), "s"(slabs), "s"(nslab), "s"(pitch), "s"(eta), "s"(q), "s"(p), "s"(imgmap), "s"(nd.P), "s"(nd.nl));
     if (ctl && mode != UPD_GRAD_ONLY) {
         const StepCtl me = ctl[blockIdx.y];
         eps = me.eps;
@@ -48,24 +51,19 @@ __global__ __launch_bounds__(UC * UG) void k_update(
     const int c4 = blockIdx.x * UC + tx;                // float4 column
     const int jf = c4 * 4 + ty;                         // ty < 4 selects which of the column's 4 parameters this thread finishes
     const bool fin = ty < 4 && jf < nd.P;
+    // every request of the block leaves before its first wait: the slab loads first, in all waves, then what the finishing threads need
     UpdPre u;
+    UpdCol col;
+    if (mode != UPD_FIRST) upd_column_issue<UG>(col, slabs, nslab, pitch, c4, ty);
     if (fin) upd_prefetch(u, nd, mode, eta, jf, q_cur, g_cur, q, p, imgmap);
-    float4 gs = make_float4(0.f, 0.f, 0.f, 0.f);
+    float gj = 0.f;
     if (mode != UPD_FIRST) {
-        part[ty][tx] = upd_column_partial<UG>(slabs, nslab, pitch, c4, ty);
-        __syncthreads();
-#pragma unroll
-        for (int h = UG / 2; h > 0; h >>= 1) {
-            if (ty < h) {
-                const float4 a = part[ty][tx], b = part[ty + h][tx];
-                part[ty][tx] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-            }
-            __syncthreads();
-        }
-        gs = part[0][tx];
+        part[ty][tx] = upd_column_sum<UG>(col, slabs, nslab, pitch, c4, ty);
+        __syncthreads();                               // the only one: the finishing threads add the UG partials in registers
+        if (!fin) return;
+        gj = upd_block_sum<UC, UG>(part, tx, ty);
     }
     if (!fin) return;
-    const float gj = ty == 0 ? gs.x : ty == 1 ? gs.y : ty == 2 ? gs.z : gs.w;
     upd_finish(u, nd, mode, eps, eta, jf, gj, q, p, g, imgmap, qimg, gd);
 }
 

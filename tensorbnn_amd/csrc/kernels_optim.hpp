@@ -90,17 +90,8 @@ __global__ __launch_bounds__(UC * UG) void k_optim(
     if (frozen) return;                                 // (the whole block: no barrier is left waiting)
     part[ty][tx] = upd_column_partial<UG>(slabs, nslab, pitch, c4, ty);
     __syncthreads();
-#pragma unroll
-    for (int h = UG / 2; h > 0; h >>= 1) {
-        if (ty < h) {
-            const float4 a = part[ty][tx], b = part[ty + h][tx];
-            part[ty][tx] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-        }
-        __syncthreads();
-    }
     if (!fin) return;
-    const float4 gs = part[0][tx];
-    float gj = ty == 0 ? gs.x : ty == 1 ? gs.y : ty == 2 ? gs.z : gs.w;
+    float gj = upd_block_sum<UC, UG>(part, tx, ty);     // (k_update's reduction: one barrier, the tree's additions in registers)
     if (!likelihood_only) gj += prior_grad(prior, loc, scale, th);
     g[jf] = gj;
     mj = s.b1 * mj + s.omb1 * gj;
