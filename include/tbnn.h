@@ -71,9 +71,20 @@ enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
  * log1p(e^-|t|) and never exp(f): every finite f gives a finite term (Poisson's overflow past the fp32 range of exp does not occur).  They
  * accumulate y log p + r log q; the constant C = sum_i w_i sum_k (lgamma(y + 1) + lgamma(r) - lgamma(y + r)) is computed with the data (or
  * row weights), in fp64 and bit for bit the same from run to run, and subtracted where the log-probability is formed -- Poisson's rules for
- * tbnn_set_data_device and row shards hold.  Code 9 and every other value are not assigned. */
+ * tbnn_set_data_device and row shards hold.  Code 9 and every other value are not assigned;
+ * HETERO_GAUSSIAN: regression whose noise scale the network predicts.  The network has EXACTLY 2 outputs and no activation after the last
+ * layer (anything else is refused by tbnn_create, tbnn_create_multi and tbnn_fused_kernel_available): output 0 is the mean f, output 1 is
+ * g = log s, and y ~ N(f, exp(g)^2).  Per ROW, with G = log(1e8) (the clip the Gaussian kinds apply to their sd), gc = min(max(g, -G), G),
+ * u = exp(-2 gc) and r = y - f:  log p(y | f, g) = -1/2 log(2 pi) - gc - 1/2 r^2 u,  dL/df = r u,  dL/dg = r^2 u - 1 for -G <= g <= G,
+ * else 0 (the derivative of the clipped function, as the Bernoulli clip's zero gradient outside its range).  No likelihood hyper
+ * (H = 4 n_layers; the hyper transition touches no data); fixed_sd and lik_df are not read.  A row weight scales the row's term and both
+ * deltas.  The kernels accumulate sum_i w_i (-gc - 1/2 r^2 u); the constant -1/2 log(2 pi) W, W the rows that normalise the Gaussian kinds
+ * (their count, the sum of the row weights, n_total of a row-sharded chain), is added in fp64 where the log-probability is formed, and stat
+ * of tbnn_logp_grad is the data term INCLUDING it, as under Poisson.  Targets stay [n][d_out] = [n][2] at this interface: column 0 is y,
+ * column 1 is NOT READ.  A non-finite statistic rejects the proposal.  tbnn_metrics compares output 0 with target column 0 only.  Codes 4,
+ * 6, 7, 9, 11 and every other value are not assigned. */
 enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5,
-       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10 };
+       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10, TBNN_LIK_HETERO_GAUSSIAN = 12 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or

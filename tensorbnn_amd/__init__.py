@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "NegativeBinomialLikelihood":
         from .likelihood import NegativeBinomialLikelihood
         return NegativeBinomialLikelihood
+    if name == "HeteroscedasticGaussianLikelihood":
+        from .likelihood import HeteroscedasticGaussianLikelihood
+        return HeteroscedasticGaussianLikelihood
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

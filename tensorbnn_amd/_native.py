@@ -22,6 +22,7 @@ PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
 LIK_STUDENT_T = 8                                                                                  # (nor are 6 and 7)
 LIK_NEG_BINOMIAL = 10                                                                              # (nor is 9)
+LIK_HETERO_GAUSSIAN = 12                                                                           # (nor is 11)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
 OPT_POSTERIOR, OPT_LIKELIHOOD = 0, 1
 XFORM_NONE, XFORM_EXP, XFORM_SIGMOID, XFORM_SOFTMAX = 0, 1, 2, 3
@@ -285,6 +286,18 @@ def _set_row_weights(chain, w):
     chain.row_weighted = True
 
 
+def pad_targets(Y, n: int, d_out: int, likelihood: int) -> np.ndarray:
+    """targets as the C interface takes them, float32 [n, d_out].  Under LIK_HETERO_GAUSSIAN (d_out = 2: mean and log-sd, ONE target per
+    row) n targets -- [n] or [n, 1] -- become column 0 of [n, 2] with zeros in column 1, which the library does not read; [n, 2] is taken
+    as it is"""
+    Y = _f32(Y)
+    if int(likelihood) == LIK_HETERO_GAUSSIAN and d_out == 2 and Y.size == n:
+        out = np.zeros((n, 2), dtype=np.float32)
+        out[:, 0] = Y.reshape(n)
+        return out
+    return Y.reshape(n, d_out)
+
+
 class Chain:
     """One HMC chain on one device (tbnn_handle)."""
 
@@ -343,7 +356,7 @@ class Chain:
     # ---- data / state
     def set_data(self, X, Y):
         X = _f32(X).reshape(-1, self.d_in)
-        Y = _f32(Y).reshape(X.shape[0], self.d_out)
+        Y = pad_targets(Y, X.shape[0], self.d_out, self._jit_args[1])
         self.n = X.shape[0]
         _check(lib.tbnn_set_data(self._h, _p(X), _p(Y), self.n))
         self.row_weighted = False          # (new rows: the library dropped the weights)
@@ -467,7 +480,7 @@ class Chain:
 
     def set_validation(self, X, Y):
         X = _f32(X).reshape(-1, self.d_in)
-        Y = _f32(Y).reshape(X.shape[0], self.d_out)
+        Y = pad_targets(Y, X.shape[0], self.d_out, self._jit_args[1])
         _check(lib.tbnn_set_validation(self._h, _p(X), _p(Y), X.shape[0]))
         self.nv = X.shape[0]
 
@@ -505,11 +518,15 @@ class Chain:
         them; want=False: the targets are not asked for"""
         if want and xp is not None and Y is None:
             raise ValueError("rows X need their targets Y")
-        yp = None if (Y is None or not want) else _f32(Y).reshape(-1, self.d_out)
+        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        yp = None if (Y is None or not want) else _f32(Y)
+        if yp is not None:
+            # (LIK_HETERO_GAUSSIAN: one target per row, padded to the two columns of the interface)
+            yp = pad_targets(yp, n, self.d_out, lik) if (lik == LIK_HETERO_GAUSSIAN and yp.size == n) else yp.reshape(-1, self.d_out)
         if yp is not None and yp.shape[0] != n:
             raise ValueError(f"Y must hold {n} rows")
         sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (m,)))
-        return yp, sdp, self._jit_args[1] if likelihood is None else int(likelihood)
+        return yp, sdp, lik
 
     def ensemble_moments(self, thetas, X=None, which: int = 1, weights=None, xform: int = XFORM_NONE, scale: float = 1.0,
                          shift: float = 0.0, var: bool = True):
@@ -583,14 +600,16 @@ class Chain:
         quantiles at probs, each in (0, 1) (None: no probs).  F float64 [d_out, rows]: the mixture CDF at the targets, the PIT values; asked
         for by cdf=True, or cdf=None and Y given (Y None with X None: the staged targets); else None.  F_below: under LIK_POISSON / LIK_NEG_BINOMIAL the CDF at
         target - 1 (a count's PIT lies in [F_below, F]), else None.  likelihood: LIK_GAUSSIAN / LIK_FIXED_GAUSSIAN / LIK_POISSON / LIK_NEG_BINOMIAL (None: the
-        chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd)"""
+        chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd).  Under LIK_HETERO_GAUSSIAN (a 2-output chain:
+        mean and log-sd) the mixture of N(f_i, exp(g_i)^2), one distribution per row: q [n_probs, 1, rows], F [1, rows]; sd is not read"""
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
         want_cdf = (Y is not None) if cdf is None else bool(cdf)
         yp, sdp, lik = self._ensemble_targets(th.shape[0], xp, n, Y, sd, likelihood, want=want_cdf)
         pr = None if probs is None else np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
-        q = None if pr is None else np.empty((pr.size, self.d_out, n), dtype=np.float64)
-        F = np.empty((self.d_out, n), dtype=np.float64) if want_cdf else None
-        Fb = np.empty((self.d_out, n), dtype=np.float64) if want_cdf and lik in (LIK_POISSON, LIK_NEG_BINOMIAL) else None
+        od = 1 if lik == LIK_HETERO_GAUSSIAN else self.d_out          # (its two outputs describe ONE distribution per row)
+        q = None if pr is None else np.empty((pr.size, od, n), dtype=np.float64)
+        F = np.empty((od, n), dtype=np.float64) if want_cdf else None
+        Fb = np.empty((od, n), dtype=np.float64) if want_cdf and lik in (LIK_POISSON, LIK_NEG_BINOMIAL) else None
         _check(lib.tbnn_ensemble_predictive(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
                                             _pd(pr), 0 if pr is None else pr.size, _pd(q), _pd(F), _pd(Fb)))
         return q, F, Fb
@@ -698,7 +717,7 @@ class ChainGroup:
 
     def set_data(self, X, Y):
         X = _f32(X).reshape(-1, self.d_in)
-        Y = _f32(Y).reshape(X.shape[0], self.d_out)
+        Y = pad_targets(Y, X.shape[0], self.d_out, self._jit_args[1])
         self.n = X.shape[0]
         _check(lib.tbnn_set_data(self._h, _p(X), _p(Y), self.n))
         self.row_weighted = False          # (new rows: the library dropped the weights)

@@ -18,11 +18,16 @@ enum { SHAPE_LIK_STUDENT = 8 };
 // the same bit on the Poisson code: the negative-binomial data term of TBNN_LIK_NEG_BINOMIAL, the log-rate f of the Poisson kind under
 // another loss; weighted: SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN | SHAPE_LIK_WEIGHTED.  (The bit is not defined on the other two codes.)
 enum { SHAPE_LIK_NEGBIN = 8 };
+// a further flag bit on the Gaussian code: the heteroscedastic Gaussian of TBNN_LIK_HETERO_GAUSSIAN -- exactly two outputs per row, the mean
+// f and the log-sd g, ONE term per row (kernels_fast.hpp: lik_pair); weighted: SHAPE_LIK_HETERO | SHAPE_LIK_WEIGHTED.  (Not defined on the
+// other codes, nor together with SHAPE_LIK_STUDENT.)
+enum { SHAPE_LIK_HETERO = 16 };
 // ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
 __host__ __device__ constexpr int shape_lik(int lik) {
     return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS :
            lik == TBNN_LIK_STUDENT_T ? (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS) :
-           lik == TBNN_LIK_NEG_BINOMIAL ? (SHAPE_LIK_NEGBIN | SHAPE_LIK_POIS) : SHAPE_LIK_GAUSS;
+           lik == TBNN_LIK_NEG_BINOMIAL ? (SHAPE_LIK_NEGBIN | SHAPE_LIK_POIS) :
+           lik == TBNN_LIK_HETERO_GAUSSIAN ? (SHAPE_LIK_HETERO | SHAPE_LIK_GAUSS) : SHAPE_LIK_GAUSS;
 }
 
 #define TBNN_WAVE 64
@@ -160,6 +165,29 @@ __device__ __forceinline__ float negbin_elem(float fi, float y, double& stat, fl
     const float d = negbin_term(fi, y, r, lr, &term);
     stat += (double)(wt * term);
     return wt * d;
+}
+
+// Heteroscedastic Gaussian (TBNN_LIK_HETERO_GAUSSIAN): one ROW of a 2-output network, f the mean and g the log of the sd.  With
+// G = log(1e8) (the clip of lik_sigma, on the log scale), gc = g clipped to [-G, G], u = e^(-2 gc) by the hardware exp2 (within
+// [1e-16, 1e16]: never 0 or inf) and r = y - f: the row's term -gc - 1/2 r^2 u (the constant -1/2 log(2 pi) per row: data_logp,
+// kernels_hmc.hpp), dL/df = r u and dL/dg = r^2 u - 1 inside the clip, 0 outside it (the derivative of the clipped function, as the
+// Bernoulli clip's).  The clip is two selects, not fminf / fmaxf: a NaN g stays NaN, the statistic is not finite and k_energy rejects the
+// proposal; so does r^2 u past the fp32 range.  Adds wt term to stat when `count`, returns wt dL/df and wt dL/dg in *df, *dg.  A
+// multiplication by the weight 1 is exact and nothing here is contracted (the reason given at log1p_fast: which of r u, r (r u),
+// 1/2 q + gc the compiler fuses is its choice per instantiation): a weighted kernel at weight 1 gives the unweighted kernel's bits.  One
+// function for the fused families (kernels_fast.hpp: lik_pair) and the kernels that branch at run time.
+#define HETERO_LOG_CLIP 18.420680743952367f          // log(1e8)
+__device__ __forceinline__ void hetero_pair(float f, float g, float y, float wt, bool count, double& stat, float* df, float* dg) {
+#pragma clang fp contract(off)
+    float gc = g < -HETERO_LOG_CLIP ? -HETERO_LOG_CLIP : g;
+    gc = g > HETERO_LOG_CLIP ? HETERO_LOG_CLIP : gc;
+    const bool inside = g >= -HETERO_LOG_CLIP && g <= HETERO_LOG_CLIP;
+    const float u = __expf(-2.f * gc);
+    const float r = y - f, ru = r * u, q = r * ru;
+    const float term = -gc - 0.5f * q;
+    if (count) stat += (double)(wt * term);
+    *df = wt * ru;
+    *dg = inside ? wt * (q - 1.f) : 0.f;
 }
 
 __device__ __forceinline__ float act_fwd(float z, int act) {

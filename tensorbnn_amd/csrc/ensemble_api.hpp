@@ -26,6 +26,8 @@ static int ens_check_xform(const std::string& who, int xform, int d_out) {
 static int ens_check_lik(const std::string& who, int likelihood, int d_out, const float* X, const float* Y) {
     if (!lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
     if (likelihood == TBNN_LIK_CATEGORICAL && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
+    if (likelihood == TBNN_LIK_HETERO_GAUSSIAN && d_out != 2)
+        return fail(-1, who + ": the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
     if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
     return 0;
 }
@@ -517,10 +519,12 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
         return fail(-1, who + ": the predictive distribution of a label is its posterior-mean probability: tbnn_ensemble_moments returns it");
     if (likelihood == TBNN_LIK_STUDENT_T)
         return fail(-1, who + ": the Student-t predictive distribution (a mixture of t CDFs: the incomplete beta function on the device) is not built");
-    const bool gauss = ens_gaussian(likelihood);
-    if (!gauss && likelihood != TBNN_LIK_POISSON && likelihood != TBNN_LIK_NEG_BINOMIAL) return fail(-1, who + ": unknown likelihood");
+    const bool gauss = ens_gaussian(likelihood), het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
+    if (!gauss && !het && likelihood != TBNN_LIK_POISSON && likelihood != TBNN_LIK_NEG_BINOMIAL) return fail(-1, who + ": unknown likelihood");
+    // (heteroscedastic Gaussian: every network brings its own s_i(x) = exp(gc_i) in output 1 -- sd is not read, cst keeps w_i / W alone)
+    if (het && d_out != 2) return fail(-1, who + ": the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
     // (the wording predates the negative binomial, which takes cdf_below_out too; tests match on it)
-    if (cdf_below_out && gauss) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
+    if (cdf_below_out && (gauss || het)) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
     if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     // the budget of ensemble_row_blocks, judged here before m values of sd and net_w are read and 3 m doubles staged
     ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
@@ -554,7 +558,9 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
     double smax = 0.0;
     ENS_TRY(pred_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, probs, n_probs, q_out, cdf_out, cdf_below_out, cst, pz, &smax));
     if (!q_out) n_probs = 0;
-    const bool pois = likelihood == TBNN_LIK_POISSON, negb = likelihood == TBNN_LIK_NEG_BINOMIAL;
+    const bool pois = likelihood == TBNN_LIK_POISSON, negb = likelihood == TBNN_LIK_NEG_BINOMIAL, het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
+    // result planes per row: one per output; the heteroscedastic Gaussian's two outputs describe ONE distribution per row
+    const int od = het ? 1 : d_out;
     // the dispersion of the negative binomial: the descriptor's lik_df on such a handle, what tbnn_set_lik_df set on any other
     double disp = 0.0;
     if (negb) {
@@ -569,7 +575,7 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
     long rbk = 0;
     return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
         [&](long rb) -> int {
-            rbk = rb * d_out;
+            rbk = rb * od;
             // a block's results: n_probs quantile planes, then the CDF and the CDF below
             HIPCHK(dRes.alloc(((size_t)n_probs + 2) * rbk));
             ENS_TRY(ens_upload(h, dCst, cst.data(), cst.size()));
@@ -578,7 +584,7 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
             return 0;
         },
         [&](long r0, long r, long rows, const float* t) -> int {
-            const long tot = r * d_out;
+            const long tot = r * od;                       // elements: (output, row) pairs; heteroscedastic Gaussian: rows
             const dim3 grid(ens_grid(tot)), tb(ENS_TB);
             const double* c = dCst;
             const double* p = dP;
@@ -588,18 +594,20 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
             if (q_out) {
                 if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else if (negb) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_NEG_BINOMIAL, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
+                else if (het) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_HETERO_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 HIPCHK(hipGetLastError());
-                ENS_TRY(ens_copy_planes(h, q_out, r0, rows, q, r, (size_t)n_probs * d_out));
+                ENS_TRY(ens_copy_planes(h, q_out, r0, rows, q, r, (size_t)n_probs * od));
             }
             if (cdf_out) {
                 const float* y = dYrows + (size_t)r0 * d_out;
                 if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else if (negb) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_NEG_BINOMIAL>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
+                else if (het) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_HETERO_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 HIPCHK(hipGetLastError());
-                ENS_TRY(ens_copy_planes(h, cdf_out, r0, rows, F, r, (size_t)d_out));
-                if (Fb) ENS_TRY(ens_copy_planes(h, cdf_below_out, r0, rows, Fb, r, (size_t)d_out));
+                ENS_TRY(ens_copy_planes(h, cdf_out, r0, rows, F, r, (size_t)od));
+                if (Fb) ENS_TRY(ens_copy_planes(h, cdf_below_out, r0, rows, Fb, r, (size_t)od));
             }
             return 0;
         });

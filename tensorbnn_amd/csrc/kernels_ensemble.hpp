@@ -156,6 +156,12 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
             t = fma((double)y[k], (double)d, t);
         }
         l = t - sy * (double)logf(s);
+    } else if (lik == TBNN_LIK_HETERO_GAUSSIAN) {
+        // ONE term per row (d_out == 2: the host refuses anything else): f the mean, g the log-sd clipped to +-log(1e8), target column 0;
+        // the definition of include/tbnn.h in fp64.  (Two selects, not fmin / fmax: a NaN g stays NaN.)
+        const double G = 18.420680743952367, g = (double)f[(size_t)n];
+        const double gc = g < -G ? -G : (g > G ? G : g), r = (double)y[0] - (double)f[0];
+        l = -0.9189385332046727 /* 1/2 log 2pi */ - gc - 0.5 * r * r * exp(-2.0 * gc);
     } else if (lik == TBNN_LIK_POISSON) {
         for (int k = 0; k < d_out; ++k) {
             const double fk = (double)f[(size_t)k * n], yk = (double)y[k];
@@ -646,6 +652,15 @@ __device__ __forceinline__ double ens_ulp64(double v) {
     return __longlong_as_double(__double_as_longlong(av) + 1) - av;
 }
 
+// the heteroscedastic Gaussian's log-sd as the likelihood reads it: g clipped to +-log(1e8) (two selects: a NaN stays NaN)
+__device__ __forceinline__ double ens_het_gc(float g) {
+    const double G = 18.420680743952367, gd = (double)g;
+    return gd < -G ? -G : (gd > G ? G : gd);
+}
+
+// (TBNN_LIK_HETERO_GAUSSIAN: an element is a ROW -- tot = r, the block is [m][2][r], network i's mean f_i at t[2 i tot + e] and its
+// log-sd g_i one plane further; s_i = exp(gc_i) and c_i = exp(-gc_i) / sqrt 2 are formed per (network, row) where the Gaussian kinds read
+// cst[2 m + i] and cst[m + i]; a NaN f_i or g_i of a network that counts gives NaN, one of a network of weight 0 is not looked at.)
 // t: the block [m][tot] of untransformed predictions, tot = d_out r; Y: the block's targets [r][d_out]; cst[2][m]: w_i / W and, Gaussian
 // kinds, 1 / (s_i sqrt 2).  cdf[tot] = F(y); below[tot] (Poisson, or null) = F(y - 1).  Networks of weight 0 add nothing; a NaN among an
 // element's f_i or a NaN target (Poisson: any target that is not finite) gives NaN.  Poisson: the target is read at k = floor(y), F = 0 for k < 0, and a non-finite rate or one
@@ -658,6 +673,8 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
                                                           double disp) {
 #pragma clang fp contract(off)
     constexpr bool COUNTS = LIK == TBNN_LIK_POISSON || LIK == TBNN_LIK_NEG_BINOMIAL;
+    constexpr bool HET = LIK == TBNN_LIK_HETERO_GAUSSIAN;
+    const long ns = HET ? 2 * tot : tot;                  // floats between two networks' predictions of an element
     const double lr = LIK == TBNN_LIK_NEG_BINOMIAL ? log(disp) : 0.0;
     for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
         const float* __restrict__ te = t + e;
@@ -667,8 +684,15 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
         if (LIK == TBNN_LIK_NEG_BINOMIAL) bad += k > ENS_NB_MAX;
         double F = 0.0, Fb = 0.0;
         for (int i = 0; i < m; ++i) {
-            const float fv = te[(size_t)i * tot];
+            const float fv = te[(size_t)i * ns];
             const double wn = cst[i];
+            if (HET) {
+                if (!(wn > 0.0)) continue;                  // (a network of weight 0 adds nothing, whatever it holds)
+                const float gv = te[(size_t)i * ns + tot];
+                bad += (fv != fv) + (gv != gv);
+                F += wn * ens_phi(y, (double)fv, exp(-ens_het_gc(gv)) * 0.70710678118654752440);
+                continue;
+            }
             bad += fv != fv;
             if (!(wn > 0.0)) continue;
             if (LIK == TBNN_LIK_POISSON) {
@@ -716,7 +740,9 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                                                                 double disp) {
 #pragma clang fp contract(off)
     constexpr bool NEGB = LIK == TBNN_LIK_NEG_BINOMIAL;
+    constexpr bool HET = LIK == TBNN_LIK_HETERO_GAUSSIAN;          // (a Gaussian kind below: the same bracket, search and stopping rule)
     const bool gauss = LIK != TBNN_LIK_POISSON && !NEGB;
+    const long ns = HET ? 2 * tot : tot;                  // floats between two networks' predictions of an element
     const double lr = NEGB ? log(disp) : 0.0;
     for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
         const float* __restrict__ te = t + e;
@@ -727,6 +753,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
             int ph[QP];                                // Gaussian: 0 verifying a, 1 verifying b, 2 searching; + 8 per push outward.  -1: done
             int bad = 0;
             double mean = 0.0;
+            double smx = HET ? 0.0 : smax;                 // the widening's scale: HET the element's own largest s_i that counts
 #pragma unroll
             for (int j = 0; j < QP; ++j) {
                 pj[j] = probs[min(p0 + j, np - 1)];
@@ -734,13 +761,16 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                 ph[j] = p0 + j < np ? 0 : -1;              // (a slot past the last is never evaluated)
             }
             for (int i = 0; i < m; ++i) {
-                const float fv = te[(size_t)i * tot];
+                const float fv = te[(size_t)i * ns];
                 const double wn = cst[i];
-                bad += fv != fv;
+                if (!HET) bad += fv != fv;
+                float gv = 0.f;
+                if (HET && wn > 0.0) { gv = te[(size_t)i * ns + tot]; bad += (fv != fv) + (gv != gv); }      // (weight 0: not looked at)
                 if (!(wn > 0.0)) continue;
                 if (gauss) {
                     bad += fabsf(fv) == INFINITY;
-                    const double s = cst[2 * m + i];
+                    const double s = HET ? exp(ens_het_gc(gv)) : cst[2 * m + i];
+                    if (HET) smx = fmax(smx, s);
 #pragma unroll
                     for (int j = 0; j < QP; ++j) {
                         const double v = fma(s, probs[np + min(p0 + j, np - 1)], (double)fv);
@@ -755,7 +785,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
 #pragma unroll
             for (int j = 0; j < QP; ++j) {
                 if (gauss) {
-                    const double d = 0x1p-44 * (fmax(fabs(a[j]), fabs(b[j])) + smax);
+                    const double d = 0x1p-44 * (fmax(fabs(a[j]), fabs(b[j])) + smx);
                     a[j] -= d; b[j] += d;
                     x[j] = a[j]; wd[j] = b[j] - a[j];
                 } else {
@@ -773,9 +803,9 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                 for (int i = 0; i < m; ++i) {
                     const double wn = cst[i];
                     if (!(wn > 0.0)) continue;
-                    const double f = (double)te[(size_t)i * tot];
+                    const double f = (double)te[(size_t)i * ns];
                     if (gauss) {
-                        const double c = cst[m + i], wc = wn * c;
+                        const double c = HET ? exp(-ens_het_gc(te[(size_t)i * ns + tot])) * 0.70710678118654752440 : cst[m + i], wc = wn * c;
 #pragma unroll
                         for (int j = 0; j < QP; ++j) {
                             if (ph[j] >= 0) {

@@ -44,7 +44,11 @@ struct Shape {
     static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT,
                           POIS = (LIK_ & (3 | SHAPE_LIK_NEGBIN)) == SHAPE_LIK_POIS, NEGB = (LIK_ & (3 | SHAPE_LIK_NEGBIN)) == (SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN),
                           WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0, STUD = (LIK_ & (3 | SHAPE_LIK_STUDENT)) == (SHAPE_LIK_GAUSS | SHAPE_LIK_STUDENT);
-    static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & ~(3 | SHAPE_LIK_WEIGHTED | SHAPE_LIK_STUDENT)) == 0, "unknown likelihood code");
+    // (bit 16, on the Gaussian code alone: the heteroscedastic Gaussian -- two outputs, one term per row: lik_pair)
+    static constexpr bool HET = (LIK_ & SHAPE_LIK_HETERO) != 0;
+    static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & ~(3 | SHAPE_LIK_WEIGHTED | SHAPE_LIK_STUDENT | SHAPE_LIK_HETERO)) == 0, "unknown likelihood code");
+    static_assert(!HET || ((LIK_ & (3 | SHAPE_LIK_STUDENT)) == SHAPE_LIK_GAUSS && LACT_ == TBNN_ACT_NONE && D[NL] == 2),
+                  "heteroscedastic Gaussian: a flag on the plain Gaussian code, exactly 2 outputs (mean, log-sd), no last activation");
     static_assert((LIK_ & SHAPE_LIK_STUDENT) == 0 || STUD || NEGB,
                   "bit 8 is a flag on the Gaussian code (Student-t: SHAPE_LIK_STUDENT) and on the Poisson code (negative binomial: SHAPE_LIK_NEGBIN)");
     static_assert(!(POIS || NEGB) || LACT_ == TBNN_ACT_NONE, "Poisson, negative binomial: the last layer's output is the log-rate (no last activation)");
@@ -617,6 +621,7 @@ __device__ __forceinline__ float lik_np1(const NetDev& nd) {
 template <class S>
 __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat, float wt = 1.f, float np1 = 0.f) {
     static_assert(!S::CAT, "the categorical likelihood couples a row's outputs: cat_delta4 on the MFMA output tile, no per-element path");
+    static_assert(!S::HET, "the heteroscedastic Gaussian couples a row's two outputs: lik_pair, once both are computed");
     float da;
     if constexpr (S::BERN) {
         const float p = fminf(fmaxf(fi, 1e-8f), 1.f - 1e-7f);
@@ -685,6 +690,19 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
         }
     }
     return da * actc_bwd<S::LACT>(fi);
+}
+
+// Heteroscedastic Gaussian (S::HET; TBNN_LIK_HETERO_GAUSSIAN): the likelihood of one ROW once both of its outputs are computed -- f0 the
+// mean, f1 the log-sd, yy target column 0 (column 1 is not read) -- by hetero_pair (common.hpp).  The VALU last layer of every family
+// holds both outputs of the row in the same lane, so nothing crosses lanes.  dz[0], dz[1]: dL/df and dL/dg (no last activation), 0 for a
+// row past the end; the row's term is counted when `count`.  wt: the row weight (1 in an unweighted instantiation: an exact product).
+template <class S>
+__device__ __forceinline__ void lik_pair(float f0, float f1, float yy, bool rvalid, bool count, double& stat, float wt, float* dz) {
+    static_assert(S::HET, "lik_pair is the heteroscedastic Gaussian's");
+    float d0 = 0.f, d1 = 0.f;
+    if (rvalid) hetero_pair(f0, f1, yy, S::WTD ? wt : 1.f, count, stat, &d0, &d1);
+    dz[0] = d0;
+    dz[1] = d1;
 }
 
 // Categorical likelihood (TBNN_LIK_CATEGORICAL) of the 16 rows of NT output tiles in the MFMA D layout: lane (row i16, group g) holds the
@@ -785,8 +803,10 @@ struct TileStep {
                 p += __shfl_xor(p, 16, 64);
                 p += __shfl_xor(p, 32, 64);
                 const float fi = actc_fwd<S::LACT>(p + LR.b[o]);
-                dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
+                if constexpr (S::HET) dzl[o] = fi;      // (both outputs first: lik_pair below)
+                else dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
             }
+            if constexpr (S::HET) lik_pair<S>(dzl[0], dzl[1], y[0], rvalid, g == 0, stat, wt, dzl);
             TSTAMP(9);
             // dW_L / db_L partial sums, delta_{L-1}
 #pragma unroll

@@ -1086,7 +1086,9 @@ struct Coop3 {
 #pragma unroll
         for (int o = 0; o < NFd; ++o) dzf[o] = 0.f;
 #pragma unroll
-        for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0 && wave == 0, stat, wt, np1) : 0.f;
+        for (int o = 0; o < d_out; ++o)
+            if constexpr (!S::HET) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0 && wave == 0, stat, wt, np1) : 0.f;
+        if constexpr (S::HET) lik_pair<S>(T.af[L][0], T.af[L][1], y[0], rvalid, g == 0 && wave == 0, stat, wt, dzf);
         if (wave == 0) FringeDW<S, L>::run(FP, T, dzf, g);
         f32x4 dzL[C::MT(L)];
 #pragma unroll
@@ -1590,7 +1592,9 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         // likelihood on the all-fringe last layer
         float dzf[NFd];
 #pragma unroll
-        for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
+        for (int o = 0; o < d_out; ++o)
+            if constexpr (!S::HET) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
+        if constexpr (S::HET) lik_pair<S>(T.af[L][0], T.af[L][1], y[0], rvalid, g == 0, stat, wt, dzf);
         TSTAMP(30);
         // (the last layer's fringe sums -- a dozen packed FMAs -- wait until the N-fringe operands of layer L-1 are on their way: NCF)
         if constexpr (!C::NCF(L > 0 ? L - 1 : 0)) FringeDW<S, L>::run(FP, T, dzf, g);

@@ -93,6 +93,13 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
             const float ps = sy / s;
             for (int i = 0; i < nd.d_out; ++i)
                 DA0[i * GEN_RB + tid] = valid ? wt * (Y[R * nd.d_out + i] - expf(f[i * GEN_RB + tid] - m) * ps) : 0.f;
+        } else if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) {
+            // one term per row of the two outputs (mean, log-sd) against target column 0: hetero_pair (common.hpp), the fused kernels' arithmetic
+            const float* f = ACT + (size_t)nd.actOff[nd.nl - 1] * GEN_RB;
+            float d0, d1;
+            hetero_pair(f[tid], f[GEN_RB + tid], valid ? Y[R * 2] : 0.f, wt, valid, stat, &d0, &d1);
+            DA0[tid] = valid ? d0 : 0.f;
+            DA0[GEN_RB + tid] = valid ? d1 : 0.f;
         } else {
             const float* f = ACT + (size_t)nd.actOff[nd.nl - 1] * GEN_RB;
             for (int i = 0; i < nd.d_out; ++i) {
@@ -213,7 +220,8 @@ __global__ __launch_bounds__(GEN_RB) void k_forward_generic(
 //   p = f*sd + mean, r = y*sd + mean (metrics.py:36-42), optionally exp() of either (scaleExp; SquaredError does
 //   not exponentiate the validation predictions, :44-47 -- the caller passes the flags)
 //   part[3b+0] += (p-r)^2, part[3b+1] += 100|(p-r)/r|, part[3b+2] += |r - round(p)|   (round half to even, tf.round)
-__global__ __launch_bounds__(256) void k_metrics(const float* __restrict__ f, const float* __restrict__ Y, long n, int d_out,
+// d_out: the outputs compared, ys >= d_out: the floats per row of Y (TBNN_LIK_HETERO_GAUSSIAN: output 0, the mean, against column 0 of 2)
+__global__ __launch_bounds__(256) void k_metrics(const float* __restrict__ f, const float* __restrict__ Y, long n, int d_out, int ys,
                                                   float mean, float sd, int exp_pred, int exp_real, double* __restrict__ part) {
     __shared__ double red[8];
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -221,7 +229,7 @@ __global__ __launch_bounds__(256) void k_metrics(const float* __restrict__ f, co
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (long)gridDim.x * blockDim.x) {
         const long row = e / d_out; const int o = (int)(e - row * d_out);
         float p = f[(size_t)o * n + row] * sd + mean;
-        float r = Y[e] * sd + mean;
+        float r = Y[row * ys + o] * sd + mean;
         if (exp_pred) p = expf(p);
         if (exp_real) r = expf(r);
         const float d = p - r;

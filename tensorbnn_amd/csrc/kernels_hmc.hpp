@@ -163,6 +163,8 @@ __device__ __forceinline__ double data_logp(const NetDev& nd, const float* __res
     if (nd.lik == TBNN_LIK_POISSON) return stat - lik_c;                                   // the statistic is sum w (y f - e^f)
     if (nd.lik == TBNN_LIK_NEG_BINOMIAL) return stat - lik_c;                              // ... sum w (y log p + r log q)
     if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
+    // heteroscedastic Gaussian: the statistic is sum w (-gc - 1/2 r^2 u), ONE term per row: the constant -1/2 log(2 pi) counts n rows
+    if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) return stat - 0.5 * 1.8378770664093453 /* log 2pi */ * n;
     if (nd.lik == TBNN_LIK_STUDENT_T) {
         // the statistic is sum w log1p(r^2 / (nu s^2)): n d_out c(nu, s) - (nu + 1) / 2 stat,
         // c = lgamma((nu + 1) / 2) - lgamma(nu / 2) - 1/2 log(nu pi) - log s (include/tbnn.h TBNN_LIK_STUDENT_T)

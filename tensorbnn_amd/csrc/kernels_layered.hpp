@@ -405,6 +405,19 @@ __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restr
         if (threadIdx.x == 0) pstat[blockIdx.x] = tot;
         return;
     }
+    if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) {
+        // one thread per data ROW: its two outputs (mean, log-sd) against target column 0 (hetero_pair, common.hpp; no last activation)
+        for (long row = (long)blockIdx.x * 256 + threadIdx.x; row < n; row += (long)gridDim.x * 256) {
+            const size_t rb = (size_t)(row >> 4) * TMl * 256 + (row & 15) * 16;
+            float d0, d1;
+            hetero_pair(f[rb], f[rb + 1], Y[row * 2], wrow ? wrow[row] : 1.f, true, stat, &d0, &d1);
+            dz[rb] = d0;
+            dz[rb + 1] = d1;
+        }
+        const double tot = block_sum(stat, red);
+        if (threadIdx.x == 0) pstat[blockIdx.x] = tot;
+        return;
+    }
     // one thread per (row, output) element: with many outputs a thread per ROW ran the library logarithms of all of them one after the
     // other (784 -> 100 -> 100 -> 10 at n = 12 k: 9.6 us for 120 k elements)
     const long nel = n * nd.d_out;
@@ -617,6 +630,17 @@ __global__ __launch_bounds__(256) void k_lay_tail(NetDev nd, LayPlan p, const fl
                     y[t][j] = (row < n && o < nd.d_out) ? Y[row * nd.d_out + o] : 0.f;
                 }
             cat_delta<TT, true>(a, y, live, row < n, g, stat, dz, (wrow && row < n) ? wrow[row] : 1.f);
+        } else if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) {
+            // the row's two outputs (mean, log-sd: slots 0 and 1 of lane group 0) against target column 0: hetero_pair (common.hpp)
+            const long row = rt * 16 + i16;
+#pragma unroll
+            for (int t = 0; t < TT; ++t) dz[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (g == 0 && row < n) {
+                float d0, d1;
+                hetero_pair(a[0][0], a[0][1], Y[row * 2], wrow ? wrow[row] : 1.f, true, stat, &d0, &d1);
+                dz[0][0] = d0;
+                dz[0][1] = d1;
+            }
         } else {
             const long row = rt * 16 + i16;
             const float wt = (wrow && row < n) ? wrow[row] : 1.f;
@@ -756,6 +780,17 @@ __global__ __launch_bounds__(256) void k_lay_last(NetDev nd, LayPlan p, const fl
             fv[0] = f;
             cat_delta<1, true>(fv, yv, live, row < n, g, stat, dv, wt);
             dz = dv[0];
+        } else if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) {
+            // the row's two outputs (mean, log-sd: slots 0 and 1 of lane group 0; lact is NONE: tbnn_create) against target column 0
+#pragma unroll
+            for (int j = 0; j < 4; ++j) f[j] = 4 * g + j < 2 ? acc0[j] + acc1[j] : 0.f;
+            dz = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (g == 0 && row < n) {
+                float d0, d1;
+                hetero_pair(f[0], f[1], Y[row * 2], wt, true, stat, &d0, &d1);
+                dz[0] = d0;
+                dz[1] = d1;
+            }
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {

@@ -453,10 +453,18 @@ __global__ __launch_bounds__(MID_THREADS, 1) __attribute__((amdgpu_waves_per_eu(
                     if (rvalid && g == 0) fout[(size_t)o * n + tile * 16 + i16] = fi;      // [d_out][n]
                     dzl[o] = 0.f;
                 } else {
-                    dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
-                    LR.accb[o] += dzl[o];
+                    if constexpr (S::HET) dzl[o] = fi;      // (both outputs first: lik_pair below)
+                    else {
+                        dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
+                        LR.accb[o] += dzl[o];
+                    }
                 }
                 MSTAMP(18 + 3 * o);
+            }
+            if constexpr (S::HET && !FWD) {
+                lik_pair<S>(dzl[0], dzl[1], y[0], rvalid, g == 0, stat, wt, dzl);
+                LR.accb[0] += dzl[0];
+                LR.accb[1] += dzl[1];
             }
         }
         if constexpr (!FWD) {

@@ -461,9 +461,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) __attribute__((amdgpu_waves_per_eu
                 if (rvalid && g == 0) fout[(size_t)o * n + tile * 16 + i16] = fi;      // [d_out][n]
                 dzl[o] = 0.f;
             } else {
-                dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
+                if constexpr (S::HET) dzl[o] = fi;      // (both outputs first: lik_pair below)
+                else dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
             }
         }
+        if constexpr (S::HET && !FWD) lik_pair<S>(dzl[0], dzl[1], y[0], rvalid, g == 0, stat, wt, dzl);
         }
         if constexpr (!FWD) {
         f32x4 dz[C::MAXT];

@@ -148,7 +148,9 @@ __global__ __launch_bounds__(64 * NW, 1) __attribute__((amdgpu_waves_per_eu(NW /
 #pragma unroll
             for (int o = 0; o < NFd; ++o) dzf[o] = 0.f;
 #pragma unroll
-            for (int o = 0; o < d_out; ++o) dzf[o] = rvalid ? lik_delta<S>(T.af[LL][o], y[o], inv_var, gq == 0, stat, 1.f, np1) : 0.f;
+            for (int o = 0; o < d_out; ++o)
+                if constexpr (!S::HET) dzf[o] = rvalid ? lik_delta<S>(T.af[LL][o], y[o], inv_var, gq == 0, stat, 1.f, np1) : 0.f;
+            if constexpr (S::HET) lik_pair<S>(T.af[LL][0], T.af[LL][1], y[0], rvalid, gq == 0, stat, 1.f, dzf);
             if constexpr (!C::NCF(LL > 0 ? LL - 1 : 0)) FringeDW<S, LL>::run(FP, T, dzf, gq);
             f32x4 dzL[C::MT(LL)];
             f32x4 dzp[C::MT(LL - 1)];

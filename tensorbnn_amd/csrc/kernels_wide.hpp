@@ -598,9 +598,17 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) __attribute__((amdgpu_waves_per_eu
                     if (rvalid && g == 0) fout[(size_t)o * n + tile * 16 + i16] = fi;      // [d_out][n]
                     dzl[o] = 0.f;
                 } else {
-                    dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
-                    accbL[o] += dzl[o];
+                    if constexpr (S::HET) dzl[o] = fi;      // (both outputs first: lik_pair below)
+                    else {
+                        dzl[o] = rvalid ? lik_delta<S>(fi, y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
+                        accbL[o] += dzl[o];
+                    }
                 }
+            }
+            if constexpr (S::HET && !FWD) {
+                lik_pair<S>(dzl[0], dzl[1], y[0], rvalid, g == 0, stat, wt, dzl);
+                accbL[0] += dzl[0];
+                accbL[1] += dzl[1];
             }
             if constexpr (FWD) { base = (base + C::NCHF) & (WIDE_RING - 1); continue; }
 #pragma unroll

@@ -163,7 +163,8 @@ extern "C" int tbnn_device_count(void) {
 
 // the TBNN_LIK_* values (4, 6 and 7 are not among them: include/tbnn.h)
 static bool lik_known(int lik) {
-    return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON || lik == TBNN_LIK_STUDENT_T || lik == TBNN_LIK_NEG_BINOMIAL;
+    return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON || lik == TBNN_LIK_STUDENT_T || lik == TBNN_LIK_NEG_BINOMIAL ||
+           lik == TBNN_LIK_HETERO_GAUSSIAN;
 }
 // the count likelihoods: targets finite and >= 0, the last layer's output a log-rate, the constant of stage_lik_const
 static bool lik_counts(int lik) { return lik == TBNN_LIK_POISSON || lik == TBNN_LIK_NEG_BINOMIAL; }
@@ -200,6 +201,11 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
         if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
             return fail(-1, "the negative-binomial likelihood takes the last layer's outputs as log-rates (log link): the last layer must carry no activation");
         if (!df_ok(d->lik_df)) return fail(-1, "the negative-binomial likelihood needs lik_df (its dispersion r) finite and > 0");
+    }
+    if (d->likelihood == TBNN_LIK_HETERO_GAUSSIAN) {
+        if (nd.out[nd.nl - 1] != 2) return fail(-1, "the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
+        if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
+            return fail(-1, "the heteroscedastic Gaussian likelihood takes the last layer's outputs as mean and log-sd: the last layer must carry no activation");
     }
     nd.P = off;
     nd.lik = d->likelihood;
@@ -863,7 +869,11 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->profile) drain_profile(h);
     if (logp) *logp = lp;
-    if (stat) { double s = 0; for (double v : ps) s += v; *stat = s - lik_const(h); }      // (Poisson: the log-likelihood with its constant)
+    if (stat) {
+        double s = 0; for (double v : ps) s += v;
+        *stat = s - lik_const(h);                                                          // (Poisson: the log-likelihood with its constant)
+        if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) *stat -= 0.5 * 1.8378770664093453 /* log 2pi */ * rows_total(h);      // (... as data_logp adds it)
+    }
     return 0;
 }
 
@@ -939,10 +949,12 @@ extern "C" int tbnn_metrics(tbnn_handle h, int which, const float* theta, float 
     if (rc) return rc;
     const int MB = 256;
     HIPCHK(h->mpart.grow(3 * MB, 3 * MB));
-    const long tot = n * h->nd.d_out;
+    // (heteroscedastic Gaussian: output 1 is the log-sd and target column 1 is not read -- the mean against column 0 alone)
+    const int d_cmp = h->nd.lik == TBNN_LIK_HETERO_GAUSSIAN ? 1 : h->nd.d_out;
+    const long tot = n * d_cmp;
     const int grid = (int)std::min<long>(MB, (tot + 255) / 256);
     hipLaunchKernelGGL(k_metrics, dim3(grid), dim3(256), 0, h->stream, (const float*)h->fbuf, (const float*)(which ? h->dYv : h->dY), n,
-                       h->nd.d_out, mean, sd, exp_pred, exp_real, h->mpart);
+                       d_cmp, h->nd.d_out, mean, sd, exp_pred, exp_real, h->mpart);
     HIPCHK(hipGetLastError());
     std::vector<double> part(3 * (size_t)grid);
     HIPCHK(hipMemcpyAsync(part.data(), h->mpart, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));

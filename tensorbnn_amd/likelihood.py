@@ -200,3 +200,33 @@ class NegativeBinomialLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+class HeteroscedasticGaussianLikelihood(Likelihood):
+    """Regression whose noise scale the network predicts: the last dense layer has EXACTLY 2 outputs with no activation after it, output 0
+    the mean f and output 1 the log of the standard deviation g, and y ~ N(f, exp(g)^2) row by row (include/tbnn.h
+    TBNN_LIK_HETERO_GAUSSIAN).  With G = log(1e8), gc = clip(g, -G, G):  log p(y | f, g) = -1/2 log(2 pi) - gc - 1/2 (y - f)^2 exp(-2 gc).
+    One target per row (trainY [n] or [n, 1]; [n, 2] is taken with column 1 ignored).  predict returns both outputs, [2, rows]: the mean
+    and the log-sd.  No hyper-parameter."""
+    kind = nat.LIK_HETERO_GAUSSIAN
+    LOG_CLIP = math.log(1e8)
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.mainProbsInHypers = False
+
+    def logDensity(self, f, g, y):
+        """the log density of y under N(f, exp(g)^2), element by element in float64 (g clipped to +-log(1e8))"""
+        gc = np.clip(np.asarray(g, dtype=np.float64), -self.LOG_CLIP, self.LOG_CLIP)
+        r = np.asarray(y, dtype=np.float64) - np.asarray(f, dtype=np.float64)
+        return -0.5 * math.log(2.0 * math.pi) - gc - 0.5 * r * r * np.exp(-2.0 * gc)
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """the log density per row in float64, [1, rows]; the sum is the data term.  realVals: [rows], [rows, 1] or [rows, 2] (column 0)"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [2, rows]: mean, log-sd
+        y = np.asarray(kwargs["realVals"], dtype=np.float64)
+        y = y.reshape(-1) if y.size == f.shape[1] else y.reshape(f.shape[1], -1)[:, 0]
+        return self.logDensity(f[0], f[1], y)[None, :]
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

@@ -135,13 +135,16 @@ class predictor(object):
     def _data_logprob(self, likelihood, trainX, trainY, n):
         """summed log-likelihood of the training rows under every n-th network (see the module docstring)"""
         from .layer import _multivariate_log_prob
-        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, NegativeBinomialLikelihood,
-                                 PoissonLikelihood, StudentTLikelihood, log_softmax)
+        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, HeteroscedasticGaussianLikelihood,
+                                 NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood, log_softmax)
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
         for i, f in enumerate(preds):
             cur = np.asarray(f, dtype=np.float32).T                             # [rows, d_out]
+            if isinstance(likelihood, HeteroscedasticGaussianLikelihood):       # one target per row against the (mean, log-sd) pair
+                out.append(np.float32(np.sum(likelihood.makeResponseLikelihood(None, predict=lambda *_a, _f=cur.T: _f, realVals=y))))
+                continue
             real = y.reshape(cur.shape)
             if isinstance(likelihood, CategoricalLikelihood):
                 out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
@@ -191,7 +194,7 @@ class predictor(object):
             raise ValueError(f"weights must hold one value per picked network ({picked.shape[0]})")
         return picked, w
 
-    def predictMoments(self, inputMatrix, n=1, weights=None, transform=None, sd=1.0, mean=0.0, countVariance=False):
+    def predictMoments(self, inputMatrix, n=1, weights=None, transform=None, sd=1.0, mean=0.0, countVariance=False, noiseVariance=False):
         """Posterior-predictive mean and population variance of every n-th network's predictions, (mean, var) as float64 [d_out, rows],
         reduced on the device: only the two results cross to the host.  Per value t = transform(f) * sd + mean (the de-normalisation of
         the metrics).  transform None: softmax under a CategoricalLikelihood -- class probabilities averaged over the posterior, not
@@ -200,8 +203,23 @@ class predictor(object):
         returns.  countVariance (with the exp transform, sd = 1, mean = 0): the second array is the total predictive variance of a
         COUNT, E[rate] + Var[rate] (the Poisson noise plus the posterior spread of the rate) -- under a NegativeBinomialLikelihood
         E[rate] + Var[rate] + E[rate^2] / dispersion, E[rate^2] = Var[rate] + E[rate]^2 --, added on the host to the two arrays the
-        device returns."""
-        from .likelihood import NegativeBinomialLikelihood
+        device returns.
+        Under a HeteroscedasticGaussianLikelihood the two outputs are the mean f and the log-sd g, and the plain call (like predict)
+        returns the moments of both, [2, rows].  noiseVariance=True (that likelihood only; transform None, sd = 1, mean = 0): (E[f],
+        Var[f] + E[s^2]), each [1, rows], s = exp(g) -- the total predictive variance of a new observation, the epistemic spread of the
+        mean plus the expected noise variance; E[s^2] = Var[s] + E[s]^2 from a second reduction on the device under the exp transform."""
+        from .likelihood import HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood
+        if noiseVariance:
+            if not isinstance(self.likelihood, HeteroscedasticGaussianLikelihood):
+                raise ValueError("noiseVariance needs a HeteroscedasticGaussianLikelihood: only there does the network predict its noise")
+            if transform is not None or float(sd) != 1.0 or float(mean) != 0.0 or countVariance:
+                raise ValueError("noiseVariance takes the outputs as they are: transform None, sd = 1, mean = 0, no countVariance")
+            picked, w = self._picked(n, weights)
+            ch = self._ensure_chain()
+            x = np.asarray(inputMatrix, dtype=np.float32)
+            m, v = ch.ensemble_moments(picked, X=x, weights=w, xform=nat.XFORM_NONE)
+            ms, vs = ch.ensemble_moments(picked, X=x, weights=w, xform=nat.XFORM_EXP)
+            return m[:1], v[:1] + (vs[1:2] + ms[1:2] * ms[1:2])
         transform = self._transform(transform)
         if countVariance and (transform != "exp" or float(sd) != 1.0 or float(mean) != 0.0):
             raise ValueError("countVariance needs the rate itself: transform 'exp' (the default under a PoissonLikelihood), sd = 1, mean = 0")
