@@ -297,6 +297,35 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
 int tbnn_ensemble_loglik(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                          const float* net_w, int which, const float* X, const float* Y, int64_t n, double* per_net,
                          double* lppd_rows);
+/* Classification uncertainty: how sure is the ensemble of a label, and is that sureness noise in the data or disagreement between the
+ * networks?  Arguments up to `n` as tbnn_ensemble_moments'; likelihood: TBNN_LIK_BERNOULLI or TBNN_LIK_CATEGORICAL, the kind to read the
+ * outputs under, independent of the handle's own (as tbnn_ensemble_loglik's).  Per network i and row r, from the fp32 forward output f:
+ *   categorical  (K = d_out >= 2 logits per row)  p_ik = exp(f_k - max_j f_j) / sum_j exp(f_j - max_j f_j) in fp32, the very values
+ *                tbnn_ensemble_moments forms under TBNN_XFORM_SOFTMAX; H_i = -sum_k p_ik log p_ik, the log and the sum in fp64 from the
+ *                fp32 p_ik, classes in index order, 0 log 0 = 0; the vote a_i = the smallest k with p_ik maximal (ties go to the lowest
+ *                class).  One entropy per row.
+ *   Bernoulli    (every output a label of its own: an element is an (output, row) pair)  p_i = f clipped to [1e-8, 1 - 1e-7] in fp32,
+ *                the clip of the likelihood and of tbnn_ensemble_loglik; H_i = -(p_i log p_i + (1 - p_i) log1p(-p_i)) in fp64; the vote
+ *                is p_i >= 1/2.  One entropy per element.
+ * With W = sum_i w_i (net_w NULL: every w_i = 1), all sums fp64 in network order, not contracted:
+ *   prob_out      pbar_k = sum_i w_i p_ik / W        the posterior-mean probability (Bernoulli: of the label 1)
+ *   vote_out      sum_i w_i [a_i == k] / W           the share of the posterior that votes for class k (Bernoulli: for the label 1); the
+ *                                                   variation ratio is 1 - max_k of it (Bernoulli: 1 - max(vote, 1 - vote))
+ *   total_out     H[pbar], the same formula in fp64  the entropy of the predictive distribution
+ *   aleatoric_out sum_i w_i H_i / W                  the expected entropy under the posterior: noise in the data
+ *   epistemic_out max(total - aleatoric, 0)          the mutual information of label and network ("BALD"): model disagreement.  By
+ *                                                   Jensen's inequality the difference is >= 0; only rounding can take it below
+ * prob_out, vote_out: host [d_out][n] doubles; total_out, aleatoric_out, epistemic_out: host [n] doubles categorical, [d_out][n] Bernoulli.
+ * Any of the five may be NULL, not all.  NaN: a NaN among a row's values (Bernoulli: an element's) under ANY network, whatever its weight,
+ * gives NaN in every output of that row (element); infinite logits go through the softmax as under tbnn_ensemble_moments (f - max is NaN
+ * at +inf, the row NaN).  A thread owns its row or element and walks the networks in order; the sums cross the chunks of networks
+ * (2^28 floats of predictions each) in one device buffer: the same bits from run to run, whatever the grid and the chunking.
+ * Refused, with nothing written: every output NULL, a likelihood other than the two label kinds (regression and count kinds:
+ * tbnn_ensemble_predictive and tbnn_ensemble_moments answer there), TBNN_LIK_CATEGORICAL with d_out < 2, weights breaking the rules above,
+ * and what tbnn_ensemble_moments refuses of m, theta_stride, which and n. */
+int tbnn_ensemble_uncertainty(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
+                              int which, const float* X, int64_t n, double* prob_out, double* vote_out, double* total_out,
+                              double* aleatoric_out, double* epistemic_out);
 /* Posterior-predictive quantiles (credible intervals) over the network axis.  Arguments up to `n` as tbnn_ensemble_moments'; the values
  * ranked per (output, row) are the m values t_i = xform(f_i) * scale + shift, formed in fp32 BEFORE the ranking (a negative scale or the
  * softmax need no special case).  probs: n_probs probabilities in [0, 1], 1 <= n_probs <= 64; out: host [n_probs][d_out][n] doubles.

@@ -119,6 +119,7 @@ SYMBOLS = [
     ("tbnn_ensemble_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_series_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, _dp, _dp]),
     ("tbnn_ensemble_loglik", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp]),
+    ("tbnn_ensemble_uncertainty", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, C.c_int64, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_ensemble_predictive", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp,
                                            _dp]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
@@ -539,6 +540,22 @@ class Chain:
         _check(lib.tbnn_ensemble_moments(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), float(shift), int(which),
                                          _p(xp), n, _pd(mean), _pd(vr)))
         return mean, vr
+
+    def ensemble_uncertainty(self, thetas, X=None, which: int = 1, weights=None, likelihood=None):
+        """classification uncertainty over an ensemble, reduced on the device (tbnn_ensemble_uncertainty; the definition is in
+        include/tbnn.h): a dict of float64 arrays -- probs and votes [d_out, rows] (the posterior-mean probability of each label and the
+        share of the posterior that votes for it), total, aleatoric and epistemic (the entropy of the mean, the mean entropy of the
+        networks and their difference, the mutual information): [rows] under LIK_CATEGORICAL, [d_out, rows] under LIK_BERNOULLI.
+        likelihood: one of the two (None: the chain's own); weights: one per network or None (equal).  X None: the staged rows (0 train,
+        1 validation)"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        lik = self._jit_args[1] if likelihood is None else int(likelihood)
+        per_row = (n,) if lik == LIK_CATEGORICAL else (self.d_out, n)
+        out = {"probs": np.empty((self.d_out, n), dtype=np.float64), "votes": np.empty((self.d_out, n), dtype=np.float64)}
+        out.update({k: np.empty(per_row, dtype=np.float64) for k in ("total", "aleatoric", "epistemic")})
+        _check(lib.tbnn_ensemble_uncertainty(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(w), int(which), _p(xp), n,
+                                             *[_pd(out[k]) for k in ("probs", "votes", "total", "aleatoric", "epistemic")]))
+        return out
 
     _QUANT_METHODS = {"linear": QUANT_LINEAR, "inverted_cdf": QUANT_INVERTED_CDF}
 

@@ -293,6 +293,58 @@ extern "C" int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t
     return 0;
 }
 
+// Classification uncertainty: sums over networks like the moments', so the NETWORKS are cut (ensemble_forward), not the rows.  One device
+// buffer carries S, V and A across the chunks and takes the finish kernel's two planes behind them: (2 d_out + 3) n doubles categorical,
+// 5 d_out n Bernoulli.
+extern "C" int tbnn_ensemble_uncertainty(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
+                                         int which, const float* X, int64_t n, double* prob_out, double* vote_out, double* total_out,
+                                         double* aleatoric_out, double* epistemic_out) {
+    NEED(h);
+    const std::string who = "ensemble_uncertainty";
+    const int d_out = h->nd.d_out;
+    if (!prob_out && !vote_out && !total_out && !aleatoric_out && !epistemic_out) return fail(-1, who + ": every output is null");
+    const bool cat = likelihood == TBNN_LIK_CATEGORICAL;
+    if (!cat && likelihood != TBNN_LIK_BERNOULLI)
+        return fail(-1, who + ": the entropy split and the votes are those of a label: TBNN_LIK_BERNOULLI or TBNN_LIK_CATEGORICAL (regression and "
+                              "count kinds: tbnn_ensemble_predictive and tbnn_ensemble_moments)");
+    if (cat && d_out < 2) return fail(-1, who + ": the categorical likelihood needs at least 2 outputs (one logit per class)");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    Buf<double> acc;
+    Buf<float> dW;
+    long tot = 0, rt = 0, nrows = 0;
+    ENS_TRY(ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, ens_chunk_floats(),
+        [&](long rows, int) -> int {
+            nrows = rows;
+            tot = rows * d_out;
+            rt = cat ? rows : tot;                          // the entropies: one per row, Bernoulli one per element
+            HIPCHK(acc.alloc(2 * (size_t)tot + 3 * (size_t)rt));
+            if (net_w) ENS_TRY(ens_upload(h, dW, net_w, (size_t)m));
+            return 0;
+        },
+        [&](int i0, int c, const float* dOut, long rows) -> int {
+            const float* w = net_w ? dW + i0 : nullptr;
+            if (cat)
+                hipLaunchKernelGGL(k_ens_uncert_softmax, dim3(ens_grid(rows)), dim3(ENS_TB), 0, h->stream, dOut, c, rows, d_out, w, (int)(i0 == 0),
+                                   (double*)acc);
+            else
+                hipLaunchKernelGGL(k_ens_uncert, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, dOut, c, tot, w, (int)(i0 == 0), (double*)acc);
+            HIPCHK(hipGetLastError());
+            return 0;
+        }));
+    if (cat) hipLaunchKernelGGL(k_ens_uncert_finish_softmax, dim3(ens_grid(nrows)), dim3(ENS_TB), 0, h->stream, (double*)acc, nrows, d_out, W);
+    else hipLaunchKernelGGL(k_ens_uncert_finish, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, tot, W);
+    HIPCHK(hipGetLastError());
+    // the buffer's planes in order: pbar, vote [d_out][n]; aleatoric, total, epistemic [rt]
+    double* const outs[5] = {prob_out, vote_out, aleatoric_out, total_out, epistemic_out};
+    const size_t offs[5] = {0, (size_t)tot, 2 * (size_t)tot, 2 * (size_t)tot + (size_t)rt, 2 * (size_t)tot + 2 * (size_t)rt};
+    for (int k = 0; k < 5; ++k)
+        if (outs[k]) HIPCHK(hipMemcpyAsync(outs[k], acc + offs[k], (size_t)(k < 2 ? tot : rt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 extern "C" int tbnn_ensemble_quantiles(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int method,
                                        int xform, float scale, float shift, int which, const float* X, int64_t n, const double* probs,
                                        int32_t n_probs, double* out) {

@@ -12,6 +12,13 @@
 //             summed over its outputs); k_ens_lppd_finish: M + log S - log W.  Per network, the rows of a workgroup are summed over the
 //             wavefront (shuffles), then over the four waves through LDS in a fixed order, into part[workgroup][network]; the host adds
 //             the workgroups in index order, so the per-network sums are the same from run to run.
+//   uncertainty acc = S[d_out n], V[d_out n], A[rt], then two result planes [rt] (rt = n categorical, d_out n Bernoulli): the plain sums
+//             S_k = sum_i w_i p_ik of each network's own label probabilities, V_k = sum_i w_i [a_i == k] of its votes (Bernoulli:
+//             [p_i >= 1/2]) and A = sum_i w_i H_i of its entropies H_i = -sum_k p_ik log p_ik -- the direct form, log and sum in fp64
+//             from the fp32 p_ik, 0 log 0 = 0.  The values lie in [0, 1]: no shift.  A later chunk reads the three back and goes on in
+//             network order.  k_ens_uncert_finish*: pbar = S / W, vote = V / W, total = H[pbar], aleatoric = A / W, epistemic =
+//             total - aleatoric, not below 0 (Jensen: only rounding takes it there).  A NaN among a row's values under any network
+//             makes every output of the row NaN, whatever that network's weight.  Contraction off.
 //
 //   quantiles the block [m][d_out][rb] of ALL m networks over a block of rows (a quantile needs every network's value of an element at once,
 //             so the host cuts the rows, not the networks).  k_ens_transform writes t_i over f_i in place; k_ens_quantiles selects order
@@ -129,6 +136,129 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_moments_finish(double* __restric
         const double m1 = acc[tot + e] / W;
         acc[e] += m1;
         acc[tot + e] = fmax(fma(-m1, m1, acc[2 * tot + e] / W), 0.0);
+    }
+}
+
+// ---- classification uncertainty: entropy split and votes (tbnn_ensemble_uncertainty) ----
+// -x log x in fp64, 0 at x = 0 (a NaN stays NaN: the comparison is false)
+__device__ __forceinline__ double ens_neg_xlogx(double x) {
+#pragma clang fp contract(off)
+    return x == 0.0 ? 0.0 : -(x * log(x));
+}
+
+// Bernoulli: an element is an (output, row) pair, as in k_ens_moments.  acc: S[tot], V[tot], A[tot] (then the finish kernel's two planes).
+// p = clip(f, 1e-8, 1 - 1e-7) in fp32 (ens_row_loglik's clip, which swallows a NaN: it is carried beside the sums instead)
+__global__ __launch_bounds__(ENS_TB) void k_ens_uncert(const float* __restrict__ out, int c, long tot, const float* __restrict__ w, int first,
+                                                        double* __restrict__ acc) {
+#pragma clang fp contract(off)
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
+        double s = 0.0, v = 0.0, a = 0.0;
+        if (!first) { s = acc[e]; v = acc[tot + e]; a = acc[2 * tot + e]; }
+#pragma unroll 4
+        for (int i = 0; i < c; ++i) {
+            const float f = out[(size_t)i * tot + e];
+            const float p = fminf(fmaxf(f, 1e-8f), 1.f - 1e-7f);
+            const double pd = (double)p, wi = w ? (double)w[i] : 1.0;
+            const double bad = f != f ? (double)NAN : 0.0;
+            const double h = -(pd * log(pd) + (1.0 - pd) * log1p(-pd));
+            s += wi * pd + bad;
+            v += wi * (p >= 0.5f ? 1.0 : 0.0) + bad;
+            a += wi * h + bad;
+        }
+        acc[e] = s; acc[tot + e] = v; acc[2 * tot + e] = a;
+    }
+}
+
+// in place: S <- pbar, V <- vote, A <- aleatoric; the two planes behind them <- total, epistemic
+__global__ __launch_bounds__(ENS_TB) void k_ens_uncert_finish(double* __restrict__ acc, long tot, double W) {
+#pragma clang fp contract(off)
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
+        const double pb = acc[e] / W, q = 1.0 - pb;
+        const double t1 = pb == 0.0 ? 0.0 : pb * log(pb), t2 = q == 0.0 ? 0.0 : q * log1p(-pb);
+        const double total = -(t1 + t2), al = acc[2 * tot + e] / W, d = total - al;
+        acc[e] = pb;
+        acc[tot + e] = acc[tot + e] / W;
+        acc[2 * tot + e] = al;
+        acc[3 * tot + e] = total;
+        acc[4 * tot + e] = d < 0.0 ? 0.0 : d;                    // (a select, not fmax: a NaN stays NaN)
+    }
+}
+
+// Categorical: a thread owns a row.  acc: S[d_out][n], V[d_out][n], A[n] (then the finish kernel's two planes [n]).  Per network the
+// walks of k_ens_moments_softmax (maximum, sum) and a third over the probabilities p_k = ens_exp_diff(f_k, max) / s themselves: the vote
+// a_i, the smallest k with p_k maximal, and -- in the first tile's pass only -- the entropy H_i.  ENS_KT classes' S and V sit in
+// registers at a time and the walks are repeated for the next ENS_KT.  A NaN logit makes s, every p_k and H_i NaN; the votes get it from s.
+__global__ __launch_bounds__(ENS_TB) void k_ens_uncert_softmax(const float* __restrict__ out, int c, long n, int d_out, const float* __restrict__ w,
+                                                                int first, double* __restrict__ acc) {
+    const long tot = n * d_out;
+    for (long row = (long)blockIdx.x * ENS_TB + threadIdx.x; row < n; row += (long)gridDim.x * ENS_TB) {
+        for (int k0 = 0; k0 < d_out; k0 += ENS_KT) {
+            double s1[ENS_KT], v1[ENS_KT], a = 0.0;
+#pragma unroll
+            for (int j = 0; j < ENS_KT; ++j) {
+                const bool on = !first && k0 + j < d_out;
+                const long e = (long)(k0 + j) * n + row;
+                s1[j] = on ? acc[e] : 0.0; v1[j] = on ? acc[tot + e] : 0.0;
+            }
+            if (k0 == 0 && !first) a = acc[2 * tot + row];
+            for (int i = 0; i < c; ++i) {
+                const float* __restrict__ f = out + (size_t)i * tot + row;
+                float mx = -INFINITY, s = 0.f;
+                for (int k = 0; k < d_out; ++k) mx = fmaxf(mx, f[(size_t)k * n]);
+                for (int k = 0; k < d_out; ++k) s += ens_exp_diff(f[(size_t)k * n], mx);
+                // (mx and s above: the statements of k_ens_moments_softmax, contracted as there -- the same p_k bit for bit; fp64 below)
+                {
+#pragma clang fp contract(off)
+                    const double wi = w ? (double)w[i] : 1.0;
+                    const double bad = s != s ? (double)NAN : 0.0;
+                    float best = -1.f;
+                    int arg = 0;
+                    double hsum = 0.0;
+                    for (int k = 0; k < d_out; ++k) {
+                        const float p = ens_exp_diff(f[(size_t)k * n], mx) / s;
+                        if (p > best) { best = p; arg = k; }
+                        if (k0 == 0) hsum += ens_neg_xlogx((double)p);
+                    }
+                    if (k0 == 0) a += wi * hsum;
+#pragma unroll
+                    for (int j = 0; j < ENS_KT; ++j) {
+                        if (k0 + j < d_out) {
+                            const double p = (double)(ens_exp_diff(f[(size_t)(k0 + j) * n], mx) / s);
+                            s1[j] += wi * p;
+                            v1[j] += wi * (arg == k0 + j ? 1.0 : 0.0) + bad;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < ENS_KT; ++j) {
+                if (k0 + j < d_out) {
+                    const long e = (long)(k0 + j) * n + row;
+                    acc[e] = s1[j]; acc[tot + e] = v1[j];
+                }
+            }
+            if (k0 == 0) acc[2 * tot + row] = a;
+        }
+    }
+}
+
+// in place: S <- pbar, V <- vote, A <- aleatoric; the two planes [n] behind them <- total = H[pbar] (classes in index order), epistemic
+__global__ __launch_bounds__(ENS_TB) void k_ens_uncert_finish_softmax(double* __restrict__ acc, long n, int d_out, double W) {
+#pragma clang fp contract(off)
+    const long tot = n * d_out;
+    for (long row = (long)blockIdx.x * ENS_TB + threadIdx.x; row < n; row += (long)gridDim.x * ENS_TB) {
+        double total = 0.0;
+        for (int k = 0; k < d_out; ++k) {
+            const long e = (long)k * n + row;
+            const double pb = acc[e] / W;
+            total += ens_neg_xlogx(pb);
+            acc[e] = pb;
+            acc[tot + e] = acc[tot + e] / W;
+        }
+        const double al = acc[2 * tot + row] / W, d = total - al;
+        acc[2 * tot + row] = al;
+        acc[2 * tot + n + row] = total;
+        acc[2 * tot + 2 * n + row] = d < 0.0 ? 0.0 : d;            // (a select, not fmax: a NaN stays NaN)
     }
 }
 

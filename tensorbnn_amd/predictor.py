@@ -455,6 +455,119 @@ class predictor(object):
                                            likelihood=lik.kind, sd=self._network_sd(lik, n), weights=w)
         return (Fb, F) if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) else F
 
+    # ---- classification: entropy split, votes (tbnn_ensemble_uncertainty) and calibration of the posterior-mean classifier ----
+    def _label_likelihood(self, likelihood):
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, (BernoulliLikelihood, CategoricalLikelihood)):
+            raise ValueError("the entropy split, the votes and the calibration table are those of a label: a BernoulliLikelihood or a "
+                             "CategoricalLikelihood; for a regression predictMoments(noiseVariance=True) separates the noise from the "
+                             "posterior spread and predictiveInterval / predictiveCDF check the intervals")
+        return lik
+
+    def predictUncertainty(self, inputMatrix, n=1, weights=None, likelihood=None):
+        """How sure is the ensemble of a label, and why?  Over every n-th network, reduced on the device (the definition is in
+        include/tbnn.h, tbnn_ensemble_uncertainty), a dict of float64 arrays: probs [d_out, rows], the posterior-mean probability of each
+        class (BernoulliLikelihood: of the label 1 of each output); votes [d_out, rows], the share of the posterior whose own arg-max is that
+        class (Bernoulli: whose p >= 1/2); total, the entropy of probs; aleatoric, the posterior mean of each network's own entropy (noise
+        in the data); epistemic = total - aleatoric >= 0, the mutual information between label and network ("BALD": what the networks
+        disagree about); variation_ratio = 1 - max_k votes_k (Bernoulli: 1 - max(vote, 1 - vote)).  The entropies and the variation ratio
+        are [rows] under a CategoricalLikelihood and [d_out, rows] under a BernoulliLikelihood, natural logarithms.  likelihood None: the
+        predictor's own; a regression or count likelihood is refused.  weights: one per picked network, e.g. what reweight returns."""
+        from .likelihood import CategoricalLikelihood
+        lik = self._label_likelihood(likelihood)
+        picked, w = self._picked(n, weights)
+        ch = self._ensure_chain()
+        out = ch.ensemble_uncertainty(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, likelihood=lik.kind)
+        v = out["votes"]
+        out["variation_ratio"] = 1.0 - (v.max(axis=0) if isinstance(lik, CategoricalLikelihood) else np.maximum(v, 1.0 - v))
+        return out
+
+    @staticmethod
+    def _check_bins(bins):
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= 1000:
+            raise ValueError("bins must be an integer in 1 .. 1000")
+        return int(bins)
+
+    @staticmethod
+    def _calibration_table(probs, Y, bins, kind):
+        """The reliability table of a classifier that predicts the probabilities probs, float64 [d_out, rows], against the labels Y; kind
+        "categorical" (the columns of probs are class probabilities; Y one-hot or probability rows [rows, K], label = the first arg-max, or
+        an integer vector [rows]) or "bernoulli" (every output a label of its own, the entry the probability of 1, clipped to
+        [1e-8, 1 - 1e-7] first; Y [rows, d_out] or [rows] of 0 / 1, label = y >= 1/2).  Host only, NumPy; see calibration for the result."""
+        bins = predictor._check_bins(bins)
+        if kind not in ("categorical", "bernoulli"):
+            raise ValueError("kind must be 'categorical' or 'bernoulli'")
+        p = np.asarray(probs, dtype=np.float64)
+        if p.ndim != 2:
+            raise ValueError("probs must be [d_out, rows]")
+        K, rows = p.shape
+        y = np.asarray(Y)
+        if kind == "categorical":
+            if y.ndim == 1:
+                if y.size != rows:
+                    raise ValueError(f"Y must hold {rows} labels")
+                label = y.astype(np.int64)
+                if np.any(label != y) or np.any(label < 0) or np.any(label >= K):
+                    raise ValueError(f"integer labels must lie in 0 .. {K - 1}")
+            else:
+                if y.shape != (rows, K):
+                    raise ValueError(f"Y must be [{rows}, {K}] or an integer vector [{rows}]")
+                label = np.argmax(y, axis=1)
+            predicted = np.argmax(p, axis=0)                                    # (the first of equal maxima: ties to the lowest class)
+            confidence = p[predicted, np.arange(rows)]
+            correct = predicted == label
+            with np.errstate(divide="ignore"):
+                nll = float(np.mean(-np.log(p[label, np.arange(rows)])))
+            onehot = np.zeros((K, rows))
+            onehot[label, np.arange(rows)] = 1.0
+            brier = float(np.mean(np.sum((p - onehot) ** 2, axis=0)))
+        else:
+            y = y.reshape(rows, K) if y.size == rows * K else None
+            if y is None:
+                raise ValueError(f"Y must be [{rows}, {K}]")
+            label = (y.T >= 0.5)
+            p = np.clip(p, np.float64(np.float32(1e-8)), np.float64(np.float32(1.0) - np.float32(1e-7)))
+            predicted = p >= 0.5
+            confidence = np.maximum(p, 1.0 - p)
+            correct = predicted == label
+            nll = float(np.mean(-np.where(label, np.log(p), np.log1p(-p))))
+            brier = float(np.mean((p - label) ** 2))
+            predicted = predicted.astype(np.int64)
+        edges = np.linspace(0.0, 1.0, bins + 1)
+        # right-closed bins (e_{b-1}, e_b], 0 in the first
+        idx = np.clip(np.searchsorted(edges, confidence, side="left") - 1, 0, bins - 1)
+        count = np.bincount(idx.reshape(-1), minlength=bins)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            conf_b = np.bincount(idx.reshape(-1), weights=confidence.reshape(-1), minlength=bins) / count
+            acc_b = np.bincount(idx.reshape(-1), weights=correct.reshape(-1).astype(np.float64), minlength=bins) / count
+        conf_b[count == 0] = np.nan
+        acc_b[count == 0] = np.nan
+        gap = np.abs(acc_b - conf_b)
+        full = count > 0
+        return {"accuracy": float(np.mean(correct)), "nll": nll, "brier": brier,
+                "ece": float(np.sum(count[full] / confidence.size * gap[full])), "mce": float(np.max(gap[full])),
+                "bins": {"edges": edges, "count": count, "confidence": conf_b, "accuracy": acc_b},
+                "predicted": predicted, "confidence": confidence, "correct": correct}
+
+    def calibration(self, inputMatrix, realVals, bins=10, n=1, weights=None, likelihood=None):
+        """Is the ensemble's sureness honest?  The reliability table of the posterior-mean classifier (predictUncertainty's probs) against
+        held-out labels -- the classification counterpart of predictiveCDF's PIT values.  The probabilities come from the device; the table
+        is d_out x rows doubles of NumPy on the host.  Labels: CategoricalLikelihood one-hot or probability rows [rows, K] (label = the
+        first arg-max) or an integer vector [rows]; BernoulliLikelihood [rows, d_out] or [rows] of 0 / 1 (label = y >= 1/2).  Returns a
+        dict: accuracy; nll, the mean of -log pbar_label (Bernoulli: from pbar clipped to [1e-8, 1 - 1e-7]); brier, the mean over the rows
+        of sum_k (pbar_k - y_k)^2 (Bernoulli: the mean over the elements of the square); ece = sum_b n_b / n |acc_b - conf_b| and
+        mce = max_b |acc_b - conf_b| over the non-empty bins; bins: edges, count, confidence, accuracy -- `bins` (1 .. 1000) equal-width
+        bins over [0, 1], right-closed, 0 in the first, an empty bin with count 0 and NaN means; and the row arrays predicted (arg-max,
+        ties to the lowest class; Bernoulli pbar >= 1/2), confidence (max_k pbar_k; Bernoulli max(pbar, 1 - pbar)) and correct."""
+        from .likelihood import CategoricalLikelihood
+        lik = self._label_likelihood(likelihood)
+        bins = self._check_bins(bins)                                                     # (before the device is asked for anything)
+        picked, w = self._picked(n, weights)
+        ch = self._ensure_chain()
+        probs = ch.ensemble_uncertainty(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, likelihood=lik.kind)["probs"]
+        return self._calibration_table(probs, realVals, bins, "categorical" if isinstance(lik, CategoricalLikelihood) else "bernoulli")
+
     def _ensure_chain(self):
         if self._chain is None:
             self._chain = nat.Chain(self._descriptor(), likelihood=nat.LIK_FIXED_GAUSSIAN, fixed_sd=1.0,
