@@ -30,13 +30,19 @@ tf.float32 everywhere: Examples/trainRegression.py:41, layer.py:116,
 paramAdapter.py:60); ``np.float64`` is the high-precision arm used to bound
 rounding error.
 
-EXTENSIONS BEYOND THE REFERENCE.  The categorical and Poisson likelihoods and
-the per-row likelihood weights ``w`` are the library's own (definitions:
-``include/tbnn.h`` TBNN_LIK_CATEGORICAL / TBNN_LIK_POISSON /
+EXTENSIONS BEYOND THE REFERENCE.  The categorical, Poisson, Student-t,
+negative-binomial and heteroscedastic Gaussian likelihoods and the per-row
+likelihood weights ``w`` are the library's own (definitions: ``include/tbnn.h``
+TBNN_LIK_CATEGORICAL / _POISSON / _STUDENT_T / _NEG_BINOMIAL / _HETERO_GAUSSIAN,
 tbnn_set_row_weights, ``tensorbnn_amd/likelihood.py``): there are no reference
 lines to cite, and torch.autograd alone pins them (tests/test_oracle.py).  Their
 docstrings say "extension".  With ``w=None`` the Gaussian, fixed-sd Gaussian
-and Bernoulli paths are the reference's, operation by operation.
+and Bernoulli paths are the reference's, operation by operation.  The element
+functions of the last three have two arms of their own: ``np.float64`` is the
+definition as written, ``np.float32`` the kernels' operation order
+(``csrc/common.hpp`` log1p_fast, negbin_term, hetero_pair); in both the terms
+are summed in fp64 and the constant is fp64, as the library's accumulators do,
+and the value is a float64.
 """
 from __future__ import annotations
 
@@ -55,7 +61,9 @@ ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_EXP, ACT_ELU = 0, 1, 2, 3, 4, 5
 PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
 LIK_CATEGORICAL, LIK_POISSON = 3, 5       # extensions: include/tbnn.h TBNN_LIK_* (4 is unassigned)
-LIKELIHOODS = (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON)
+LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN = 8, 10, 12     # extensions too (the codes between are unassigned)
+LIKELIHOODS = (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON,
+               LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN)
 
 
 @dataclass
@@ -75,7 +83,8 @@ class DenseSpec:
 class NetSpec:
     layers: List[DenseSpec]
     likelihood: int = LIK_GAUSSIAN
-    fixed_sd: float = 0.1          # FixedGaussianLikelihood(sd=...) likelihood.py:138-141
+    fixed_sd: float = 0.1          # FixedGaussianLikelihood(sd=...) likelihood.py:138-141; the Student-t scale (extension)
+    lik_df: float = 0.0            # extension (NetDev::lik_df): Student-t degrees of freedom nu, negative-binomial dispersion r
 
     @property
     def n_params(self) -> int:
@@ -279,6 +288,176 @@ def _log_softmax(f):
     return z - np.log(np.exp(z).sum(axis=0, keepdims=True))
 
 
+def student_scale(spec: NetSpec):
+    """extension: the Student-t scale s, spec.fixed_sd as the library receives it (fp32), clipped to [1e-8, 1e8] as the Gaussian kinds
+    clip theirs."""
+    return min(max(float(np.float32(spec.fixed_sd)), 1e-8), 1e8)
+
+
+def student_const(nu, s):
+    """extension: lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log s, the constant of one (row, output) element, fp64."""
+    nu = float(nu)
+    return math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi) - math.log(float(s))
+
+
+def log1p_kernel32(u):
+    """extension: csrc/common.hpp log1p_fast in fp32 NumPy: the series 2 z (1 + z^2/3 + z^4/5 + z^6/7), z = u / (2 + u), below u = 1/4
+    and log(1 + u) from there on."""
+    u = np.asarray(u, dtype=np.float32)
+    one, two = np.float32(1), np.float32(2)
+    with np.errstate(over="ignore", invalid="ignore"):
+        z = u * (one / (two + u))
+        z2 = z * z
+        ser = (two * z) * (z2 * (z2 * (z2 * np.float32(1.0 / 7.0) + np.float32(0.2)) + np.float32(1.0 / 3.0)) + one)
+        return np.where(u < np.float32(0.25), ser, np.log(one + u)).astype(np.float32)
+
+
+def student_elementwise(f, Y, nu, s, dtype):
+    """extension: (log1p(r^2 / (nu s^2)), dL/df = (nu+1) r / (nu s^2 + r^2)), r = y - f, each [d_out, n] in ``dtype``; f [d_out, n],
+    Y [n, d_out] (or flat).  np.float64: as written, np.log1p and a division.  np.float32: the kernel's operations (log1p_fast,
+    kernels_fast.hpp lik_delta): k = 1 / (nu s^2), u = r r k, log1p_kernel32(u), the delta (nu + 1) (r k) / (1 + u)."""
+    dt = dtype
+    f = np.asarray(f, dtype=dt)
+    y = np.asarray(Y, dtype=dt).reshape(f.shape[1], -1).T
+    r = y - f
+    if dt == np.float64:
+        ns2 = float(nu) * float(s) ** 2
+        return np.log1p(r * r / ns2), (float(nu) + 1.0) * r / (ns2 + r * r)
+    nu32, s32 = np.float32(nu), np.float32(s)
+    k = np.float32(1) / (nu32 * s32 * s32)
+    u = r * r * k
+    d = (nu32 + np.float32(1)) * (r * k) * (np.float32(1) / (np.float32(1) + u))
+    return log1p_kernel32(u), d.astype(np.float32)
+
+
+def student_terms(f, Y, nu, s):
+    """extension: the Student-t log density per (output, row), fp64 [d_out, n]:
+    lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log s - (nu+1)/2 log1p(r^2 / (nu s^2))."""
+    t, _d = student_elementwise(f, Y, nu, s, np.float64)
+    return student_const(nu, s) - 0.5 * (float(nu) + 1.0) * t
+
+
+def negbin_const_terms(Y, r):
+    """extension: lgamma(y + r) - lgamma(r) - lgamma(y + 1) per target, fp64 (the shape of Y)."""
+    y = np.asarray(Y, dtype=np.float64)
+    return lgamma(y + float(r)) - math.lgamma(float(r)) - lgamma(y + 1.0)
+
+
+def negbin_elementwise(f, Y, r, dtype):
+    """extension: (y log p + r log q, dL/df = y q - r p), f the log of the mean mu, r the dispersion, p = mu / (r + mu), q = r / (r + mu),
+    each [d_out, n] in ``dtype``; f [d_out, n], Y [n, d_out] (or flat).  np.float64: as written, log(r + mu) through np.logaddexp, the
+    delta as r (y - mu) / (r + mu).  np.float32: the kernel's operations (negbin_term): t = f - log r, a = |t|, e = exp(-a),
+    l = log1p_kernel32(e), -log p = max(-t, 0) + l, -log q = max(t, 0) + l, p and q from e and one reciprocal of 1 + e by the sign of t."""
+    dt = dtype
+    f = np.asarray(f, dtype=dt)
+    y = np.asarray(Y, dtype=dt).reshape(f.shape[1], -1).T
+    if dt == np.float64:
+        r = float(r)
+        lr = math.log(r)
+        lden = np.logaddexp(f, lr)                               # log(r + mu)
+        with np.errstate(over="ignore"):
+            mu = np.exp(f)
+            d = np.where(np.isfinite(mu), r * (y - mu) / (r + mu), -r)
+        return y * (f - lden) + r * (lr - lden), d
+    one = np.float32(1)
+    r32 = np.float32(r)
+    lr = np.log(r32)                                             # (fp32: the kernels' logf of the prologue)
+    t = f - lr
+    a = np.abs(t)
+    e = np.exp(-a).astype(np.float32)
+    l = log1p_kernel32(e)
+    nlp = np.maximum(-t, np.float32(0)) + l
+    nlq = np.maximum(t, np.float32(0)) + l
+    rc = one / (one + e)
+    s = e * rc
+    pos = t >= 0
+    p, q = np.where(pos, rc, s), np.where(pos, s, rc)
+    return (-(y * nlp + r32 * nlq)).astype(np.float32), (y * q - r32 * p).astype(np.float32)
+
+
+def negbin_terms(f, Y, r):
+    """extension: the negative-binomial log density per (output, row), fp64 [d_out, n]:
+    lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y log p + r log q."""
+    f = np.asarray(f, dtype=np.float64)
+    t, _d = negbin_elementwise(f, Y, r, np.float64)
+    return t + negbin_const_terms(np.asarray(Y, dtype=np.float64).reshape(f.shape[1], -1).T, r)
+
+
+_FP64_DATA_TERM = (LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN)     # summed by _data_term
+LOG_CLIP = math.log(1e8)                      # the heteroscedastic clip of the log-sd output
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def hetero_targets(Y, n):
+    """extension: the one target per row, [n]: Y is [n], [n, 1] or [n, 2] (column 0)."""
+    Y = np.asarray(Y)
+    return Y.reshape(n) if Y.size == n else Y.reshape(n, -1)[:, 0]
+
+
+def hetero_pair(f, Y, dtype):
+    """extension: (the row terms -gc - 1/2 r^2 u [n], the deltas [2, n]: dL/df = r u and dL/dg = r^2 u - 1 for -G <= g <= G, else 0) in
+    ``dtype``; f [2, n]: output 0 the mean, output 1 the log-sd g; G = log(1e8), gc = min(max(g, -G), G), u = exp(-2 gc), r = y - f.
+    The operations are the kernel's, in its order (hetero_pair): the clip as two selects, u, r, ru = r u, q = r ru, the term
+    -gc - 1/2 q, the deltas ru and q - 1; np.float64 runs the same ones."""
+    dt = dtype
+    f = np.asarray(f, dtype=dt)
+    assert f.shape[0] == 2
+    y = np.asarray(hetero_targets(Y, f.shape[1]), dtype=dt)
+    G = dt(LOG_CLIP)
+    g = f[1]
+    gc = np.where(g < -G, -G, g)
+    gc = np.where(g > G, G, gc).astype(dt)
+    inside = (g >= -G) & (g <= G)
+    with np.errstate(over="ignore"):
+        u = np.exp(dt(-2) * gc).astype(dt)
+        r = (y - f[0]).astype(dt)
+        ru = (r * u).astype(dt)
+        q = (r * ru).astype(dt)
+        term = (-gc - dt(0.5) * q).astype(dt)
+        dg = np.where(inside, q - dt(1), dt(0)).astype(dt)
+    return term, np.stack([ru, dg]).astype(dt)
+
+
+def hetero_terms(f, Y):
+    """extension: the heteroscedastic Gaussian log density per row, fp64 [n]: -1/2 log(2 pi) - gc - 1/2 r^2 u."""
+    t, _d = hetero_pair(np.asarray(f, dtype=np.float64), Y, np.float64)
+    return t - HALF_LOG_2PI
+
+
+def _data_term(spec: NetSpec, f, Y, dtype, w):
+    """extension: (the data term as a float64, the statistic sum_i w_i t_i as the kernels accumulate it) of the Student-t, negative-binomial
+    and heteroscedastic likelihoods: the element terms t in ``dtype``, a row's weight applied in ``dtype`` (the kernel: wt * term), the sum
+    and the constant in fp64.  A weighted row scales its share of the constant too (Student-t, heteroscedastic: sum(w) rows)."""
+    n = f.shape[1]
+    if spec.likelihood == LIK_STUDENT_T:
+        t, _d = student_elementwise(f, Y, spec.lik_df, student_scale(spec), dtype)
+    elif spec.likelihood == LIK_NEG_BINOMIAL:
+        t, _d = negbin_elementwise(f, Y, spec.lik_df, dtype)
+    elif spec.likelihood == LIK_HETERO_GAUSSIAN:
+        t, _d = hetero_pair(f, Y, dtype)
+    else:
+        raise ValueError(spec.likelihood)
+    if w is not None:
+        t = np.asarray(w, dtype=dtype) * t
+    stat = float(np.sum(t.astype(np.float64)))
+    rows = float(n) if w is None else float(np.sum(np.asarray(w, dtype=np.float64)))
+    if spec.likelihood == LIK_STUDENT_T:
+        nu, s = spec.lik_df, student_scale(spec)
+        return np.float64(rows * f.shape[0] * student_const(nu, s) - 0.5 * (float(nu) + 1.0) * stat), stat
+    if spec.likelihood == LIK_HETERO_GAUSSIAN:
+        return np.float64(stat - HALF_LOG_2PI * rows), stat
+    c = negbin_const_terms(np.asarray(Y, dtype=np.float64).reshape(n, -1).T, spec.lik_df)          # [d_out, n]
+    if w is not None:
+        c = np.asarray(w, dtype=np.float64) * c
+    return np.float64(stat + float(np.sum(c))), stat
+
+
+def data_statistic(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
+    """extension: the statistic the kernels accumulate for the Student-t (sum w log1p(u)), negative-binomial (sum w (y log p + r log q))
+    and heteroscedastic (sum w (-gc - 1/2 r^2 u)) likelihoods: their data term less its constant and, for Student-t, its factor."""
+    return _data_term(spec, np.asarray(f, dtype=dtype), Y, dtype, w)[1]
+
+
 def log_likelihood(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
     """makeResponseLikelihood summed (network.py:388-391): Gaussian
     likelihood.py:69-96, fixed :143-169, Bernoulli :210-237.  f is [d_out,n].
@@ -287,9 +466,13 @@ def log_likelihood(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
     categorical: sum_k y_k (f_k - m - log sum_j exp(f_j - m)), m the row's max, labels one-hot or soft;
     Poisson: y f - exp(f) - lgamma(y + 1), returned in fp64 in either arm (it carries the fp64 constant);
     ``w``: one weight >= 0 per row (None = 1) scales the row's term before the sum, and a Gaussian row counts w_i times
-    (the row count becomes sum w)."""
+    (the row count becomes sum w);
+    Student-t, negative binomial, heteroscedastic Gaussian: :func:`student_terms`, :func:`negbin_terms`, :func:`hetero_terms` summed
+    by :func:`_data_term`, a float64 in either arm as well."""
     dt = dtype
     f = np.asarray(f, dtype=dt)
+    if spec.likelihood in _FP64_DATA_TERM:
+        return _data_term(spec, f, Y, dt, w)[0]
     if w is not None:
         w = np.asarray(w, dtype=dt)
     if spec.likelihood in (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN):
@@ -334,6 +517,8 @@ def target_log_prob(spec: NetSpec, theta, eta, X, Y, dtype=np.float32, w=None):
     if spec.likelihood == LIK_POISSON:      # extension: (priors + data term) - C in fp64, the library's order, in either arm
         data, const = _poisson_terms(f, Y, dt, w)
         return np.float64(prob) + np.float64(data) - const
+    if spec.likelihood in _FP64_DATA_TERM:  # extension: priors + data term in fp64, in either arm
+        return np.float64(prob) + log_likelihood(spec, eta, f, Y, dt, w)
     return dt(prob + log_likelihood(spec, eta, f, Y, dt, w))         # :388-391
 
 
@@ -356,8 +541,9 @@ def prior_grad(l: DenseSpec, h4, W, b, dtype=np.float32):
 
 
 def likelihood_grad(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
-    """dL/df [d_out, n] of :func:`log_likelihood`.  Extensions: categorical y_k - softmax_k sum_j y_j, Poisson y - exp(f), and
-    ``w`` scaling a row's dL/df."""
+    """dL/df [d_out, n] of :func:`log_likelihood`.  Extensions: categorical y_k - softmax_k sum_j y_j, Poisson y - exp(f), the deltas
+    of :func:`student_elementwise`, :func:`negbin_elementwise` and :func:`hetero_pair` ([2, n]: dL/df and dL/dg), and ``w`` scaling a
+    row's dL/df."""
     dt = dtype
     n = f.shape[1]
     if spec.likelihood in (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN):
@@ -375,6 +561,12 @@ def likelihood_grad(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
         d_a = y - np.exp(_log_softmax(f)) * y.sum(axis=0, keepdims=True)
     elif spec.likelihood == LIK_POISSON:
         d_a = np.asarray(Y, dtype=dt).reshape(n, -1).T - np.exp(f)
+    elif spec.likelihood == LIK_STUDENT_T:
+        d_a = student_elementwise(f, Y, spec.lik_df, student_scale(spec), dt)[1]
+    elif spec.likelihood == LIK_NEG_BINOMIAL:
+        d_a = negbin_elementwise(f, Y, spec.lik_df, dt)[1]
+    elif spec.likelihood == LIK_HETERO_GAUSSIAN:
+        d_a = hetero_pair(f, Y, dt)[1]
     else:
         raise ValueError(spec.likelihood)
     return d_a if w is None else np.asarray(w, dtype=dt) * d_a
@@ -466,6 +658,20 @@ def hmc_step(value_and_grad, q0, eps, L, p0, log_u, dtype=np.float32, energy_dty
                       sjd=sjd, trace_logp=trace, theta_proposed=q.copy(), p_final=p.copy())
 
 
+def likelihood_value_and_grad(spec: NetSpec, theta, eta, X, Y, dtype=np.float32, w=None):
+    """extension: the data log-likelihood alone and its gradient (tbnn_optimize's objective "likelihood"): the target minus its prior
+    terms."""
+    dt = dtype
+    lp, g = target_log_prob_and_grad(spec, theta, eta, X, Y, dt, w)
+    theta = np.asarray(theta, dtype=dt)
+    eta = np.asarray(eta, dtype=dt)
+    prior, pg = dt(0), []
+    for i, (l, (W, b)) in enumerate(zip(spec.layers, unflatten(spec, theta))):
+        prior = dt(prior + layer_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt))
+        pg.append(tuple(prior_grad(l, eta[4 * i:4 * i + 4], W, b, dt)))
+    return lp - prior, (g - flatten(pg).astype(dt)).astype(dt)
+
+
 def weight_step(spec, theta, eta, X, Y, eps, L, p0, log_u, dtype=np.float32, energy_dtype=None, w=None):
     """InnerStepMain, network.py:368-412."""
     vg = lambda q: target_log_prob_and_grad(spec, q, eta, X, Y, dtype, w)
@@ -486,7 +692,7 @@ def hyper_log_prob(spec: NetSpec, eta, theta, X, Y, dtype=np.float32, w=None):
     if spec.likelihood == LIK_GAUSSIAN:                              # mainProbsInHypers, likelihood.py:67
         f = forward(spec, theta, X, dt)
         prob = dt(prob + log_likelihood(spec, eta, f, Y, dt, w))     # :435-438
-    elif spec.likelihood not in LIKELIHOODS:                         # (the others have no hyper: the priors alone)
+    elif spec.likelihood not in LIKELIHOODS:                         # (the others have no hyper: the priors alone, X and Y unread)
         raise ValueError(spec.likelihood)
     return prob
 
@@ -886,12 +1092,12 @@ def load_networks(folder):
 # Synthetic workloads of BASELINE.md section 3 / SURVEY section 8(d)
 # ----------------------------------------------------------------------------
 def make_spec(dims, act=ACT_RELU, prior=PRIOR_CAUCHY, likelihood=LIK_GAUSSIAN, final_act=ACT_NONE,
-              fixed_sd=0.1):
+              fixed_sd=0.1, lik_df=0.0):
     layers = []
     for i in range(len(dims) - 1):
         last = i == len(dims) - 2
         layers.append(DenseSpec(dims[i], dims[i + 1], final_act if last else act, prior))
-    return NetSpec(layers, likelihood, fixed_sd)
+    return NetSpec(layers, likelihood, fixed_sd, lik_df)
 
 
 def synth_problem(dims, n, act=ACT_RELU, prior=PRIOR_CAUCHY, likelihood=LIK_GAUSSIAN):

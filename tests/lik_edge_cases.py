@@ -1,7 +1,7 @@
 """The datasets of tests/test_likelihood_edges_host.py and tests/test_gpu_likelihood_edges.py: the Poisson, Student-t, negative-binomial and
 heteroscedastic Gaussian likelihoods on the inputs where their element arithmetic (csrc/common.hpp log1p_fast, negbin_term, hetero_pair;
 kernels_fast.hpp lik_delta's Poisson branch) changes regime.  Importable without a GPU; no reference formula is stated here -- the fp64 and
-fp32 arms are those of student_ref, negbin_ref, hetero_ref and the oracle's Poisson.
+fp32 arms are the oracle's.
 
 A BAND is a range of the quantity the element code branches on (Student-t: u = (y - f)^2 / (nu s^2); negative binomial: t = f - log r;
 heteroscedastic Gaussian: g, the log-sd output; Poisson: the log-rate).  One dataset holds ONE band on every (row, output), so the band's
@@ -51,7 +51,7 @@ NEGBIN_BANDS = {           # sign (0: both), |t| range
     "deep+": (+1, 60.0, 104.0), "deep-": (-1, 60.0, 104.0),
     "far+": (+1, 1e3, 1e6), "far-": (-1, 1e3, 1e6),                    # far past the range of exp: e = 0
 }
-HETERO_CLIP = hr.LOG_CLIP
+HETERO_CLIP = o.LOG_CLIP
 HETERO_BANDS = {           # sign (0: both), |g| range
     "inside": (0, -3.0, 3.0),
     "near+": (+1, 16.0, 18.40), "near-": (-1, 16.0, 18.40),
@@ -113,14 +113,13 @@ def _pool(lik, case):
     return _POOL[key]
 
 
-def _spec(lik, dims, act, prior, s=1.0):
-    if lik == "student":
-        return sr.make_spec(dims, act, prior, s)
-    if lik == "negbin":
-        return nb.make_spec(dims, act, prior)
-    if lik == "hetero":
-        return hr.make_spec(dims, act, prior)
-    return o.make_spec(dims, act, prior, o.LIK_POISSON, o.ACT_NONE)
+LIK_CODE = {"student": o.LIK_STUDENT_T, "negbin": o.LIK_NEG_BINOMIAL, "hetero": o.LIK_HETERO_GAUSSIAN, "poisson": o.LIK_POISSON}
+
+
+def _spec(lik, dims, act, prior, s=1.0, df=0.0):
+    """s: the Student-t scale (the other likelihoods have none); df: nu (Student-t) or r (negative binomial)"""
+    scale = {"fixed_sd": float(s)} if lik == "student" else {}
+    return o.make_spec(dims, act, prior, LIK_CODE[lik], o.ACT_NONE, lik_df=float(df), **scale)
 
 
 def _placed(spec, theta, X, ranges):
@@ -188,13 +187,13 @@ def _build(lik, case, band):
     par, mix = {}, None
     if lik == "student":
         nu, s, lo, hi = STUDENT_BANDS[band]
-        spec = _spec(lik, dims, act, prior, s)
+        spec = _spec(lik, dims, act, prior, s, nu)
         idx = np.sort(rng.permutation(POOL)[:N_ROWS])
         X, theta = Xp[idx], theta0
         z = _z64(spec, theta, X)
         u = np.exp(rng.uniform(math.log(lo * 1.001), math.log(hi / 1.001), (N_ROWS, d_out)))
         sg = np.array([_sign(i_ds, k) for k in range(d_out)])
-        Y = (z.T + sg * sr.scale_of(spec) * np.sqrt(nu * u)).astype(np.float32)
+        Y = (z.T + sg * o.student_scale(spec) * np.sqrt(nu * u)).astype(np.float32)
         par = {"nu": nu, "s": s}
     else:
         if lik == "negbin":
@@ -217,7 +216,7 @@ def _build(lik, case, band):
             ranges = [("sd", 8.3, -95.4)] if d_out == 1 else [FLUSH_TOP if k % 2 == 0 else FLUSH_BOTTOM for k in range(d_out)]
         else:
             ranges = [POISSON_BANDS[band]] * d_out
-        spec = _spec(lik, dims, act, prior)
+        spec = _spec(lik, dims, act, prior, df=par.get("r", 0.0))
         theta, z, amax = _placed(spec, theta0, Xp, ranges)
         if lik == "poisson" and band == "high":
             # the fp32 gradient slabs hold sums of e^f a over the rows: keep n max|a| e^(z_max) below FLT_MAX / 16 (still inside the band)
@@ -256,7 +255,7 @@ def _build(lik, case, band):
         if lik == "negbin":
             for mix in MIXES:
                 Y = _counts(np.random.default_rng(rng.integers(1 << 30)), z, par["r"], mix)
-                if ratio(nb.elementwise(z, Y, par["r"], np.float64)[1]).max() <= 4.0:
+                if ratio(o.negbin_elementwise(z, Y, par["r"], np.float64)[1]).max() <= 4.0:
                     break
         elif lik == "hetero":
             rho = np.exp(rng.uniform(math.log(1e-3), math.log(1e2), N_ROWS))
@@ -292,12 +291,6 @@ def target(ds, dtype, w=None, theta=None, eta=None):
     th = ds.theta if theta is None else theta
     et = ds.eta if eta is None else eta
     with np.errstate(over="ignore", invalid="ignore"):
-        if ds.lik == "student":
-            return sr.target_log_prob_and_grad(ds.spec, ds.par["nu"], th, et, ds.X, ds.Y, dtype, w)
-        if ds.lik == "negbin":
-            return nb.target_log_prob_and_grad(ds.spec, ds.par["r"], th, et, ds.X, ds.Y, dtype, w)
-        if ds.lik == "hetero":
-            return hr.target_log_prob_and_grad(ds.spec, th, et, ds.X, ds.Y, dtype, w)
         return o.target_log_prob_and_grad(ds.spec, th, et, ds.X, ds.Y, dtype, w=w)
 
 
@@ -308,11 +301,7 @@ def statistic(ds, dtype, w=None):
     f = o.forward(ds.spec, ds.theta.astype(dt), ds.X.astype(dt), dt)
     with np.errstate(over="ignore", invalid="ignore"):
         if ds.lik == "student":
-            return sr.data_log_prob(ds.spec, ds.par["nu"], f, ds.Y, dt, w)[1]
-        if ds.lik == "negbin":
-            return nb.data_log_prob(ds.spec, ds.par["r"], f, ds.Y, dt, w)[0]
-        if ds.lik == "hetero":
-            return hr.data_log_prob(ds.spec, f, ds.Y, dt, w)[0]
+            return o.data_statistic(ds.spec, ds.eta, f, ds.Y, dt, w)
         return float(o.log_likelihood(ds.spec, ds.eta.astype(dt), f, ds.Y, dt, w))
 
 
@@ -320,16 +309,14 @@ def deltas(ds):
     """the data term's derivative [d_out, n] on the fp64 reference, and the branch quantity [d_out or 1, n]"""
     z = _z64(ds.spec, ds.theta, ds.X)
     with np.errstate(over="ignore"):
-        if ds.lik == "student":
-            s = sr.scale_of(ds.spec)
-            y = np.asarray(ds.Y, np.float64).reshape(z.shape[1], -1).T
-            return sr.elementwise(z, ds.Y, ds.par["nu"], s, np.float64)[1], (y - z) ** 2 / (ds.par["nu"] * s * s), z
-        if ds.lik == "negbin":
-            return nb.elementwise(z, ds.Y, ds.par["r"], np.float64)[1], z - math.log(float(np.float32(ds.par["r"]))), z
-        if ds.lik == "hetero":
-            return hr.pair(z, ds.Y, np.float64)[1], z[1:2], z
+        d = o.likelihood_grad(ds.spec, ds.eta, z, ds.Y, np.float64)
+    if ds.lik == "student":
+        s = o.student_scale(ds.spec)
         y = np.asarray(ds.Y, np.float64).reshape(z.shape[1], -1).T
-        return y - np.exp(z), z, z
+        return d, (y - z) ** 2 / (ds.par["nu"] * s * s), z
+    if ds.lik == "negbin":
+        return d, z - math.log(float(np.float32(ds.par["r"]))), z
+    return d, (z[1:2] if ds.lik == "hetero" else z), z
 
 
 def in_band(ds, q):

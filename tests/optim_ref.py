@@ -33,23 +33,9 @@ def adam_step(theta, g, m, v, vhat, t, lr, b1=B1, b2=B2, eps=EPS, amsgrad=True, 
     return theta.astype(dt), m.astype(dt), v.astype(dt), vhat.astype(dt)
 
 
-def likelihood_value_and_grad(spec, theta, eta, X, Y, dtype=np.float64, w=None):
-    """the data log-likelihood alone and its gradient: the oracle's target minus its prior terms"""
-    dt = dtype
-    lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt, w=w)
-    theta = np.asarray(theta, dtype=dt)
-    eta = np.asarray(eta, dtype=dt)
-    parts = o.unflatten(spec, theta)
-    prior, pg = dt(0), []
-    for i, (l, (W, b)) in enumerate(zip(spec.layers, parts)):
-        prior = prior + o.layer_log_prob(l, eta[4 * i:4 * i + 4], W, b, dt)
-        pg.append(tuple(o.prior_grad(l, eta[4 * i:4 * i + 4], W, b, dt)))
-    return lp - prior, (g - o.flatten(pg).astype(dt)).astype(dt)
-
-
 def value_and_grad(spec, theta, eta, X, Y, dtype=np.float64, w=None, objective="posterior"):
     if objective == "likelihood":
-        return likelihood_value_and_grad(spec, theta, eta, X, Y, dtype, w)
+        return o.likelihood_value_and_grad(spec, theta, eta, X, Y, dtype, w)
     return o.target_log_prob_and_grad(spec, theta, eta, X, Y, dtype, w=w)
 
 

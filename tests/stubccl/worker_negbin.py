@@ -28,13 +28,13 @@ SHAPES = {
 
 def problem(name):
     dims, n, act, prior, _jit, r = SHAPES[name]
-    return nb.problem_of(dims, n, act, prior, r) + (r,)
+    return nb.problem_of(dims, n, act, prior, r)
 
 
-def chain_of(name, spec, r):
+def chain_of(name, spec):
     jit = SHAPES[name][4]
     layers = [(l.in_dim, l.out_dim, l.act, l.prior) for l in spec.layers]
-    kw = dict(likelihood=nat.LIK_NEG_BINOMIAL, lik_df=r)
+    kw = dict(likelihood=nat.LIK_NEG_BINOMIAL, lik_df=spec.lik_df)
     if jit is None:
         return nat.Chain(layers, kernel=nat.KERNEL_GENERIC, **kw)
     return nat.Chain(layers, kernel=nat.KERNEL_AUTO, jit=jit, **kw)
@@ -44,8 +44,8 @@ def main():
     rank, world, idfile, outfile = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
     res = {}
     for name in SHAPES:
-        spec, X, Y, theta, eta, r = problem(name)
-        ch = chain_of(name, spec, r)
+        spec, X, Y, theta, eta = problem(name)
+        ch = chain_of(name, spec)
         comm = nat.Comm(ch, world, rank, exchange_id(rank, idfile + "." + name))
         lo, hi = parallel.shard_rows(ch, X, Y, comm)
         ch.set_state(theta); ch.set_hypers(eta)

@@ -1,8 +1,8 @@
 """GPU: HeteroscedasticGaussianLikelihood (TBNN_LIK_HETERO_GAUSSIAN) -- a 2-output network predicts the mean f and the log-sd g of each
 row, log p = -1/2 log(2 pi) - gc - 1/2 (y - f)^2 exp(-2 gc), gc = g clipped to +-log(1e8), ONE term per row -- on every kernel family that
 takes a 2-output network: the narrow fast3 and fast kernels and their one-launch trajectory kernel, mid, tall and wide (the VALU last
-layer), each likelihood path of the layered family (k_lay_tail, k_lay_last, k_lay_lik) and the generic kernel.  Against tests/hetero_ref.py
-in fp64 (the oracle has no such likelihood): the value with its constant, the gradient per tensor, the forward outputs, an injected weight
+layer), each likelihood path of the layered family (k_lay_tail, k_lay_last, k_lay_lik) and the generic kernel.  Against the oracle in fp64
+(the cases are tests/hetero_ref.py's): the value with its constant, the gradient per tensor, the forward outputs, an injected weight
 transition with both decisions (log u placed on either side of the reference's log accept ratio, two bands away), a hyper transition, every
 launch repeated bit for bit.  Then: the clip, row weights, refusals, target padding, the device metrics, trainChains against solo runs,
 pre-training, a row-sharded chain on the stub collective library, and an end-to-end fit on data whose noise grows 10x over the inputs
@@ -34,7 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FUSED = {"fast3": "", "fast": "fast3", "mid": "fast3,fast,tall,wide", "tall": "fast3,fast,mid,wide", "wide": "fast3,fast,mid,tall"}
 CASES = {k: v for k, v in hr.CASES.items() if v[4] != "traj"}
 NET = [1, 16, 16, 2]                                              # the network(...) of the trainChains and end-to-end tests (tanh)
-LIK = hr.LIK_HETERO_GAUSSIAN
+LIK = o.LIK_HETERO_GAUSSIAN
 LAY_KERNEL = {"lay_last": "last", "lay_separate": "lik", "lay_tail": "tail"}
 
 
@@ -69,14 +69,14 @@ def jit_jobs():
     jobs = []
     for dims, _n, act, prior, fam, _env in hr.CASES.values():
         if fam in FUSED:
-            jobs.append(job(hr.make_spec(dims, act, prior), skip=FUSED[fam]))
+            jobs.append(job(o.make_spec(dims, act, prior, LIK, o.ACT_NONE), skip=FUSED[fam]))
         elif fam == "traj":
-            jobs.append(job(hr.make_spec(dims, act, prior)))
-    jobs.append(job(hr.make_spec(*[hr.CASES["fast3"][i] for i in (0, 2, 3)]), weighted=True))
-    jobs.append(job(hr.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY)))
+            jobs.append(job(o.make_spec(dims, act, prior, LIK, o.ACT_NONE)))
+    jobs.append(job(o.make_spec(*[hr.CASES["fast3"][i] for i in (0, 2, 3)], LIK, o.ACT_NONE), weighted=True))
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE)))
     # the fixed-sd fit of the end-to-end test (1-16-16-1) and the predictors' forward chains (fixed-sd Gaussian handles)
     jobs.append(job(o.make_spec([1, 16, 16, 1], o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_FIXED_GAUSSIAN, o.ACT_NONE), lik=o.LIK_FIXED_GAUSSIAN))
-    jobs.append(job(hr.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY), lik=o.LIK_FIXED_GAUSSIAN))
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), lik=o.LIK_FIXED_GAUSSIAN))
     return [j for i, j in enumerate(jobs) if j not in jobs[:i]]
 
 
@@ -146,9 +146,9 @@ def test_value_gradient_forward(native, monkeypatch, name):
     check_value_gradient(name, lp, g, spec, hr.ref64(name))
     # stat is the data term with its constant (as Poisson's), and logp minus it the priors
     f64 = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
-    data64, _stat64 = hr.data_log_prob(spec, f64, Y, np.float64)
+    data64 = float(o.log_likelihood(spec, eta, f64, Y, np.float64))
     assert abs(st - data64) <= 4e-6 * abs(data64), (st, data64)
-    prior = float(hr.prior_log_prob(spec, theta, eta, np.float64))
+    prior = float(hr.ref64(name)[0] - data64)
     assert abs((lp - st) - prior) <= 4e-6 * max(abs(lp), 1.0)
     assert f.shape == (2, m)
     assert np.abs(f - f64[:, :m]).max() <= 1e-4 * max(1.0, np.abs(f64).max())
@@ -163,7 +163,7 @@ def test_transitions(native, monkeypatch, name):
     ch.set_data(X, Y)
     lp64 = hr.ref64(name)[0]
     eps = hr.step_size(name)
-    ref = hr.weight_step(spec, theta, eta, X, Y, eps, 4, p0, -1e30, np.float64)
+    ref = o.weight_step(spec, theta, eta, X, Y, eps, 4, p0, -1e30, np.float64)
     tol = 2e-2 + 1e-4 * abs(ref.log_accept_ratio) + 4e-7 * abs(lp64)
     # log u on either side of the reference's log accept ratio, two bands away: the kernel's rounding cannot flip the decision
     for log_u, accept in ((ref.log_accept_ratio - 2 * tol, True), (ref.log_accept_ratio + 2 * tol, False)):
@@ -183,13 +183,13 @@ def test_transitions(native, monkeypatch, name):
     ch.set_state(theta); ch.set_hypers(eta)
     ch.logp_grad(theta, eta)
     out = ch.hyper_step(1e-4, 9, p0=ph, log_u=-1e30)
-    ref = hr.hyper_step(spec, eta, theta, X, Y, 1e-4, 9, ph, -1e30, np.float64)
+    ref = o.hyper_step(spec, eta, theta, X, Y, 1e-4, 9, ph, -1e30, np.float64)
     assert abs(out["log_accept_ratio"] - ref.log_accept_ratio) <= 2e-2 + 1e-3 * abs(ref.log_accept_ratio)
     assert np.allclose(ch.get_hypers(), ref.theta, rtol=1e-4, atol=1e-5)
     # after the accepted hyper transition the cached gradient is refreshed for the new priors: the next weight step starts from it
     eta2 = ch.get_hypers()
     lp_new, g_new, _ = ch.logp_grad(theta, eta2)
-    check_value_gradient(name + " after the hyper step", lp_new, g_new, spec, hr.target_log_prob_and_grad(spec, theta, eta2, X, Y, np.float64))
+    check_value_gradient(name + " after the hyper step", lp_new, g_new, spec, o.target_log_prob_and_grad(spec, theta, eta2, X, Y, np.float64))
     ch.close()
 
 
@@ -208,7 +208,7 @@ def test_trajectory_kernel(native, monkeypatch):
     lp64 = hr.ref64("traj")[0]
     eps = hr.step_size("traj")
     for L in (1, 9):
-        ref = hr.weight_step(spec, theta, eta, X, Y, eps, L, p0, -1e30, np.float64)
+        ref = o.weight_step(spec, theta, eta, X, Y, eps, L, p0, -1e30, np.float64)
         ch.set_state(theta); ch.set_hypers(eta)
         out = ch.hmc_step(eps, L, p0=p0, log_u=-1e30)
         assert ch.last_transition_path == "trajectory"
@@ -243,14 +243,14 @@ def test_clip(native, monkeypatch, name, bias):
     th = theta.copy()
     th[j] = bias
     g64_out = o.forward(spec, th.astype(np.float64), X.astype(np.float64), np.float64)[1]
-    assert np.all(np.abs(g64_out) > hr.LOG_CLIP + 0.5)
-    ref = hr.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64)
+    assert np.all(np.abs(g64_out) > o.LOG_CLIP + 0.5)
+    ref = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64)
     ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y)
     lp, g, _st = ch.logp_grad(th, eta)
     ch.close()
     check_value_gradient(f"{name} clip {bias:+g}", lp, g, spec, ref)
-    pg = hr.prior_grad_flat(spec, th, eta, np.float64)[j]
+    pg = o.prior_grad(spec.layers[-1], eta[-4:].astype(np.float64), *o.unflatten(spec, th.astype(np.float64))[-1], np.float64)[1][1, 0]
     assert ref[1][j] == pg                                                # (the reference: no data part either)
     print(f"[hetero] {name} clip {bias:+g}: gradient of the bias {g[j]:.9g}, the prior's own {pg:.9g}")
     assert abs(float(g[j]) - pg) <= 4 * np.spacing(np.float32(abs(pg))), (g[j], pg)
@@ -262,7 +262,7 @@ def test_row_weights(native, monkeypatch, name):
     n = min(600, X.shape[0])
     X, Y = X[:n], Y[:n]
     w = np.random.default_rng(21).integers(0, 4, n).astype(np.float32)
-    vg = lambda Xs, Ys, ws=None: hr.target_log_prob_and_grad(spec, theta, eta, Xs, Ys, np.float64, ws)
+    vg = lambda Xs, Ys, ws=None: o.target_log_prob_and_grad(spec, theta, eta, Xs, Ys, np.float64, ws)
     ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y)
     plain = ch.logp_grad(theta, eta)
@@ -337,7 +337,7 @@ def test_refusals_padding_and_metrics(native, monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------------------------- pre-training
 def test_pretraining_against_the_restatement(native, monkeypatch):
-    """Chain.optimize for a few steps against the Adam / AMSGrad restatement of tests/optim_ref.py driven by hetero_ref's gradient: the
+    """Chain.optimize for a few steps against the Adam / AMSGrad restatement of tests/optim_ref.py driven by the oracle's gradient: the
     checked objectives to the value band, the last step's gradient to the gradient band, theta to 8 x the restatement's own fp32 gap"""
     name, steps = "fast3_two_outputs", 6
     spec, X, Y, theta0, eta = hr.problem(name)
@@ -348,10 +348,10 @@ def test_pretraining_against_the_restatement(native, monkeypatch):
         m = v = vhat = np.zeros_like(theta)
         trace, g = [], None
         for i in range(steps):
-            lp, g = hr.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)
+            lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)
             trace.append(float(lp))
             theta, m, v, vhat = R.adam_step(theta, g, m, v, vhat, i + 1, R.LR, dtype=dt)
-        trace.append(float(hr.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)[0]))
+        trace.append(float(o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)[0]))
         return np.asarray(trace), theta, g
 
     ch = make_chain(native, monkeypatch, name, spec)
@@ -424,7 +424,7 @@ def test_row_shard_two_ranks(tmp_path, native, monkeypatch):
         np.testing.assert_array_equal(ranks[0][name + "_g"], ranks[1][name + "_g"])
         assert float(ranks[0][name + "_lp"]) == float(ranks[1][name + "_lp"])
         check_value_gradient("shard " + name, float(ranks[0][name + "_lp"]), ranks[0][name + "_g"], spec,
-                             hr.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64))
+                             o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64))
         ref.close()
 
 

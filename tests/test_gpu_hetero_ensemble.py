@@ -27,7 +27,7 @@ from test_gpu_predictive import LD, PHI_FIG, U, int_weights, mix
 
 pytestmark = pytest.mark.gpu
 
-LIK = hr.LIK_HETERO_GAUSSIAN
+LIK = o.LIK_HETERO_GAUSSIAN
 M, N, DIMS = 24, 257, [1, 16, 16, 2]
 PROBS = [0.05, 0.5, 0.95]
 
@@ -58,7 +58,7 @@ def setup(native):
 def F_ref(y, f, w):
     """the mixture CDF at y [n] (or broadcastable) from the fp32 outputs f [m, 2, n], fp64 with the sum in extended precision"""
     f64 = f.astype(np.float64)
-    s = np.exp(np.clip(f64[:, 1], -hr.LOG_CLIP, hr.LOG_CLIP))
+    s = np.exp(np.clip(f64[:, 1], -o.LOG_CLIP, o.LOG_CLIP))
     return mix(sp.ndtr((np.asarray(y, dtype=np.float64)[None] - f64[:, 0]) / s), w)
 
 
@@ -68,9 +68,9 @@ def test_loglik_loo_and_waic(native):
     from test_gpu_loo import TOL
     ch, X, Y, thetas, f = setup(native)
     f64 = f.astype(np.float64)
-    l = np.stack([hr.terms(f64[i], Y) for i in range(M)])                                   # [m, n]: one term per row
-    gc = np.clip(f64[:, 1], -hr.LOG_CLIP, hr.LOG_CLIP)
-    mag = hr.HALF_LOG_2PI + np.abs(gc) + 0.5 * (Y.astype(np.float64)[None] - f64[:, 0]) ** 2 * np.exp(-2.0 * gc)
+    l = np.stack([o.hetero_terms(f64[i], Y) for i in range(M)])                                   # [m, n]: one term per row
+    gc = np.clip(f64[:, 1], -o.LOG_CLIP, o.LOG_CLIP)
+    mag = o.HALF_LOG_2PI + np.abs(gc) + 0.5 * (Y.astype(np.float64)[None] - f64[:, 0]) ** 2 * np.exp(-2.0 * gc)
     got = ch.ensemble_loo(thetas, Y=Y, X=X, pointwise=True)
     again = ch.ensemble_loo(thetas, Y=Y.reshape(-1, 1), X=X, likelihood=LIK, pointwise=True)       # [n, 1] targets: the same bits
     for key in got:
@@ -108,7 +108,7 @@ def test_predictive_cdf_and_quantiles(native):
     ch, X, Y, thetas, f = setup(native)
     t = T(M)
     f64 = f.astype(np.float64)
-    s = np.exp(np.clip(f64[:, 1], -hr.LOG_CLIP, hr.LOG_CLIP))
+    s = np.exp(np.clip(f64[:, 1], -o.LOG_CLIP, o.LOG_CLIP))
     real_w = (np.random.default_rng(3).random(M) + 0.05).astype(np.float32)
     real_w[5] = 0.0
     for tag, w in (("equal", None), ("importance weights", real_w), ("integer weights", int_weights(M))):
@@ -234,7 +234,7 @@ def test_predictor_noise_variance_and_intervals(tmp_path, monkeypatch, native):
     assert m.shape == v.shape == (2, 100)
     mean, tot = p.predictMoments(Xv, noiseVariance=True)
     assert mean.shape == tot.shape == (1, 100)
-    s2 = np.exp(2.0 * np.clip(f[:, 1], -hr.LOG_CLIP, hr.LOG_CLIP))
+    s2 = np.exp(2.0 * np.clip(f[:, 1], -o.LOG_CLIP, o.LOG_CLIP))
     want = f[:, 0].var(axis=0) + s2.mean(axis=0)
     assert np.allclose(mean[0], f[:, 0].mean(axis=0), rtol=1e-12, atol=1e-12)
     # (the device forms exp(g) from the fp32 output in fp32: 1e-6 of the value)

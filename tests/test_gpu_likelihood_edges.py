@@ -1,6 +1,6 @@
 """GPU: the Poisson, Student-t, negative-binomial and heteroscedastic Gaussian likelihoods at the edges of their element arithmetic
 (csrc/common.hpp log1p_fast, negbin_term, hetero_pair; kernels_fast.hpp lik_delta's Poisson branch), on every kernel family, against the
-fp64 arms of student_ref, negbin_ref, hetero_ref and the oracle's Poisson.  The likelihood modules (test_gpu_poisson / _student / _negbin /
+fp64 arms of the oracle.  The likelihood modules (test_gpu_poisson / _student / _negbin /
 _hetero) hold one well-conditioned problem per family and check sums over 500 .. 3,000 rows; here every dataset of tests/lik_edge_cases.py
 holds ONE band of the quantity the element code branches on, on all of its 301 rows, so a formula that is wrong on one regime is not
 diluted: log1p_fast's series and its switch at u = 1/4, negbin_term around t = 0, at |t| = ln 4, where e^-|t| passes through the denormals
@@ -11,7 +11,7 @@ modules' own CASES (their make_chain builds the chains and asserts the kernel na
 (1) test_band: per (likelihood, case, band) logp_grad at the dataset's state -- value, statistic and gradient per tensor against fp64 --
     and forward over the rows at 1e-4 max(1, |f64|); every launch three times, bit-identical; everything finite.
 (2) test_negbin_finite_where_promised: an injected transition from a far+ and a deep- dataset on fast3 (per-step kernels) and on the
-    trajectory kernel, both decisions against negbin_ref.weight_step in fp64: never rejected for a non-finite statistic.
+    trajectory kernel, both decisions against the oracle's weight_step in fp64: never rejected for a non-finite statistic.
 (3) test_rejected_where_promised: a momentum that carries the proposal to where the fp32 statistic is not finite (Student-t: u = inf or a
     non-finite f; heteroscedastic Gaussian: r^2 u past fp32 or a NaN g) is rejected whatever log u, and the chain keeps its state bit for bit.
     A NaN in a kernel is an ordinary value: nothing here faults.
@@ -28,10 +28,8 @@ run-time libraries built."""
 import numpy as np
 import pytest
 
-import hetero_ref as hr
 import lik_edge_cases as E
 import negbin_ref as nb
-import student_ref as sr
 import tbnn_oracle as o
 import test_gpu_hetero as tgh
 import test_gpu_negbin as tgn
@@ -78,10 +76,6 @@ def test_cases_are_the_likelihood_modules_own():
 
 def make(native, monkeypatch, ds, **kw):
     """the likelihood module's own make_chain: the case's family, environment and skip string, the kernel name asserted"""
-    if ds.lik == "student":
-        return tgs.make_chain(native, monkeypatch, ds.case, ds.spec, ds.par["nu"], **kw)
-    if ds.lik == "negbin":
-        return tgn.make_chain(native, monkeypatch, ds.case, ds.spec, ds.par["r"], **kw)
     return MODULE[ds.lik].make_chain(native, monkeypatch, ds.case, ds.spec, **kw)
 
 
@@ -139,7 +133,7 @@ def test_negbin_finite_where_promised(native, monkeypatch, case, band):
     if case == E.TRAJ:
         monkeypatch.setenv("TBNN_TRAJ", "1")
         monkeypatch.setenv("TBNN_JIT_SKIP", "")
-        ch = native.Chain(layers_of(ds.spec), likelihood=nb.LIK_NEG_BINOMIAL, lik_df=r, jit=True, seed=SEED)
+        ch = native.Chain(layers_of(ds.spec), likelihood=o.LIK_NEG_BINOMIAL, lik_df=r, jit=True, seed=SEED)
         assert ch.kernel_name.startswith("jit-fast3<") and ",neg-binomial;" in ch.kernel_name, ch.kernel_name
         path = "trajectory"
     else:
@@ -154,7 +148,7 @@ def test_negbin_finite_where_promised(native, monkeypatch, case, band):
         # leaves fp32) -- a choice of input from the reference alone, as test_gpu_poisson's large-rate transition makes it; deep-: unchanged
         eps = nb.step_size(case) * min(1.0, np.abs(nb.ref64(case)[1]).max() / np.abs(E.arms(ds)["g64"]).max())
         lp64 = E.arms(ds)["lp64"]
-        ref = nb.weight_step(ds.spec, r, ds.theta, ds.eta, ds.X, ds.Y, eps, 4, p0, -1e30, np.float64)
+        ref = o.weight_step(ds.spec, ds.theta, ds.eta, ds.X, ds.Y, eps, 4, p0, -1e30, np.float64)
         assert np.isfinite(ref.log_accept_ratio) and np.isfinite(ref.logp_new)
         tol = 2e-2 + 1e-4 * abs(ref.log_accept_ratio) + 4e-7 * abs(lp64)
         # log u on either side of the reference's log accept ratio, two bands away: the kernel's rounding cannot flip the decision
@@ -192,11 +186,7 @@ def test_rejected_where_promised(native, monkeypatch, lik, case):
     q1 = ds.theta.astype(np.float64) + EPS_FAR * (p0.astype(np.float64) + 0.5 * EPS_FAR * g64)          # the proposal of ONE leapfrog step
     with np.errstate(over="ignore", invalid="ignore"):
         f1 = o.forward(ds.spec, q1, ds.X.astype(np.float64), np.float64).astype(np.float32)
-        if lik == "student":
-            t32, _d = sr.elementwise(f1, ds.Y, ds.par["nu"], sr.scale_of(ds.spec), np.float32)
-        else:
-            t32, _d = hr.pair(f1, ds.Y, np.float32)
-        stat32 = float(np.sum(t32.astype(np.float64)))
+        stat32 = o.data_statistic(ds.spec, ds.eta, f1, ds.Y, np.float32)
     assert not np.isfinite(stat32), (ds.tag, stat32)
     assert float(np.sum(p0.astype(np.float64) ** 2)) < E.FLT_MAX / 16.0            # the kinetic energy is no reason to reject
     ch = make(native, monkeypatch, ds, seed=SEED)

@@ -2,7 +2,7 @@
 log p = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y log p + r log q per (row, output), p = sigmoid(f - log r) -- on every kernel family:
 the narrow fast3 and fast kernels and their one-launch trajectory kernel, mid, tall and wide (the VALU last layer of one or two outputs and
 the MFMA output tile of 3 .. 16), each likelihood path of the layered family (k_lay_tail, k_lay_last, k_lay_lik) and the generic kernel.
-Against tests/negbin_ref.py in fp64 (the oracle has no such likelihood): the value with its constant, the gradient per tensor, the forward
+Against the oracle in fp64 (the cases are tests/negbin_ref.py's): the value with its constant, the gradient per tensor, the forward
 outputs, an injected weight transition with both decisions (log u placed on either side of the reference's log accept ratio, two bands
 away), a hyper transition, every launch repeated bit for bit.  Then: row weights, the Poisson limit, refusals, trainChains against solo
 runs, pre-training, the ensemble reductions, a row-sharded chain on the stub collective library, and an end-to-end fit on over-dispersed
@@ -39,7 +39,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FUSED = {"fast3": "", "fast": "fast3", "mid": "fast3,fast,tall,wide", "tall": "fast3,fast,mid,wide", "wide": "fast3,fast,mid,tall"}
 CASES = {k: v for k, v in nb.CASES.items() if v[4] != "traj"}
 NET = [1, 16, 16, 1]                                              # the network(...) of the trainChains and end-to-end tests (tanh)
-LIK = nb.LIK_NEG_BINOMIAL
+LIK = o.LIK_NEG_BINOMIAL
 LIMIT_DIMS = [5, 50, 50, 50, 1]
 
 
@@ -55,15 +55,15 @@ def jit_jobs():
     jobs = []
     for dims, _n, act, prior, fam, _env, _r in nb.CASES.values():
         if fam in FUSED:
-            jobs.append(job(nb.make_spec(dims, act, prior), skip=FUSED[fam]))
+            jobs.append(job(o.make_spec(dims, act, prior, LIK, o.ACT_NONE), skip=FUSED[fam]))
         elif fam == "traj":
-            jobs.append(job(nb.make_spec(dims, act, prior)))
-    jobs.append(job(nb.make_spec(LIMIT_DIMS, o.ACT_RELU, o.PRIOR_CAUCHY), weighted=True))
-    jobs.append(job(nb.make_spec(LIMIT_DIMS, o.ACT_RELU, o.PRIOR_CAUCHY), lik=o.LIK_POISSON))          # the Poisson limit's other side
-    jobs.append(job(nb.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY)))
+            jobs.append(job(o.make_spec(dims, act, prior, LIK, o.ACT_NONE)))
+    jobs.append(job(o.make_spec(LIMIT_DIMS, o.ACT_RELU, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), weighted=True))
+    jobs.append(job(o.make_spec(LIMIT_DIMS, o.ACT_RELU, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), lik=o.LIK_POISSON))          # the Poisson limit's other side
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE)))
     # the Poisson fit of the end-to-end test and the predictors' forward chains (fixed-sd Gaussian handles)
-    jobs.append(job(nb.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY), lik=o.LIK_POISSON))
-    jobs.append(job(nb.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY), lik=o.LIK_FIXED_GAUSSIAN))
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), lik=o.LIK_POISSON))
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), lik=o.LIK_FIXED_GAUSSIAN))
     return [j for i, j in enumerate(jobs) if j not in jobs[:i]]
 
 
@@ -89,11 +89,11 @@ def check_value_gradient(tag, lp, g, spec, ref64):
     assert max(eg) <= 1e-4, (tag, eg)
 
 
-def make_chain(native, monkeypatch, name, spec, r, **kw):
+def make_chain(native, monkeypatch, name, spec, **kw):
     fam, env = nb.CASES[name][4], nb.CASES[name][5]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    kw = dict(likelihood=LIK, lik_df=r, **kw)
+    kw = dict(likelihood=LIK, lik_df=spec.lik_df, **kw)
     if fam in FUSED:
         monkeypatch.setenv("TBNN_JIT_SKIP", FUSED[fam])
         ch = native.Chain(layers_of(spec), jit=True, **kw)
@@ -112,8 +112,8 @@ def make_chain(native, monkeypatch, name, spec, r, **kw):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_value_gradient_forward(native, monkeypatch, name):
-    spec, X, Y, theta, eta, r = nb.problem(name)
-    ch = make_chain(native, monkeypatch, name, spec, r)
+    spec, X, Y, theta, eta = nb.problem(name)
+    ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y)
     lp, g, st = ch.logp_grad(theta, eta)
     for _ in range(2):
@@ -126,9 +126,9 @@ def test_value_gradient_forward(native, monkeypatch, name):
     check_value_gradient(name, lp, g, spec, nb.ref64(name))
     # stat is the data term with its constant (as Poisson's): sum (y log p + r log q) - C, and logp minus it the priors
     f64 = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
-    data64, _stat64 = nb.data_log_prob(spec, r, f64, Y, np.float64)
+    data64 = float(o.log_likelihood(spec, eta, f64, Y, np.float64))
     assert abs(st - data64) <= 4e-6 * abs(data64), (st, data64)
-    prior = float(nb.prior_log_prob(spec, theta, eta, np.float64))
+    prior = float(nb.ref64(name)[0] - data64)
     assert abs((lp - st) - prior) <= 4e-6 * max(abs(lp), 1.0)
     assert f.shape == (spec.layers[-1].out_dim, m)
     assert np.abs(f - f64[:, :m]).max() <= 1e-4 * max(1.0, np.abs(f64).max())
@@ -136,14 +136,14 @@ def test_value_gradient_forward(native, monkeypatch, name):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_transitions(native, monkeypatch, name):
-    spec, X, Y, theta, eta, r = nb.problem(name)
+    spec, X, Y, theta, eta = nb.problem(name)
     rng = np.random.default_rng(4)
     p0 = rng.standard_normal(spec.n_params).astype(np.float32)
-    ch = make_chain(native, monkeypatch, name, spec, r, seed=SEED, chain_id=2)
+    ch = make_chain(native, monkeypatch, name, spec, seed=SEED, chain_id=2)
     ch.set_data(X, Y)
     lp64 = nb.ref64(name)[0]
     eps = nb.step_size(name)
-    ref = nb.weight_step(spec, r, theta, eta, X, Y, eps, 4, p0, -1e30, np.float64)
+    ref = o.weight_step(spec, theta, eta, X, Y, eps, 4, p0, -1e30, np.float64)
     tol = 2e-2 + 1e-4 * abs(ref.log_accept_ratio) + 4e-7 * abs(lp64)
     # log u on either side of the reference's log accept ratio, two bands away: the kernel's rounding cannot flip the decision
     for log_u, accept in ((ref.log_accept_ratio - 2 * tol, True), (ref.log_accept_ratio + 2 * tol, False)):
@@ -163,20 +163,21 @@ def test_transitions(native, monkeypatch, name):
     ch.set_state(theta); ch.set_hypers(eta)
     ch.logp_grad(theta, eta)
     out = ch.hyper_step(1e-4, 9, p0=ph, log_u=-1e30)
-    ref = nb.hyper_step(spec, eta, theta, X, Y, 1e-4, 9, ph, -1e30, np.float64)
+    ref = o.hyper_step(spec, eta, theta, X, Y, 1e-4, 9, ph, -1e30, np.float64)
     assert abs(out["log_accept_ratio"] - ref.log_accept_ratio) <= 2e-2 + 1e-3 * abs(ref.log_accept_ratio)
     assert np.allclose(ch.get_hypers(), ref.theta, rtol=1e-4, atol=1e-5)
     # after the accepted hyper transition the cached gradient is refreshed for the new priors: the next weight step starts from it
     eta2 = ch.get_hypers()
     lp_new, g_new, _ = ch.logp_grad(theta, eta2)
-    check_value_gradient(name + " after the hyper step", lp_new, g_new, spec, nb.target_log_prob_and_grad(spec, r, theta, eta2, X, Y, np.float64))
+    check_value_gradient(name + " after the hyper step", lp_new, g_new, spec, o.target_log_prob_and_grad(spec, theta, eta2, X, Y, np.float64))
     ch.close()
 
 
 def test_trajectory_kernel(native, monkeypatch):
     """a small narrow problem takes the one-launch trajectory kernel; the traced run of the same transition (per-step kernels) agrees with
     fp64 step by step"""
-    spec, X, Y, theta, eta, r = nb.problem("traj")
+    spec, X, Y, theta, eta = nb.problem("traj")
+    r = spec.lik_df
     monkeypatch.setenv("TBNN_TRAJ", "1")
     monkeypatch.setenv("TBNN_JIT_SKIP", "")
     ch = native.Chain(layers_of(spec), likelihood=LIK, lik_df=r, jit=True, seed=SEED)
@@ -188,7 +189,7 @@ def test_trajectory_kernel(native, monkeypatch):
     lp64 = nb.ref64("traj")[0]
     eps = nb.step_size("traj")
     for L in (1, 9):
-        ref = nb.weight_step(spec, r, theta, eta, X, Y, eps, L, p0, -1e30, np.float64)
+        ref = o.weight_step(spec, theta, eta, X, Y, eps, L, p0, -1e30, np.float64)
         ch.set_state(theta); ch.set_hypers(eta)
         out = ch.hmc_step(eps, L, p0=p0, log_u=-1e30)
         assert ch.last_transition_path == "trajectory"
@@ -215,12 +216,12 @@ def test_trajectory_kernel(native, monkeypatch):
 
 @pytest.mark.parametrize("name", ["fast3", "lay_last"])
 def test_row_weights(native, monkeypatch, name):
-    spec, X, Y, theta, eta, r = nb.problem(name)
+    spec, X, Y, theta, eta = nb.problem(name)
     n = min(600, X.shape[0])
     X, Y = X[:n], Y[:n]
     w = np.random.default_rng(21).integers(0, 4, n).astype(np.float32)
-    vg = lambda Xs, Ys, ws=None: nb.target_log_prob_and_grad(spec, r, theta, eta, Xs, Ys, np.float64, ws)
-    ch = make_chain(native, monkeypatch, name, spec, r)
+    vg = lambda Xs, Ys, ws=None: o.target_log_prob_and_grad(spec, theta, eta, Xs, Ys, np.float64, ws)
+    ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y)
     plain = ch.logp_grad(theta, eta)
     # a weight of 1 everywhere: the unweighted bits
@@ -259,7 +260,7 @@ def test_poisson_limit(native, monkeypatch):
     X, f = X[keep], f[keep]
     assert 1000 <= X.shape[0] < n and X.shape[0] % 16 != 0
     Y = np.random.default_rng(3).poisson(np.exp(f)).astype(np.float32).reshape(-1, 1)
-    _t, d_nb = nb.elementwise(f[None], Y, 1e6, np.float64)
+    _t, d_nb = o.negbin_elementwise(f[None], Y, 1e6, np.float64)
     d_po = Y[:, 0].astype(np.float64) - np.exp(f)
     print(f"[negbin] Poisson limit at r = 1e6, rates <= {np.exp(f).max():.2f}: the two fp64 definitions' deltas differ by "
           f"{np.abs(d_nb[0] - d_po).max() / np.abs(d_po).max():.2e} of the largest delta")
@@ -280,7 +281,8 @@ def test_poisson_limit(native, monkeypatch):
 
 
 def test_refusals(native, monkeypatch):
-    spec, X, Y, theta, eta, r = nb.problem("generic")
+    spec, X, Y, theta, eta = nb.problem("generic")
+    r = spec.lik_df
     layers = layers_of(spec)
     for df in (0.0, -1.0, float("nan"), float("inf")):
         with pytest.raises(native.TbnnError, match="lik_df"):
@@ -337,10 +339,10 @@ def test_refusals(native, monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------------------------- pre-training
 def test_pretraining_against_the_restatement(native, monkeypatch):
-    """Chain.optimize for a few steps against the Adam / AMSGrad restatement of tests/optim_ref.py driven by negbin_ref's gradient: the
+    """Chain.optimize for a few steps against the Adam / AMSGrad restatement of tests/optim_ref.py driven by the oracle's gradient: the
     checked objectives to the value band, the last step's gradient to the gradient band, theta to 8 x the restatement's own fp32 gap"""
     name, steps = "fast3_two_outputs", 6
-    spec, X, Y, theta0, eta, r = nb.problem(name)
+    spec, X, Y, theta0, eta = nb.problem(name)
 
     def run(dtype):
         dt = dtype
@@ -348,13 +350,13 @@ def test_pretraining_against_the_restatement(native, monkeypatch):
         m = v = vhat = np.zeros_like(theta)
         trace, g = [], None
         for i in range(steps):
-            lp, g = nb.target_log_prob_and_grad(spec, r, theta, eta, X, Y, dt)
+            lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)
             trace.append(float(lp))
             theta, m, v, vhat = R.adam_step(theta, g, m, v, vhat, i + 1, R.LR, dtype=dt)
-        trace.append(float(nb.target_log_prob_and_grad(spec, r, theta, eta, X, Y, dt)[0]))
+        trace.append(float(o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)[0]))
         return np.asarray(trace), theta, g
 
-    ch = make_chain(native, monkeypatch, name, spec, r)
+    ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y); ch.set_state(theta0); ch.set_hypers(eta)
     out = ch.optimize(steps, lr=R.LR, check_every=1, keep="last")
     th, st = ch.get_state(), ch.optim_state()
@@ -378,7 +380,7 @@ def term_magnitudes(f, Y, r):
     f = np.asarray(f, dtype=np.float64)
     y = np.asarray(Y, dtype=np.float64).reshape(f.shape[1], -1).T
     lg = np.vectorize(math.lgamma, otypes=[np.float64])
-    t, _d = nb.elementwise(f, Y, r, np.float64)
+    t, _d = o.negbin_elementwise(f, Y, r, np.float64)
     return np.abs(lg(y + r)) + abs(math.lgamma(r)) + np.abs(lg(y + 1.0)) + np.abs(t)
 
 
@@ -392,7 +394,8 @@ def test_ensemble_loglik_and_loo(native, monkeypatch):
     from psis_ref import psis_ref
     from test_gpu_ensemble import U, logsumexp_rows
     from test_gpu_loo import TOL
-    spec, X, Y, theta, eta, r = nb.problem("generic")
+    spec, X, Y, theta, eta = nb.problem("generic")
+    r = spec.lik_df
     m, n, d_out = 16, X.shape[0], spec.layers[-1].out_dim
     assert (n, d_out) == (517, 4) and r == 1e4
     rng = np.random.default_rng(31)
@@ -404,7 +407,7 @@ def test_ensemble_loglik_and_loo(native, monkeypatch):
     for tag, (ch, disp) in handles.items():
         f = ch.forward_many(thetas, X=X).astype(np.float64)                          # [m, d_out, n]
         rr = float(np.float32(disp))
-        l = np.stack([nb.terms(f[i], Y, rr).sum(axis=0) for i in range(m)])                 # [m, n]
+        l = np.stack([o.negbin_terms(f[i], Y, rr).sum(axis=0) for i in range(m)])                 # [m, n]
         mag = np.stack([term_magnitudes(f[i], Y, rr).sum(axis=0) for i in range(m)])
         got = ch.ensemble_loo(thetas, Y=Y, X=X, likelihood=LIK, pointwise=True)
         again = ch.ensemble_loo(thetas, Y=Y, X=X, likelihood=LIK, pointwise=True)
@@ -461,8 +464,8 @@ def test_row_shard_two_ranks(tmp_path, native, monkeypatch):
         assert p.returncode == 0, log[-3000:]
         ranks.append(np.load(out))
     for name in ws.SHAPES:
-        spec, X, Y, theta, eta, r = ws.problem(name)
-        ref = ws.chain_of(name, spec, r)
+        spec, X, Y, theta, eta = ws.problem(name)
+        ref = ws.chain_of(name, spec)
         ref.set_data(X, Y); ref.set_state(theta); ref.set_hypers(eta)
         lp0, g0, st0 = ref.logp_grad(theta, eta)
         p0 = np.random.default_rng(5).standard_normal(spec.n_params).astype(np.float32)
@@ -485,7 +488,7 @@ def test_row_shard_two_ranks(tmp_path, native, monkeypatch):
         np.testing.assert_array_equal(ranks[0][name + "_g"], ranks[1][name + "_g"])
         assert float(ranks[0][name + "_lp"]) == float(ranks[1][name + "_lp"])
         check_value_gradient("shard " + name, float(ranks[0][name + "_lp"]), ranks[0][name + "_g"], spec,
-                             nb.target_log_prob_and_grad(spec, r, theta, eta, X, Y, np.float64))
+                             o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64))
         ref.close()
 
 

@@ -1,8 +1,8 @@
 """GPU: StudentTLikelihood (TBNN_LIK_STUDENT_T) -- independent Student-t noise of fixed scale s and nu degrees of freedom,
 log p = c(nu, s) - (nu + 1) / 2 log1p(r^2 / (nu s^2)) per (row, output) -- on every kernel family: the narrow fast3 and fast kernels and their
 one-launch trajectory kernel, mid, tall and wide (the VALU last layer of one or two outputs and the MFMA output tile of 3 .. 16), each
-likelihood path of the layered family (k_lay_tail, k_lay_last, k_lay_lik) and the generic kernel.  Against tests/student_ref.py in fp64 (the
-oracle has no such likelihood): the value with its constant, the gradient per tensor, the forward outputs, an injected weight transition with
+likelihood path of the layered family (k_lay_tail, k_lay_last, k_lay_lik) and the generic kernel.  Against the oracle in fp64 (the cases are
+tests/student_ref.py's): the value with its constant, the gradient per tensor, the forward outputs, an injected weight transition with
 both decisions (log u placed on either side of the reference's log accept ratio, two bands away), a hyper transition, every launch repeated
 bit for bit.  Then: row weights, the Gaussian limit, refusals, trainChains against solo runs, pre-training, the ensemble reductions, a
 row-sharded chain on the stub collective library, and an end-to-end fit on contaminated data against the Gaussian fit.
@@ -38,7 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FUSED = {"fast3": "", "fast": "fast3", "mid": "fast3,fast,tall,wide", "tall": "fast3,fast,mid,wide", "wide": "fast3,fast,mid,tall"}
 CASES = {k: v for k, v in sr.CASES.items() if v[4] != "traj"}
 NET = [1, 16, 16, 1]                                              # the network(...) of the trainChains and end-to-end tests (tanh)
-LIK = sr.LIK_STUDENT_T
+LIK = o.LIK_STUDENT_T
 
 
 def job(spec, lik=LIK, skip="", weighted=False):
@@ -51,15 +51,15 @@ def job(spec, lik=LIK, skip="", weighted=False):
 def jit_jobs():
     """the run-time instantiations this module asks for (jit.prebuild's job format): 12 libraries"""
     jobs = []
-    for dims, _n, act, prior, fam, _env, _nu, s in sr.CASES.values():
+    for dims, _n, act, prior, fam, _env, _nu, _s in sr.CASES.values():
         if fam in FUSED:
-            jobs.append(job(sr.make_spec(dims, act, prior, s), skip=FUSED[fam]))
+            jobs.append(job(o.make_spec(dims, act, prior, LIK, o.ACT_NONE), skip=FUSED[fam]))
         elif fam == "traj":
-            jobs.append(job(sr.make_spec(dims, act, prior, s)))
-    jobs.append(job(sr.make_spec([5, 50, 50, 50, 1], o.ACT_RELU, o.PRIOR_CAUCHY, 0.1), weighted=True))
-    jobs.append(job(sr.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, 0.1)))
+            jobs.append(job(o.make_spec(dims, act, prior, LIK, o.ACT_NONE)))
+    jobs.append(job(o.make_spec([5, 50, 50, 50, 1], o.ACT_RELU, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), weighted=True))
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE)))
     # the Gaussian fit of the end-to-end test and the predictors' forward chains (fixed-sd Gaussian handles)
-    jobs.append(job(sr.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, 0.1), lik=o.LIK_FIXED_GAUSSIAN))
+    jobs.append(job(o.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY, LIK, o.ACT_NONE), lik=o.LIK_FIXED_GAUSSIAN))
     return [j for i, j in enumerate(jobs) if j not in jobs[:i]]
 
 
@@ -85,11 +85,11 @@ def check_value_gradient(tag, lp, g, spec, ref64):
     assert max(eg) <= 1e-4, (tag, eg)
 
 
-def make_chain(native, monkeypatch, name, spec, nu, **kw):
+def make_chain(native, monkeypatch, name, spec, **kw):
     fam, env = sr.CASES[name][4], sr.CASES[name][5]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    kw = dict(likelihood=LIK, fixed_sd=spec.fixed_sd, lik_df=nu, **kw)
+    kw = dict(likelihood=LIK, fixed_sd=spec.fixed_sd, lik_df=spec.lik_df, **kw)
     if fam in FUSED:
         monkeypatch.setenv("TBNN_JIT_SKIP", FUSED[fam])
         ch = native.Chain(layers_of(spec), jit=True, **kw)
@@ -108,8 +108,8 @@ def make_chain(native, monkeypatch, name, spec, nu, **kw):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_value_gradient_forward(native, monkeypatch, name):
-    spec, X, Y, theta, eta, nu = sr.problem(name)
-    ch = make_chain(native, monkeypatch, name, spec, nu)
+    spec, X, Y, theta, eta = sr.problem(name)
+    ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y)
     lp, g, st = ch.logp_grad(theta, eta)
     for _ in range(2):
@@ -122,10 +122,11 @@ def test_value_gradient_forward(native, monkeypatch, name):
     check_value_gradient(name, lp, g, spec, sr.ref64(name))
     # stat is sum log1p(r^2 / (nu s^2)): the data term is rows d_out c(nu, s) - (nu + 1) / 2 stat, and logp minus it the priors
     f64 = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
-    data64, stat64 = sr.data_log_prob(spec, nu, f64, Y, np.float64)
+    nu = spec.lik_df
+    stat64 = o.data_statistic(spec, eta, f64, Y, np.float64)
     assert abs(st - stat64) <= 4e-6 * abs(stat64), (st, stat64)
-    data = X.shape[0] * spec.layers[-1].out_dim * sr.const(nu, sr.scale_of(spec)) - 0.5 * (nu + 1.0) * st
-    prior = float(sr.prior_log_prob(spec, theta, eta, np.float64))
+    data = X.shape[0] * spec.layers[-1].out_dim * o.student_const(nu, o.student_scale(spec)) - 0.5 * (nu + 1.0) * st
+    prior = float(sr.ref64(name)[0] - o.log_likelihood(spec, eta, f64, Y, np.float64))
     assert abs((lp - data) - prior) <= 4e-6 * max(abs(lp), 1.0)
     assert f.shape == (spec.layers[-1].out_dim, m)
     assert np.abs(f - f64[:, :m]).max() <= 1e-4 * max(1.0, np.abs(f64).max())
@@ -133,14 +134,14 @@ def test_value_gradient_forward(native, monkeypatch, name):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_transitions(native, monkeypatch, name):
-    spec, X, Y, theta, eta, nu = sr.problem(name)
+    spec, X, Y, theta, eta = sr.problem(name)
     rng = np.random.default_rng(4)
     p0 = rng.standard_normal(spec.n_params).astype(np.float32)
-    ch = make_chain(native, monkeypatch, name, spec, nu, seed=SEED, chain_id=2)
+    ch = make_chain(native, monkeypatch, name, spec, seed=SEED, chain_id=2)
     ch.set_data(X, Y)
     lp64 = sr.ref64(name)[0]
     eps = sr.step_size(name)
-    ref = sr.weight_step(spec, nu, theta, eta, X, Y, eps, 4, p0, -1e30, np.float64)
+    ref = o.weight_step(spec, theta, eta, X, Y, eps, 4, p0, -1e30, np.float64)
     tol = 2e-2 + 1e-4 * abs(ref.log_accept_ratio) + 4e-7 * abs(lp64)
     # log u on either side of the reference's log accept ratio, two bands away: the kernel's rounding cannot flip the decision
     for log_u, accept in ((ref.log_accept_ratio - 2 * tol, True), (ref.log_accept_ratio + 2 * tol, False)):
@@ -160,23 +161,23 @@ def test_transitions(native, monkeypatch, name):
     ch.set_state(theta); ch.set_hypers(eta)
     ch.logp_grad(theta, eta)
     out = ch.hyper_step(1e-4, 9, p0=ph, log_u=-1e30)
-    ref = sr.hyper_step(spec, eta, theta, X, Y, 1e-4, 9, ph, -1e30, np.float64)
+    ref = o.hyper_step(spec, eta, theta, X, Y, 1e-4, 9, ph, -1e30, np.float64)
     assert abs(out["log_accept_ratio"] - ref.log_accept_ratio) <= 2e-2 + 1e-3 * abs(ref.log_accept_ratio)
     assert np.allclose(ch.get_hypers(), ref.theta, rtol=1e-4, atol=1e-5)
     # after the accepted hyper transition the cached gradient is refreshed for the new priors: the next weight step starts from it
     eta2 = ch.get_hypers()
     lp_new, g_new, _ = ch.logp_grad(theta, eta2)
-    check_value_gradient(name + " after the hyper step", lp_new, g_new, spec, sr.target_log_prob_and_grad(spec, nu, theta, eta2, X, Y, np.float64))
+    check_value_gradient(name + " after the hyper step", lp_new, g_new, spec, o.target_log_prob_and_grad(spec, theta, eta2, X, Y, np.float64))
     ch.close()
 
 
 def test_trajectory_kernel(native, monkeypatch):
     """a small narrow problem takes the one-launch trajectory kernel; the traced run of the same transition (per-step kernels) agrees with
     fp64 step by step"""
-    spec, X, Y, theta, eta, nu = sr.problem("traj")
+    spec, X, Y, theta, eta = sr.problem("traj")
     monkeypatch.setenv("TBNN_TRAJ", "1")
     monkeypatch.setenv("TBNN_JIT_SKIP", "")
-    ch = native.Chain(layers_of(spec), likelihood=LIK, fixed_sd=spec.fixed_sd, lik_df=nu, jit=True, seed=SEED)
+    ch = native.Chain(layers_of(spec), likelihood=LIK, fixed_sd=spec.fixed_sd, lik_df=spec.lik_df, jit=True, seed=SEED)
     assert ch.kernel_name.startswith("jit-fast3<") and ",student-t;" in ch.kernel_name, ch.kernel_name
     ch.set_data(X, Y)
     lp, g, _ = ch.logp_grad(theta, eta)
@@ -185,7 +186,7 @@ def test_trajectory_kernel(native, monkeypatch):
     lp64 = sr.ref64("traj")[0]
     eps = sr.step_size("traj")
     for L in (1, 9):
-        ref = sr.weight_step(spec, nu, theta, eta, X, Y, eps, L, p0, -1e30, np.float64)
+        ref = o.weight_step(spec, theta, eta, X, Y, eps, L, p0, -1e30, np.float64)
         ch.set_state(theta); ch.set_hypers(eta)
         out = ch.hmc_step(eps, L, p0=p0, log_u=-1e30)
         assert ch.last_transition_path == "trajectory"
@@ -212,12 +213,12 @@ def test_trajectory_kernel(native, monkeypatch):
 
 @pytest.mark.parametrize("name", ["fast3", "lay_last"])
 def test_row_weights(native, monkeypatch, name):
-    spec, X, Y, theta, eta, nu = sr.problem(name)
+    spec, X, Y, theta, eta = sr.problem(name)
     n = min(600, X.shape[0])
     X, Y = X[:n], Y[:n]
     w = np.random.default_rng(21).integers(0, 4, n).astype(np.float32)
-    vg = lambda Xs, Ys, ws=None: sr.target_log_prob_and_grad(spec, nu, theta, eta, Xs, Ys, np.float64, ws)
-    ch = make_chain(native, monkeypatch, name, spec, nu)
+    vg = lambda Xs, Ys, ws=None: o.target_log_prob_and_grad(spec, theta, eta, Xs, Ys, np.float64, ws)
+    ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y)
     plain = ch.logp_grad(theta, eta)
     # a weight of 1 everywhere: the unweighted bits
@@ -272,7 +273,8 @@ def test_gaussian_limit(native, monkeypatch):
 
 
 def test_refusals(native, monkeypatch):
-    spec, X, Y, theta, eta, nu = sr.problem("generic")
+    spec, X, Y, theta, eta = sr.problem("generic")
+    nu = spec.lik_df
     layers = layers_of(spec)
     for df in (0.0, -1.0, float("nan"), float("inf")):
         with pytest.raises(native.TbnnError, match="lik_df"):
@@ -313,10 +315,10 @@ def test_refusals(native, monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------------------------- pre-training
 def test_pretraining_against_the_restatement(native, monkeypatch):
-    """Chain.optimize for a few steps against the Adam / AMSGrad restatement of tests/optim_ref.py driven by student_ref's gradient: the
+    """Chain.optimize for a few steps against the Adam / AMSGrad restatement of tests/optim_ref.py driven by the oracle's gradient: the
     checked objectives to the value band, the last step's gradient to the gradient band, theta to 8 x the restatement's own fp32 gap"""
     name, steps = "fast3_two_outputs", 6
-    spec, X, Y, theta0, eta, nu = sr.problem(name)
+    spec, X, Y, theta0, eta = sr.problem(name)
 
     def run(dtype):
         dt = dtype
@@ -324,13 +326,13 @@ def test_pretraining_against_the_restatement(native, monkeypatch):
         m = v = vhat = np.zeros_like(theta)
         trace, g = [], None
         for i in range(steps):
-            lp, g = sr.target_log_prob_and_grad(spec, nu, theta, eta, X, Y, dt)
+            lp, g = o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)
             trace.append(float(lp))
             theta, m, v, vhat = R.adam_step(theta, g, m, v, vhat, i + 1, R.LR, dtype=dt)
-        trace.append(float(sr.target_log_prob_and_grad(spec, nu, theta, eta, X, Y, dt)[0]))
+        trace.append(float(o.target_log_prob_and_grad(spec, theta, eta, X, Y, dt)[0]))
         return np.asarray(trace), theta, g
 
-    ch = make_chain(native, monkeypatch, name, spec, nu)
+    ch = make_chain(native, monkeypatch, name, spec)
     ch.set_data(X, Y); ch.set_state(theta0); ch.set_hypers(eta)
     out = ch.optimize(steps, lr=R.LR, check_every=1, keep="last")
     th, st = ch.get_state(), ch.optim_state()
@@ -359,7 +361,8 @@ def test_ensemble_loglik_and_loo(native, monkeypatch):
     from psis_ref import psis_ref
     from test_gpu_ensemble import U, logsumexp_rows
     from test_gpu_loo import TOL
-    spec, X, Y, theta, eta, nu = sr.problem("generic")
+    spec, X, Y, theta, eta = sr.problem("generic")
+    nu = spec.lik_df
     m, n, d_out = 16, X.shape[0], spec.layers[-1].out_dim
     assert (n, d_out) == (517, 4)
     rng = np.random.default_rng(31)
@@ -371,9 +374,9 @@ def test_ensemble_loglik_and_loo(native, monkeypatch):
     handles["gaussian"][0].set_lik_df(30.0)
     for tag, (ch, sd, df) in handles.items():
         f = ch.forward_many(thetas, X=X).astype(np.float64)                          # [m, d_out, n]
-        s_i = np.full(m, sr.scale_of(spec)) if sd is None else sd.astype(np.float64)
-        l = np.stack([sr.terms(f[i], Y, df, s_i[i]).sum(axis=0) for i in range(m)])                 # [m, n]
-        mag = np.stack([(abs(sr.const(df, s_i[i])) + 2 * abs(math.lgamma(0.5 * (df + 1.0))) + np.abs(sr.terms(f[i], Y, df, s_i[i]))).sum(axis=0) for i in range(m)])
+        s_i = np.full(m, o.student_scale(spec)) if sd is None else sd.astype(np.float64)
+        l = np.stack([o.student_terms(f[i], Y, df, s_i[i]).sum(axis=0) for i in range(m)])                 # [m, n]
+        mag = np.stack([(abs(o.student_const(df, s_i[i])) + 2 * abs(math.lgamma(0.5 * (df + 1.0))) + np.abs(o.student_terms(f[i], Y, df, s_i[i]))).sum(axis=0) for i in range(m)])
         got = ch.ensemble_loo(thetas, Y=Y, X=X, likelihood=LIK, sd=sd, pointwise=True)
         again = ch.ensemble_loo(thetas, Y=Y, X=X, likelihood=LIK, sd=sd, pointwise=True)
         for key in got:
@@ -429,8 +432,8 @@ def test_row_shard_two_ranks(tmp_path, native, monkeypatch):
         assert p.returncode == 0, log[-3000:]
         ranks.append(np.load(out))
     for name in ws.SHAPES:
-        spec, X, Y, theta, eta, nu = ws.problem(name)
-        ref = ws.chain_of(name, spec, nu)
+        spec, X, Y, theta, eta = ws.problem(name)
+        ref = ws.chain_of(name, spec)
         ref.set_data(X, Y); ref.set_state(theta); ref.set_hypers(eta)
         lp0, g0, st0 = ref.logp_grad(theta, eta)
         p0 = np.random.default_rng(5).standard_normal(spec.n_params).astype(np.float32)
@@ -453,7 +456,7 @@ def test_row_shard_two_ranks(tmp_path, native, monkeypatch):
         np.testing.assert_array_equal(ranks[0][name + "_g"], ranks[1][name + "_g"])
         assert float(ranks[0][name + "_lp"]) == float(ranks[1][name + "_lp"])
         check_value_gradient("shard " + name, float(ranks[0][name + "_lp"]), ranks[0][name + "_g"], spec,
-                             sr.target_log_prob_and_grad(spec, nu, theta, eta, X, Y, np.float64))
+                             o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float64))
         ref.close()
 
 

@@ -1,4 +1,4 @@
-"""CPU: the heteroscedastic Gaussian likelihood (TBNN_LIK_HETERO_GAUSSIAN) without a GPU -- the reference of tests/hetero_ref.py against
+"""CPU: the heteroscedastic Gaussian likelihood (TBNN_LIK_HETERO_GAUSSIAN) without a GPU -- the oracle's heteroscedastic likelihood against
 central differences and SciPy, its fp32 arm (the kernel's own operations) inside HALF the GPU module's bands on every case of
 tests/test_gpu_hetero.py, the Python class, the kernels' likelihood code and the run-time kernel plumbing, the C ABI's admission rules
 (tbnn_fused_kernel_available runs the same descriptor check as tbnn_create), the target padding, and a cross-compile of two shapes through
@@ -25,10 +25,10 @@ def test_reference_formula_against_scipy():
     want = norm.logpdf(y, loc=f, scale=np.exp(g))
     got = lik.logDensity(f, g, y)
     assert got.dtype == np.float64 and np.allclose(got, want, rtol=1e-12, atol=1e-12)
-    assert np.allclose(hr.terms(np.stack([f, g]), y), want, rtol=1e-12, atol=1e-12)
+    assert np.allclose(o.hetero_terms(np.stack([f, g]), y), want, rtol=1e-12, atol=1e-12)
     # the clip: g beyond +-log(1e8) is read as the bound
     for gg in (25.0, -25.0):
-        assert lik.logDensity(0.0, gg, 1e-9) == lik.logDensity(0.0, math.copysign(hr.LOG_CLIP, gg), 1e-9)
+        assert lik.logDensity(0.0, gg, 1e-9) == lik.logDensity(0.0, math.copysign(o.LOG_CLIP, gg), 1e-9)
     # makeResponseLikelihood: [1, rows], one target per row in any of the three layouts
     pred = lambda *_a: np.stack([f, g]).astype(np.float32)
     base = lik.makeResponseLikelihood(None, predict=pred, realVals=y.astype(np.float32))
@@ -44,22 +44,22 @@ def test_reference_gradient_against_central_differences():
     th = theta.astype(np.float64)
     w = np.random.default_rng(2).integers(0, 3, 40).astype(np.float64)
     for weights in (None, w):
-        lp, g = hr.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, weights)
+        lp, g = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, weights)
         h = 1e-6
         for j in range(spec.n_params):
             e = np.zeros_like(th)
             e[j] = h
-            num = (hr.target_log_prob_and_grad(spec, th + e, eta, X, Y, np.float64, weights)[0]
-                   - hr.target_log_prob_and_grad(spec, th - e, eta, X, Y, np.float64, weights)[0]) / (2 * h)
+            num = (o.target_log_prob_and_grad(spec, th + e, eta, X, Y, np.float64, weights)[0]
+                   - o.target_log_prob_and_grad(spec, th - e, eta, X, Y, np.float64, weights)[0]) / (2 * h)
             assert abs(num - g[j]) <= 2e-6 * max(1.0, abs(g[j])), (j, num, g[j])
     # integer weights are duplicated rows, the constant included
     idx = np.repeat(np.arange(40), w.astype(int))
-    a = hr.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, w)
-    b = hr.target_log_prob_and_grad(spec, th, eta, X[idx], Y[idx], np.float64)
+    a = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, w)
+    b = o.target_log_prob_and_grad(spec, th, eta, X[idx], Y[idx], np.float64)
     assert math.isclose(a[0], b[0], rel_tol=1e-12) and np.allclose(a[1], b[1], rtol=1e-10, atol=1e-12)
     # outside the clip the derivative with respect to g is 0, and a NaN g stays NaN in both arms
     for dt in (np.float64, np.float32):
-        t, d = hr.pair(np.array([[0.0, 0.0, 0.0], [25.0, -25.0, np.nan]]), np.array([1.0, 1e-9, 1.0]), dt)
+        t, d = o.hetero_pair(np.array([[0.0, 0.0, 0.0], [25.0, -25.0, np.nan]]), np.array([1.0, 1e-9, 1.0]), dt)
         assert d[1][0] == 0 and d[1][1] == 0 and np.isfinite(t[:2]).all() and np.isnan(t[2]) and np.isnan(d[0][2])
 
 
@@ -69,7 +69,7 @@ def test_reference_in_fp32_stays_inside_half_the_bands(name):
     of the GPU module's injected transition -- within HALF the GPU bands; and the problem has what the module promises of it"""
     spec, X, Y, theta, eta = hr.problem(name)
     lp64, g64 = hr.ref64(name)
-    lp32, g32 = hr.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
+    lp32, g32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
     gv, gg = abs(lp32 - lp64) / max(abs(lp64), 1.0), tensor_errs(spec, g32, g64, 1e-3)
     f = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
     q = (Y.astype(np.float64) - f[0]) ** 2 * np.exp(-2.0 * f[1])
@@ -81,8 +81,8 @@ def test_reference_in_fp32_stays_inside_half_the_bands(name):
     assert np.all(tiles.min(axis=1) < 1e-2) and np.all(tiles.max(axis=1) > 50.0)        # both regimes in every full tile
     assert gv <= 2e-6 and max(gg) <= 5e-5, (gv, gg)
     p0 = np.random.default_rng(4).standard_normal(spec.n_params).astype(np.float32)
-    r64 = hr.weight_step(spec, theta, eta, X, Y, hr.step_size(name), 4, p0, -1e30, np.float64)
-    r32 = hr.weight_step(spec, theta, eta, X, Y, hr.step_size(name), 4, p0, -1e30, np.float32)
+    r64 = o.weight_step(spec, theta, eta, X, Y, hr.step_size(name), 4, p0, -1e30, np.float64)
+    r32 = o.weight_step(spec, theta, eta, X, Y, hr.step_size(name), 4, p0, -1e30, np.float32, np.float64)
     tol = 2e-2 + 1e-4 * abs(r64.log_accept_ratio) + 4e-7 * abs(lp64)
     print(f"[hetero] {name}: lar fp32 {r32.log_accept_ratio:.6g} fp64 {r64.log_accept_ratio:.6g} (band {tol:.3g})")
     assert abs(r32.log_accept_ratio - r64.log_accept_ratio) <= 0.5 * tol
@@ -95,10 +95,10 @@ def test_clip_cases_in_fp32(name):
     for bias in (25.0, -25.0):
         th = theta.copy()
         th[j] = bias
-        lp64, g64 = hr.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64)
-        lp32, g32 = hr.target_log_prob_and_grad(spec, th, eta, X, Y, np.float32)
+        lp64, g64 = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64)
+        lp32, g32 = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float32)
         assert np.isfinite(lp32) and abs(lp32 - lp64) <= 2e-6 * abs(lp64) and max(tensor_errs(spec, g32, g64, 1e-3)) <= 5e-5
-        assert g64[j] == hr.prior_grad_flat(spec, th, eta, np.float64)[j]
+        assert g64[j] == o.prior_grad(spec.layers[-1], eta[-4:].astype(np.float64), *o.unflatten(spec, th.astype(np.float64))[-1], np.float64)[1][1, 0]
 
 
 def test_cases_are_the_student_cases_ending_in_two():

@@ -2,7 +2,7 @@
 datasets hold both sides of the clip in every 16-row tile, the Poisson `high` datasets keep the fp32 gradient sums finite, and no last-layer
 bias gradient is a cancelled sum; (2) the fp32 arm of each reference (the kernel's formula operation by operation) against its fp64 arm
 at every dataset, in the suite's metrics: the printed gaps are what the GPU module's bands come from (lik_edge_cases.arms); (3) sensitivity:
-seven subtly wrong element formulas, applied to a copy of the fp32 arm kept HERE (nothing in tests/*_ref.py changes), are caught by at least
+seven subtly wrong element formulas, applied to a copy of the fp32 arm kept HERE (nothing in the oracle changes), are caught by at least
 one named band, and the ordinary CASES problems of the likelihood modules let most of them through.
 
 Measured here (fp32 arm against fp64 over all datasets; NOTES.md has the table): value gaps to 1.5e-5, gradient gaps to 5.5e-5, both at
@@ -86,7 +86,7 @@ def test_parametrisation_covers_every_case_and_band():
 
 # ---------------------------------------------------------------------------------------------------------------------- the fp32 arm, copied
 def log1p32(u, mut=None):
-    """student_ref.log1p_kernel32; (a): log(1 + u) in fp32; (b): the switch at u < 4"""
+    """the oracle's log1p_kernel32; (a): log(1 + u) in fp32; (b): the switch at u < 4"""
     u = np.asarray(u, dtype=np.float32)
     one, two = np.float32(1), np.float32(2)
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
@@ -104,8 +104,8 @@ def elem32(ds, f, mut=None):
     f = np.asarray(f, dtype=np.float32)
     with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
         if ds.lik == "hetero":
-            y = np.asarray(hr.targets(ds.Y, f.shape[1]), dtype=np.float32)
-            G = np.float32(hr.LOG_CLIP)
+            y = np.asarray(o.hetero_targets(ds.Y, f.shape[1]), dtype=np.float32)
+            G = np.float32(o.LOG_CLIP)
             g = f[1]
             gc = np.where(g < -G, -G, g)
             gc = np.where(g > G, G, gc).astype(np.float32)
@@ -119,7 +119,7 @@ def elem32(ds, f, mut=None):
             return term[None], np.stack([ru, dg]).astype(np.float32)
         y = np.asarray(ds.Y, dtype=np.float32).reshape(f.shape[1], -1).T
         if ds.lik == "student":
-            nu32, s32 = np.float32(ds.par["nu"]), np.float32(sr.scale_of(ds.spec))
+            nu32, s32 = np.float32(ds.par["nu"]), np.float32(o.student_scale(ds.spec))
             r = y - f
             k = one / (nu32 * s32 * s32)
             u = r * r * k
@@ -220,9 +220,8 @@ def ordinary(lik):
         return out
     mod = {"student": sr, "negbin": nb, "hetero": hr}[lik]
     for name in mod.CASES:
-        pr = mod.problem(name)
-        spec, X, Y, theta, eta = pr[:5]
-        par = {"nu": pr[5], "s": spec.fixed_sd} if lik == "student" else {"r": pr[5]} if lik == "negbin" else {}
+        spec, X, Y, theta, eta = mod.problem(name)
+        par = {"nu": spec.lik_df, "s": spec.fixed_sd} if lik == "student" else {"r": spec.lik_df} if lik == "negbin" else {}
         out[name] = E.Dataset(lik=lik, case=name, band="CASES", spec=spec, X=X, Y=Y, theta=theta, eta=eta, par=par, mix=None)
     return out
 

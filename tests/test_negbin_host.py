@@ -1,8 +1,8 @@
-"""NegativeBinomialLikelihood (TBNN_LIK_NEG_BINOMIAL) without a GPU: the tests' fp64 reference (tests/negbin_ref.py) against SciPy's
+"""NegativeBinomialLikelihood (TBNN_LIK_NEG_BINOMIAL) without a GPU: the oracle's fp64 negative-binomial likelihood against SciPy's
 negative-binomial log mass at integer targets and against central differences, the Python class and the predictor's plumbing on a stub
 chain, the kernels' likelihood code and the run-time kernel plumbing, the C ABI's admission rules (tbnn_fused_kernel_available runs the
 descriptor checks of tbnn_create on the host), and `test_reference_in_fp32_stays_inside_the_bands`: the kernel's own formula in fp32
-(negbin_ref's fp32 arm) against the fp64 definition at every case of tests/test_gpu_negbin.py, inside the project's bands -- value 4e-6
+(the oracle's fp32 arm) against the fp64 definition at every case of tests/test_gpu_negbin.py, inside the project's bands -- value 4e-6
 relative, gradient 1e-4 of each tensor's largest entry, log accept ratio 2e-2 + 1e-4 |lar| + 4e-7 |logp|.  Measured, fp32 arm vs fp64 over
 the 13 cases: value gaps 1.0e-8 .. 1.2e-7, gradient gaps 1.0e-7 .. 1.0e-6: no case needs a band of its own."""
 import ctypes as C
@@ -32,7 +32,7 @@ def test_reference_formula():
     for r in (0.5, 2.5, 30.0, 1e4):
         y = rng.poisson(rng.gamma(r, np.exp(np.clip(f, -5, 8)) / r)).T.astype(np.float64)          # [rows, d_out], integers
         y[0] = 0.0
-        got = nb.terms(f, y, r)
+        got = o.negbin_terms(f, y, r)
         assert got.shape == (3, 50) and got.dtype == np.float64 and np.all(np.isfinite(got))
         # SciPy: nbinom(n = r, p = r / (r + mu)); its p is formed from f here as the stable sigmoid
         p = np.where(f > math.log(r), np.exp(math.log(r) - f) / (1.0 + np.exp(math.log(r) - f)), 1.0 / (1.0 + np.exp(f - math.log(r))))
@@ -53,9 +53,9 @@ def test_reference_formula():
     pois = y.T * f[1:] - np.exp(f[1:]) - np.vectorize(math.lgamma)(y.T + 1.0)
     # (the two log masses differ by ((y - mu)^2 - y) / (2 r) to first order in 1 / r; the lgamma differences at r = 1e7 add ~1e-7)
     mu = np.exp(f[1:])
-    assert np.all(np.abs(nb.terms(f[1:], y, 1e7) - pois) <= ((y.T - mu) ** 2 + y.T + 1.0) / 1e7 + 1e-6)
+    assert np.all(np.abs(o.negbin_terms(f[1:], y, 1e7) - pois) <= ((y.T - mu) ** 2 + y.T + 1.0) / 1e7 + 1e-6)
     # the delta is r (y - mu) / (r + mu), bounded by r from below
-    _t, d = nb.elementwise(f, np.zeros((50, 3)), 2.5, np.float64)
+    _t, d = o.negbin_elementwise(f, np.zeros((50, 3)), 2.5, np.float64)
     assert np.all(d >= -2.5) and d[0, 1] == pytest.approx(-2.5, rel=1e-9)
 
 
@@ -64,18 +64,18 @@ def test_reference_gradient_against_central_differences():
     th = theta.astype(np.float64)
     w = np.random.default_rng(2).integers(0, 3, 40).astype(np.float64)
     for weights in (None, w):
-        lp, g = nb.target_log_prob_and_grad(spec, 2.5, th, eta, X, Y, np.float64, weights)
+        lp, g = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, weights)
         h = 1e-6
         for j in range(0, spec.n_params, 3):
             e = np.zeros_like(th)
             e[j] = h
-            num = (nb.target_log_prob_and_grad(spec, 2.5, th + e, eta, X, Y, np.float64, weights)[0]
-                   - nb.target_log_prob_and_grad(spec, 2.5, th - e, eta, X, Y, np.float64, weights)[0]) / (2 * h)
+            num = (o.target_log_prob_and_grad(spec, th + e, eta, X, Y, np.float64, weights)[0]
+                   - o.target_log_prob_and_grad(spec, th - e, eta, X, Y, np.float64, weights)[0]) / (2 * h)
             assert abs(num - g[j]) <= 1e-6 * max(1.0, abs(g[j])), (j, num, g[j])
     # integer weights are duplicated rows, the constant included
     idx = np.repeat(np.arange(40), w.astype(int))
-    a = nb.target_log_prob_and_grad(spec, 2.5, th, eta, X, Y, np.float64, w)
-    b = nb.target_log_prob_and_grad(spec, 2.5, th, eta, X[idx], Y[idx], np.float64)
+    a = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, w)
+    b = o.target_log_prob_and_grad(spec, th, eta, X[idx], Y[idx], np.float64)
     assert math.isclose(a[0], b[0], rel_tol=1e-12) and np.allclose(a[1], b[1], rtol=1e-10, atol=1e-12)
 
 
@@ -85,10 +85,10 @@ def test_fp32_arm_is_finite_for_every_finite_log_rate():
     f = np.array([[-1e30, -1e4, -104.0, -88.0, -20.0, 0.0, 20.0, 88.0, 89.0, 104.0, 1e4, 1e30]], dtype=np.float32)
     y = np.full((f.shape[1], 1), 7.0, dtype=np.float32)
     for r in (0.5, 1e4):
-        t, d = nb.elementwise(f, y, r, np.float32)
+        t, d = o.negbin_elementwise(f, y, r, np.float32)
         assert np.all(np.isfinite(t)) and np.all(np.isfinite(d)) and np.all(t <= 0)
         assert np.all(d <= 7.0) and np.all(d >= -np.float32(r))
-    t, d = nb.elementwise(np.array([[np.nan]], dtype=np.float32), y[:1], 2.5, np.float32)
+    t, d = o.negbin_elementwise(np.array([[np.nan]], dtype=np.float32), y[:1], 2.5, np.float32)
     assert np.isnan(t).all() and np.isnan(d).all()
 
 
@@ -96,9 +96,10 @@ def test_fp32_arm_is_finite_for_every_finite_log_rate():
 def test_reference_in_fp32_stays_inside_the_bands(name):
     """CPU arithmetic only: the kernel's formula in fp32 against the fp64 definition -- value, gradient per tensor, and the log accept ratio
     of the GPU module's injected transition"""
-    spec, X, Y, theta, eta, r = nb.problem(name)
+    spec, X, Y, theta, eta = nb.problem(name)
+    r = spec.lik_df
     lp64, g64 = nb.ref64(name)
-    lp32, g32 = nb.target_log_prob_and_grad(spec, r, theta, eta, X, Y, np.float32)
+    lp32, g32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
     gv, gg = abs(lp32 - lp64) / max(abs(lp64), 1.0), tensor_errs(spec, g32, g64, 1e-3)
     f = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
     t = f - math.log(r)
@@ -107,8 +108,8 @@ def test_reference_in_fp32_stays_inside_the_bands(name):
     assert Y.min() == 0 and Y.max() > 20 and np.all(Y == np.floor(Y))
     assert gv <= 4e-6 and max(gg) <= 1e-4, (gv, gg)
     p0 = np.random.default_rng(4).standard_normal(spec.n_params).astype(np.float32)
-    r64 = nb.weight_step(spec, r, theta, eta, X, Y, nb.step_size(name), 4, p0, -1e30, np.float64)
-    r32 = nb.weight_step(spec, r, theta, eta, X, Y, nb.step_size(name), 4, p0, -1e30, np.float32)
+    r64 = o.weight_step(spec, theta, eta, X, Y, nb.step_size(name), 4, p0, -1e30, np.float64)
+    r32 = o.weight_step(spec, theta, eta, X, Y, nb.step_size(name), 4, p0, -1e30, np.float32, np.float64)
     tol = 2e-2 + 1e-4 * abs(r64.log_accept_ratio) + 4e-7 * abs(lp64)
     print(f"[negbin] {name}: lar fp32 {r32.log_accept_ratio:.6g} fp64 {r64.log_accept_ratio:.6g} (band {tol:.3g})")
     assert abs(r32.log_accept_ratio - r64.log_accept_ratio) <= tol
@@ -138,7 +139,7 @@ def test_python_class_terms_and_shapes():
     y[5] += 120.0
     out = lik.makeResponseLikelihood(None, predict=lambda train, _x: f, realVals=y)
     assert out.shape == (2, 31) and out.dtype == np.float64 and np.all(np.isfinite(out))
-    np.testing.assert_allclose(out, nb.terms(f.astype(np.float64), y.astype(np.float64), 4.0), rtol=1e-12)
+    np.testing.assert_allclose(out, o.negbin_terms(f.astype(np.float64), y.astype(np.float64), 4.0), rtol=1e-12)
     for bad in (0.0, -1.0, float("nan"), float("inf")):
         with pytest.raises(ValueError):
             NegativeBinomialLikelihood(dispersion=bad)
@@ -182,7 +183,7 @@ def test_predictor_host_paths():
     lik = NegativeBinomialLikelihood(dispersion=3.0)
     got = p._data_logprob(lik, X, Y, 1)
     for g, f in zip(got, preds):
-        assert np.isclose(g, nb.terms(f.astype(np.float64), Y.astype(np.float64), 3.0).sum(), rtol=1e-6)
+        assert np.isclose(g, o.negbin_terms(f.astype(np.float64), Y.astype(np.float64), 3.0).sum(), rtol=1e-6)
     assert got[0] > got[1]
     # the stub chain: the likelihood code, no sd, the dispersion set on the forward chain before the call, the pair for counts
     p = stub_predictor(lik, HYPERS)

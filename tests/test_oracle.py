@@ -97,6 +97,16 @@ def _torch_target(spec, theta, eta, X, Y, w=None):
             return (wt * y * torch.log_softmax(f, dim=0)).sum()
         if spec.likelihood == o.LIK_POISSON:
             return (wt * (y * f - torch.exp(f) - torch.lgamma(y + 1))).sum()
+        if spec.likelihood == o.LIK_STUDENT_T:
+            nu, s = (torch.tensor(v, dtype=torch.float64) for v in (spec.lik_df, spec.fixed_sd))
+            return (wt * torch.distributions.StudentT(nu, f, s).log_prob(y)).sum()
+        if spec.likelihood == o.LIK_NEG_BINOMIAL:
+            r = torch.tensor(spec.lik_df, dtype=torch.float64)
+            lden = torch.logaddexp(f, torch.log(r))
+            return (wt * (torch.lgamma(y + r) - torch.lgamma(r) - torch.lgamma(y + 1) + y * (f - lden) + r * (torch.log(r) - lden))).sum()
+        if spec.likelihood == o.LIK_HETERO_GAUSSIAN:
+            gc = torch.clamp(f[1], -math.log(1e8), math.log(1e8))
+            return (wt * (-0.5 * math.log(2 * math.pi) - gc - 0.5 * (y[0] - f[0]) ** 2 * torch.exp(-2 * gc))).sum()
         assert spec.likelihood in (o.LIK_GAUSSIAN, o.LIK_FIXED_GAUSSIAN)
         s = torch.clamp(et[-1] ** 2, 1e-8, 1e8) if spec.likelihood == o.LIK_GAUSSIAN else torch.tensor(spec.fixed_sd, dtype=torch.float64)
         n_el = wt.sum() * f.shape[0]                     # (unweighted: f.numel(), exactly)
@@ -189,9 +199,11 @@ def test_hand_coded_gradients_match_autograd_last_activation(case):
     np.testing.assert_allclose(hg, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
 
 
-# the extensions beyond the reference (the categorical and Poisson likelihoods, per-row likelihood weights): autograd is all that pins them
+# the extensions beyond the reference (the categorical, Poisson, Student-t, negative-binomial and heteroscedastic Gaussian likelihoods,
+# per-row likelihood weights): autograd is all that pins them
 EXT_CASES = {
-    # dims, rows, hidden activation, prior, likelihood, targets, weighted
+    # dims, rows, hidden activation, prior, likelihood, targets (Student-t: nu, at the scale STUDENT_S; negative binomial: r;
+    # heteroscedastic: None, or the last bias of output 1 that puts every row's log-sd beyond the clip), weighted
     "cat_onehot": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "onehot", False),
     "cat_soft": ([4, 12, 12, 3], 80, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_CATEGORICAL, "soft", False),
     "cat_large_logits": ([4, 12, 12, 3], 80, o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "large", False),
@@ -202,18 +214,34 @@ EXT_CASES = {
     "weighted_bern": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_BERNOULLI, None, True),
     "weighted_cat": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "soft", True),
     "weighted_pois": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_POISSON, "counts", True),
+    "student_nu1": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_STUDENT_T, 1.0, False),
+    "student_nu2.5": ([4, 12, 12, 2], 80, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_STUDENT_T, 2.5, False),
+    "student_nu1e4": ([3, 12, 9, 2], 60, o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_STUDENT_T, 1e4, False),
+    "negbin_r0.5": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_GAUSSIAN, o.LIK_NEG_BINOMIAL, 0.5, False),
+    "negbin_r30": ([4, 12, 12, 2], 80, o.ACT_SIGMOID, o.PRIOR_CAUCHY, o.LIK_NEG_BINOMIAL, 30.0, False),
+    "negbin_r1e4": ([3, 12, 9, 2], 60, o.ACT_ELU, o.PRIOR_CAUCHY, o.LIK_NEG_BINOMIAL, 1e4, False),
+    "hetero": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_HETERO_GAUSSIAN, None, False),
+    "hetero_gaussian_prior": ([4, 12, 12, 2], 80, o.ACT_RELU, o.PRIOR_GAUSSIAN, o.LIK_HETERO_GAUSSIAN, None, False),
+    "hetero_clip_above": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_HETERO_GAUSSIAN, 25.0, False),
+    "hetero_clip_below": ([3, 12, 9, 2], 60, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_HETERO_GAUSSIAN, -25.0, False),
+    "weighted_student": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_STUDENT_T, 2.5, True),
+    "weighted_negbin": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_NEG_BINOMIAL, 30.0, True),
+    "weighted_hetero": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_HETERO_GAUSSIAN, None, True),
 }
+STUDENT_S = 0.25                         # (exact in fp32: the oracle takes the scale as the library receives it)
+COUNTS = (o.LIK_POISSON, o.LIK_NEG_BINOMIAL)
 
 
 def _ext_problem(case):
     dims, n, act, prior, lik, targets, weighted = EXT_CASES[case]
-    if lik in (o.LIK_CATEGORICAL, o.LIK_POISSON):
+    if lik not in (o.LIK_GAUSSIAN, o.LIK_FIXED_GAUSSIAN, o.LIK_BERNOULLI):
         _g, X, Yr, theta, eta = o.synth_problem(dims, n, act, prior, o.LIK_GAUSSIAN)        # standardised teacher outputs [n, K]
-        spec = o.make_spec(dims, act, prior, lik, o.ACT_NONE)
+        spec = o.make_spec(dims, act, prior, lik, o.ACT_NONE, fixed_sd=STUDENT_S,
+                           lik_df=targets if lik in (o.LIK_STUDENT_T, o.LIK_NEG_BINOMIAL) else 0.0)
         eta = eta[:spec.n_hypers]                                                           # no likelihood hyper
     else:
         spec, X, Y, theta, eta = o.synth_problem(dims, n, act, prior, lik)
-    ow, _ob = spec.offsets()[-1]
+    ow, ob = spec.offsets()[-1]
     theta = theta.astype(np.float64)
     if lik == o.LIK_CATEGORICAL:
         e = np.exp(2.0 * Yr - (2.0 * Yr).max(axis=1, keepdims=True))
@@ -221,7 +249,7 @@ def _ext_problem(case):
         if targets == "large":           # the last layer scaled until the logits pass +-70: exp(f) without the max shift overflows in fp32
             theta[ow:] *= 80.0 / np.abs(o.forward(spec, theta, X, np.float64)).max()
             assert np.abs(o.forward(spec, theta, X, np.float64)).max() > 70
-    if lik == o.LIK_POISSON:
+    if lik in COUNTS:
         Y = np.random.default_rng(11).poisson(np.exp(np.clip(1.5 + 1.5 * Yr, -3.0, 6.0))).astype(np.float64)
         Y[::5] = 0.0                     # zero counts
         Y[1::5] += 0.5                   # counts need not be integers: lgamma(y + 1)
@@ -229,6 +257,18 @@ def _ext_problem(case):
         if np.abs(f).max() > 5.0:        # the state's own log-rates within [-5, 5]
             theta[ow:] *= 5.0 / np.abs(f).max()
         assert np.abs(o.forward(spec, theta, X, np.float64)).max() <= 5.0 + 1e-9 and (Y == 0).any() and (Y % 1 != 0).any()
+    if lik == o.LIK_STUDENT_T:           # the teacher's outputs plus N(0, s^2), every tenth row moved by 30 s: both ends of r^2 / (nu s^2)
+        Y = Yr + STUDENT_S * np.random.default_rng(11).standard_normal(Yr.shape)
+        Y[::10] += 30.0 * STUDENT_S
+    if lik == o.LIK_HETERO_GAUSSIAN:     # one target per row; the state's own outputs within [-5, 5], so that exp(-2 g) stays moderate
+        Y = Yr[:, 0] + 0.3 * np.random.default_rng(11).standard_normal(n)
+        theta[ow:] *= min(1.0, 5.0 / np.abs(o.forward(spec, theta, X, np.float64)).max())
+        if targets is not None:          # the clip: every row's log-sd beyond +-log(1e8), dL/dg exactly 0
+            theta[ob + 1] = targets
+            if targets > 0:              # above the clip u = exp(-2 G) = 1e-16: residuals of 1e16 keep dL/df = r u at O(1), where an error in it shows
+                Y = Y + 1e16 * (-1.0) ** np.arange(n)
+            f = o.forward(spec, theta, X, np.float64)
+            assert np.all(np.abs(f[1]) > o.LOG_CLIP) and np.all(o.likelihood_grad(spec, eta, f, Y, np.float64)[1] == 0)
     return spec, X, np.asarray(Y, np.float64), theta, eta, (_real_weights(n) if weighted else None)
 
 
@@ -259,7 +299,8 @@ def test_extension_gradients_match_autograd(case):
         np.testing.assert_allclose(hg2, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
 
 
-@pytest.mark.parametrize("case", ["weighted_gauss", "weighted_fixed_gauss", "weighted_bern", "weighted_cat", "weighted_pois"])
+@pytest.mark.parametrize("case", ["weighted_gauss", "weighted_fixed_gauss", "weighted_bern", "weighted_cat", "weighted_pois",
+                                  "weighted_student", "weighted_negbin", "weighted_hetero"])
 def test_integer_weights_are_repeated_rows(case):
     spec, X, Y, theta, eta, _w = _ext_problem(case)
     w = np.random.default_rng(11).integers(0, 4, len(X))
@@ -275,7 +316,7 @@ def test_integer_weights_are_repeated_rows(case):
     np.testing.assert_allclose(hg, hg_r, rtol=0, atol=1e-12 * np.abs(hg_r).max())
 
 
-@pytest.mark.parametrize("case", ["weighted_cat", "weighted_pois"])
+@pytest.mark.parametrize("case", ["weighted_cat", "weighted_pois", "weighted_student", "weighted_negbin", "weighted_hetero"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_unit_weights_are_exactly_unweighted(case, dtype):
     spec, X, Y, theta, eta, _w = _ext_problem(case)
@@ -284,7 +325,7 @@ def test_unit_weights_are_exactly_unweighted(case, dtype):
     assert lp1 == lp and np.array_equal(g1, g)
 
 
-@pytest.mark.parametrize("code", [4, 6, -1])
+@pytest.mark.parametrize("code", [4, 6, -1, 7, 9, 11])
 def test_unknown_likelihood_code_raises(code):
     """a code the oracle does not know is an error in every target, never another likelihood's chain"""
     spec, X, Y, theta, eta = o.synth_problem([3, 5, 2], 10, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_FIXED_GAUSSIAN)

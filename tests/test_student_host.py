@@ -1,7 +1,7 @@
-"""StudentTLikelihood (TBNN_LIK_STUDENT_T) without a GPU: the tests' fp64 reference (tests/student_ref.py) against SciPy's t density (or, without
+"""StudentTLikelihood (TBNN_LIK_STUDENT_T) without a GPU: the oracle's fp64 Student-t likelihood against SciPy's t density (or, without
 SciPy, the Cauchy density at nu = 1) and against central differences, the Python class, the kernels' likelihood code and the run-time
 kernel plumbing, the C ABI's admission rules (tbnn_fused_kernel_available runs the descriptor checks of tbnn_create on the host), and
-`test_reference_in_fp32_stays_inside_the_bands`: the kernel's own formula in fp32 (student_ref's fp32 arm) against the fp64 definition at
+`test_reference_in_fp32_stays_inside_the_bands`: the kernel's own formula in fp32 (the oracle's fp32 arm) against the fp64 definition at
 every case of tests/test_gpu_student.py, inside the project's bands -- value 4e-6 relative, gradient 1e-4 of each tensor's largest entry, log
 accept ratio 2e-2 + 1e-4 |lar| + 4e-7 |logp|.  That test decided the form of log1p the kernels use (csrc/common.hpp log1p_fast: a series
 below 1/4, the hardware log2 above).  Measured, fp32 arm vs fp64 over the 13 cases: value gaps 1.5e-9 .. 9.4e-8, gradient gaps 9.9e-8 .. 1.8e-6:
@@ -33,7 +33,7 @@ def test_reference_formula():
     except ImportError:
         student = None
     for nu, s in ((1.0, 0.1), (2.5, 1.0), (30.0, 0.1), (1e4, 1.0)):
-        got = sr.terms(f, y, nu, s)
+        got = o.student_terms(f, y, nu, s)
         assert got.shape == (3, 50) and got.dtype == np.float64
         if student is not None:
             # (the constant differences two lgamma values, 3.8e4 each at nu = 1e4: a few of THEIR ulps is all either side can promise)
@@ -48,18 +48,18 @@ def test_reference_gradient_against_central_differences():
     th = theta.astype(np.float64)
     w = np.random.default_rng(2).integers(0, 3, 40).astype(np.float64)
     for weights in (None, w):
-        lp, g = sr.target_log_prob_and_grad(spec, 2.5, th, eta, X, Y, np.float64, weights)
+        lp, g = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, weights)
         h = 1e-6
         for j in range(0, spec.n_params, 3):
             e = np.zeros_like(th)
             e[j] = h
-            num = (sr.target_log_prob_and_grad(spec, 2.5, th + e, eta, X, Y, np.float64, weights)[0]
-                   - sr.target_log_prob_and_grad(spec, 2.5, th - e, eta, X, Y, np.float64, weights)[0]) / (2 * h)
+            num = (o.target_log_prob_and_grad(spec, th + e, eta, X, Y, np.float64, weights)[0]
+                   - o.target_log_prob_and_grad(spec, th - e, eta, X, Y, np.float64, weights)[0]) / (2 * h)
             assert abs(num - g[j]) <= 1e-6 * max(1.0, abs(g[j])), (j, num, g[j])
     # the data term's constant counts W = sum w rows; integer weights are duplicated rows
     idx = np.repeat(np.arange(40), w.astype(int))
-    a = sr.target_log_prob_and_grad(spec, 2.5, th, eta, X, Y, np.float64, w)
-    b = sr.target_log_prob_and_grad(spec, 2.5, th, eta, X[idx], Y[idx], np.float64)
+    a = o.target_log_prob_and_grad(spec, th, eta, X, Y, np.float64, w)
+    b = o.target_log_prob_and_grad(spec, th, eta, X[idx], Y[idx], np.float64)
     assert math.isclose(a[0], b[0], rel_tol=1e-12) and np.allclose(a[1], b[1], rtol=1e-10, atol=1e-12)
 
 
@@ -67,9 +67,10 @@ def test_reference_gradient_against_central_differences():
 def test_reference_in_fp32_stays_inside_the_bands(name):
     """CPU arithmetic only: the kernel's formula in fp32 against the fp64 definition -- value, gradient per tensor, and the log accept ratio
     of the GPU module's injected transition"""
-    spec, X, Y, theta, eta, nu = sr.problem(name)
+    spec, X, Y, theta, eta = sr.problem(name)
+    nu = spec.lik_df
     lp64, g64 = sr.ref64(name)
-    lp32, g32 = sr.target_log_prob_and_grad(spec, nu, theta, eta, X, Y, np.float32)
+    lp32, g32 = o.target_log_prob_and_grad(spec, theta, eta, X, Y, np.float32)
     gv, gg = abs(lp32 - lp64) / max(abs(lp64), 1.0), tensor_errs(spec, g32, g64, 1e-3)
     f = o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
     u = (Y.reshape(f.shape[1], -1).T - f) ** 2 / (nu * spec.fixed_sd ** 2)
@@ -77,8 +78,8 @@ def test_reference_in_fp32_stays_inside_the_bands(name):
     assert u.min() < 0.01 and u.max() > 0.25                    # both branches of the kernel's log1p, in one problem
     assert gv <= 4e-6 and max(gg) <= 1e-4, (gv, gg)
     p0 = np.random.default_rng(4).standard_normal(spec.n_params).astype(np.float32)
-    r64 = sr.weight_step(spec, nu, theta, eta, X, Y, sr.step_size(name), 4, p0, -1e30, np.float64)
-    r32 = sr.weight_step(spec, nu, theta, eta, X, Y, sr.step_size(name), 4, p0, -1e30, np.float32)
+    r64 = o.weight_step(spec, theta, eta, X, Y, sr.step_size(name), 4, p0, -1e30, np.float64)
+    r32 = o.weight_step(spec, theta, eta, X, Y, sr.step_size(name), 4, p0, -1e30, np.float32, np.float64)
     tol = 2e-2 + 1e-4 * abs(r64.log_accept_ratio) + 4e-7 * abs(lp64)
     print(f"[student] {name}: lar fp32 {r32.log_accept_ratio:.6g} fp64 {r64.log_accept_ratio:.6g} (band {tol:.3g})")
     assert abs(r32.log_accept_ratio - r64.log_accept_ratio) <= tol
@@ -100,7 +101,7 @@ def test_python_class_terms_and_shapes():
     y[5] += 12.0
     out = lik.makeResponseLikelihood(None, predict=lambda train, _x: f, realVals=y)
     assert out.shape == (2, 31) and out.dtype == np.float64 and np.all(np.isfinite(out))
-    np.testing.assert_allclose(out, sr.terms(f.astype(np.float64), y.astype(np.float64), 4.0, float(np.float64(0.3))), rtol=1e-12)
+    np.testing.assert_allclose(out, o.student_terms(f.astype(np.float64), y.astype(np.float64), 4.0, float(np.float64(0.3))), rtol=1e-12)
     for bad in ({"df": 0.0, "sd": 1.0}, {"df": -1.0, "sd": 1.0}, {"df": float("nan"), "sd": 1.0}, {"df": float("inf"), "sd": 1.0}, {"df": 3.0, "sd": 0.0}):
         with pytest.raises(ValueError):
             StudentTLikelihood(**bad)
@@ -119,7 +120,7 @@ def test_predictor_host_paths():
     lik = StudentTLikelihood(df=3.0, sd=0.1)
     got = p._data_logprob(lik, X, Y, 1)
     for g, f in zip(got, preds):
-        assert np.isclose(g, sr.terms(f.astype(np.float64), Y.astype(np.float64), 3.0, 0.1).sum(), rtol=1e-6)
+        assert np.isclose(g, o.student_terms(f.astype(np.float64), Y.astype(np.float64), 3.0, 0.1).sum(), rtol=1e-6)
     assert got[0] > got[1]
     p.likelihood = lik
     for call in (lambda: p.predictiveQuantiles(X, 0.5), lambda: p.predictiveInterval(X), lambda: p.predictiveCDF(X, Y)):
