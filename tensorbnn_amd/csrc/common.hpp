@@ -106,11 +106,19 @@ struct Scal {
 // Likelihood standard deviation used on the hot path.
 // Gaussian: clip(eta_last^2, 1e-8, 1e8) (likelihood.py:88 + BNN_functions.py:23-24);
 // FixedGaussian: sd as given (likelihood.py:162), same clip inside multivariateLogProb.
-__device__ __forceinline__ float lik_sigma(const NetDev& nd, const float* __restrict__ eta) {
-    float s = (nd.lik == TBNN_LIK_GAUSSIAN) ? eta[nd.H - 1] * eta[nd.H - 1] : nd.fixed_sd;
+// The clip is written once (lik_sigma_clip); lik_sigma_from is lik_sigma for a caller that has loaded the hyper already
+// (k_fwd_bwd_fast3 requests it with its first batch of loads; eta_last is not used unless the likelihood has its own noise hyper).
+__device__ __forceinline__ float lik_sigma_clip(float s) {
     s = fmaxf(s, 1e-8f);
     s = fminf(s, 1e8f);
     return s;
+}
+__device__ __forceinline__ float lik_sigma(const NetDev& nd, const float* __restrict__ eta) {
+    const float s = (nd.lik == TBNN_LIK_GAUSSIAN) ? eta[nd.H - 1] * eta[nd.H - 1] : nd.fixed_sd;
+    return lik_sigma_clip(s);
+}
+__device__ __forceinline__ float lik_sigma_from(const NetDev& nd, float eta_last) {
+    return lik_sigma_clip((nd.lik == TBNN_LIK_GAUSSIAN) ? eta_last * eta_last : nd.fixed_sd);
 }
 
 // Student-t (TBNN_LIK_STUDENT_T).  A kernel derives two constants once in its prologue: k = 1 / (nu s^2), which scales the squared residual

@@ -1437,7 +1437,8 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     using C = F3Cfg<S>;
     // every argument the prologue's requests are made from, read here: one batch of scalar loads with one wait, in front of the
     // branches below (the early exit, the stamp), each of which otherwise gets a group of loads and a wait of its own
-    asm volatile("" :: "s"(cs.ctl), "s"(cs.t), "s"(cs.img), "s"(stamps), "s"(qimg), "s"(X), "s"(Y), "s"(n), "s"(gridDim.x));
+    asm volatile("" :: "s"(cs.ctl), "s"(cs.t), "s"(cs.img), "s"(stamps), "s"(qimg), "s"(X), "s"(Y), "s"(n), "s"(gridDim.x),
+                 "s"(eta), "s"(cs.eta), "s"(nd.lik), "s"(nd.H));
     // gridDim.y = chains of a multi-chain handle (tbnn_create_multi): this workgroup's chain
     if (chain_done(cs.ctl, cs.t, blockIdx.y)) return;           // a chain past its own L (per-chain step control)
     qimg += (size_t)blockIdx.y * cs.img; eta += (size_t)blockIdx.y * cs.eta; slabs += (size_t)blockIdx.y * cs.slab; pstat += (size_t)blockIdx.y * PSTAT_CAP;
@@ -1476,6 +1477,10 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     // first forward pass) -- and only then the tile split below, whose division used to run before a single request had left.
     long tile = wg;
     fetch(tile);
+    // the noise scale's hyper (lik_sigma) leaves with the first requests, unconditionally (entry 0 where the likelihood has none of its
+    // own: every chain has its layers' four): as a branch behind the barrier it was a memory round trip of its own with nothing under it
+    const bool eta_lik = nd.lik == TBNN_LIK_GAUSSIAN;
+    const float eta_s = eta[eta_lik ? nd.H - 1 : 0];
     constexpr bool WTDMA = C::STATIC_FLOATS > C::WB_FLOATS;
     // (the image is read with a clamped index, not a predicated load: a predicate made the compiler copy a register the loads in
     // flight were still writing, and wait for all of them in the middle of the group; the store below keeps its bound)
@@ -1495,11 +1500,26 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         if (rem > 0 && rem <= 2 * G) { main_end = ntiles - rem; ncoop = rem <= G ? 1 : 2; }
     }
     if constexpr ((TBNN_SKEL & 1) != 0) { main_end = 0; ncoop = 0; }       // diagnostic: the launch's fixed cost
+    f32x4 dW[C::DW3_TILES > 0 ? C::DW3_TILES : 1];
+    float FP[C::FP_REGS > 0 ? C::FP_REGS : 1];
     {
         // the zero fill of the per-wave images runs under the image loads' latency, then the LDS stores
         __builtin_amdgcn_sched_barrier(0);
         float4* z = reinterpret_cast<float4*>(wl);
         for (int e = lane; e < C::WAVE3_FLOATS / 4; e += 64) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+        __builtin_amdgcn_sched_barrier(0);
+        // ... and so does everything else that needs registers and lane ids only: the ones columns of the activation images (behind
+        // the zero fill: a wave's LDS writes land in order) and the zero fill of both accumulator sets, each pinned where it stands (an
+        // empty statement that takes the register: left alone the compiler sinks them into the tile loop's preheader, 140 instructions
+        // behind the barrier with nothing to hide them)
+        if (g == 0) wl[C::aoff3(0) + d_in * C::PR + i16] = 1.f;
+#pragma unroll
+        for (int l = 1; l < C::NLM3; ++l)
+            if (C::in(l) % 16 == 0 && g == 0) wl[C::aoff3(l) + C::in(l) * C::PR + i16] = 1.f;
+#pragma unroll
+        for (int t = 0; t < C::DW3_TILES; ++t) { dW[t] = f32x4{0.f, 0.f, 0.f, 0.f}; asm volatile("" : "+a"(dW[t])); }
+#pragma unroll
+        for (int t = 0; t < C::FP_REGS; ++t) { FP[t] = 0.f; asm volatile("" : "+v"(FP[t])); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 0; k < IMG_IT; ++k) { const int e = tid + k * FAST_THREADS; if (e < IMG_N4) *reinterpret_cast<f32x4*>(lds + 4 * e) = imgv[k]; }
@@ -1541,21 +1561,11 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
     TB_STAMP(1); TSTAMPO(58);
 
     constexpr int NFd = C::maxNF() > 0 ? C::maxNF() : 1;
-    f32x4 dW[C::DW3_TILES > 0 ? C::DW3_TILES : 1];
-#pragma unroll
-    for (int t = 0; t < C::DW3_TILES; ++t) dW[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float FP[C::FP_REGS > 0 ? C::FP_REGS : 1];
-#pragma unroll
-    for (int t = 0; t < C::FP_REGS; ++t) FP[t] = 0.f;
-    const float sigma = lik_sigma(nd, eta);
+    const float sigma = lik_sigma_from(nd, eta_s);       // lik_sigma, its load made above
     const float inv_var = lik_inv_var<S>(nd, sigma);
     const float np1 = lik_np1<S>(nd);                     // (Student-t: the delta's factor; negative binomial: r; not read otherwise)
     double stat = 0.0;
 
-    if (g == 0) wl[C::aoff3(0) + d_in * C::PR + i16] = 1.f;
-#pragma unroll
-    for (int l = 1; l < C::NLM3; ++l)
-        if (C::in(l) % 16 == 0 && g == 0) wl[C::aoff3(l) + C::in(l) * C::PR + i16] = 1.f;
     typename Fwd3<S, 0>::Pre P0;                 // layer 0's operands (A, bias, fringe weights): the same for every tile
     Fwd3<S, 0>::pre_all(P0, lds, i16, g);
 
@@ -1568,10 +1578,48 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
         __syncthreads();
         wt_pending = false;
     }
-    for (; tile < main_end; tile += W) {
+    // Row bookkeeping of the loop in scalar registers.  Which tile a trip runs is a wave-uniform fact, and so is everything the fetch
+    // and the validity tests ask about it; as 64-bit per-lane arithmetic (there is no scalar 64-bit ordered compare, so `tile <
+    // main_end` and `row < n` were vector compares on SGPR operands) it cost ~19 vector instructions per tile, each ~9 cycles of
+    // matrix time.  Here: a 32-bit trip count; the rows' base addresses as scalar pointers that advance at the back edge, with one
+    // per-lane byte offset computed once; and the one ragged tile (the data set's last, when n % 16 != 0) named by the trip it falls
+    // on, so that every other tile runs without a per-lane predicate, zero substitutes or selects.  A wave requests the next tile's
+    // rows only when it has a next trip (an absent tile is no request at all), behind the likelihood -- the last reader of the current
+    // rows -- so that they land in the registers the current ones leave: no copies at the back edge.
+    // (32 bits: a wave's trips are at most n / 64, and 2^31 of them would be rows past any device's memory; W is the launch's wave count.)
+    int trips = 0, rag_trip = -1;
+    const int nlast = (int)(n - (ntiles - 1) * 16);                     // rows of the last tile: 1 .. 16
+    {
+        const long q = ntiles / W, rem = ntiles % W;
+        const unsigned w32 = (unsigned)wg, r32 = (unsigned)rem;
+        if (main_end == ntiles) {                                       // no cooperative round: the remainder is a plain extra round
+            trips = (int)q + (w32 < r32 ? 1 : 0);
+            if (nlast < 16 && ntiles > 0) {                             // the last tile: wave rem - 1 in trip q, or wave W - 1 in trip q - 1
+                if (r32 > 0) { if (w32 == r32 - 1) rag_trip = (int)q; }
+                else if (w32 == (unsigned)W - 1) rag_trip = (int)q - 1;
+            }
+        } else {
+            trips = (int)q;                                             // (the ragged tile is a cooperative one)
+        }
+        if constexpr ((TBNN_SKEL & 1) != 0) trips = 0;
+    }
+    unsigned xb[C::KS0], yb[d_out];                                     // per-lane byte offsets inside a tile's rows
+#pragma unroll
+    for (int t = 0; t < C::KS0; ++t) xb[t] = 4u * (unsigned)(i16 * d_in + (4 * t + g < d_in ? 4 * t + g : 0));
+#pragma unroll
+    for (int o = 0; o < d_out; ++o) yb[o] = 4u * (unsigned)(i16 * d_out + o);
+    const long xstep = W * (16 * d_in), ystep = W * (16 * d_out), wstep = W * 16;
+    // (the three pointers below run past the arrays on a wave's last trip and on a wave without a tile: they are formed, never read --
+    // every load through them stands behind `trip + 1 < trips`)
+    const float* Xq = X + (wg + W) * (16 * d_in);                       // the NEXT tile's rows
+    const float* Yq = Y + (wg + W) * (16 * d_out);
+    const float* Wq = Y + n * d_out + (wg + W) * 16;                    // (weighted instantiations: row_weight)
+    const unsigned long long cnt_full = __ballot(g == 0), cnt_ragged = __ballot(g == 0 && i16 < nlast);     // lanes that count a row's term
+    auto at = [](const float* base, unsigned byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
+    for (int trip = 0; trip < trips; ++trip, Xq += xstep, Yq += ystep, Wq += wstep) {
         Tile3<S> T;
         float y[d_out];
-        const bool rvalid = tile * 16 + i16 < n;
+        const bool ragged = trip == rag_trip;
 #pragma unroll
         for (int t = 0; t < C::KS0; ++t) {
             T.x0[t] = xn[t];
@@ -1581,7 +1629,6 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int o = 0; o < d_out; ++o) y[o] = yn[o];
         const float wt = wn;
-        fetch(tile + W);
         TSTAMP(0);
         Fwd3<S, 0>::run_h(T, lds, wl, i16, g, P0);
         if (wt_pending) {                       // first tile only, the same on all four waves
@@ -1590,12 +1637,44 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             wt_pending = false;
         }
         // likelihood on the all-fringe last layer
+        // (one evaluation for every tile: which lanes count is a scalar choice between two lane masks, and the ragged tile alone
+        // passes its deltas through a select -- the padding rows' values are computed from zeros and dropped, as they always were)
         float dzf[NFd];
+        const bool cnt = __builtin_amdgcn_inverse_ballot_w64(ragged ? cnt_ragged : cnt_full);
 #pragma unroll
         for (int o = 0; o < d_out; ++o)
-            if constexpr (!S::HET) dzf[o] = rvalid ? lik_delta<S>(T.af[L][o], y[o], inv_var, g == 0, stat, wt, np1) : 0.f;
-        if constexpr (S::HET) lik_pair<S>(T.af[L][0], T.af[L][1], y[0], rvalid, g == 0, stat, wt, dzf);
+            if constexpr (!S::HET) dzf[o] = lik_delta<S>(T.af[L][o], y[o], inv_var, cnt, stat, wt, np1);
+        if constexpr (S::HET) lik_pair<S>(T.af[L][0], T.af[L][1], y[0], true, cnt, stat, wt, dzf);
+        if (ragged) {
+            asm volatile("; ragged tile: deltas of the padding rows");           // (a block of its own: not folded into a select on every tile)
+#pragma unroll
+            for (int o = 0; o < d_out; ++o) dzf[o] = i16 < nlast ? dzf[o] : 0.f;
+        }
         TSTAMP(30);
+        // the requests stay behind the likelihood (nothing that reads memory crosses the statement), and the offsets pass through an
+        // empty statement on every trip: their widening then stays with the loads, where instruction selection makes `scalar base +
+        // 32-bit lane offset` of it, instead of a 64-bit per-lane sum hoisted out of the loop and added to the base on every tile
+        asm volatile("" : "+v"(dzf[0]) :: "memory");
+#pragma unroll
+        for (int t = 0; t < C::KS0; ++t) asm volatile("" : "+v"(xb[t]));
+#pragma unroll
+        for (int o = 0; o < d_out; ++o) asm volatile("" : "+v"(yb[o]));
+        if (trip + 1 < trips) {
+            if (trip + 1 != rag_trip) {
+#pragma unroll
+                for (int t = 0; t < C::KS0; ++t) xn[t] = (4 * t + g < d_in) ? at(Xq, xb[t]) : 0.f;
+#pragma unroll
+                for (int o = 0; o < d_out; ++o) yn[o] = at(Yq, yb[o]);
+                if constexpr (S::WTD) wn = at(Wq, 4u * (unsigned)i16);
+            } else {
+                const bool ok = i16 < nlast;
+#pragma unroll
+                for (int t = 0; t < C::KS0; ++t) xn[t] = (ok && 4 * t + g < d_in) ? at(Xq, xb[t]) : 0.f;
+#pragma unroll
+                for (int o = 0; o < d_out; ++o) yn[o] = ok ? at(Yq, yb[o]) : 0.f;
+                if constexpr (S::WTD) wn = ok ? at(Wq, 4u * (unsigned)i16) : 0.f;
+            }
+        }
         // (the last layer's fringe sums -- a dozen packed FMAs -- wait until the N-fringe operands of layer L-1 are on their way: NCF)
         if constexpr (!C::NCF(L > 0 ? L - 1 : 0)) FringeDW<S, L>::run(FP, T, dzf, g);
         // delta of layer L-1, then the pipeline
@@ -1628,6 +1707,14 @@ __global__ __launch_bounds__(FAST_THREADS, 1) __attribute__((amdgpu_waves_per_eu
             }
         }
         if (first) { TB_STAMP(2); TSTAMPO(59); first = false; }
+        // the next tile's rows are taken over HERE, at the back edge: with no copy left to read them, their first reader would be the
+        // loop's first instruction, and the compiler's wait for them would stand in front of the FIRST tile as well -- a wait for the
+        // W^T transfer and the cooperative tiles' rows, in flight since the prologue
+#pragma unroll
+        for (int t = 0; t < C::KS0; ++t) asm volatile("" : "+v"(xn[t]));
+#pragma unroll
+        for (int o = 0; o < d_out; ++o) asm volatile("" : "+v"(yn[o]));
+        if constexpr (S::WTD) asm volatile("" : "+v"(wn));
     }
     TB_STAMP(3); TSTAMPO(60);
     mfma_drain_acc(dW);
