@@ -424,6 +424,45 @@ int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64
 int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                              const float* net_w, int which, const float* X, const float* Y, int64_t n, const double* probs,
                              int32_t n_probs, double* q_out, double* cdf_out, double* cdf_below_out);
+/* The continuous ranked probability score (CRPS) of the predictive mixture at the targets: a proper score in the units of the target that
+ * rewards calibration and sharpness together, from the closed form for a mixture of Gaussians (Grimit, Gneiting, Berrocal, Johnson 2006) --
+ * no quadrature.  Arguments up to `n` as tbnn_ensemble_predictive's (likelihood, sd, net_w, rows, targets).
+ * An element is an (output, row) pair.  Under TBNN_LIK_HETERO_GAUSSIAN an element is a row, giving one result plane (od = 1; else
+ * od = d_out), as in tbnn_ensemble_predictive.
+ *   Network weights are w_i (NULL: all 1), with W = sum_i w_i and omega_i = w_i / W (one rounded fp64 quotient per network, from the host).
+ *   Network i predicts f_i, formed in fp32 and widened to fp64.
+ *   The scale s_i is sd[i], or fixed_sd when sd is NULL, clipped to [1e-8, 1e8] in fp32 as tbnn_ensemble_loglik clips it.
+ *   Under the heteroscedastic kind, s_i = exp(gc_i) per (network, row), gc_i the log-sd output clipped to +-log(1e8).
+ *   The target is y.
+ * The pair term is
+ *   A(mu, sigma) = E|N(mu, sigma^2)| = sigma [2 phi(mu / sigma) + (mu / sigma) erf(mu / (sigma sqrt 2))].
+ * Both terms of A are >= 0, so nothing cancels inside it.  The three outputs are
+ *   error  = sum_i omega_i A(y - f_i, s_i)                                          = E|Y - y|
+ *   spread = 1/2 sum_i sum_j omega_i omega_j A(f_i - f_j, sqrt(s_i^2 + s_j^2))      = 1/2 E|Y - Y'|, the diagonal included, where
+ *            A(0, s_i sqrt 2) = 2 s_i / sqrt pi
+ *   crps   = error - spread.
+ * noise = 0 selects the ensemble CRPS of the networks' outputs alone, the limit s -> 0, where A(mu, 0) = |mu|.  In that mode sd is not
+ * read and the heteroscedastic kind reads its mean plane only.  noise = 1: the predictive mixture above.
+ * Everything is fp64 and not contracted.  The order of every sum is fixed: the networks are cut into tiles of 8, network i belongs to lane
+ * g = i mod 8 of its element's eight; a lane adds its error terms in ascending i, and its pair terms (omega_i omega_j) A_ij for j <= i
+ * (the term j = i at half weight, which with the symmetry of A gives the double sum above) over its networks i ascending, for each i the
+ * tiles of j ascending and j ascending within a tile; the eight lanes' sums are then added in lane order.  Every one of these sums is
+ * compensated (Kahan).  Networks of weight 0 are left out of every sum.  The result is the same bits from run to run, whatever the grid and
+ * whatever the row blocks.
+ * NaN: a NaN target makes the element NaN.  Gaussian kinds: a NaN f_i under any network, whatever its weight, makes the element NaN.
+ * Heteroscedastic kind: a NaN f_i or (noise = 1) g_i of a network that counts makes the element NaN; a network of weight 0 is not looked
+ * at.  An infinite f_i among the networks that count makes the element NaN.  All three outputs of such an element are NaN.
+ * crps_out, error_out, spread_out: host [od][n] doubles each, or NULL; at least one of the three.  The rows are cut into blocks as for
+ * tbnn_ensemble_quantiles (a block's 3 od rb results are held beside it).  The work is m (m + 1) / 2 pair terms per element, an erf and an
+ * exp each.
+ * Refused, with nothing written: every output NULL, X without Y, noise not 0 or 1, TBNN_LIK_BERNOULLI / TBNN_LIK_CATEGORICAL (a label:
+ * tbnn_ensemble_uncertainty), TBNN_LIK_POISSON / TBNN_LIK_NEG_BINOMIAL (the pair term of two count distributions has no closed form: not
+ * built), TBNN_LIK_STUDENT_T (no closed form either, and its predictive distribution is not built), any other likelihood code,
+ * TBNN_LIK_HETERO_GAUSSIAN with d_out != 2, m > 4096 (a launch is quadratic in m: a limit of the interface), n not matching the staged
+ * rows, a NaN sd (noise = 1), weights breaking the rules above, m d_out 64 > 2^28. */
+int tbnn_ensemble_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                       const float* net_w, int which, const float* X, const float* Y, int64_t n, int noise,
+                       double* crps_out, double* error_out, double* spread_out);
 /* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
  * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
  * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).

@@ -122,6 +122,7 @@ SYMBOLS = [
     ("tbnn_ensemble_uncertainty", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, C.c_int64, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_ensemble_predictive", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp,
                                            _dp]),
+    ("tbnn_ensemble_crps", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_int, _dp, _dp, _dp]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
@@ -630,6 +631,21 @@ class Chain:
         _check(lib.tbnn_ensemble_predictive(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
                                             _pd(pr), 0 if pr is None else pr.size, _pd(q), _pd(F), _pd(Fb)))
         return q, F, Fb
+
+    def ensemble_crps(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, weights=None, noise: bool = True):
+        """continuous ranked probability score of the predictive mixture at the targets, from its closed form over all pairs of networks on
+        the device (tbnn_ensemble_crps; the definition is in include/tbnn.h): a dict of float64 arrays [d_out, rows] -- crps = error - spread,
+        error = E|Y - y| and spread = 1/2 E|Y - Y'| under the mixture over the networks of N(f_i, s_i^2).  likelihood: LIK_GAUSSIAN /
+        LIK_FIXED_GAUSSIAN (None: the chain's own); sd: one per network (None: the chain's fixed_sd); under LIK_HETERO_GAUSSIAN (a 2-output
+        chain) s_i = exp(g_i) per row, sd is not read and the arrays are [1, rows].  noise=False: the CRPS of the networks' outputs alone
+        (s -> 0), sd is not read.  weights: one per network or None (equal); Y None with X None: the staged targets.  At most 4096 networks"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        yp, sdp, lik = self._ensemble_targets(th.shape[0], xp, n, Y, sd, likelihood)
+        od = 1 if lik == LIK_HETERO_GAUSSIAN else self.d_out          # (its two outputs describe ONE distribution per row)
+        out = {k: np.empty((od, n), dtype=np.float64) for k in ("crps", "error", "spread")}
+        _check(lib.tbnn_ensemble_crps(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
+                                      1 if noise else 0, *[_pd(out[k]) for k in ("crps", "error", "spread")]))
+        return out
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,
                      psis: bool = True):

@@ -665,6 +665,83 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
         });
 }
 
+// what tbnn_ensemble_crps refuses before it touches a device, and the per-network constants it stages: cst[2][m] = w_i / W and, Gaussian
+// kinds with noise, s_i (with noise = 0 sd is not read)
+static int crps_check(const std::string& who, int likelihood, float fixed_sd, int d_out, const float* sd, const float* net_w, int32_t m, const float* X,
+                      const float* Y, int noise, const double* crps_out, const double* error_out, const double* spread_out, std::vector<double>& cst) {
+    if (!crps_out && !error_out && !spread_out) return fail(-1, who + ": every output is null");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (noise != 0 && noise != 1) return fail(-1, who + ": noise must be 0 (the networks' outputs alone) or 1 (with the observation noise)");
+    if (likelihood == TBNN_LIK_BERNOULLI || likelihood == TBNN_LIK_CATEGORICAL)
+        return fail(-1, who + ": the CRPS is a score of a real-valued prediction; a label's uncertainty and calibration: tbnn_ensemble_uncertainty");
+    if (likelihood == TBNN_LIK_POISSON || likelihood == TBNN_LIK_NEG_BINOMIAL)
+        return fail(-1, who + ": the CRPS of a count distribution is not built (the pair term E|Y_i - Y_j| of two count distributions has no closed "
+                              "form: a sum of (F(k) - 1{y <= k})^2 over the support, another kernel)");
+    if (likelihood == TBNN_LIK_STUDENT_T)
+        return fail(-1, who + ": the CRPS under TBNN_LIK_STUDENT_T is not built (the pair term of two t distributions has no closed form, and the "
+                              "Student-t predictive distribution is not built either)");
+    const bool gauss = ens_gaussian(likelihood), het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
+    if (!gauss && !het) return fail(-1, who + ": unknown likelihood");
+    if (het && d_out != 2) return fail(-1, who + ": the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (m > ENS_CRPS_MAX_M)
+        return fail(-1, who + ": m = " + std::to_string(m) + " exceeds " + std::to_string(ENS_CRPS_MAX_M) + " networks (the work is quadratic in m)");
+    ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    std::vector<float> sig;
+    const bool scales = gauss && noise;
+    if (scales) ENS_TRY(ens_sigmas(who, sd, fixed_sd, m, sig));
+    cst.assign(2 * (size_t)m, 0.0);
+    for (int32_t i = 0; i < m; ++i) {
+        cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
+        if (scales) cst[(size_t)m + i] = (double)sig[i];
+    }
+    return 0;
+}
+
+// The CRPS of the predictive mixture: every (output, row) needs all m networks at once, so the rows are cut (ensemble_row_blocks); a block's
+// three result planes are held beside it.
+extern "C" int tbnn_ensemble_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
+                                  const float* net_w, int which, const float* X, const float* Y, int64_t n, int noise, double* crps_out,
+                                  double* error_out, double* spread_out) {
+    NEED(h);
+    const std::string who = "ensemble_crps";
+    const int d_out = h->nd.d_out;
+    std::vector<double> cst;
+    ENS_TRY(crps_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, noise, crps_out, error_out, spread_out, cst));
+    const bool het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
+    const int od = het ? 1 : d_out;                          // (its two outputs describe ONE distribution per row)
+    ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
+    const float* dYrows = nullptr;
+    Buf<float> dY;
+    Buf<double> dCst, dRes;
+    long rbk = 0;
+    return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
+        [&](long rb) -> int {
+            rbk = rb * od;
+            HIPCHK(dRes.alloc(3 * (size_t)rbk));
+            ENS_TRY(ens_upload(h, dCst, cst.data(), cst.size()));
+            return ens_stage_targets(h, which, Y, n, dY, &dYrows);
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            const long tot = r * od;                       // elements: (output, row) pairs; heteroscedastic Gaussian: rows
+            const dim3 grid((unsigned)std::min<long>((tot + ENS_CE - 1) / ENS_CE, 65536)), tb(ENS_TB);
+            const float* y = dYrows + (size_t)r0 * d_out;
+            const double* c = dCst;
+            double* res = dRes;
+            if (het && noise) hipLaunchKernelGGL((k_ens_crps<TBNN_LIK_HETERO_GAUSSIAN, true>), grid, tb, 0, h->stream, t, (int)m, tot, r, d_out, y, c, res, rbk);
+            else if (het) hipLaunchKernelGGL((k_ens_crps<TBNN_LIK_HETERO_GAUSSIAN, false>), grid, tb, 0, h->stream, t, (int)m, tot, r, d_out, y, c, res, rbk);
+            else if (noise) hipLaunchKernelGGL((k_ens_crps<TBNN_LIK_GAUSSIAN, true>), grid, tb, 0, h->stream, t, (int)m, tot, r, d_out, y, c, res, rbk);
+            else hipLaunchKernelGGL((k_ens_crps<TBNN_LIK_GAUSSIAN, false>), grid, tb, 0, h->stream, t, (int)m, tot, r, d_out, y, c, res, rbk);
+            HIPCHK(hipGetLastError());
+            double* const outs[3] = {crps_out, error_out, spread_out};
+            for (int k = 0; k < 3; ++k)
+                if (outs[k]) ENS_TRY(ens_copy_planes(h, outs[k], r0, rows, res + (size_t)k * rbk, r, (size_t)od));
+            return 0;
+        });
+}
+
 // M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)
 static void psis_sizes(int32_t m, double r_eff, int* M, int* G, int* q) {
     *M = (int)std::ceil(std::min(0.2 * (double)m, 3.0 * std::sqrt((double)m / r_eff)));

@@ -37,6 +37,10 @@
 //             k_ens_loglik) with the rows' lppd and p_waic; k_ens_psis smooths each row's importance ratios (definition: include/tbnn.h,
 //             tbnn_ensemble_loo): the cutoff by bisection on the order-preserving 64-bit key, the tail gathered into a scratch [M][rb] and
 //             ranked there by counting, the generalised Pareto fit in one sweep over the G candidates.  All fp64, contraction off.
+//   crps        the same block, untransformed: k_ens_crps forms the continuous ranked probability score of the predictive mixture (definition:
+//             include/tbnn.h, tbnn_ensemble_crps) from its closed form, a sum over all PAIRS of networks.  The one kernel here that is not
+//             one thread per element: ENS_CL lanes share an element, each holds one network of a tile in registers and walks the other
+//             tile's networks from LDS (layout and summation order: at the kernel).  All fp64, contraction off, no atomics.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -53,6 +57,10 @@
 #define ENS_PRED_PASSES 256   // trial points per probability at the most (Gaussian: the moves at least halve, a bisection at the worst; Poisson: <= 2 log2 of the count)
 #define ENS_POIS_MAX_RATE 1073741824.0   // 2^30: a larger (or non-finite) rate makes the element NaN
 #define ENS_NB_MAX 1048576.0             // 2^20: the negative binomial's ceiling on the rate AND on the count k; beyond either the element is NaN
+#define ENS_CT 8        // networks per tile of the pair kernel (k_ens_crps): one per lane of an element
+#define ENS_CE 32       // elements a workgroup of the pair kernel owns
+#define ENS_CL (ENS_TB / ENS_CE)   // lanes that share an element there: one network of a tile each, so ENS_CL == ENS_CT
+#define ENS_CRPS_MAX_M 4096   // networks of tbnn_ensemble_crps at the most: a launch is quadratic in m (a limit of the interface)
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
 __device__ __forceinline__ float ens_xform(float f, int xform) {
@@ -1188,5 +1196,142 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_psis(const double* __restrict__ 
             ens_lse_step(lw, M2, S2);
         }
         elpd[row] = (M1 + log(S1)) - (M2 + log(S2));
+    }
+}
+
+// ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
+// compensated (Kahan) accumulation: s + the running sum of what the additions lost; the sums below are of terms >= 0
+__device__ __forceinline__ void ens_kahan(double a, double& s, double& c) {
+#pragma clang fp contract(off)
+    const double y = a - c;
+    const double t = s + y;
+    c = (t - s) - y;
+    s = t;
+}
+
+// A(mu, sigma) = E|N(mu, sigma^2)| = sigma [2 phi(z) + z erf(z / sqrt 2)], z = |mu| / sigma, sigma > 0: both terms >= 0
+__device__ __forceinline__ double ens_abs_normal(double mu, double sigma) {
+#pragma clang fp contract(off)
+    const double z = fabs(mu) / sigma;
+    return sigma * (0.79788456080286535588 * exp(-0.5 * (z * z)) + z * erf(z * 0.70710678118654752440));
+}
+
+// t: the block [m][tot] of untransformed predictions (TBNN_LIK_HETERO_GAUSSIAN: [m][2][tot], tot = r, as k_ens_pred_cdf reads it); Y: the
+// block's targets [r][d_out]; cst[2][m]: w_i / W and, Gaussian kinds with NOISE, s_i.  res[3][rbk]: crps, error, spread of the block's
+// tot elements.  NOISE false: A(mu, 0) = |mu|, no scale is read (heteroscedastic kind: the mean plane alone).
+//
+// Layout.  A workgroup owns ENS_CE = 32 consecutive elements at a time, thread tid the element el = tid % 32 as lane g = tid / 32 of its
+// ENS_CL = 8.  The networks are cut into tiles of ENS_CT = 8.  For tile I, lane g keeps network i = 8 I + g of its element in REGISTERS
+// (f_i, s_i, w_i / W) and adds the element's error term of that network; then the tiles J = 0 .. I pass through LDS one after the other,
+// [8][32] doubles of f_j (heteroscedastic kind: and of s_j = exp(gc_j)), every thread staging the one value (network 8 J + g, element el)
+// -- its 32 neighbours read 128 contiguous bytes -- so a prediction comes from memory once per tile pass and is read eight times from LDS.
+// The tile is double-buffered: the value of tile J + 1 is loaded before tile J is walked and written after, one barrier per tile pair.
+// A wave reads f_j of ONE j for its 32 elements: 32 consecutive doubles, one bank row, the two half-waves (two values of g) the same
+// addresses -- no bank conflict.  Lane g walks j = 8 J .. 8 J + 7 (J < I), j = 8 I .. i on the diagonal tile (NOISE false: .. i - 1, the
+// diagonal term is 0), skipping networks of weight 0, which are never looked at in the pair walk.  w_j / W and the Gaussian kinds' s_j
+// are read from cst at an index the whole wave shares.
+// Sums, all compensated (ens_kahan), in this order: a lane's error sum over its networks i = g, g + 8, ... ascending; a lane's spread sum
+// over I ascending, J ascending, j ascending, of (w_i / W)(w_j / W) A(f_i - f_j, sqrt(s_i^2 + s_j^2)), the diagonal term (j = i) at half
+// weight; then, through LDS, the element's eight lanes g = 0 .. 7 in order.  crps = error - spread.  Nothing depends on the element's
+// place in its workgroup, the grid or the block: the same bits from run to run and whatever the row blocks.
+// NaN (all three results): a NaN target; Gaussian kinds: a NaN f_i under any network; heteroscedastic kind: a NaN f_i or (NOISE) g_i of a
+// network that counts; an infinite f_i of a network that counts.
+template <int LIK, bool NOISE>
+__global__ __launch_bounds__(ENS_TB) void k_ens_crps(const float* __restrict__ t, int m, long tot, long r, int d_out, const float* __restrict__ Y,
+                                                      const double* __restrict__ cst, double* __restrict__ res, long rbk) {
+#pragma clang fp contract(off)
+    static_assert(ENS_CL == ENS_CT && ENS_CT * ENS_CE == ENS_TB, "one staged value per thread and tile, one network of a tile per lane");
+    constexpr bool HET = LIK == TBNN_LIK_HETERO_GAUSSIAN;
+    __shared__ double fJ[2][ENS_CT][ENS_CE];
+    __shared__ double sJ[HET && NOISE ? 2 : 1][ENS_CT][ENS_CE];
+    __shared__ double red[2][ENS_CL][ENS_CE];
+    __shared__ int redbad[ENS_CL][ENS_CE];
+    const int el = threadIdx.x % ENS_CE, g = threadIdx.x / ENS_CE;
+    const long ns = HET ? 2 * tot : tot;                  // floats between two networks' predictions of an element
+    const int nt = (m + ENS_CT - 1) / ENS_CT;
+    int b = 0;
+    for (long e0 = (long)blockIdx.x * ENS_CE; e0 < tot; e0 += (long)gridDim.x * ENS_CE) {
+        const long e = e0 + el;
+        const bool live = e < tot;
+        const float yf = live ? Y[(size_t)(e % r) * d_out + e / r] : 0.f;
+        const double y = (double)yf;
+        int bad = yf != yf;
+        double es = 0.0, ec = 0.0, ss = 0.0, sc = 0.0;
+        for (int I = 0; I < nt; ++I) {
+            // this lane's network of tile I; it is also the value this thread stages when J reaches I
+            const int i = I * ENS_CT + g;
+            const bool have = live && i < m;
+            const double wi = have ? cst[i] : 0.0;
+            double fi = 0.0, si = 1.0;
+            if (have) {
+                const float fv = t[(size_t)i * ns + e];
+                fi = (double)fv;
+                if (!HET) bad += fv != fv;
+                if (NOISE && !HET) si = cst[(size_t)m + i];
+                if (wi > 0.0) {
+                    if (HET && NOISE) {
+                        const float gv = t[(size_t)i * ns + tot + e];
+                        si = exp(ens_het_gc(gv));
+                        bad += gv != gv;
+                    }
+                    bad += (fv != fv) + (fabsf(fv) == INFINITY);
+                    ens_kahan(wi * (NOISE ? ens_abs_normal(y - fi, si) : fabs(y - fi)), es, ec);
+                }
+            }
+            // the staged value of tile J = 0: network g
+            double pf = 0.0, ps = 1.0;
+            if (live && g < m) {
+                pf = (double)t[(size_t)g * ns + e];
+                if (HET && NOISE) ps = exp(ens_het_gc(t[(size_t)g * ns + tot + e]));
+            }
+            for (int J = 0; J <= I; ++J) {
+                fJ[b][g][el] = pf;
+                if (HET && NOISE) sJ[b][g][el] = ps;
+                __syncthreads();
+                const int jn = J + 1 <= I ? (J + 1) * ENS_CT + g : m;         // the next tile's network of this thread, loaded under the walk
+                float nf = 0.f, ng = 0.f;
+                if (live && jn < m) {
+                    nf = t[(size_t)jn * ns + e];
+                    if (HET && NOISE) ng = t[(size_t)jn * ns + tot + e];
+                }
+                if (have && wi > 0.0) {
+                    const int j0 = J * ENS_CT;
+                    const int last = J < I ? min(ENS_CT, m - j0) - 1 : (NOISE ? g : g - 1);
+                    const double vi = si * si;
+                    for (int jl = 0; jl <= last; ++jl) {
+                        const double wj = cst[j0 + jl];
+                        if (!(wj > 0.0)) continue;
+                        const double mu = fi - fJ[b][jl][el];
+                        double a;
+                        if (NOISE) {
+                            const double sj = HET ? sJ[b][jl][el] : cst[(size_t)m + j0 + jl];
+                            a = ens_abs_normal(mu, sqrt(vi + sj * sj));
+                        } else {
+                            a = fabs(mu);
+                        }
+                        const double wij = wi * wj;
+                        ens_kahan((J == I && jl == g ? 0.5 * wij : wij) * a, ss, sc);
+                    }
+                }
+                pf = (double)nf;
+                if (HET && NOISE) ps = exp(ens_het_gc(ng));
+                b ^= 1;
+            }
+        }
+        red[0][g][el] = es; red[1][g][el] = ss; redbad[g][el] = bad;
+        __syncthreads();
+        if (g == 0 && live) {
+            double E = 0.0, Ec = 0.0, S = 0.0, Sc = 0.0;
+            int anybad = 0;
+#pragma unroll
+            for (int l = 0; l < ENS_CL; ++l) {
+                ens_kahan(red[0][l][el], E, Ec);
+                ens_kahan(red[1][l][el], S, Sc);
+                anybad += redbad[l][el];
+            }
+            res[e] = anybad ? (double)NAN : E - S;
+            res[rbk + e] = anybad ? (double)NAN : E;
+            res[2 * rbk + e] = anybad ? (double)NAN : S;
+        }
     }
 }

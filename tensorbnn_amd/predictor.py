@@ -455,6 +455,77 @@ class predictor(object):
                                            likelihood=lik.kind, sd=self._network_sd(lik, n), weights=w)
         return (Fb, F) if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) else F
 
+    # ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
+    def _crps_likelihood(self, likelihood):
+        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, NegativeBinomialLikelihood, PoissonLikelihood,
+                                 StudentTLikelihood)
+        lik = self.likelihood if likelihood is None else likelihood
+        if isinstance(lik, (BernoulliLikelihood, CategoricalLikelihood)):
+            raise ValueError("the CRPS is a score of a real-valued prediction: predictUncertainty and calibration judge a label")
+        if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)):
+            raise ValueError("the CRPS is not built for a PoissonLikelihood or NegativeBinomialLikelihood (the pair term of two count "
+                             "distributions has no closed form); logPredictiveDensity, loo, waic and predictiveCDF are")
+        if isinstance(lik, StudentTLikelihood):
+            raise ValueError("the CRPS is not built for a StudentTLikelihood (the pair term of two t distributions has no closed form); "
+                             "logPredictiveDensity, loo and waic are")
+        return lik
+
+    def crps(self, inputMatrix, realVals, n=1, weights=None, likelihood=None, noise=True):
+        """The continuous ranked probability score of the rows: a proper score in the units of the target that rewards calibration and
+        sharpness together, bounded where the log score is not.  The predictive distribution is predictiveQuantiles' -- the mixture over
+        every n-th network of N(f_i, s_i^2), s_i the network's own standard deviation (its saved last hyper as logPredictiveDensity reads
+        it, or the fixed sd; exp of the log-sd output under a HeteroscedasticGaussianLikelihood) -- and the score its closed form over
+        all pairs of networks, on the device (the definition is in include/tbnn.h).  Targets in the networks' own (normalised) units, as
+        predictiveCDF's.  noise=False: the ensemble CRPS of the networks' outputs alone.  Returns a dict: crps, error = E|Y - y| and
+        spread = 1/2 E|Y - Y'| (crps = error - spread), float64 [d_out, rows]; mean_crps [d_out], the mean over the rows that are not
+        NaN; se [d_out] = sqrt(var(rows, ddof=1) / rows) over the same rows; n_bad, the number of NaN elements.  compareCrps compares
+        two results over the same rows.  weights: one per picked network, e.g. what reweight returns."""
+        lik = self._crps_likelihood(likelihood)
+        picked, w = self._picked(n, weights)
+        ch = self._ensure_chain()
+        res = ch.ensemble_crps(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
+                               likelihood=lik.kind, sd=self._network_sd(lik, n) if noise else None, weights=w, noise=bool(noise))
+        res.update(self._crps_summary(res["crps"]))
+        return res
+
+    @staticmethod
+    def _crps_summary(rows):
+        """mean_crps and se per output over the rows that are not NaN, and the count of NaN elements"""
+        rows = np.asarray(rows, dtype=np.float64)
+        ok = ~np.isnan(rows)
+        mean, se = np.full(rows.shape[0], np.nan), np.full(rows.shape[0], np.nan)
+        for k in range(rows.shape[0]):
+            v = rows[k][ok[k]]
+            if v.size:
+                mean[k] = v.mean()
+            if v.size > 1:
+                se[k] = np.sqrt(np.var(v, ddof=1) / v.size)
+        return {"mean_crps": mean, "se": se, "n_bad": int((~ok).sum())}
+
+    @staticmethod
+    def compareCrps(a, b):
+        """Two results of crps over the SAME rows, possibly of two predictors: crps_diff, the mean over the rows of crps(a) - crps(b)
+        (negative: a is better), and se_diff = sqrt(var(a_rows - b_rows, ddof=1) / rows), the paired standard error; each per output.
+        Rows that are NaN in either result are left out.  Host only."""
+        def rows(r):
+            if not isinstance(r, dict) or "crps" not in r:
+                raise ValueError("compareCrps takes the dicts crps returns")
+            v = np.asarray(r["crps"], dtype=np.float64)
+            return v.reshape(1, -1) if v.ndim < 2 else v
+        ra, rb = rows(a), rows(b)
+        if ra.shape != rb.shape:
+            raise ValueError(f"the results cover {ra.shape[-1]} and {rb.shape[-1]} rows of {ra.shape[0]} and {rb.shape[0]} outputs: a "
+                             "comparison needs the same rows")
+        d = ra - rb
+        diff, se = np.full(d.shape[0], np.nan), np.full(d.shape[0], np.nan)
+        for k in range(d.shape[0]):
+            v = d[k][~np.isnan(d[k])]
+            if v.size:
+                diff[k] = v.mean()
+            if v.size > 1:
+                se[k] = np.sqrt(np.var(v, ddof=1) / v.size)
+        return {"crps_diff": diff, "se_diff": se}
+
     # ---- classification: entropy split, votes (tbnn_ensemble_uncertainty) and calibration of the posterior-mean classifier ----
     def _label_likelihood(self, likelihood):
         from .likelihood import BernoulliLikelihood, CategoricalLikelihood
