@@ -242,6 +242,10 @@ int tbnn_debug_draw(tbnn_handle h, uint32_t epoch, uint32_t purpose, int32_t n, 
  * closing half kick, kept whether or not the proposal was accepted).  With it a test can run the integrator backwards: from q_L
  * with p0 = -p_L the same L steps must return to q_0 (tfp's leapfrog is time-reversible; call sites network.py:394-408). */
 int tbnn_debug_momentum(tbnn_handle h, float* p_out);
+/* diagnostic (tests/test_gpu_many_tiles.py): how many statistic partials a fused pass of the staged rows writes and tbnn_logp_grad sums --
+ * on the one-kernel families the workgroups of the launch (with the test hook TBNN_FAST_GRID: the small grid); 0 before tbnn_set_data.
+ * Read only. */
+int tbnn_debug_stat_partials(tbnn_handle h);
 /* epoch counter that keys the RNG (incremented by every tbnn_hmc_step) */
 int tbnn_set_epoch(tbnn_handle h, uint32_t epoch);
 /* record a hipEvent pair around every stride-th fused fwd+bwd launch on the

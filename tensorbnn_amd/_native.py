@@ -110,6 +110,7 @@ SYMBOLS = [
     ("tbnn_debug_stamps", C.c_int, [_H, C.POINTER(C.c_uint64)]),
     ("tbnn_debug_fused_burst", C.c_int, [_H, C.c_int32, C.POINTER(C.c_float)]),
     ("tbnn_debug_momentum", C.c_int, [_H, _fp]),
+    ("tbnn_debug_stat_partials", C.c_int, [_H]),
     ("tbnn_set_validation", C.c_int, [_H, _fp, _fp, C.c_int64]),
     ("tbnn_predict", C.c_int, [_H, C.c_int, _fp, _fp]),
     ("tbnn_forward_many", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int64, _fp]),
@@ -343,6 +344,11 @@ class Chain:
     def last_transition_path(self) -> str:
         """"per-step" | "trajectory": the kernels that ran the last transition's leapfrog steps"""
         return lib.tbnn_last_transition_path(self._h).decode()
+
+    @property
+    def stat_partials(self) -> int:
+        """how many statistic partials a fused pass of the staged rows writes: the workgroups of a one-kernel family's launch (tests)"""
+        return _check(lib.tbnn_debug_stat_partials(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -736,6 +742,11 @@ class ChainGroup:
     def last_transition_path(self) -> str:
         """"per-step" | "trajectory": the kernels that ran the last transition's leapfrog steps"""
         return lib.tbnn_last_transition_path(self._h).decode()
+
+    @property
+    def stat_partials(self) -> int:
+        """how many statistic partials a fused pass writes per chain (Chain.stat_partials)"""
+        return _check(lib.tbnn_debug_stat_partials(self._h))
 
     def close(self):
         if getattr(self, "_h", None):

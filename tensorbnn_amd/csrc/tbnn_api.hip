@@ -418,6 +418,7 @@ extern "C" int tbnn_param_count(tbnn_handle h) { NEED(h); return h->nd.P; }
 extern "C" int tbnn_hyper_count(tbnn_handle h) { NEED(h); return h->nd.H; }
 extern "C" const char* tbnn_kernel_name(tbnn_handle h) { return h && h->be ? h->be->name() : ""; }
 extern "C" const char* tbnn_last_transition_path(tbnn_handle h) { return h ? h->last_path : ""; }
+extern "C" int tbnn_debug_stat_partials(tbnn_handle h) { NEED(h); return h->grid; }
 extern "C" int tbnn_set_profiling(tbnn_handle h, int stride) {
     NEED(h);
     h->profile = stride > 0 ? stride : 0;
