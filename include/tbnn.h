@@ -81,10 +81,21 @@ enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
  * deltas.  The kernels accumulate sum_i w_i (-gc - 1/2 r^2 u); the constant -1/2 log(2 pi) W, W the rows that normalise the Gaussian kinds
  * (their count, the sum of the row weights, n_total of a row-sharded chain), is added in fp64 where the log-probability is formed, and stat
  * of tbnn_logp_grad is the data term INCLUDING it, as under Poisson.  Targets stay [n][d_out] = [n][2] at this interface: column 0 is y,
- * column 1 is NOT READ.  A non-finite statistic rejects the proposal.  tbnn_metrics compares output 0 with target column 0 only.  Codes 4,
- * 6, 7, 9, 11 and every other value are not assigned. */
+ * column 1 is NOT READ.  A non-finite statistic rejects the proposal.  tbnn_metrics compares output 0 with target column 0 only;
+ * GAMMA: positive, continuous, right-skewed targets (durations, amounts, concentrations), any d_out >= 1 independent outputs, no
+ * activation after the last layer: its output f is the LOG of the mean, mu = exp(f).  The shape a = the descriptor's lik_df, finite and
+ * > 0 (tbnn_create, tbnn_create_multi and tbnn_fused_kernel_available refuse any other lik_df); variance mu^2 / a, a constant coefficient
+ * of variation 1 / sqrt(a); a = 1 is the exponential distribution.  fixed_sd is not read.  No likelihood hyper (H = 4 n_layers).  Targets
+ * are finite and strictly > 0: staging refuses anything else, zero too (log y enters the constant).  Per (row, output):
+ * log p(y | f) = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f),  dL/df = a (y exp(-f) - 1).  The kernels accumulate
+ * stat = sum_i w_i (f + y e^-f) with one hardware exp per element and return the delta w a (y e^-f - 1); the constant
+ * C = sum_i w_i sum_k (lgamma(a) - a log a - (a - 1) log y_ik) is computed with the data (or row weights), in fp64 and bit for bit the same
+ * from run to run, and the log-probability is formed as -a stat - C -- Poisson's rules for tbnn_set_data_device, validation data and row
+ * shards hold, and stat of tbnn_logp_grad is the data term -a stat - C itself.  A log-mean below the fp32 range of exp(-f) gives a
+ * non-finite statistic: the proposal is rejected and the chain keeps its state (Poisson's rule, on the other side).  Codes 4, 6, 7, 9,
+ * 11, 13 and every other value are not assigned. */
 enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5,
-       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10, TBNN_LIK_HETERO_GAUSSIAN = 12 };
+       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10, TBNN_LIK_HETERO_GAUSSIAN = 12, TBNN_LIK_GAMMA = 14 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or
@@ -104,7 +115,7 @@ typedef struct tbnn_net_desc {
     int32_t likelihood;  /* TBNN_LIK_* */
     float fixed_sd;      /* FixedGaussianLikelihood(sd=) likelihood.py:138-141; the scale s of TBNN_LIK_STUDENT_T */
     int32_t kernel;      /* TBNN_KERNEL_* */
-    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; ignored under every other likelihood (this was `int32_t reserved`:
+    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; TBNN_LIK_GAMMA: the shape a; ignored under every other likelihood (this was `int32_t reserved`:
                           * the same size and offset, and the all-zero bits callers passed there are 0.0) */
 } tbnn_net_desc;
 
@@ -294,7 +305,8 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
  * tbnn_ensemble_moments with TBNN_XFORM_EXP); Student-t: the density of TBNN_LIK_STUDENT_T per output in fp64, its scale s_i = sd[i] or
  * NULL = fixed_sd, clipped as the Gaussian kinds', its nu the handle's lik_df -- the descriptor's on a Student-t handle, what
  * tbnn_set_lik_df set on any other (0, never set: refused); negative binomial: the density of TBNN_LIK_NEG_BINOMIAL per output in fp64 in
- * its stable form, its dispersion r the handle's lik_df by the same rule.
+ * its stable form, its dispersion r the handle's lik_df by the same rule; Gamma: the density of TBNN_LIK_GAMMA per output in fp64, its
+ * shape a the handle's lik_df by the same rule.
  *   per_net[i]   = sum over rows and outputs of the terms under network i          (m doubles, or NULL)
  *   lppd_rows[r] = log sum_i w_i p(y_r | theta_i) - log W, p the product over the row's outputs   (n doubles, or NULL)
  * Both are the same bits from run to run. */
@@ -408,13 +420,22 @@ int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64
  *                    k, never more than 10 sqrt(max(r, k + 1)) + 100 double steps; F(k) = 0 for k < 0.  Quantile at p: the smallest integer
  *                    k >= 0 with F(k) >= p, searched as Poisson's from the weighted mean rate, the first step floor(sqrt(mean + mean^2 / r))
  *                    + 1.  The CDF at a target y is taken at floor(y).  Ceilings: 2^20 on the rate exp(f_i) and on k (below).
+ *   TBNN_LIK_GAMMA   a = the handle's shape (the descriptor's lik_df on a Gamma handle, else what tbnn_set_lik_df set; never set: refused).
+ *                    F(y) = (1/W) sum_i w_i P(a, a y exp(-f_i)), P the regularised lower incomplete gamma function in fp64: for x < a + 1 its
+ *                    series, returned as P (a small lower tail is not formed as 1 - (1 - P)), else 1 - Q from the continued fraction or,
+ *                    from a = 2^16 on, Temme's expansion; never more than 10 sqrt(max(a, x)) + 100 terms.  F = 0 for y <= 0.  Quantile at p:
+ *                    the Gaussian scheme on the positive axis -- the bracket [min_i, max_i] of the components' own quantiles
+ *                    exp(f_i) g_p / a (g_p the standard Gamma(a, 1) quantile, staged by the host), widened relatively and VERIFIED with
+ *                    multiplicative pushes until F(lo) < p <= F(hi) as evaluated, then Newton steps on the mixture density safeguarded by
+ *                    the midpoint: the upper end hi of a bracket of at most 2 ulp64(hi) with F(lo) < p <= F(hi), or a point with F == p.
+ *                    cdf_below_out is refused (a continuous CDF has no step).  A network of weight 0 is not looked at, whatever it holds.
  * q_out: host [n_probs][d_out][n] doubles, or NULL (then probs may be NULL too); probs: n_probs probabilities in the OPEN interval (0, 1)
  * (the Gaussian quantile at 0 or 1 is infinite), 1 <= n_probs <= 64.  cdf_out: host [d_out][n] doubles = F(y) at the targets, or NULL; Y is
  * then needed by tbnn_ensemble_loglik's rules (host targets [n, d_out]; NULL with X NULL = the staged targets of `which`; X without Y is
  * refused).  cdf_below_out (TBNN_LIK_POISSON and TBNN_LIK_NEG_BINOMIAL only, with cdf_out; or NULL): [d_out][n] doubles = F(y - 1), the lower end of the target's step
  * (a discrete PIT value lies anywhere in [F(y - 1), F(y)]).  At least one of q_out and cdf_out must be given.
  * NaN: an element with a NaN among its f_i (any weight) gives NaN in every output; so does, among the networks with w_i > 0, a lambda_i
- * that is not finite or exceeds 2^30 (Poisson; negative binomial: 2^20) or, for the quantiles alone, an infinite f_i (Gaussian).  A NaN
+ * that is not finite or exceeds 2^30 (Poisson; negative binomial: 2^20), a Gamma mean exp(f_i) that is 0 or not finite or, for the quantiles alone, an infinite f_i (Gaussian).  A NaN
  * target gives a NaN CDF; under Poisson and the negative binomial so does any target that is not finite, and a negative one gives 0.  Under
  * the negative binomial a target with floor(y) > 2^20 gives a NaN CDF too, no trial of the quantile search goes past k = 2^20, and a
  * probability whose F(2^20) is still below it gives NaN for that probability alone.  Networks of weight 0 add nothing.  The results are the
@@ -502,7 +523,8 @@ int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t the
 /* The degrees of freedom nu that tbnn_ensemble_loglik and tbnn_ensemble_loo use when they judge under TBNN_LIK_STUDENT_T on a handle whose
  * OWN likelihood is another one (a forward handle for saved networks is usually a fixed-sd Gaussian one).  Nothing else reads it.  Refused
  * (-1): a TBNN_LIK_STUDENT_T handle (its nu is the descriptor's lik_df), a df that is not finite and > 0.  The same value is the dispersion r
- * when they judge under TBNN_LIK_NEG_BINOMIAL; a TBNN_LIK_NEG_BINOMIAL handle (its r is the descriptor's lik_df) is refused too. */
+ * when they judge under TBNN_LIK_NEG_BINOMIAL; a TBNN_LIK_NEG_BINOMIAL handle (its r is the descriptor's lik_df) is refused too.  And the
+ * shape a when they -- and tbnn_ensemble_predictive -- judge under TBNN_LIK_GAMMA; a TBNN_LIK_GAMMA handle is refused likewise. */
 int tbnn_set_lik_df(tbnn_handle h, float df);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)

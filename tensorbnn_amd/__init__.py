@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == "HeteroscedasticGaussianLikelihood":
         from .likelihood import HeteroscedasticGaussianLikelihood
         return HeteroscedasticGaussianLikelihood
+    if name == "GammaLikelihood":
+        from .likelihood import GammaLikelihood
+        return GammaLikelihood
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

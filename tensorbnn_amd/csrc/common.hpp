@@ -22,12 +22,16 @@ enum { SHAPE_LIK_NEGBIN = 8 };
 // f and the log-sd g, ONE term per row (kernels_fast.hpp: lik_pair); weighted: SHAPE_LIK_HETERO | SHAPE_LIK_WEIGHTED.  (Not defined on the
 // other codes, nor together with SHAPE_LIK_STUDENT.)
 enum { SHAPE_LIK_HETERO = 16 };
+// the same bit on the Poisson code: the Gamma data term of TBNN_LIK_GAMMA, the log-mean f of the Poisson kind under another loss;
+// weighted: SHAPE_LIK_POIS | SHAPE_LIK_GAMMA | SHAPE_LIK_WEIGHTED.  (Not defined on the other two codes, nor together with SHAPE_LIK_NEGBIN.)
+enum { SHAPE_LIK_GAMMA = 16 };
 // ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
 __host__ __device__ constexpr int shape_lik(int lik) {
     return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS :
            lik == TBNN_LIK_STUDENT_T ? (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS) :
            lik == TBNN_LIK_NEG_BINOMIAL ? (SHAPE_LIK_NEGBIN | SHAPE_LIK_POIS) :
-           lik == TBNN_LIK_HETERO_GAUSSIAN ? (SHAPE_LIK_HETERO | SHAPE_LIK_GAUSS) : SHAPE_LIK_GAUSS;
+           lik == TBNN_LIK_HETERO_GAUSSIAN ? (SHAPE_LIK_HETERO | SHAPE_LIK_GAUSS) :
+           lik == TBNN_LIK_GAMMA ? (SHAPE_LIK_GAMMA | SHAPE_LIK_POIS) : SHAPE_LIK_GAUSS;
 }
 
 #define TBNN_WAVE 64
@@ -51,7 +55,7 @@ struct NetDev {
     int maxW;                     // widest layer (in or out)
     float fixed_sd;
     int reserved_flags;           // bit 0: fast kernel processes one tile at a time (diagnostic)
-    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r (0 otherwise)
+    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; TBNN_LIK_GAMMA: the shape a (0 otherwise)
 };
 
 // Gradient-slab stores of the narrow family: WRITE-THROUGH (global_store ... sc1: a relaxed agent-scope atomic store) when the slabs
@@ -173,6 +177,26 @@ __device__ __forceinline__ float negbin_elem(float fi, float y, double& stat, fl
     const float d = negbin_term(fi, y, r, lr, &term);
     stat += (double)(wt * term);
     return wt * d;
+}
+
+// Gamma with log link (TBNN_LIK_GAMMA, defined in include/tbnn.h), fi the log of the mean.  ONE hardware exp2: e = e^-f, the element's
+// part of the statistic f + y e^-f (its factor -a and the constant: data_logp, kernels_hmc.hpp) and, returned, y e^-f - 1: dL/df over the
+// shape a, which the caller multiplies in.  A log-mean below the fp32 range of e^-f gives inf: the statistic is not finite and k_energy
+// rejects the proposal (Poisson's rule, on the other side); NaN gives NaN.  Not contracted, for the reason given at log1p_fast.  One
+// function for lik_delta's compile-time branch and the kernels that branch at run time.
+__device__ __forceinline__ float gamma_term(float fi, float y, float* term) {
+#pragma clang fp contract(off)
+    const float ye = y * __expf(-fi);
+    *term = fi + ye;
+    return ye - 1.f;
+}
+// ... for the kernels that branch at run time (layered, generic): adds wt term to stat, returns wt dL/df = wt (a (y e^-f - 1))
+__device__ __forceinline__ float gamma_elem(float fi, float y, double& stat, float wt, float a) {
+#pragma clang fp contract(off)
+    float term;
+    const float d = gamma_term(fi, y, &term);
+    stat += (double)(wt * term);
+    return wt * (a * d);
 }
 
 // Heteroscedastic Gaussian (TBNN_LIK_HETERO_GAUSSIAN): one ROW of a 2-output network, f the mean and g the log of the sd.  With

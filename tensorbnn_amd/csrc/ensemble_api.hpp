@@ -61,7 +61,7 @@ static int ens_sigmas(const std::string& who, const float* sd, float fixed_sd, i
 
 // what tbnn_ensemble_loglik and tbnn_ensemble_loo stage per network: *scaled = the likelihood has a scale (the Gaussian kinds, Student-t) -- sig
 // and cst as ens_sigmas forms them; under TBNN_LIK_STUDENT_T *nu = the handle's degrees of freedom (its descriptor's, or what
-// tbnn_set_lik_df set on a handle of another likelihood; under TBNN_LIK_NEG_BINOMIAL the dispersion r, by the same rule) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
+// tbnn_set_lik_df set on a handle of another likelihood; under TBNN_LIK_NEG_BINOMIAL the dispersion r and under TBNN_LIK_GAMMA the shape a, by the same rule) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
 static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, const float* sd, int32_t m, bool* scaled, std::vector<float>& sig,
                           std::vector<double>& cst, double* nu) {
     const bool student = likelihood == TBNN_LIK_STUDENT_T;
@@ -77,6 +77,12 @@ static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, c
         const float r = h->nd.lik == TBNN_LIK_NEG_BINOMIAL ? h->nd.lik_df : h->ens_df;
         if (!df_ok(r)) return fail(-1, who + ": judging under TBNN_LIK_NEG_BINOMIAL needs the dispersion: call tbnn_set_lik_df on this handle first");
         *nu = (double)r;
+    }
+    if (likelihood == TBNN_LIK_GAMMA) {
+        // the shape a travels where nu does: the descriptor's lik_df on a Gamma handle, else what tbnn_set_lik_df set
+        const float a = h->nd.lik == TBNN_LIK_GAMMA ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(a)) return fail(-1, who + ": judging under TBNN_LIK_GAMMA needs the shape: call tbnn_set_lik_df on this handle first");
+        *nu = (double)a;
     }
     if (*scaled) ENS_TRY(ens_sigmas(who, sd, h->nd.fixed_sd, m, sig, &cst));
     if (student) {
@@ -553,11 +559,27 @@ static double ens_norm_ppf(double p) {
     return q < 0.0 ? -v : v;
 }
 
+// the p-quantile of the standard Gamma(a, 1) distribution, for the bracket of k_ens_pred_quantiles alone (the kernel verifies and repairs
+// the bracket, so this is a seed, not a result): outward from a by factors of 4 until P(a, lo) < p <= P(a, hi) by ens_gamma_p compiled for
+// the host, then bisection on the log scale
+static double ens_std_gamma_ppf(double a, double p) {
+    double lo = a, hi = a;
+    for (int k = 0; k < 600 && !(ens_gamma_p(a, lo) < p) && lo > 1e-300; ++k) lo *= 0.25;
+    for (int k = 0; k < 600 && !(ens_gamma_p(a, hi) >= p) && hi < 1e300; ++k) hi *= 4.0;
+    for (int k = 0; k < 200 && hi > lo * (1.0 + 4e-16); ++k) {
+        const double mid = std::sqrt(lo) * std::sqrt(hi);
+        if (!(mid > lo && mid < hi)) break;
+        if (ens_gamma_p(a, mid) >= p) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+
 // what tbnn_ensemble_predictive refuses before it touches a device, and the per-network constants it stages: cst[3][m] = w_i / W,
-// 1 / (s_i sqrt 2), s_i (the last two: Gaussian kinds); pz[2][n_probs] = p, Phi^-1(p); *smax = the largest s_i among the networks that count
+// 1 / (s_i sqrt 2), s_i (the last two: Gaussian kinds); pz[2][n_probs] = p, Phi^-1(p) (TBNN_LIK_GAMMA: p, g_p / shape, g_p the standard
+// Gamma(shape, 1) quantile -- the caller passes the shape, 0 otherwise); *smax = the largest s_i among the networks that count
 static int pred_check(const std::string& who, int likelihood, float fixed_sd, int d_out, const float* sd, const float* net_w, int32_t m, const float* X,
                       const float* Y, const double* probs, int32_t n_probs, const double* q_out, const double* cdf_out, const double* cdf_below_out,
-                      std::vector<double>& cst, std::vector<double>& pz, double* smax) {
+                      std::vector<double>& cst, std::vector<double>& pz, double* smax, double shape) {
     if (!q_out && !cdf_out) return fail(-1, who + ": q_out and cdf_out are both null");
     if (q_out && !probs) return fail(-1, who + ": null probs with q_out");
     if (cdf_below_out && !cdf_out) return fail(-1, who + ": cdf_below_out without cdf_out");
@@ -572,11 +594,12 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
     if (likelihood == TBNN_LIK_STUDENT_T)
         return fail(-1, who + ": the Student-t predictive distribution (a mixture of t CDFs: the incomplete beta function on the device) is not built");
     const bool gauss = ens_gaussian(likelihood), het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
-    if (!gauss && !het && likelihood != TBNN_LIK_POISSON && likelihood != TBNN_LIK_NEG_BINOMIAL) return fail(-1, who + ": unknown likelihood");
+    const bool gam = likelihood == TBNN_LIK_GAMMA;
+    if (!gauss && !het && !gam && likelihood != TBNN_LIK_POISSON && likelihood != TBNN_LIK_NEG_BINOMIAL) return fail(-1, who + ": unknown likelihood");
     // (heteroscedastic Gaussian: every network brings its own s_i(x) = exp(gc_i) in output 1 -- sd is not read, cst keeps w_i / W alone)
     if (het && d_out != 2) return fail(-1, who + ": the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
     // (the wording predates the negative binomial, which takes cdf_below_out too; tests match on it)
-    if (cdf_below_out && (gauss || het)) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
+    if (cdf_below_out && (gauss || het || gam)) return fail(-1, who + ": cdf_below_out is for TBNN_LIK_POISSON (a continuous CDF has no step)");
     if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     // the budget of ensemble_row_blocks, judged here before m values of sd and net_w are read and 3 m doubles staged
     ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
@@ -596,7 +619,10 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
         if (cst[i] > 0.0) *smax = std::max(*smax, sc);
     }
     pz.assign(2 * (size_t)std::max(n_probs, 1), 0.0);
-    for (int32_t j = 0; j < n_probs; ++j) { pz[j] = probs[j]; pz[(size_t)n_probs + j] = ens_norm_ppf(probs[j]); }
+    for (int32_t j = 0; j < n_probs; ++j) {
+        pz[j] = probs[j];
+        pz[(size_t)n_probs + j] = gam ? ens_std_gamma_ppf(shape, probs[j]) / shape : ens_norm_ppf(probs[j]);
+    }
     return 0;
 }
 
@@ -608,13 +634,21 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
     const int d_out = h->nd.d_out;
     std::vector<double> cst, pz;
     double smax = 0.0;
-    ENS_TRY(pred_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, probs, n_probs, q_out, cdf_out, cdf_below_out, cst, pz, &smax));
+    // the shape of the Gamma likelihood: the descriptor's lik_df on such a handle, what tbnn_set_lik_df set on any other
+    const bool gam = likelihood == TBNN_LIK_GAMMA;
+    double shape = 0.0;
+    if (gam) {
+        const float a = h->nd.lik == TBNN_LIK_GAMMA ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(a)) return fail(-1, who + ": the predictive distribution under TBNN_LIK_GAMMA needs the shape: call tbnn_set_lik_df on this handle first");
+        shape = (double)a;
+    }
+    ENS_TRY(pred_check(who, likelihood, h->nd.fixed_sd, d_out, sd, net_w, m, X, Y, probs, n_probs, q_out, cdf_out, cdf_below_out, cst, pz, &smax, shape));
     if (!q_out) n_probs = 0;
     const bool pois = likelihood == TBNN_LIK_POISSON, negb = likelihood == TBNN_LIK_NEG_BINOMIAL, het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
     // result planes per row: one per output; the heteroscedastic Gaussian's two outputs describe ONE distribution per row
     const int od = het ? 1 : d_out;
     // the dispersion of the negative binomial: the descriptor's lik_df on such a handle, what tbnn_set_lik_df set on any other
-    double disp = 0.0;
+    double disp = shape;
     if (negb) {
         const float r = h->nd.lik == TBNN_LIK_NEG_BINOMIAL ? h->nd.lik_df : h->ens_df;
         if (!df_ok(r)) return fail(-1, who + ": the predictive distribution under TBNN_LIK_NEG_BINOMIAL needs the dispersion: call tbnn_set_lik_df on this handle first");
@@ -646,6 +680,7 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
             if (q_out) {
                 if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else if (negb) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_NEG_BINOMIAL, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
+                else if (gam) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAMMA, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else if (het) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_HETERO_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 HIPCHK(hipGetLastError());
@@ -655,6 +690,7 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
                 const float* y = dYrows + (size_t)r0 * d_out;
                 if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else if (negb) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_NEG_BINOMIAL>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
+                else if (gam) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAMMA>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else if (het) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_HETERO_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 HIPCHK(hipGetLastError());
@@ -677,6 +713,8 @@ static int crps_check(const std::string& who, int likelihood, float fixed_sd, in
     if (likelihood == TBNN_LIK_POISSON || likelihood == TBNN_LIK_NEG_BINOMIAL)
         return fail(-1, who + ": the CRPS of a count distribution is not built (the pair term E|Y_i - Y_j| of two count distributions has no closed "
                               "form: a sum of (F(k) - 1{y <= k})^2 over the support, another kernel)");
+    if (likelihood == TBNN_LIK_GAMMA)
+        return fail(-1, who + ": the CRPS under TBNN_LIK_GAMMA is not built (the pair term E|Y_i - Y_j| of two Gamma distributions has no closed form)");
     if (likelihood == TBNN_LIK_STUDENT_T)
         return fail(-1, who + ": the CRPS under TBNN_LIK_STUDENT_T is not built (the pair term of two t distributions has no closed form, and the "
                               "Student-t predictive distribution is not built either)");

@@ -278,6 +278,8 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_uncert_finish_softmax(double* __
 //   Poisson          y f - exp(f) - lgamma(y + 1) per output, f the log-rate, in fp64 (include/tbnn.h TBNN_LIK_POISSON)
 //   neg. binomial    lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y log p + r log q per output in fp64, p = sigmoid(f - log r), the logs in
 //                    the stable form of negbin_term (common.hpp); r arrives in `nu` (ensemble_api.hpp ens_lik_consts)
+//   Gamma            a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f) per output in fp64, f the log of the mean (include/tbnn.h
+//                    TBNN_LIK_GAMMA); the shape a arrives in `nu`, by the rule the dispersion follows
 //   Student-t        cst - (nu + 1) / 2 log1p(((y - f) / sigma)^2 / nu) per output in fp64 (include/tbnn.h TBNN_LIK_STUDENT_T; sigma clipped by
 //                    the host, cst = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma: ensemble_api.hpp ens_lik_consts)
 __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restrict__ f, long n, const float* __restrict__ y, int d_out, float sigma,
@@ -311,6 +313,12 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
             const double yk = (double)y[k], t = (double)f[(size_t)k * n] - lr;
             const double lp1 = log1p(exp(-fabs(t)));
             l += (lgamma(yk + nu) - lgr - lgamma(yk + 1.0)) - (yk * (fmax(-t, 0.0) + lp1) + nu * (fmax(t, 0.0) + lp1));
+        }
+    } else if (lik == TBNN_LIK_GAMMA) {
+        const double c0 = nu * log(nu) - lgamma(nu);
+        for (int k = 0; k < d_out; ++k) {
+            const double yk = (double)y[k], fk = (double)f[(size_t)k * n];
+            l += (c0 + (nu - 1.0) * log(yk)) - nu * (fk + yk * exp(-fk));
         }
     } else if (lik == TBNN_LIK_STUDENT_T) {
         for (int k = 0; k < d_out; ++k) {
@@ -617,7 +625,7 @@ __device__ __forceinline__ double ens_phi(double y, double f, double c) {
 
 // log1p(mu) - mu.  Below |mu| < 1/32 the difference of the two would lose |mu| 2^-53 / (mu^2 / 2) of itself, so the series
 // -mu^2/2 + mu^3/3 - ... is summed there (14 terms: the first left out is below 2^-57 of the result)
-__device__ __forceinline__ double ens_log1pmx(double mu) {
+__host__ __device__ __forceinline__ double ens_log1pmx(double mu) {
 #pragma clang fp contract(off)
     if (fabs(mu) >= 0.03125) return log1p(mu) - mu;
     double t = 0.0;
@@ -626,10 +634,10 @@ __device__ __forceinline__ double ens_log1pmx(double mu) {
     return mu * mu * t;
 }
 
-// log of x^a e^-x / Gamma(a + 1), a >= 1, x > 0.  Written out, a log x - x - lgamma(a + 1) cancels terms of size a log a, so from a = 32 on
+// log of x^a e^-x / Gamma(a + 1), a > 0, x > 0.  Written out, a log x - x - lgamma(a + 1) cancels terms of size a log a, so from a = 32 on
 // it is formed around the peak instead: with mu = (x - a) / a and Stirling's series for lgamma,
 //   a (log1p(mu) - mu) - 1/2 log(2 pi a) - (1/(12 a) - 1/(360 a^3) + 1/(1260 a^5))        (next term 1/(1680 a^7) < 3e-14)
-__device__ __forceinline__ double ens_pois_logpref(double a, double x) {
+__host__ __device__ __forceinline__ double ens_pois_logpref(double a, double x) {
 #pragma clang fp contract(off)
     if (a < 32.0) return a * log(x) - x - lgamma(a + 1.0);
     const double r = 1.0 / a, r2 = r * r;
@@ -649,7 +657,10 @@ __device__ __forceinline__ double ens_pois_logpref(double a, double x) {
 //   Q = erfc(eta sqrt(a / 2)) / 2 + exp(-a eta^2 / 2) / sqrt(2 pi a) (c0 + c1 / a + c2 / a^2),   c0 = 1 / mu - 1 / eta, ...
 // Past the e^-80 exit |eta| < 0.05 there, where the c_k are summed from their Taylor series (the closed forms cancel); what is left out is
 // below 1e-16 of Q.  So the cost of one evaluation does not grow with the rate beyond 2^16.
-__device__ __forceinline__ double ens_gamma_q(double a, double x) {
+// The series and the fraction hold for every a > 0, an integer or not (the fraction of a non-integer a does not end by itself: it
+// converges, and the cap of 10 sqrt(max(a, x)) + 100 terms holds): ens_gamma_p and the Gamma likelihood's CDF call it with any shape.
+// (__host__ too: the host stages the standard Gamma quantiles that seed k_ens_pred_quantiles' bracket with the same function.)
+__host__ __device__ __forceinline__ double ens_gamma_q(double a, double x) {
 #pragma clang fp contract(off)
     if (x <= 0.0) return 1.0;
     const double lp = ens_pois_logpref(a, x);
@@ -691,6 +702,29 @@ __device__ __forceinline__ double ens_gamma_q(double a, double x) {
         if (fabs(del - 1.0) < 2.3e-16) break;
     }
     return fmin(pref * a * h, 1.0);
+}
+
+// P(a, x) = 1 - Q(a, x), the regularised LOWER incomplete gamma function, for any a > 0 and x >= 0 (+inf: 1): the CDF at y of a Gamma
+// distribution of shape a and mean mu is P(a, a y / mu).  On the series' side (x < a + 1, a < 2^16) it is returned as the series gives
+// it, pref sum_n x^n / ((a + 1) .. (a + n)) in ens_gamma_q's own order -- a small lower tail is not formed as 1 - (1 - P); elsewhere
+// 1 - Q from the fraction or Temme's expansion, where Q is the small side or both are of order 1.
+__host__ __device__ __forceinline__ double ens_gamma_p(double a, double x) {
+#pragma clang fp contract(off)
+    if (!(x > 0.0)) return 0.0;
+    if (x == (double)INFINITY) return 1.0;
+    if (!(x < a + 1.0) || a >= ENS_Q_TEMME_A) return 1.0 - ens_gamma_q(a, x);
+    const double lp = ens_pois_logpref(a, x);
+    if (lp < -80.0) return 0.0;
+    const double pref = exp(lp);
+    const int itmax = (int)(10.0 * sqrt(fmax(a, x))) + 100;
+    double ap = a, del = 1.0, sum = 1.0;
+    for (int it = 0; it < itmax; ++it) {
+        ap += 1.0;
+        del *= x / ap;
+        sum += del;
+        if (del < sum * 1e-17) break;
+    }
+    return fmin(pref * sum, 1.0);
 }
 
 // ---- the regularised incomplete beta function I_x(a, b), fp64 (the negative-binomial CDF: Pr[Y <= k] = I_q(r, k + 1), q = r / (r + mu)) ----
@@ -804,7 +838,9 @@ __device__ __forceinline__ double ens_het_gc(float g) {
 // element's f_i or a NaN target (Poisson: any target that is not finite) gives NaN.  Poisson: the target is read at k = floor(y), F = 0 for k < 0, and a non-finite rate or one
 // above 2^30 among the networks that count gives NaN.  Negative binomial (disp = r, the dispersion; not read otherwise): as Poisson with
 // F(k) = sum_i w_i / W I_{q_i}(r, k + 1), q_i = sigmoid(log r - f_i); its ceilings are 2^20 on the rate AND on k = floor(y): beyond either
-// the element is NaN (ENS_NB_MAX).
+// the element is NaN (ENS_NB_MAX).  Gamma (TBNN_LIK_GAMMA; disp = the shape a): F(y) = sum_i w_i / W P(a, a y exp(-f_i)) by ens_gamma_p,
+// F = 0 for y <= 0; NaN for a NaN target and, among the networks that count, a NaN f_i or a mean exp(f_i) that is 0 or not finite (a
+// network of weight 0 is not looked at, whatever it holds).
 template <int LIK>
 __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict__ t, int m, long tot, long r, int d_out, const float* __restrict__ Y,
                                                           const double* __restrict__ cst, double* __restrict__ cdf, double* __restrict__ below,
@@ -831,13 +867,17 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
                 F += wn * ens_phi(y, (double)fv, exp(-ens_het_gc(gv)) * 0.70710678118654752440);
                 continue;
             }
-            bad += fv != fv;
+            if (LIK != TBNN_LIK_GAMMA) bad += fv != fv;        // (Gamma: a network of weight 0 is not looked at; a NaN that counts: below)
             if (!(wn > 0.0)) continue;
             if (LIK == TBNN_LIK_POISSON) {
                 const double lam = exp((double)fv);
                 if (!(lam <= ENS_POIS_MAX_RATE)) { bad += 1; continue; }
                 if (k >= 0.0) F += wn * ens_gamma_q(k + 1.0, lam);
                 if (below && k >= 1.0) Fb += wn * ens_gamma_q(k, lam);
+            } else if (LIK == TBNN_LIK_GAMMA) {
+                const double mu = exp((double)fv);
+                if (!(mu > 0.0 && mu < (double)INFINITY)) { bad += 1; continue; }       // (the mean 0 or not finite; a NaN f_i too)
+                if (y > 0.0) F += wn * ens_gamma_p(disp, (disp * y) * exp(-(double)fv));
             } else if (LIK == TBNN_LIK_NEG_BINOMIAL) {
                 const double lam = exp((double)fv);
                 if (!(lam <= ENS_NB_MAX)) { bad += 1; continue; }
@@ -872,6 +912,13 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
 //   neg. binomial (disp = r; not read otherwise) Poisson's slots with F(k) = sum_i w_i / W I_{q_i}(r, k + 1): from k = floor(mean rate), the first
 //             step floor(sqrt(mean + mean^2 / r)) + 1.  No trial goes past k = 2^20 (ENS_NB_MAX): a probability whose F(2^20) is still below it
 //             gives NaN, and so does a rate that is not finite or above 2^20 among the networks that count.
+//   Gamma     (disp = the shape a) the Gaussian scheme on the positive axis: probs[np + j] holds g_p / a, g_p the p-quantile of the standard
+//             Gamma(a, 1) from the host, so exp(f_i) g_p / a is component i's own p-quantile and [min_i, max_i] of those the bracket; it is
+//             widened by the FACTOR 1 + 2^-44 at each end and verified with multiplicative pushes (an end on the wrong side becomes the other
+//             end and moves out by the square of the ends' ratio, up to 16 times), so no end reaches 0.  Then the same safeguarded Newton
+//             search in y, its slope the mixture density sum_i w_i / W (a / mu_i) x_i^(a - 1) e^-x_i / Gamma(a), x_i = a y / mu_i, formed in
+//             logs (infinite at 0 for a < 1: the step is then refused for the midpoint); the same stopping rule, the result the upper end.
+//             NaN: a NaN f_i, or a mean exp(f_i) that is 0 or not finite among the networks that count.
 template <int LIK, int QP>
 __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __restrict__ t, int m, long tot, const double* __restrict__ cst,
                                                                 const double* __restrict__ probs, int np, double smax, double* __restrict__ res,
@@ -879,7 +926,9 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
 #pragma clang fp contract(off)
     constexpr bool NEGB = LIK == TBNN_LIK_NEG_BINOMIAL;
     constexpr bool HET = LIK == TBNN_LIK_HETERO_GAUSSIAN;          // (a Gaussian kind below: the same bracket, search and stopping rule)
-    const bool gauss = LIK != TBNN_LIK_POISSON && !NEGB;
+    constexpr bool GAM = LIK == TBNN_LIK_GAMMA;
+    const bool gauss = LIK != TBNN_LIK_POISSON && !NEGB;      // (the continuous kinds: the Gaussian ones and Gamma)
+    const double lga = GAM ? lgamma(disp) : 0.0;
     const long ns = HET ? 2 * tot : tot;                  // floats between two networks' predictions of an element
     const double lr = NEGB ? log(disp) : 0.0;
     for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
@@ -901,11 +950,19 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
             for (int i = 0; i < m; ++i) {
                 const float fv = te[(size_t)i * ns];
                 const double wn = cst[i];
-                if (!HET) bad += fv != fv;
+                if (!HET && LIK != TBNN_LIK_GAMMA) bad += fv != fv;
                 float gv = 0.f;
                 if (HET && wn > 0.0) { gv = te[(size_t)i * ns + tot]; bad += (fv != fv) + (gv != gv); }      // (weight 0: not looked at)
                 if (!(wn > 0.0)) continue;
-                if (gauss) {
+                if (GAM) {
+                    const double mu = exp((double)fv);
+                    bad += !(mu > 0.0 && mu < (double)INFINITY);           // (a NaN f_i too; a network of weight 0 is not looked at)
+#pragma unroll
+                    for (int j = 0; j < QP; ++j) {
+                        const double v = mu * probs[np + min(p0 + j, np - 1)];
+                        a[j] = fmin(a[j], v); b[j] = fmax(b[j], v);
+                    }
+                } else if (gauss) {
                     bad += fabsf(fv) == INFINITY;
                     const double s = HET ? exp(ens_het_gc(gv)) : cst[2 * m + i];
                     if (HET) smx = fmax(smx, s);
@@ -922,7 +979,10 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
             }
 #pragma unroll
             for (int j = 0; j < QP; ++j) {
-                if (gauss) {
+                if (GAM) {
+                    a[j] *= 1.0 - 0x1p-44; b[j] *= 1.0 + 0x1p-44;
+                    x[j] = a[j]; wd[j] = b[j] / a[j];                                   // (while verifying: the ends' ratio)
+                } else if (gauss) {
                     const double d = 0x1p-44 * (fmax(fabs(a[j]), fabs(b[j])) + smx);
                     a[j] -= d; b[j] += d;
                     x[j] = a[j]; wd[j] = b[j] - a[j];
@@ -942,7 +1002,17 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     const double wn = cst[i];
                     if (!(wn > 0.0)) continue;
                     const double f = (double)te[(size_t)i * ns];
-                    if (gauss) {
+                    if (GAM) {
+                        const double am = disp * exp(-f);                                   // a / mu_i
+#pragma unroll
+                        for (int j = 0; j < QP; ++j) {
+                            if (ph[j] >= 0) {
+                                const double xi = x[j] * am;
+                                F[j] += wn * ens_gamma_p(disp, xi);
+                                D[j] += wn * (am * exp((disp - 1.0) * log(xi) - xi - lga));
+                            }
+                        }
+                    } else if (gauss) {
                         const double c = HET ? exp(-ens_het_gc(te[(size_t)i * ns + tot])) * 0.70710678118654752440 : cst[m + i], wc = wn * c;
 #pragma unroll
                         for (int j = 0; j < QP; ++j) {
@@ -988,10 +1058,12 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     const int stage = ph[j] & 7, pushes = ph[j] >> 3;
                     if (stage == 0) {                                                       // x == a: F(a) < p wanted
                         if (F[j] < p || pushes >= 16) { ph[j] = 1; x[j] = b[j]; }
+                        else if (GAM) { b[j] = a[j]; a[j] /= wd[j] * wd[j]; wd[j] = b[j] / a[j]; x[j] = a[j]; ph[j] += 8; }
                         else { b[j] = a[j]; a[j] -= 2.0 * wd[j]; wd[j] = b[j] - a[j]; x[j] = a[j]; ph[j] += 8; }
                         continue;
                     }
                     if (stage == 1) {                                                       // x == b: F(b) >= p wanted
+                        if (GAM && !(F[j] >= p) && pushes < 16) { a[j] = b[j]; b[j] *= wd[j] * wd[j]; wd[j] = b[j] / a[j]; x[j] = b[j]; ph[j] += 8; continue; }
                         if (!(F[j] >= p) && pushes < 16) { a[j] = b[j]; b[j] += 2.0 * wd[j]; wd[j] = b[j] - a[j]; x[j] = b[j]; ph[j] += 8; continue; }
                         ph[j] = 2;
                         wd[j] = 4.0 * (b[j] - a[j]);                                        // (the first trial may be a Newton step)
@@ -999,8 +1071,8 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     else a[j] = x[j];
                     const double w = b[j] - a[j];
                     if (F[j] == p || !(w > 2.0 * ens_ulp64(b[j]))) { ph[j] = -1; continue; }
-                    // F' = D / sqrt pi
-                    const double step = (p - F[j]) * 1.7724538509055160273 / D[j];
+                    // F' = D / sqrt pi (Gamma: D itself)
+                    const double step = (p - F[j]) * (GAM ? 1.0 : 1.7724538509055160273) / D[j];
                     const double xn = x[j] + step + (0x1p-20 * step + copysign(2.0 * ens_ulp64(x[j]), step));
                     const bool newton = xn > a[j] && xn < b[j] && fabs(xn - x[j]) <= 0.5 * wd[j];
                     const double xt = newton ? xn : a[j] + 0.5 * w;

@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FAST_THREADS (FAST_WAVES * 64)
 
 // HACT: activation after every hidden layer, LACT: after the last layer,
-// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT / SHAPE_LIK_NEGBIN; `false` / `true` still spell the first two) -- all
+// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT / SHAPE_LIK_NEGBIN / SHAPE_LIK_HETERO / SHAPE_LIK_GAMMA; `false` / `true` still spell the first two) -- all
 // compile-time so the tile body is one straight-line block the scheduler can interleave.
 // Round 6: network.add takes any sequence of layers and activations (tensorBNN/network.py:173-191) -- a stack whose hidden layers do NOT all
 // carry the same activation has HACT = TBNN_ACT_PACKED | sum_l act_l << 3 l (hidden layer l = 0 .. NL - 2; at most 9 of them: fused_ops.hpp,
@@ -42,16 +42,21 @@ struct Shape {
     static constexpr int HCODE = HACT_, LACT = LACT_, LIK = LIK_;
     // (bit 8 is SHAPE_LIK_STUDENT on the Gaussian code and SHAPE_LIK_NEGBIN on the Poisson code: POIS is the plain Poisson term only)
     static constexpr bool BERN = (LIK_ & 3) == SHAPE_LIK_BERN, CAT = (LIK_ & 3) == SHAPE_LIK_CAT,
-                          POIS = (LIK_ & (3 | SHAPE_LIK_NEGBIN)) == SHAPE_LIK_POIS, NEGB = (LIK_ & (3 | SHAPE_LIK_NEGBIN)) == (SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN),
+                          POIS = (LIK_ & (3 | SHAPE_LIK_NEGBIN | SHAPE_LIK_GAMMA)) == SHAPE_LIK_POIS,
+                          NEGB = (LIK_ & (3 | SHAPE_LIK_NEGBIN | SHAPE_LIK_GAMMA)) == (SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN),
                           WTD = (LIK_ & SHAPE_LIK_WEIGHTED) != 0, STUD = (LIK_ & (3 | SHAPE_LIK_STUDENT)) == (SHAPE_LIK_GAUSS | SHAPE_LIK_STUDENT);
-    // (bit 16, on the Gaussian code alone: the heteroscedastic Gaussian -- two outputs, one term per row: lik_pair)
-    static constexpr bool HET = (LIK_ & SHAPE_LIK_HETERO) != 0;
+    // (bit 16 is SHAPE_LIK_HETERO on the Gaussian code -- the heteroscedastic Gaussian, two outputs, one term per row: lik_pair -- and
+    // SHAPE_LIK_GAMMA on the Poisson code: the Gamma term of lik_delta; nowhere else)
+    static constexpr bool HET = (LIK_ & (3 | SHAPE_LIK_HETERO)) == (SHAPE_LIK_GAUSS | SHAPE_LIK_HETERO);
+    static constexpr bool GAMMA = (LIK_ & (3 | SHAPE_LIK_NEGBIN | SHAPE_LIK_GAMMA)) == (SHAPE_LIK_POIS | SHAPE_LIK_GAMMA);
     static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & ~(3 | SHAPE_LIK_WEIGHTED | SHAPE_LIK_STUDENT | SHAPE_LIK_HETERO)) == 0, "unknown likelihood code");
     static_assert(!HET || ((LIK_ & (3 | SHAPE_LIK_STUDENT)) == SHAPE_LIK_GAUSS && LACT_ == TBNN_ACT_NONE && D[NL] == 2),
                   "heteroscedastic Gaussian: a flag on the plain Gaussian code, exactly 2 outputs (mean, log-sd), no last activation");
+    static_assert((LIK_ & SHAPE_LIK_HETERO) == 0 || HET || GAMMA,
+                  "bit 16 is a flag on the Gaussian code (heteroscedastic: SHAPE_LIK_HETERO) and on the Poisson code (Gamma: SHAPE_LIK_GAMMA), not with bit 8");
     static_assert((LIK_ & SHAPE_LIK_STUDENT) == 0 || STUD || NEGB,
                   "bit 8 is a flag on the Gaussian code (Student-t: SHAPE_LIK_STUDENT) and on the Poisson code (negative binomial: SHAPE_LIK_NEGBIN)");
-    static_assert(!(POIS || NEGB) || LACT_ == TBNN_ACT_NONE, "Poisson, negative binomial: the last layer's output is the log-rate (no last activation)");
+    static_assert(!(POIS || NEGB || GAMMA) || LACT_ == TBNN_ACT_NONE, "Poisson, negative binomial, Gamma: the last layer's output is the log of the mean (no last activation)");
     static_assert(!CAT || (LACT_ == TBNN_ACT_NONE && D[NL] >= 2), "categorical: logits (no last activation), at least 2 outputs");
     static_assert((HACT_ & TBNN_ACT_PACKED) == 0 || NL - 1 <= 9, "a packed activation code holds 9 hidden layers");
     static constexpr int act(int l) { return l == NL - 1 ? LACT_ : ((HACT_ & TBNN_ACT_PACKED) ? (HACT_ >> (3 * l)) & 7 : HACT_); }
@@ -605,19 +610,20 @@ template <class S>
 __device__ __forceinline__ float lik_inv_var(const NetDev& nd, float sigma) {
     if constexpr (S::STUD) return 1.f / (nd.lik_df * sigma * sigma);
     else if constexpr (S::NEGB) return logf(nd.lik_df);
+    else if constexpr (S::GAMMA) return 0.f;              // (not read: fixed_sd plays no part under TBNN_LIK_GAMMA)
     else return 1.f / (sigma * sigma);
 }
 // the second constant of the prologue: nu + 1 (Student-t: the delta's factor; not read by the other kinds); a negative-binomial
-// instantiation: r itself
+// instantiation: r itself; a Gamma one: the shape a
 template <class S>
 __device__ __forceinline__ float lik_np1(const NetDev& nd) {
-    if constexpr (S::NEGB) return nd.lik_df;
+    if constexpr (S::NEGB || S::GAMMA) return nd.lik_df;
     else return nd.lik_df + 1.f;
 }
 
 // likelihood for one output value: statistic (counted when `count`), returns dL/df * act'.  A weighted instantiation scales the
 // residual / the row's term and its derivative by the row weight `wt` before either enters a sum: weight 1 gives the unweighted bits.
-// inv_var: lik_inv_var; np1: lik_np1, read by a Student-t or negative-binomial instantiation only.
+// inv_var: lik_inv_var; np1: lik_np1, read by a Student-t, negative-binomial or Gamma instantiation only.
 template <class S>
 __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat, float wt = 1.f, float np1 = 0.f) {
     static_assert(!S::CAT, "the categorical likelihood couples a row's outputs: cat_delta4 on the MFMA output tile, no per-element path");
@@ -657,6 +663,19 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
 #pragma clang fp contract(off)
         float term;
         const float d = negbin_term(fi, yy, np1, inv_var, &term);
+        if constexpr (S::WTD) {
+            if (count) stat += (double)(wt * term);
+            da = wt * d;
+        } else {
+            if (count) stat += (double)term;
+            da = d;
+        }
+    } else if constexpr (S::GAMMA) {
+        // TBNN_LIK_GAMMA: fi is the log of the mean and np1 holds the shape a (lik_np1); the term f + y e^-f (its factor -a and the
+        // constant: data_logp, kernels_hmc.hpp) and dL/df = a (y e^-f - 1) by gamma_term (common.hpp; one hardware exp2, not contracted)
+#pragma clang fp contract(off)
+        float term;
+        const float d = np1 * gamma_term(fi, yy, &term);
         if constexpr (S::WTD) {
             if (count) stat += (double)(wt * term);
             da = wt * d;

@@ -14,7 +14,7 @@
 // Math restated from the reference: dense W@a+b layer.py:278, activations
 // activationFunctions.py:36/49/62, Gaussian residual likelihood.py:88-94 +
 // BNN_functions.py:23-32, Bernoulli likelihood.py:226-236, categorical (softmax over a row's outputs:
-// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T), negative binomial (TBNN_LIK_NEG_BINOMIAL); reverse mode per
+// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T), negative binomial (TBNN_LIK_NEG_BINOMIAL), Gamma (TBNN_LIK_GAMMA); reverse mode per
 // SURVEY.md A12 (TF autodiff has no source in the tree).
 #pragma once
 #include "common.hpp"
@@ -132,6 +132,10 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
                     const float big = 1.f / (1.f + e), small = e / (1.f + e);
                     const float p = t >= 0.f ? big : small, qq = t >= 0.f ? small : big;
                     if (valid) { stat += (double)(wt * -(y * (fmaxf(-t, 0.f) + l) + rr * (fmaxf(t, 0.f) + l))); da = wt * (y * qq - rr * p); }
+                } else if (nd.lik == TBNN_LIK_GAMMA) {
+                    // fi is the log of the mean: f + y e^-f (its factor -a and the constant: data_logp), dL/df = a (y e^-f - 1); library expf
+                    const float ye = y * expf(-fi);
+                    if (valid) { stat += (double)(wt * (fi + ye)); da = wt * (nd.lik_df * (ye - 1.f)); }
                 } else {
                     const float r = y - fi;
                     const float wr = wt * r;

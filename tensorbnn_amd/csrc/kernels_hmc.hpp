@@ -118,17 +118,26 @@ __global__ __launch_bounds__(256) void k_shard_unpack(int P, const double* __res
 // Count targets at data staging (TBNN_LIK_POISSON, TBNN_LIK_NEG_BINOMIAL): the constant C of the log-probability, which the fused kernels
 // leave out of their statistic (no lgamma in the hot loop) -- Poisson (r = 0): C = sum_i w_i sum_k lgamma(y_ik + 1); negative binomial
 // (r > 0, the dispersion): C = sum_i w_i sum_k (lgamma(y_ik + 1) + lgamma(r) - lgamma(y_ik + r)) -- and the count of targets that are not
-// finite and >= 0 (the staging call refuses the data then).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and
+// finite and >= 0 (the staging call refuses the data then).  mode LIKC_GAMMA (TBNN_LIK_GAMMA, r = the shape a): C = sum_i w_i sum_k
+// (lgamma(a) - a log a - (a - 1) log y_ik), and the count of targets that are not finite and > 0 (log y enters C: zero is refused too).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and
 // counts out[2 b + 1]) the host adds in block order: the same bits from run to run.  w: one weight per row, null: weight 1.
 #define LIKC_BLOCKS 64
+enum { LIKC_COUNTS = 0, LIKC_GAMMA = 1 };
 __global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y, const float* __restrict__ w, long n, int d_out,
-                                                     double* __restrict__ out, double r) {
+                                                     double* __restrict__ out, double r, int mode) {
     __shared__ double red[4];
     double c = 0.0, bad = 0.0;
     const long nel = n * d_out;
     const double lgr = r > 0.0 ? lgamma(r) : 0.0;
+    const double g0 = mode == LIKC_GAMMA ? lgr - r * log(r) : 0.0;
     for (long el = (long)blockIdx.x * 256 + threadIdx.x; el < nel; el += (long)LIKC_BLOCKS * 256) {
         const float y = Y[el];
+        if (mode == LIKC_GAMMA) {
+            if (!(y > 0.f && y < INFINITY)) { bad += 1.0; continue; }
+            const double wt = w ? (double)w[el / d_out] : 1.0;
+            c += wt * (g0 - (r - 1.0) * log((double)y));
+            continue;
+        }
         if (!(y >= 0.f && y < INFINITY)) { bad += 1.0; continue; }
         const double wt = w ? (double)w[el / d_out] : 1.0;
         double t = lgamma((double)y + 1.0);
@@ -157,11 +166,12 @@ __global__ __launch_bounds__(256) void k_make_image(int P, const float* __restri
 }
 
 // data-term log-likelihood from the reduced statistic; n: the rows that normalise the Gaussian (their count, or W = sum of the row weights);
-// lik_c: the constant C of the Poisson / negative-binomial log-probability over the staged rows (k_pois_const; tbnn_api.hip:
+// lik_c: the constant C of the Poisson / negative-binomial / Gamma log-probability over the staged rows (k_pois_const; tbnn_api.hip:
 // stage_lik_const; 0 otherwise)
 __device__ __forceinline__ double data_logp(const NetDev& nd, const float* __restrict__ eta, double stat, double n, double lik_c) {
     if (nd.lik == TBNN_LIK_POISSON) return stat - lik_c;                                   // the statistic is sum w (y f - e^f)
     if (nd.lik == TBNN_LIK_NEG_BINOMIAL) return stat - lik_c;                              // ... sum w (y log p + r log q)
+    if (nd.lik == TBNN_LIK_GAMMA) return -(double)nd.lik_df * stat - lik_c;               // ... sum w (f + y e^-f), its factor -a
     if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
     // heteroscedastic Gaussian: the statistic is sum w (-gc - 1/2 r^2 u), ONE term per row: the constant -1/2 log(2 pi) counts n rows
     if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) return stat - 0.5 * 1.8378770664093453 /* log 2pi */ * n;

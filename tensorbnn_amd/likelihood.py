@@ -230,3 +230,35 @@ class HeteroscedasticGaussianLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+class GammaLikelihood(Likelihood):
+    """Positive, continuous, right-skewed targets (durations, amounts, concentrations): the last dense layer's outputs (no activation after
+    it) are the LOGS of the means, and each target is Gamma distributed with mean mu = exp(f) and the fixed shape a:
+    Var = mu^2 / shape, a constant coefficient of variation 1 / sqrt(shape); shape = 1 is the exponential distribution.  Per (row, output):
+    log p(y | f) = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f)  (include/tbnn.h TBNN_LIK_GAMMA), targets finite and > 0.
+    No hyper-parameter: the shape is fixed (GammaLikelihood(shape=a))."""
+    kind = nat.LIK_GAMMA
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.shape = float(kwargs["shape"])
+        if not (self.shape > 0 and math.isfinite(self.shape)):
+            raise ValueError("GammaLikelihood needs shape > 0 and finite")
+        self.mainProbsInHypers = False
+
+    def logDensity(self, f, y):
+        """the log density of the targets y > 0 at log-means f, element by element in float64"""
+        a = self.shape
+        f = np.asarray(f, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        return (a * math.log(a) - math.lgamma(a)) + (a - 1.0) * np.log(y) - a * (f + y * np.exp(-f))
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """the log density per (output, row) in float64, [d_out, rows] as PoissonLikelihood's; the sum is the data term"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [d_out, rows]: log-means
+        y = np.asarray(kwargs["realVals"], dtype=np.float64).reshape(-1, f.shape[0]).T
+        return self.logDensity(f, y)
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

@@ -135,8 +135,9 @@ class predictor(object):
     def _data_logprob(self, likelihood, trainX, trainY, n):
         """summed log-likelihood of the training rows under every n-th network (see the module docstring)"""
         from .layer import _multivariate_log_prob
-        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, HeteroscedasticGaussianLikelihood,
-                                 NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood, log_softmax)
+        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, GammaLikelihood,
+                                 HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood,
+                                 log_softmax)
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
@@ -149,7 +150,7 @@ class predictor(object):
             if isinstance(likelihood, CategoricalLikelihood):
                 out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
                 continue
-            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood, NegativeBinomialLikelihood)):
+            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood, NegativeBinomialLikelihood, GammaLikelihood)):
                 terms = likelihood.makeResponseLikelihood(None, predict=lambda *_a, _f=cur.T: _f, realVals=real)
                 out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1) / of the t / negative-binomial log densities
                 continue
@@ -169,10 +170,10 @@ class predictor(object):
 
     def _transform(self, transform):
         """the name of the transform asked for; None: the one the predictor's likelihood implies"""
-        from .likelihood import CategoricalLikelihood, NegativeBinomialLikelihood, PoissonLikelihood
+        from .likelihood import CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood, PoissonLikelihood
         if transform is None:
             transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
-                         "exp" if isinstance(self.likelihood, (PoissonLikelihood, NegativeBinomialLikelihood)) else "none")
+                         "exp" if isinstance(self.likelihood, (PoissonLikelihood, NegativeBinomialLikelihood, GammaLikelihood)) else "none")
         if transform not in self._TRANSFORMS:
             raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
         return transform
@@ -207,8 +208,18 @@ class predictor(object):
         Under a HeteroscedasticGaussianLikelihood the two outputs are the mean f and the log-sd g, and the plain call (like predict)
         returns the moments of both, [2, rows].  noiseVariance=True (that likelihood only; transform None, sd = 1, mean = 0): (E[f],
         Var[f] + E[s^2]), each [1, rows], s = exp(g) -- the total predictive variance of a new observation, the epistemic spread of the
-        mean plus the expected noise variance; E[s^2] = Var[s] + E[s]^2 from a second reduction on the device under the exp transform."""
-        from .likelihood import HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood
+        mean plus the expected noise variance; E[s^2] = Var[s] + E[s]^2 from a second reduction on the device under the exp transform.
+        Under a GammaLikelihood the default transform is exp too (the mean mu itself), and noiseVariance=True (transform None or "exp",
+        sd = 1, mean = 0) returns (E[mu], Var[mu] + E[mu^2] / shape): the posterior spread of the mean plus the expected Gamma noise
+        variance mu^2 / shape, added on the host as countVariance is."""
+        from .likelihood import GammaLikelihood, HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood
+        if noiseVariance and isinstance(self.likelihood, GammaLikelihood):
+            if transform not in (None, "exp") or float(sd) != 1.0 or float(mean) != 0.0 or countVariance:
+                raise ValueError("noiseVariance under a GammaLikelihood needs the mean itself: transform None or 'exp', sd = 1, mean = 0, no "
+                                 "countVariance")
+            picked, w = self._picked(n, weights)
+            m, v = self._ensure_chain().ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=nat.XFORM_EXP)
+            return m, v + (v + m * m) / self.likelihood.shape
         if noiseVariance:
             if not isinstance(self.likelihood, HeteroscedasticGaussianLikelihood):
                 raise ValueError("noiseVariance needs a HeteroscedasticGaussianLikelihood: only there does the network predict its noise")
@@ -380,8 +391,12 @@ class predictor(object):
         """the standard deviation of every n-th network under a Gaussian kind of likelihood, float32 [picked]: the fixed sd, or each
         network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; the scale of a StudentTLikelihood; None
         for the other likelihoods"""
-        from .likelihood import FixedGaussianLikelihood, NegativeBinomialLikelihood, StudentTLikelihood
+        from .likelihood import FixedGaussianLikelihood, GammaLikelihood, NegativeBinomialLikelihood, StudentTLikelihood
         picked = len(range(0, self.numNetworks, n))
+        if isinstance(lik, GammaLikelihood):
+            # no scale; its shape set on the forward chain (a fixed-sd Gaussian handle) before the reduction that judges under it
+            self._ensure_chain().set_lik_df(lik.shape)
+            return None
         if isinstance(lik, NegativeBinomialLikelihood):
             # no scale; its dispersion set on the forward chain (a fixed-sd Gaussian handle) before the reduction that judges under it
             self._ensure_chain().set_lik_df(lik.dispersion)
@@ -415,15 +430,18 @@ class predictor(object):
         its prediction, inverted on the device -- under a Gaussian kind of likelihood N(f_i, s_i^2) with s_i the network's own standard
         deviation (its saved last hyper as logPredictiveDensity reads it, or the fixed sd), under a PoissonLikelihood the counts'
         Poisson(exp(f_i)) and under a NegativeBinomialLikelihood their negative binomial of mean exp(f_i) and the likelihood's
-        dispersion, whose quantile is the smallest count k with F(k) >= p.  likelihood None: the predictor's own.  weights: one
+        dispersion, whose quantile is the smallest count k with F(k) >= p; under a GammaLikelihood the Gamma of mean exp(f_i) and
+        the likelihood's shape, a continuous distribution on y > 0 inverted as the Gaussian mixture is.  likelihood None: the predictor's own.  weights: one
         per picked network, e.g. what reweight returns.  The result is q * sd + mean, the de-normalisation of the metrics, applied on
-        the host in fp64: sd > 0, and counts take none (sd = 1, mean = 0).  predictQuantiles gives the credible quantiles of the
+        the host in fp64: sd > 0, and counts and Gamma targets take none (sd = 1, mean = 0).  predictQuantiles gives the credible quantiles of the
         network's output instead; Bernoulli and categorical likelihoods are refused (predictMoments returns a label's probability)."""
-        from .likelihood import NegativeBinomialLikelihood, PoissonLikelihood
+        from .likelihood import GammaLikelihood, NegativeBinomialLikelihood, PoissonLikelihood
         lik = self._predictive_likelihood(likelihood)
         sd, mean = float(sd), float(mean)
         if not sd > 0.0:
             raise ValueError("sd must be > 0 (a negative scale would turn the quantiles round)")
+        if isinstance(lik, GammaLikelihood) and (sd != 1.0 or mean != 0.0):
+            raise ValueError("Gamma targets are not de-normalised: sd = 1, mean = 0 under a GammaLikelihood")
         if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) and (sd != 1.0 or mean != 0.0):
             raise ValueError("counts are not de-normalised: sd = 1, mean = 0 under a PoissonLikelihood or NegativeBinomialLikelihood")
         picked, w = self._picked(n, weights)
@@ -446,7 +464,7 @@ class predictor(object):
         """The PIT values of the rows: the predictive CDF of predictiveQuantiles at the observed targets realVals, float64 [d_out, rows]
         -- uniform on (0, 1) over held-out rows when the predictive distribution is calibrated.  Targets in the networks' own
         (normalised) units.  Under a PoissonLikelihood or NegativeBinomialLikelihood the pair (F(y - 1), F(y)): a count's PIT value lies
-        anywhere on its step."""
+        anywhere on its step.  Under a GammaLikelihood F alone, as under the Gaussian kinds: the CDF is continuous."""
         from .likelihood import NegativeBinomialLikelihood, PoissonLikelihood
         lik = self._predictive_likelihood(likelihood)
         picked, w = self._picked(n, weights)
@@ -457,9 +475,12 @@ class predictor(object):
 
     # ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
     def _crps_likelihood(self, likelihood):
-        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, NegativeBinomialLikelihood, PoissonLikelihood,
-                                 StudentTLikelihood)
+        from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood,
+                                 PoissonLikelihood, StudentTLikelihood)
         lik = self.likelihood if likelihood is None else likelihood
+        if isinstance(lik, GammaLikelihood):
+            raise ValueError("the CRPS is not built for a GammaLikelihood (the pair term of two Gamma distributions has no closed form); "
+                             "logPredictiveDensity, loo, waic, predictiveInterval and predictiveCDF are")
         if isinstance(lik, (BernoulliLikelihood, CategoricalLikelihood)):
             raise ValueError("the CRPS is a score of a real-valued prediction: predictUncertainty and calibration judge a label")
         if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)):
@@ -528,8 +549,12 @@ class predictor(object):
 
     # ---- classification: entropy split, votes (tbnn_ensemble_uncertainty) and calibration of the posterior-mean classifier ----
     def _label_likelihood(self, likelihood):
-        from .likelihood import BernoulliLikelihood, CategoricalLikelihood
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood
         lik = self.likelihood if likelihood is None else likelihood
+        if isinstance(lik, GammaLikelihood):
+            raise ValueError("the entropy split and the votes are those of a label, not of a GammaLikelihood's positive target: "
+                             "predictMoments(noiseVariance=True) separates the Gamma noise from the posterior spread of the mean, and "
+                             "predictiveInterval / predictiveCDF check the intervals")
         if not isinstance(lik, (BernoulliLikelihood, CategoricalLikelihood)):
             raise ValueError("the entropy split, the votes and the calibration table are those of a label: a BernoulliLikelihood or a "
                              "CategoricalLikelihood; for a regression predictMoments(noiseVariance=True) separates the noise from the "
