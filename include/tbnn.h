@@ -86,7 +86,10 @@ enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
  * activation after the last layer: its output f is the LOG of the mean, mu = exp(f).  The shape a = the descriptor's lik_df, finite and
  * > 0 (tbnn_create, tbnn_create_multi and tbnn_fused_kernel_available refuse any other lik_df); variance mu^2 / a, a constant coefficient
  * of variation 1 / sqrt(a); a = 1 is the exponential distribution.  fixed_sd is not read.  No likelihood hyper (H = 4 n_layers).  Targets
- * are finite and strictly > 0: staging refuses anything else, zero too (log y enters the constant).  Per (row, output):
+ * are finite, strictly > 0 and at most 2^100 (1.2676506e30): staging refuses anything else, zero too (log y enters the constant).  The
+ * ceiling: where exp(-f) leaves fp32's normal range (f > 87.3) the hardware exp returns 0 and an element loses y exp(-f) < y 2^-126, below
+ * 2^-26 of the 1 it is subtracted from for every admitted target.  fp32-denormal targets are admitted: the kernels' products and the
+ * constant keep them (tests/test_gpu_likelihood_edges.py test_denormal_targets).  Per (row, output):
  * log p(y | f) = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f),  dL/df = a (y exp(-f) - 1).  The kernels accumulate
  * stat = sum_i w_i (f + y e^-f) with one hardware exp per element and return the delta w a (y e^-f - 1); the constant
  * C = sum_i w_i sum_k (lgamma(a) - a log a - (a - 1) log y_ik) is computed with the data (or row weights), in fp64 and bit for bit the same

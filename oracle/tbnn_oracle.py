@@ -31,16 +31,16 @@ paramAdapter.py:60); ``np.float64`` is the high-precision arm used to bound
 rounding error.
 
 EXTENSIONS BEYOND THE REFERENCE.  The categorical, Poisson, Student-t,
-negative-binomial and heteroscedastic Gaussian likelihoods and the per-row
+negative-binomial, heteroscedastic Gaussian and Gamma likelihoods and the per-row
 likelihood weights ``w`` are the library's own (definitions: ``include/tbnn.h``
-TBNN_LIK_CATEGORICAL / _POISSON / _STUDENT_T / _NEG_BINOMIAL / _HETERO_GAUSSIAN,
-tbnn_set_row_weights, ``tensorbnn_amd/likelihood.py``): there are no reference
+TBNN_LIK_CATEGORICAL / _POISSON / _STUDENT_T / _NEG_BINOMIAL / _HETERO_GAUSSIAN /
+_GAMMA, tbnn_set_row_weights, ``tensorbnn_amd/likelihood.py``): there are no reference
 lines to cite, and torch.autograd alone pins them (tests/test_oracle.py).  Their
 docstrings say "extension".  With ``w=None`` the Gaussian, fixed-sd Gaussian
 and Bernoulli paths are the reference's, operation by operation.  The element
-functions of the last three have two arms of their own: ``np.float64`` is the
+functions of the last four have two arms of their own: ``np.float64`` is the
 definition as written, ``np.float32`` the kernels' operation order
-(``csrc/common.hpp`` log1p_fast, negbin_term, hetero_pair); in both the terms
+(``csrc/common.hpp`` log1p_fast, negbin_term, hetero_pair, gamma_term); in both the terms
 are summed in fp64 and the constant is fp64, as the library's accumulators do,
 and the value is a float64.
 """
@@ -62,8 +62,9 @@ PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2
 LIK_CATEGORICAL, LIK_POISSON = 3, 5       # extensions: include/tbnn.h TBNN_LIK_* (4 is unassigned)
 LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN = 8, 10, 12     # extensions too (the codes between are unassigned)
+LIK_GAMMA = 14                           # extension too
 LIKELIHOODS = (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON,
-               LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN)
+               LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN, LIK_GAMMA)
 
 
 @dataclass
@@ -84,7 +85,7 @@ class NetSpec:
     layers: List[DenseSpec]
     likelihood: int = LIK_GAUSSIAN
     fixed_sd: float = 0.1          # FixedGaussianLikelihood(sd=...) likelihood.py:138-141; the Student-t scale (extension)
-    lik_df: float = 0.0            # extension (NetDev::lik_df): Student-t degrees of freedom nu, negative-binomial dispersion r
+    lik_df: float = 0.0            # extension (NetDev::lik_df): Student-t degrees of freedom nu, negative-binomial dispersion r, Gamma shape a
 
     @property
     def n_params(self) -> int:
@@ -383,7 +384,36 @@ def negbin_terms(f, Y, r):
     return t + negbin_const_terms(np.asarray(Y, dtype=np.float64).reshape(f.shape[1], -1).T, r)
 
 
-_FP64_DATA_TERM = (LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN)     # summed by _data_term
+def gamma_const_terms(Y, a):
+    """extension: a log a - lgamma(a) + (a - 1) log y per target, fp64 (the shape of Y): the part of the Gamma log density that does not
+    depend on f."""
+    y = np.asarray(Y, dtype=np.float64)
+    a = float(a)
+    return (a * math.log(a) - math.lgamma(a)) + (a - 1.0) * np.log(y)
+
+
+def gamma_elementwise(f, Y, a, dtype):
+    """extension: (f + y e^-f, dL/df = a (y e^-f - 1)), f the log of the mean, a the shape, each [d_out, n] in ``dtype``; f [d_out, n],
+    Y [n, d_out] (or flat).  np.float64: the definition.  np.float32: the kernel's operations (gamma_term, kernels_fast.hpp lik_delta):
+    e = exp(-f), ye = y e, the term f + ye, the delta a (ye - 1).  A log-mean below the range of exp(-f) gives inf in either arm."""
+    dt = dtype
+    f = np.asarray(f, dtype=dt)
+    y = np.asarray(Y, dtype=dt).reshape(f.shape[1], -1).T
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.exp(-f).astype(dt)
+        ye = (y * e).astype(dt)
+        return (f + ye).astype(dt), (dt(a) * (ye - dt(1))).astype(dt)
+
+
+def gamma_terms(f, Y, a):
+    """extension: the Gamma log density per (output, row), fp64 [d_out, n]:
+    a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f)."""
+    f = np.asarray(f, dtype=np.float64)
+    t, _d = gamma_elementwise(f, Y, a, np.float64)
+    return gamma_const_terms(np.asarray(Y, dtype=np.float64).reshape(f.shape[1], -1).T, a) - float(a) * t
+
+
+_FP64_DATA_TERM = (LIK_STUDENT_T, LIK_NEG_BINOMIAL, LIK_HETERO_GAUSSIAN, LIK_GAMMA)     # summed by _data_term
 LOG_CLIP = math.log(1e8)                      # the heteroscedastic clip of the log-sd output
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
@@ -425,9 +455,10 @@ def hetero_terms(f, Y):
 
 
 def _data_term(spec: NetSpec, f, Y, dtype, w):
-    """extension: (the data term as a float64, the statistic sum_i w_i t_i as the kernels accumulate it) of the Student-t, negative-binomial
-    and heteroscedastic likelihoods: the element terms t in ``dtype``, a row's weight applied in ``dtype`` (the kernel: wt * term), the sum
-    and the constant in fp64.  A weighted row scales its share of the constant too (Student-t, heteroscedastic: sum(w) rows)."""
+    """extension: (the data term as a float64, the statistic sum_i w_i t_i as the kernels accumulate it) of the Student-t, negative-binomial,
+    heteroscedastic and Gamma likelihoods: the element terms t in ``dtype``, a row's weight applied in ``dtype`` (the kernel: wt * term),
+    the sum and the constant in fp64.  A weighted row scales its share of the constant too (Student-t, heteroscedastic: sum(w) rows).
+    Gamma: the statistic is sum w (f + y e^-f), its factor -a and the constant sum w (a log a - lgamma(a) + (a - 1) log y) are fp64."""
     n = f.shape[1]
     if spec.likelihood == LIK_STUDENT_T:
         t, _d = student_elementwise(f, Y, spec.lik_df, student_scale(spec), dtype)
@@ -435,6 +466,8 @@ def _data_term(spec: NetSpec, f, Y, dtype, w):
         t, _d = negbin_elementwise(f, Y, spec.lik_df, dtype)
     elif spec.likelihood == LIK_HETERO_GAUSSIAN:
         t, _d = hetero_pair(f, Y, dtype)
+    elif spec.likelihood == LIK_GAMMA:
+        t, _d = gamma_elementwise(f, Y, spec.lik_df, dtype)
     else:
         raise ValueError(spec.likelihood)
     if w is not None:
@@ -446,15 +479,19 @@ def _data_term(spec: NetSpec, f, Y, dtype, w):
         return np.float64(rows * f.shape[0] * student_const(nu, s) - 0.5 * (float(nu) + 1.0) * stat), stat
     if spec.likelihood == LIK_HETERO_GAUSSIAN:
         return np.float64(stat - HALF_LOG_2PI * rows), stat
-    c = negbin_const_terms(np.asarray(Y, dtype=np.float64).reshape(n, -1).T, spec.lik_df)          # [d_out, n]
+    y64 = np.asarray(Y, dtype=np.float64).reshape(n, -1).T                                         # [d_out, n]
+    c = gamma_const_terms(y64, spec.lik_df) if spec.likelihood == LIK_GAMMA else negbin_const_terms(y64, spec.lik_df)
     if w is not None:
         c = np.asarray(w, dtype=np.float64) * c
+    if spec.likelihood == LIK_GAMMA:
+        return np.float64(-float(spec.lik_df) * stat + float(np.sum(c))), stat
     return np.float64(stat + float(np.sum(c))), stat
 
 
 def data_statistic(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
-    """extension: the statistic the kernels accumulate for the Student-t (sum w log1p(u)), negative-binomial (sum w (y log p + r log q))
-    and heteroscedastic (sum w (-gc - 1/2 r^2 u)) likelihoods: their data term less its constant and, for Student-t, its factor."""
+    """extension: the statistic the kernels accumulate for the Student-t (sum w log1p(u)), negative-binomial (sum w (y log p + r log q)),
+    heteroscedastic (sum w (-gc - 1/2 r^2 u)) and Gamma (sum w (f + y e^-f)) likelihoods: their data term less its constant and, for
+    Student-t and Gamma, its factor."""
     return _data_term(spec, np.asarray(f, dtype=dtype), Y, dtype, w)[1]
 
 
@@ -467,8 +504,8 @@ def log_likelihood(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
     Poisson: y f - exp(f) - lgamma(y + 1), returned in fp64 in either arm (it carries the fp64 constant);
     ``w``: one weight >= 0 per row (None = 1) scales the row's term before the sum, and a Gaussian row counts w_i times
     (the row count becomes sum w);
-    Student-t, negative binomial, heteroscedastic Gaussian: :func:`student_terms`, :func:`negbin_terms`, :func:`hetero_terms` summed
-    by :func:`_data_term`, a float64 in either arm as well."""
+    Student-t, negative binomial, heteroscedastic Gaussian, Gamma: :func:`student_terms`, :func:`negbin_terms`, :func:`hetero_terms`,
+    :func:`gamma_terms` summed by :func:`_data_term`, a float64 in either arm as well."""
     dt = dtype
     f = np.asarray(f, dtype=dt)
     if spec.likelihood in _FP64_DATA_TERM:
@@ -542,8 +579,8 @@ def prior_grad(l: DenseSpec, h4, W, b, dtype=np.float32):
 
 def likelihood_grad(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
     """dL/df [d_out, n] of :func:`log_likelihood`.  Extensions: categorical y_k - softmax_k sum_j y_j, Poisson y - exp(f), the deltas
-    of :func:`student_elementwise`, :func:`negbin_elementwise` and :func:`hetero_pair` ([2, n]: dL/df and dL/dg), and ``w`` scaling a
-    row's dL/df."""
+    of :func:`student_elementwise`, :func:`negbin_elementwise`, :func:`hetero_pair` ([2, n]: dL/df and dL/dg) and
+    :func:`gamma_elementwise`, and ``w`` scaling a row's dL/df."""
     dt = dtype
     n = f.shape[1]
     if spec.likelihood in (LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN):
@@ -567,6 +604,8 @@ def likelihood_grad(spec: NetSpec, eta, f, Y, dtype=np.float32, w=None):
         d_a = negbin_elementwise(f, Y, spec.lik_df, dt)[1]
     elif spec.likelihood == LIK_HETERO_GAUSSIAN:
         d_a = hetero_pair(f, Y, dt)[1]
+    elif spec.likelihood == LIK_GAMMA:
+        d_a = gamma_elementwise(f, Y, spec.lik_df, dt)[1]
     else:
         raise ValueError(spec.likelihood)
     return d_a if w is None else np.asarray(w, dtype=dt) * d_a

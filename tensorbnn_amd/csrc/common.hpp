@@ -182,7 +182,9 @@ __device__ __forceinline__ float negbin_elem(float fi, float y, double& stat, fl
 // Gamma with log link (TBNN_LIK_GAMMA, defined in include/tbnn.h), fi the log of the mean.  ONE hardware exp2: e = e^-f, the element's
 // part of the statistic f + y e^-f (its factor -a and the constant: data_logp, kernels_hmc.hpp) and, returned, y e^-f - 1: dL/df over the
 // shape a, which the caller multiplies in.  A log-mean below the fp32 range of e^-f gives inf: the statistic is not finite and k_energy
-// rejects the proposal (Poisson's rule, on the other side); NaN gives NaN.  Not contracted, for the reason given at log1p_fast.  One
+// rejects the proposal (Poisson's rule, on the other side); NaN gives NaN.  On the other side, a log-mean above 87.3 puts e^-f below
+// fp32's normal range and the hardware exp2 returns 0: the element becomes the term f and the delta -a, short of y e^-f < y 2^-126.  Staging
+// admits targets up to 2^100 only (k_pois_const, GAMMA_Y_MAX), so what is lost stays below 2^-26 next to the 1 it is subtracted from.  Not contracted, for the reason given at log1p_fast.  One
 // function for lik_delta's compile-time branch and the kernels that branch at run time.
 __device__ __forceinline__ float gamma_term(float fi, float y, float* term) {
 #pragma clang fp contract(off)

@@ -119,10 +119,13 @@ __global__ __launch_bounds__(256) void k_shard_unpack(int P, const double* __res
 // leave out of their statistic (no lgamma in the hot loop) -- Poisson (r = 0): C = sum_i w_i sum_k lgamma(y_ik + 1); negative binomial
 // (r > 0, the dispersion): C = sum_i w_i sum_k (lgamma(y_ik + 1) + lgamma(r) - lgamma(y_ik + r)) -- and the count of targets that are not
 // finite and >= 0 (the staging call refuses the data then).  mode LIKC_GAMMA (TBNN_LIK_GAMMA, r = the shape a): C = sum_i w_i sum_k
-// (lgamma(a) - a log a - (a - 1) log y_ik), and the count of targets that are not finite and > 0 (log y enters C: zero is refused too).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and
+// (lgamma(a) - a log a - (a - 1) log y_ik), and the count of targets that are not finite and > 0 (log y enters C: zero is refused too) or lie
+// above GAMMA_Y_MAX = 2^100: where e^-f leaves fp32's normal range (f > 87.3) the hardware exp2 of gamma_term returns 0 and the element
+// loses y e^-f < y 2^-126, which the ceiling keeps below 2^-26 next to the 1 it is subtracted from (include/tbnn.h TBNN_LIK_GAMMA).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and
 // counts out[2 b + 1]) the host adds in block order: the same bits from run to run.  w: one weight per row, null: weight 1.
 #define LIKC_BLOCKS 64
 enum { LIKC_COUNTS = 0, LIKC_GAMMA = 1 };
+#define GAMMA_Y_MAX 0x1p100f
 __global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y, const float* __restrict__ w, long n, int d_out,
                                                      double* __restrict__ out, double r, int mode) {
     __shared__ double red[4];
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y,
     for (long el = (long)blockIdx.x * 256 + threadIdx.x; el < nel; el += (long)LIKC_BLOCKS * 256) {
         const float y = Y[el];
         if (mode == LIKC_GAMMA) {
-            if (!(y > 0.f && y < INFINITY)) { bad += 1.0; continue; }
+            if (!(y > 0.f && y <= GAMMA_Y_MAX)) { bad += 1.0; continue; }
             const double wt = w ? (double)w[el / d_out] : 1.0;
             c += wt * (g0 - (r - 1.0) * log((double)y));
             continue;

@@ -459,7 +459,7 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
 }
 
 // Poisson, negative binomial and Gamma (TBNN_LIK_POISSON, TBNN_LIK_NEG_BINOMIAL, TBNN_LIK_GAMMA; any other likelihood: C = 0, nothing runs): the constant C of the n rows dY (device) under the row weights dw
-// (device, null: none) -- k_pois_const, its partials added here in block order -- and the refusal of targets that are not counts (Gamma: not finite and > 0).  Called
+// (device, null: none) -- k_pois_const, its partials added here in block order -- and the refusal of targets that are not counts (Gamma: not finite and > 0, or above 2^100).  Called
 // by everything that stages rows or weights BEFORE it changes the handle: a refusal leaves the handle as it was.
 static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY, const float* dw, long n, double* C) {
     *C = 0.0;
@@ -476,7 +476,7 @@ static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY,
     double c = 0.0, bad = 0.0;
     for (int b = 0; b < LIKC_BLOCKS; ++b) { c += host[2 * b]; bad += host[2 * b + 1]; }
     if (bad > 0.0 && gam)
-        return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are zero, negative or not finite: under the Gamma likelihood targets must be finite and > 0");
+        return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are zero, negative, not finite or above the ceiling: under the Gamma likelihood targets must be finite and > 0 and at most 2^100 (1.2676506e30)");
     if (bad > 0.0)
         return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are negative or not finite: the " + (nb ? "negative-binomial" : "Poisson") + " likelihood takes counts (finite, >= 0)");
     *C = c;

@@ -236,7 +236,8 @@ class GammaLikelihood(Likelihood):
     """Positive, continuous, right-skewed targets (durations, amounts, concentrations): the last dense layer's outputs (no activation after
     it) are the LOGS of the means, and each target is Gamma distributed with mean mu = exp(f) and the fixed shape a:
     Var = mu^2 / shape, a constant coefficient of variation 1 / sqrt(shape); shape = 1 is the exponential distribution.  Per (row, output):
-    log p(y | f) = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f)  (include/tbnn.h TBNN_LIK_GAMMA), targets finite and > 0.
+    log p(y | f) = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f)  (include/tbnn.h TBNN_LIK_GAMMA), targets finite, > 0 and at most 2^100
+    (1.27e30: the staging call refuses a larger one, and zero).
     No hyper-parameter: the shape is fixed (GammaLikelihood(shape=a))."""
     kind = nat.LIK_GAMMA
 

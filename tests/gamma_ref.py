@@ -1,33 +1,34 @@
-"""The reference of the Gamma likelihood (include/tbnn.h TBNN_LIK_GAMMA) for the tests: the oracle (oracle/tbnn_oracle.py) has no such
-likelihood, so the data term and its derivative are stated here and everything else -- the forward pass, the priors and their gradients,
-the reverse mode's layer loop, the leapfrog / Metropolis step, the hyper transition -- is the oracle's.
+"""The cases of the Gamma likelihood's tests (include/tbnn.h TBNN_LIK_GAMMA) and thin wrappers over the oracle, which models the
+likelihood (oracle/tbnn_oracle.py LIK_GAMMA: gamma_elementwise, gamma_const_terms, gamma_terms and the Gamma branches of its targets).
 
 Per (row, output), f the log of the mean, a the shape, mu = exp(f):
     log p(y | f) = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f)
     dL/df        = a (y exp(-f) - 1)
-A row weight w_i scales the row's terms and deltas.
+A row weight w_i scales the row's terms and deltas.  The two arms (np.float64: the definition; np.float32: the kernel's own formula,
+operation by operation) are described at the oracle's gamma_elementwise and _data_term.
 
-Two arms.  dtype=np.float64: the definition as written.  dtype=np.float32: the KERNEL's own formula, operation by operation in fp32
-(csrc/common.hpp gamma_term, csrc/kernels_fast.hpp lik_delta): e = exp(-f), ye = y e, the term f + ye, the delta a (ye - 1), a weight
-multiplied onto either afterwards; the terms are summed in fp64, as the kernels' accumulators sum them, the factor -a and the constant
-C = sum w (lgamma(a) - a log a - (a - 1) log y) are fp64 (csrc/kernels_hmc.hpp data_logp, k_pois_const), and the priors are the oracle's
-fp32 arm.  The network's own arithmetic (matrix products, activations) is the oracle's in that dtype.
-
-A spec here is the oracle's NetSpec with likelihood LIK_FIXED_GAUSSIAN and no last activation (no likelihood hyper: H = 4 layers): the
-oracle's own hyper transition of such a spec is the layer priors alone, which is the Gamma hyper transition too."""
+A spec here is the oracle's NetSpec with likelihood LIK_GAMMA, no last activation and lik_df = a (no likelihood hyper: H = 4 layers).  The
+functions below keep the call shapes the Gamma modules were written with -- (spec, a, ...) -- assert that the spec carries that shape and
+hand over to the oracle."""
 import functools
-import math
 
 import numpy as np
 
 import tbnn_oracle as o
 import student_ref as _sr
 
-LIK_GAMMA = 14
+LIK_GAMMA = o.LIK_GAMMA
+assert LIK_GAMMA == 14
 
 
-def make_spec(dims, act, prior):
-    return o.make_spec(dims, act, prior, o.LIK_FIXED_GAUSSIAN, o.ACT_NONE)
+def make_spec(dims, act, prior, a=0.0):
+    """a: the shape (0: a spec for its layers alone, as the run-time jobs read it)"""
+    return o.make_spec(dims, act, prior, o.LIK_GAMMA, o.ACT_NONE, lik_df=float(a))
+
+
+def _checked(spec, a):
+    assert spec.likelihood == o.LIK_GAMMA and spec.lik_df == a, (spec.likelihood, spec.lik_df, a)
+    return spec
 
 
 def prior_log_prob(spec, theta, eta, dtype):
@@ -40,84 +41,37 @@ def prior_log_prob(spec, theta, eta, dtype):
     return prob
 
 
-def const_terms(Y, a):
-    """a log a - lgamma(a) + (a - 1) log y per target, fp64 (the shape of Y): the part of the log density that does not depend on f"""
-    y = np.asarray(Y, dtype=np.float64)
-    a = float(a)
-    return (a * math.log(a) - math.lgamma(a)) + (a - 1.0) * np.log(y)
-
-
-def elementwise(f, Y, a, dtype):
-    """(f + y e^-f, dL/df = a (y e^-f - 1)), each [d_out, n] in `dtype`; f [d_out, n], Y [n, d_out] (or flat)"""
-    dt = dtype
-    f = np.asarray(f, dtype=dt)
-    y = np.asarray(Y, dtype=dt).reshape(f.shape[1], -1).T
-    with np.errstate(over="ignore", invalid="ignore"):
-        e = np.exp(-f).astype(dt)
-        ye = (y * e).astype(dt)
-        return (f + ye).astype(dt), (dt(a) * (ye - dt(1))).astype(dt)
-
-
-def terms(f, Y, a):
-    """the log density per (output, row), fp64 [d_out, n]"""
-    f = np.asarray(f, dtype=np.float64)
-    t, _d = elementwise(f, Y, a, np.float64)
-    return const_terms(np.asarray(Y, dtype=np.float64).reshape(f.shape[1], -1).T, a) - float(a) * t
+const_terms = o.gamma_const_terms
+elementwise = o.gamma_elementwise
+terms = o.gamma_terms
 
 
 def data_log_prob(spec, a, f, Y, dtype=np.float64, w=None):
     """(the data term as a float64, the statistic sum w (f + y e^-f) as the kernels accumulate it)"""
-    t, _d = elementwise(f, Y, a, dtype)
-    c = const_terms(np.asarray(Y, dtype=np.float64).reshape(f.shape[1], -1).T, a)          # [d_out, n]
-    if w is not None:
-        t = (np.asarray(w, dtype=dtype) * t).astype(dtype)       # (the kernel: wt * term in fp32, then the fp64 sum)
-        c = np.asarray(w, dtype=np.float64) * c
-    stat = float(np.sum(t.astype(np.float64)))
-    return -float(a) * stat + float(np.sum(c)), stat
+    lp, stat = o._data_term(_checked(spec, a), np.asarray(f, dtype=dtype), Y, dtype, w)
+    return float(lp), stat
 
 
 def target_log_prob_and_grad(spec, a, theta, eta, X, Y, dtype=np.float64, w=None):
-    """(log posterior as a float64, its gradient in `dtype`): the oracle's target_log_prob_and_grad with the Gamma data term"""
-    dt = dtype
-    theta, eta = np.asarray(theta, dtype=dt), np.asarray(eta, dtype=dt)
-    parts = o.unflatten(spec, theta)
-    f, acts = o.forward(spec, theta, X, dt, keep=True)
-    logp = float(prior_log_prob(spec, theta, eta, dt)) + data_log_prob(spec, a, f, Y, dt, w)[0]
-    _t, d_a = elementwise(f, Y, a, dt)
-    if w is not None:
-        d_a = (np.asarray(w, dtype=dt) * d_a).astype(dt)
-    grads = [None] * len(spec.layers)
-    for i in range(len(spec.layers) - 1, -1, -1):
-        l = spec.layers[i]
-        W, b = parts[i]
-        delta = (d_a * o.act_grad_from_output(acts[i + 1], l.act)).astype(dt)
-        gW = delta @ acts[i].T
-        gb = np.sum(delta, axis=1, keepdims=True, dtype=dt)
-        pW, pb = o.prior_grad(l, eta[4 * i:4 * i + 4], W, b, dt)
-        grads[i] = ((gW + pW).astype(dt), (gb + pb).astype(dt))
-        if i > 0:
-            d_a = (W.T @ delta).astype(dt)
-    return logp, o.flatten(grads).astype(dt)
+    """(log posterior as a float64, its gradient in `dtype`)"""
+    lp, g = o.target_log_prob_and_grad(_checked(spec, a), theta, eta, X, Y, dtype, w=w)
+    return float(lp), g
 
 
 def likelihood_value_and_grad(spec, a, theta, eta, X, Y, dtype=np.float64, w=None):
     """the data term alone and its gradient (tbnn_optimize's objective "likelihood")"""
-    dt = dtype
-    lp, g = target_log_prob_and_grad(spec, a, theta, eta, X, Y, dt, w)
-    th, et = np.asarray(theta, dtype=dt), np.asarray(eta, dtype=dt)
-    pg = [tuple(o.prior_grad(l, et[4 * i:4 * i + 4], W, b, dt)) for i, (l, (W, b)) in enumerate(zip(spec.layers, o.unflatten(spec, th)))]
-    return lp - float(prior_log_prob(spec, th, et, dt)), (g - o.flatten(pg).astype(dt)).astype(dt)
+    lp, g = o.likelihood_value_and_grad(_checked(spec, a), theta, eta, X, Y, dtype, w=w)
+    return float(lp), g
 
 
 def weight_step(spec, a, theta, eta, X, Y, eps, L, p0, log_u, dtype=np.float64, w=None):
-    """one weight transition: the oracle's leapfrog and Metropolis step over this module's value and gradient (energies in fp64)"""
-    vg = lambda q: target_log_prob_and_grad(spec, a, q, eta, X, Y, dtype, w)
-    return o.hmc_step(vg, theta, eps, L, p0, log_u, dtype, np.float64)
+    """one weight transition: the oracle's leapfrog and Metropolis step (energies in fp64)"""
+    return o.weight_step(_checked(spec, a), theta, eta, X, Y, eps, L, p0, log_u, dtype, np.float64, w=w)
 
 
 def hyper_step(spec, eta, theta, X, Y, eps_h, L_h, p0, log_u, dtype=np.float64):
-    """the hyper transition: no likelihood hyper and no data term -- the oracle's own for a fixed-sd spec"""
-    assert spec.likelihood == o.LIK_FIXED_GAUSSIAN
+    """the hyper transition: no likelihood hyper and no data term -- the layer priors alone"""
+    assert spec.likelihood == o.LIK_GAMMA
     return o.hyper_step(spec, eta, theta, X, Y, eps_h, L_h, p0, log_u, dtype)
 
 
@@ -131,7 +85,7 @@ def problem_of(dims, n, act, prior, a, seed=11):
     """(spec, X, Y, theta, eta): the oracle's synthetic rows and initial state; the targets are drawn from the model -- Gamma of shape a
     and mean exp(0.5 + 0.8 z), z the oracle's teacher's standardised outputs -- and kept strictly positive in fp32"""
     _g, X, Yr, theta, eta = o.synth_problem(dims, n, act, prior, o.LIK_GAUSSIAN)
-    spec = make_spec(dims, act, prior)
+    spec = make_spec(dims, act, prior, a)
     if dims[0] > 64:
         X = (X / np.sqrt(dims[0] / 16.0)).astype(np.float32)          # keep a long fan-in's pre-activations O(1)
     eta = np.asarray(eta[:spec.n_hypers], dtype=np.float32)          # no likelihood hyper

@@ -1,10 +1,10 @@
-"""The datasets of tests/test_likelihood_edges_host.py and tests/test_gpu_likelihood_edges.py: the Poisson, Student-t, negative-binomial and
-heteroscedastic Gaussian likelihoods on the inputs where their element arithmetic (csrc/common.hpp log1p_fast, negbin_term, hetero_pair;
-kernels_fast.hpp lik_delta's Poisson branch) changes regime.  Importable without a GPU; no reference formula is stated here -- the fp64 and
+"""The datasets of tests/test_likelihood_edges_host.py and tests/test_gpu_likelihood_edges.py: the Poisson, Student-t, negative-binomial,
+heteroscedastic Gaussian and Gamma likelihoods on the inputs where their element arithmetic (csrc/common.hpp log1p_fast, negbin_term,
+hetero_pair, gamma_term; kernels_fast.hpp lik_delta's Poisson branch) changes regime.  Importable without a GPU; no reference formula is stated here -- the fp64 and
 fp32 arms are the oracle's.
 
 A BAND is a range of the quantity the element code branches on (Student-t: u = (y - f)^2 / (nu s^2); negative binomial: t = f - log r;
-heteroscedastic Gaussian: g, the log-sd output; Poisson: the log-rate).  One dataset holds ONE band on every (row, output), so the band's
+heteroscedastic Gaussian: g, the log-sd output; Poisson: the log-rate; Gamma: the log-mean f, or rho = y e^-f).  One dataset holds ONE band on every (row, output), so the band's
 error is not diluted by well-conditioned rows.  A dataset is built as test_gpu_edges.saturated_problem builds its own: the case's shape,
 activations, priors and initial state (student_ref.CASES / hetero_ref.CASES), the hidden layers left alone, the last layer rescaled and
 shifted per output so that the fp64 outputs at the fp32 state land in the band over a pool of rows, N_ROWS = 301 rows (18 full 16-row tiles
@@ -12,6 +12,8 @@ and a ragged one) picked from the pool.  Student-t leaves the outputs O(1) and p
 
 Conditioning: in every dataset the residual signs (one per output, alternating over outputs and datasets) or the mixture of count targets
 are chosen so that the last layer's bias gradient is no cancelled sum on the fp64 reference -- sum |delta| / |sum delta| <= 4 per output.
+Gamma targets drawn from the model would have E[delta] = 0: a factor c per output (2 or 1/2, alternating as the signs do) takes them off the
+model's mean; the bands placed through rho are one-signed by construction.
 
 Bands of the GPU module (`arms`): the project's (value 4e-6 relative, gradient 1e-4 of each tensor's largest entry, floor 1e-3)
 wherever the fp32 arm of the reference is inside HALF of them; otherwise max(project band, 8 x the fp32 arm's gap against fp64), the rule of
@@ -20,6 +22,7 @@ import math
 
 import numpy as np
 
+import gamma_ref as gr
 import hetero_ref as hr
 import negbin_ref as nb
 import student_ref as sr
@@ -29,7 +32,8 @@ from tensor_checks import tensor_errs
 N_ROWS = 301
 POOL = 16000
 FLT_MAX = float(np.finfo(np.float32).max)
-LIKS = ("student", "negbin", "hetero", "poisson")
+FLT_MIN = float(np.finfo(np.float32).tiny)
+LIKS = ("student", "negbin", "hetero", "poisson", "gamma")          # (a dataset's seed holds the index: new likelihoods go at the end)
 # the kernels reached: narrow (fast3, fast), mid VALU / MFMA output tile, tall, wide VALU / MFMA, the three layered likelihood
 # kernels, generic; the heteroscedastic Gaussian has the 2-output versions (hetero_ref.CASES: no MFMA-output case)
 CASE_NAMES = ("fast3", "fast", "mid1", "mid10", "tall", "wide1", "wide10", "lay_last", "lay_separate", "lay_tail", "generic")
@@ -66,11 +70,32 @@ POISSON_BANDS = {"deep-": (-104.0, -20.0), "high": (60.0, 80.0), "flush": (-104.
 # flush them and NumPy keep them, either inside the band -- while a term that keeps mu away from 0 (max(mu, FLT_MIN)) doubles the sum.
 # With one output the two groups are rows taken in turn (every 16-row tile holds both); with more, the outputs take the groups in turn
 FLUSH_TOP, FLUSH_BOTTOM = (-87.3, -86.8), (-104.0, -103.0)
-BANDS = {"student": STUDENT_BANDS, "negbin": NEGBIN_BANDS, "hetero": HETERO_BANDS, "poisson": POISSON_BANDS}
+# Gamma (csrc/common.hpp gamma_term: e = e^-f, ye = y e, the term f + ye, the delta a (ye - 1)): the range of the log-mean f and, where the
+# targets are placed through it, of rho = y e^-f (None: targets drawn from the model, Gamma of shape a around c e^f, c in {2, 1/2})
+GAMMA_BANDS = {
+    "deep-": (-86.0, -20.0, None),            # e^-f to 2e37 times y down to 1e-37 (every target >= FLT_MIN), the product O(1); (a - 1) log y large in the constant
+    # e^-f down to 3e-30 times targets to 2^100, the documented ceiling on a target (include/tbnn.h): model-drawn targets at log-means to 85
+    # would reach ~1e37, which staging refuses since the ceiling; log-means from 68 to where e^-f leaves the normal range are `high-top`
+    "high": (40.0, 68.0, None),
+    "flush": (87.4, 104.0, (1.0, 2.0 ** 100)),          # e^-f denormal or 0: the term is f, the delta -a (here the third entry is the range of y itself)
+    "small": (-3.0, 3.0, (1e-30, 1e-3)),      # targets far below the mean: the delta tends to -a, the term to f -- what a clamp or floor on ye changes
+    "big": (-3.0, 3.0, (1e3, 1e20)),          # statistic and slabs dominated by ye: sums to ~1e25 in the fp32 slabs, still finite
+    # the top of the admitted target range (include/tbnn.h: 2^100) against the largest denormal e^-f: the hardware exp flushes it and the
+    # element loses rho = y e^-f up to 2^-26 -- inside every band; NumPy's fp32 arm keeps it
+    "flush-top": (87.4, 88.6, (2.0 ** 90, 2.0 ** 100)),          # (the sixth band: at the end, a dataset's seed holds the index)
+    # between `high` and `flush`: e^-f normal, down to 1.2e-38, times admitted targets, log-uniform over 2^60 .. 2^100: rho from ~1 down to
+    # 1e-20 -- the smallest normal e^-f against the largest targets staging admits
+    "high-top": (68.0, 87.3, (2.0 ** 60, 2.0 ** 100)),
+}
+Y_MAX = 2.0 ** 100                            # the ceiling on a Gamma target (include/tbnn.h)
+GAMMA_Y_BANDS = ("flush", "flush-top", "high-top")          # the bands whose third entry is the range of the targets themselves
+GAMMA_FLUSHED = ("flush", "flush-top")         # ... and those where e^-f lies below FLT_MIN on every element
+GAMMA_C = (2.0, 0.5)                          # the factor that takes model-drawn targets off the model's mean: E|delta| / |E delta| <= 3 for both
+BANDS = {"student": STUDENT_BANDS, "negbin": NEGBIN_BANDS, "hetero": HETERO_BANDS, "poisson": POISSON_BANDS, "gamma": GAMMA_BANDS}
 R_EDGE = (0.5, 30.0, 1e4, 1e6)                # the dispersions, spread over the cases as negbin_ref._DISPERSIONS is
 MIXES = ((1 / 3, 1 / 3, 1 / 3), (0.6, 0.2, 0.2), (0.2, 0.6, 0.2), (0.2, 0.2, 0.6), (0.8, 0.1, 0.1), (0.1, 0.8, 0.1), (0.1, 0.1, 0.8))
 MAX_COUNT = 1e8                               # the documented ceiling on a count
-WEIGHT_BAND = {"student": "switch", "negbin": "switch+", "hetero": "straddle", "poisson": "deep-"}
+WEIGHT_BAND = {"student": "switch", "negbin": "switch+", "hetero": "straddle", "poisson": "deep-", "gamma": "deep-"}
 
 
 def case_names(lik, traj=False):
@@ -79,7 +104,7 @@ def case_names(lik, traj=False):
 
 
 def case_of(lik, case):
-    """(dims, rows, act, prior, family, env) of the likelihood's own CASES (the Poisson module's shapes are student_ref's)"""
+    """(dims, rows, act, prior, family, env) of the likelihood's own CASES (the Poisson and Gamma modules' shapes are student_ref's)"""
     return tuple((hr.CASES if lik == "hetero" else sr.CASES)[case][:6])
 
 
@@ -87,8 +112,18 @@ def dispersion(case):
     return R_EDGE[list(nb.CASES).index(case) % 4]
 
 
+def gamma_f_range(band):
+    return GAMMA_BANDS[band][:2]
+
+
+def gamma_shape(case):
+    """gamma_ref.CASES' own: spread over 0.5, 2, 10 and 200"""
+    return gr.CASES[case][6]
+
+
 class Dataset:
-    """lik, case, band; spec, X, Y, theta, eta; par: nu and s (Student-t) or r (negative binomial); mix: the count mixture chosen"""
+    """lik, case, band; spec, X, Y, theta, eta; par: nu and s (Student-t), r (negative binomial) or a and the factors c per output (Gamma);
+    mix: the count mixture chosen"""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -113,11 +148,12 @@ def _pool(lik, case):
     return _POOL[key]
 
 
-LIK_CODE = {"student": o.LIK_STUDENT_T, "negbin": o.LIK_NEG_BINOMIAL, "hetero": o.LIK_HETERO_GAUSSIAN, "poisson": o.LIK_POISSON}
+LIK_CODE = {"student": o.LIK_STUDENT_T, "negbin": o.LIK_NEG_BINOMIAL, "hetero": o.LIK_HETERO_GAUSSIAN, "poisson": o.LIK_POISSON,
+            "gamma": o.LIK_GAMMA}
 
 
 def _spec(lik, dims, act, prior, s=1.0, df=0.0):
-    """s: the Student-t scale (the other likelihoods have none); df: nu (Student-t) or r (negative binomial)"""
+    """s: the Student-t scale (the other likelihoods have none); df: nu (Student-t), r (negative binomial) or a (Gamma)"""
     scale = {"fixed_sd": float(s)} if lik == "student" else {}
     return o.make_spec(dims, act, prior, LIK_CODE[lik], o.ACT_NONE, lik_df=float(df), **scale)
 
@@ -178,7 +214,68 @@ def _z64(spec, theta, X):
     return o.forward(spec, theta.astype(np.float64), X.astype(np.float64), np.float64)
 
 
+def _build_gamma(case, band, f_range=None, rho_range=None):
+    """a Gamma dataset: the log-means placed on the band's range, the targets drawn from the model around c e^f (rows whose targets leave
+    [FLT_MIN, 2^100] in fp32 are not taken), or placed through y or rho = y e^-f, log-uniform.  The keywords are for the dataset outside
+    the matrix (`measured`)."""
+    lik = "gamma"
+    dims, act, prior, Xp, theta0, eta0 = _pool(lik, case)
+    names = case_names(lik, traj=True)
+    bands = list(GAMMA_BANDS) + list(MEASURED)
+    i_ds = names.index(case) + bands.index(band)
+    rng = np.random.default_rng(1000 * LIKS.index(lik) + 37 * names.index(case) + bands.index(band))
+    d_out = dims[-1]
+    a = gamma_shape(case)
+    if f_range is None:
+        lo, hi, tr = GAMMA_BANDS[band]
+        y_range, rho_range = (tr, None) if band in GAMMA_Y_BANDS else (None, tr)
+    else:
+        (lo, hi), y_range = f_range, None
+    spec = _spec(lik, dims, act, prior, df=a)
+    theta, z, _amax = _placed(spec, theta0, Xp, [(lo, hi)] * d_out)
+    idx = np.flatnonzero(np.all((z >= lo) & (z <= hi), axis=0))
+    c = np.array([GAMMA_C[0] if _sign(i_ds, k) > 0 else GAMMA_C[1] for k in range(d_out)])
+    if y_range is None and rho_range is None:
+        # targets from the model over every candidate row; a row is taken if all of its targets are normal fp32 numbers up to the ceiling 2^100
+        Yp = rng.gamma(a, c[None, :] * np.exp(z[:, idx].T) / a).astype(np.float32)
+        idx = idx[np.all((Yp >= FLT_MIN) & (Yp <= Y_MAX), axis=1)]
+    assert idx.size >= N_ROWS, (lik, case, band, idx.size)
+    idx = np.sort(rng.permutation(idx)[:N_ROWS])
+    X = Xp[idx]
+    z = _z64(spec, theta, X)
+    if y_range is None and rho_range is None:
+        Y = rng.gamma(a, c[None, :] * np.exp(z.T) / a)
+        for _ in range(64):                    # (the second draw is independent of the first: a row may leave the range again)
+            out = ~np.all((Y.astype(np.float32) >= FLT_MIN) & (Y.astype(np.float32) <= Y_MAX), axis=1)
+            if not out.any():
+                break
+            Y[out] = rng.gamma(a, c[None, :] * np.exp(z.T[out]) / a)
+        assert not out.any(), (lik, case, band)
+    else:
+        rg = y_range if y_range is not None else rho_range
+        v = np.exp(rng.uniform(math.log(rg[0] * 1.001), math.log(rg[1] / 1.001), (N_ROWS, d_out)))
+        Y = v if y_range is not None else v * np.exp(z.T)
+    eta = np.asarray(eta0[:spec.n_hypers], dtype=np.float32)
+    return Dataset(lik=lik, case=case, band=band, spec=spec, X=X, Y=Y.astype(np.float32), theta=theta, eta=eta, par={"a": a, "c": c}, mix=None)
+
+
+# A Gamma dataset outside the matrix (keyword arguments of _build_gamma), on DENORMAL_CASES: fp32-denormal targets, which staging admits
+# (include/tbnn.h) -- f just above the overflow of e^-f, rho of O(1) on both sides of 1, so that y = rho e^f lies below FLT_MIN on almost every
+# element and a kernel that flushed a denormal target to 0 would turn rho into 0: tests/test_gpu_likelihood_edges.py test_denormal_targets
+MEASURED = {"denormal-targets": dict(f_range=(-88.5, -87.5), rho_range=(0.05, 1.5))}
+DENORMAL_CASES = ("fast3", "mid10", "lay_last")
+
+
+def measured(case, kind):
+    key = ("gamma", case, kind)
+    if key not in _DATASETS:
+        _DATASETS[key] = _build_gamma(case, kind, **MEASURED[kind])
+    return _DATASETS[key]
+
+
 def _build(lik, case, band):
+    if lik == "gamma":
+        return _build_gamma(case, band)
     dims, act, prior, Xp, theta0, eta0 = _pool(lik, case)
     names = case_names(lik, traj=True)
     i_ds = names.index(case) + list(BANDS[lik]).index(band)
@@ -316,6 +413,8 @@ def deltas(ds):
         return d, (y - z) ** 2 / (ds.par["nu"] * s * s), z
     if ds.lik == "negbin":
         return d, z - math.log(float(np.float32(ds.par["r"]))), z
+    if ds.lik == "gamma" and ds.band in ("small", "big"):          # rho = y e^-f (the log-means' own range: gamma_f_range)
+        return d, np.asarray(ds.Y, np.float64).reshape(z.shape[1], -1).T * np.exp(-z), z
     return d, (z[1:2] if ds.lik == "hetero" else z), z
 
 
@@ -326,6 +425,9 @@ def in_band(ds, q):
         return (q >= lo) & (q <= hi)
     if ds.lik == "poisson":
         lo, hi = POISSON_BANDS[ds.band]
+        return (q >= lo) & (q <= hi)
+    if ds.lik == "gamma":
+        lo, hi = GAMMA_BANDS[ds.band][2] if ds.band in ("small", "big") else GAMMA_BANDS[ds.band][:2]
         return (q >= lo) & (q <= hi)
     sign, lo, hi = BANDS[ds.lik][ds.band]
     if ds.band == "straddle":

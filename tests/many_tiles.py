@@ -26,10 +26,12 @@ import os
 
 import numpy as np
 
+import gamma_ref as gr
 import hetero_ref as hr
 import negbin_ref as nb
 import student_ref as sr
 import tbnn_oracle as o
+import test_gpu_gamma as gam
 import test_gpu_hetero as het
 import test_gpu_multiout as mo
 import test_gpu_negbin as neg
@@ -51,15 +53,15 @@ LOGP_BAND, GRAD_BAND, STAT_BAND, FLOOR = 4e-6, 1e-4, 4e-6, 1e-3
 
 # the likelihood's tag in a run-time kernel's name (csrc/fused_ops.hpp: fused_ops_shape)
 TAG = {"gaussian": None, "bernoulli": "bernoulli", "categorical": "categorical", "poisson": "poisson", "negbin": "neg-binomial",
-       "student": "student-t", "hetero": "hetero-gaussian"}
+       "student": "student-t", "hetero": "hetero-gaussian", "gamma": "gamma"}
 
 Case = collections.namedtuple("Case", "id family path lik weighted owner name rows grid zero_ragged")
 
 # owner -> (its table, its TBNN_JIT_SKIP per family or None when the table carries it, its jit_jobs)
 OWNERS = {"student": (sr.CASES, stu.FUSED, stu.jit_jobs), "negbin": (nb.CASES, neg.FUSED, neg.jit_jobs), "hetero": (hr.CASES, het.FUSED, het.jit_jobs),
-          "poisson": (poi.CASES, poi.FUSED, poi.jit_jobs), "rw": (rw.CASES, None, rw.jit_jobs), "multiout": (mo.CASES, mo.SKIP, None)}
+          "poisson": (poi.CASES, poi.FUSED, poi.jit_jobs), "gamma": (gr.CASES, gam.FUSED, gam.jit_jobs), "rw": (rw.CASES, None, rw.jit_jobs), "multiout": (mo.CASES, mo.SKIP, None)}
 FAMILY_AT = {"multiout": 5}                 # where an owner's table holds the kernel family (the others: 4)
-LIK_OF_OWNER = {"student": "student", "negbin": "negbin", "hetero": "hetero", "poisson": "poisson"}
+LIK_OF_OWNER = {"student": "student", "negbin": "negbin", "hetero": "hetero", "poisson": "poisson", "gamma": "gamma"}
 RW_LIK = {o.LIK_GAUSSIAN: "gaussian", o.LIK_BERNOULLI: "bernoulli", o.LIK_CATEGORICAL: "categorical"}
 SHAPES_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "jit_shapes.json")
 
@@ -69,25 +71,30 @@ CELLS = [
     ("fast3", "valu1", "rw", "fast3_configs1", True), ("fast3", "valu1", "rw", "fast3_bern", True), ("fast3", "valu1", "poisson", "fast3", True),
     ("fast3", "valu1", "student", "fast3", True), ("fast3", "valu1", "negbin", "fast3", True), ("fast3", "valu2", "hetero", "fast3", True),
     ("fast3", "valu2", "student", "fast3_two_outputs", False), ("fast3", "valu2", "poisson", "fast3_two_outputs", False),
+    ("fast3", "valu1", "gamma", "fast3", True), ("fast3", "valu2", "gamma", "fast3_two_outputs", False),
     # fast: k_fwd_bwd_fast
     ("fast", "valu2", "rw", "fast_gauss", True), ("fast", "valu2", "rw", "fast_bern", True), ("fast", "valu1", "poisson", "fast", False),
     ("fast", "valu1", "student", "fast", False), ("fast", "valu1", "negbin", "fast", False), ("fast", "valu2", "hetero", "fast", False),
+    ("fast", "valu1", "gamma", "fast", True),
     # mid, the VALU last layer of one or two outputs
     ("mid", "valu1", "student", "mid1", False), ("mid", "valu1", "negbin", "mid1", False), ("mid", "valu1", "poisson", "mid1", False),
-    ("mid", "valu2", "hetero", "mid", False), ("mid", "valu2", "rw", "mid_bern", True),
+    ("mid", "valu2", "hetero", "mid", False), ("mid", "valu2", "rw", "mid_bern", True), ("mid", "valu1", "gamma", "mid1", False),
     # mid, the MFMA output tile (10 outputs: Y in the D layout, cat_delta4)
     ("mid", "mfma10", "rw", "mid_gauss", True), ("mid", "mfma10", "rw", "mid_cat", True), ("mid", "mfma10", "multiout", "bern10", False),
     ("mid", "mfma10", "poisson", "mid10", False),
     ("mid", "mfma10", "student", "mid10", False), ("mid", "mfma10", "negbin", "mid10", False),
+    ("mid", "mfma10", "gamma", "mid10", True),          # (row weights with Y in the D layout under a log-link likelihood)
     # tall
     ("tall", "valu1", "rw", "tall_gauss", True), ("tall", "valu1", "poisson", "tall", False), ("tall", "mfma10", "rw", "tall_cat", True),
+    ("tall", "valu1", "gamma", "tall", False),
     # wide
     ("wide", "valu1", "student", "wide1", False), ("wide", "mfma10", "student", "wide10", False), ("wide", "valu1", "poisson", "wide1", False),
     ("wide", "mfma10", "poisson", "wide10", False), ("wide", "mfma10", "rw", "wide_gauss", True), ("wide", "mfma10", "rw", "wide_cat", True),
+    ("wide", "valu1", "gamma", "wide1", False), ("wide", "mfma10", "gamma", "wide10", False),
 ]
 # weighted cases that run once more with every row of the ragged tile at weight 0: (family, owner, name, rows)
 ZERO_RAGGED = [("fast3", "rw", "fast3_configs1", 381), ("fast3", "hetero", "fast3", 393), ("fast", "rw", "fast_bern", 381),
-               ("mid", "rw", "mid_gauss", 381), ("mid", "rw", "mid_bern", 333)]
+               ("mid", "rw", "mid_gauss", 381), ("mid", "rw", "mid_bern", 333), ("fast", "gamma", "fast", 381)]
 
 
 def lik_of(owner, name):
@@ -173,7 +180,7 @@ def _problem_of(owner, name, n):
         assert n <= X.shape[0]
         return spec, X[:n], Y[:n], theta, eta
     c = OWNERS[owner][0][name]
-    gen = {"student": sr.problem_of, "negbin": nb.problem_of, "hetero": hr.problem_of, "poisson": poi.problem_of}[owner]
+    gen = {"student": sr.problem_of, "negbin": nb.problem_of, "hetero": hr.problem_of, "poisson": poi.problem_of, "gamma": gr.problem_of}[owner]
     return gen(c[0], n, c[2], c[3], *c[6:])
 
 
@@ -220,7 +227,7 @@ def ref64(case, weighted=None):
 
 def statistic(spec, theta, eta, X, Y, dtype, w=None):
     """what tbnn_logp_grad returns as stat, from the oracle: sum w (y - f)^2 under the Gaussian likelihood, sum w log1p(u) under Student-t,
-    the (weighted) log-likelihood with its constant under the others"""
+    the (weighted) log-likelihood with its constant under the others (Gamma: factor and constant included, as its module judges it)"""
     f = o.forward(spec, np.asarray(theta, dtype), np.asarray(X, dtype), dtype)
     if spec.likelihood == o.LIK_GAUSSIAN:
         r2 = ((np.asarray(Y, dtype).reshape(f.shape[1], -1).T - f) ** 2).sum(axis=0)
@@ -231,8 +238,9 @@ def statistic(spec, theta, eta, X, Y, dtype, w=None):
 
 
 def stat_gap(case, lp, st, lp64, st64):
-    """(error, band) of a statistic, by the rule of the likelihood's own module: Student-t, negative binomial and heteroscedastic 4e-6 of
-    the statistic (tests/test_gpu_student.py, test_gpu_negbin.py, test_gpu_hetero.py); Poisson: logp - stat, the priors, within 4e-6 of
+    """(error, band) of a statistic, by the rule of the likelihood's own module: Student-t, negative binomial, heteroscedastic and Gamma
+    4e-6 of the statistic (tests/test_gpu_student.py, test_gpu_negbin.py, test_gpu_hetero.py, test_gpu_gamma.py: the data term with its
+    constant); Poisson: logp - stat, the priors, within 4e-6 of
     max(|logp|, 1) (tests/test_gpu_poisson.py: the statistic carries the fp64 constant); Gaussian, Bernoulli and categorical, whose
     modules do not judge it: 4e-6 of the statistic, as the first three"""
     if case.lik == "poisson":

@@ -50,7 +50,8 @@ def job(spec, lik=LIK, skip="", weighted=False):
 
 
 def jit_jobs():
-    """the run-time instantiations this module asks for (jit.prebuild's job format): 12 libraries"""
+    """the run-time instantiations this module asks for (jit.prebuild's job format): 14 libraries, two of them -- the weighted fast and
+    mid10 ones -- for tests/many_tiles.py alone"""
     jobs = []
     for dims, _n, act, prior, fam, _env, _a in gr.CASES.values():
         if fam in FUSED:
@@ -59,6 +60,9 @@ def jit_jobs():
             jobs.append(job(gr.make_spec(dims, act, prior)))
     c = gr.CASES["fast3"]
     jobs.append(job(gr.make_spec(c[0], c[2], c[3]), weighted=True))
+    for name in ("fast", "mid10"):
+        c = gr.CASES[name]
+        jobs.append(job(gr.make_spec(c[0], c[2], c[3]), skip=FUSED[c[4]], weighted=True))
     jobs.append(job(gr.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY)))
     jobs.append(job(gr.make_spec(NET, o.ACT_TANH, o.PRIOR_CAUCHY), lik=o.LIK_FIXED_GAUSSIAN))      # the predictors' forward chains
     return [j for i, j in enumerate(jobs) if j not in jobs[:i]]
@@ -304,6 +308,22 @@ def test_refusals(native, monkeypatch):
         Yb[7, 1] = bad
         with pytest.raises(native.TbnnError, match="finite and > 0"):
             ch.set_data(X, Yb)
+    after = ch.logp_grad(theta, eta)
+    assert after[0] == before[0] and np.array_equal(after[1], before[1])
+    # the ceiling on a target, 2^100 (include/tbnn.h): the next fp32 number above it is refused with a message that names the ceiling, and
+    # the handle keeps its rows; exactly 2^100 is staged
+    Yb = Y.copy()
+    Yb[7, 1] = np.float32(2.0 ** 100) * (np.float32(1) + np.float32(2.0 ** -23))
+    assert Yb[7, 1] > np.float32(2.0 ** 100) and np.isfinite(Yb[7, 1])
+    with pytest.raises(native.TbnnError, match=r"at most 2\^100"):
+        ch.set_data(X, Yb)
+    after = ch.logp_grad(theta, eta)
+    assert after[0] == before[0] and np.array_equal(after[1], before[1])
+    Yb[7, 1] = np.float32(2.0 ** 100)
+    ch.set_data(X, Yb)
+    top = ch.logp_grad(theta, eta)
+    assert np.isfinite(top[0]) and np.all(np.isfinite(top[1])) and top[0] != before[0]
+    ch.set_data(X, Y)
     after = ch.logp_grad(theta, eta)
     assert after[0] == before[0] and np.array_equal(after[1], before[1])
     with pytest.raises(native.TbnnError):

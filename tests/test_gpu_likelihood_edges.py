@@ -1,11 +1,12 @@
-"""GPU: the Poisson, Student-t, negative-binomial and heteroscedastic Gaussian likelihoods at the edges of their element arithmetic
-(csrc/common.hpp log1p_fast, negbin_term, hetero_pair; kernels_fast.hpp lik_delta's Poisson branch), on every kernel family, against the
-fp64 arms of the oracle.  The likelihood modules (test_gpu_poisson / _student / _negbin /
-_hetero) hold one well-conditioned problem per family and check sums over 500 .. 3,000 rows; here every dataset of tests/lik_edge_cases.py
+"""GPU: the Poisson, Student-t, negative-binomial, heteroscedastic Gaussian and Gamma likelihoods at the edges of their element arithmetic
+(csrc/common.hpp log1p_fast, negbin_term, hetero_pair, gamma_term; kernels_fast.hpp lik_delta's Poisson branch), on every kernel family,
+against the fp64 arms of the oracle.  The likelihood modules (test_gpu_poisson / _student / _negbin /
+_hetero / _gamma) hold one well-conditioned problem per family and check sums over 500 .. 3,000 rows; here every dataset of tests/lik_edge_cases.py
 holds ONE band of the quantity the element code branches on, on all of its 301 rows, so a formula that is wrong on one regime is not
 diluted: log1p_fast's series and its switch at u = 1/4, negbin_term around t = 0, at |t| = ln 4, where e^-|t| passes through the denormals
 and far past the range of exp, hetero_pair just inside, just outside and across the clip within one 16-row tile, the Poisson term with
-the rate flushed to 0, around FLT_MIN and with e^f to 1e34.  The shapes, activations, priors, TBNN_JIT_SKIP strings and environments are the likelihood
+the rate flushed to 0, around FLT_MIN and with e^f to 1e34, the Gamma term with e^-f to 2e37 against targets down to 1e-37, with e^-f
+denormal or 0, and with y e^-f from 1e-30 to 1e20.  The shapes, activations, priors, TBNN_JIT_SKIP strings and environments are the likelihood
 modules' own CASES (their make_chain builds the chains and asserts the kernel names), so the run-time libraries are the ones they compile.
 
 (1) test_band: per (likelihood, case, band) logp_grad at the dataset's state -- value, statistic and gradient per tensor against fp64 --
@@ -14,8 +15,10 @@ modules' own CASES (their make_chain builds the chains and asserts the kernel na
     trajectory kernel, both decisions against the oracle's weight_step in fp64: never rejected for a non-finite statistic.
 (3) test_rejected_where_promised: a momentum that carries the proposal to where the fp32 statistic is not finite (Student-t: u = inf or a
     non-finite f; heteroscedastic Gaussian: r^2 u past fp32 or a NaN g) is rejected whatever log u, and the chain keeps its state bit for bit.
+    Gamma: a proposal whose last layer is the dataset's rescaled until log-means lie below -88.8, where e^-f is inf.
     A NaN in a kernel is an ordinary value: nothing here faults.
 (4) test_row_weights_at_an_edge: weights all 1 give the unweighted bits, integer weights the fp64 reference with w.
+(5) test_denormal_targets: Gamma targets below FLT_MIN, which staging admits, on three families at the project's bands.
 
 Bands (lik_edge_cases.arms): the project's -- value and statistic 4e-6 relative, gradient 1e-4 of each tensor's largest entry (floor
 1e-3), forward 1e-4 -- wherever tests/test_likelihood_edges_host.py shows the reference's fp32 arm inside HALF of them; otherwise
@@ -24,13 +27,15 @@ alone.  The hardware exp flushes denormal results where NumPy's does not: at dee
 
 Measured on an MI355X (NOTES.md has the table per likelihood and band): the device within 0.63 of its band everywhere (`hetero mid
 straddle`, value 2.5e-6), Poisson `high` next at 0.48 (value 1.9e-6); every other band below 0.35 (Poisson `flush`, the statistic 1.4e-6).  251 tests in 10.9 s with the
-run-time libraries built."""
+run-time libraries built.  Gamma, added since (NOTES.md): `deep-` on wide10 at 0.78 of its widened band (value 5.7e-5, a = 200), `high` at
+0.32, every other Gamma band and the denormal targets below 0.08; 338 tests."""
 import numpy as np
 import pytest
 
 import lik_edge_cases as E
 import negbin_ref as nb
 import tbnn_oracle as o
+import test_gpu_gamma as tgg
 import test_gpu_hetero as tgh
 import test_gpu_negbin as tgn
 import test_gpu_poisson as tgp
@@ -40,15 +45,16 @@ from test_gpu_freerun import SEED
 
 pytestmark = pytest.mark.gpu
 
-MODULE = {"student": tgs, "negbin": tgn, "hetero": tgh, "poisson": tgp}
+MODULE = {"student": tgs, "negbin": tgn, "hetero": tgh, "poisson": tgp, "gamma": tgg}
+TRAJ_LIKS = ("negbin", "gamma")           # the log-link likelihoods whose transitions here run on the trajectory kernel too
 FUSED = tgs.FUSED
 
 
 def jit_jobs(lik):
     """the run-time instantiations of one likelihood's cases here (the likelihood module's own: same layers, likelihood and skip), the
-    weighted fast3 library and, for the negative binomial, the trajectory case"""
+    weighted fast3 library and, for the negative binomial and Gamma, the trajectory case"""
     mod, jobs = MODULE[lik], []
-    for case in E.case_names(lik, traj=lik == "negbin"):
+    for case in E.case_names(lik, traj=lik in TRAJ_LIKS):
         dims, _n, act, prior, fam, _env = E.case_of(lik, case)
         if fam in FUSED or fam == "traj":
             jobs.append(mod.job(E._spec(lik, dims, act, prior), skip=FUSED.get(fam, "")))
@@ -72,10 +78,15 @@ def test_cases_are_the_likelihood_modules_own():
     for case in E.CASE_NAMES:
         assert tuple(tgp.CASES[case][:6]) == E.case_of("poisson", case) and tuple(nb.CASES[case][:6]) == E.case_of("negbin", case)
     assert tuple(tgp.TRAJ) == E.case_of("negbin", E.TRAJ)[:4]
+    for case in E.CASE_NAMES + (E.TRAJ,):
+        assert tuple(tgg.gr.CASES[case][:6]) == E.case_of("gamma", case) and tgg.gr.CASES[case][6] == E.gamma_shape(case)
+    assert tgg.FUSED == FUSED and all(j in tgg.jit_jobs() for j in jit_jobs("gamma"))
 
 
 def make(native, monkeypatch, ds, **kw):
     """the likelihood module's own make_chain: the case's family, environment and skip string, the kernel name asserted"""
+    if ds.lik == "gamma":          # (its make_chain takes the shape: the call shape of the Gamma modules)
+        return tgg.make_chain(native, monkeypatch, ds.case, ds.spec, ds.par["a"], **kw)
     return MODULE[ds.lik].make_chain(native, monkeypatch, ds.case, ds.spec, **kw)
 
 
@@ -119,6 +130,21 @@ def test_band(native, monkeypatch, key):
     assert f.shape == f64.shape and np.all(np.isfinite(f)), f"{ds.tag}: forward not finite"
     err = np.abs(f - f64) / np.maximum(1.0, np.abs(f64))
     assert err.max() <= 1e-4, f"{ds.tag}: forward {err.max():.3e} of max(1, |f64|)"
+
+
+@pytest.mark.parametrize("case", E.DENORMAL_CASES)
+def test_denormal_targets(native, monkeypatch, case):
+    """include/tbnn.h admits every target > 0, the fp32 denormals too: a dataset whose targets lie below FLT_MIN (lik_edge_cases.MEASURED) is
+    staged, and value, statistic and gradient meet the project's bands -- a kernel or a staging constant that took a denormal target for 0
+    would turn rho = y e^-f of O(1) into 0 (or log y into -inf)"""
+    ds = E.measured(case, "denormal-targets")
+    ch = make(native, monkeypatch, ds)
+    try:
+        ch.set_data(ds.X, ds.Y)
+        lp, g, st, _f = launch3(ch, ds)
+    finally:
+        ch.close()
+    judge(ds, lp, g, st)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- finite where promised
@@ -171,6 +197,7 @@ def test_negbin_finite_where_promised(native, monkeypatch, case, band):
 
 # ---------------------------------------------------------------------------------------------------------------------- rejected where promised
 REJECT = [("student", c) for c in ("fast3", "mid10", "lay_last", "generic")] + [("hetero", c) for c in ("fast3", "mid", "lay_last", "generic")]
+REJECT += [("gamma", c) for c in ("fast3", E.TRAJ, "mid10", "lay_last", "generic")]          # (rejected_gamma, below)
 EPS_FAR, P_FAR = 1e4, 1e16          # theta moves by ~1e20 per coordinate; the kinetic energy, sum p^2 ~ 1e32 P, stays inside fp32
 
 
@@ -178,7 +205,10 @@ EPS_FAR, P_FAR = 1e4, 1e16          # theta moves by ~1e20 per coordinate; the k
 def test_rejected_where_promised(native, monkeypatch, lik, case):
     """a momentum that carries the one-step proposal to outputs ~1e20 and beyond: on the CPU, the fp32 arm's statistic at the fp64
     proposal is not finite (Student-t: r^2 k = inf, or f itself past fp32; heteroscedastic Gaussian: r^2 u = inf on a row whose g lies
-    below the clip, or a non-finite f, g).  The kernels' statistic is then inf or NaN -- ordinary values -- and k_energy rejects"""
+    below the clip, or a non-finite f, g).  The kernels' statistic is then inf or NaN -- ordinary values -- and k_energy rejects.
+    Gamma: rejected_gamma"""
+    if lik == "gamma":
+        return rejected_gamma(native, monkeypatch, case)
     ds = E.dataset(lik, case, "switch" if lik == "student" else "inside")
     rng = np.random.default_rng(8)
     p0 = (P_FAR * rng.standard_normal(ds.spec.n_params)).astype(np.float32)
@@ -200,6 +230,61 @@ def test_rejected_where_promised(native, monkeypatch, lik, case):
             after = ch.logp_grad()
             assert after[0] == before[0] and np.array_equal(after[1], before[1]) and np.all(np.isfinite(after[1])), ds.tag
         ok = ch.hmc_step(3e-5, 3, p0=(p0 / P_FAR).astype(np.float32), log_u=-1e30)          # and it goes on from there
+        assert ok["accepted"] == 1 and np.isfinite(ok["log_accept_ratio"]) and np.isfinite(ok["logp_new"]) and np.all(np.isfinite(ch.get_state()))
+    finally:
+        ch.close()
+
+
+GAMMA_FAR, GAMMA_EPS = 1.5, 1e-3          # the last layer's factor: log-means of [-86, -20] become [-129, -30]; the step of the injected proposal
+
+
+def rejected_gamma(native, monkeypatch, case):
+    """include/tbnn.h: a log-mean below the fp32 range of e^-f gives a statistic that is not finite, and the proposal is rejected.  The
+    `deep-` dataset with its last layer times 1.5 has log-means below -88.8 on some rows: logp_grad there is not finite (an ordinary
+    value: nothing faults), and a one-step transition whose injected momentum carries the chain from the dataset's state to that proposal
+    is rejected whatever log u; the state, the hypers and the next logp_grad are bit for bit what they were.  Per-step kernels of four
+    families and the one-launch trajectory kernel."""
+    ds = E.dataset("gamma", case, "deep-")
+    a, spec = ds.par["a"], ds.spec
+    ow, _ob = spec.offsets()[-1]
+    far = ds.theta.copy()
+    far[ow:] *= np.float32(GAMMA_FAR)
+    g64 = E.arms(ds)["g64"]
+    # the momentum of ONE leapfrog step of size eps from theta to `far`: q1 = theta + eps (p0 + eps / 2 g)
+    p0 = ((far.astype(np.float64) - ds.theta) / GAMMA_EPS - 0.5 * GAMMA_EPS * g64).astype(np.float32)
+    q1 = ds.theta.astype(np.float64) + GAMMA_EPS * (p0.astype(np.float64) + 0.5 * GAMMA_EPS * g64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for q in (far.astype(np.float64), q1):
+            f1 = o.forward(spec, q, ds.X.astype(np.float64), np.float64)
+            assert (f1 < -88.8).sum() >= 8 and np.all(np.isfinite(f1)), (ds.tag, f1.min())
+            assert not np.isfinite(o.data_statistic(spec, ds.eta, f1.astype(np.float32), ds.Y, np.float32)), ds.tag
+    assert float(np.sum(p0.astype(np.float64) ** 2)) < E.FLT_MAX / 16.0            # the kinetic energy is no reason to reject
+    if case == E.TRAJ:
+        monkeypatch.setenv("TBNN_TRAJ", "1")
+        monkeypatch.setenv("TBNN_JIT_SKIP", "")
+        ch = native.Chain(layers_of(spec), likelihood=o.LIK_GAMMA, lik_df=a, jit=True, seed=SEED)
+        assert ch.kernel_name.startswith("jit-fast3<") and ",gamma;" in ch.kernel_name, ch.kernel_name
+        path = "trajectory"
+    else:
+        monkeypatch.setenv("TBNN_TRAJ", "0")
+        ch = make(native, monkeypatch, ds, seed=SEED)
+        path = "per-step"
+    try:
+        ch.set_data(ds.X, ds.Y)
+        lp_far, _g_far, st_far = ch.logp_grad(far, ds.eta)
+        assert not np.isfinite(lp_far) and not np.isfinite(st_far), (ds.tag, lp_far, st_far)
+        ch.set_state(ds.theta); ch.set_hypers(ds.eta)
+        before = ch.logp_grad()
+        assert np.isfinite(before[0]) and np.all(np.isfinite(before[1]))
+        for log_u in (-1e30, 0.0):
+            out = ch.hmc_step(GAMMA_EPS, 1, p0=p0, log_u=log_u)
+            assert ch.last_transition_path == path, ch.last_transition_path
+            assert out["accepted"] == 0 and out["log_accept_ratio"] == -np.inf, (ds.tag, log_u, out["accepted"], out["log_accept_ratio"])
+            assert np.array_equal(ch.get_state(), ds.theta) and np.array_equal(ch.get_hypers(), ds.eta), ds.tag
+            after = ch.logp_grad()
+            assert after[0] == before[0] and np.array_equal(after[1], before[1]) and np.all(np.isfinite(after[1])), ds.tag
+        small = (1e-3 * np.random.default_rng(8).standard_normal(spec.n_params)).astype(np.float32)
+        ok = ch.hmc_step(1e-7, 3, p0=small, log_u=-1e30)          # and it goes on from there
         assert ok["accepted"] == 1 and np.isfinite(ok["log_accept_ratio"]) and np.isfinite(ok["logp_new"]) and np.all(np.isfinite(ch.get_state()))
     finally:
         ch.close()

@@ -178,7 +178,8 @@ def test_two_chain_group_is_the_solo_chains(native, monkeypatch):
 
 
 @pytest.mark.parametrize("cid", ["fast3-valu1-student-weighted-381rows", "fast-valu2-gaussian-weighted-381rows",
-                                 "mid-mfma10-categorical-weighted-381rows", "tall-valu1-gaussian-weighted-1007rows"])
+                                 "mid-mfma10-categorical-weighted-381rows", "tall-valu1-gaussian-weighted-1007rows",
+                                 "fast-valu1-gamma-weighted-381rows", "mid-mfma10-gamma-weighted-381rows"])
 def test_default_grid_and_small_grid(native, monkeypatch, cid):
     """the same rows and weights on the launch the library sizes itself and on the small one: both inside the bands, and the second one
     really small"""

@@ -13,12 +13,18 @@ Mutation (g), max(mu, FLT_MIN) in the Poisson term, moves one element by at most
 whose metrics have floors (1 and 1e-3), nothing can show it, and `deep-` and `high` do not.  The statistic is judged relative to itself, so
 the Poisson band `flush` (lik_edge_cases.FLUSH_TOP / FLUSH_BOTTOM) shows it: every target 0, a third of the elements just above FLT_MIN
 carrying the sum (~1e-36), the rest at the bottom of the denormals, where flushing them or not moves the sum by 1.5e-7 of itself and
-max(mu, FLT_MIN) doubles it (gap / band 3e5)."""
+max(mu, FLT_MIN) doubles it (gap / band 3e5).
+
+Gamma (seven bands, NOTES.md has the fp32 arm's gaps per band): occupancy, targets inside [FLT_MIN, 2^100] (the staging ceiling), the
+conditioning cap, no overflow in the fp64 arm; mutations (h) .. (m), each caught by EVERY case of the bands named for it (GAMMA_NAMED) or
+recorded as invisible with the reason (INVISIBLE): (l), the hardware's own flush of e^-f, must stay invisible at `flush` and `flush-top`.
+Three `deep-` datasets with a = 200 take widened value and statistic bands (-a f against (a - 1) log y cancels: NOTES.md)."""
 import math
 
 import numpy as np
 import pytest
 
+import gamma_ref as gr
 import hetero_ref as hr
 import lik_edge_cases as E
 import negbin_ref as nb
@@ -26,7 +32,7 @@ import student_ref as sr
 import tbnn_oracle as o
 
 FLT_MIN = np.float32(np.finfo(np.float32).tiny)
-KEYS = E.all_keys() + [("negbin", E.TRAJ, "far+"), ("negbin", E.TRAJ, "deep-")]
+KEYS = E.all_keys() + [("negbin", E.TRAJ, "far+"), ("negbin", E.TRAJ, "deep-"), ("gamma", E.TRAJ, "deep-")]
 
 
 @pytest.mark.parametrize("key", KEYS, ids=lambda k: "-".join(k))
@@ -71,11 +77,47 @@ def test_dataset_holds_its_band_and_is_well_conditioned(key):
             assert all(t.any() and not t.all() for t in (top[0, i:i + 16] for i in range(0, n, 16))), "both groups in every 16-row tile"
     if ds.lik == "poisson" and ds.band == "deep-":
         assert np.all(ds.Y[np.arange(n) % 4 != 3] == 0) and np.all((ds.Y[3::4] >= 1) & (ds.Y[3::4] <= 3))
+    if ds.lik == "gamma":
+        lo, hi = E.gamma_f_range(ds.band)
+        assert np.all((z >= lo) & (z <= hi)), (ds.tag, z.min(), z.max())                      # the log-means, whatever the band is placed through
+        assert ds.Y.shape == (n, d_out) and np.all(ds.Y >= FLT_MIN) and np.all(ds.Y <= E.Y_MAX)      # normal fp32 numbers the staging call admits
+        assert ds.par["a"] == gr.CASES[ds.case][6] == ds.spec.lik_df and set(ds.par["c"]) <= set(E.GAMMA_C)
+        with np.errstate(over="raise", invalid="raise", divide="raise"):                       # no overflow in the fp64 arm
+            t64, d64 = o.gamma_elementwise(z, ds.Y, ds.par["a"], np.float64)
+        assert np.all(np.isfinite(t64)) and np.all(np.isfinite(d64)) and np.all(np.isfinite(o.gamma_terms(z, ds.Y, ds.par["a"])))
+        rho = ds.Y.astype(np.float64).T * np.exp(-z)
+        if ds.band in ("deep-", "high"):          # targets from the model around c e^f: rho is O(1), no row decides the sum
+            assert 0.2 <= np.median(rho) <= 4.0 and rho.max() <= 64.0, (ds.tag, np.median(rho), rho.max())
+        if ds.band in E.GAMMA_FLUSHED:            # e^-f below FLT_MIN on every element, and what it multiplies at most 2^100
+            assert np.all(np.exp(-z) < float(FLT_MIN)) and ds.Y.max() <= 2.0 ** 100 and rho.max() < 2.0 ** -26
+        if ds.band == "high-top":                 # e^-f a normal number on every element, against targets up to the ceiling
+            assert np.all(np.exp(-z) > float(FLT_MIN)) and ds.Y.max() <= 2.0 ** 100 and rho.max() > 1e-2 and rho.min() < 1e-15
+        if ds.band in ("small", "big") + E.GAMMA_FLUSHED:
+            assert np.all(d < 0) or np.all(d > 0)                                              # one-signed by construction
+
+
+@pytest.mark.parametrize("case", E.DENORMAL_CASES)
+def test_denormal_target_dataset(case):
+    """the dataset of test_gpu_likelihood_edges.test_denormal_targets: nearly every target an fp32 denormal, none 0, e^-f below its overflow,
+    rho on both sides of 1, well conditioned, and the fp32 arm inside half of the project's bands"""
+    ds = E.measured(case, "denormal-targets")
+    d, _q, z = E.deltas(ds)
+    a = E.arms(ds)
+    rho = ds.Y.astype(np.float64).T * np.exp(-z)
+    print(f"[edges] {ds.tag}: targets [{ds.Y.min():.3g}, {ds.Y.max():.3g}], {float((ds.Y < FLT_MIN).mean()):.3f} of them denormal, f [{z.min():.2f}, {z.max():.2f}], "
+          f"rho [{rho.min():.3g}, {rho.max():.3g}]; fp32 arm: value gap {a['gv']:.3e}, gradient gaps max {max(a['gg']):.3e}, statistic gap {a['gs']:.3e}")
+    assert ds.Y.dtype == np.float32 and np.all(ds.Y > 0) and (ds.Y < FLT_MIN).mean() >= 0.99
+    assert np.all((z >= -88.5) & (z <= -87.5)) and rho.min() < 0.1 and rho.max() > 1.2 and np.all(E.ratio(d) <= 4.0)
+    assert np.isfinite(a["lp32"]) and np.all(np.isfinite(a["g32"]))
+    assert a["gv"] <= 2e-6 and a["gs"] <= 2e-6 and max(a["gg"]) <= 5e-5 and (a["bv"], a["bs"], max(a["bg"])) == (4e-6, 4e-6, 1e-4)
 
 
 def test_parametrisation_covers_every_case_and_band():
     keys = E.all_keys()
-    assert len(keys) == 11 * 4 + 11 * 9 + 9 * 6 + 11 * 3
+    assert len(keys) == 11 * 4 + 11 * 9 + 9 * 6 + 11 * 3 + 11 * len(E.GAMMA_BANDS) and len(E.GAMMA_BANDS) >= 5
+    assert E.LIKS[:4] == ("student", "negbin", "hetero", "poisson")          # a dataset's seed holds the index: the order stays
+    assert [E.gamma_shape(c) for c in E.CASE_NAMES[:4]] == [0.5, 10.0, 200.0, 0.5] and {E.gamma_shape(c) for c in E.CASE_NAMES} == {0.5, 2.0, 10.0, 200.0}
+    assert all(gr.CASES[c][:6] == sr.CASES[c][:6] for c in E.CASE_NAMES + (E.TRAJ,))
     assert [E.dispersion(c) for c in E.CASE_NAMES[:4]] == [0.5, 1e4, 1e6, 0.5] and {E.dispersion(c) for c in E.CASE_NAMES} == set(E.R_EDGE)
     for lik in E.LIKS:
         for case in E.case_names(lik):
@@ -139,6 +181,18 @@ def elem32(ds, f, mut=None):
             p, q = np.where(pos, rc, s), np.where(pos, s, rc)
             nlp = -np.log(p) if mut == "d" else np.maximum(-t, np.float32(0)) + l
             return (-(y * nlp + r32 * nlq)).astype(np.float32), (y * q - r32 * p).astype(np.float32)
+        if ds.lik == "gamma":
+            a32 = np.float32(ds.par["a"])
+            e = np.exp(-f).astype(np.float32)
+            if mut == "h":
+                e = np.minimum(e, np.float32(1e30))
+            if mut == "l":
+                e = np.where(e < FLT_MIN, np.float32(0), e)
+            ye = (y * e).astype(np.float32)
+            if mut in ("i", "m"):
+                ye = np.maximum(ye, np.float32(1e-6 if mut == "i" else 1e-2))
+            d = (a32 * ye - one) if mut == "j" else a32 * (ye - one)
+            return (ye if mut == "k" else f + ye).astype(np.float32), d.astype(np.float32)
         mu = np.exp(f)
         if mut == "g":
             mu = np.maximum(mu, FLT_MIN)
@@ -147,7 +201,7 @@ def elem32(ds, f, mut=None):
 
 def coefficient(ds):
     """d(log posterior) / d(sum of elem32's terms)"""
-    return -0.5 * (ds.par["nu"] + 1.0) if ds.lik == "student" else 1.0
+    return -0.5 * (ds.par["nu"] + 1.0) if ds.lik == "student" else -float(ds.par["a"]) if ds.lik == "gamma" else 1.0
 
 
 def value_grad32(ds, a32, mut=None):
@@ -161,7 +215,8 @@ def value_grad32(ds, a32, mut=None):
     t, d_a = elem32(ds, f, mut)
     with np.errstate(over="ignore", invalid="ignore"):
         moved = float(np.sum(t.astype(np.float64))) - float(np.sum(t0.astype(np.float64)))
-        lp, st = a32["lp32"] + coefficient(ds) * moved, a32["st32"] + moved
+        # (the statistic of `arms`: Student-t's is the sum of the terms itself, the others' the data term -- Gamma's with its factor -a)
+        lp, st = a32["lp32"] + coefficient(ds) * moved, a32["st32"] + (moved if ds.lik == "student" else coefficient(ds) * moved)
         grads = [None] * len(spec.layers)
         for i in range(len(spec.layers) - 1, -1, -1):
             l = spec.layers[i]
@@ -177,7 +232,8 @@ def value_grad32(ds, a32, mut=None):
 
 
 @pytest.mark.parametrize("key", [("student", "fast3", "switch"), ("student", "mid10", "small"), ("negbin", "wide10", "deep-"), ("negbin", "generic", "zero"),
-                                 ("hetero", "fast", "straddle"), ("hetero", "lay_tail", "near-"), ("poisson", "tall", "high"), ("poisson", "mid10", "deep-")],
+                                 ("hetero", "fast", "straddle"), ("hetero", "lay_tail", "near-"), ("poisson", "tall", "high"), ("poisson", "mid10", "deep-"),
+                                 ("gamma", "fast3", "deep-"), ("gamma", "mid10", "flush"), ("gamma", "wide10", "big"), ("gamma", "lay_tail", "small")],
                          ids=lambda k: "-".join(k))
 def test_the_copy_is_the_reference_arm(key):
     """unmutated, value_grad32 gives the reference's fp32 arm: the gradient bit for bit"""
@@ -196,7 +252,23 @@ MUTATIONS = {
     "e": (("hetero",), "hetero_pair uses dg = q - 1 outside the clip too"),
     "f": (("hetero",), "hetero_pair clips g but computes u from the unclipped g"),
     "g": (("poisson",), "Poisson's mu becomes max(mu, FLT_MIN)"),
+    "h": (("gamma",), "gamma_term puts a ceiling on e^-f: min(e, 1e30)"),
+    "i": (("gamma",), "gamma_term puts a floor under y e^-f: max(ye, 1e-6)"),
+    "j": (("gamma",), "the Gamma delta becomes a ye - 1 for a (ye - 1)"),
+    "k": (("gamma",), "the Gamma term loses f"),
+    "l": (("gamma",), "e^-f flushed to 0 below FLT_MIN (the hardware exp's own behaviour)"),
+    "m": (("gamma",), "gamma_term puts a floor under y e^-f: max(ye, 1e-2)"),
 }
+# the Gamma mutations and the bands named for them: EVERY case of a named band must catch the mutation; (l) is what the hardware does, and
+# the band `flush` must NOT catch it on any case -- the band admits the hardware
+GAMMA_NAMED = {"h": ("deep-",), "i": (), "j": tuple(b for b in E.GAMMA_BANDS if b != "big"), "k": ("high", "flush", "flush-top", "high-top"), "l": (), "m": ("small",)}
+# INVISIBLE, with the reason.  (i), a floor of 1e-6 under ye: it moves one delta by at most 1e-6 a, that is 1e-6 of the deltas' own size
+# (|delta| >= a (1 - 1e-3) at `small`), and one term by 1e-6 against |f| of O(1): a hundredth of the gradient band (1e-4 of a tensor's largest
+# entry) and a quarter of the value band at the very most -- no band of the suite's metrics can show a change of 1e-6 relative, at `small` or
+# anywhere.  The same floor at 1e-2, (m), is 1e-2 relative and every `small` dataset catches it: a floor shows once it reaches the bands.
+# (l), the flush: invisible by design (above).  (j) is named for every band but `big`: there the deltas are a rho with rho from 1e3 to 1e20, the
+# largest entries carry every tensor's norm, and the a - 1 that (j) adds to each is below 1e-17 of them.
+INVISIBLE = ("i", "l")
 # the bands the GPU builds with (a), (c), (e) in csrc/common.hpp must fail on: what this module predicts (printed; NOTES.md has the runs)
 
 
@@ -218,10 +290,10 @@ def ordinary(lik):
             spec, X, Y, theta, eta = tp.problem(name)
             out[name] = E.Dataset(lik=lik, case=name, band="CASES", spec=spec, X=X, Y=Y, theta=theta, eta=eta, par={}, mix=None)
         return out
-    mod = {"student": sr, "negbin": nb, "hetero": hr}[lik]
+    mod = {"student": sr, "negbin": nb, "hetero": hr, "gamma": gr}[lik]
     for name in mod.CASES:
-        spec, X, Y, theta, eta = mod.problem(name)
-        par = {"nu": spec.lik_df, "s": spec.fixed_sd} if lik == "student" else {"r": spec.lik_df} if lik == "negbin" else {}
+        spec, X, Y, theta, eta = mod.problem(name)[:5]
+        par = {"nu": spec.lik_df, "s": spec.fixed_sd} if lik == "student" else {"r": spec.lik_df} if lik == "negbin" else {"a": spec.lik_df} if lik == "gamma" else {}
         out[name] = E.Dataset(lik=lik, case=name, band="CASES", spec=spec, X=X, Y=Y, theta=theta, eta=eta, par=par, mix=None)
     return out
 
@@ -250,6 +322,12 @@ ORDINARY_CATCHES = {
     "e": {"hetero": set()},
     "f": {"hetero": set()},
     "g": {"poisson": set()},
+    "h": {"gamma": set()},
+    "i": {"gamma": set()},
+    "j": {"gamma": set(gr.CASES) - {"mid10"}},       # (a delta off by a - 1 on every element; mid10, a = 0.5 on ten outputs, stays inside)
+    "k": {"gamma": set(gr.CASES)},
+    "l": {"gamma": set()},
+    "m": {"gamma": {"fast3", "fast3_two_outputs", "lay_last", "tall", "traj"}},          # (shapes 0.5 and 2: targets below a hundredth of the mean)
 }
 
 
@@ -271,7 +349,13 @@ def test_mutation_is_caught(mut):
     print(f"[edges] mutation ({mut}) {what}: caught by {len(caught)} datasets, bands "
           + ", ".join(f"{l} {b} ({sum(1 for c in caught if (c[0], c[2]) == (l, b))} cases, gap/band to "
                       f"{max(c[3] for c in caught if (c[0], c[2]) == (l, b)):.3g})" for l, b in bands))
+    if mut in INVISIBLE:
+        assert not caught, f"mutation ({mut}) {what} is caught by {caught}" + (": the bands must admit the hardware" if mut == "l" else "")
+        return
     assert caught, f"mutation ({mut}) {what}: no band's gap exceeds its GPU band"
+    for band in GAMMA_NAMED.get(mut, ()):
+        missed = [c for c in E.case_names("gamma") if ("gamma", c, band) not in {k[:3] for k in caught}]
+        assert not missed, f"mutation ({mut}) {what}: the band {band} named for it lets it through on {missed}"
 
 
 @pytest.mark.parametrize("mut", list(MUTATIONS))

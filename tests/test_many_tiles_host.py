@@ -42,18 +42,22 @@ def test_tall_row_count_walks_groups():
 def test_the_table_fills_the_cells():
     cells = {(c.family, c.path, c.lik, c.weighted) for c in mt.CASES}
     for fam in ("fast3", "fast"):
-        for lik in ("gaussian", "bernoulli", "poisson", "student", "negbin", "hetero"):
+        for lik in ("gaussian", "bernoulli", "poisson", "student", "negbin", "hetero", "gamma"):
             assert any(f == fam and l == lik and not w for f, _p, l, w in cells), (fam, lik)
-    for lik in ("gaussian", "bernoulli", "poisson", "student", "negbin", "hetero"):
+    for lik in ("gaussian", "bernoulli", "poisson", "student", "negbin", "hetero", "gamma"):
         assert any(f == "fast3" and l == lik and w for f, _p, l, w in cells), lik
     assert ("fast3", "valu2", "student", False) in cells and ("fast", "valu2", "gaussian", True) in cells and ("fast", "valu2", "bernoulli", True) in cells
-    for lik in ("student", "negbin", "poisson", "hetero", "bernoulli"):
+    for lik in ("student", "negbin", "poisson", "hetero", "bernoulli", "gamma"):
         assert any(f == "mid" and p.startswith("valu") and l == lik for f, p, l, _w in cells), lik
-    for lik in ("gaussian", "bernoulli", "categorical", "poisson", "student", "negbin"):
+    for lik in ("gaussian", "bernoulli", "categorical", "poisson", "student", "negbin", "gamma"):
         assert ("mid", "mfma10", lik, False) in cells, lik
     for lik in ("gaussian", "categorical"):
         assert ("mid", "mfma10", lik, True) in cells and ("wide", "mfma10", lik, True) in cells, lik
     assert {("tall", "valu1", "gaussian", True), ("tall", "valu1", "poisson", False), ("tall", "mfma10", "categorical", True)} <= cells
+    # Gamma: every fused family, both narrow output counts, and its three weighted libraries (fast3, fast, the MFMA output tile of mid)
+    assert {("fast3", "valu1", "gamma", True), ("fast3", "valu2", "gamma", False), ("fast", "valu1", "gamma", True), ("mid", "mfma10", "gamma", True),
+            ("tall", "valu1", "gamma", False), ("wide", "valu1", "gamma", False), ("wide", "mfma10", "gamma", False)} <= cells
+    assert any(c.zero_ragged and c.lik == "gamma" and c.family == "fast" and c.rows == 381 for c in mt.CASES)
     assert sum(c.zero_ragged for c in mt.CASES) >= 1
     for c in mt.CASES:
         rows = {"wide": [mt.N_WIDE], "tall": [mt.TALL_ROWS], "mid": list(mt.MID_ROWS.values())}.get(c.family, list(mt.NARROW_ROWS.values()))

@@ -104,6 +104,9 @@ def _torch_target(spec, theta, eta, X, Y, w=None):
             r = torch.tensor(spec.lik_df, dtype=torch.float64)
             lden = torch.logaddexp(f, torch.log(r))
             return (wt * (torch.lgamma(y + r) - torch.lgamma(r) - torch.lgamma(y + 1) + y * (f - lden) + r * (torch.log(r) - lden))).sum()
+        if spec.likelihood == o.LIK_GAMMA:              # shape a, mean exp(f): rate a exp(-f)
+            a = torch.tensor(spec.lik_df, dtype=torch.float64)
+            return (wt * torch.distributions.Gamma(a, a * torch.exp(-f)).log_prob(y)).sum()
         if spec.likelihood == o.LIK_HETERO_GAUSSIAN:
             gc = torch.clamp(f[1], -math.log(1e8), math.log(1e8))
             return (wt * (-0.5 * math.log(2 * math.pi) - gc - 0.5 * (y[0] - f[0]) ** 2 * torch.exp(-2 * gc))).sum()
@@ -199,11 +202,11 @@ def test_hand_coded_gradients_match_autograd_last_activation(case):
     np.testing.assert_allclose(hg, hg_t, rtol=1e-8, atol=1e-9 * np.abs(hg_t).max())
 
 
-# the extensions beyond the reference (the categorical, Poisson, Student-t, negative-binomial and heteroscedastic Gaussian likelihoods,
-# per-row likelihood weights): autograd is all that pins them
+# the extensions beyond the reference (the categorical, Poisson, Student-t, negative-binomial, heteroscedastic Gaussian and Gamma
+# likelihoods, per-row likelihood weights): autograd is all that pins them
 EXT_CASES = {
-    # dims, rows, hidden activation, prior, likelihood, targets (Student-t: nu, at the scale STUDENT_S; negative binomial: r;
-    # heteroscedastic: None, or the last bias of output 1 that puts every row's log-sd beyond the clip), weighted
+    # dims, rows, hidden activation, prior, likelihood, targets (Student-t: nu, at the scale STUDENT_S; negative binomial: r; Gamma: the
+    # shape a; heteroscedastic: None, or the last bias of output 1 that puts every row's log-sd beyond the clip), weighted
     "cat_onehot": ([4, 12, 12, 3], 80, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "onehot", False),
     "cat_soft": ([4, 12, 12, 3], 80, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_CATEGORICAL, "soft", False),
     "cat_large_logits": ([4, 12, 12, 3], 80, o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_CATEGORICAL, "large", False),
@@ -227,6 +230,11 @@ EXT_CASES = {
     "weighted_student": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_STUDENT_T, 2.5, True),
     "weighted_negbin": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_NEG_BINOMIAL, 30.0, True),
     "weighted_hetero": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_HETERO_GAUSSIAN, None, True),
+    "gamma_a0.5_one_output": ([3, 12, 9, 1], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_GAMMA, 0.5, False),
+    "gamma_a10": ([4, 12, 12, 3], 80, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_GAMMA, 10.0, False),
+    "gamma_a200": ([3, 12, 9, 2], 60, o.ACT_RELU, o.PRIOR_CAUCHY, o.LIK_GAMMA, 200.0, False),
+    "weighted_gamma": ([3, 12, 9, 2], 60, o.ACT_TANH, o.PRIOR_CAUCHY, o.LIK_GAMMA, 2.0, True),
+    "weighted_gamma_a0.5_one_output": ([3, 12, 9, 1], 60, o.ACT_ELU, o.PRIOR_GAUSSIAN, o.LIK_GAMMA, 0.5, True),
 }
 STUDENT_S = 0.25                         # (exact in fp32: the oracle takes the scale as the library receives it)
 COUNTS = (o.LIK_POISSON, o.LIK_NEG_BINOMIAL)
@@ -237,7 +245,7 @@ def _ext_problem(case):
     if lik not in (o.LIK_GAUSSIAN, o.LIK_FIXED_GAUSSIAN, o.LIK_BERNOULLI):
         _g, X, Yr, theta, eta = o.synth_problem(dims, n, act, prior, o.LIK_GAUSSIAN)        # standardised teacher outputs [n, K]
         spec = o.make_spec(dims, act, prior, lik, o.ACT_NONE, fixed_sd=STUDENT_S,
-                           lik_df=targets if lik in (o.LIK_STUDENT_T, o.LIK_NEG_BINOMIAL) else 0.0)
+                           lik_df=targets if lik in (o.LIK_STUDENT_T, o.LIK_NEG_BINOMIAL, o.LIK_GAMMA) else 0.0)
         eta = eta[:spec.n_hypers]                                                           # no likelihood hyper
     else:
         spec, X, Y, theta, eta = o.synth_problem(dims, n, act, prior, lik)
@@ -257,6 +265,14 @@ def _ext_problem(case):
         if np.abs(f).max() > 5.0:        # the state's own log-rates within [-5, 5]
             theta[ow:] *= 5.0 / np.abs(f).max()
         assert np.abs(o.forward(spec, theta, X, np.float64)).max() <= 5.0 + 1e-9 and (Y == 0).any() and (Y % 1 != 0).any()
+    if lik == o.LIK_GAMMA:               # positive targets of shape a around exp(0.5 + 0.8 z), every fifth row far off its mean on either side;
+        f = o.forward(spec, theta, X, np.float64)                   # the state's own log-means within [-5, 5]
+        if np.abs(f).max() > 5.0:
+            theta[ow:] *= 5.0 / np.abs(f).max()
+        Y = np.maximum(np.random.default_rng(11).gamma(targets, np.exp(0.5 + 0.8 * Yr) / targets), 1e-30)
+        Y[::5] *= 50.0
+        Y[1::5] /= 50.0
+        assert np.abs(o.forward(spec, theta, X, np.float64)).max() <= 5.0 + 1e-9 and np.all(Y > 0)
     if lik == o.LIK_STUDENT_T:           # the teacher's outputs plus N(0, s^2), every tenth row moved by 30 s: both ends of r^2 / (nu s^2)
         Y = Yr + STUDENT_S * np.random.default_rng(11).standard_normal(Yr.shape)
         Y[::10] += 30.0 * STUDENT_S
@@ -300,7 +316,8 @@ def test_extension_gradients_match_autograd(case):
 
 
 @pytest.mark.parametrize("case", ["weighted_gauss", "weighted_fixed_gauss", "weighted_bern", "weighted_cat", "weighted_pois",
-                                  "weighted_student", "weighted_negbin", "weighted_hetero"])
+                                  "weighted_student", "weighted_negbin", "weighted_hetero", "weighted_gamma",
+                                  "weighted_gamma_a0.5_one_output"])
 def test_integer_weights_are_repeated_rows(case):
     spec, X, Y, theta, eta, _w = _ext_problem(case)
     w = np.random.default_rng(11).integers(0, 4, len(X))
@@ -316,7 +333,8 @@ def test_integer_weights_are_repeated_rows(case):
     np.testing.assert_allclose(hg, hg_r, rtol=0, atol=1e-12 * np.abs(hg_r).max())
 
 
-@pytest.mark.parametrize("case", ["weighted_cat", "weighted_pois", "weighted_student", "weighted_negbin", "weighted_hetero"])
+@pytest.mark.parametrize("case", ["weighted_cat", "weighted_pois", "weighted_student", "weighted_negbin", "weighted_hetero",
+                                  "weighted_gamma", "weighted_gamma_a0.5_one_output"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_unit_weights_are_exactly_unweighted(case, dtype):
     spec, X, Y, theta, eta, _w = _ext_problem(case)
