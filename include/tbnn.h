@@ -95,10 +95,26 @@ enum { TBNN_PRIOR_CAUCHY = 0, TBNN_PRIOR_GAUSSIAN = 1 };
  * C = sum_i w_i sum_k (lgamma(a) - a log a - (a - 1) log y_ik) is computed with the data (or row weights), in fp64 and bit for bit the same
  * from run to run, and the log-probability is formed as -a stat - C -- Poisson's rules for tbnn_set_data_device, validation data and row
  * shards hold, and stat of tbnn_logp_grad is the data term -a stat - C itself.  A log-mean below the fp32 range of exp(-f) gives a
- * non-finite statistic: the proposal is rejected and the chain keeps its state (Poisson's rule, on the other side).  Codes 4, 6, 7, 9,
- * 11, 13 and every other value are not assigned. */
+ * non-finite statistic: the proposal is rejected and the chain keeps its state (Poisson's rule, on the other side);
+ * WEIBULL: times to an event, some rows RIGHT-CENSORED (survival data: time to failure, relapse, churn), any d_out >= 1 independent
+ * outputs, no activation after the last layer: its output f is the LOG of the Weibull scale, lambda = exp(f) (the accelerated-failure-time
+ * parameterisation).  The shape k = the descriptor's lik_df, finite and > 0 (tbnn_create, tbnn_create_multi and
+ * tbnn_fused_kernel_available refuse any other lik_df); k = 1 is the exponential model.  fixed_sd is not read.  No likelihood hyper
+ * (H = 4 n_layers).  CENSORING TRAVELS IN THE SIGN OF THE TARGET: y > 0 is an event observed at time y, y < 0 a row right-censored at
+ * time |y| (the event had not happened by then); times are positive, so the sign is free, and target layout, staging, row shards and row
+ * weights keep their shape.  With d = 1 for an event and 0 for a censored row, t = |y| and u = (t e^-f)^k = exp(k (log t - f)), per
+ * (row, output):   event  log p = log k + (k - 1) log t - k f - u;   censored  log S = -u;   dL/df = k (u - d).
+ * A row weight scales the row's term and its delta.  Targets are admitted when they are finite, nonzero and 2^-100 <= |y| <= 2^100 (the
+ * floor hands the hardware log a normal fp32 number, the ceiling is Gamma's): staging refuses anything else and names the rule, and the
+ * handle keeps the rows it had.  The kernels accumulate stat = sum_i w_i (k d f + u), one fp32 term per element from one hardware log and
+ * one hardware exp, and return the delta w k (u - d); the constant C = -sum_i w_i sum_out d (log k + (k - 1) log t) is computed with the
+ * data (or row weights), in fp64 and bit for bit the same from run to run, and the log-probability is formed as -stat - C -- Gamma's rules
+ * for tbnn_set_data_device, validation data and row shards hold, and stat of tbnn_logp_grad is the data term -stat - C itself.  If u
+ * overflows fp32 the statistic is not finite: the proposal is rejected and the chain keeps its state (Poisson's and Gamma's rule).
+ * tbnn_metrics reads the target as staged, sign included.  Left and interval censoring, and a sampled or predicted shape, are not built.
+ * Codes 4, 6, 7, 9, 11, 13, 15 and every other value are not assigned. */
 enum { TBNN_LIK_GAUSSIAN = 0, TBNN_LIK_FIXED_GAUSSIAN = 1, TBNN_LIK_BERNOULLI = 2, TBNN_LIK_CATEGORICAL = 3, TBNN_LIK_POISSON = 5,
-       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10, TBNN_LIK_HETERO_GAUSSIAN = 12, TBNN_LIK_GAMMA = 14 };
+       TBNN_LIK_STUDENT_T = 8, TBNN_LIK_NEG_BINOMIAL = 10, TBNN_LIK_HETERO_GAUSSIAN = 12, TBNN_LIK_GAMMA = 14, TBNN_LIK_WEIBULL = 16 };
 
 /* kernel selection for the forward+backward pass.  AUTO: a fused shape-specialised MFMA kernel where one covers the network
  * (built in or registered at run time), else the layered run-time-shape MFMA kernels (any architecture); FAST: a fused kernel or
@@ -118,7 +134,7 @@ typedef struct tbnn_net_desc {
     int32_t likelihood;  /* TBNN_LIK_* */
     float fixed_sd;      /* FixedGaussianLikelihood(sd=) likelihood.py:138-141; the scale s of TBNN_LIK_STUDENT_T */
     int32_t kernel;      /* TBNN_KERNEL_* */
-    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; TBNN_LIK_GAMMA: the shape a; ignored under every other likelihood (this was `int32_t reserved`:
+    float lik_df;        /* TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; TBNN_LIK_GAMMA: the shape a; TBNN_LIK_WEIBULL: the shape k; ignored under every other likelihood (this was `int32_t reserved`:
                           * the same size and offset, and the all-zero bits callers passed there are 0.0) */
 } tbnn_net_desc;
 
@@ -309,7 +325,8 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
  * NULL = fixed_sd, clipped as the Gaussian kinds', its nu the handle's lik_df -- the descriptor's on a Student-t handle, what
  * tbnn_set_lik_df set on any other (0, never set: refused); negative binomial: the density of TBNN_LIK_NEG_BINOMIAL per output in fp64 in
  * its stable form, its dispersion r the handle's lik_df by the same rule; Gamma: the density of TBNN_LIK_GAMMA per output in fp64, its
- * shape a the handle's lik_df by the same rule.
+ * shape a the handle's lik_df by the same rule; Weibull: per output the log density of TBNN_LIK_WEIBULL on an event row (y > 0) and the log
+ * survival function -u on a right-censored one (y < 0), in fp64, its shape k the handle's lik_df by the same rule.
  *   per_net[i]   = sum over rows and outputs of the terms under network i          (m doubles, or NULL)
  *   lppd_rows[r] = log sum_i w_i p(y_r | theta_i) - log W, p the product over the row's outputs   (n doubles, or NULL)
  * Both are the same bits from run to run. */
@@ -432,6 +449,13 @@ int tbnn_series_diagnostics(tbnn_handle h, const float* series, int32_t m, int64
  *                    multiplicative pushes until F(lo) < p <= F(hi) as evaluated, then Newton steps on the mixture density safeguarded by
  *                    the midpoint: the upper end hi of a bracket of at most 2 ulp64(hi) with F(lo) < p <= F(hi), or a point with F == p.
  *                    cdf_below_out is refused (a continuous CDF has no step).  A network of weight 0 is not looked at, whatever it holds.
+ *   TBNN_LIK_WEIBULL k = the handle's shape (the descriptor's lik_df on a Weibull handle, else what tbnn_set_lik_df set; never set: refused).
+ *                    F(t) = (1/W) sum_i w_i (-expm1(-u_i)), u_i = exp(k (log t - f_i)), read at t = |y|: the sign of a target is its
+ *                    censoring flag, and on a censored row the PIT lies in [F, 1] (the caller knows which rows those are).  F = 0 for
+ *                    t = 0.  Quantile at p: Gamma's scheme -- the host stages g_p = (-log1p(-p))^(1/k), exp(f_i) g_p is component i's own
+ *                    quantile, the bracket is multiplicative, widened and VERIFIED, the search the safeguarded Newton search with the
+ *                    closed-form density (k / t) u_i exp(-u_i), the same stopping rule, the result the upper end.  cdf_below_out is
+ *                    refused; NaN rules as Gamma's, with the scale exp(f_i) for the mean.
  * q_out: host [n_probs][d_out][n] doubles, or NULL (then probs may be NULL too); probs: n_probs probabilities in the OPEN interval (0, 1)
  * (the Gaussian quantile at 0 or 1 is infinite), 1 <= n_probs <= 64.  cdf_out: host [d_out][n] doubles = F(y) at the targets, or NULL; Y is
  * then needed by tbnn_ensemble_loglik's rules (host targets [n, d_out]; NULL with X NULL = the staged targets of `which`; X without Y is
@@ -527,7 +551,8 @@ int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, int64_t the
  * OWN likelihood is another one (a forward handle for saved networks is usually a fixed-sd Gaussian one).  Nothing else reads it.  Refused
  * (-1): a TBNN_LIK_STUDENT_T handle (its nu is the descriptor's lik_df), a df that is not finite and > 0.  The same value is the dispersion r
  * when they judge under TBNN_LIK_NEG_BINOMIAL; a TBNN_LIK_NEG_BINOMIAL handle (its r is the descriptor's lik_df) is refused too.  And the
- * shape a when they -- and tbnn_ensemble_predictive -- judge under TBNN_LIK_GAMMA; a TBNN_LIK_GAMMA handle is refused likewise. */
+ * shape a when they -- and tbnn_ensemble_predictive -- judge under TBNN_LIK_GAMMA; a TBNN_LIK_GAMMA handle is refused likewise.  And the
+ * shape k under TBNN_LIK_WEIBULL; a TBNN_LIK_WEIBULL handle is refused likewise. */
 int tbnn_set_lik_df(tbnn_handle h, float df);
 /* metrics.py:30-141 in one pass over the predictions: with p = f*sd+mean, r = y*sd+mean (exp() of either on
  * request: scaleExp; SquaredError leaves the validation predictions un-exponentiated, metrics.py:44-47)

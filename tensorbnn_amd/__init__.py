@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "GammaLikelihood":
         from .likelihood import GammaLikelihood
         return GammaLikelihood
+    if name == "WeibullLikelihood":
+        from .likelihood import WeibullLikelihood
+        return WeibullLikelihood
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

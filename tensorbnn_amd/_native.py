@@ -22,6 +22,7 @@ PRIOR_CAUCHY, PRIOR_GAUSSIAN = 0, 1
 LIK_GAUSSIAN, LIK_FIXED_GAUSSIAN, LIK_BERNOULLI, LIK_CATEGORICAL, LIK_POISSON = 0, 1, 2, 3, 5      # (4 is not assigned: include/tbnn.h)
 LIK_STUDENT_T = 8                                                                                  # (nor are 6 and 7)
 LIK_GAMMA = 14                                                                                     # (nor are 11 and 13)
+LIK_WEIBULL = 16                                                                                   # (nor is 15)
 LIK_NEG_BINOMIAL = 10                                                                              # (nor is 9)
 LIK_HETERO_GAUSSIAN = 12                                                                           # (nor is 11)
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
@@ -310,7 +311,7 @@ class Chain:
                  jit: Optional[bool] = None, lik_df: float = 0.0):
         """jit: compile + register MFMA kernels for a shape outside the ahead-of-time registries (jit.py);
         None -> the TBNN_JIT environment switch (default on); only consulted for KERNEL_AUTO / KERNEL_FAST.
-        lik_df: the degrees of freedom of LIK_STUDENT_T (its scale is fixed_sd), the dispersion r of LIK_NEG_BINOMIAL, the shape a of LIK_GAMMA; ignored under every
+        lik_df: the degrees of freedom of LIK_STUDENT_T (its scale is fixed_sd), the dispersion r of LIK_NEG_BINOMIAL, the shape a of LIK_GAMMA, the shape k of LIK_WEIBULL; ignored under every
         other likelihood."""
         arr = (LayerDesc * len(layers))(*[LayerDesc(*map(int, l)) for l in layers])
         self._layers_keepalive = arr
@@ -624,8 +625,8 @@ class Chain:
         prediction -- inverted and evaluated on the device (tbnn_ensemble_predictive): (q, F, F_below).  q float64 [n_probs, d_out, rows]: the
         quantiles at probs, each in (0, 1) (None: no probs).  F float64 [d_out, rows]: the mixture CDF at the targets, the PIT values; asked
         for by cdf=True, or cdf=None and Y given (Y None with X None: the staged targets); else None.  F_below: under LIK_POISSON / LIK_NEG_BINOMIAL the CDF at
-        target - 1 (a count's PIT lies in [F_below, F]), else None.  likelihood: LIK_GAUSSIAN / LIK_FIXED_GAUSSIAN / LIK_POISSON / LIK_NEG_BINOMIAL / LIK_GAMMA (a continuous
-        CDF: F_below None; its shape: the chain's lik_df, or set_lik_df) (None: the
+        target - 1 (a count's PIT lies in [F_below, F]), else None.  likelihood: LIK_GAUSSIAN / LIK_FIXED_GAUSSIAN / LIK_POISSON / LIK_NEG_BINOMIAL / LIK_GAMMA / LIK_WEIBULL (a continuous
+        CDF: F_below None; its shape: the chain's lik_df, or set_lik_df; LIK_WEIBULL reads a target at |y|, its sign being the censoring flag) (None: the
         chain's own); sd: one per network for the Gaussian kinds (None: the chain's fixed_sd).  Under LIK_HETERO_GAUSSIAN (a 2-output chain:
         mean and log-sd) the mixture of N(f_i, exp(g_i)^2), one distribution per row: q [n_probs, 1, rows], F [1, rows]; sd is not read"""
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
@@ -702,7 +703,7 @@ class Chain:
     def set_lik_df(self, df: float):
         """the degrees of freedom ensemble_loglik / ensemble_loo use when they judge under LIK_STUDENT_T on a chain whose own likelihood is
         another one (tbnn_set_lik_df); a LIK_STUDENT_T chain takes them from its constructor's lik_df and refuses this call.  The same
-        value is the dispersion r when they -- and ensemble_predictive -- judge under LIK_NEG_BINOMIAL; the shape a under LIK_GAMMA; a LIK_NEG_BINOMIAL or LIK_GAMMA chain refuses
+        value is the dispersion r when they -- and ensemble_predictive -- judge under LIK_NEG_BINOMIAL; the shape a under LIK_GAMMA and k under LIK_WEIBULL; a LIK_NEG_BINOMIAL, LIK_GAMMA or LIK_WEIBULL chain refuses
         the call too"""
         _check(lib.tbnn_set_lik_df(self._h, float(df)))
 

@@ -25,13 +25,17 @@ enum { SHAPE_LIK_HETERO = 16 };
 // the same bit on the Poisson code: the Gamma data term of TBNN_LIK_GAMMA, the log-mean f of the Poisson kind under another loss;
 // weighted: SHAPE_LIK_POIS | SHAPE_LIK_GAMMA | SHAPE_LIK_WEIGHTED.  (Not defined on the other two codes, nor together with SHAPE_LIK_NEGBIN.)
 enum { SHAPE_LIK_GAMMA = 16 };
+// bits 8 and 16 TOGETHER on the Poisson code: the Weibull data term of TBNN_LIK_WEIBULL with right-censored targets, the log-scale f under
+// a third element-wise loss; weighted: SHAPE_LIK_POIS | SHAPE_LIK_WEIBULL | SHAPE_LIK_WEIGHTED.  (Not defined on the other codes.)
+enum { SHAPE_LIK_WEIBULL = 8 | 16 };
 // ... of a TBNN_LIK_* value (Gaussian and fixed-sd Gaussian share their kernels: the sd is a run-time argument)
 __host__ __device__ constexpr int shape_lik(int lik) {
     return lik == TBNN_LIK_BERNOULLI ? SHAPE_LIK_BERN : lik == TBNN_LIK_CATEGORICAL ? SHAPE_LIK_CAT : lik == TBNN_LIK_POISSON ? SHAPE_LIK_POIS :
            lik == TBNN_LIK_STUDENT_T ? (SHAPE_LIK_STUDENT | SHAPE_LIK_GAUSS) :
            lik == TBNN_LIK_NEG_BINOMIAL ? (SHAPE_LIK_NEGBIN | SHAPE_LIK_POIS) :
            lik == TBNN_LIK_HETERO_GAUSSIAN ? (SHAPE_LIK_HETERO | SHAPE_LIK_GAUSS) :
-           lik == TBNN_LIK_GAMMA ? (SHAPE_LIK_GAMMA | SHAPE_LIK_POIS) : SHAPE_LIK_GAUSS;
+           lik == TBNN_LIK_GAMMA ? (SHAPE_LIK_GAMMA | SHAPE_LIK_POIS) :
+           lik == TBNN_LIK_WEIBULL ? (SHAPE_LIK_WEIBULL | SHAPE_LIK_POIS) : SHAPE_LIK_GAUSS;
 }
 
 #define TBNN_WAVE 64
@@ -55,7 +59,7 @@ struct NetDev {
     int maxW;                     // widest layer (in or out)
     float fixed_sd;
     int reserved_flags;           // bit 0: fast kernel processes one tile at a time (diagnostic)
-    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; TBNN_LIK_GAMMA: the shape a (0 otherwise)
+    float lik_df;                 // TBNN_LIK_STUDENT_T: the degrees of freedom nu; TBNN_LIK_NEG_BINOMIAL: the dispersion r; TBNN_LIK_GAMMA: the shape a; TBNN_LIK_WEIBULL: the shape k (0 otherwise)
 };
 
 // Gradient-slab stores of the narrow family: WRITE-THROUGH (global_store ... sc1: a relaxed agent-scope atomic store) when the slabs
@@ -199,6 +203,30 @@ __device__ __forceinline__ float gamma_elem(float fi, float y, double& stat, flo
     const float d = gamma_term(fi, y, &term);
     stat += (double)(wt * term);
     return wt * (a * d);
+}
+
+// Weibull with right-censored targets (TBNN_LIK_WEIBULL, defined in include/tbnn.h), fi the log of the scale, k the shape.  The SIGN of
+// the target is the censoring flag: y > 0 an event at time y (d = 1), y < 0 a row still running at time |y| (d = 0); the sign test and
+// t = |y| read the same register.  ONE hardware log2 and ONE hardware exp2: u = (t e^-f)^k = exp(k (log t - f)), the element's part of
+// the statistic k d f + u (its sign and the constant: data_logp, kernels_hmc.hpp) and, returned, u - d: dL/df over the shape k, which the
+// caller multiplies in.  The term is picked by a select, not formed as d (k f): a NaN stays a NaN (y, f or u), and u past the fp32 range
+// gives inf -- the statistic is not finite and k_energy rejects the proposal (Poisson's and Gamma's rule).  Staging admits 2^-100 <= |y|
+// <= 2^100 only (k_pois_const), so the hardware log sees a normal number.  Not contracted, for the reason given at log1p_fast.  One
+// function for lik_delta's compile-time branch and the kernels that branch at run time.
+__device__ __forceinline__ float weibull_term(float fi, float y, float k, float* term) {
+#pragma clang fp contract(off)
+    const bool event = y > 0.f;
+    const float u = __expf(k * (__logf(fabsf(y)) - fi));
+    *term = event ? k * fi + u : u;
+    return event ? u - 1.f : u;
+}
+// ... for the kernels that branch at run time (layered, generic): adds wt term to stat, returns wt dL/df = wt (k (u - d))
+__device__ __forceinline__ float weibull_elem(float fi, float y, double& stat, float wt, float k) {
+#pragma clang fp contract(off)
+    float term;
+    const float d = weibull_term(fi, y, k, &term);
+    stat += (double)(wt * term);
+    return wt * (k * d);
 }
 
 // Heteroscedastic Gaussian (TBNN_LIK_HETERO_GAUSSIAN): one ROW of a 2-output network, f the mean and g the log of the sd.  With

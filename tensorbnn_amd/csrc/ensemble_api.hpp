@@ -61,7 +61,7 @@ static int ens_sigmas(const std::string& who, const float* sd, float fixed_sd, i
 
 // what tbnn_ensemble_loglik and tbnn_ensemble_loo stage per network: *scaled = the likelihood has a scale (the Gaussian kinds, Student-t) -- sig
 // and cst as ens_sigmas forms them; under TBNN_LIK_STUDENT_T *nu = the handle's degrees of freedom (its descriptor's, or what
-// tbnn_set_lik_df set on a handle of another likelihood; under TBNN_LIK_NEG_BINOMIAL the dispersion r and under TBNN_LIK_GAMMA the shape a, by the same rule) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
+// tbnn_set_lik_df set on a handle of another likelihood; under TBNN_LIK_NEG_BINOMIAL the dispersion r, under TBNN_LIK_GAMMA the shape a and under TBNN_LIK_WEIBULL the shape k, by the same rule) and cst[i] = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma_i
 static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, const float* sd, int32_t m, bool* scaled, std::vector<float>& sig,
                           std::vector<double>& cst, double* nu) {
     const bool student = likelihood == TBNN_LIK_STUDENT_T;
@@ -83,6 +83,12 @@ static int ens_lik_consts(tbnn_ctx* h, const std::string& who, int likelihood, c
         const float a = h->nd.lik == TBNN_LIK_GAMMA ? h->nd.lik_df : h->ens_df;
         if (!df_ok(a)) return fail(-1, who + ": judging under TBNN_LIK_GAMMA needs the shape: call tbnn_set_lik_df on this handle first");
         *nu = (double)a;
+    }
+    if (likelihood == TBNN_LIK_WEIBULL) {
+        // the shape k travels where nu does: the descriptor's lik_df on a Weibull handle, else what tbnn_set_lik_df set
+        const float k = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(k)) return fail(-1, who + ": judging under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
+        *nu = (double)k;
     }
     if (*scaled) ENS_TRY(ens_sigmas(who, sd, h->nd.fixed_sd, m, sig, &cst));
     if (student) {
@@ -310,6 +316,9 @@ extern "C" int tbnn_ensemble_uncertainty(tbnn_handle h, const float* thetas, int
     const int d_out = h->nd.d_out;
     if (!prob_out && !vote_out && !total_out && !aleatoric_out && !epistemic_out) return fail(-1, who + ": every output is null");
     const bool cat = likelihood == TBNN_LIK_CATEGORICAL;
+    if (likelihood == TBNN_LIK_WEIBULL)
+        return fail(-1, who + ": the entropy split and the votes are those of a label, not of TBNN_LIK_WEIBULL's time to an event (tbnn_ensemble_predictive "
+                              "gives its CDF and quantiles)");
     if (!cat && likelihood != TBNN_LIK_BERNOULLI)
         return fail(-1, who + ": the entropy split and the votes are those of a label: TBNN_LIK_BERNOULLI or TBNN_LIK_CATEGORICAL (regression and "
                               "count kinds: tbnn_ensemble_predictive and tbnn_ensemble_moments)");
@@ -575,7 +584,7 @@ static double ens_std_gamma_ppf(double a, double p) {
 }
 
 // what tbnn_ensemble_predictive refuses before it touches a device, and the per-network constants it stages: cst[3][m] = w_i / W,
-// 1 / (s_i sqrt 2), s_i (the last two: Gaussian kinds); pz[2][n_probs] = p, Phi^-1(p) (TBNN_LIK_GAMMA: p, g_p / shape, g_p the standard
+// 1 / (s_i sqrt 2), s_i (the last two: Gaussian kinds); pz[2][n_probs] = p, Phi^-1(p) (TBNN_LIK_WEIBULL: p, (-log1p(-p))^(1 / shape), the standard Weibull quantile; TBNN_LIK_GAMMA: p, g_p / shape, g_p the standard
 // Gamma(shape, 1) quantile -- the caller passes the shape, 0 otherwise); *smax = the largest s_i among the networks that count
 static int pred_check(const std::string& who, int likelihood, float fixed_sd, int d_out, const float* sd, const float* net_w, int32_t m, const float* X,
                       const float* Y, const double* probs, int32_t n_probs, const double* q_out, const double* cdf_out, const double* cdf_below_out,
@@ -594,7 +603,7 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
     if (likelihood == TBNN_LIK_STUDENT_T)
         return fail(-1, who + ": the Student-t predictive distribution (a mixture of t CDFs: the incomplete beta function on the device) is not built");
     const bool gauss = ens_gaussian(likelihood), het = likelihood == TBNN_LIK_HETERO_GAUSSIAN;
-    const bool gam = likelihood == TBNN_LIK_GAMMA;
+    const bool wei = likelihood == TBNN_LIK_WEIBULL, gam = likelihood == TBNN_LIK_GAMMA || wei;       // (gam: a continuous kind on the positive axis)
     if (!gauss && !het && !gam && likelihood != TBNN_LIK_POISSON && likelihood != TBNN_LIK_NEG_BINOMIAL) return fail(-1, who + ": unknown likelihood");
     // (heteroscedastic Gaussian: every network brings its own s_i(x) = exp(gc_i) in output 1 -- sd is not read, cst keeps w_i / W alone)
     if (het && d_out != 2) return fail(-1, who + ": the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
@@ -621,7 +630,13 @@ static int pred_check(const std::string& who, int likelihood, float fixed_sd, in
     pz.assign(2 * (size_t)std::max(n_probs, 1), 0.0);
     for (int32_t j = 0; j < n_probs; ++j) {
         pz[j] = probs[j];
-        pz[(size_t)n_probs + j] = gam ? ens_std_gamma_ppf(shape, probs[j]) / shape : ens_norm_ppf(probs[j]);
+        // (a Weibull shape so small that the standard quantile leaves fp64's normal range would seed a bracket end of 0 or inf)
+        if (wei) {
+            const double g = std::pow(-std::log1p(-probs[j]), 1.0 / shape);
+            if (!(g >= 0x1p-1022 && g < (double)INFINITY))
+                return fail(-1, who + ": the standard Weibull quantile (-log1p(-p))^(1/k) at one of the probabilities is not a normal fp64 number: the shape is too small for it");
+        }
+        pz[(size_t)n_probs + j] = wei ? std::pow(-std::log1p(-probs[j]), 1.0 / shape) : gam ? ens_std_gamma_ppf(shape, probs[j]) / shape : ens_norm_ppf(probs[j]);
     }
     return 0;
 }
@@ -635,8 +650,14 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
     std::vector<double> cst, pz;
     double smax = 0.0;
     // the shape of the Gamma likelihood: the descriptor's lik_df on such a handle, what tbnn_set_lik_df set on any other
-    const bool gam = likelihood == TBNN_LIK_GAMMA;
+    const bool gam = likelihood == TBNN_LIK_GAMMA, wei = likelihood == TBNN_LIK_WEIBULL;
     double shape = 0.0;
+    if (wei) {
+        // (the Weibull likelihood's: by the same rule)
+        const float k = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(k)) return fail(-1, who + ": the predictive distribution under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
+        shape = (double)k;
+    }
     if (gam) {
         const float a = h->nd.lik == TBNN_LIK_GAMMA ? h->nd.lik_df : h->ens_df;
         if (!df_ok(a)) return fail(-1, who + ": the predictive distribution under TBNN_LIK_GAMMA needs the shape: call tbnn_set_lik_df on this handle first");
@@ -681,6 +702,7 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
                 if (pois) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_POISSON, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else if (negb) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_NEG_BINOMIAL, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else if (gam) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAMMA, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
+                else if (wei) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_WEIBULL, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else if (het) hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_HETERO_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 else hipLaunchKernelGGL((k_ens_pred_quantiles<TBNN_LIK_GAUSSIAN, ENS_PQ>), grid, tb, 0, h->stream, t, m, tot, c, p, n_probs, smax, q, disp);
                 HIPCHK(hipGetLastError());
@@ -691,6 +713,7 @@ extern "C" int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int3
                 if (pois) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else if (negb) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_NEG_BINOMIAL>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else if (gam) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAMMA>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
+                else if (wei) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_WEIBULL>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else if (het) hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_HETERO_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 else hipLaunchKernelGGL(k_ens_pred_cdf<TBNN_LIK_GAUSSIAN>, grid, tb, 0, h->stream, t, m, tot, r, d_out, y, c, F, Fb, disp);
                 HIPCHK(hipGetLastError());
@@ -715,6 +738,9 @@ static int crps_check(const std::string& who, int likelihood, float fixed_sd, in
                               "form: a sum of (F(k) - 1{y <= k})^2 over the support, another kernel)");
     if (likelihood == TBNN_LIK_GAMMA)
         return fail(-1, who + ": the CRPS under TBNN_LIK_GAMMA is not built (the pair term E|Y_i - Y_j| of two Gamma distributions has no closed form)");
+    if (likelihood == TBNN_LIK_WEIBULL)
+        return fail(-1, who + ": the CRPS under TBNN_LIK_WEIBULL is not built (no kernel forms the pair term E|Y_i - Y_j| of two Weibull distributions, and a censored "
+                              "row has no observed value to score)");
     if (likelihood == TBNN_LIK_STUDENT_T)
         return fail(-1, who + ": the CRPS under TBNN_LIK_STUDENT_T is not built (the pair term of two t distributions has no closed form, and the "
                               "Student-t predictive distribution is not built either)");

@@ -63,7 +63,7 @@ static inline void fused_ops_shape(FusedOps* o, const char* prefix, const char* 
     if (S::HCODE & TBNN_ACT_PACKED) {
         for (int l = 0; l + 1 < S::NL && k < (int)sizeof(o->name) - 16; ++l) k += snprintf(o->name + k, sizeof(o->name) - k, l ? "+%s" : "%s", an[S::act(l) & 7]);
     } else k += snprintf(o->name + k, sizeof(o->name) - k, "%s", an[S::HCODE & 7]);
-    k += snprintf(o->name + k, sizeof(o->name) - k, ",%s%s%s;", an[S::LACT], S::BERN ? ",bernoulli" : S::CAT ? ",categorical" : S::POIS ? ",poisson" : S::NEGB ? ",neg-binomial" : S::GAMMA ? ",gamma" : S::STUD ? ",student-t" : S::HET ? ",hetero-gaussian" : "", S::WTD ? ",weighted" : "");
+    k += snprintf(o->name + k, sizeof(o->name) - k, ",%s%s%s;", an[S::LACT], S::BERN ? ",bernoulli" : S::CAT ? ",categorical" : S::POIS ? ",poisson" : S::NEGB ? ",neg-binomial" : S::GAMMA ? ",gamma" : S::WEIB ? ",weibull" : S::STUD ? ",student-t" : S::HET ? ",hetero-gaussian" : "", S::WTD ? ",weighted" : "");
     for (int i = 0; i <= S::NL && k < (int)sizeof(o->name) - 8; ++i) k += snprintf(o->name + k, sizeof(o->name) - k, i ? ",%d" : "%d", S::D[i]);
     snprintf(o->name + k, sizeof(o->name) - k, ">");
 }

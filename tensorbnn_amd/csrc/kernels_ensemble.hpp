@@ -280,6 +280,9 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_uncert_finish_softmax(double* __
 //                    the stable form of negbin_term (common.hpp); r arrives in `nu` (ensemble_api.hpp ens_lik_consts)
 //   Gamma            a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f) per output in fp64, f the log of the mean (include/tbnn.h
 //                    TBNN_LIK_GAMMA); the shape a arrives in `nu`, by the rule the dispersion follows
+//   Weibull          per output in fp64, f the log of the scale, t = |y|, u = exp(k (log t - f)) (include/tbnn.h TBNN_LIK_WEIBULL): an event
+//                    (y > 0) gives the log density log k + (k - 1) log t - k f - u, a right-censored row (y < 0) the log survival -u; the
+//                    shape k arrives in `nu`, by the rule the dispersion follows
 //   Student-t        cst - (nu + 1) / 2 log1p(((y - f) / sigma)^2 / nu) per output in fp64 (include/tbnn.h TBNN_LIK_STUDENT_T; sigma clipped by
 //                    the host, cst = lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu pi) - log sigma: ensemble_api.hpp ens_lik_consts)
 __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restrict__ f, long n, const float* __restrict__ y, int d_out, float sigma,
@@ -319,6 +322,13 @@ __device__ __forceinline__ double ens_row_loglik(int lik, const float* __restric
         for (int k = 0; k < d_out; ++k) {
             const double yk = (double)y[k], fk = (double)f[(size_t)k * n];
             l += (c0 + (nu - 1.0) * log(yk)) - nu * (fk + yk * exp(-fk));
+        }
+    } else if (lik == TBNN_LIK_WEIBULL) {
+        const double lk = log(nu);
+        for (int k = 0; k < d_out; ++k) {
+            const double yk = (double)y[k], fk = (double)f[(size_t)k * n], lt = log(fabs(yk));
+            const double u = exp(nu * (lt - fk));
+            l += yk > 0.0 ? ((lk + (nu - 1.0) * lt) - nu * fk) - u : -u;
         }
     } else if (lik == TBNN_LIK_STUDENT_T) {
         for (int k = 0; k < d_out; ++k) {
@@ -840,7 +850,9 @@ __device__ __forceinline__ double ens_het_gc(float g) {
 // F(k) = sum_i w_i / W I_{q_i}(r, k + 1), q_i = sigmoid(log r - f_i); its ceilings are 2^20 on the rate AND on k = floor(y): beyond either
 // the element is NaN (ENS_NB_MAX).  Gamma (TBNN_LIK_GAMMA; disp = the shape a): F(y) = sum_i w_i / W P(a, a y exp(-f_i)) by ens_gamma_p,
 // F = 0 for y <= 0; NaN for a NaN target and, among the networks that count, a NaN f_i or a mean exp(f_i) that is 0 or not finite (a
-// network of weight 0 is not looked at, whatever it holds).
+// network of weight 0 is not looked at, whatever it holds).  Weibull (TBNN_LIK_WEIBULL; disp = the shape k): the target is read at
+// t = |y| (its sign is the censoring flag, which the caller knows: on a censored row the PIT lies in [F, 1]),
+// F(t) = sum_i w_i / W (-expm1(-u_i)), u_i = exp(k (log t - f_i)), F = 0 for t = 0; Gamma's NaN rules, the scale exp(f_i) for the mean.
 template <int LIK>
 __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict__ t, int m, long tot, long r, int d_out, const float* __restrict__ Y,
                                                           const double* __restrict__ cst, double* __restrict__ cdf, double* __restrict__ below,
@@ -867,7 +879,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
                 F += wn * ens_phi(y, (double)fv, exp(-ens_het_gc(gv)) * 0.70710678118654752440);
                 continue;
             }
-            if (LIK != TBNN_LIK_GAMMA) bad += fv != fv;        // (Gamma: a network of weight 0 is not looked at; a NaN that counts: below)
+            if (LIK != TBNN_LIK_GAMMA && LIK != TBNN_LIK_WEIBULL) bad += fv != fv;        // (Gamma, Weibull: a network of weight 0 is not looked at; a NaN that counts: below)
             if (!(wn > 0.0)) continue;
             if (LIK == TBNN_LIK_POISSON) {
                 const double lam = exp((double)fv);
@@ -878,6 +890,10 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
                 const double mu = exp((double)fv);
                 if (!(mu > 0.0 && mu < (double)INFINITY)) { bad += 1; continue; }       // (the mean 0 or not finite; a NaN f_i too)
                 if (y > 0.0) F += wn * ens_gamma_p(disp, (disp * y) * exp(-(double)fv));
+            } else if (LIK == TBNN_LIK_WEIBULL) {
+                const double lam = exp((double)fv);
+                if (!(lam > 0.0 && lam < (double)INFINITY)) { bad += 1; continue; }     // (the scale 0 or not finite; a NaN f_i too)
+                if (fabs(y) > 0.0) F += wn * -expm1(-exp(disp * (log(fabs(y)) - (double)fv)));
             } else if (LIK == TBNN_LIK_NEG_BINOMIAL) {
                 const double lam = exp((double)fv);
                 if (!(lam <= ENS_NB_MAX)) { bad += 1; continue; }
@@ -919,6 +935,9 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_cdf(const float* __restrict
 //             search in y, its slope the mixture density sum_i w_i / W (a / mu_i) x_i^(a - 1) e^-x_i / Gamma(a), x_i = a y / mu_i, formed in
 //             logs (infinite at 0 for a < 1: the step is then refused for the midpoint); the same stopping rule, the result the upper end.
 //             NaN: a NaN f_i, or a mean exp(f_i) that is 0 or not finite among the networks that count.
+//   Weibull   (disp = the shape k) Gamma's scheme: probs[np + j] holds g_p = (-log1p(-p))^(1/k) from the host, so exp(f_i) g_p is component
+//             i's own p-quantile; the same multiplicative bracket, verification and safeguarded Newton search, with the closed forms
+//             F_i(y) = -expm1(-u_i) and F_i'(y) = (k / y) exp(z_i - u_i), z_i = k (log y - f_i), u_i = exp(z_i); the same stopping rule, the upper end.
 template <int LIK, int QP>
 __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __restrict__ t, int m, long tot, const double* __restrict__ cst,
                                                                 const double* __restrict__ probs, int np, double smax, double* __restrict__ res,
@@ -926,9 +945,10 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
 #pragma clang fp contract(off)
     constexpr bool NEGB = LIK == TBNN_LIK_NEG_BINOMIAL;
     constexpr bool HET = LIK == TBNN_LIK_HETERO_GAUSSIAN;          // (a Gaussian kind below: the same bracket, search and stopping rule)
-    constexpr bool GAM = LIK == TBNN_LIK_GAMMA;
-    const bool gauss = LIK != TBNN_LIK_POISSON && !NEGB;      // (the continuous kinds: the Gaussian ones and Gamma)
-    const double lga = GAM ? lgamma(disp) : 0.0;
+    constexpr bool WEI = LIK == TBNN_LIK_WEIBULL;
+    constexpr bool GAM = LIK == TBNN_LIK_GAMMA || WEI;          // (the kinds on the positive axis: multiplicative bracket and pushes)
+    const bool gauss = LIK != TBNN_LIK_POISSON && !NEGB;      // (the continuous kinds: the Gaussian ones, Gamma and Weibull)
+    const double lga = GAM && !WEI ? lgamma(disp) : 0.0;
     const long ns = HET ? 2 * tot : tot;                  // floats between two networks' predictions of an element
     const double lr = NEGB ? log(disp) : 0.0;
     for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < tot; e += (long)gridDim.x * ENS_TB) {
@@ -950,7 +970,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
             for (int i = 0; i < m; ++i) {
                 const float fv = te[(size_t)i * ns];
                 const double wn = cst[i];
-                if (!HET && LIK != TBNN_LIK_GAMMA) bad += fv != fv;
+                if (!HET && !GAM) bad += fv != fv;
                 float gv = 0.f;
                 if (HET && wn > 0.0) { gv = te[(size_t)i * ns + tot]; bad += (fv != fv) + (gv != gv); }      // (weight 0: not looked at)
                 if (!(wn > 0.0)) continue;
@@ -1002,7 +1022,18 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     const double wn = cst[i];
                     if (!(wn > 0.0)) continue;
                     const double f = (double)te[(size_t)i * ns];
-                    if (GAM) {
+                    if (WEI) {
+#pragma unroll
+                        for (int j = 0; j < QP; ++j) {
+                            if (ph[j] >= 0) {
+                                // (the density's u e^-u as exp(z - u), z = log u: a far-off network, u = inf, adds 0 -- not inf * 0 -- and
+                                // the Newton step of the others stays alive)
+                                const double z = disp * (log(x[j]) - f), u = exp(z);
+                                F[j] += wn * -expm1(-u);
+                                D[j] += wn * ((disp / x[j]) * exp(z - u));
+                            }
+                        }
+                    } else if (GAM) {
                         const double am = disp * exp(-f);                                   // a / mu_i
 #pragma unroll
                         for (int j = 0; j < QP; ++j) {
@@ -1071,7 +1102,7 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_pred_quantiles(const float* __re
                     else a[j] = x[j];
                     const double w = b[j] - a[j];
                     if (F[j] == p || !(w > 2.0 * ens_ulp64(b[j]))) { ph[j] = -1; continue; }
-                    // F' = D / sqrt pi (Gamma: D itself)
+                    // F' = D / sqrt pi (Gamma, Weibull: D itself)
                     const double step = (p - F[j]) * (GAM ? 1.0 : 1.7724538509055160273) / D[j];
                     const double xn = x[j] + step + (0x1p-20 * step + copysign(2.0 * ens_ulp64(x[j]), step));
                     const bool newton = xn > a[j] && xn < b[j] && fabs(xn - x[j]) <= 0.5 * wd[j];

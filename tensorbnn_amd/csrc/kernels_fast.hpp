@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FAST_THREADS (FAST_WAVES * 64)
 
 // HACT: activation after every hidden layer, LACT: after the last layer,
-// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT / SHAPE_LIK_NEGBIN / SHAPE_LIK_HETERO / SHAPE_LIK_GAMMA; `false` / `true` still spell the first two) -- all
+// LIK: the likelihood (SHAPE_LIK_*: the Gaussian family, Bernoulli, categorical, Poisson, | SHAPE_LIK_STUDENT / SHAPE_LIK_NEGBIN / SHAPE_LIK_HETERO / SHAPE_LIK_GAMMA / SHAPE_LIK_WEIBULL; `false` / `true` still spell the first two) -- all
 // compile-time so the tile body is one straight-line block the scheduler can interleave.
 // Round 6: network.add takes any sequence of layers and activations (tensorBNN/network.py:173-191) -- a stack whose hidden layers do NOT all
 // carry the same activation has HACT = TBNN_ACT_PACKED | sum_l act_l << 3 l (hidden layer l = 0 .. NL - 2; at most 9 of them: fused_ops.hpp,
@@ -49,14 +49,16 @@ struct Shape {
     // SHAPE_LIK_GAMMA on the Poisson code: the Gamma term of lik_delta; nowhere else)
     static constexpr bool HET = (LIK_ & (3 | SHAPE_LIK_HETERO)) == (SHAPE_LIK_GAUSS | SHAPE_LIK_HETERO);
     static constexpr bool GAMMA = (LIK_ & (3 | SHAPE_LIK_NEGBIN | SHAPE_LIK_GAMMA)) == (SHAPE_LIK_POIS | SHAPE_LIK_GAMMA);
+    // (bits 8 and 16 together on the Poisson code: the Weibull term of lik_delta, targets right-censored by their sign)
+    static constexpr bool WEIB = (LIK_ & (3 | SHAPE_LIK_WEIBULL)) == (SHAPE_LIK_POIS | SHAPE_LIK_WEIBULL);
     static_assert(LIK_ >= SHAPE_LIK_GAUSS && (LIK_ & ~(3 | SHAPE_LIK_WEIGHTED | SHAPE_LIK_STUDENT | SHAPE_LIK_HETERO)) == 0, "unknown likelihood code");
     static_assert(!HET || ((LIK_ & (3 | SHAPE_LIK_STUDENT)) == SHAPE_LIK_GAUSS && LACT_ == TBNN_ACT_NONE && D[NL] == 2),
                   "heteroscedastic Gaussian: a flag on the plain Gaussian code, exactly 2 outputs (mean, log-sd), no last activation");
-    static_assert((LIK_ & SHAPE_LIK_HETERO) == 0 || HET || GAMMA,
-                  "bit 16 is a flag on the Gaussian code (heteroscedastic: SHAPE_LIK_HETERO) and on the Poisson code (Gamma: SHAPE_LIK_GAMMA), not with bit 8");
-    static_assert((LIK_ & SHAPE_LIK_STUDENT) == 0 || STUD || NEGB,
-                  "bit 8 is a flag on the Gaussian code (Student-t: SHAPE_LIK_STUDENT) and on the Poisson code (negative binomial: SHAPE_LIK_NEGBIN)");
-    static_assert(!(POIS || NEGB || GAMMA) || LACT_ == TBNN_ACT_NONE, "Poisson, negative binomial, Gamma: the last layer's output is the log of the mean (no last activation)");
+    static_assert((LIK_ & SHAPE_LIK_HETERO) == 0 || HET || GAMMA || WEIB,
+                  "bit 16 is a flag on the Gaussian code (heteroscedastic: SHAPE_LIK_HETERO) and on the Poisson code (Gamma: SHAPE_LIK_GAMMA; with bit 8: SHAPE_LIK_WEIBULL)");
+    static_assert((LIK_ & SHAPE_LIK_STUDENT) == 0 || STUD || NEGB || WEIB,
+                  "bit 8 is a flag on the Gaussian code (Student-t: SHAPE_LIK_STUDENT) and on the Poisson code (negative binomial: SHAPE_LIK_NEGBIN; with bit 16: SHAPE_LIK_WEIBULL)");
+    static_assert(!(POIS || NEGB || GAMMA || WEIB) || LACT_ == TBNN_ACT_NONE, "Poisson, negative binomial, Gamma, Weibull: the last layer's output is the log of the mean / scale (no last activation)");
     static_assert(!CAT || (LACT_ == TBNN_ACT_NONE && D[NL] >= 2), "categorical: logits (no last activation), at least 2 outputs");
     static_assert((HACT_ & TBNN_ACT_PACKED) == 0 || NL - 1 <= 9, "a packed activation code holds 9 hidden layers");
     static constexpr int act(int l) { return l == NL - 1 ? LACT_ : ((HACT_ & TBNN_ACT_PACKED) ? (HACT_ >> (3 * l)) & 7 : HACT_); }
@@ -610,20 +612,20 @@ template <class S>
 __device__ __forceinline__ float lik_inv_var(const NetDev& nd, float sigma) {
     if constexpr (S::STUD) return 1.f / (nd.lik_df * sigma * sigma);
     else if constexpr (S::NEGB) return logf(nd.lik_df);
-    else if constexpr (S::GAMMA) return 0.f;              // (not read: fixed_sd plays no part under TBNN_LIK_GAMMA)
+    else if constexpr (S::GAMMA || S::WEIB) return 0.f;   // (not read: fixed_sd plays no part under TBNN_LIK_GAMMA / TBNN_LIK_WEIBULL)
     else return 1.f / (sigma * sigma);
 }
 // the second constant of the prologue: nu + 1 (Student-t: the delta's factor; not read by the other kinds); a negative-binomial
-// instantiation: r itself; a Gamma one: the shape a
+// instantiation: r itself; a Gamma one: the shape a; a Weibull one: the shape k
 template <class S>
 __device__ __forceinline__ float lik_np1(const NetDev& nd) {
-    if constexpr (S::NEGB || S::GAMMA) return nd.lik_df;
+    if constexpr (S::NEGB || S::GAMMA || S::WEIB) return nd.lik_df;
     else return nd.lik_df + 1.f;
 }
 
 // likelihood for one output value: statistic (counted when `count`), returns dL/df * act'.  A weighted instantiation scales the
 // residual / the row's term and its derivative by the row weight `wt` before either enters a sum: weight 1 gives the unweighted bits.
-// inv_var: lik_inv_var; np1: lik_np1, read by a Student-t, negative-binomial or Gamma instantiation only.
+// inv_var: lik_inv_var; np1: lik_np1, read by a Student-t, negative-binomial, Gamma or Weibull instantiation only.
 template <class S>
 __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bool count, double& stat, float wt = 1.f, float np1 = 0.f) {
     static_assert(!S::CAT, "the categorical likelihood couples a row's outputs: cat_delta4 on the MFMA output tile, no per-element path");
@@ -676,6 +678,20 @@ __device__ __forceinline__ float lik_delta(float fi, float yy, float inv_var, bo
 #pragma clang fp contract(off)
         float term;
         const float d = np1 * gamma_term(fi, yy, &term);
+        if constexpr (S::WTD) {
+            if (count) stat += (double)(wt * term);
+            da = wt * d;
+        } else {
+            if (count) stat += (double)term;
+            da = d;
+        }
+    } else if constexpr (S::WEIB) {
+        // TBNN_LIK_WEIBULL: fi is the log of the scale, np1 holds the shape k (lik_np1) and the sign of yy the censoring flag; the term
+        // k d f + u, u = (|y| e^-f)^k (its sign and the constant: data_logp, kernels_hmc.hpp) and dL/df = k (u - d) by weibull_term
+        // (common.hpp; one hardware log2 and one hardware exp2, not contracted)
+#pragma clang fp contract(off)
+        float term;
+        const float d = np1 * weibull_term(fi, yy, np1, &term);
         if constexpr (S::WTD) {
             if (count) stat += (double)(wt * term);
             da = wt * d;

@@ -14,7 +14,7 @@
 // Math restated from the reference: dense W@a+b layer.py:278, activations
 // activationFunctions.py:36/49/62, Gaussian residual likelihood.py:88-94 +
 // BNN_functions.py:23-32, Bernoulli likelihood.py:226-236, categorical (softmax over a row's outputs:
-// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T), negative binomial (TBNN_LIK_NEG_BINOMIAL), Gamma (TBNN_LIK_GAMMA); reverse mode per
+// include/tbnn.h TBNN_LIK_CATEGORICAL), Poisson with a log link (TBNN_LIK_POISSON), Student-t (TBNN_LIK_STUDENT_T), negative binomial (TBNN_LIK_NEG_BINOMIAL), Gamma (TBNN_LIK_GAMMA), Weibull with right-censored targets (TBNN_LIK_WEIBULL); reverse mode per
 // SURVEY.md A12 (TF autodiff has no source in the tree).
 #pragma once
 #include "common.hpp"
@@ -136,6 +136,11 @@ __global__ __launch_bounds__(GEN_RB) void k_fwd_bwd_generic(
                     // fi is the log of the mean: f + y e^-f (its factor -a and the constant: data_logp), dL/df = a (y e^-f - 1); library expf
                     const float ye = y * expf(-fi);
                     if (valid) { stat += (double)(wt * (fi + ye)); da = wt * (nd.lik_df * (ye - 1.f)); }
+                } else if (nd.lik == TBNN_LIK_WEIBULL) {
+                    // fi is the log of the scale, the sign of y the censoring flag (y > 0: an event, d = 1), u = (|y| e^-f)^k: k d f + u (its
+                    // sign and the constant: data_logp), dL/df = k (u - d); library logf / expf
+                    const float kk = nd.lik_df, u = expf(kk * (logf(fabsf(y)) - fi));
+                    if (valid) { stat += (double)(wt * (y > 0.f ? kk * fi + u : u)); da = wt * (kk * (y > 0.f ? u - 1.f : u)); }
                 } else {
                     const float r = y - fi;
                     const float wr = wt * r;

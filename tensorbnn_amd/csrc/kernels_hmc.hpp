@@ -124,8 +124,12 @@ __global__ __launch_bounds__(256) void k_shard_unpack(int P, const double* __res
 // loses y e^-f < y 2^-126, which the ceiling keeps below 2^-26 next to the 1 it is subtracted from (include/tbnn.h TBNN_LIK_GAMMA).  fp64, a FIXED grid of LIKC_BLOCKS workgroups whose partials out[2 b] (and
 // counts out[2 b + 1]) the host adds in block order: the same bits from run to run.  w: one weight per row, null: weight 1.
 #define LIKC_BLOCKS 64
-enum { LIKC_COUNTS = 0, LIKC_GAMMA = 1 };
+// mode LIKC_WEIBULL (TBNN_LIK_WEIBULL, r = the shape k; the sign of a target is its censoring flag, y > 0 an event): C = -sum_i w_i sum_k
+// d_ik (log k + (k - 1) log |y_ik|), events alone, and the count of targets that are NaN, zero or have |y| outside [2^-100, 2^100] (the
+// floor hands the hardware log2 of weibull_term a normal fp32 number; the ceiling is Gamma's).
+enum { LIKC_COUNTS = 0, LIKC_GAMMA = 1, LIKC_WEIBULL = 2 };
 #define GAMMA_Y_MAX 0x1p100f
+#define WEIBULL_T_MIN 0x1p-100f
 __global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y, const float* __restrict__ w, long n, int d_out,
                                                      double* __restrict__ out, double r, int mode) {
     __shared__ double red[4];
@@ -133,12 +137,22 @@ __global__ __launch_bounds__(256) void k_pois_const(const float* __restrict__ Y,
     const long nel = n * d_out;
     const double lgr = r > 0.0 ? lgamma(r) : 0.0;
     const double g0 = mode == LIKC_GAMMA ? lgr - r * log(r) : 0.0;
+    const double lk = mode == LIKC_WEIBULL ? log(r) : 0.0;
     for (long el = (long)blockIdx.x * 256 + threadIdx.x; el < nel; el += (long)LIKC_BLOCKS * 256) {
         const float y = Y[el];
         if (mode == LIKC_GAMMA) {
             if (!(y > 0.f && y <= GAMMA_Y_MAX)) { bad += 1.0; continue; }
             const double wt = w ? (double)w[el / d_out] : 1.0;
             c += wt * (g0 - (r - 1.0) * log((double)y));
+            continue;
+        }
+        if (mode == LIKC_WEIBULL) {
+            const float t = fabsf(y);
+            if (!(t >= WEIBULL_T_MIN && t <= GAMMA_Y_MAX)) { bad += 1.0; continue; }
+            if (y > 0.f) {
+                const double wt = w ? (double)w[el / d_out] : 1.0;
+                c -= wt * (lk + (r - 1.0) * log((double)t));
+            }
             continue;
         }
         if (!(y >= 0.f && y < INFINITY)) { bad += 1.0; continue; }
@@ -175,6 +189,7 @@ __device__ __forceinline__ double data_logp(const NetDev& nd, const float* __res
     if (nd.lik == TBNN_LIK_POISSON) return stat - lik_c;                                   // the statistic is sum w (y f - e^f)
     if (nd.lik == TBNN_LIK_NEG_BINOMIAL) return stat - lik_c;                              // ... sum w (y log p + r log q)
     if (nd.lik == TBNN_LIK_GAMMA) return -(double)nd.lik_df * stat - lik_c;               // ... sum w (f + y e^-f), its factor -a
+    if (nd.lik == TBNN_LIK_WEIBULL) return -stat - lik_c;                                  // ... sum w (k d f + u), u = (|y| e^-f)^k
     if (nd.lik == TBNN_LIK_BERNOULLI || nd.lik == TBNN_LIK_CATEGORICAL) return stat;      // the statistic is the log-probability
     // heteroscedastic Gaussian: the statistic is sum w (-gc - 1/2 r^2 u), ONE term per row: the constant -1/2 log(2 pi) counts n rows
     if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) return stat - 0.5 * 1.8378770664093453 /* log 2pi */ * n;

@@ -365,7 +365,7 @@ __device__ __forceinline__ float lay_poisson(float fi, float y, double& stat, fl
 }
 
 // likelihood (restated as in kernels_generic.hpp): statistic (Gaussian: sum of squared residuals; Bernoulli, categorical, Poisson: log-prob;
-// Student-t: sum of log1p(r^2 / (nu s^2)); negative binomial: sum of y log p + r log q; Gamma: sum of f + y e^-f) and
+// Student-t: sum of log1p(r^2 / (nu s^2)); negative binomial: sum of y log p + r log q; Gamma: sum of f + y e^-f; Weibull: sum of k d f + u) and
 // dz of the last layer = dL/df * act'(f).  f, dz: blocks [row tile][TMl][16][16]; one thread per data row.  Only the real
 // (row, output) entries of dz are written: the padding was zeroed when the store was allocated and nothing else writes it.
 // wrow: one weight per row (tbnn_set_row_weights), null: weight 1 -- a row's residual / term and its dz are scaled by it before any sum.
@@ -438,6 +438,8 @@ __global__ __launch_bounds__(256) void k_lay_lik(NetDev nd, const float* __restr
                 da = negbin_elem(fi, y, stat, wt, nd.lik_df, nb_lr);
             } else if (nd.lik == TBNN_LIK_GAMMA) {
                 da = gamma_elem(fi, y, stat, wt, nd.lik_df);
+            } else if (nd.lik == TBNN_LIK_WEIBULL) {
+                da = weibull_elem(fi, y, stat, wt, nd.lik_df);
             } else {
                 const float res = y - fi;                                   // likelihood.py:88-94
                 const float wr = wt * res;
@@ -665,6 +667,8 @@ __global__ __launch_bounds__(256) void k_lay_tail(NetDev nd, LayPlan p, const fl
                             da = negbin_elem(fi, y, stat, wt, nd.lik_df, nb_lr);
                         } else if (nd.lik == TBNN_LIK_GAMMA) {
                             da = gamma_elem(fi, y, stat, wt, nd.lik_df);
+                        } else if (nd.lik == TBNN_LIK_WEIBULL) {
+                            da = weibull_elem(fi, y, stat, wt, nd.lik_df);
                         } else {
                             const float res = y - fi;                                  // likelihood.py:88-94
                             const float wr = wt * res;
@@ -814,6 +818,8 @@ __global__ __launch_bounds__(256) void k_lay_last(NetDev nd, LayPlan p, const fl
                         da = negbin_elem(fi, y, stat, wt, nd.lik_df, nb_lr);
                     } else if (nd.lik == TBNN_LIK_GAMMA) {
                         da = gamma_elem(fi, y, stat, wt, nd.lik_df);
+                    } else if (nd.lik == TBNN_LIK_WEIBULL) {
+                        da = weibull_elem(fi, y, stat, wt, nd.lik_df);
                     } else {
                         const float res = y - fi;                                  // likelihood.py:88-94
                         const float wr = wt * res;

@@ -105,7 +105,7 @@ struct tbnn_ctx {
     // (tbnn_set_lik_df; 0: not set -- a Student-t handle's own are nd.lik_df)
     float ens_df = 0.f;
     // TBNN_LIK_POISSON: C = sum_i w_i sum_k lgamma(y_ik + 1) of the staged rows (stage_lik_const; all chains share it); TBNN_LIK_NEG_BINOMIAL:
-    // ... (lgamma(y_ik + 1) + lgamma(r) - lgamma(y_ik + r)); TBNN_LIK_GAMMA: ... (lgamma(a) - a log a - (a - 1) log y_ik); 0 otherwise
+    // ... (lgamma(y_ik + 1) + lgamma(r) - lgamma(y_ik + r)); TBNN_LIK_GAMMA: ... (lgamma(a) - a log a - (a - 1) log y_ik); TBNN_LIK_WEIBULL: ... -d_ik (log k + (k - 1) log |y_ik|); 0 otherwise
     double lik_c = 0.0;
     int want = TBNN_KERNEL_AUTO;          // tbnn_net_desc::kernel (the re-selection of tbnn_set_row_weights follows it)
     // validation data (network.py:47-51) and the prediction buffer of tbnn_predict / tbnn_metrics
@@ -164,13 +164,13 @@ extern "C" int tbnn_device_count(void) {
 // the TBNN_LIK_* values (4, 6 and 7 are not among them: include/tbnn.h)
 static bool lik_known(int lik) {
     return (lik >= TBNN_LIK_GAUSSIAN && lik <= TBNN_LIK_CATEGORICAL) || lik == TBNN_LIK_POISSON || lik == TBNN_LIK_STUDENT_T || lik == TBNN_LIK_NEG_BINOMIAL ||
-           lik == TBNN_LIK_HETERO_GAUSSIAN || lik == TBNN_LIK_GAMMA;
+           lik == TBNN_LIK_HETERO_GAUSSIAN || lik == TBNN_LIK_GAMMA || lik == TBNN_LIK_WEIBULL;
 }
 // the count likelihoods: targets finite and >= 0, the last layer's output a log-rate, the constant of stage_lik_const
 static bool lik_counts(int lik) { return lik == TBNN_LIK_POISSON || lik == TBNN_LIK_NEG_BINOMIAL; }
-// the likelihoods whose log-probability has a constant that depends on the targets (stage_lik_const): the count ones and TBNN_LIK_GAMMA
-// (targets finite and > 0)
-static bool lik_has_const(int lik) { return lik_counts(lik) || lik == TBNN_LIK_GAMMA; }
+// the likelihoods whose log-probability has a constant that depends on the targets (stage_lik_const): the count ones, TBNN_LIK_GAMMA
+// (targets finite and > 0) and TBNN_LIK_WEIBULL (targets signed: nonzero, 2^-100 <= |y| <= 2^100)
+static bool lik_has_const(int lik) { return lik_counts(lik) || lik == TBNN_LIK_GAMMA || lik == TBNN_LIK_WEIBULL; }
 // degrees of freedom a Student-t term can be formed with (and a dispersion a negative-binomial one can)
 static bool df_ok(float df) { return df > 0.f && df < INFINITY; }
 
@@ -210,6 +210,11 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
             return fail(-1, "the Gamma likelihood takes the last layer's outputs as log-means (log link): the last layer must carry no activation");
         if (!df_ok(d->lik_df)) return fail(-1, "the Gamma likelihood needs lik_df (its shape a) finite and > 0");
     }
+    if (d->likelihood == TBNN_LIK_WEIBULL) {
+        if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
+            return fail(-1, "the Weibull likelihood takes the last layer's outputs as log-scales (log link): the last layer must carry no activation");
+        if (!df_ok(d->lik_df)) return fail(-1, "the Weibull likelihood needs lik_df (its shape k) finite and > 0");
+    }
     if (d->likelihood == TBNN_LIK_HETERO_GAUSSIAN) {
         if (nd.out[nd.nl - 1] != 2) return fail(-1, "the heteroscedastic Gaussian likelihood needs exactly 2 outputs: mean and log-sd");
         if (nd.act[nd.nl - 1] != TBNN_ACT_NONE)
@@ -227,7 +232,7 @@ static int build_netdev(const tbnn_net_desc* d, NetDev& nd) {
         if (!df_ok(d->lik_df)) return fail(-1, "the Student-t likelihood needs lik_df (its degrees of freedom) finite and > 0");
         nd.lik_df = d->lik_df;
     }
-    if (nd.lik == TBNN_LIK_NEG_BINOMIAL || nd.lik == TBNN_LIK_GAMMA) nd.lik_df = d->lik_df;
+    if (nd.lik == TBNN_LIK_NEG_BINOMIAL || nd.lik == TBNN_LIK_GAMMA || nd.lik == TBNN_LIK_WEIBULL) nd.lik_df = d->lik_df;
     return 0;
 }
 
@@ -458,17 +463,17 @@ static int alloc_workspace(tbnn_ctx* h, long n) {
     return 0;
 }
 
-// Poisson, negative binomial and Gamma (TBNN_LIK_POISSON, TBNN_LIK_NEG_BINOMIAL, TBNN_LIK_GAMMA; any other likelihood: C = 0, nothing runs): the constant C of the n rows dY (device) under the row weights dw
-// (device, null: none) -- k_pois_const, its partials added here in block order -- and the refusal of targets that are not counts (Gamma: not finite and > 0, or above 2^100).  Called
+// Poisson, negative binomial, Gamma and Weibull (TBNN_LIK_POISSON, TBNN_LIK_NEG_BINOMIAL, TBNN_LIK_GAMMA, TBNN_LIK_WEIBULL; any other likelihood: C = 0, nothing runs): the constant C of the n rows dY (device) under the row weights dw
+// (device, null: none) -- k_pois_const, its partials added here in block order -- and the refusal of targets that are not counts (Gamma: not finite and > 0, or above 2^100; Weibull: NaN, zero or |y| outside [2^-100, 2^100]).  Called
 // by everything that stages rows or weights BEFORE it changes the handle: a refusal leaves the handle as it was.
 static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY, const float* dw, long n, double* C) {
     *C = 0.0;
     if (!lik_has_const(h->nd.lik)) return 0;
-    const bool nb = h->nd.lik == TBNN_LIK_NEG_BINOMIAL, gam = h->nd.lik == TBNN_LIK_GAMMA;
+    const bool nb = h->nd.lik == TBNN_LIK_NEG_BINOMIAL, gam = h->nd.lik == TBNN_LIK_GAMMA, wei = h->nd.lik == TBNN_LIK_WEIBULL;
     Buf<double> part;
     HIPCHK(part.alloc(2 * LIKC_BLOCKS));
-    hipLaunchKernelGGL(k_pois_const, dim3(LIKC_BLOCKS), dim3(256), 0, h->stream, dY, dw, n, h->nd.d_out, (double*)part, nb || gam ? (double)h->nd.lik_df : 0.0,
-                       gam ? (int)LIKC_GAMMA : (int)LIKC_COUNTS);
+    hipLaunchKernelGGL(k_pois_const, dim3(LIKC_BLOCKS), dim3(256), 0, h->stream, dY, dw, n, h->nd.d_out, (double*)part, nb || gam || wei ? (double)h->nd.lik_df : 0.0,
+                       gam ? (int)LIKC_GAMMA : wei ? (int)LIKC_WEIBULL : (int)LIKC_COUNTS);
     HIPCHK(hipGetLastError());
     double host[2 * LIKC_BLOCKS];
     HIPCHK(hipMemcpyAsync(host, part, sizeof(host), hipMemcpyDeviceToHost, h->stream));
@@ -477,6 +482,8 @@ static int stage_lik_const(tbnn_ctx* h, const std::string& who, const float* dY,
     for (int b = 0; b < LIKC_BLOCKS; ++b) { c += host[2 * b]; bad += host[2 * b + 1]; }
     if (bad > 0.0 && gam)
         return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are zero, negative, not finite or above the ceiling: under the Gamma likelihood targets must be finite and > 0 and at most 2^100 (1.2676506e30)");
+    if (bad > 0.0 && wei)
+        return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are zero, not finite or out of range: under the Weibull likelihood a target is a signed time (y > 0 an event, y < 0 censored at |y|), finite, nonzero and 2^-100 <= |y| <= 2^100");
     if (bad > 0.0)
         return fail(-1, who + ": " + std::to_string((long long)bad) + " target(s) are negative or not finite: the " + (nb ? "negative-binomial" : "Poisson") + " likelihood takes counts (finite, >= 0)");
     *C = c;
@@ -792,7 +799,8 @@ static int launch_fwd_bwd(tbnn_ctx* h, const float* q, const float* eta, const S
                                h->pitch, P, (float*)nullptr, h->shard_buf);
         hipLaunchKernelGGL(k_shard_pack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, dense ? (const float*)row : (const float*)nullptr,
                            (const double*)h->pstat, h->grid, h->shard_buf,
-                           h->nd.lik == TBNN_LIK_GAMMA ? -h->lik_c / (double)h->nd.lik_df : h->lik_c);   // (Gamma: data_logp scales the statistic by -a)
+                           h->nd.lik == TBNN_LIK_GAMMA ? -h->lik_c / (double)h->nd.lik_df :             // (Gamma: data_logp scales the statistic by -a)
+                           h->nd.lik == TBNN_LIK_WEIBULL ? -h->lik_c : h->lik_c);                       // (Weibull: ... by -1)
         NCCLCHK(g_rccl.AllReduce(h->shard_buf, h->shard_buf, (size_t)P + 1, ncclDouble, ncclSum, h->shard->comm, h->stream));
         hipLaunchKernelGGL(k_shard_unpack, dim3((P + 255) / 256), dim3(256), 0, h->stream, P, (const double*)h->shard_buf, row, h->pstat_red);
     }
@@ -886,6 +894,7 @@ extern "C" int tbnn_logp_grad(tbnn_handle h, const float* theta, const float* et
         double s = 0; for (double v : ps) s += v;
         *stat = s - lik_const(h);                                                          // (Poisson: the log-likelihood with its constant)
         if (nd.lik == TBNN_LIK_GAMMA) *stat = -(double)nd.lik_df * s - lik_const(h);       // (... as data_logp forms it from sum w (f + y e^-f))
+        if (nd.lik == TBNN_LIK_WEIBULL) *stat = -s - lik_const(h);                         // (... from sum w (k d f + u))
         if (nd.lik == TBNN_LIK_HETERO_GAUSSIAN) *stat -= 0.5 * 1.8378770664093453 /* log 2pi */ * rows_total(h);      // (... as data_logp adds it)
     }
     return 0;
@@ -1156,6 +1165,7 @@ extern "C" int tbnn_set_lik_df(tbnn_handle h, float df) {
     if (h->nd.lik == TBNN_LIK_STUDENT_T) return fail(-1, "set_lik_df: a Student-t handle takes its degrees of freedom from the descriptor's lik_df");
     if (h->nd.lik == TBNN_LIK_NEG_BINOMIAL) return fail(-1, "set_lik_df: a negative-binomial handle takes its dispersion from the descriptor's lik_df");
     if (h->nd.lik == TBNN_LIK_GAMMA) return fail(-1, "set_lik_df: a Gamma handle takes its shape from the descriptor's lik_df");
+    if (h->nd.lik == TBNN_LIK_WEIBULL) return fail(-1, "set_lik_df: a Weibull handle takes its shape from the descriptor's lik_df");
     if (!df_ok(df)) return fail(-1, "set_lik_df: df must be finite and > 0");
     h->ens_df = df;
     return 0;

@@ -74,6 +74,7 @@ LIK_GAUSS, LIK_BERN, LIK_CAT, LIK_POIS = 0, 1, 2, 3      # csrc/common.hpp: SHAP
 LIK_WEIGHTED = 4                            # csrc/common.hpp: SHAPE_LIK_WEIGHTED -- the flag bit of kernels that take row weights
 LIK_STUDENT = 8                             # csrc/common.hpp: SHAPE_LIK_STUDENT -- the flag bit, on LIK_GAUSS, of the Student-t data term
 LIK_GAMMA = 16                              # csrc/common.hpp: SHAPE_LIK_GAMMA -- bit 16 on LIK_POIS: the Gamma data term (on LIK_GAUSS the bit is hetero)
+LIK_WEIBULL = 8 | 16                        # csrc/common.hpp: SHAPE_LIK_WEIBULL -- both bits on LIK_POIS: the Weibull data term with right-censored targets
 LIK_NEGBIN = 8                              # csrc/common.hpp: SHAPE_LIK_NEGBIN -- the same bit on LIK_POIS: the negative-binomial data term
 LIK_HETERO = 16                             # csrc/common.hpp: SHAPE_LIK_HETERO -- on LIK_GAUSS: the heteroscedastic Gaussian (2 outputs, one term per row)
 
@@ -84,6 +85,7 @@ def lik_code(likelihood: int, weighted: bool = False) -> int:
     from . import _native as nat
     code = {nat.LIK_BERNOULLI: LIK_BERN, nat.LIK_CATEGORICAL: LIK_CAT, nat.LIK_POISSON: LIK_POIS,
             nat.LIK_STUDENT_T: LIK_STUDENT | LIK_GAUSS, nat.LIK_NEG_BINOMIAL: LIK_NEGBIN | LIK_POIS, nat.LIK_GAMMA: LIK_GAMMA | LIK_POIS,
+            nat.LIK_WEIBULL: LIK_WEIBULL | LIK_POIS,
             nat.LIK_HETERO_GAUSSIAN: LIK_HETERO | LIK_GAUSS}.get(int(likelihood), LIK_GAUSS)
     return code | (LIK_WEIGHTED if weighted else 0)
 
@@ -116,7 +118,8 @@ def families(dims, lik: int = LIK_GAUSS) -> list:
     # (nor the Student-t / negative-binomial flag: the Gaussian residual, the Poisson log-rate under another element-wise loss)
     # (nor the heteroscedastic flag where it applies: the VALU last layer of every family holds both outputs of a row in one lane --
     # lik_pair, csrc/kernels_fast.hpp; tbnn_create refuses any other output count)
-    # (bit 16 on the Poisson code is the Gamma flag, LIK_GAMMA: another element-wise loss on the log-mean, Poisson's reach)
+    # (bit 16 on the Poisson code is the Gamma flag, LIK_GAMMA: another element-wise loss on the log-mean, Poisson's reach; bits 8 and 16
+    # together LIK_WEIBULL, a third one on the log-scale)
     if lik & LIK_HETERO and lik & 3 == LIK_GAUSS and dims[-1] != 2:
         return []
     if lik & ~(LIK_WEIGHTED | LIK_STUDENT | LIK_HETERO) == LIK_CAT:
@@ -289,6 +292,8 @@ def source(dims, hact, lact, lik, family) -> str:
                LIK_POIS | LIK_NEGBIN | LIK_WEIGHTED: "SHAPE_LIK_POIS | SHAPE_LIK_NEGBIN | SHAPE_LIK_WEIGHTED",
                LIK_POIS | LIK_GAMMA: "SHAPE_LIK_POIS | SHAPE_LIK_GAMMA",
                LIK_POIS | LIK_GAMMA | LIK_WEIGHTED: "SHAPE_LIK_POIS | SHAPE_LIK_GAMMA | SHAPE_LIK_WEIGHTED",
+               LIK_POIS | LIK_WEIBULL: "SHAPE_LIK_POIS | SHAPE_LIK_WEIBULL",
+               LIK_POIS | LIK_WEIBULL | LIK_WEIGHTED: "SHAPE_LIK_POIS | SHAPE_LIK_WEIBULL | SHAPE_LIK_WEIGHTED",
                LIK_HETERO: "SHAPE_LIK_HETERO", LIK_HETERO | LIK_WEIGHTED: "SHAPE_LIK_HETERO | SHAPE_LIK_WEIGHTED"}.get(int(lik), str(int(lik)))
     shape = f"Shape<{hact}, {lact}, {lik_arg}, {', '.join(map(str, dims))}>"
     if family == "wide":

@@ -263,3 +263,49 @@ class GammaLikelihood(Likelihood):
 
     def calcultateLogProb(self, *argv, **kwargs):
         return [np.float32(0) for _ in range(len(kwargs["hypers"]))]
+
+
+class WeibullLikelihood(Likelihood):
+    """Times to an event, some rows right-censored (survival data: time to failure, to relapse, to churn): the last dense layer's outputs
+    (no activation after it) are the LOGS of the Weibull scales, lambda = exp(f) (the accelerated-failure-time parameterisation), and the
+    shape k is fixed (WeibullLikelihood(shape=k)); shape = 1 is the exponential model.  Censoring travels in the SIGN of the target:
+    y > 0 is an event observed at time y, y < 0 a row still running at time |y| (`encode` builds such targets).  With t = |y| and
+    u = (t exp(-f))^k, per (row, output): an event gives log p = log k + (k - 1) log t - k f - u, a censored row log S = -u
+    (include/tbnn.h TBNN_LIK_WEIBULL); targets finite, nonzero, 2^-100 <= |y| <= 2^100.  No hyper-parameter."""
+    kind = nat.LIK_WEIBULL
+
+    def __init__(self, *argv, **kwargs):
+        self.hypers = []
+        self.shape = float(kwargs["shape"])
+        if not (self.shape > 0 and math.isfinite(self.shape)):
+            raise ValueError("WeibullLikelihood needs shape > 0 and finite")
+        self.mainProbsInHypers = False
+
+    @staticmethod
+    def encode(times, observed):
+        """the signed float32 targets of the event times `times` (> 0) and the flags `observed` (true: the event was seen at that time;
+        false: the row was right-censored then): +t for an event, -t for a censored row, in the shape of `times`"""
+        t = np.asarray(times, dtype=np.float32)
+        d = np.broadcast_to(np.asarray(observed).astype(bool), t.shape)
+        if not (np.all(np.isfinite(t)) and np.all(t > 0)):
+            raise ValueError("WeibullLikelihood.encode: times must be finite and > 0 (the sign of a target is its censoring flag)")
+        return np.where(d, t, -t).astype(np.float32)
+
+    def logDensity(self, f, y):
+        """element by element in float64, at log-scales f: the log density of an event target (y > 0), the log survival function of a
+        right-censored one (y < 0)"""
+        k = self.shape
+        f = np.asarray(f, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        lt = np.log(np.abs(y))
+        u = np.exp(k * (lt - f))
+        return np.where(y > 0, (math.log(k) + (k - 1.0) * lt - k * f) - u, -u)
+
+    def makeResponseLikelihood(self, *argv, **kwargs):
+        """the term per (output, row) in float64, [d_out, rows] as GammaLikelihood's; the sum is the data term"""
+        f = np.asarray(kwargs["predict"](True, argv[0]), dtype=np.float64)        # [d_out, rows]: log-scales
+        y = np.asarray(kwargs["realVals"], dtype=np.float64).reshape(-1, f.shape[0]).T
+        return self.logDensity(f, y)
+
+    def calcultateLogProb(self, *argv, **kwargs):
+        return [np.float32(0) for _ in range(len(kwargs["hypers"]))]

@@ -168,10 +168,10 @@ class network(object):
         lik = likelihood if likelihood is not None else getattr(self, "likelihood", None)
         kind = lik.kind if lik is not None else nat.LIK_FIXED_GAUSSIAN
         sd = float(getattr(lik, "fixed_sd", 0.1)) if lik is not None else 0.1
-        # StudentTLikelihood: its degrees of freedom; NegativeBinomialLikelihood: its dispersion; GammaLikelihood: its shape (all travel as lik_df)
+        # StudentTLikelihood: its degrees of freedom; NegativeBinomialLikelihood: its dispersion; GammaLikelihood and WeibullLikelihood: their shape (all travel as lik_df)
         df = (float(getattr(lik, "df", 0.0)) if kind == nat.LIK_STUDENT_T else
               float(getattr(lik, "dispersion", 0.0)) if kind == nat.LIK_NEG_BINOMIAL else
-              float(getattr(lik, "shape", 0.0)) if kind == nat.LIK_GAMMA else 0.0)
+              float(getattr(lik, "shape", 0.0)) if kind in (nat.LIK_GAMMA, nat.LIK_WEIBULL) else 0.0)
         w = self.trainWeights
         key = (tuple(map(tuple, self._dense)), kind, sd, df, None if w is None else hash(np.asarray(w, np.float32).tobytes()))
         if self._chain is None or self._chain_key != key:
@@ -438,7 +438,7 @@ class network(object):
                              device=self.device, seed=self.seed, chain_id=self.chain_id, kernel=self.kernel,
                              lik_df=(float(getattr(likelihood, "df", 0.0)) if likelihood.kind == nat.LIK_STUDENT_T else
                                      float(getattr(likelihood, "dispersion", 0.0)) if likelihood.kind == nat.LIK_NEG_BINOMIAL else
-                                     float(getattr(likelihood, "shape", 0.0)) if likelihood.kind == nat.LIK_GAMMA else 0.0))
+                                     float(getattr(likelihood, "shape", 0.0)) if likelihood.kind in (nat.LIK_GAMMA, nat.LIK_WEIBULL) else 0.0))
         C = grp.C
         if verbose:
             print("tensorbnn_amd: fused kernel", grp.kernel_name, "x", C, "chains")

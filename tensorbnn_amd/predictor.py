@@ -137,7 +137,7 @@ class predictor(object):
         from .layer import _multivariate_log_prob
         from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, FixedGaussianLikelihood, GammaLikelihood,
                                  HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood,
-                                 log_softmax)
+                                 WeibullLikelihood, log_softmax)
         preds = self.predict(trainX, n)
         y = np.asarray(trainY, dtype=np.float32)
         out = []
@@ -150,7 +150,7 @@ class predictor(object):
             if isinstance(likelihood, CategoricalLikelihood):
                 out.append(np.float32(np.sum(real * log_softmax(cur, axis=1))))     # sum_rows sum_k y_k log softmax_k
                 continue
-            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood, NegativeBinomialLikelihood, GammaLikelihood)):
+            if isinstance(likelihood, (PoissonLikelihood, StudentTLikelihood, NegativeBinomialLikelihood, GammaLikelihood, WeibullLikelihood)):
                 terms = likelihood.makeResponseLikelihood(None, predict=lambda *_a, _f=cur.T: _f, realVals=real)
                 out.append(np.float32(np.sum(terms)))                           # sum of y f - exp(f) - lgamma(y + 1) / of the t / negative-binomial log densities
                 continue
@@ -170,10 +170,10 @@ class predictor(object):
 
     def _transform(self, transform):
         """the name of the transform asked for; None: the one the predictor's likelihood implies"""
-        from .likelihood import CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood, PoissonLikelihood
+        from .likelihood import CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, WeibullLikelihood
         if transform is None:
             transform = ("softmax" if isinstance(self.likelihood, CategoricalLikelihood) else
-                         "exp" if isinstance(self.likelihood, (PoissonLikelihood, NegativeBinomialLikelihood, GammaLikelihood)) else "none")
+                         "exp" if isinstance(self.likelihood, (PoissonLikelihood, NegativeBinomialLikelihood, GammaLikelihood, WeibullLikelihood)) else "none")
         if transform not in self._TRANSFORMS:
             raise ValueError(f"transform must be one of {sorted(self._TRANSFORMS)} or None")
         return transform
@@ -211,8 +211,20 @@ class predictor(object):
         mean plus the expected noise variance; E[s^2] = Var[s] + E[s]^2 from a second reduction on the device under the exp transform.
         Under a GammaLikelihood the default transform is exp too (the mean mu itself), and noiseVariance=True (transform None or "exp",
         sd = 1, mean = 0) returns (E[mu], Var[mu] + E[mu^2] / shape): the posterior spread of the mean plus the expected Gamma noise
-        variance mu^2 / shape, added on the host as countVariance is."""
-        from .likelihood import GammaLikelihood, HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood
+        variance mu^2 / shape, added on the host as countVariance is.
+        Under a WeibullLikelihood the default transform is exp as well (the scale lambda), and noiseVariance=True (the same conditions)
+        returns (E[m_i], Var[m_i] + E[v_i]) of the time to the event: each network's mean m_i = lambda_i Gamma(1 + 1/k) and variance
+        v_i = lambda_i^2 (Gamma(1 + 2/k) - Gamma(1 + 1/k)^2), from the moments of lambda the device returns."""
+        from .likelihood import GammaLikelihood, HeteroscedasticGaussianLikelihood, NegativeBinomialLikelihood, WeibullLikelihood
+        if noiseVariance and isinstance(self.likelihood, WeibullLikelihood):
+            if transform not in (None, "exp") or float(sd) != 1.0 or float(mean) != 0.0 or countVariance:
+                raise ValueError("noiseVariance under a WeibullLikelihood needs the scale itself: transform None or 'exp', sd = 1, mean = 0, no "
+                                 "countVariance")
+            picked, w = self._picked(n, weights)
+            m, v = self._ensure_chain().ensemble_moments(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w, xform=nat.XFORM_EXP)
+            k = self.likelihood.shape
+            g1, g2 = math.gamma(1.0 + 1.0 / k), math.gamma(1.0 + 2.0 / k)
+            return g1 * m, g1 * g1 * v + (g2 - g1 * g1) * (v + m * m)
         if noiseVariance and isinstance(self.likelihood, GammaLikelihood):
             if transform not in (None, "exp") or float(sd) != 1.0 or float(mean) != 0.0 or countVariance:
                 raise ValueError("noiseVariance under a GammaLikelihood needs the mean itself: transform None or 'exp', sd = 1, mean = 0, no "
@@ -391,9 +403,9 @@ class predictor(object):
         """the standard deviation of every n-th network under a Gaussian kind of likelihood, float32 [picked]: the fixed sd, or each
         network's saved last hyper (0.1 where none was saved), read as _data_logprob reads it; the scale of a StudentTLikelihood; None
         for the other likelihoods"""
-        from .likelihood import FixedGaussianLikelihood, GammaLikelihood, NegativeBinomialLikelihood, StudentTLikelihood
+        from .likelihood import FixedGaussianLikelihood, GammaLikelihood, NegativeBinomialLikelihood, StudentTLikelihood, WeibullLikelihood
         picked = len(range(0, self.numNetworks, n))
-        if isinstance(lik, GammaLikelihood):
+        if isinstance(lik, (GammaLikelihood, WeibullLikelihood)):
             # no scale; its shape set on the forward chain (a fixed-sd Gaussian handle) before the reduction that judges under it
             self._ensure_chain().set_lik_df(lik.shape)
             return None
@@ -431,17 +443,20 @@ class predictor(object):
         deviation (its saved last hyper as logPredictiveDensity reads it, or the fixed sd), under a PoissonLikelihood the counts'
         Poisson(exp(f_i)) and under a NegativeBinomialLikelihood their negative binomial of mean exp(f_i) and the likelihood's
         dispersion, whose quantile is the smallest count k with F(k) >= p; under a GammaLikelihood the Gamma of mean exp(f_i) and
-        the likelihood's shape, a continuous distribution on y > 0 inverted as the Gaussian mixture is.  likelihood None: the predictor's own.  weights: one
+        the likelihood's shape, a continuous distribution on y > 0 inverted as the Gaussian mixture is, and under a WeibullLikelihood the
+        Weibull of scale exp(f_i) and the likelihood's shape, the distribution of the time to the event, by the same search.  likelihood None: the predictor's own.  weights: one
         per picked network, e.g. what reweight returns.  The result is q * sd + mean, the de-normalisation of the metrics, applied on
-        the host in fp64: sd > 0, and counts and Gamma targets take none (sd = 1, mean = 0).  predictQuantiles gives the credible quantiles of the
+        the host in fp64: sd > 0, and counts, Gamma targets and Weibull times take none (sd = 1, mean = 0).  predictQuantiles gives the credible quantiles of the
         network's output instead; Bernoulli and categorical likelihoods are refused (predictMoments returns a label's probability)."""
-        from .likelihood import GammaLikelihood, NegativeBinomialLikelihood, PoissonLikelihood
+        from .likelihood import GammaLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, WeibullLikelihood
         lik = self._predictive_likelihood(likelihood)
         sd, mean = float(sd), float(mean)
         if not sd > 0.0:
             raise ValueError("sd must be > 0 (a negative scale would turn the quantiles round)")
         if isinstance(lik, GammaLikelihood) and (sd != 1.0 or mean != 0.0):
             raise ValueError("Gamma targets are not de-normalised: sd = 1, mean = 0 under a GammaLikelihood")
+        if isinstance(lik, WeibullLikelihood) and (sd != 1.0 or mean != 0.0):
+            raise ValueError("Weibull times are not de-normalised: sd = 1, mean = 0 under a WeibullLikelihood")
         if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) and (sd != 1.0 or mean != 0.0):
             raise ValueError("counts are not de-normalised: sd = 1, mean = 0 under a PoissonLikelihood or NegativeBinomialLikelihood")
         picked, w = self._picked(n, weights)
@@ -464,7 +479,8 @@ class predictor(object):
         """The PIT values of the rows: the predictive CDF of predictiveQuantiles at the observed targets realVals, float64 [d_out, rows]
         -- uniform on (0, 1) over held-out rows when the predictive distribution is calibrated.  Targets in the networks' own
         (normalised) units.  Under a PoissonLikelihood or NegativeBinomialLikelihood the pair (F(y - 1), F(y)): a count's PIT value lies
-        anywhere on its step.  Under a GammaLikelihood F alone, as under the Gaussian kinds: the CDF is continuous."""
+        anywhere on its step.  Under a GammaLikelihood F alone, as under the Gaussian kinds: the CDF is continuous.  Under a WeibullLikelihood F alone
+        too, read at |y|: the sign of a target is its censoring flag, and on a censored row the PIT value lies in [F, 1]."""
         from .likelihood import NegativeBinomialLikelihood, PoissonLikelihood
         lik = self._predictive_likelihood(likelihood)
         picked, w = self._picked(n, weights)
@@ -473,11 +489,36 @@ class predictor(object):
                                            likelihood=lik.kind, sd=self._network_sd(lik, n), weights=w)
         return (Fb, F) if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) else F
 
+    def survival(self, X, times, n=1, weights=None, likelihood=None):
+        """The posterior-mean survival curve of every row of X under a WeibullLikelihood: S(t) = 1 - F(t), the probability that the event
+        has not happened by time t, float64 [len(times), d_out, rows].  times: finite and > 0.  n, weights, likelihood: as
+        predictiveCDF's.  (A host loop of predictiveCDF over the times, one device reduction per time: there is no time grid on the
+        device.)"""
+        from .likelihood import WeibullLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, WeibullLikelihood):
+            raise ValueError("survival needs a WeibullLikelihood: the survival curve is that of a time to an event")
+        ts = np.asarray(times, dtype=np.float64).reshape(-1)
+        if ts.size < 1 or not (np.all(np.isfinite(ts)) and np.all(ts > 0)):
+            raise ValueError("survival: times must be finite and > 0, at least one")
+        x = np.asarray(X, dtype=np.float32)
+        rows = x.shape[0]
+        d_out = self._ensure_chain().d_out
+        out = []
+        for t in ts:                                                   # the host loop: one predictiveCDF per time
+            y = np.full((rows, d_out), np.float32(t), dtype=np.float32)
+            out.append(1.0 - self.predictiveCDF(x, y, n=n, weights=weights, likelihood=lik))
+        return np.stack(out, axis=0)
+
     # ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
     def _crps_likelihood(self, likelihood):
         from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood,
-                                 PoissonLikelihood, StudentTLikelihood)
+                                 PoissonLikelihood, StudentTLikelihood, WeibullLikelihood)
         lik = self.likelihood if likelihood is None else likelihood
+        if isinstance(lik, WeibullLikelihood):
+            raise ValueError("the CRPS is not built for a WeibullLikelihood (no kernel forms the pair term of two Weibull distributions, and a "
+                             "censored row has no observed value to score); logPredictiveDensity, loo, waic, predictiveInterval, "
+                             "predictiveCDF and survival are")
         if isinstance(lik, GammaLikelihood):
             raise ValueError("the CRPS is not built for a GammaLikelihood (the pair term of two Gamma distributions has no closed form); "
                              "logPredictiveDensity, loo, waic, predictiveInterval and predictiveCDF are")
@@ -549,8 +590,12 @@ class predictor(object):
 
     # ---- classification: entropy split, votes (tbnn_ensemble_uncertainty) and calibration of the posterior-mean classifier ----
     def _label_likelihood(self, likelihood):
-        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood
+        from .likelihood import BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood, WeibullLikelihood
         lik = self.likelihood if likelihood is None else likelihood
+        if isinstance(lik, WeibullLikelihood):
+            raise ValueError("the entropy split and the votes are those of a label, not of a WeibullLikelihood's time to an event: "
+                             "predictMoments(noiseVariance=True) separates the Weibull noise from the posterior spread of the scale, and "
+                             "predictiveInterval / predictiveCDF / survival describe the time")
         if isinstance(lik, GammaLikelihood):
             raise ValueError("the entropy split and the votes are those of a label, not of a GammaLikelihood's positive target: "
                              "predictMoments(noiseVariance=True) separates the Gamma noise from the posterior spread of the mean, and "
