@@ -515,6 +515,45 @@ int tbnn_ensemble_predictive(tbnn_handle h, const float* thetas, int32_t m, int6
 int tbnn_ensemble_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* sd,
                        const float* net_w, int which, const float* X, const float* Y, int64_t n, int noise,
                        double* crps_out, double* error_out, double* spread_out);
+/* The CRPS of a predictive mixture of COUNT distributions, by a sweep over the support (tbnn_ensemble_crps refuses counts: their pair term
+ * has no closed form).  Arguments as tbnn_ensemble_crps's, without sd and noise.  An element is an (output, row) pair; f_i, w_i, W and
+ * omega_i = w_i / W as there.  Component i is Poisson(exp(f_i)) (TBNN_LIK_POISSON) or the negative binomial of mean mu_i = exp(f_i) and
+ * dispersion r (TBNN_LIK_NEG_BINOMIAL), with CDF I_q(r, k + 1), q = r / (r + mu_i), as tbnn_ensemble_predictive reads it; r is the
+ * descriptor's lik_df on a negative-binomial handle, else what tbnn_set_lik_df set.  Only these two codes are accepted, whatever the
+ * handle's own likelihood.  With F(k) = sum_i omega_i F_i(k) and S(k) = 1 - F(k) the three outputs are
+ *   error  = sum_{0 <= k < y} F(k) + sum_{k >= y} S(k)          = E|Y - y|
+ *   spread = sum_{k >= 0} F(k) S(k)                             = 1/2 E|Y - Y'|
+ *   crps   = sum_{k >= 0} (F(k) - 1{y <= k})^2                  = error - spread,
+ * the planes of tbnn_ensemble_crps with the same meaning.  y is the target as staged; a non-integer y enters through 1{y <= k} only, a
+ * negative y puts every k on the upper side.  Each of the three is summed on its own from terms >= 0 (crps: F^2 below y, S^2 from y on),
+ * so crps equals error - spread to rounding, not bit for bit.
+ * Window rule.  Network i has a window [lo_i, hi_i]: the run of k around its mode whose pmf is at least e^-80 = 1.8e-35.  Below the window
+ * F_i is taken as 0, above it as 1.  The pmf is anchored once, by exp of its log at the mode, and moved by its ratio recurrence (Poisson
+ * p(k+1) = p(k) mu / (k+1); negative binomial p(k+1) = p(k) (k + r) / (k + 1) (1 - q)) outward to find the window, then inward again in the
+ * sweep; no incomplete gamma or beta function is evaluated.  Below y, F_i(k) is the ascending sum of the pmf from lo_i; from y on, S_i(k)
+ * is the sum of the pmf from hi_i DOWN to k + 1, the sweep descending from the top of the range: neither tail is formed as 1 - (1 - x).
+ * Truncation bound.  Outside its window a component's pmf is below e^-80 and falls at least geometrically, at a ratio rho < 1 - 2^-16 for
+ * every element within the ceilings below; what F_i = 0 / S_i = 0 leaves out of any of the three sums is at most e^-80 / (1 - rho)^2 < 1e-25
+ * per component, times omega_i.  Inside, a pmf carries the rounding of its recurrence: a relative 2^-52 per step from the mode.
+ * Order of sums.  All fp64, not contracted.  Network i belongs to lane g = i mod 8 of its element's eight.  The support is walked in tiles of
+ * 16 values of k, the lower side ascending from the smallest lo_i, the upper side descending from the largest hi_i; tiles no window
+ * touches are jumped and enter as (length) x (C, C (1 - C), C^2), C the constant mixture there.  At one k a lane adds omega_i F_i(k) over
+ * its networks in ascending i, the networks wholly passed last as one sum; the eight lanes are added in lane order.  The terms of k go to
+ * lane (k - tile start) mod 8, which keeps three compensated (Kahan) sums in the order walked, lane 0 taking the jumps; at the end the
+ * eight lanes are added in order, compensated.  The same bits from run to run, whatever the grid and the row blocks.
+ * NaN and ceilings (all three outputs of the element): a target that is not finite or above 2^20; a NaN f_i under any network; among the
+ * networks that count (omega_i > 0) a rate that is not finite or above 2^20 -- both kinds (tbnn_ensemble_predictive allows Poisson 2^30; here
+ * the cost of an element grows with sqrt(rate) m, so the lower ceiling is deliberate); a window that reaches more than 2^21 above its mode, or an
+ * element whose range (the union of the windows and y) spans more than 2^21 values of k -- heavy negative-binomial tails at small r and
+ * large mean: such an element is NaN, never truncated.  Networks of weight 0 are not looked at otherwise.
+ * crps_out, error_out, spread_out: host [d_out][n] doubles each, or NULL; at least one.  The rows are cut into blocks as for
+ * tbnn_ensemble_quantiles; the sweep keeps 40 bytes per (network, element) beside the 4 of the prediction, counted into the same budget.
+ * The work per element is the sum of its windows' widths (about 26 sqrt(rate) for Poisson) plus m / 8 per tile walked: linear in m.
+ * Refused, with nothing written: every output NULL, X without Y, any likelihood code but the two (by name), m < 1, m > 4096, n not matching
+ * the staged rows, TBNN_LIK_NEG_BINOMIAL without a dispersion, weights breaking the rules above, 11 m d_out 64 > 2^28. */
+int tbnn_ensemble_count_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
+                             int which, const float* X, const float* Y, int64_t n, double* crps_out, double* error_out,
+                             double* spread_out);
 /* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
  * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
  * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).

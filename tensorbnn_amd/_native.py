@@ -126,6 +126,7 @@ SYMBOLS = [
     ("tbnn_ensemble_predictive", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp,
                                            _dp]),
     ("tbnn_ensemble_crps", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_int, _dp, _dp, _dp]),
+    ("tbnn_ensemble_count_crps", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp, _dp]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
@@ -654,6 +655,20 @@ class Chain:
         out = {k: np.empty((od, n), dtype=np.float64) for k in ("crps", "error", "spread")}
         _check(lib.tbnn_ensemble_crps(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(sdp), _p(w), int(which), _p(xp), _p(yp), n,
                                       1 if noise else 0, *[_pd(out[k]) for k in ("crps", "error", "spread")]))
+        return out
+
+    def ensemble_count_crps(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, weights=None):
+        """continuous ranked probability score of a predictive mixture of COUNT distributions at the targets, by a sweep over the support
+        on the device (tbnn_ensemble_count_crps; the definition is in include/tbnn.h): a dict of float64 arrays [d_out, rows] -- crps,
+        error = E|Y - y| and spread = 1/2 E|Y - Y'| under the mixture over the networks of Poisson(exp(f_i)) (LIK_POISSON) or the negative
+        binomial of mean exp(f_i) (LIK_NEG_BINOMIAL; its dispersion: the chain's lik_df, or set_lik_df).  likelihood None: the chain's own;
+        any other kind is refused.  weights: one per network or None (equal); Y None with X None: the staged targets.  NaN: a target or a
+        rate above 2^20, a NaN prediction, a support wider than 2^21.  At most 4096 networks"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        yp, _sd, lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, likelihood)
+        out = {k: np.empty((self.d_out, n), dtype=np.float64) for k in ("crps", "error", "spread")}
+        _check(lib.tbnn_ensemble_count_crps(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n,
+                                            *[_pd(out[k]) for k in ("crps", "error", "spread")]))
         return out
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,

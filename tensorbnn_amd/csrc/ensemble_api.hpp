@@ -735,7 +735,7 @@ static int crps_check(const std::string& who, int likelihood, float fixed_sd, in
         return fail(-1, who + ": the CRPS is a score of a real-valued prediction; a label's uncertainty and calibration: tbnn_ensemble_uncertainty");
     if (likelihood == TBNN_LIK_POISSON || likelihood == TBNN_LIK_NEG_BINOMIAL)
         return fail(-1, who + ": the CRPS of a count distribution is not built (the pair term E|Y_i - Y_j| of two count distributions has no closed "
-                              "form: a sum of (F(k) - 1{y <= k})^2 over the support, another kernel)");
+                              "form: a sum of (F(k) - 1{y <= k})^2 over the support, another kernel: tbnn_ensemble_count_crps)");
     if (likelihood == TBNN_LIK_GAMMA)
         return fail(-1, who + ": the CRPS under TBNN_LIK_GAMMA is not built (the pair term E|Y_i - Y_j| of two Gamma distributions has no closed form)");
     if (likelihood == TBNN_LIK_WEIBULL)
@@ -804,6 +804,83 @@ extern "C" int tbnn_ensemble_crps(tbnn_handle h, const float* thetas, int32_t m,
                 if (outs[k]) ENS_TRY(ens_copy_planes(h, outs[k], r0, rows, res + (size_t)k * rbk, r, (size_t)od));
             return 0;
         });
+}
+
+static const char* ens_lik_name(int likelihood) {
+    switch (likelihood) {
+        case TBNN_LIK_GAUSSIAN: return "TBNN_LIK_GAUSSIAN";
+        case TBNN_LIK_FIXED_GAUSSIAN: return "TBNN_LIK_FIXED_GAUSSIAN";
+        case TBNN_LIK_BERNOULLI: return "TBNN_LIK_BERNOULLI";
+        case TBNN_LIK_CATEGORICAL: return "TBNN_LIK_CATEGORICAL";
+        case TBNN_LIK_STUDENT_T: return "TBNN_LIK_STUDENT_T";
+        case TBNN_LIK_HETERO_GAUSSIAN: return "TBNN_LIK_HETERO_GAUSSIAN";
+        case TBNN_LIK_GAMMA: return "TBNN_LIK_GAMMA";
+        case TBNN_LIK_WEIBULL: return "TBNN_LIK_WEIBULL";
+    }
+    return nullptr;
+}
+
+// The CRPS of a mixture of count distributions (definition: include/tbnn.h; kernel: k_ens_count_crps).  The refusals are crps_check's, in
+// its order, with the likelihood rule turned round; the sweep's scratch, ENS_CC_PLANES doubles per (network, element), is counted into the
+// row blocks' budget beside the predictions.
+extern "C" int tbnn_ensemble_count_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
+                                        int which, const float* X, const float* Y, int64_t n, double* crps_out, double* error_out,
+                                        double* spread_out) {
+    NEED(h);
+    const std::string who = "ensemble_count_crps";
+    const int d_out = h->nd.d_out;
+    if (!crps_out && !error_out && !spread_out) return fail(-1, who + ": every output is null");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    const bool negb = likelihood == TBNN_LIK_NEG_BINOMIAL;
+    if (likelihood != TBNN_LIK_POISSON && !negb) {
+        const char* name = ens_lik_name(likelihood);
+        if (!name) return fail(-1, who + ": unknown likelihood");
+        return fail(-1, who + ": " + name + " is not a count likelihood (TBNN_LIK_POISSON and TBNN_LIK_NEG_BINOMIAL are; the Gaussian kinds: "
+                              "tbnn_ensemble_crps)");
+    }
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (m > ENS_CRPS_MAX_M)
+        return fail(-1, who + ": m = " + std::to_string(m) + " exceeds " + std::to_string(ENS_CRPS_MAX_M) + " networks (the work per element grows with m)");
+    const size_t extra = (size_t)ENS_CC_PLANES * sizeof(double) * (size_t)m * (size_t)d_out;
+    ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out + extra / sizeof(float), nullptr, "rows of all m networks and the sweep's scratch"));
+    double W = 0.0, disp = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    if (negb) {
+        // the dispersion: the descriptor's lik_df on a negative-binomial handle, what tbnn_set_lik_df set on any other
+        const float r = h->nd.lik == TBNN_LIK_NEG_BINOMIAL ? h->nd.lik_df : h->ens_df;
+        if (!df_ok(r)) return fail(-1, who + ": the CRPS under TBNN_LIK_NEG_BINOMIAL needs the dispersion: call tbnn_set_lik_df on this handle first");
+        disp = (double)r;
+    }
+    std::vector<double> cst((size_t)m);
+    for (int32_t i = 0; i < m; ++i) cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
+    ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
+    const float* dYrows = nullptr;
+    Buf<float> dY;
+    Buf<double> dCst, dRes, dScr;
+    long rbk = 0;
+    return ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
+        [&](long rb) -> int {
+            rbk = rb * d_out;
+            HIPCHK(dRes.alloc(3 * (size_t)rbk));
+            HIPCHK(dScr.alloc((size_t)ENS_CC_PLANES * (size_t)m * (size_t)rbk));
+            ENS_TRY(ens_upload(h, dCst, cst.data(), cst.size()));
+            return ens_stage_targets(h, which, Y, n, dY, &dYrows);
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            const long tot = r * d_out;
+            const dim3 grid((unsigned)std::min<long>((tot + ENS_CE - 1) / ENS_CE, 65536)), tb(ENS_TB);
+            const float* y = dYrows + (size_t)r0 * d_out;
+            const double* c = dCst;
+            double* res = dRes;
+            double* scr = dScr;
+            if (negb) hipLaunchKernelGGL(k_ens_count_crps<TBNN_LIK_NEG_BINOMIAL>, grid, tb, 0, h->stream, t, (int)m, tot, r, d_out, y, c, disp, scr, res, rbk);
+            else hipLaunchKernelGGL(k_ens_count_crps<TBNN_LIK_POISSON>, grid, tb, 0, h->stream, t, (int)m, tot, r, d_out, y, c, disp, scr, res, rbk);
+            HIPCHK(hipGetLastError());
+            double* const outs[3] = {crps_out, error_out, spread_out};
+            for (int k = 0; k < 3; ++k)
+                if (outs[k]) ENS_TRY(ens_copy_planes(h, outs[k], r0, rows, res + (size_t)k * rbk, r, (size_t)d_out));
+            return 0;
+        }, extra);
 }
 
 // M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)

@@ -41,6 +41,10 @@
 //             include/tbnn.h, tbnn_ensemble_crps) from its closed form, a sum over all PAIRS of networks.  The one kernel here that is not
 //             one thread per element: ENS_CL lanes share an element, each holds one network of a tile in registers and walks the other
 //             tile's networks from LDS (layout and summation order: at the kernel).  All fp64, contraction off, no atomics.
+//   count crps  the same block, log-rates: k_ens_count_crps sums (F(k) - 1{y <= k})^2 over the support of a mixture of Poisson or negative-binomial
+//             components (definition: include/tbnn.h, tbnn_ensemble_count_crps), whose pair term has no closed form.  The same eight lanes
+//             per element; each steps its networks' pmf recurrences over a tile of k in registers, the per-k mixtures meet in LDS
+//             (windows, tiles, gaps and summation order: at the kernel).  All fp64, contraction off, no atomics.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -61,6 +65,10 @@
 #define ENS_CE 32       // elements a workgroup of the pair kernel owns
 #define ENS_CL (ENS_TB / ENS_CE)   // lanes that share an element there: one network of a tile each, so ENS_CL == ENS_CT
 #define ENS_CRPS_MAX_M 4096   // networks of tbnn_ensemble_crps at the most: a launch is quadratic in m (a limit of the interface)
+#define ENS_CK 16       // values of k per tile of the support sweep (k_ens_count_crps): two per lane of an element
+#define ENS_CC_CUT 1.8048513878454153e-35   // e^-80: a component's pmf below it ends its window (the exit of ens_gamma_q / ens_betainc)
+#define ENS_CC_RANGE 2097152.0              // 2^21: the values of k an element's sweep (or one window above its mode) may span; beyond it NaN
+#define ENS_CC_PLANES 5                     // scratch of the sweep per (network, element), in doubles: the window and four state planes
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
 __device__ __forceinline__ float ens_xform(float f, int xform) {
@@ -1436,5 +1444,225 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_crps(const float* __restrict__ t
             res[rbk + e] = anybad ? (double)NAN : E;
             res[2 * rbk + e] = anybad ? (double)NAN : S;
         }
+    }
+}
+
+// ---- the CRPS of a mixture of count distributions: a sweep over the support (tbnn_ensemble_count_crps) ----
+// Component i of an element is Poisson(mu_i) or the negative binomial of mean mu_i and dispersion `disp`, mu_i = exp(f_i).  With F the
+// mixture CDF, S = 1 - F and ky = max(ceil(y), 0):  error = sum_{k < ky} F(k) + sum_{k >= ky} S(k),  spread = sum_k F(k) S(k),
+// crps = sum_{k < ky} F(k)^2 + sum_{k >= ky} S(k)^2 -- three sums of terms >= 0, each accumulated on its own.
+//
+// Windows.  Network i has a window [lo_i, hi_i] around its mode: the k whose pmf is at least e^-80 (ENS_CC_CUT).  Below it F_i is taken as
+// 0, above it as 1.  The pmf is anchored ONCE, by exp of ens_pois_logpref / ens_beta_logpref at the mode, and walked outward by its ratio
+// recurrence (Poisson p(k + 1) = p(k) mu / (k + 1); negative binomial p(k + 1) = p(k) (k + r) / (k + 1) (1 - q)) until it falls below the
+// cut: that walk gives lo_i, hi_i and the pmf at both ends.  No incomplete gamma or beta function is called.  A window that reaches more
+// than 2^21 above its mode, or an element whose range (the union of the windows and ky) spans more than 2^21, is NaN (ENS_CC_RANGE).
+// The two sides.  The lower side, k = kmin .. ky - 1, is swept ASCENDING with F_i(k) = sum_{lo_i <= j <= k} p_i(j), started from p_i(lo_i).
+// The upper side is swept DESCENDING from the top of the range: at x = kmax .. ky + 1 the term is S(x - 1), with
+// S_i(x - 1) = sum_{x <= j <= hi_i} p_i(j), started from p_i(hi_i).  Both are sums of positive terms in growing order: no tail is formed
+// as 1 - (1 - x).  In the sweep coordinate u (u = k ascending; u = -x descending) the two sides are one piece of code.
+//
+// Layout.  A workgroup owns ENS_CE = 32 consecutive elements, thread tid the element el = tid % 32 as lane g = tid / 32 of its ENS_CL = 8;
+// lane g owns the networks i = g, g + 8, ...  A prediction is read from memory once per element, in the setup (32 neighbours: 128
+// contiguous bytes).  What a network needs later lives in a scratch of ENS_CC_PLANES doubles per (network, element), [plane][m][tot],
+// read and written coalesced over the element: (lo, hi) as two ints, the pmf at lo (then the running pmf of the ascending side), the
+// pmf at hi (then that of the descending side), the running F_i or S_i, and the network's own factor of the recurrence (mu_i or 1 - q_i).
+// The sweep goes in tiles of ENS_CK = 16 positions.  Per tile a lane walks its networks in ascending i: one wholly behind the tile adds
+// its weight to a constant, one wholly ahead is skipped (its start is remembered), one that touches the tile has its (p, F_i) loaded into
+// REGISTERS, stepped over the 16 positions -- the position's own factor of the ratio comes from a register table built once per tile, so
+// a step is two multiplications and two additions -- and stored back if its window goes on.  The lane's 16 partial mixtures (registers)
+// then meet in LDS.
+// LDS: part[8][16][32] doubles (32 KiB), cgs[8][32] and nxs[8][32] (the lanes' constants and next starts), red[3][8][32] and redbad[8][32]
+// for the closing sums.  Every access has el as the fast index: a wave touches 32 consecutive doubles per (lane, position), its two
+// half-waves two such rows -- no bank conflict.  A tile costs two barriers: one (__syncthreads_or, which also tells the workgroup whether any
+// element still sweeps) before part is written, one before it is read.  After the second, lane g sums positions g and g + 8 of the tile
+// over the eight lanes IN LANE ORDER and adds the three terms to its own compensated sums (ens_kahan).
+// Gaps.  The next tile starts at the smallest start among the networks ahead, or right behind this tile if a window goes on; positions
+// jumped over are a gap in which the mixture is the constant C = the weights of the networks behind, and lane 0 adds
+// (gap length) x (C, C (1 - C), C^2) in O(1).  So the cost is the sum of the windows' widths plus, per tile walked, a look at each of the
+// lane's networks -- a network at rate 2 and one at rate 4000 do not cost 4000 steps of the first.
+// Order of every sum: a lane's partial mixture over its networks in ascending i, then its constant; the mixture over the lanes g = 0 .. 7;
+// a lane's three sums over the ascending side's tiles, then the descending side's, in the order walked (lane 0: a gap before the tile
+// behind it); at the end the eight lanes in order (ens_kahan).  Nothing depends on the element's place in its workgroup, the grid or the
+// row block: the same bits from run to run.
+// NaN (all three): a target that is not finite or above 2^20; a NaN f_i under any network; among the networks that count a rate that is
+// not finite or above 2^20 (ENS_NB_MAX -- both kinds: the cost grows with sqrt(rate) m); the range rule above.  Networks of weight 0 are
+// not looked at otherwise.
+template <int LIK>
+__device__ __forceinline__ double ens_cc_pmf(double k, double mu, double disp, double q, double pp) {
+#pragma clang fp contract(off)
+    if (LIK == TBNN_LIK_POISSON) return k == 0.0 ? exp(-mu) : exp(ens_pois_logpref(k, mu));
+    // q^r pp^(k + 1) / B(r, k + 1) = pmf(k) pp (r + k)
+    return exp(ens_beta_logpref(disp, k + 1.0, q, pp)) / (pp * (disp + k));
+}
+
+// the position's factor of the step that ARRIVES at x: from x - 1 (UP) or from x + 1; the network's factor (mu or 1 - q, or 1 over it) apart
+template <int LIK, bool UP>
+__device__ __forceinline__ double ens_cc_ratio(double x, double disp) {
+#pragma clang fp contract(off)
+    if (LIK == TBNN_LIK_POISSON) return UP ? 1.0 / x : x + 1.0;
+    return UP ? (x - 1.0 + disp) / x : (x + 1.0) / (x + disp);
+}
+
+// one side of an element's sweep, positions u = us .. ue in the sweep coordinate (UP: u = k; else u = -x); sums[6]: the lane's three
+// compensated sums (value, compensation).  Every thread of the workgroup calls it: the barriers are the workgroup's.
+template <int LIK, bool UP>
+__device__ __forceinline__ void ens_cc_sweep(int el, int g, bool skip, long e, int m, long tot, const double* __restrict__ cst,
+                                             const int2* __restrict__ win, double* __restrict__ st, double disp, double us, double ue,
+                                             double (*part)[ENS_CK][ENS_CE], double (*cgs)[ENS_CE], double (*nxs)[ENS_CE], double* sums) {
+#pragma clang fp contract(off)
+    const size_t plane = (size_t)m * tot;
+    double* __restrict__ stp = st + (UP ? 0 : plane);           // the anchor at the window's near end, then the running pmf
+    double* __restrict__ stv = st + 2 * plane;                  // the running F_i (S_i)
+    const double* __restrict__ stc = st + 3 * plane;            // mu_i (1 - q_i)
+    bool fin = skip || us > ue;
+    double u0 = us, udone = us - 1.0;
+    for (;;) {
+        if (!__syncthreads_or(!fin)) break;
+        if (!fin) {
+            const bool closing = u0 > ue;                       // the pass behind the last position: the constant of the last gap alone
+            double acc[ENS_CK], rt[ENS_CK];
+#pragma unroll
+            for (int j = 0; j < ENS_CK; ++j) {
+                acc[j] = 0.0;
+                rt[j] = closing ? 0.0 : ens_cc_ratio<LIK, UP>(UP ? u0 + (double)j : -(u0 + (double)j), disp);
+            }
+            double cg = 0.0, nx = (double)INFINITY;
+            const double ulast = u0 + (double)(ENS_CK - 1);
+            for (int i = g; i < m; i += ENS_CL) {
+                const double wi = cst[i];
+                if (!(wi > 0.0)) continue;
+                const size_t o = (size_t)i * tot + e;
+                const int2 w2 = win[o];
+                const double su = UP ? (double)w2.x : -(double)w2.y, tu = UP ? (double)w2.y : -(double)w2.x;
+                if (tu < u0) { cg += wi; continue; }             // wholly behind: F_i = 1 (S_i = 1)
+                if (su > ue || closing) continue;                // never reached on this side
+                if (su > ulast) { nx = fmin(nx, su); continue; }
+                double p = stp[o], V = su < u0 ? stv[o] : 0.0;
+                const double c = UP ? stc[o] : 1.0 / stc[o];
+#pragma unroll
+                for (int j = 0; j < ENS_CK; ++j) {
+                    const double u = u0 + (double)j;
+                    if (u == su) V = p;                          // (p holds the anchor)
+                    else if (u > su && u <= tu) { p = p * (rt[j] * c); V += p; }
+                    acc[j] += wi * (u > tu ? 1.0 : (u >= su ? V : 0.0));
+                }
+                if (tu > ulast) { stp[o] = p; stv[o] = V; nx = fmin(nx, ulast + 1.0); }
+            }
+#pragma unroll
+            for (int j = 0; j < ENS_CK; ++j) part[g][j][el] = acc[j] + cg;
+            cgs[g][el] = cg; nxs[g][el] = nx;
+        }
+        __syncthreads();
+        if (!fin) {
+            double C = 0.0, nxt = (double)INFINITY;
+#pragma unroll
+            for (int l = 0; l < ENS_CL; ++l) { C += cgs[l][el]; nxt = fmin(nxt, nxs[l][el]); }
+            const double gap = u0 - udone - 1.0;
+            if (g == 0 && gap > 0.0) {
+                ens_kahan(gap * C, sums[0], sums[1]);
+                ens_kahan(gap * (C * (1.0 - C)), sums[2], sums[3]);
+                ens_kahan(gap * (C * C), sums[4], sums[5]);
+            }
+#pragma unroll
+            for (int jj = 0; jj < ENS_CK / ENS_CL; ++jj) {
+                const int j = g + jj * ENS_CL;
+                if (u0 + (double)j <= ue) {
+                    double F = 0.0;
+#pragma unroll
+                    for (int l = 0; l < ENS_CL; ++l) F += part[l][j][el];
+                    ens_kahan(F, sums[0], sums[1]);
+                    ens_kahan(F * (1.0 - F), sums[2], sums[3]);
+                    ens_kahan(F * F, sums[4], sums[5]);
+                }
+            }
+            if (u0 > ue) fin = true;
+            else { udone = fmin(u0 + (double)(ENS_CK - 1), ue); u0 = fmin(nxt, ue + 1.0); }
+        }
+    }
+}
+
+// t: the block [m][tot] of untransformed predictions (log-rates), tot = d_out r; Y: the block's targets [r][d_out]; cst[m]: w_i / W; disp:
+// the dispersion (negative binomial; not read otherwise); scratch: ENS_CC_PLANES m tot doubles; res[3][rbk]: crps, error, spread
+template <int LIK>
+__global__ __launch_bounds__(ENS_TB) void k_ens_count_crps(const float* __restrict__ t, int m, long tot, long r, int d_out, const float* __restrict__ Y,
+                                                            const double* __restrict__ cst, double disp, double* __restrict__ scratch,
+                                                            double* __restrict__ res, long rbk) {
+#pragma clang fp contract(off)
+    static_assert(ENS_CL * ENS_CE == ENS_TB && ENS_CK % ENS_CL == 0, "eight lanes per element, the tile's positions dealt out evenly");
+    constexpr bool NEGB = LIK == TBNN_LIK_NEG_BINOMIAL;
+    __shared__ double part[ENS_CL][ENS_CK][ENS_CE];
+    __shared__ double cgs[ENS_CL][ENS_CE], nxs[ENS_CL][ENS_CE];
+    __shared__ double red[3][ENS_CL][ENS_CE];
+    __shared__ int redbad[ENS_CL][ENS_CE];
+    const int el = threadIdx.x % ENS_CE, g = threadIdx.x / ENS_CE;
+    const size_t plane = (size_t)m * tot;
+    int2* __restrict__ win = reinterpret_cast<int2*>(scratch);
+    double* __restrict__ st = scratch + plane;
+    const double lr = NEGB ? log(disp) : 0.0;
+    for (long e0 = (long)blockIdx.x * ENS_CE; e0 < tot; e0 += (long)gridDim.x * ENS_CE) {
+        const long e = e0 + el;
+        const bool live = e < tot;
+        const float yf = live ? Y[(size_t)(e % r) * d_out + e / r] : 0.f;
+        const double y = (double)yf, ky = y > 0.0 ? ceil(y) : 0.0;
+        int bad = !(fabsf(yf) < INFINITY) || y > ENS_NB_MAX;
+        double kmin = (double)INFINITY, kmax = -1.0;
+        for (int i = g; i < m && live; i += ENS_CL) {
+            const float fv = t[(size_t)i * tot + e];
+            bad += fv != fv;
+            if (!(cst[i] > 0.0)) continue;
+            const double f = (double)fv, mu = exp(f);
+            double q = 0.0, pp = 0.0;
+            if (NEGB) ens_nb_qp(lr, f, q, pp);
+            if (!(mu <= ENS_NB_MAX)) { bad += 1; continue; }
+            const double cu = NEGB ? pp : mu;
+            double lo = 0.0, hi = 0.0, pl = 1.0, ph = 1.0;       // (a rate that underflowed to 0: all the mass at k = 0)
+            if (cu > 0.0) {
+                const double mode = NEGB ? (disp > 1.0 ? floor((disp - 1.0) * mu / disp) : 0.0) : floor(mu);
+                const double pm = ens_cc_pmf<LIK>(mode, mu, disp, q, pp), icu = 1.0 / cu;
+                lo = hi = mode; pl = ph = pm;
+                while (lo > 0.0) {
+                    const double pn = pl * (ens_cc_ratio<LIK, false>(lo - 1.0, disp) * icu);
+                    if (pn < ENS_CC_CUT) break;
+                    lo -= 1.0; pl = pn;
+                }
+                for (;;) {
+                    const double pn = ph * (ens_cc_ratio<LIK, true>(hi + 1.0, disp) * cu);
+                    if (!(pn >= ENS_CC_CUT)) break;
+                    hi += 1.0; ph = pn;
+                    if (hi - mode > ENS_CC_RANGE) { bad += 1; break; }
+                }
+            }
+            const size_t o = (size_t)i * tot + e;
+            win[o] = make_int2((int)lo, (int)hi);
+            st[o] = pl; st[plane + o] = ph; st[3 * plane + o] = cu;
+            kmin = fmin(kmin, lo); kmax = fmax(kmax, hi);
+        }
+        nxs[g][el] = kmin; cgs[g][el] = kmax; redbad[g][el] = bad;
+        __syncthreads();
+        int anybad = 0;
+#pragma unroll
+        for (int l = 0; l < ENS_CL; ++l) { kmin = fmin(kmin, nxs[l][el]); kmax = fmax(kmax, cgs[l][el]); anybad += redbad[l][el]; }
+        if (!(fmax(kmax, ky) - fmin(kmin, ky) <= ENS_CC_RANGE)) anybad = 1;
+        const bool skip = !live || anybad;
+        double sums[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        // (the sweep's first barrier stands between the reads above and its writes to cgs and nxs)
+        ens_cc_sweep<LIK, true>(el, g, skip, e, m, tot, cst, win, st, disp, kmin, ky - 1.0, part, cgs, nxs, sums);
+        ens_cc_sweep<LIK, false>(el, g, skip, e, m, tot, cst, win, st, disp, -kmax, -(ky + 1.0), part, cgs, nxs, sums);
+        red[0][g][el] = sums[0]; red[1][g][el] = sums[2]; red[2][g][el] = sums[4];
+        __syncthreads();
+        if (g == 0 && live) {
+            double E = 0.0, Ec = 0.0, S = 0.0, Sc = 0.0, Cr = 0.0, Cc = 0.0;
+#pragma unroll
+            for (int l = 0; l < ENS_CL; ++l) {
+                ens_kahan(red[0][l][el], E, Ec);
+                ens_kahan(red[1][l][el], S, Sc);
+                ens_kahan(red[2][l][el], Cr, Cc);
+            }
+            res[e] = anybad ? (double)NAN : Cr;
+            res[rbk + e] = anybad ? (double)NAN : E;
+            res[2 * rbk + e] = anybad ? (double)NAN : S;
+        }
+        __syncthreads();                                        // (red and redbad are rewritten by the next elements' setup)
     }
 }

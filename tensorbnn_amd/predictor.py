@@ -526,7 +526,8 @@ class predictor(object):
             raise ValueError("the CRPS is a score of a real-valued prediction: predictUncertainty and calibration judge a label")
         if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)):
             raise ValueError("the CRPS is not built for a PoissonLikelihood or NegativeBinomialLikelihood (the pair term of two count "
-                             "distributions has no closed form); logPredictiveDensity, loo, waic and predictiveCDF are")
+                             "distributions has no closed form: countCrps sums over the support instead); logPredictiveDensity, loo, waic and "
+                             "predictiveCDF are")
         if isinstance(lik, StudentTLikelihood):
             raise ValueError("the CRPS is not built for a StudentTLikelihood (the pair term of two t distributions has no closed form); "
                              "logPredictiveDensity, loo and waic are")
@@ -547,6 +548,28 @@ class predictor(object):
         ch = self._ensure_chain()
         res = ch.ensemble_crps(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
                                likelihood=lik.kind, sd=self._network_sd(lik, n) if noise else None, weights=w, noise=bool(noise))
+        res.update(self._crps_summary(res["crps"]))
+        return res
+
+    def countCrps(self, inputMatrix, realVals, n=1, weights=None, likelihood=None):
+        """The continuous ranked probability score of the rows under a PoissonLikelihood or NegativeBinomialLikelihood: crps's score for
+        counts, in the units of the count.  The predictive distribution is predictiveQuantiles' -- the mixture over every n-th network of
+        Poisson(exp(f_i)), or of the negative binomial of mean exp(f_i) and the likelihood's dispersion -- and the score the sum of
+        (F(k) - 1{y <= k})^2 over the support, on the device (the definition, its windows and ceilings are in include/tbnn.h,
+        tbnn_ensemble_count_crps).  Returns crps's dict -- crps, error, spread float64 [d_out, rows], mean_crps, se, n_bad -- so compareCrps
+        takes it: e.g. Poisson against negative binomial, or two dispersions, over the same rows.  NaN elements: a target or a rate above
+        2^20, a support wider than 2^21 (a heavy tail at a small dispersion and a large mean).  Any other likelihood raises ValueError (the
+        Gaussian kinds: crps)."""
+        from .likelihood import NegativeBinomialLikelihood, PoissonLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)):
+            raise ValueError("countCrps scores counts: a PoissonLikelihood or NegativeBinomialLikelihood (the Gaussian kinds: crps; not "
+                             f"{type(lik).__name__})")
+        picked, w = self._picked(n, weights)
+        ch = self._ensure_chain()
+        self._network_sd(lik, n)                                       # (a NegativeBinomialLikelihood: its dispersion onto the forward chain)
+        res = ch.ensemble_count_crps(picked, Y=np.asarray(realVals, dtype=np.float32), X=np.asarray(inputMatrix, dtype=np.float32),
+                                     likelihood=lik.kind, weights=w)
         res.update(self._crps_summary(res["crps"]))
         return res
 

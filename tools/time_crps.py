@@ -12,7 +12,11 @@ measured forward_many over all rows.  The work is linear in the rows, so the ext
 full size, which the host cannot hold.
 Prints one JSON line per shape with the library's build id, the pair terms per call, and the largest deviation between the two routes on
 the host's rows in units of 2^-53 (error + spread), with the device's own deviation from the 40-digit restatement (crps_ref.ref40) on the
-first three rows.  Needs a gfx950 device; there is no fallback."""
+first three rows.
+`--counts`: the same for predictor.countCrps (tbnn_ensemble_count_crps, the support sweep k_ens_count_crps) at the flagship shape under a
+PoissonLikelihood and a NegativeBinomialLikelihood(dispersion=5), the network's outputs read as log-rates (the last layer scaled to a third and centred on log 5: moderate rates), targets drawn from a randomly
+picked network's Poisson; the host route is forward_many followed by the SciPy restatement tests/count_crps_ref.py row by row, EXTRAPOLATED
+from COUNT_HOST_ROWS rows in the same way.  Needs a gfx950 device; there is no fallback."""
 import json
 import os
 import statistics
@@ -60,9 +64,50 @@ def memory_predictor(dims, thetas):
     return p
 
 
+COUNT_HOST_ROWS = 32
+
+
+def counts():
+    """one JSON line per count likelihood at the flagship shape"""
+    import count_crps_ref as cc
+    from tensorbnn_amd.likelihood import NegativeBinomialLikelihood, PoissonLikelihood
+    dims, n = SHAPES["flagship"]
+    rng = np.random.default_rng(0)
+    X = rng.standard_normal((n, dims[0])).astype(np.float32)
+    base = np.concatenate([(rng.standard_normal(o * i + o) * (2.0 / i) ** 0.5) for i, o in zip(dims[:-1], dims[1:])])
+    thetas = (base[None, :] + 0.1 * rng.standard_normal((M, base.size))).astype(np.float32)
+    # moderate rates: the last layer (the final dims[-2] weights and the bias) scaled to a third and centred on log 5
+    thetas[:, -(dims[-2] + 1):-1] *= np.float32(1.0 / 3.0)
+    thetas[:, -1] = thetas[:, -1] / np.float32(3.0) + np.float32(np.log(5.0))
+    p = memory_predictor(dims, thetas)
+    ch = p._chain
+    f = ch.forward_many(thetas, X=X)
+    Y = rng.poisson(np.exp(f[rng.integers(0, M, n), 0, np.arange(n)].astype(np.float64))).astype(np.float32)[:, None]
+    fwd = round(1e3 * median_of(lambda: ch.forward_many(thetas, X=X)), 3)
+    for lik, r in ((PoissonLikelihood(), None), (NegativeBinomialLikelihood(dispersion=5.0), 5.0)):
+        p.likelihood = lik
+        res = {"shape": "flagship, counts", "likelihood": type(lik).__name__, "dims": dims, "networks": M, "rows": n, "kernel": ch.kernel_name,
+               "build_id": nat.build_id(), "rate_quantiles_1_50_99": [float(v) for v in np.exp(np.quantile(f.astype(np.float64), [0.01, 0.5, 0.99]))],
+               "forward_many_ms": fwd}
+        res["predictor_count_crps_ms"] = round(1e3 * median_of(lambda: p.countCrps(X, Y)), 3)
+        got = p.countCrps(X, Y)
+        t0 = time.perf_counter()
+        ref = [cc.count_crps_ref(f[:, 0, i], np.ones(M), Y[i], lik.kind, r) for i in range(COUNT_HOST_ROWS)]
+        t_host = time.perf_counter() - t0
+        res["host_rows"] = COUNT_HOST_ROWS
+        res["host_scipy_ms_on_host_rows"] = round(1e3 * t_host, 1)
+        res["host_route_extrapolated_ms"] = round(1e3 * t_host * n / COUNT_HOST_ROWS + fwd, 1)
+        res["largest_difference"] = {k: float(max(abs(got[k][0, i] - ref[i][a][0]) for i in range(COUNT_HOST_ROWS))) for a, k in enumerate(("crps", "error", "spread"))}
+        res["mean_crps"], res["se"], res["n_bad"] = float(got["mean_crps"][0]), float(got["se"][0]), got["n_bad"]
+        print(json.dumps(res), flush=True)
+    ch.close()
+
+
 def main():
     if nat.device_count() < 1:
         sys.exit("time_crps: no gfx950 device")
+    if "--counts" in sys.argv:
+        return counts()
     for name, (dims, n) in SHAPES.items():
         rng = np.random.default_rng(0)
         X = (rng.standard_normal((n, dims[0])) / np.sqrt(max(dims[0] / 16.0, 1.0))).astype(np.float32)
