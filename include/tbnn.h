@@ -554,6 +554,40 @@ int tbnn_ensemble_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t th
 int tbnn_ensemble_count_crps(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
                              int which, const float* X, const float* Y, int64_t n, double* crps_out, double* error_out,
                              double* spread_out);
+/* Harrell's concordance index (C-index) of a survival ensemble: the share of comparable pairs of rows that a network ranks in the order in
+ * which their events happened.  Counted on the device, per network and for the posterior-mean score.  Arguments up to `n` as
+ * tbnn_ensemble_moments' (networks, weights, rows) and tbnn_ensemble_loglik's (targets), without a likelihood: the scores are the raw
+ * outputs whatever the handle's own likelihood.  Per output column o, each its own survival problem with its own targets:
+ *   time and flag   t_i = |y_i|, e_i = (y_i > 0): the encoding of TBNN_LIK_WEIBULL's targets (a censored row carries -t)
+ *   score           s_i, the output for the row: under TBNN_LIK_WEIBULL the log of the scale, and with a fixed shape every quantile and the
+ *                   mean of the predicted time increase in it.  Larger means a later event
+ *   comparable      the ordered pair (i, j) iff e_i = 1 and (t_i < t_j, or t_i == t_j and e_j = 0): i is seen to fail while j is known to
+ *                   outlive it.  A row censored at an event's time outlives it; two events at the same time are not comparable; a
+ *                   censored i opens no pair
+ *   concordant      a comparable pair with s_i < s_j; tied: s_i == s_j; discordant otherwise
+ *   C               (concordant + tied / 2) / comparable, left to the caller; comparable == 0 (every row censored, say): NaN
+ * Per network the scores are compared as the fp32 values the forward kernels produce, unchanged.  The posterior-mean score is
+ * sbar_i = sum_k w_k s_{k,i} / W in fp64 -- the bits tbnn_ensemble_moments returns as its mean under TBNN_XFORM_NONE, scale 1, shift 0, by
+ * the same kernels -- and is compared in fp64.  The network weights enter sbar alone; there are no row weights.
+ * A network with a NaN score anywhere in a column reports concordant = tied = -1 for that column; the other networks are unaffected.  A NaN
+ * in sbar does the same to the mean's counts of the column.
+ * Targets must be finite and nonzero: anything else is refused -- a caller's Y before the device is touched, staged targets (Y NULL with X
+ * NULL) after they have been copied back once for the staging below.
+ * Staging and work.  The host sorts the rows of a column by (t ascending, events before censored rows at equal t), stably; in that order
+ * the rows comparable to position i are the suffix [jstart_i, n), jstart_i the first position behind an event's run of equal-time events
+ * and n for a censored row, so comparable = sum_i (n - jstart_i) is the host's and the device compares scores only: n^2 / 2 pairs per
+ * network and column at about four vector operations each, no floating-point arithmetic.  The counts are integers summed by atomics, so
+ * they are the same from run to run and whatever the chunks.  The networks are cut into chunks as for tbnn_ensemble_moments; the sorted
+ * copy of one column counts into the same budget (half of it each).
+ * n is at most 2^22 = 4,194,304 rows: the list of work items grows with (n / 1024)^2.  (A lane's 32-bit counters cannot wrap at any n: an
+ * item gives a lane at most 2^15 pairs, after which they are widened to 64 bits.)
+ * comparable_out: host [d_out]; net_counts_out: host [m][d_out][2] (concordant, tied); mean_counts_out: host [d_out][2]; mean_score_out:
+ * host [d_out][n] doubles, sbar in the caller's row order; each may be NULL, not all four.
+ * Refused, with nothing written: every output NULL, X without Y, m < 1, weights breaking the rules of tbnn_ensemble_moments, n not matching
+ * the staged rows, more than 2^22 rows, a target that is 0 or not finite. */
+int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int which,
+                              const float* X, const float* Y, int64_t n, int64_t* comparable_out, int64_t* net_counts_out,
+                              int64_t* mean_counts_out, double* mean_score_out);
 /* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
  * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
  * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).

@@ -127,6 +127,8 @@ SYMBOLS = [
                                            _dp]),
     ("tbnn_ensemble_crps", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_int, _dp, _dp, _dp]),
     ("tbnn_ensemble_count_crps", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp, _dp]),
+    ("tbnn_ensemble_concordance", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, _fp, _fp, C.c_int64, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
@@ -670,6 +672,26 @@ class Chain:
         _check(lib.tbnn_ensemble_count_crps(self._h, _p(th), th.shape[0], th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n,
                                             *[_pd(out[k]) for k in ("crps", "error", "spread")]))
         return out
+
+    def ensemble_concordance(self, thetas, Y=None, X=None, which: int = 1, weights=None):
+        """Harrell's concordance index of a survival ensemble, its pairs counted on the device (tbnn_ensemble_concordance; the definition is
+        in include/tbnn.h): targets as WeibullLikelihood.encode leaves them (|y| the time, y < 0 a censored row), scores the raw outputs.
+        A dict: comparable int64 [d_out]; concordant, tied int64 [m, d_out], per network (-1 where the network holds a NaN score in the
+        column); mean_concordant, mean_tied int64 [d_out], of the posterior-mean score; mean_score float64 [d_out, rows], that score -- the
+        bits of ensemble_moments' mean.  C = (concordant + tied / 2) / comparable.  weights: one per network or None (equal), read by the
+        mean score alone; Y None with X None: the staged targets"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        yp, _sd, _lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, None)
+        m = th.shape[0]
+        comparable = np.empty(self.d_out, dtype=np.int64)
+        net = np.empty((m, self.d_out, 2), dtype=np.int64)
+        mean = np.empty((self.d_out, 2), dtype=np.int64)
+        score = np.empty((self.d_out, n), dtype=np.float64)
+        _pl = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(lib.tbnn_ensemble_concordance(self._h, _p(th), m, th.shape[1], _p(w), int(which), _p(xp), _p(yp), n, _pl(comparable), _pl(net),
+                                             _pl(mean), _pd(score)))
+        return {"comparable": comparable, "concordant": net[:, :, 0].copy(), "tied": net[:, :, 1].copy(), "mean_concordant": mean[:, 0].copy(),
+                "mean_tied": mean[:, 1].copy(), "mean_score": score}
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,
                      psis: bool = True):

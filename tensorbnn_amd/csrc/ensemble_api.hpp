@@ -883,6 +883,178 @@ extern "C" int tbnn_ensemble_count_crps(tbnn_handle h, const float* thetas, int3
         }, extra);
 }
 
+// what tbnn_ensemble_concordance asks of its targets: a time |y| that is finite and not 0, its sign the censoring flag
+static int conc_check_targets(const std::string& who, const float* Y, size_t count) {
+    for (size_t i = 0; i < count; ++i)
+        if (!std::isfinite(Y[i]) || Y[i] == 0.f)
+            return fail(-1, who + ": target " + std::to_string(i) + " is not a finite, nonzero time (its sign is the censoring flag)");
+    return 0;
+}
+
+// The host staging of one output column o of tbnn_ensemble_concordance (definition: include/tbnn.h; layout: k_ens_concordance).  Y: the
+// targets [n][d_out].  perm[n]: the rows stable-sorted by (time ascending, events before censored rows at equal times).  jstart[npad]: in
+// that order the rows comparable to position i are the suffix [jstart_i, n) -- an event's starts behind its run of equal-time events, a
+// censored row's is empty (n), as is every position from n on.  *comparable = sum_i (n - jstart_i).  The work items of the column are
+// appended to `items`: per i-tile the j-tiles from the one that holds the tile's smallest jstart_i < n to the last, cut into spans of at
+// most ENS_CONC_SPAN tiles as equal as they come, each with the first j-tile at or above the tile's largest jstart_i < n (no mask from
+// there on).  Nothing here reads a score.
+static void conc_stage(const float* Y, long n, int d_out, int o, long npad, int* perm, int* jstart, std::vector<int4>& items, int64_t* comparable) {
+    auto time_of = [&](int i) { return std::fabs(Y[(size_t)i * d_out + o]); };
+    auto event = [&](int i) { return Y[(size_t)i * d_out + o] > 0.f; };
+    for (long i = 0; i < n; ++i) perm[i] = (int)i;
+    std::stable_sort(perm, perm + n, [&](int a, int b) {
+        const float ta = time_of(a), tb = time_of(b);
+        return ta != tb ? ta < tb : (event(a) && !event(b));
+    });
+    int64_t comp = 0;
+    for (long i = 0; i < n;) {
+        if (!event(perm[i])) { jstart[i++] = (int)n; continue; }
+        long e = i + 1;
+        while (e < n && event(perm[e]) && time_of(perm[e]) == time_of(perm[i])) ++e;
+        for (; i < e; ++i) { jstart[i] = (int)e; comp += n - e; }
+    }
+    for (long i = n; i < npad; ++i) jstart[i] = (int)n;
+    *comparable = comp;
+    const int ntile = (int)(npad / ENS_CI);
+    for (int t = 0; t < ntile; ++t) {
+        long lo = n, hi = -1;
+        for (long i = (long)t * ENS_CI; i < std::min<long>(n, (long)(t + 1) * ENS_CI); ++i)
+            if (jstart[i] < n) { lo = std::min<long>(lo, jstart[i]); hi = std::max<long>(hi, jstart[i]); }
+        if (hi < 0) continue;
+        const int j0 = (int)(lo / ENS_CI), len = ntile - j0, full = (int)((hi + ENS_CI - 1) / ENS_CI);
+        const int parts = (len + ENS_CONC_SPAN - 1) / ENS_CONC_SPAN;
+        for (int p = 0; p < parts; ++p)
+            items.push_back(make_int4(t, j0 + (int)((long)len * p / parts), j0 + (int)((long)len * (p + 1) / parts), full));
+    }
+}
+
+// Harrell's concordance index of a survival ensemble (definition: include/tbnn.h; kernels: k_ens_conc_gather, k_ens_concordance).  A
+// network's index needs all of its rows, so the NETWORKS are cut (ensemble_forward): half of the chunk budget goes to the predictions,
+// the other half to the sorted copy S[chunk][npad] of one output at a time (npad: n rounded up to ENS_CI).  The posterior-mean score is
+// k_ens_moments' / k_ens_moments_finish's mean, launched as tbnn_ensemble_moments launches them, and is counted after the last chunk as
+// one fp64 "network".  Slot m of the flag and count buffers is the mean's.
+extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int which,
+                                         const float* X, const float* Y, int64_t n, int64_t* comparable_out, int64_t* net_counts_out,
+                                         int64_t* mean_counts_out, double* mean_score_out) {
+    NEED(h);
+    const std::string who = "ensemble_concordance";
+    const int d_out = h->nd.d_out;
+    if (!comparable_out && !net_counts_out && !mean_counts_out && !mean_score_out) return fail(-1, who + ": every output is null");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
+    const std::string too_many = who + ": more than " + std::to_string(ENS_CONC_MAX_N) + " rows (the work list grows with the square of the rows)";
+    if (Y && n >= 1) {
+        if (n > ENS_CONC_MAX_N) return fail(-1, too_many);
+        ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
+    }
+    const bool want_mean = mean_counts_out || mean_score_out;
+    std::vector<float> Yh;
+    std::vector<int> perm, js, hbad;
+    std::vector<int4> items;
+    std::vector<size_t> item_off((size_t)d_out + 1, 0);
+    std::vector<int64_t> comp((size_t)d_out, 0);
+    std::vector<unsigned long long> hcnt;
+    Buf<int> dPerm, dJs, dBad;
+    Buf<int4> dItems;
+    Buf<float> dS, dW;
+    Buf<double> acc, dSm;
+    Buf<unsigned long long> dCnt;
+    long rows = 0, npad = 0, tot = 0;
+    // column o of a set of sorted scores S[c][npad]: the pair kernel over the column's work items, into the counts of slot `slot` on
+    auto count_pairs = [&](auto* S, int c, int o, size_t slot) -> int {
+        const size_t ni = item_off[o + 1] - item_off[o];
+        if (!ni) return 0;
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
+        hipLaunchKernelGGL(k_ens_concordance<T>, dim3((unsigned)ni, (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream, S, c, rows, npad,
+                           (const int*)(dJs + (size_t)o * npad), (const int4*)(dItems + item_off[o]), dCnt + (slot * d_out + o) * 2, 2 * d_out);
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    ENS_TRY(ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, std::max<size_t>(1, ens_chunk_floats() / 2),
+        [&](long r, int chunk) -> int {
+            rows = r;
+            if (rows > ENS_CONC_MAX_N) return fail(-1, too_many);
+            npad = (rows + ENS_CI - 1) / ENS_CI * ENS_CI;
+            tot = rows * d_out;
+            const float* Yrows = Y;
+            if (!Y) {
+                // the staged targets, copied back once: the staging below is the host's
+                Buf<float> none;
+                const float* dY = nullptr;
+                ENS_TRY(ens_stage_targets(h, which, nullptr, rows, none, &dY));
+                Yh.resize((size_t)tot);
+                HIPCHK(hipMemcpyAsync(Yh.data(), dY, (size_t)tot * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+                Yrows = Yh.data();
+                ENS_TRY(conc_check_targets(who, Yrows, (size_t)tot));
+            }
+            perm.resize((size_t)tot);
+            js.resize((size_t)d_out * npad);
+            for (int o = 0; o < d_out; ++o) {
+                conc_stage(Yrows, rows, d_out, o, npad, perm.data() + (size_t)o * rows, js.data() + (size_t)o * npad, items, &comp[o]);
+                item_off[o + 1] = items.size();
+            }
+            ENS_TRY(ens_upload(h, dPerm, perm.data(), perm.size()));
+            ENS_TRY(ens_upload(h, dJs, js.data(), js.size()));
+            if (!items.empty()) ENS_TRY(ens_upload(h, dItems, items.data(), items.size()));
+            const size_t slots = ((size_t)m + 1) * d_out;
+            HIPCHK(dBad.alloc(slots));
+            HIPCHK(dCnt.alloc(2 * slots));
+            HIPCHK(hipMemsetAsync(dBad, 0, slots * sizeof(int), h->stream));
+            HIPCHK(hipMemsetAsync(dCnt, 0, 2 * slots * sizeof(unsigned long long), h->stream));
+            if (net_counts_out) HIPCHK(dS.alloc((size_t)chunk * npad));
+            if (want_mean) {
+                HIPCHK(acc.alloc(3 * (size_t)tot));
+                HIPCHK(dSm.alloc((size_t)npad));
+                if (net_w) ENS_TRY(ens_upload(h, dW, net_w, (size_t)m));
+            }
+            return 0;
+        },
+        [&](int i0, int c, const float* dOut, long) -> int {
+            if (want_mean) {
+                hipLaunchKernelGGL(k_ens_moments, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, dOut, c, tot, (int)TBNN_XFORM_NONE, 1.f, 0.f,
+                                   net_w ? (const float*)(dW + i0) : nullptr, (int)(i0 == 0), (double*)acc);
+                HIPCHK(hipGetLastError());
+            }
+            for (int o = 0; o < d_out && net_counts_out; ++o) {
+                hipLaunchKernelGGL(k_ens_conc_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream, dOut + (size_t)o * rows, (size_t)tot, c,
+                                   (const int*)(dPerm + (size_t)o * rows), rows, npad, (float*)dS, dBad + (size_t)i0 * d_out + o, d_out);
+                HIPCHK(hipGetLastError());
+                ENS_TRY(count_pairs((const float*)dS, c, o, (size_t)i0));
+            }
+            return 0;
+        }));
+    if (want_mean) {
+        hipLaunchKernelGGL(k_ens_moments_finish, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, tot, W);
+        HIPCHK(hipGetLastError());
+        for (int o = 0; o < d_out && mean_counts_out; ++o) {
+            hipLaunchKernelGGL(k_ens_conc_gather<double>, dim3(ens_grid(npad), 1), dim3(ENS_TB), 0, h->stream, (const double*)(acc + (size_t)o * rows), (size_t)0, 1,
+                               (const int*)(dPerm + (size_t)o * rows), rows, npad, (double*)dSm, dBad + (size_t)m * d_out + o, d_out);
+            HIPCHK(hipGetLastError());
+            ENS_TRY(count_pairs((const double*)dSm, 1, o, (size_t)m));
+        }
+    }
+    const size_t slots = ((size_t)m + 1) * d_out;
+    hbad.resize(slots);
+    hcnt.resize(2 * slots);
+    HIPCHK(hipMemcpyAsync(hbad.data(), dBad, slots * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hcnt.data(), dCnt, 2 * slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    if (mean_score_out) HIPCHK(hipMemcpyAsync(mean_score_out, acc, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // a NaN among a network's scores of a column: -1 for both of its counts there
+    auto put = [&](int64_t* dst, size_t slot0, size_t count) {
+        for (size_t s = 0; s < count; ++s)
+            for (int k = 0; k < 2; ++k) dst[2 * s + k] = hbad[slot0 + s] ? -1 : (int64_t)hcnt[2 * (slot0 + s) + k];
+    };
+    if (net_counts_out) put(net_counts_out, 0, (size_t)m * d_out);
+    if (mean_counts_out) put(mean_counts_out, (size_t)m * d_out, (size_t)d_out);
+    for (int o = 0; o < d_out && comparable_out; ++o) comparable_out[o] = comp[o];
+    return 0;
+}
+
 // M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)
 static void psis_sizes(int32_t m, double r_eff, int* M, int* G, int* q) {
     *M = (int)std::ceil(std::min(0.2 * (double)m, 3.0 * std::sqrt((double)m / r_eff)));

@@ -45,6 +45,10 @@
 //             components (definition: include/tbnn.h, tbnn_ensemble_count_crps), whose pair term has no closed form.  The same eight lanes
 //             per element; each steps its networks' pmf recurrences over a tile of k in registers, the per-k mixtures meet in LDS
 //             (windows, tiles, gaps and summation order: at the kernel).  All fp64, contraction off, no atomics.
+//   concordance a chunk [c][d_out][n] like the moments' (a network's concordance index needs all of its rows, so the NETWORKS are cut):
+//             k_ens_conc_gather copies one output's scores into the order the host sorted the rows in, k_ens_concordance counts the
+//             concordant and tied pairs among the comparable ones (definition: include/tbnn.h, tbnn_ensemble_concordance): row tiles in
+//             registers against score tiles from LDS, compares only, 64-bit integer atomics (layout and work list: at the kernel).
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -69,6 +73,10 @@
 #define ENS_CC_CUT 1.8048513878454153e-35   // e^-80: a component's pmf below it ends its window (the exit of ens_gamma_q / ens_betainc)
 #define ENS_CC_RANGE 2097152.0              // 2^21: the values of k an element's sweep (or one window above its mode) may span; beyond it NaN
 #define ENS_CC_PLANES 5                     // scratch of the sweep per (network, element), in doubles: the window and four state planes
+#define ENS_CR 4        // sorted rows a lane of the concordance kernel (k_ens_concordance) holds in registers
+#define ENS_CI (ENS_TB * ENS_CR)   // rows of its i-tile, and scores of a j-tile in LDS: 1024
+#define ENS_CONC_SPAN 8            // j-tiles of a work item at the most: a lane counts at most ENS_CR ENS_CI ENS_CONC_SPAN = 2^15 pairs per item
+#define ENS_CONC_MAX_N 4194304     // 2^22 rows of tbnn_ensemble_concordance at the most: the work list grows with (n / ENS_CI)^2 (a limit of the interface)
 
 // t = xform(f) * scale + shift, the de-normalisation of tbnn_metrics (softmax: the caller passes the probability as f)
 __device__ __forceinline__ float ens_xform(float f, int xform) {
@@ -1664,5 +1672,124 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_count_crps(const float* __restri
             res[2 * rbk + e] = anybad ? (double)NAN : S;
         }
         __syncthreads();                                        // (red and redbad are rewritten by the next elements' setup)
+    }
+}
+
+// ---- Harrell's concordance index of a survival ensemble: pair counting (tbnn_ensemble_concordance) ----
+// The host sorts the rows of one output by (time ascending, events before censored rows at equal times): perm.  In that order the rows
+// comparable to sorted position i are a SUFFIX [jstart_i, n) -- an event's starts behind its run of equal-time events, a censored row's is
+// empty (jstart_i = n) -- so the times are not looked at again: the kernels compare scores only, and no floating-point arithmetic happens here.
+//
+// k_ens_conc_gather: S[net][i] = out[net][perm[i]] for i < n (writes coalesced, reads gathered), NaN for n <= i < npad = n rounded up to
+// ENS_CI: a NaN is neither below nor equal to anything, so the padding needs no mask.  bad[net * bad_stride] = 1 where the network holds a
+// NaN among its n scores: every writer stores the same value, a plain store.  T = float: the c networks of a chunk, `stride` values apart
+// in out; T = double: the one posterior-mean score (c = 1).
+template <class T>
+__global__ __launch_bounds__(ENS_TB) void k_ens_conc_gather(const T* __restrict__ out, size_t stride, int c, const int* __restrict__ perm, long n,
+                                                             long npad, T* __restrict__ S, int* __restrict__ bad, int bad_stride) {
+    for (int net = blockIdx.y; net < c; net += gridDim.y) {
+        for (long i = (long)blockIdx.x * ENS_TB + threadIdx.x; i < npad; i += (long)gridDim.x * ENS_TB) {
+            T v = (T)NAN;
+            if (i < n) {
+                v = out[(size_t)net * stride + perm[i]];
+                if (v != v) bad[(size_t)net * bad_stride] = 1;
+            }
+            S[(size_t)net * npad + i] = v;
+        }
+    }
+}
+
+// S[c][npad]: the sorted scores; jstart[npad]: the suffix starts (n from position n on); items: the host's work list, (i-tile, first j-tile,
+// one past the last j-tile, first j-tile that needs no mask); counts: this output's (concordant, tied) of the chunk's first network, the
+// next network's cnt_stride further on.  Grid: work items x networks of the chunk.
+//
+// Layout.  An i-tile is ENS_CI = 1024 consecutive sorted rows in REGISTERS: lane tid holds the ENS_CR = 4 scores s_i of rows
+// i0 + tid + 256 r (coalesced loads) and their jstart_i.  A row that opens no pair (jstart_i >= n: censored, or an event nothing outlives)
+// takes s_i = NaN and drops out of every compare, so censored rows do not widen the masked range below.  The j-tiles, 1024 scores each,
+// pass through LDS double-buffered: every thread loads the four scores 4 tid .. 4 tid + 3 of tile J + 1 (one 16-byte load; fp64: two)
+// before tile J is walked and stores them after, one barrier per tile, as k_ens_crps does.  The walk reads LDS 16 bytes at a time at an
+// address the whole wave shares -- a broadcast, no bank conflict -- and one read serves 4 x ENS_CR = 16 pairs per lane.
+// Per pair: two compares (s_i < s_j, s_i == s_j) and two adds of their outcomes into the lane's two 32-bit counters.  The per-lane form
+// was chosen over compare -> wave mask -> population count because the boundary tiles' mask j >= jstart_i differs from lane to lane and
+// joins the per-lane form as one more compare, where the wave form would need a second mask operation per pair; and it keeps the loop
+// on the vector unit alone.
+// Triangularity.  Of an i-tile the host passes jlo and jhi, the smallest and the largest jstart_i < n.  j-tiles wholly below jlo are not
+// in the item; tiles that start at or above jhi (J >= item.w) run the unmasked loop; the tiles between -- about two, more where long runs of
+// equal times straddle them -- add the compare j >= jstart_i.
+// Load balance.  The j-range of an i-tile (long for early tiles, short for late ones) is cut into items of at most ENS_CONC_SPAN j-tiles,
+// as equal as they come; the list depends on n and jstart alone, never on the scores or the chunking.
+// Counters.  A lane counts at most 2^15 pairs per item in 32 bits; at the item's end both counters are widened to 64 bits, summed over the
+// wave by shuffles, and lane 0 adds them with one 64-bit integer atomicAdd each.  Integer sums are order-free: the same counts from run
+// to run and whatever the chunks.
+template <class T>
+__global__ __launch_bounds__(ENS_TB) void k_ens_concordance(const T* __restrict__ S, int c, long n, long npad, const int* __restrict__ jstart,
+                                                             const int4* __restrict__ items, unsigned long long* __restrict__ counts, int cnt_stride) {
+    typedef T V4 __attribute__((ext_vector_type(4)));
+    static_assert(ENS_CI == 4 * ENS_TB, "a thread stages four scores of a j-tile");
+    __shared__ V4 tile[2][ENS_TB];
+    const int tid = threadIdx.x;
+    const int4 it = items[blockIdx.x];
+    const long i0 = (long)it.x * ENS_CI;
+    int js[ENS_CR];
+#pragma unroll
+    for (int r = 0; r < ENS_CR; ++r) js[r] = jstart[i0 + tid + ENS_TB * r];
+    int b = 0;
+    for (int net = blockIdx.y; net < c; net += gridDim.y) {
+        const T* __restrict__ s = S + (size_t)net * npad;
+        T si[ENS_CR];
+#pragma unroll
+        for (int r = 0; r < ENS_CR; ++r) {
+            const T v = s[i0 + tid + ENS_TB * r];
+            si[r] = (long)js[r] < n ? v : (T)NAN;
+        }
+        unsigned cc = 0, tt = 0;
+        V4 nxt = *(const V4*)(s + (size_t)it.y * ENS_CI + 4 * tid);
+        for (int J = it.y; J < it.z; ++J) {
+            tile[b][tid] = nxt;
+            __syncthreads();
+            if (J + 1 < it.z) nxt = *(const V4*)(s + (size_t)(J + 1) * ENS_CI + 4 * tid);
+            if (J >= it.w) {
+#pragma unroll 2
+                for (int q = 0; q < ENS_TB; ++q) {
+                    const V4 v = tile[b][q];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                        for (int r = 0; r < ENS_CR; ++r) {
+                            cc += si[r] < v[k];
+                            tt += si[r] == v[k];
+                        }
+                    }
+                }
+            } else {
+                const int jb = J * ENS_CI;
+#pragma unroll 2
+                for (int q = 0; q < ENS_TB; ++q) {
+                    const V4 v = tile[b][q];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = jb + 4 * q + k;
+#pragma unroll
+                        for (int r = 0; r < ENS_CR; ++r) {
+                            const bool on = j >= js[r];
+                            cc += on & (si[r] < v[k]);
+                            tt += on & (si[r] == v[k]);
+                        }
+                    }
+                }
+            }
+            b ^= 1;
+        }
+        unsigned long long c64 = cc, t64 = tt;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            c64 += __shfl_down(c64, off);
+            t64 += __shfl_down(t64, off);
+        }
+        if ((tid & 63) == 0) {
+            unsigned long long* dst = counts + (size_t)net * cnt_stride;
+            atomicAdd(dst, c64);
+            atomicAdd(dst + 1, t64);
+        }
     }
 }

@@ -510,6 +510,50 @@ class predictor(object):
             out.append(1.0 - self.predictiveCDF(x, y, n=n, weights=weights, likelihood=lik))
         return np.stack(out, axis=0)
 
+    def concordance(self, X, Y, n=1, weights=None, likelihood=None):
+        """Harrell's concordance index (C-index) of the ensemble under a WeibullLikelihood: the share of comparable pairs of rows -- one
+        seen to fail while the other is known to outlive it -- that the score (the network's output, the log of the Weibull scale) ranks
+        in the order of their events; score ties count a half.  0.5 is a coin's ranking, 1 a perfect one; calibration does not enter.  Y:
+        targets as WeibullLikelihood.encode leaves them, each output column its own problem.  The pairs are counted on the device for
+        every n-th network and for the posterior-mean score (the definition is in include/tbnn.h, tbnn_ensemble_concordance).  Returns a
+        dict: c_index float64 [d_out], of the posterior-mean score (the point predictor's); per_network float64 [m', d_out], one C per
+        picked network -- the posterior distribution of C; mean, sd, q05, q50, q95 [d_out] of per_network over the networks whose C is
+        not NaN (weighted where weights is given: weighted mean and variance, quantiles of the weighted inverted CDF); n_bad, the count
+        of NaN entries of per_network (a NaN score, or no comparable pair); comparable, n_events, n_censored int64 [d_out]."""
+        from .likelihood import WeibullLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, WeibullLikelihood):
+            raise ValueError("concordance needs a WeibullLikelihood: the pairs are ordered by times to an event with a censoring flag, not "
+                             f"by the targets of a {type(lik).__name__}")
+        picked, w = self._picked(n, weights)
+        y = np.asarray(Y, dtype=np.float32)
+        res = self._ensure_chain().ensemble_concordance(picked, Y=y, X=np.asarray(X, dtype=np.float32), weights=w)
+        comp = res["comparable"].astype(np.float64)
+
+        def ratio(conc, tied):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return np.where((conc >= 0) & (comp > 0), (conc + 0.5 * tied) / comp, np.nan)
+        per = ratio(res["concordant"], res["tied"])
+        d_out = per.shape[1]
+        out = {"c_index": ratio(res["mean_concordant"], res["mean_tied"]), "per_network": per, "n_bad": int(np.isnan(per).sum()),
+               "comparable": res["comparable"], "n_events": (y.reshape(-1, d_out) > 0).sum(axis=0).astype(np.int64),
+               "n_censored": (y.reshape(-1, d_out) < 0).sum(axis=0).astype(np.int64)}
+        stats = {k: np.full(d_out, np.nan) for k in ("mean", "sd", "q05", "q50", "q95")}
+        wk = np.ones(per.shape[0]) if w is None else w.astype(np.float64)
+        for o in range(d_out):
+            ok = ~np.isnan(per[:, o]) & (wk > 0)
+            if not ok.any():
+                continue
+            v, ww = per[ok, o], wk[ok] / wk[ok].sum()
+            stats["mean"][o] = np.sum(ww * v)
+            stats["sd"][o] = np.sqrt(np.sum(ww * (v - stats["mean"][o]) ** 2))
+            order = np.argsort(v, kind="stable")
+            cdf = np.cumsum(ww[order])
+            for key, p in (("q05", 0.05), ("q50", 0.5), ("q95", 0.95)):
+                stats[key][o] = np.quantile(v, p) if w is None else v[order][min(np.searchsorted(cdf, p), v.size - 1)]
+        out.update(stats)
+        return out
+
     # ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
     def _crps_likelihood(self, likelihood):
         from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood,
