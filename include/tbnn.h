@@ -588,6 +588,55 @@ int tbnn_ensemble_count_crps(tbnn_handle h, const float* thetas, int32_t m, int6
 int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int which,
                               const float* X, const float* Y, int64_t n, int64_t* comparable_out, int64_t* net_counts_out,
                               int64_t* mean_counts_out, double* mean_score_out);
+/* The time-dependent Brier score of a survival ensemble with inverse-probability-of-censoring weights (IPCW; Graf, Schmoor, Sauerbrei,
+ * Schumacher 1999) over a grid of times: the calibration score beside the concordance index's ranking.  Formed on the device, per network
+ * and for the mixture, with the mixture's survival curves.  Arguments up to `n` as tbnn_ensemble_count_crps' (networks, the likelihood to
+ * judge under, weights, rows, targets).  Per output column o, each its own survival problem:
+ *   targets         t_i = |y_i|, e_i = (y_i > 0): the encoding of TBNN_LIK_WEIBULL and of tbnn_ensemble_concordance
+ *   grid            `times`: T times tau_1 < ... < tau_T, finite, > 0, strictly ascending, 1 <= T <= 256, shared by all columns
+ *   survival        network i at row r and time tau_j: S_i = exp(-u), u = exp(k (log tau_j - f_i)); k the handle's shape as
+ *                   tbnn_ensemble_predictive reads it, f_i the fp32 output widened to fp64, everything after it fp64 and not contracted.
+ *                   The device forms the exponent as c_j - k f_i with c_j = k log tau_j from the host (no factored power of tau: tau^k
+ *                   alone overflows where the definition does not).  The mixture: Sbar = sum_i omega_i S_i, omega_i = w_i / W staged by
+ *                   the host as for tbnn_ensemble_crps, summed in network order
+ *   censoring G     the Kaplan-Meier estimate of the CENSORING time, on the host in fp64 (tbnn_ipcw_weights), from the scored rows
+ *                   themselves or, where G_Y [n_g][d_out] is given, from those targets (the training set, say).  At equal times events
+ *                   leave the risk set before censored rows (the tie rule of tbnn_ensemble_concordance): at a distinct censoring time s,
+ *                   c_s = the rows censored at s, r_s = #{t > s} + #{t == s, censored}, and G(x) = the product of 1 - c_s / r_s over
+ *                   s <= x taken in ascending s; G(x-) the same over s < x
+ *   weight          of row r at tau_j, picked by selects, never by products:  1 / G(tau_j) if t_r > tau_j (indicator I = 1);
+ *                   1 / G(t_r-) if t_r <= tau_j and e_r = 1 (I = 0);  0 otherwise (censored before tau_j).  A weight that is needed
+ *                   but whose G is 0 is NaN, and so is every sum it enters; an unused infinite weight never enters a sum
+ *   bs_mean[o][j]   (1 / n) sum_r w_rj (I_rj - Sbar_rj)^2          bs_net[i][o][j]   the same with S_i in place of Sbar
+ *   surv[j][o][r]   Sbar_rj, the mixture's survival curve on the grid
+ *   mean_weight[o][j]  (1 / n) sum_r w_rj: 1 up to rounding when G comes from the scored rows (a diagnostic)
+ * NaN, no masking: a NaN f_i makes that network's bs_net NaN for the column (every time), and, whatever the network's weight, Sbar of
+ * that row NaN: with it bs_mean[o] at every time and the row's surv.  A network of weight 0 is otherwise left out of Sbar and still gets
+ * its bs_net.  f = +-inf needs no case: S is 1 or 0.
+ * Work and sums.  The rows are cut into blocks as for tbnn_ensemble_crps (all m networks of a row are needed for Sbar).  A wave of
+ * k_ens_brier owns 64 rows and a tile of 8 times; per network the 64 rows' terms are summed by a transposing butterfly over the wave, the
+ * wave's successive row tiles are added in order into the workgroup's own slab of a partial buffer, a finish kernel adds the slabs in
+ * workgroup order and carries the sums from block to block in block order, and the host divides by n once.  No atomics: the same bits
+ * from run to run.  The partial buffer holds (m + 2) d_out T doubles per workgroup and at most 2^22 doubles (32 MiB) in all, or one
+ * workgroup's slab where that alone is larger (at most 4098 x 256 x d_out doubles), whatever n: the grid is sized to it, never above 1024.
+ * (Where one slab passes 2^21 doubles the grid is down to one workgroup per column, which walks all of a block's rows: slow.)
+ * bs_mean_out: host [d_out][T]; bs_net_out: host [m][d_out][T]; surv_out: host [T][d_out][n]; mean_weight_out: host [d_out][T]; each may
+ * be NULL, not all four.
+ * Refused, with nothing written: every output NULL, X without Y, a likelihood other than TBNN_LIK_WEIBULL, no shape set (a handle of
+ * another likelihood: tbnn_set_lik_df), T outside 1 .. 256, a time that is not finite, not > 0 or not above its predecessor, a target that
+ * is 0 or not finite (in Y or G_Y), m < 1 or m > 4096, weights breaking the rules of tbnn_ensemble_moments, n not matching the staged
+ * rows, 64 rows of all m networks above the block budget of 2^28 floats. */
+int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w, int which,
+                        const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times, int32_t T,
+                        double* bs_mean_out, double* bs_net_out, double* surv_out, double* mean_weight_out);
+/* The host half of tbnn_ensemble_brier: the IPCW weights of its definition above, in fp64.  No handle, no device.  Y [n][d_out]: the
+ * scored rows' signed targets; G_Y [n_g][d_out]: the targets the censoring distribution is estimated from, or NULL (n_g ignored): Y's.
+ * row_ginv_out [d_out][n] = 1 / G(t_r-) per row (read by the kernel on a row with an event at or before a grid time); time_ginv_out
+ * [d_out][T] = 1 / G(tau_j).  Where G is 0 the entry is NaN.  Either output may be NULL.  Returns 0, or -1 with tbnn_last_error set and
+ * nothing written: n < 1, d_out < 1, G_Y with n_g < 1, T outside 1 .. 256, a time that is not finite, not > 0 or not ascending, a target
+ * that is 0 or not finite. */
+int tbnn_ipcw_weights(const float* Y, int64_t n, int32_t d_out, const float* G_Y, int64_t n_g, const double* times, int32_t T,
+                      double* row_ginv_out, double* time_ginv_out);
 /* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
  * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
  * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).

@@ -129,6 +129,9 @@ SYMBOLS = [
     ("tbnn_ensemble_count_crps", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _dp, _dp, _dp]),
     ("tbnn_ensemble_concordance", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, _fp, _fp, C.c_int64, C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
+    ("tbnn_ensemble_brier", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _fp, C.c_int64, _dp, C.c_int32,
+                                      _dp, _dp, _dp, _dp]),
+    ("tbnn_ipcw_weights", C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
@@ -229,6 +232,20 @@ def _p(a: Optional[np.ndarray]):
 def _pd(a: Optional[np.ndarray]):
     """the same for a float64 array"""
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def ipcw_weights(Y, times, censoringY=None):
+    """The inverse-probability-of-censoring weights of tbnn_ensemble_brier, on the host (tbnn_ipcw_weights: no handle, no device).  Y
+    [n, d_out] signed targets, times the grid, censoringY the targets the Kaplan-Meier estimate G of the censoring time is taken from
+    (None: Y) -> (1 / G(t_r-) float64 [d_out, n], 1 / G(tau_j) float64 [d_out, T]), NaN where G is 0"""
+    y = _f32(Y)
+    y = y.reshape(-1, 1) if y.ndim < 2 else y
+    n, d_out = y.shape
+    gy = None if censoringY is None else _f32(censoringY).reshape(-1, d_out)
+    ts = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    row, tim = np.empty((d_out, n), dtype=np.float64), np.empty((d_out, ts.size), dtype=np.float64)
+    _check(lib.tbnn_ipcw_weights(_p(y), n, d_out, _p(gy), 0 if gy is None else gy.shape[0], _pd(ts), ts.size, _pd(row), _pd(tim)))
+    return row, tim
 
 
 def build_id() -> str:
@@ -692,6 +709,30 @@ class Chain:
                                              _pl(mean), _pd(score)))
         return {"comparable": comparable, "concordant": net[:, :, 0].copy(), "tied": net[:, :, 1].copy(), "mean_concordant": mean[:, 0].copy(),
                 "mean_tied": mean[:, 1].copy(), "mean_score": score}
+
+    def ensemble_brier(self, thetas, times, Y=None, X=None, which: int = 1, weights=None, likelihood=None, censoringY=None, per_network: bool = True,
+                       curves: bool = False):
+        """The time-dependent Brier score of a survival ensemble with inverse-probability-of-censoring weights over the grid `times`
+        (finite, > 0, ascending, at most 256), reduced on the device (tbnn_ensemble_brier; the definition is in include/tbnn.h): targets
+        as WeibullLikelihood.encode leaves them, the shape the chain's lik_df or set_lik_df.  A dict of float64 arrays: brier [d_out, T],
+        of the mixture's survival curve; mean_weight [d_out, T], the mean IPCW weight (1 when the censoring distribution comes from the
+        scored rows); per_network [m, d_out, T] (per_network=True); curves [T, d_out, rows], the mixture's survival probabilities
+        (curves=True).  censoringY: the targets the censoring distribution is estimated from (None: the scored rows'); weights: one per
+        network or None (equal), read by the mixture alone; Y None with X None: the staged targets"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        yp, _sd, lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, likelihood)
+        m = th.shape[0]
+        ts = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        gy = None if censoringY is None else _f32(censoringY).reshape(-1, self.d_out)
+        out = {"brier": np.empty((self.d_out, ts.size), dtype=np.float64), "mean_weight": np.empty((self.d_out, ts.size), dtype=np.float64)}
+        if per_network:
+            out["per_network"] = np.empty((m, self.d_out, ts.size), dtype=np.float64)
+        if curves:
+            out["curves"] = np.empty((ts.size, self.d_out, n), dtype=np.float64)
+        _check(lib.tbnn_ensemble_brier(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, _p(gy),
+                                       0 if gy is None else gy.shape[0], _pd(ts), ts.size, _pd(out["brier"]), _pd(out.get("per_network")),
+                                       _pd(out.get("curves")), _pd(out["mean_weight"])))
+        return out
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,
                      psis: bool = True):

@@ -1055,6 +1055,166 @@ extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int
     return 0;
 }
 
+// what tbnn_ensemble_brier and tbnn_ipcw_weights ask of the grid
+static int brier_check_times(const std::string& who, const double* times, int32_t T) {
+    if (T < 1 || T > ENS_BRIER_MAX_T) return fail(-1, who + ": T must be 1 .. " + std::to_string(ENS_BRIER_MAX_T));
+    if (!times) return fail(-1, who + ": null times");
+    for (int32_t j = 0; j < T; ++j)
+        if (!std::isfinite(times[j]) || !(times[j] > 0.0) || (j > 0 && !(times[j] > times[j - 1])))
+            return fail(-1, who + ": time " + std::to_string(j) + " is not finite, not > 0 or not above its predecessor");
+    return 0;
+}
+
+// The Kaplan-Meier estimate of the censoring time of one column of S [ns][d_out] (definition: include/tbnn.h, tbnn_ensemble_brier): cs,
+// the distinct censoring times ascending, and cum[i] = the product of 1 - c_s / r_s over cs[0 .. i] taken in that order.  At equal times
+// events leave the risk set first: r_s counts the rows with t > s and the rows censored at s.
+static void ipcw_km(const float* S, long ns, int d_out, int o, std::vector<double>& cs, std::vector<double>& cum) {
+    std::vector<float> all((size_t)ns), cen;
+    for (long i = 0; i < ns; ++i) {
+        const float y = S[(size_t)i * d_out + o];
+        all[i] = std::fabs(y);
+        if (y < 0.f) cen.push_back(-y);
+    }
+    std::sort(all.begin(), all.end());
+    std::sort(cen.begin(), cen.end());
+    cs.clear();
+    cum.clear();
+    double g = 1.0;
+    for (size_t a = 0; a < cen.size();) {
+        size_t b = a;
+        while (b < cen.size() && cen[b] == cen[a]) ++b;
+        const double c = (double)(b - a), risk = (double)(all.end() - std::upper_bound(all.begin(), all.end(), cen[a])) + c;
+        g *= 1.0 - c / risk;
+        cs.push_back((double)cen[a]);
+        cum.push_back(g);
+        a = b;
+    }
+}
+
+extern "C" int tbnn_ipcw_weights(const float* Y, int64_t n, int32_t d_out, const float* G_Y, int64_t n_g, const double* times, int32_t T,
+                                 double* row_ginv_out, double* time_ginv_out) {
+    const std::string who = "ipcw_weights";
+    if (!Y || n < 1 || d_out < 1 || (G_Y && n_g < 1)) return fail(-1, who + ": null targets, n < 1, d_out < 1 or G_Y with n_g < 1");
+    ENS_TRY(brier_check_times(who, times, T));
+    ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
+    if (G_Y) ENS_TRY(conc_check_targets(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
+    std::vector<double> cs, cum;
+    auto ginv = [&](size_t upto) {                               // 1 / the product over the first `upto` censoring times
+        const double g = upto ? cum[upto - 1] : 1.0;
+        return g > 0.0 ? 1.0 / g : (double)NAN;
+    };
+    for (int o = 0; o < d_out; ++o) {
+        ipcw_km(G_Y ? G_Y : Y, G_Y ? (long)n_g : (long)n, d_out, o, cs, cum);
+        for (int64_t i = 0; i < n && row_ginv_out; ++i)           // G(t-): the censoring times below t
+            row_ginv_out[(size_t)o * n + i] = ginv((size_t)(std::lower_bound(cs.begin(), cs.end(), (double)std::fabs(Y[(size_t)i * d_out + o])) - cs.begin()));
+        for (int32_t j = 0; j < T && time_ginv_out; ++j)          // G(tau): those at or below it
+            time_ginv_out[(size_t)o * T + j] = ginv((size_t)(std::upper_bound(cs.begin(), cs.end(), times[j]) - cs.begin()));
+    }
+    return 0;
+}
+
+// The IPCW Brier score over a time grid (definition: include/tbnn.h; kernels: k_ens_brier, k_ens_brier_finish).  Every row needs all m
+// networks at once for Sbar, so the rows are cut (ensemble_row_blocks).  The host stages omega_i = w_i / W, c_j = k log tau_j and the
+// weights of tbnn_ipcw_weights; a block's row sums land in the partial buffer, one slab per workgroup, and k_ens_brier_finish carries them
+// into acc [d_out][slots][T] in block order (slots: the m networks where bs_net is wanted, then the mixture and the weights); the host
+// divides by n once.  The grid: as many workgroups as the block has 64-row tiles, at most ENS_BRIER_MAX_WG, and no more than keep the
+// partial buffer within ENS_BRIER_PART doubles (one workgroup whatever its slab takes).  Where one slab alone exceeds half that bound (bs_net
+// with m near 4096 at T = 256) the grid collapses to d_out workgroups, each walking all of a block's row tiles: correct, and long-running.
+extern "C" int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
+                                   int which, const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times,
+                                   int32_t T, double* bs_mean_out, double* bs_net_out, double* surv_out, double* mean_weight_out) {
+    NEED(h);
+    const std::string who = "ensemble_brier";
+    const int d_out = h->nd.d_out;
+    if (!bs_mean_out && !bs_net_out && !surv_out && !mean_weight_out) return fail(-1, who + ": every output is null");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (likelihood != TBNN_LIK_WEIBULL) {
+        const char* name = ens_lik_name(likelihood);
+        if (!name && !lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
+        return fail(-1, who + ": " + (name ? name : "this likelihood") + " has no survival function with a censoring flag (TBNN_LIK_WEIBULL has)");
+    }
+    // the shape: the descriptor's lik_df on a Weibull handle, what tbnn_set_lik_df set on any other
+    const float kf = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
+    if (!df_ok(kf)) return fail(-1, who + ": the survival function under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
+    ENS_TRY(brier_check_times(who, times, T));
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (m > ENS_BRIER_MAX_M) return fail(-1, who + ": m = " + std::to_string(m) + " exceeds " + std::to_string(ENS_BRIER_MAX_M) + " networks");
+    ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
+    if (G_Y && n_g < 1) return fail(-1, who + ": G_Y with n_g < 1");
+    if (Y && n >= 1) ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
+    if (G_Y) ENS_TRY(conc_check_targets(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
+    const double k = (double)kf;
+    const bool nets = bs_net_out != nullptr;
+    const int slots = nets ? m + 2 : 2;
+    const size_t slab = (size_t)d_out * slots * T;
+    const long wg_max = std::max<long>(1, std::min<long>(ENS_BRIER_MAX_WG, (long)(ENS_BRIER_PART / slab)));
+    std::vector<double> cst((size_t)m + 2 * (size_t)T), rgi, tgi((size_t)d_out * T), sums(slab);
+    for (int32_t i = 0; i < m; ++i) cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
+    for (int32_t j = 0; j < T; ++j) {
+        cst[(size_t)m + j] = k * std::log(times[j]);
+        cst[(size_t)m + T + j] = times[j];
+    }
+    std::vector<float> Yh;
+    const float* dYrows = nullptr;
+    Buf<float> dY;
+    Buf<double> dCst, dRg, dTg, dSurv, dPart, dAcc;
+    long rbk = 0, total = 0;
+    ENS_TRY(ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
+        [&](long rb) -> int {
+            rbk = rb;
+            total = X ? (long)n : (which ? h->nv : h->n);
+            ENS_TRY(ens_stage_targets(h, which, Y, total, dY, &dYrows));
+            const float* Yrows = Y;
+            if (!Y) {
+                // the staged targets, copied back once: the censoring distribution is the host's
+                Yh.resize((size_t)total * d_out);
+                HIPCHK(hipMemcpyAsync(Yh.data(), dYrows, Yh.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+                Yrows = Yh.data();
+            }
+            rgi.resize((size_t)d_out * total);
+            ENS_TRY(tbnn_ipcw_weights(Yrows, total, d_out, G_Y, n_g, times, T, rgi.data(), tgi.data()));
+            ENS_TRY(ens_upload(h, dCst, cst.data(), cst.size()));
+            ENS_TRY(ens_upload(h, dRg, rgi.data(), rgi.size()));
+            ENS_TRY(ens_upload(h, dTg, tgi.data(), tgi.size()));
+            if (surv_out) HIPCHK(dSurv.alloc((size_t)T * d_out * rb));
+            HIPCHK(dPart.alloc(slab * (size_t)std::min<long>(wg_max, (rb + 63) / 64)));
+            HIPCHK(dAcc.alloc(slab));
+            return 0;
+        },
+        [&](long r0, long r, long rows, const float* t) -> int {
+            const int nwg = (int)std::min<long>(wg_max, (r + 63) / 64);
+            const dim3 grid((unsigned)nwg, (unsigned)d_out), tb(ENS_TB);
+            const float* y = dYrows + (size_t)r0 * d_out;
+            const double* c = dCst;
+            const double* rg = dRg + r0;
+            const double* tg = dTg;
+            double* sv = surv_out ? (double*)dSurv : nullptr;
+            double* part = dPart;
+            if (nets) hipLaunchKernelGGL(k_ens_brier<true>, grid, tb, 0, h->stream, t, (int)m, r, d_out, y, c, k, c + m, c + m + T, tg, rg, rows, (int)T, sv, part);
+            else hipLaunchKernelGGL(k_ens_brier<false>, grid, tb, 0, h->stream, t, (int)m, r, d_out, y, c, k, c + m, c + m + T, tg, rg, rows, (int)T, sv, part);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_ens_brier_finish, dim3(ens_grid((long)slab)), tb, 0, h->stream, (const double*)part, nwg, (long)slab, (double*)dAcc, (int)(r0 == 0));
+            HIPCHK(hipGetLastError());
+            if (surv_out) ENS_TRY(ens_copy_planes(h, surv_out, r0, rows, sv, r, (size_t)T * d_out));
+            return 0;
+        }));
+    HIPCHK(hipMemcpy(sums.data(), dAcc, slab * sizeof(double), hipMemcpyDeviceToHost));
+    // acc [d_out][slots][T] -> the caller's planes, divided by n once
+    const double dn = (double)total;
+    for (int o = 0; o < d_out; ++o)
+        for (int32_t j = 0; j < T; ++j) {
+            const double* s = sums.data() + (size_t)o * slots * T + j;
+            for (int32_t i = 0; i < m && nets; ++i) bs_net_out[((size_t)i * d_out + o) * T + j] = s[(size_t)i * T] / dn;
+            if (bs_mean_out) bs_mean_out[(size_t)o * T + j] = s[(size_t)(slots - 2) * T] / dn;
+            if (mean_weight_out) mean_weight_out[(size_t)o * T + j] = s[(size_t)(slots - 1) * T] / dn;
+        }
+    return 0;
+}
+
 // M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)
 static void psis_sizes(int32_t m, double r_eff, int* M, int* G, int* q) {
     *M = (int)std::ceil(std::min(0.2 * (double)m, 3.0 * std::sqrt((double)m / r_eff)));

@@ -49,6 +49,11 @@
 //             k_ens_conc_gather copies one output's scores into the order the host sorted the rows in, k_ens_concordance counts the
 //             concordant and tied pairs among the comparable ones (definition: include/tbnn.h, tbnn_ensemble_concordance): row tiles in
 //             registers against score tiles from LDS, compares only, 64-bit integer atomics (layout and work list: at the kernel).
+//   brier       the block [m][d_out][rb] of all m networks, untransformed: k_ens_brier forms the Weibull survival probabilities of every
+//             network at every row and grid time, the mixture's curve and the IPCW Brier sums of both (definition: include/tbnn.h,
+//             tbnn_ensemble_brier): a lane per row with a register tile of 8 times, the per-network row sums by a transposing butterfly
+//             over the wave, one partial per (workgroup, network, column, time), k_ens_brier_finish in workgroup order.  fp64, contraction
+//             off, no atomics.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -1791,5 +1796,157 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_concordance(const T* __restrict_
             atomicAdd(dst, c64);
             atomicAdd(dst + 1, t64);
         }
+    }
+}
+
+// ---- the IPCW Brier score of a survival ensemble over a time grid (tbnn_ensemble_brier) ----
+#define ENS_BT 8                  // times of a lane's register tile (the butterflies below are written for 8)
+#define ENS_BRIER_MAX_T 256       // grid times at the most: their constants live in LDS, padded to a multiple of ENS_BT
+#define ENS_BRIER_MAX_M 4096      // networks at the most (a limit of the interface, tbnn_ensemble_crps')
+#define ENS_BRIER_PART 4194304    // 2^22 doubles: the partial buffer, or one workgroup's slab where that is larger
+#define ENS_BRIER_MAX_WG 1024     // workgroups of k_ens_brier at the most
+
+// A halving (transposing) butterfly over the three lane bits TOP, TOP / 2, TOP / 4: every lane brings 8 values; at each step a lane keeps
+// the half of its values its bit selects, hands the other half to the lane across that bit and adds what it receives: 4 + 2 + 1 adds.  The
+// lane is left with value number 4 b2 + 2 b1 + b0 (b: its three bits) summed over the 8 lanes that differ from it in those bits alone.
+// Every lane of the wave must call it (shuffles).
+template <int TOP>
+__device__ __forceinline__ double ens_halve8(const double (&v)[8], int lane) {
+#pragma clang fp contract(off)
+    const bool u2 = lane & TOP, u1 = lane & (TOP >> 1), u0 = lane & (TOP >> 2);
+    double a[4], b[2];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) a[h] = (u2 ? v[h + 4] : v[h]) + __shfl_xor(u2 ? v[h] : v[h + 4], TOP);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) b[h] = (u1 ? a[h + 2] : a[h]) + __shfl_xor(u1 ? a[h] : a[h + 2], TOP >> 1);
+    return (u0 ? b[1] : b[0]) + __shfl_xor(u0 ? b[0] : b[1], TOP >> 2);
+}
+
+// t: the block [m][d_out][r] of untransformed predictions (the logs of the Weibull scales); Y: the block's signed targets [r][d_out];
+// cst[m]: omega_i = w_i / W; kshape: k; gc[T], gtau[T]: c_j = k log tau_j and tau_j; tginv[d_out][T]: 1 / G(tau_j); rginv: 1 / G(t_r-)
+// of the block's first row in column 0, column o rg_stride further on (NaN where G is 0, both).  surv: the block's [T][d_out][r] or null.
+// part: the partial buffer, one slab [d_out][slots][T] per workgroup, slots = NET ? m + 2 : 2 -- the networks (NET), then the mixture's
+// score and the weights.  Grid: workgroups x d_out; NET = false leaves the per-network terms and their sums out.
+//
+// Mapping.  A lane owns a ROW: a wave reads the 64 consecutive fp32 predictions of one network and column in one coalesced load, the next
+// network's issued before this one's are consumed.  The lane's register tile is ENS_BT = 8 times: 8 fp64 accumulators of Sbar, the 8
+// weights w_rj and indicators I_rj (formed once per row tile from t_r, e_r, 1 / G(t_r-) and the grid constants, which all lanes read from
+// LDS at one address: a broadcast), and c_j.  The four waves of a workgroup own the SAME 64 rows and split the time tiles (wave w: tiles w,
+// w + 4, ...); the workgroup walks its row tiles blockIdx.x, blockIdx.x + gridDim.x, ... in that order; the network loop is innermost.
+// Per network and row a = k f is formed once, then S = exp(-exp(c_j - a)) per time: the direct form, two exponentials per probability,
+// nothing factored (tau^k alone overflows where c_j - a does not).
+// Sums.  A network's 8 terms w (I - S)^2 of a lane are summed over the wave's 64 rows TOGETHER: ens_halve8<32> over lane bits 5..3 leaves
+// a lane with ONE time's sum over 8 rows (7 adds where 8 separate reductions take 24); 8 networks' worth of those are kept, and
+// ens_halve8<4> over lane bits 2..0 then finishes all of them at once (7 more adds): lane L holds the 64-row sum of network
+// i0 + (L & 7) at time j0 + (L >> 3), 63 adds per 64 sums where six shuffle rounds each would take 384.  That lane adds it to its element
+// of the workgroup's slab: a plain read-modify-write by the one lane that ever touches the element, the first row tile storing instead,
+// so the slab needs no clearing, holds its row tiles' sums in tile order, and no atomic is used (the slab of all m networks and T times
+// does not fit LDS: up to 8 MiB).  The mixture's terms and the weights go the same way after the last network, as slots m and m + 1.
+// k_ens_brier_finish adds the slabs in workgroup order.  Rows past r and times past T are computed on harmless values (weight 0) and
+// never stored.  NaN: S and every product keep it (w * NaN, omega * NaN with w or omega 0 included), which is the definition's rule.
+template <bool NET>
+__global__ __launch_bounds__(ENS_TB) void k_ens_brier(const float* __restrict__ t, int m, long r, int d_out, const float* __restrict__ Y,
+                                                       const double* __restrict__ cst, double kshape, const double* __restrict__ gc,
+                                                       const double* __restrict__ gtau, const double* __restrict__ tginv,
+                                                       const double* __restrict__ rginv, long rg_stride, int T, double* __restrict__ surv,
+                                                       double* part) {
+#pragma clang fp contract(off)
+    static_assert(ENS_BT == 8 && ENS_TB == 256, "four waves, eight times per tile: the butterflies are written for them");
+    __shared__ double sc[ENS_BRIER_MAX_T], st[ENS_BRIER_MAX_T], sg[ENS_BRIER_MAX_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, o = blockIdx.y;
+    const int ntt = (T + ENS_BT - 1) / ENS_BT, slots = NET ? m + 2 : 2, slot0 = NET ? m : 0;
+    for (int j = tid; j < ntt * ENS_BT; j += ENS_TB) {
+        sc[j] = j < T ? gc[j] : 0.0;
+        st[j] = j < T ? gtau[j] : 0.0;
+        sg[j] = j < T ? tginv[(size_t)o * T + j] : 0.0;
+    }
+    __syncthreads();
+    const size_t tot = (size_t)r * d_out;
+    double* slab = part + ((size_t)blockIdx.x * d_out + o) * slots * T;
+    const int jl = (lane >> 3) & 7, il = lane & 7;                  // the time and the network of a tile the lane ends up with
+    const long ntile = (r + 63) / 64;
+    for (long rt = blockIdx.x; rt < ntile; rt += gridDim.x) {
+        const bool first = rt == (long)blockIdx.x;
+        const long row = rt * 64 + lane;
+        const bool live = row < r;
+        const float y = live ? Y[(size_t)row * d_out + o] : 1.f;
+        const double tv = (double)fabsf(y), rg = live ? rginv[(size_t)o * rg_stride + row] : 0.0;
+        const bool ev = y > 0.f;
+        const float* __restrict__ tp = t + (size_t)o * r + row;     // (read only where live)
+        for (int tt = wave; tt < ntt; tt += ENS_TB / 64) {
+            const int j0 = tt * ENS_BT;
+            double cj[ENS_BT], w[ENS_BT], ind[ENS_BT], sb[ENS_BT], pend[8];
+#pragma unroll
+            for (int j = 0; j < ENS_BT; ++j) {
+                const bool alive = tv > st[j0 + j];
+                cj[j] = sc[j0 + j];
+                w[j] = !live ? 0.0 : alive ? sg[j0 + j] : ev ? rg : 0.0;
+                ind[j] = alive ? 1.0 : 0.0;
+                sb[j] = 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) pend[q] = 0.0;
+            float fn = live ? tp[0] : 0.f;
+            for (int i0 = 0; i0 < m; i0 += 8) {
+                const int nq = min(8, m - i0);
+#pragma unroll 1
+                for (int q = 0; q < nq; ++q) {
+                    const int i = i0 + q;
+                    const float f = fn;
+                    if (i + 1 < m) fn = live ? tp[(size_t)(i + 1) * tot] : 0.f;
+                    const double a = kshape * (double)f, om = cst[i];
+                    double v[ENS_BT];
+#pragma unroll
+                    for (int j = 0; j < ENS_BT; ++j) {
+                        const double S = exp(-exp(cj[j] - a)), d = ind[j] - S;
+                        sb[j] += om * S;
+                        v[j] = w[j] * (d * d);
+                    }
+                    if (NET) {
+                        const double s8 = ens_halve8<32>(v, lane);
+#pragma unroll
+                        for (int qq = 0; qq < 8; ++qq) pend[qq] = q == qq ? s8 : pend[qq];
+                    }
+                }
+                if (NET) {
+                    const double s = ens_halve8<4>(pend, lane);     // (slots past nq hold an earlier tile's values: not stored)
+                    if (il < nq && j0 + jl < T) {
+                        double* p = slab + (size_t)(i0 + il) * T + j0 + jl;
+                        double old = 0.0;
+                        if (!first) old = *p;
+                        *p = old + s;
+                    }
+                }
+            }
+            double vm[ENS_BT];
+#pragma unroll
+            for (int j = 0; j < ENS_BT; ++j) {
+                const double d = ind[j] - sb[j];
+                vm[j] = w[j] * (d * d);
+                if (surv && live && j0 + j < T) surv[((size_t)(j0 + j) * d_out + o) * r + row] = sb[j];
+            }
+            pend[0] = ens_halve8<32>(vm, lane);
+            pend[1] = ens_halve8<32>(w, lane);
+#pragma unroll
+            for (int q = 2; q < 8; ++q) pend[q] = 0.0;
+            const double s = ens_halve8<4>(pend, lane);
+            if (il < 2 && j0 + jl < T) {
+                double* p = slab + (size_t)(slot0 + il) * T + j0 + jl;
+                double old = 0.0;
+                if (!first) old = *p;
+                *p = old + s;
+            }
+        }
+    }
+}
+
+// acc[count] (count = d_out slots T) = (first ? 0 : acc) + the nwg workgroups' slabs, added in workgroup order: the sums over a block's
+// rows, carried from block to block in block order.  The host divides by n.
+__global__ __launch_bounds__(ENS_TB) void k_ens_brier_finish(const double* __restrict__ part, int nwg, long count, double* __restrict__ acc, int first) {
+#pragma clang fp contract(off)
+    for (long e = (long)blockIdx.x * ENS_TB + threadIdx.x; e < count; e += (long)gridDim.x * ENS_TB) {
+        double s = first ? 0.0 : acc[e];
+        for (int g = 0; g < nwg; ++g) s += part[(size_t)g * count + e];
+        acc[e] = s;
     }
 }

@@ -492,8 +492,8 @@ class predictor(object):
     def survival(self, X, times, n=1, weights=None, likelihood=None):
         """The posterior-mean survival curve of every row of X under a WeibullLikelihood: S(t) = 1 - F(t), the probability that the event
         has not happened by time t, float64 [len(times), d_out, rows].  times: finite and > 0.  n, weights, likelihood: as
-        predictiveCDF's.  (A host loop of predictiveCDF over the times, one device reduction per time: there is no time grid on the
-        device.)"""
+        predictiveCDF's.  (A host loop of predictiveCDF over the times, one device reduction per time; brierScore(curves=True) returns
+        the same curves from one pass on the device.)"""
         from .likelihood import WeibullLikelihood
         lik = self.likelihood if likelihood is None else likelihood
         if not isinstance(lik, WeibullLikelihood):
@@ -538,6 +538,14 @@ class predictor(object):
         out = {"c_index": ratio(res["mean_concordant"], res["mean_tied"]), "per_network": per, "n_bad": int(np.isnan(per).sum()),
                "comparable": res["comparable"], "n_events": (y.reshape(-1, d_out) > 0).sum(axis=0).astype(np.int64),
                "n_censored": (y.reshape(-1, d_out) < 0).sum(axis=0).astype(np.int64)}
+        out.update(self._per_network_stats(per, w))
+        return out
+
+    @staticmethod
+    def _per_network_stats(per, w):
+        """mean, sd, q05, q50, q95 [d_out] of a per-network score per [m', d_out] over the networks whose score is not NaN (weighted where
+        w is given: weighted mean and variance, quantiles of the weighted inverted CDF); NaN where no network is left"""
+        d_out = per.shape[1]
         stats = {k: np.full(d_out, np.nan) for k in ("mean", "sd", "q05", "q50", "q95")}
         wk = np.ones(per.shape[0]) if w is None else w.astype(np.float64)
         for o in range(d_out):
@@ -551,7 +559,51 @@ class predictor(object):
             cdf = np.cumsum(ww[order])
             for key, p in (("q05", 0.05), ("q50", 0.5), ("q95", 0.95)):
                 stats[key][o] = np.quantile(v, p) if w is None else v[order][min(np.searchsorted(cdf, p), v.size - 1)]
-        out.update(stats)
+        return stats
+
+    def brierScore(self, X, Y, times=None, n=1, weights=None, likelihood=None, censoringY=None, curves=False):
+        """The time-dependent Brier score of the ensemble under a WeibullLikelihood with inverse-probability-of-censoring weights (Graf et
+        al. 1999) and its integral: calibration AND sharpness of the survival curves, where concordance judges the ranking alone.  0 is
+        perfect, 0.25 what a constant S = 1/2 scores.  Y: targets as WeibullLikelihood.encode leaves them, each output column its own
+        problem.  times: the grid, finite, > 0, ascending, at most 256 (None: 32 equally spaced times from the 10 % to the 90 % quantile
+        of the observed event times of Y, pooled over the columns).  censoringY: the targets the censoring distribution is estimated
+        from, the training set's, say (None: Y's own).  Everything is formed on the device for every n-th network and for their mixture
+        in one pass over the forward passes (the definition is in include/tbnn.h, tbnn_ensemble_brier).  Returns a dict: times [T];
+        brier float64 [T, d_out], of the mixture's survival curve; per_network [m', T, d_out]; ibs [d_out], the trapezoid of brier over
+        times divided by tau_T - tau_1 (NaN for T < 2); ibs_per_network [m', d_out] -- the posterior distribution of the IBS -- with its
+        mean, sd, q05, q50, q95 [d_out] as concordance forms them; mean_weight [T, d_out], the mean weight (1 when the censoring
+        distribution comes from Y itself); n_events, n_censored int64 [d_out]; n_bad, the count of NaN entries of ibs_per_network; and,
+        with curves=True, curves [T, d_out, rows], the mixture's survival probabilities on the grid."""
+        from .likelihood import WeibullLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, WeibullLikelihood):
+            raise ValueError("brierScore needs a WeibullLikelihood: the score is that of survival curves against times to an event with a "
+                             f"censoring flag, not the targets of a {type(lik).__name__}")
+        y = np.asarray(Y, dtype=np.float32)
+        if times is None:
+            ev = np.unique(y[y > 0])
+            if ev.size < 2:
+                raise ValueError("brierScore: the default grid needs at least two distinct event times in Y; pass times")
+            times = np.linspace(*np.quantile(y[y > 0].astype(np.float64), [0.1, 0.9]), 32)
+        ts = np.asarray(times, dtype=np.float64).reshape(-1)
+        picked, w = self._picked(n, weights)
+        self._network_sd(lik, n)                                       # (sets the shape on the forward chain)
+        res = self._ensure_chain().ensemble_brier(picked, ts, Y=y, X=np.asarray(X, dtype=np.float32), weights=w, likelihood=lik.kind,
+                                                  censoringY=censoringY, curves=curves)
+        d_out = res["brier"].shape[0]
+
+        def ibs(b):                                                    # [..., T] -> [...]
+            if ts.size < 2:
+                return np.full(b.shape[:-1], np.nan)
+            return np.sum(0.5 * (b[..., 1:] + b[..., :-1]) * np.diff(ts), axis=-1) / (ts[-1] - ts[0])
+        per = ibs(res["per_network"])
+        out = {"times": ts, "brier": res["brier"].T.copy(), "per_network": res["per_network"].transpose(0, 2, 1).copy(), "ibs": ibs(res["brier"]),
+               "ibs_per_network": per, "mean_weight": res["mean_weight"].T.copy(), "n_bad": int(np.isnan(per).sum()),
+               "n_events": (y.reshape(-1, d_out) > 0).sum(axis=0).astype(np.int64),
+               "n_censored": (y.reshape(-1, d_out) < 0).sum(axis=0).astype(np.int64)}
+        out.update(self._per_network_stats(per, w))
+        if curves:
+            out["curves"] = res["curves"]
         return out
 
     # ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
