@@ -637,6 +637,45 @@ int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m, int64_t t
  * that is 0 or not finite. */
 int tbnn_ipcw_weights(const float* Y, int64_t n, int32_t d_out, const float* G_Y, int64_t n_g, const double* times, int32_t T,
                       double* row_ginv_out, double* time_ginv_out);
+/* The cumulative/dynamic time-dependent AUC of a survival ensemble with inverse-probability-of-censoring weights (Uno, Cai, Tian, Wei
+ * 2007; Hung, Chiang 2010) over a grid of times: at horizon tau, how well the model separates the rows that fail by tau from the rows that
+ * survive it -- the ranking score per horizon beside tbnn_ensemble_concordance's pooled one and tbnn_ensemble_brier's calibration.  Counted
+ * on the device, per network and for the mixture.  Arguments up to `T` are tbnn_ensemble_brier's.  Per output column o, each its own
+ * survival problem:
+ *   targets         t_r = |y_r|, e_r = (y_r > 0): the encoding of TBNN_LIK_WEIBULL, tbnn_ensemble_concordance and tbnn_ensemble_brier
+ *   grid            `times`, under the rules of tbnn_ensemble_brier: finite, > 0, strictly ascending, 1 <= T <= 256
+ *   case at tau_g   row i iff e_i = 1 and t_i <= tau_g          control at tau_g   row j iff t_j > tau_g, event or censored
+ *                   a row censored at or before tau_g is neither; t == tau_g makes an event a case and never a control
+ *   case weight     omega_i = 1 / G(t_i-): the row_ginv_out of tbnn_ipcw_weights unchanged, from the scored rows or from G_Y as in
+ *                   tbnn_ensemble_brier.  A needed weight whose G is 0 is NaN and makes that AUC value NaN
+ *   auc(g)          sum_i sum_j omega_i [1{r_i > r_j} + 1/2 1{r_i == r_j}] / (W_g C_g) over the cases i and the controls j at tau_g;
+ *                   W_g the sum of omega_i over the cases, formed on the host in fp64 in sorted order; C_g the number of controls;
+ *                   NaN where there is no case or no control
+ *   risk, network   r = -f, the raw fp32 output compared as fp32: the same at every time, a pair is concordant iff f_i < f_j
+ *   risk, mixture   r = 1 - Sbar(tau_g | x): concordant iff Sbar_i < Sbar_j, compared in fp64.  Sbar is the bits tbnn_ensemble_brier
+ *                   returns in surv_out for the same arguments (its kernel forms them here too), so saturated curves (Sbar == 1.0 or
+ *                   0.0) are ties.  The mixture orders the rows differently at different times; a single network does not
+ * NaN: a network with a NaN score in a column reports NaN for that column at every time; a NaN anywhere in Sbar at tau_g makes the
+ * mixture's auc(g) NaN.  The network weights enter Sbar alone; there are no row weights.
+ * Staging and work.  The host sorts the rows of a column by time once and lays them out in segments between grid times, each padded with
+ * NaN scores to 4 positions, so that the controls at tau_g are a suffix that starts on a multiple of 4 and the device never reads a time.
+ * A pair is compared once per network, not once per grid time: k_ens_auc holds a tile of 1024 case rows in registers, walks the control
+ * tiles through LDS from the end of the sorted order downwards with running integer counters per row, and at every grid boundary it
+ * crosses adds omega_i (2 concordant + tied) of the rows that are cases there, in fp64, summed over the workgroup in a fixed order.  The
+ * mixture is the same kernel on fp64 scores, one job per grid time that scores its own boundary alone; its curves are held on the device
+ * for at most 2^25 / (d_out n) grid times at a time.  Sums: one slab of T doubles per (workgroup, network), at most 1024 workgroups per
+ * network and 2^22 doubles per launch whatever n; a workgroup walks its work items in list order, a finish kernel adds the slabs in
+ * workgroup order.  The work list depends on n, the sort and the grid alone.  No floating-point atomics: the same bits from run to run
+ * and whatever the network chunks.  The networks are cut into chunks as for tbnn_ensemble_concordance, the rows of the mixture's pass into
+ * blocks as for tbnn_ensemble_brier.
+ * n is at most 2^22 rows, as tbnn_ensemble_concordance's.  (A row's 32-bit counters cannot wrap: a row meets at most 2^22 + 2^11
+ * positions, so 2 concordant + tied stays below 2^24; it is widened to fp64, exactly, at every boundary.)
+ * auc_mix_out: host [d_out][T]; auc_net_out: host [m][d_out][T]; case_weight_out: host [d_out][T], W_g; controls_out: host [d_out][T],
+ * C_g; each may be NULL, not all four.
+ * Refused, with nothing written: everything tbnn_ensemble_brier refuses, and more than 2^22 rows. */
+int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w, int which,
+                      const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times, int32_t T,
+                      double* auc_mix_out, double* auc_net_out, double* case_weight_out, int64_t* controls_out);
 /* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
  * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
  * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).

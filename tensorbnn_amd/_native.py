@@ -132,6 +132,8 @@ SYMBOLS = [
     ("tbnn_ensemble_brier", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _fp, C.c_int64, _dp, C.c_int32,
                                       _dp, _dp, _dp, _dp]),
     ("tbnn_ipcw_weights", C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp]),
+    ("tbnn_ensemble_auc", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _fp, C.c_int64, _dp, C.c_int32,
+                                    _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
@@ -732,6 +734,28 @@ class Chain:
         _check(lib.tbnn_ensemble_brier(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, _p(gy),
                                        0 if gy is None else gy.shape[0], _pd(ts), ts.size, _pd(out["brier"]), _pd(out.get("per_network")),
                                        _pd(out.get("curves")), _pd(out["mean_weight"])))
+        return out
+
+    def ensemble_auc(self, thetas, times, Y=None, X=None, which: int = 1, weights=None, likelihood=None, censoringY=None, per_network: bool = True):
+        """The cumulative/dynamic time-dependent AUC of a survival ensemble with inverse-probability-of-censoring case weights over the
+        grid `times` (the rules of ensemble_brier), its pairs counted on the device once for all grid times (tbnn_ensemble_auc; the
+        definition is in include/tbnn.h): at tau, the weighted share of (case: an event by tau; control: a row that outlives tau) pairs
+        that the risk ranks correctly, ties a half.  A dict: auc float64 [d_out, T], of the mixture's survival curve (its risk at tau is
+        1 - Sbar(tau), the bits of ensemble_brier's curves); per_network [m, d_out, T] (per_network=True), each network's output being
+        its risk at every time; case_weight float64 [d_out, T], the sum of the case weights; n_controls int64 [d_out, T].  NaN where
+        there is no case or no control, or a NaN score.  censoringY, weights, likelihood, Y, X, which: as ensemble_brier's"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        yp, _sd, lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, likelihood)
+        m = th.shape[0]
+        ts = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        gy = None if censoringY is None else _f32(censoringY).reshape(-1, self.d_out)
+        out = {"auc": np.empty((self.d_out, ts.size), dtype=np.float64), "case_weight": np.empty((self.d_out, ts.size), dtype=np.float64),
+               "n_controls": np.empty((self.d_out, ts.size), dtype=np.int64)}
+        if per_network:
+            out["per_network"] = np.empty((m, self.d_out, ts.size), dtype=np.float64)
+        _check(lib.tbnn_ensemble_auc(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, _p(gy),
+                                     0 if gy is None else gy.shape[0], _pd(ts), ts.size, _pd(out["auc"]), _pd(out.get("per_network")),
+                                     _pd(out["case_weight"]), out["n_controls"].ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,

@@ -1215,6 +1215,266 @@ extern "C" int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m
     return 0;
 }
 
+// The host staging of one output column o of tbnn_ensemble_auc (definition: include/tbnn.h; layout: k_ens_auc).  Y: the targets
+// [n][d_out]; rginv: the column's 1 / G(t_r-) in row order.  The rows are stable-sorted by (time ascending, events before censored rows at
+// equal times) and laid out in segments -- segment s < T: tau_{s-1} < t <= tau_s, segment T: t > tau_T -- each padded to ENS_AUC_G
+// positions.  src, pseg, omega [npad], ppos [T]: as k_ens_auc reads them.  W [T]: the sum of the case weights at tau_g, added in sorted
+// order; ncase, ctrl [T]: the counts of cases and of controls.  The work items of the column are appended to `items`: per case tile that
+// holds a case, the control tiles from the one that holds the boundary of the tile's earliest case segment to the last, cut into spans of
+// at most ENS_AUC_SPAN tiles as equal as they come.  Nothing here reads a score.
+static void auc_stage(const float* Y, long n, int d_out, int o, const double* times, int T, const double* rginv, long npad, int* src, int* pseg,
+                      double* omega, int* ppos, double* W, int64_t* ncase, int64_t* ctrl, std::vector<int4>& items) {
+    auto time_of = [&](int i) { return std::fabs(Y[(size_t)i * d_out + o]); };
+    auto event = [&](int i) { return Y[(size_t)i * d_out + o] > 0.f; };
+    std::vector<int> order((size_t)n);
+    for (long i = 0; i < n; ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        const float ta = time_of(a), tb = time_of(b);
+        return ta != tb ? ta < tb : (event(a) && !event(b));
+    });
+    for (long p = 0; p < npad; ++p) { src[p] = -1; pseg[p] = T; omega[p] = 0.0; }
+    long p = 0, k = 0;
+    double w = 0.0;
+    int64_t cases = 0;
+    for (int s = 0; s <= T; ++s) {
+        for (; k < n && (s == T || (double)time_of(order[k]) <= times[s]); ++k, ++p) {
+            const int row = order[k];
+            src[p] = row;
+            if (s < T && event(row)) { pseg[p] = s; omega[p] = rginv[row]; w += rginv[row]; ++cases; }
+        }
+        p = (p + ENS_AUC_G - 1) / ENS_AUC_G * ENS_AUC_G;
+        if (s < T) { ppos[s] = (int)p; W[s] = w; ncase[s] = cases; ctrl[s] = n - k; }
+    }
+    const int ntile = (int)(npad / ENS_CI);
+    for (int t = 0; t < ntile; ++t) {
+        int lo = T, hi = -1;
+        for (long i = (long)t * ENS_CI; i < (long)(t + 1) * ENS_CI; ++i)
+            if (pseg[i] < T) { lo = std::min(lo, pseg[i]); hi = std::max(hi, pseg[i]); }
+        if (hi < 0) continue;
+        const int j0 = ppos[lo] / ENS_CI, len = ntile - j0, parts = (len + ENS_AUC_SPAN - 1) / ENS_AUC_SPAN;
+        for (int q = 0; q < parts; ++q)
+            items.push_back(make_int4(t, j0 + (int)((long)len * q / parts), j0 + (int)((long)len * (q + 1) / parts), lo | (hi << 16)));
+    }
+}
+
+// The cumulative/dynamic time-dependent AUC with IPCW case weights (definition: include/tbnn.h; kernels: k_ens_auc_gather, k_ens_auc,
+// k_ens_brier, k_ens_brier_finish).  Two passes over the forward kernels.  Per network: a network's AUC needs all of its rows, so the
+// NETWORKS are cut (ensemble_forward), half of the chunk budget for the predictions and half for the sorted copy of one column, as
+// tbnn_ensemble_concordance does.  The mixture: Sbar needs all m networks of a row, so the ROWS are cut (ensemble_row_blocks) and
+// k_ens_brier<false> writes the curves -- tbnn_ensemble_brier's own kernel on the same constants, so the same bits -- for a group of at
+// most ENS_AUC_CURVES / (d_out n) grid times at a time into a device copy in row order; each time of the group is then one fp64 job
+// of k_ens_auc that scores its own boundary alone.  Slabs: [workgroups][jobs of a launch][T] within ENS_AUC_PART doubles whatever n;
+// k_ens_brier_finish adds them in workgroup order.  The host divides by 2 W_g C_g.
+extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
+                                 int which, const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times,
+                                 int32_t T, double* auc_mix_out, double* auc_net_out, double* case_weight_out, int64_t* controls_out) {
+    NEED(h);
+    const std::string who = "ensemble_auc";
+    const int d_out = h->nd.d_out;
+    if (!auc_mix_out && !auc_net_out && !case_weight_out && !controls_out) return fail(-1, who + ": every output is null");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    if (likelihood != TBNN_LIK_WEIBULL) {
+        const char* name = ens_lik_name(likelihood);
+        if (!name && !lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
+        return fail(-1, who + ": " + (name ? name : "this likelihood") + " has no survival function with a censoring flag (TBNN_LIK_WEIBULL has)");
+    }
+    const float kf = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
+    if (!df_ok(kf)) return fail(-1, who + ": the survival function under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
+    ENS_TRY(brier_check_times(who, times, T));
+    if (!thetas || m < 1 || theta_stride < h->nd.P) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (m > ENS_BRIER_MAX_M) return fail(-1, who + ": m = " + std::to_string(m) + " exceeds " + std::to_string(ENS_BRIER_MAX_M) + " networks");
+    ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
+    double Wnet = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &Wnet));
+    ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
+    if (G_Y && n_g < 1) return fail(-1, who + ": G_Y with n_g < 1");
+    const std::string too_many = who + ": more than " + std::to_string(ENS_CONC_MAX_N) + " rows (the work list grows with the square of the rows)";
+    if (Y && n >= 1) {
+        if (n > ENS_CONC_MAX_N) return fail(-1, too_many);
+        ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
+    }
+    if (G_Y) ENS_TRY(conc_check_targets(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
+    if (!X && which != 0 && which != 1) return fail(-1, "which must be 0 (training rows) or 1 (validation rows)");
+    const double k = (double)kf;
+    const size_t dT = (size_t)d_out * T;
+    std::vector<float> Yh;
+    std::vector<double> rgi, tgi(dT), omega, Wc(dT), num_net, num_mix(dT, 0.0);
+    std::vector<int> src, pseg, ppos(dT), hbad;
+    std::vector<int64_t> ncase(dT), ctrl(dT);
+    std::vector<int4> items;
+    std::vector<size_t> item_off((size_t)d_out + 1, 0);
+    Buf<int> dSrc, dPseg, dPpos, dBad;
+    Buf<int4> dItems;
+    Buf<float> dS, dYown;
+    Buf<double> dOmega, dRg, dPart, dNum, dNumMix;
+    const float* dYrows = nullptr;
+    long rows = 0, npad = 0;
+    const size_t bad_slots = (size_t)m * d_out + dT;               // the networks' [m][d_out], then the mixture's [d_out][T]
+    // once, by whichever pass comes first (the rows are staged by then): the targets, the weights, the layout and the work list
+    auto prepare = [&](long total) -> int {
+        if (rows) return 0;
+        if (total > ENS_CONC_MAX_N) return fail(-1, too_many);
+        ENS_TRY(ens_stage_targets(h, which, Y, total, dYown, &dYrows));
+        const float* Yrows = Y;
+        if (!Y) {
+            // the staged targets, copied back once: the censoring distribution and the sort are the host's
+            Yh.resize((size_t)total * d_out);
+            HIPCHK(hipMemcpyAsync(Yh.data(), dYrows, Yh.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            Yrows = Yh.data();
+        }
+        rgi.resize((size_t)d_out * total);
+        ENS_TRY(tbnn_ipcw_weights(Yrows, total, d_out, G_Y, n_g, times, T, rgi.data(), tgi.data()));
+        npad = (total + (long)ENS_AUC_G * (T + 1) + ENS_CI - 1) / ENS_CI * ENS_CI;
+        src.resize((size_t)d_out * npad);
+        pseg.resize(src.size());
+        omega.resize(src.size());
+        for (int o = 0; o < d_out; ++o) {
+            const size_t a = (size_t)o * npad, b = (size_t)o * T;
+            auc_stage(Yrows, total, d_out, o, times, T, rgi.data() + (size_t)o * total, npad, src.data() + a, pseg.data() + a, omega.data() + a,
+                      ppos.data() + b, Wc.data() + b, ncase.data() + b, ctrl.data() + b, items);
+            item_off[o + 1] = items.size();
+        }
+        ENS_TRY(ens_upload(h, dSrc, src.data(), src.size()));
+        ENS_TRY(ens_upload(h, dPseg, pseg.data(), pseg.size()));
+        ENS_TRY(ens_upload(h, dOmega, omega.data(), omega.size()));
+        ENS_TRY(ens_upload(h, dPpos, ppos.data(), ppos.size()));
+        if (!items.empty()) ENS_TRY(ens_upload(h, dItems, items.data(), items.size()));
+        HIPCHK(dBad.alloc(bad_slots));
+        HIPCHK(hipMemsetAsync(dBad, 0, bad_slots * sizeof(int), h->stream));
+        size_t most = 0;
+        for (int o = 0; o < d_out; ++o) most = std::max(most, item_off[o + 1] - item_off[o]);
+        HIPCHK(dPart.alloc(std::max<size_t>((size_t)T, std::min<size_t>(ENS_AUC_PART, std::min<size_t>(most, ENS_AUC_MAX_WG) * T * (size_t)std::max<int32_t>(m, T)))));
+        rows = total;
+        return 0;
+    };
+    // column o of the sorted scores S[jobs][npad]: the pair kernel over the column's work items, a bounded number of jobs per launch, and
+    // the slabs' sum into num [jobs][T]
+    auto count_pairs = [&](auto* S, int jobs, int o, int gsel0, double* num) -> int {
+        using V = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
+        const size_t ni = item_off[o + 1] - item_off[o];
+        if (!ni) return 0;                                          // (no case at any time: num is not read)
+        const int nwg = (int)std::min<size_t>(ni, ENS_AUC_MAX_WG), per = (int)std::max<size_t>(1, (size_t)ENS_AUC_PART / ((size_t)nwg * T));
+        for (int j0 = 0; j0 < jobs; j0 += per) {
+            const int cj = std::min(per, jobs - j0);
+            hipLaunchKernelGGL(k_ens_auc<V>, dim3((unsigned)nwg, (unsigned)cj), dim3(ENS_TB), 0, h->stream, S + (size_t)j0 * npad, cj, npad,
+                               (const int*)(dPseg + (size_t)o * npad), (const double*)(dOmega + (size_t)o * npad), (const int*)(dPpos + (size_t)o * T),
+                               (int)T, (const int4*)(dItems + item_off[o]), (int)ni, gsel0 < 0 ? -1 : gsel0 + j0, (double*)dPart);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_ens_brier_finish, dim3(ens_grid((long)cj * T)), dim3(ENS_TB), 0, h->stream, (const double*)dPart, nwg, (long)cj * T,
+                               num + (size_t)j0 * T, 1);
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
+    };
+    if (auc_net_out) {
+        num_net.assign((size_t)m * dT, 0.0);
+        ENS_TRY(ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, std::max<size_t>(1, ens_chunk_floats() / 2),
+            [&](long r, int chunk) -> int {
+                ENS_TRY(prepare(r));
+                HIPCHK(dS.alloc((size_t)chunk * npad));
+                HIPCHK(dNum.alloc((size_t)m * dT));                 // [d_out][m][T]
+                return 0;
+            },
+            [&](int i0, int c, const float* dOut, long) -> int {
+                for (int o = 0; o < d_out; ++o) {
+                    hipLaunchKernelGGL(k_ens_auc_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream,
+                                       dOut + (size_t)o * rows, (size_t)rows * d_out, c, (const int*)(dSrc + (size_t)o * npad), npad, (float*)dS,
+                                       dBad + (size_t)i0 * d_out + o, d_out);
+                    HIPCHK(hipGetLastError());
+                    ENS_TRY(count_pairs((const float*)dS, c, o, -1, dNum + ((size_t)o * m + i0) * T));
+                }
+                return 0;
+            }));
+        for (int o = 0; o < d_out; ++o)
+            if (item_off[o + 1] > item_off[o])
+                HIPCHK(hipMemcpyAsync(num_net.data() + (size_t)o * m * T, dNum + (size_t)o * m * T, (size_t)m * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if (auc_mix_out) {
+        std::vector<double> cst((size_t)m + 2 * (size_t)T), tgg, got;
+        for (int32_t i = 0; i < m; ++i) cst[i] = (net_w ? (double)net_w[i] : 1.0) / Wnet;
+        Buf<double> dCst, dTg, dSurv, dBpart, dCurves, dSorted;
+        for (int g0 = 0, Tg = T; g0 < T; g0 += Tg) {
+            // a group of grid times: k_ens_brier on its own T' = Tg times (a probability's bits do not depend on its place in the grid)
+            const size_t slab = (size_t)d_out * 2 * T;
+            const long wg_max = std::max<long>(1, std::min<long>(ENS_BRIER_MAX_WG, (long)(ENS_BRIER_PART / slab)));
+            ENS_TRY(ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
+                [&](long rb) -> int {
+                    ENS_TRY(prepare(X ? (long)n : (which ? h->nv : h->n)));
+                    if (g0 == 0) {
+                        Tg = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, (size_t)ENS_AUC_CURVES / ((size_t)d_out * rows)));
+                        ENS_TRY(ens_upload(h, dRg, rgi.data(), rgi.size()));
+                        HIPCHK(dCurves.alloc((size_t)Tg * d_out * rows));
+                        HIPCHK(dSorted.alloc((size_t)Tg * npad));
+                        HIPCHK(dNumMix.alloc((size_t)Tg * T));
+                    }
+                    Tg = std::min(Tg, T - g0);
+                    for (int32_t j = 0; j < Tg; ++j) {
+                        cst[(size_t)m + j] = k * std::log(times[g0 + j]);
+                        cst[(size_t)m + Tg + j] = times[g0 + j];
+                    }
+                    tgg.resize((size_t)d_out * Tg);
+                    for (int o = 0; o < d_out; ++o)
+                        for (int32_t j = 0; j < Tg; ++j) tgg[(size_t)o * Tg + j] = tgi[(size_t)o * T + g0 + j];
+                    ENS_TRY(ens_upload(h, dCst, cst.data(), (size_t)m + 2 * (size_t)Tg));
+                    ENS_TRY(ens_upload(h, dTg, tgg.data(), tgg.size()));
+                    HIPCHK(dSurv.alloc((size_t)Tg * d_out * rb));
+                    HIPCHK(dBpart.alloc(slab * (size_t)std::min<long>(wg_max, (rb + 63) / 64)));
+                    return 0;
+                },
+                [&](long r0, long r, long, const float* t) -> int {
+                    const int nwg = (int)std::min<long>(wg_max, (r + 63) / 64);
+                    const double* c = dCst;
+                    hipLaunchKernelGGL(k_ens_brier<false>, dim3((unsigned)nwg, (unsigned)d_out), dim3(ENS_TB), 0, h->stream, t, (int)m, r, d_out,
+                                       dYrows + (size_t)r0 * d_out, c, k, c + m, c + m + Tg, (const double*)dTg, (const double*)(dRg + r0), rows, Tg,
+                                       (double*)dSurv, (double*)dBpart);
+                    HIPCHK(hipGetLastError());
+                    HIPCHK(hipMemcpy2DAsync(dCurves + r0, (size_t)rows * sizeof(double), dSurv, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
+                                            (size_t)Tg * d_out, hipMemcpyDeviceToDevice, h->stream));
+                    return 0;
+                }));
+            got.resize((size_t)Tg * T);
+            for (int o = 0; o < d_out; ++o) {
+                // job j of the column: the curve at tau_{g0 + j}, [Tg][d_out][rows] in dCurves
+                hipLaunchKernelGGL(k_ens_auc_gather<double>, dim3(ens_grid(npad), (unsigned)Tg), dim3(ENS_TB), 0, h->stream,
+                                   (const double*)(dCurves + (size_t)o * rows), (size_t)rows * d_out, Tg, (const int*)(dSrc + (size_t)o * npad), npad,
+                                   (double*)dSorted, dBad + (size_t)m * d_out + (size_t)o * T + g0, 1);
+                HIPCHK(hipGetLastError());
+                if (item_off[o + 1] == item_off[o]) continue;
+                ENS_TRY(count_pairs((const double*)dSorted, Tg, o, g0, (double*)dNumMix));
+                HIPCHK(hipMemcpyAsync(got.data(), dNumMix, got.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+                for (int j = 0; j < Tg; ++j) num_mix[(size_t)o * T + g0 + j] = got[(size_t)j * T + g0 + j];
+            }
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+    }
+    if (!rows) {
+        // neither pass ran: the weights and the counts alone, no forward pass
+        HIPCHK(hipSetDevice(h->device));
+        const long total = X ? (long)n : (which ? h->nv : h->n);
+        if (total < 1) return fail(-1, X ? who + ": n < 1" : which ? "tbnn_set_validation has not been called" : "tbnn_set_data has not been called");
+        ENS_TRY(prepare(total));
+    }
+    hbad.resize(bad_slots);
+    HIPCHK(hipMemcpyAsync(hbad.data(), dBad, bad_slots * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // auc = num / (2 W_g C_g): num sums omega (2 concordant + tied)
+    for (int o = 0; o < d_out; ++o)
+        for (int32_t g = 0; g < T; ++g) {
+            const size_t e = (size_t)o * T + g;
+            const bool some = ncase[e] > 0 && ctrl[e] > 0;
+            const double den = 2.0 * Wc[e] * (double)ctrl[e];
+            for (int32_t i = 0; i < m && auc_net_out; ++i)
+                auc_net_out[((size_t)i * d_out + o) * T + g] = some && !hbad[(size_t)i * d_out + o] ? num_net[((size_t)o * m + i) * T + g] / den : (double)NAN;
+            if (auc_mix_out) auc_mix_out[e] = some && !hbad[(size_t)m * d_out + e] ? num_mix[e] / den : (double)NAN;
+            if (case_weight_out) case_weight_out[e] = Wc[e];
+            if (controls_out) controls_out[e] = ctrl[e];
+        }
+    return 0;
+}
+
 // M = ceil(min(0.2 m, 3 sqrt(m / r_eff))), G = 30 + floor(sqrt M), q = floor(M / 4 + 1/2) (include/tbnn.h, tbnn_ensemble_loo)
 static void psis_sizes(int32_t m, double r_eff, int* M, int* G, int* q) {
     *M = (int)std::ceil(std::min(0.2 * (double)m, 3.0 * std::sqrt((double)m / r_eff)));

@@ -54,6 +54,11 @@
 //             tbnn_ensemble_brier): a lane per row with a register tile of 8 times, the per-network row sums by a transposing butterfly
 //             over the wave, one partial per (workgroup, network, column, time), k_ens_brier_finish in workgroup order.  fp64, contraction
 //             off, no atomics.
+//   auc         both: per network a chunk [c][d_out][n] like the concordance index's, for the mixture k_ens_brier's curves of a block of rows.
+//             k_ens_auc_gather copies one output's scores into the host's padded, time-sorted layout; k_ens_auc compares every (case,
+//             control) pair once for all grid times and adds the IPCW-weighted running counts at each grid boundary its descending walk
+//             crosses (definition: include/tbnn.h, tbnn_ensemble_auc; layout, work list and summation order: at the kernel); the slabs go
+//             through k_ens_brier_finish.  Integer counts, fp64 sums in a fixed order, contraction off, no atomics.
 //
 // The transforms and the Bernoulli / categorical terms are evaluated in fp32 like the sampler's kernels (kernels_generic.hpp); the Gaussian
 // term has no transcendental per element and is formed in fp64 from the fp32 prediction.  Streaming VALU kernels: no MFMA, no inline asm.
@@ -1948,5 +1953,151 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_brier_finish(const double* __res
         double s = first ? 0.0 : acc[e];
         for (int g = 0; g < nwg; ++g) s += part[(size_t)g * count + e];
         acc[e] = s;
+    }
+}
+
+// ---- the cumulative/dynamic time-dependent AUC of a survival ensemble with IPCW case weights over a time grid (tbnn_ensemble_auc) ----
+#define ENS_AUC_G 4               // the staging granule: a segment of the sorted order is padded with NaN scores to a multiple of it (one LDS read of the walk)
+#define ENS_AUC_SPAN 8            // control tiles of a work item at the most, as ENS_CONC_SPAN
+#define ENS_AUC_MAX_WG 1024       // workgroups of k_ens_auc per network at the most: each owns one slab of T doubles per network
+#define ENS_AUC_PART 4194304      // 2^22 doubles: the slab buffer of one launch (at least 16 networks' worth at 1024 workgroups and 256 times)
+#define ENS_AUC_CURVES 33554432   // 2^25 doubles: the mixture's curves held on the device at a time, in row order (and as many again, sorted)
+
+// The host sorts the rows of one output by time and lays them out in SEGMENTS: segment s < T holds the rows with tau_{s-1} < t <= tau_s,
+// segment T those with t > tau_T, each padded to a multiple of ENS_AUC_G positions, the whole to a multiple of ENS_CI (npad).  src[npad]
+// is the row a position holds, -1 for padding.  The controls at tau_g are then the suffix [ppos_g, npad), ppos_g the start of segment
+// g + 1, and the cases at tau_g the events of the segments up to g: the device never reads a time.
+//
+// k_ens_auc_gather: S[job][i] = in[job * stride + src[i]], NaN where src[i] < 0 -- a NaN is neither below nor equal to anything, so the
+// padding needs no mask.  bad[job * bad_stride] = 1 where a job holds a NaN among its rows (every writer stores the same value).
+// T = float: the networks of a chunk; T = double: the mixture's curve at one grid time per job.
+template <class T>
+__global__ __launch_bounds__(ENS_TB) void k_ens_auc_gather(const T* __restrict__ in, size_t stride, int c, const int* __restrict__ src, long npad,
+                                                            T* __restrict__ S, int* __restrict__ bad, int bad_stride) {
+    for (int job = blockIdx.y; job < c; job += gridDim.y) {
+        for (long i = (long)blockIdx.x * ENS_TB + threadIdx.x; i < npad; i += (long)gridDim.x * ENS_TB) {
+            const int k = src[i];
+            T v = (T)NAN;
+            if (k >= 0) {
+                v = in[(size_t)job * stride + k];
+                if (v != v) bad[(size_t)job * bad_stride] = 1;
+            }
+            S[(size_t)job * npad + i] = v;
+        }
+    }
+}
+
+// S[njobs][npad]: the sorted scores of the launch's jobs (a network's outputs, fp32; or the mixture's survival probabilities at ONE grid
+// time, fp64: larger means a later event in both, so a pair (case i, control j) is concordant iff s_i < s_j).  pseg[npad]: the segment of
+// a position that holds a case (an event at or before tau_T), nT for every other; omega[npad]: the case's weight 1 / G(t-), NaN where G
+// is 0 (0 where pseg is nT).  ppos[nT]: the boundaries.  items: the host's work list, (case tile, first control tile, one past the last,
+// the smallest | the largest << 16 segment among the tile's cases).  gsel0 < 0: a job scores every boundary; else job y scores boundary
+// gsel0 + y alone (the mixture: its scores are that time's).  part: one slab [nT] per (workgroup, job), [gridDim.x][njobs][nT]: the sums
+// omega_i (2 concordant + tied) over the cases at tau_g and their controls, of the items the workgroup walked.
+//
+// Sharing pairs across the grid.  A pair (i, j) is compared ONCE per job and counts at every g with pseg_i <= g and ppos_g <= j.  A case
+// tile is ENS_CI consecutive positions in registers, ENS_CR per lane as in k_ens_concordance, each with its own pair of 32-bit counters
+// (concordant, tied); the control tiles of the item pass through double-buffered LDS the same way, but DESCENDING from the item's end, so
+// that the counters hold the pairs with everything behind the current position.  Where the walk reaches a boundary ppos_g -- a multiple
+// of ENS_AUC_G, so between two LDS reads: no per-lane mask anywhere -- the lanes whose case belongs to a segment <= g contribute
+// omega_i (2 concordant + tied), formed in fp64 from the exact integers, summed over the lane's rows in index order, over the wave by an
+// xor butterfly and over the four waves in wave order; thread g adds the sum to the register it keeps for boundary g.  At the item's end
+// the boundaries that lie below its span receive its total: one reduction per distinct set of contributing lanes (g below the tile's
+// largest case segment) and one for all the others.  The ranges between boundaries are uniform over the workgroup: every barrier is met
+// by all threads.
+// Load balance and order.  The walk of a case tile (long for early tiles) is cut into items of at most ENS_AUC_SPAN control tiles; the
+// list depends on n, the sort and the grid alone.  Workgroup x walks items x, x + gridDim.x, ... in that order; k_ens_brier_finish adds
+// the slabs in workgroup order.  gridDim.x is min(items, ENS_AUC_MAX_WG) whatever the chunk, so a job's bits depend on nothing else.
+// Counters.  A row meets at most npad <= 2^22 + 2^11 controls, so 2 concordant + tied stays below 2^24 in 32 bits (an item alone gives
+// a row at most 2^13 pairs) and is widened to fp64, exactly, at every boundary.
+template <class T>
+__global__ __launch_bounds__(ENS_TB) void k_ens_auc(const T* __restrict__ S, int njobs, long npad, const int* __restrict__ pseg,
+                                                     const double* __restrict__ omega, const int* __restrict__ ppos, int nT,
+                                                     const int4* __restrict__ items, int nitems, int gsel0, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    typedef T V4 __attribute__((ext_vector_type(4)));
+    static_assert(ENS_CI == 4 * ENS_TB && ENS_AUC_G == 4, "a thread stages four scores of a control tile; a boundary falls between two LDS reads");
+    static_assert(ENS_BRIER_MAX_T <= ENS_TB, "thread g keeps the sum of boundary g");
+    __shared__ V4 tile[2][ENS_TB];
+    __shared__ double red[2][ENS_TB / 64];
+    __shared__ int sp[ENS_BRIER_MAX_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < nT) sp[tid] = ppos[tid];
+    __syncthreads();
+    int b = 0, e = 0;
+    for (int job = blockIdx.y; job < njobs; job += gridDim.y) {
+        const T* __restrict__ s = S + (size_t)job * npad;
+        double mine = 0.0;                                          // thread g: boundary g's sum over this workgroup's items
+        for (int ii = blockIdx.x; ii < nitems; ii += gridDim.x) {
+            const int4 it = items[ii];
+            int glo = it.w & 0xffff, ghi = nT - 1;
+            const int gmx = it.w >> 16;
+            if (gsel0 >= 0) {
+                if (gsel0 + job < glo) continue;                    // (no case of the tile at that time)
+                glo = ghi = gsel0 + job;
+            }
+            const int Jlo = max(it.y, sp[glo] / ENS_CI), Jhi = it.z;
+            if (Jlo >= Jhi) continue;                               // (the span lies below every boundary asked for)
+            const long i0 = (long)it.x * ENS_CI;
+            T si[ENS_CR];
+            int ps[ENS_CR];
+            double om[ENS_CR];
+            unsigned cc[ENS_CR], tt[ENS_CR];
+#pragma unroll
+            for (int r = 0; r < ENS_CR; ++r) {
+                si[r] = s[i0 + tid + ENS_TB * r];
+                ps[r] = pseg[i0 + tid + ENS_TB * r];
+                om[r] = omega[i0 + tid + ENS_TB * r];
+                cc[r] = tt[r] = 0;
+            }
+            // the sum over the workgroup's lanes whose case lies in a segment <= gmask, added to the boundaries [ga, gb)
+            auto emit = [&](int gmask, int ga, int gb) {
+                double v = 0.0;
+#pragma unroll
+                for (int r = 0; r < ENS_CR; ++r) v += ps[r] <= gmask ? om[r] * (double)(2u * cc[r] + tt[r]) : 0.0;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (lane == 0) red[e & 1][wave] = v;
+                __syncthreads();
+                if (tid >= ga && tid < gb) mine += ((red[e & 1][0] + red[e & 1][1]) + red[e & 1][2]) + red[e & 1][3];
+                ++e;
+            };
+            int gcur = ghi;
+            while (gcur >= glo && sp[gcur] >= Jhi * ENS_CI) --gcur;  // boundaries at or above the span's end: nothing of this item
+            V4 nxt = *(const V4*)(s + (size_t)(Jhi - 1) * ENS_CI + 4 * tid);
+            for (int J = Jhi - 1; J >= Jlo; --J) {
+                tile[b][tid] = nxt;
+                __syncthreads();
+                if (J > Jlo) nxt = *(const V4*)(s + (size_t)(J - 1) * ENS_CI + 4 * tid);
+                const int jb = J * ENS_CI;
+                int qhi = ENS_TB;
+                for (;;) {
+                    const bool cut = gcur >= glo && sp[gcur] >= jb;
+                    const int qlo = cut ? (sp[gcur] - jb) / ENS_AUC_G : 0;
+#pragma unroll 2
+                    for (int q = qlo; q < qhi; ++q) {
+                        const V4 v = tile[b][q];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                            for (int r = 0; r < ENS_CR; ++r) {
+                                cc[r] += si[r] < v[k];
+                                tt[r] += si[r] == v[k];
+                            }
+                        }
+                    }
+                    if (!cut) break;
+                    emit(gcur, gcur, gcur + 1);
+                    qhi = qlo;
+                    --gcur;
+                }
+                b ^= 1;
+            }
+            // the boundaries below the span, glo .. gcur: the item's total, per set of contributing lanes
+            const int gend = gcur + 1, gsame = max(glo, gmx);
+            for (int g = glo; g < min(gend, gsame); ++g) emit(g, g, g + 1);
+            if (gend > gsame) emit(gsame, gsame, gend);
+        }
+        if (tid < nT) part[((size_t)blockIdx.x * njobs + job) * nT + tid] = mine;
     }
 }

@@ -606,6 +606,46 @@ class predictor(object):
             out["curves"] = res["curves"]
         return out
 
+    def timeDependentAuc(self, X, Y, times=None, n=1, weights=None, likelihood=None, censoringY=None):
+        """The cumulative/dynamic time-dependent AUC of the ensemble under a WeibullLikelihood with inverse-probability-of-censoring
+        weights (Uno et al. 2007; Hung & Chiang 2010) and its integral: at horizon tau, how well the model separates the rows that fail
+        by tau from the rows that survive it.  0.5 is a coin's ranking, 1 a perfect one.  concordance pools all horizons and is biased
+        under heavy censoring; brierScore mixes ranking with calibration.  The mixture's risk at tau is 1 - Sbar(tau | x), which orders
+        the rows differently at different tau; a single network's is its output at every tau.  Y, times (None: brierScore's default
+        grid), censoringY, n, weights: as brierScore's.  The pairs are counted on the device, once for all grid times (the definition
+        is in include/tbnn.h, tbnn_ensemble_auc).  Returns a dict: times [T]; auc float64 [T, d_out], of the mixture; per_network
+        [m', T, d_out]; iauc [d_out], the trapezoid of auc over times divided by tau_T - tau_1, skipping nothing (NaN for T < 2 or
+        where a time has no case or no control); iauc_per_network [m', d_out] with its mean, sd, q05, q50, q95 [d_out] as concordance
+        forms them; case_weight [T, d_out], the sum of the case weights; n_controls int64 [T, d_out]; n_bad, the count of NaN entries
+        of iauc_per_network."""
+        from .likelihood import WeibullLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, WeibullLikelihood):
+            raise ValueError("timeDependentAuc needs a WeibullLikelihood: cases and controls are told apart by times to an event with a "
+                             f"censoring flag, not by the targets of a {type(lik).__name__}")
+        y = np.asarray(Y, dtype=np.float32)
+        if times is None:
+            ev = np.unique(y[y > 0])
+            if ev.size < 2:
+                raise ValueError("timeDependentAuc: the default grid needs at least two distinct event times in Y; pass times")
+            times = np.linspace(*np.quantile(y[y > 0].astype(np.float64), [0.1, 0.9]), 32)
+        ts = np.asarray(times, dtype=np.float64).reshape(-1)
+        picked, w = self._picked(n, weights)
+        self._network_sd(lik, n)                                       # (sets the shape on the forward chain)
+        res = self._ensure_chain().ensemble_auc(picked, ts, Y=y, X=np.asarray(X, dtype=np.float32), weights=w, likelihood=lik.kind,
+                                                censoringY=censoringY)
+
+        def iauc(a):                                                   # [..., T] -> [...]
+            if ts.size < 2:
+                return np.full(a.shape[:-1], np.nan)
+            return np.sum(0.5 * (a[..., 1:] + a[..., :-1]) * np.diff(ts), axis=-1) / (ts[-1] - ts[0])
+        per = iauc(res["per_network"])
+        out = {"times": ts, "auc": res["auc"].T.copy(), "per_network": res["per_network"].transpose(0, 2, 1).copy(), "iauc": iauc(res["auc"]),
+               "iauc_per_network": per, "case_weight": res["case_weight"].T.copy(), "n_controls": res["n_controls"].T.copy(),
+               "n_bad": int(np.isnan(per).sum())}
+        out.update(self._per_network_stats(per, w))
+        return out
+
     # ---- the continuous ranked probability score of the predictive mixture (tbnn_ensemble_crps) ----
     def _crps_likelihood(self, likelihood):
         from .likelihood import (BernoulliLikelihood, CategoricalLikelihood, GammaLikelihood, NegativeBinomialLikelihood,
