@@ -560,6 +560,13 @@ class Chain:
         sdp = None if sd is None else np.ascontiguousarray(np.broadcast_to(_f32(sd).reshape(-1), (m,)))
         return yp, sdp, lik
 
+    def _survival_grid(self, times, censoringY):
+        """(times float64 [T], censoringY [n_g, d_out] or None, and the arguments G_Y, n_g, times, T that tbnn_ensemble_brier and
+        tbnn_ensemble_auc take from them: the arrays stay with the caller for as long as the pointers are read)"""
+        ts = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        gy = None if censoringY is None else _f32(censoringY).reshape(-1, self.d_out)
+        return ts, gy, (_p(gy), 0 if gy is None else gy.shape[0], _pd(ts), ts.size)
+
     def ensemble_moments(self, thetas, X=None, which: int = 1, weights=None, xform: int = XFORM_NONE, scale: float = 1.0,
                          shift: float = 0.0, var: bool = True):
         """posterior-predictive mean and population variance over an ensemble, reduced on the device (tbnn_ensemble_moments):
@@ -724,16 +731,14 @@ class Chain:
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
         yp, _sd, lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, likelihood)
         m = th.shape[0]
-        ts = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
-        gy = None if censoringY is None else _f32(censoringY).reshape(-1, self.d_out)
+        ts, _gy, grid = self._survival_grid(times, censoringY)
         out = {"brier": np.empty((self.d_out, ts.size), dtype=np.float64), "mean_weight": np.empty((self.d_out, ts.size), dtype=np.float64)}
         if per_network:
             out["per_network"] = np.empty((m, self.d_out, ts.size), dtype=np.float64)
         if curves:
             out["curves"] = np.empty((ts.size, self.d_out, n), dtype=np.float64)
-        _check(lib.tbnn_ensemble_brier(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, _p(gy),
-                                       0 if gy is None else gy.shape[0], _pd(ts), ts.size, _pd(out["brier"]), _pd(out.get("per_network")),
-                                       _pd(out.get("curves")), _pd(out["mean_weight"])))
+        _check(lib.tbnn_ensemble_brier(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, *grid, _pd(out["brier"]),
+                                       _pd(out.get("per_network")), _pd(out.get("curves")), _pd(out["mean_weight"])))
         return out
 
     def ensemble_auc(self, thetas, times, Y=None, X=None, which: int = 1, weights=None, likelihood=None, censoringY=None, per_network: bool = True):
@@ -747,15 +752,13 @@ class Chain:
         th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
         yp, _sd, lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, likelihood)
         m = th.shape[0]
-        ts = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
-        gy = None if censoringY is None else _f32(censoringY).reshape(-1, self.d_out)
+        ts, _gy, grid = self._survival_grid(times, censoringY)
         out = {"auc": np.empty((self.d_out, ts.size), dtype=np.float64), "case_weight": np.empty((self.d_out, ts.size), dtype=np.float64),
                "n_controls": np.empty((self.d_out, ts.size), dtype=np.int64)}
         if per_network:
             out["per_network"] = np.empty((m, self.d_out, ts.size), dtype=np.float64)
-        _check(lib.tbnn_ensemble_auc(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, _p(gy),
-                                     0 if gy is None else gy.shape[0], _pd(ts), ts.size, _pd(out["auc"]), _pd(out.get("per_network")),
-                                     _pd(out["case_weight"]), out["n_controls"].ctypes.data_as(C.POINTER(C.c_int64))))
+        _check(lib.tbnn_ensemble_auc(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, *grid, _pd(out["auc"]),
+                                     _pd(out.get("per_network")), _pd(out["case_weight"]), out["n_controls"].ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,

@@ -883,52 +883,125 @@ extern "C" int tbnn_ensemble_count_crps(tbnn_handle h, const float* thetas, int3
         }, extra);
 }
 
-// what tbnn_ensemble_concordance asks of its targets: a time |y| that is finite and not 0, its sign the censoring flag
-static int conc_check_targets(const std::string& who, const float* Y, size_t count) {
-    for (size_t i = 0; i < count; ++i)
-        if (!std::isfinite(Y[i]) || Y[i] == 0.f)
-            return fail(-1, who + ": target " + std::to_string(i) + " is not a finite, nonzero time (its sign is the censoring flag)");
+// ---- what the survival metrics share on the host: tbnn_ensemble_concordance, tbnn_ipcw_weights, tbnn_ensemble_brier, tbnn_ensemble_auc ----
+
+// the shape k of the Weibull survival function an entry point judges under: the descriptor's lik_df on a Weibull handle, what
+// tbnn_set_lik_df set on any other.  Every other likelihood code is refused.
+static int surv_weibull_shape(tbnn_ctx* h, const std::string& who, int likelihood, double* k) {
+    if (likelihood != TBNN_LIK_WEIBULL) {
+        const char* name = ens_lik_name(likelihood);
+        if (!name && !lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
+        return fail(-1, who + ": " + (name ? name : "this likelihood") + " has no survival function with a censoring flag (TBNN_LIK_WEIBULL has)");
+    }
+    const float kf = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
+    if (!df_ok(kf)) return fail(-1, who + ": the survival function under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
+    *k = (double)kf;
+    return 0;
+}
+// the pair kernels' work list grows with the square of the rows
+static int surv_check_rows(const std::string& who, int64_t n) {
+    if (n > ENS_CONC_MAX_N)
+        return fail(-1, who + ": more than " + std::to_string(ENS_CONC_MAX_N) + " rows (the work list grows with the square of the rows)");
+    return 0;
+}
+// Survival targets: a time |y| that is finite and not 0, its sign the censoring flag.  Y [n][d_out], the scored rows' (skipped where
+// null or n < 1: the staged ones are checked once they are on the host), under the row limit of the pair kernels where max_rows;
+// G_Y [n_g][d_out], the rows the censoring distribution is estimated from, or null.
+static int surv_check_targets(const std::string& who, const float* Y, int64_t n, int d_out, const float* G_Y, int64_t n_g, bool max_rows) {
+    auto times = [](const std::string& whose, const float* y, size_t count) -> int {
+        for (size_t i = 0; i < count; ++i)
+            if (!std::isfinite(y[i]) || y[i] == 0.f)
+                return fail(-1, whose + ": target " + std::to_string(i) + " is not a finite, nonzero time (its sign is the censoring flag)");
+        return 0;
+    };
+    if (G_Y && n_g < 1) return fail(-1, who + ": G_Y with n_g < 1");
+    if (Y && n >= 1) {
+        if (max_rows) ENS_TRY(surv_check_rows(who, n));
+        ENS_TRY(times(who, Y, (size_t)n * d_out));
+    }
+    if (G_Y) ENS_TRY(times(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
+    return 0;
+}
+// the grid of tbnn_ipcw_weights, tbnn_ensemble_brier and tbnn_ensemble_auc
+static int surv_check_grid(const std::string& who, const double* times, int32_t T) {
+    if (T < 1 || T > ENS_BRIER_MAX_T) return fail(-1, who + ": T must be 1 .. " + std::to_string(ENS_BRIER_MAX_T));
+    if (!times) return fail(-1, who + ": null times");
+    for (int32_t j = 0; j < T; ++j)
+        if (!std::isfinite(times[j]) || !(times[j] > 0.0) || (j > 0 && !(times[j] > times[j - 1])))
+            return fail(-1, who + ": time " + std::to_string(j) + " is not finite, not > 0 or not above its predecessor");
     return 0;
 }
 
-// The host staging of one output column o of tbnn_ensemble_concordance (definition: include/tbnn.h; layout: k_ens_concordance).  Y: the
-// targets [n][d_out].  perm[n]: the rows stable-sorted by (time ascending, events before censored rows at equal times).  jstart[npad]: in
-// that order the rows comparable to position i are the suffix [jstart_i, n) -- an event's starts behind its run of equal-time events, a
-// censored row's is empty (n), as is every position from n on.  *comparable = sum_i (n - jstart_i).  The work items of the column are
-// appended to `items`: per i-tile the j-tiles from the one that holds the tile's smallest jstart_i < n to the last, cut into spans of at
-// most ENS_CONC_SPAN tiles as equal as they come, each with the first j-tile at or above the tile's largest jstart_i < n (no mask from
-// there on).  Nothing here reads a score.
-static void conc_stage(const float* Y, long n, int d_out, int o, long npad, int* perm, int* jstart, std::vector<int4>& items, int64_t* comparable) {
-    auto time_of = [&](int i) { return std::fabs(Y[(size_t)i * d_out + o]); };
-    auto event = [&](int i) { return Y[(size_t)i * d_out + o] > 0.f; };
-    for (long i = 0; i < n; ++i) perm[i] = (int)i;
-    std::stable_sort(perm, perm + n, [&](int a, int b) {
-        const float ta = time_of(a), tb = time_of(b);
-        return ta != tb ? ta < tb : (event(a) && !event(b));
+// The targets of the n scored rows on both sides, inside a driver's begin: dev as ens_stage_targets yields it, and host -- the caller's
+// Y or, where there is none, the staged ones copied back once: the sort and the censoring distribution are the host's.
+struct SurvTargets {
+    Buf<float> own;
+    std::vector<float> back;
+    const float* dev = nullptr;
+    const float* host = nullptr;
+    int stage(tbnn_ctx* h, int which, const float* Y, long n) {
+        ENS_TRY(ens_stage_targets(h, which, Y, n, own, &dev));
+        host = Y;
+        if (!Y) {
+            back.resize((size_t)n * h->nd.d_out);
+            HIPCHK(hipMemcpyAsync(back.data(), dev, back.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            host = back.data();
+        }
+        return 0;
+    }
+};
+
+// one output column o of the targets Y [n][d_out]
+struct SurvColumn {
+    const float* Y;
+    int d_out, o;
+    float time(int i) const { return std::fabs(Y[(size_t)i * d_out + o]); }
+    bool event(int i) const { return Y[(size_t)i * d_out + o] > 0.f; }
+};
+// order[n]: the column's rows stable-sorted by (time ascending, events before censored rows at equal times), the order both pair kernels walk
+static void surv_order(const SurvColumn& y, long n, int* order) {
+    for (long i = 0; i < n; ++i) order[i] = (int)i;
+    std::stable_sort(order, order + n, [&](int a, int b) {
+        const float ta = y.time(a), tb = y.time(b);
+        return ta != tb ? ta < tb : (y.event(a) && !y.event(b));
     });
+}
+// the work items of row tile t: the tiles from j0 to the last of ntile, cut into spans of at most `span` tiles as equal as they come,
+// each with w as its fourth field
+static void surv_cut_spans(std::vector<int4>& items, int t, int j0, int ntile, int span, int w) {
+    const int len = ntile - j0, parts = (len + span - 1) / span;
+    for (int p = 0; p < parts; ++p)
+        items.push_back(make_int4(t, j0 + (int)((long)len * p / parts), j0 + (int)((long)len * (p + 1) / parts), w));
+}
+
+// The host staging of one output column of tbnn_ensemble_concordance (definition: include/tbnn.h; layout: k_ens_concordance).
+// perm[npad]: the rows in surv_order, -1 from position n on (k_ens_sorted_gather's padding).  jstart[npad]: in that order the rows
+// comparable to position i are the suffix [jstart_i, n) -- an event's starts behind its run of equal-time events, a censored row's is
+// empty (n), as is every position from n on.  *comparable = sum_i (n - jstart_i).  The work items of the column are appended to `items`:
+// per i-tile the j-tiles from the one that holds the tile's smallest jstart_i < n to the last (surv_cut_spans, ENS_CONC_SPAN), each with
+// the first j-tile at or above the tile's largest jstart_i < n (no mask from there on).  Nothing here reads a score.
+static void conc_stage(const SurvColumn& y, long n, long npad, int* perm, int* jstart, std::vector<int4>& items, int64_t* comparable) {
+    surv_order(y, n, perm);
     int64_t comp = 0;
     for (long i = 0; i < n;) {
-        if (!event(perm[i])) { jstart[i++] = (int)n; continue; }
+        if (!y.event(perm[i])) { jstart[i++] = (int)n; continue; }
         long e = i + 1;
-        while (e < n && event(perm[e]) && time_of(perm[e]) == time_of(perm[i])) ++e;
+        while (e < n && y.event(perm[e]) && y.time(perm[e]) == y.time(perm[i])) ++e;
         for (; i < e; ++i) { jstart[i] = (int)e; comp += n - e; }
     }
-    for (long i = n; i < npad; ++i) jstart[i] = (int)n;
+    for (long i = n; i < npad; ++i) { perm[i] = -1; jstart[i] = (int)n; }
     *comparable = comp;
     const int ntile = (int)(npad / ENS_CI);
     for (int t = 0; t < ntile; ++t) {
         long lo = n, hi = -1;
         for (long i = (long)t * ENS_CI; i < std::min<long>(n, (long)(t + 1) * ENS_CI); ++i)
             if (jstart[i] < n) { lo = std::min<long>(lo, jstart[i]); hi = std::max<long>(hi, jstart[i]); }
-        if (hi < 0) continue;
-        const int j0 = (int)(lo / ENS_CI), len = ntile - j0, full = (int)((hi + ENS_CI - 1) / ENS_CI);
-        const int parts = (len + ENS_CONC_SPAN - 1) / ENS_CONC_SPAN;
-        for (int p = 0; p < parts; ++p)
-            items.push_back(make_int4(t, j0 + (int)((long)len * p / parts), j0 + (int)((long)len * (p + 1) / parts), full));
+        if (hi >= 0) surv_cut_spans(items, t, (int)(lo / ENS_CI), ntile, ENS_CONC_SPAN, (int)((hi + ENS_CI - 1) / ENS_CI));
     }
 }
 
-// Harrell's concordance index of a survival ensemble (definition: include/tbnn.h; kernels: k_ens_conc_gather, k_ens_concordance).  A
+// Harrell's concordance index of a survival ensemble (definition: include/tbnn.h; kernels: k_ens_sorted_gather, k_ens_concordance).  A
 // network's index needs all of its rows, so the NETWORKS are cut (ensemble_forward): half of the chunk budget goes to the predictions,
 // the other half to the sorted copy S[chunk][npad] of one output at a time (npad: n rounded up to ENS_CI).  The posterior-mean score is
 // k_ens_moments' / k_ens_moments_finish's mean, launched as tbnn_ensemble_moments launches them, and is counted after the last chunk as
@@ -945,13 +1018,9 @@ extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int
     double W = 0.0;
     ENS_TRY(ens_check_weights(who, net_w, m, &W));
     ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
-    const std::string too_many = who + ": more than " + std::to_string(ENS_CONC_MAX_N) + " rows (the work list grows with the square of the rows)";
-    if (Y && n >= 1) {
-        if (n > ENS_CONC_MAX_N) return fail(-1, too_many);
-        ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
-    }
+    ENS_TRY(surv_check_targets(who, Y, n, d_out, nullptr, 0, true));
     const bool want_mean = mean_counts_out || mean_score_out;
-    std::vector<float> Yh;
+    SurvTargets tg;
     std::vector<int> perm, js, hbad;
     std::vector<int4> items;
     std::vector<size_t> item_off((size_t)d_out + 1, 0);
@@ -976,25 +1045,20 @@ extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int
     ENS_TRY(ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, std::max<size_t>(1, ens_chunk_floats() / 2),
         [&](long r, int chunk) -> int {
             rows = r;
-            if (rows > ENS_CONC_MAX_N) return fail(-1, too_many);
+            ENS_TRY(surv_check_rows(who, rows));
             npad = (rows + ENS_CI - 1) / ENS_CI * ENS_CI;
             tot = rows * d_out;
             const float* Yrows = Y;
             if (!Y) {
-                // the staged targets, copied back once: the staging below is the host's
-                Buf<float> none;
-                const float* dY = nullptr;
-                ENS_TRY(ens_stage_targets(h, which, nullptr, rows, none, &dY));
-                Yh.resize((size_t)tot);
-                HIPCHK(hipMemcpyAsync(Yh.data(), dY, (size_t)tot * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                Yrows = Yh.data();
-                ENS_TRY(conc_check_targets(who, Yrows, (size_t)tot));
+                // (no kernel here reads a target, so the caller's are not uploaded: only the staged ones go through tg)
+                ENS_TRY(tg.stage(h, which, nullptr, rows));
+                Yrows = tg.host;
+                ENS_TRY(surv_check_targets(who, Yrows, rows, d_out, nullptr, 0, false));
             }
-            perm.resize((size_t)tot);
-            js.resize((size_t)d_out * npad);
+            perm.resize((size_t)d_out * npad);
+            js.resize(perm.size());
             for (int o = 0; o < d_out; ++o) {
-                conc_stage(Yrows, rows, d_out, o, npad, perm.data() + (size_t)o * rows, js.data() + (size_t)o * npad, items, &comp[o]);
+                conc_stage(SurvColumn{Yrows, d_out, o}, rows, npad, perm.data() + (size_t)o * npad, js.data() + (size_t)o * npad, items, &comp[o]);
                 item_off[o + 1] = items.size();
             }
             ENS_TRY(ens_upload(h, dPerm, perm.data(), perm.size()));
@@ -1020,8 +1084,8 @@ extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int
                 HIPCHK(hipGetLastError());
             }
             for (int o = 0; o < d_out && net_counts_out; ++o) {
-                hipLaunchKernelGGL(k_ens_conc_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream, dOut + (size_t)o * rows, (size_t)tot, c,
-                                   (const int*)(dPerm + (size_t)o * rows), rows, npad, (float*)dS, dBad + (size_t)i0 * d_out + o, d_out);
+                hipLaunchKernelGGL(k_ens_sorted_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream, dOut + (size_t)o * rows, (size_t)tot, c,
+                                   (const int*)(dPerm + (size_t)o * npad), npad, (float*)dS, dBad + (size_t)i0 * d_out + o, d_out);
                 HIPCHK(hipGetLastError());
                 ENS_TRY(count_pairs((const float*)dS, c, o, (size_t)i0));
             }
@@ -1031,8 +1095,8 @@ extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int
         hipLaunchKernelGGL(k_ens_moments_finish, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, tot, W);
         HIPCHK(hipGetLastError());
         for (int o = 0; o < d_out && mean_counts_out; ++o) {
-            hipLaunchKernelGGL(k_ens_conc_gather<double>, dim3(ens_grid(npad), 1), dim3(ENS_TB), 0, h->stream, (const double*)(acc + (size_t)o * rows), (size_t)0, 1,
-                               (const int*)(dPerm + (size_t)o * rows), rows, npad, (double*)dSm, dBad + (size_t)m * d_out + o, d_out);
+            hipLaunchKernelGGL(k_ens_sorted_gather<double>, dim3(ens_grid(npad), 1), dim3(ENS_TB), 0, h->stream, (const double*)(acc + (size_t)o * rows), (size_t)0, 1,
+                               (const int*)(dPerm + (size_t)o * npad), npad, (double*)dSm, dBad + (size_t)m * d_out + o, d_out);
             HIPCHK(hipGetLastError());
             ENS_TRY(count_pairs((const double*)dSm, 1, o, (size_t)m));
         }
@@ -1052,16 +1116,6 @@ extern "C" int tbnn_ensemble_concordance(tbnn_handle h, const float* thetas, int
     if (net_counts_out) put(net_counts_out, 0, (size_t)m * d_out);
     if (mean_counts_out) put(mean_counts_out, (size_t)m * d_out, (size_t)d_out);
     for (int o = 0; o < d_out && comparable_out; ++o) comparable_out[o] = comp[o];
-    return 0;
-}
-
-// what tbnn_ensemble_brier and tbnn_ipcw_weights ask of the grid
-static int brier_check_times(const std::string& who, const double* times, int32_t T) {
-    if (T < 1 || T > ENS_BRIER_MAX_T) return fail(-1, who + ": T must be 1 .. " + std::to_string(ENS_BRIER_MAX_T));
-    if (!times) return fail(-1, who + ": null times");
-    for (int32_t j = 0; j < T; ++j)
-        if (!std::isfinite(times[j]) || !(times[j] > 0.0) || (j > 0 && !(times[j] > times[j - 1])))
-            return fail(-1, who + ": time " + std::to_string(j) + " is not finite, not > 0 or not above its predecessor");
     return 0;
 }
 
@@ -1095,9 +1149,8 @@ extern "C" int tbnn_ipcw_weights(const float* Y, int64_t n, int32_t d_out, const
                                  double* row_ginv_out, double* time_ginv_out) {
     const std::string who = "ipcw_weights";
     if (!Y || n < 1 || d_out < 1 || (G_Y && n_g < 1)) return fail(-1, who + ": null targets, n < 1, d_out < 1 or G_Y with n_g < 1");
-    ENS_TRY(brier_check_times(who, times, T));
-    ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
-    if (G_Y) ENS_TRY(conc_check_targets(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
+    ENS_TRY(surv_check_grid(who, times, T));
+    ENS_TRY(surv_check_targets(who, Y, n, d_out, G_Y, n_g, false));
     std::vector<double> cs, cum;
     auto ginv = [&](size_t upto) {                               // 1 / the product over the first `upto` censoring times
         const double g = upto ? cum[upto - 1] : 1.0;
@@ -1113,13 +1166,58 @@ extern "C" int tbnn_ipcw_weights(const float* Y, int64_t n, int32_t d_out, const
     return 0;
 }
 
+// The one driver of k_ens_brier, for T consecutive times of a grid: tbnn_ensemble_brier's whole grid, or one group of tbnn_ensemble_auc's
+// (a probability's bits do not depend on its place in the grid).  A block's row sums land in the partial buffer, one slab
+// [d_out][slots][T] per workgroup (slots: the m networks where `nets`, then the mixture and the weights).  The grid: as many workgroups as
+// the block has 64-row tiles, at most ENS_BRIER_MAX_WG, and no more than keep the partial buffer within ENS_BRIER_PART doubles (one
+// workgroup whatever its slab takes).  Where one slab alone exceeds half that bound (nets with m near 4096 at T = 256) the grid collapses to
+// d_out workgroups, each walking all of a block's row tiles: correct, and long-running.
+struct BrierPass {
+    tbnn_ctx* h;
+    int32_t m;
+    bool nets;
+    double k;
+    int32_t T = 0;
+    size_t slab = 0;
+    long wg_max = 1;
+    std::vector<double> cst;       // [omega_i = w_i / W | k log tau_j | tau_j]
+    Buf<double> dCst, dPart;
+
+    // the constants of T times; the slab and the workgroup limit as slab_T >= T times size them (which fixes nwg, so the summation order)
+    void fill(const float* net_w, double W, const double* times, int32_t T_, int32_t slab_T) {
+        T = T_;
+        slab = (size_t)h->nd.d_out * (nets ? m + 2 : 2) * slab_T;
+        wg_max = std::max<long>(1, std::min<long>(ENS_BRIER_MAX_WG, (long)(ENS_BRIER_PART / slab)));
+        cst.resize((size_t)m + 2 * (size_t)T);
+        for (int32_t i = 0; i < m; ++i) cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
+        for (int32_t j = 0; j < T; ++j) {
+            cst[(size_t)m + j] = k * std::log(times[j]);
+            cst[(size_t)m + T + j] = times[j];
+        }
+    }
+    // inside a driver's begin(rb): the constants on the device, the partial buffer of blocks of at most rb rows
+    int stage(long rb) {
+        ENS_TRY(ens_upload(h, dCst, cst.data(), cst.size()));
+        HIPCHK(dPart.alloc(slab * (size_t)std::min<long>(wg_max, (rb + 63) / 64)));
+        return 0;
+    }
+    // the block of r rows of t [m][d_out][r], their targets y, weights rg and the grid's tg [d_out][T]; sv: the mixture's curves
+    // [T][d_out][r] or null; *nwg: the slabs written to dPart
+    int launch(const float* t, long r, const float* y, const double* tg, const double* rg, long rows, double* sv, int* nwg) {
+        *nwg = (int)std::min<long>(wg_max, (r + 63) / 64);
+        const dim3 grid((unsigned)*nwg, (unsigned)h->nd.d_out), tb(ENS_TB);
+        const double* c = dCst;
+        double* part = dPart;
+        if (nets) hipLaunchKernelGGL(k_ens_brier<true>, grid, tb, 0, h->stream, t, (int)m, r, h->nd.d_out, y, c, k, c + m, c + m + T, tg, rg, rows, (int)T, sv, part);
+        else hipLaunchKernelGGL(k_ens_brier<false>, grid, tb, 0, h->stream, t, (int)m, r, h->nd.d_out, y, c, k, c + m, c + m + T, tg, rg, rows, (int)T, sv, part);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+};
+
 // The IPCW Brier score over a time grid (definition: include/tbnn.h; kernels: k_ens_brier, k_ens_brier_finish).  Every row needs all m
-// networks at once for Sbar, so the rows are cut (ensemble_row_blocks).  The host stages omega_i = w_i / W, c_j = k log tau_j and the
-// weights of tbnn_ipcw_weights; a block's row sums land in the partial buffer, one slab per workgroup, and k_ens_brier_finish carries them
-// into acc [d_out][slots][T] in block order (slots: the m networks where bs_net is wanted, then the mixture and the weights); the host
-// divides by n once.  The grid: as many workgroups as the block has 64-row tiles, at most ENS_BRIER_MAX_WG, and no more than keep the
-// partial buffer within ENS_BRIER_PART doubles (one workgroup whatever its slab takes).  Where one slab alone exceeds half that bound (bs_net
-// with m near 4096 at T = 256) the grid collapses to d_out workgroups, each walking all of a block's row tiles: correct, and long-running.
+// networks at once for Sbar, so the rows are cut (ensemble_row_blocks).  The host stages BrierPass's constants and the weights of
+// tbnn_ipcw_weights; k_ens_brier_finish carries a block's slabs into acc [d_out][slots][T] in block order; the host divides by n once.
 extern "C" int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w,
                                    int which, const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times,
                                    int32_t T, double* bs_mean_out, double* bs_net_out, double* surv_out, double* mean_weight_out) {
@@ -1128,76 +1226,44 @@ extern "C" int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m
     const int d_out = h->nd.d_out;
     if (!bs_mean_out && !bs_net_out && !surv_out && !mean_weight_out) return fail(-1, who + ": every output is null");
     if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
-    if (likelihood != TBNN_LIK_WEIBULL) {
-        const char* name = ens_lik_name(likelihood);
-        if (!name && !lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
-        return fail(-1, who + ": " + (name ? name : "this likelihood") + " has no survival function with a censoring flag (TBNN_LIK_WEIBULL has)");
-    }
-    // the shape: the descriptor's lik_df on a Weibull handle, what tbnn_set_lik_df set on any other
-    const float kf = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
-    if (!df_ok(kf)) return fail(-1, who + ": the survival function under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
-    ENS_TRY(brier_check_times(who, times, T));
+    double k = 0.0;
+    ENS_TRY(surv_weibull_shape(h, who, likelihood, &k));
+    ENS_TRY(surv_check_grid(who, times, T));
     if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     if (m > ENS_BRIER_MAX_M) return fail(-1, who + ": m = " + std::to_string(m) + " exceeds " + std::to_string(ENS_BRIER_MAX_M) + " networks");
     ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
     double W = 0.0;
     ENS_TRY(ens_check_weights(who, net_w, m, &W));
     ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
-    if (G_Y && n_g < 1) return fail(-1, who + ": G_Y with n_g < 1");
-    if (Y && n >= 1) ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
-    if (G_Y) ENS_TRY(conc_check_targets(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
-    const double k = (double)kf;
+    ENS_TRY(surv_check_targets(who, Y, n, d_out, G_Y, n_g, false));
     const bool nets = bs_net_out != nullptr;
     const int slots = nets ? m + 2 : 2;
-    const size_t slab = (size_t)d_out * slots * T;
-    const long wg_max = std::max<long>(1, std::min<long>(ENS_BRIER_MAX_WG, (long)(ENS_BRIER_PART / slab)));
-    std::vector<double> cst((size_t)m + 2 * (size_t)T), rgi, tgi((size_t)d_out * T), sums(slab);
-    for (int32_t i = 0; i < m; ++i) cst[i] = (net_w ? (double)net_w[i] : 1.0) / W;
-    for (int32_t j = 0; j < T; ++j) {
-        cst[(size_t)m + j] = k * std::log(times[j]);
-        cst[(size_t)m + T + j] = times[j];
-    }
-    std::vector<float> Yh;
-    const float* dYrows = nullptr;
-    Buf<float> dY;
-    Buf<double> dCst, dRg, dTg, dSurv, dPart, dAcc;
-    long rbk = 0, total = 0;
+    BrierPass pass{h, m, nets, k};
+    pass.fill(net_w, W, times, T, T);
+    const size_t slab = pass.slab;
+    std::vector<double> rgi, tgi((size_t)d_out * T), sums(slab);
+    SurvTargets tg;
+    Buf<double> dRg, dTg, dSurv, dAcc;
+    long total = 0;
     ENS_TRY(ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
         [&](long rb) -> int {
-            rbk = rb;
             total = X ? (long)n : (which ? h->nv : h->n);
-            ENS_TRY(ens_stage_targets(h, which, Y, total, dY, &dYrows));
-            const float* Yrows = Y;
-            if (!Y) {
-                // the staged targets, copied back once: the censoring distribution is the host's
-                Yh.resize((size_t)total * d_out);
-                HIPCHK(hipMemcpyAsync(Yh.data(), dYrows, Yh.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                Yrows = Yh.data();
-            }
+            ENS_TRY(tg.stage(h, which, Y, total));
             rgi.resize((size_t)d_out * total);
-            ENS_TRY(tbnn_ipcw_weights(Yrows, total, d_out, G_Y, n_g, times, T, rgi.data(), tgi.data()));
-            ENS_TRY(ens_upload(h, dCst, cst.data(), cst.size()));
+            ENS_TRY(tbnn_ipcw_weights(tg.host, total, d_out, G_Y, n_g, times, T, rgi.data(), tgi.data()));
             ENS_TRY(ens_upload(h, dRg, rgi.data(), rgi.size()));
             ENS_TRY(ens_upload(h, dTg, tgi.data(), tgi.size()));
             if (surv_out) HIPCHK(dSurv.alloc((size_t)T * d_out * rb));
-            HIPCHK(dPart.alloc(slab * (size_t)std::min<long>(wg_max, (rb + 63) / 64)));
+            ENS_TRY(pass.stage(rb));
             HIPCHK(dAcc.alloc(slab));
             return 0;
         },
         [&](long r0, long r, long rows, const float* t) -> int {
-            const int nwg = (int)std::min<long>(wg_max, (r + 63) / 64);
-            const dim3 grid((unsigned)nwg, (unsigned)d_out), tb(ENS_TB);
-            const float* y = dYrows + (size_t)r0 * d_out;
-            const double* c = dCst;
-            const double* rg = dRg + r0;
-            const double* tg = dTg;
             double* sv = surv_out ? (double*)dSurv : nullptr;
-            double* part = dPart;
-            if (nets) hipLaunchKernelGGL(k_ens_brier<true>, grid, tb, 0, h->stream, t, (int)m, r, d_out, y, c, k, c + m, c + m + T, tg, rg, rows, (int)T, sv, part);
-            else hipLaunchKernelGGL(k_ens_brier<false>, grid, tb, 0, h->stream, t, (int)m, r, d_out, y, c, k, c + m, c + m + T, tg, rg, rows, (int)T, sv, part);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_ens_brier_finish, dim3(ens_grid((long)slab)), tb, 0, h->stream, (const double*)part, nwg, (long)slab, (double*)dAcc, (int)(r0 == 0));
+            int nwg = 0;
+            ENS_TRY(pass.launch(t, r, tg.dev + (size_t)r0 * d_out, dTg, dRg + r0, rows, sv, &nwg));
+            hipLaunchKernelGGL(k_ens_brier_finish, dim3(ens_grid((long)slab)), dim3(ENS_TB), 0, h->stream, (const double*)pass.dPart, nwg, (long)slab,
+                               (double*)dAcc, (int)(r0 == 0));
             HIPCHK(hipGetLastError());
             if (surv_out) ENS_TRY(ens_copy_planes(h, surv_out, r0, rows, sv, r, (size_t)T * d_out));
             return 0;
@@ -1215,32 +1281,25 @@ extern "C" int tbnn_ensemble_brier(tbnn_handle h, const float* thetas, int32_t m
     return 0;
 }
 
-// The host staging of one output column o of tbnn_ensemble_auc (definition: include/tbnn.h; layout: k_ens_auc).  Y: the targets
-// [n][d_out]; rginv: the column's 1 / G(t_r-) in row order.  The rows are stable-sorted by (time ascending, events before censored rows at
-// equal times) and laid out in segments -- segment s < T: tau_{s-1} < t <= tau_s, segment T: t > tau_T -- each padded to ENS_AUC_G
-// positions.  src, pseg, omega [npad], ppos [T]: as k_ens_auc reads them.  W [T]: the sum of the case weights at tau_g, added in sorted
-// order; ncase, ctrl [T]: the counts of cases and of controls.  The work items of the column are appended to `items`: per case tile that
-// holds a case, the control tiles from the one that holds the boundary of the tile's earliest case segment to the last, cut into spans of
-// at most ENS_AUC_SPAN tiles as equal as they come.  Nothing here reads a score.
-static void auc_stage(const float* Y, long n, int d_out, int o, const double* times, int T, const double* rginv, long npad, int* src, int* pseg,
+// The host staging of one output column of tbnn_ensemble_auc (definition: include/tbnn.h; layout: k_ens_auc).  rginv: the column's
+// 1 / G(t_r-) in row order.  The rows in surv_order are laid out in segments -- segment s < T: tau_{s-1} < t <= tau_s, segment T:
+// t > tau_T -- each padded to ENS_AUC_G positions.  src, pseg, omega [npad], ppos [T]: as k_ens_auc reads them.  W [T]: the sum of the
+// case weights at tau_g, added in sorted order; ncase, ctrl [T]: the counts of cases and of controls.  The work items of the column are
+// appended to `items`: per case tile that holds a case, the control tiles from the one that holds the boundary of the tile's earliest
+// case segment to the last (surv_cut_spans, ENS_AUC_SPAN).  Nothing here reads a score.
+static void auc_stage(const SurvColumn& y, long n, const double* times, int T, const double* rginv, long npad, int* src, int* pseg,
                       double* omega, int* ppos, double* W, int64_t* ncase, int64_t* ctrl, std::vector<int4>& items) {
-    auto time_of = [&](int i) { return std::fabs(Y[(size_t)i * d_out + o]); };
-    auto event = [&](int i) { return Y[(size_t)i * d_out + o] > 0.f; };
     std::vector<int> order((size_t)n);
-    for (long i = 0; i < n; ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        const float ta = time_of(a), tb = time_of(b);
-        return ta != tb ? ta < tb : (event(a) && !event(b));
-    });
+    surv_order(y, n, order.data());
     for (long p = 0; p < npad; ++p) { src[p] = -1; pseg[p] = T; omega[p] = 0.0; }
     long p = 0, k = 0;
     double w = 0.0;
     int64_t cases = 0;
     for (int s = 0; s <= T; ++s) {
-        for (; k < n && (s == T || (double)time_of(order[k]) <= times[s]); ++k, ++p) {
+        for (; k < n && (s == T || (double)y.time(order[k]) <= times[s]); ++k, ++p) {
             const int row = order[k];
             src[p] = row;
-            if (s < T && event(row)) { pseg[p] = s; omega[p] = rginv[row]; w += rginv[row]; ++cases; }
+            if (s < T && y.event(row)) { pseg[p] = s; omega[p] = rginv[row]; w += rginv[row]; ++cases; }
         }
         p = (p + ENS_AUC_G - 1) / ENS_AUC_G * ENS_AUC_G;
         if (s < T) { ppos[s] = (int)p; W[s] = w; ncase[s] = cases; ctrl[s] = n - k; }
@@ -1250,18 +1309,15 @@ static void auc_stage(const float* Y, long n, int d_out, int o, const double* ti
         int lo = T, hi = -1;
         for (long i = (long)t * ENS_CI; i < (long)(t + 1) * ENS_CI; ++i)
             if (pseg[i] < T) { lo = std::min(lo, pseg[i]); hi = std::max(hi, pseg[i]); }
-        if (hi < 0) continue;
-        const int j0 = ppos[lo] / ENS_CI, len = ntile - j0, parts = (len + ENS_AUC_SPAN - 1) / ENS_AUC_SPAN;
-        for (int q = 0; q < parts; ++q)
-            items.push_back(make_int4(t, j0 + (int)((long)len * q / parts), j0 + (int)((long)len * (q + 1) / parts), lo | (hi << 16)));
+        if (hi >= 0) surv_cut_spans(items, t, ppos[lo] / ENS_CI, ntile, ENS_AUC_SPAN, lo | (hi << 16));
     }
 }
 
-// The cumulative/dynamic time-dependent AUC with IPCW case weights (definition: include/tbnn.h; kernels: k_ens_auc_gather, k_ens_auc,
+// The cumulative/dynamic time-dependent AUC with IPCW case weights (definition: include/tbnn.h; kernels: k_ens_sorted_gather, k_ens_auc,
 // k_ens_brier, k_ens_brier_finish).  Two passes over the forward kernels.  Per network: a network's AUC needs all of its rows, so the
 // NETWORKS are cut (ensemble_forward), half of the chunk budget for the predictions and half for the sorted copy of one column, as
 // tbnn_ensemble_concordance does.  The mixture: Sbar needs all m networks of a row, so the ROWS are cut (ensemble_row_blocks) and
-// k_ens_brier<false> writes the curves -- tbnn_ensemble_brier's own kernel on the same constants, so the same bits -- for a group of at
+// k_ens_brier<false> writes the curves -- through BrierPass, as tbnn_ensemble_brier does, so the same bits -- for a group of at
 // most ENS_AUC_CURVES / (d_out n) grid times at a time into a device copy in row order; each time of the group is then one fp64 job
 // of k_ens_auc that scores its own boundary alone.  Slabs: [workgroups][jobs of a launch][T] within ENS_AUC_PART doubles whatever n;
 // k_ens_brier_finish adds them in workgroup order.  The host divides by 2 W_g C_g.
@@ -1273,31 +1329,19 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
     const int d_out = h->nd.d_out;
     if (!auc_mix_out && !auc_net_out && !case_weight_out && !controls_out) return fail(-1, who + ": every output is null");
     if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
-    if (likelihood != TBNN_LIK_WEIBULL) {
-        const char* name = ens_lik_name(likelihood);
-        if (!name && !lik_known(likelihood)) return fail(-1, who + ": unknown likelihood");
-        return fail(-1, who + ": " + (name ? name : "this likelihood") + " has no survival function with a censoring flag (TBNN_LIK_WEIBULL has)");
-    }
-    const float kf = h->nd.lik == TBNN_LIK_WEIBULL ? h->nd.lik_df : h->ens_df;
-    if (!df_ok(kf)) return fail(-1, who + ": the survival function under TBNN_LIK_WEIBULL needs the shape: call tbnn_set_lik_df on this handle first");
-    ENS_TRY(brier_check_times(who, times, T));
+    double k = 0.0;
+    ENS_TRY(surv_weibull_shape(h, who, likelihood, &k));
+    ENS_TRY(surv_check_grid(who, times, T));
     if (!thetas || m < 1 || theta_stride < h->nd.P) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
     if (m > ENS_BRIER_MAX_M) return fail(-1, who + ": m = " + std::to_string(m) + " exceeds " + std::to_string(ENS_BRIER_MAX_M) + " networks");
     ENS_TRY(ens_block_rows(who, 0, (size_t)m * (size_t)d_out, nullptr));
     double Wnet = 0.0;
     ENS_TRY(ens_check_weights(who, net_w, m, &Wnet));
     ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
-    if (G_Y && n_g < 1) return fail(-1, who + ": G_Y with n_g < 1");
-    const std::string too_many = who + ": more than " + std::to_string(ENS_CONC_MAX_N) + " rows (the work list grows with the square of the rows)";
-    if (Y && n >= 1) {
-        if (n > ENS_CONC_MAX_N) return fail(-1, too_many);
-        ENS_TRY(conc_check_targets(who, Y, (size_t)n * d_out));
-    }
-    if (G_Y) ENS_TRY(conc_check_targets(who + " (G_Y)", G_Y, (size_t)n_g * d_out));
+    ENS_TRY(surv_check_targets(who, Y, n, d_out, G_Y, n_g, true));
     if (!X && which != 0 && which != 1) return fail(-1, "which must be 0 (training rows) or 1 (validation rows)");
-    const double k = (double)kf;
     const size_t dT = (size_t)d_out * T;
-    std::vector<float> Yh;
+    SurvTargets tg;
     std::vector<double> rgi, tgi(dT), omega, Wc(dT), num_net, num_mix(dT, 0.0);
     std::vector<int> src, pseg, ppos(dT), hbad;
     std::vector<int64_t> ncase(dT), ctrl(dT);
@@ -1305,33 +1349,24 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
     std::vector<size_t> item_off((size_t)d_out + 1, 0);
     Buf<int> dSrc, dPseg, dPpos, dBad;
     Buf<int4> dItems;
-    Buf<float> dS, dYown;
+    Buf<float> dS;
     Buf<double> dOmega, dRg, dPart, dNum, dNumMix;
-    const float* dYrows = nullptr;
     long rows = 0, npad = 0;
     const size_t bad_slots = (size_t)m * d_out + dT;               // the networks' [m][d_out], then the mixture's [d_out][T]
     // once, by whichever pass comes first (the rows are staged by then): the targets, the weights, the layout and the work list
     auto prepare = [&](long total) -> int {
         if (rows) return 0;
-        if (total > ENS_CONC_MAX_N) return fail(-1, too_many);
-        ENS_TRY(ens_stage_targets(h, which, Y, total, dYown, &dYrows));
-        const float* Yrows = Y;
-        if (!Y) {
-            // the staged targets, copied back once: the censoring distribution and the sort are the host's
-            Yh.resize((size_t)total * d_out);
-            HIPCHK(hipMemcpyAsync(Yh.data(), dYrows, Yh.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            Yrows = Yh.data();
-        }
+        ENS_TRY(surv_check_rows(who, total));
+        ENS_TRY(tg.stage(h, which, Y, total));
         rgi.resize((size_t)d_out * total);
-        ENS_TRY(tbnn_ipcw_weights(Yrows, total, d_out, G_Y, n_g, times, T, rgi.data(), tgi.data()));
+        ENS_TRY(tbnn_ipcw_weights(tg.host, total, d_out, G_Y, n_g, times, T, rgi.data(), tgi.data()));
         npad = (total + (long)ENS_AUC_G * (T + 1) + ENS_CI - 1) / ENS_CI * ENS_CI;
         src.resize((size_t)d_out * npad);
         pseg.resize(src.size());
         omega.resize(src.size());
         for (int o = 0; o < d_out; ++o) {
             const size_t a = (size_t)o * npad, b = (size_t)o * T;
-            auc_stage(Yrows, total, d_out, o, times, T, rgi.data() + (size_t)o * total, npad, src.data() + a, pseg.data() + a, omega.data() + a,
+            auc_stage(SurvColumn{tg.host, d_out, o}, total, times, T, rgi.data() + (size_t)o * total, npad, src.data() + a, pseg.data() + a, omega.data() + a,
                       ppos.data() + b, Wc.data() + b, ncase.data() + b, ctrl.data() + b, items);
             item_off[o + 1] = items.size();
         }
@@ -1378,7 +1413,7 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
             },
             [&](int i0, int c, const float* dOut, long) -> int {
                 for (int o = 0; o < d_out; ++o) {
-                    hipLaunchKernelGGL(k_ens_auc_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream,
+                    hipLaunchKernelGGL(k_ens_sorted_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream,
                                        dOut + (size_t)o * rows, (size_t)rows * d_out, c, (const int*)(dSrc + (size_t)o * npad), npad, (float*)dS,
                                        dBad + (size_t)i0 * d_out + o, d_out);
                     HIPCHK(hipGetLastError());
@@ -1392,13 +1427,11 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     if (auc_mix_out) {
-        std::vector<double> cst((size_t)m + 2 * (size_t)T), tgg, got;
-        for (int32_t i = 0; i < m; ++i) cst[i] = (net_w ? (double)net_w[i] : 1.0) / Wnet;
-        Buf<double> dCst, dTg, dSurv, dBpart, dCurves, dSorted;
+        std::vector<double> tgg, got;
+        BrierPass pass{h, m, false, k};
+        Buf<double> dTg, dSurv, dCurves, dSorted;
         for (int g0 = 0, Tg = T; g0 < T; g0 += Tg) {
-            // a group of grid times: k_ens_brier on its own T' = Tg times (a probability's bits do not depend on its place in the grid)
-            const size_t slab = (size_t)d_out * 2 * T;
-            const long wg_max = std::max<long>(1, std::min<long>(ENS_BRIER_MAX_WG, (long)(ENS_BRIER_PART / slab)));
+            // a group of grid times: k_ens_brier on its own Tg times, its slabs (which nobody reads) sized as the whole grid's
             ENS_TRY(ensemble_row_blocks(h, who, thetas, m, theta_stride, TBNN_XFORM_NONE, 1.f, 0.f, which, X, n,
                 [&](long rb) -> int {
                     ENS_TRY(prepare(X ? (long)n : (which ? h->nv : h->n)));
@@ -1410,26 +1443,18 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
                         HIPCHK(dNumMix.alloc((size_t)Tg * T));
                     }
                     Tg = std::min(Tg, T - g0);
-                    for (int32_t j = 0; j < Tg; ++j) {
-                        cst[(size_t)m + j] = k * std::log(times[g0 + j]);
-                        cst[(size_t)m + Tg + j] = times[g0 + j];
-                    }
+                    pass.fill(net_w, Wnet, times + g0, Tg, T);
                     tgg.resize((size_t)d_out * Tg);
                     for (int o = 0; o < d_out; ++o)
                         for (int32_t j = 0; j < Tg; ++j) tgg[(size_t)o * Tg + j] = tgi[(size_t)o * T + g0 + j];
-                    ENS_TRY(ens_upload(h, dCst, cst.data(), (size_t)m + 2 * (size_t)Tg));
+                    ENS_TRY(pass.stage(rb));
                     ENS_TRY(ens_upload(h, dTg, tgg.data(), tgg.size()));
                     HIPCHK(dSurv.alloc((size_t)Tg * d_out * rb));
-                    HIPCHK(dBpart.alloc(slab * (size_t)std::min<long>(wg_max, (rb + 63) / 64)));
                     return 0;
                 },
                 [&](long r0, long r, long, const float* t) -> int {
-                    const int nwg = (int)std::min<long>(wg_max, (r + 63) / 64);
-                    const double* c = dCst;
-                    hipLaunchKernelGGL(k_ens_brier<false>, dim3((unsigned)nwg, (unsigned)d_out), dim3(ENS_TB), 0, h->stream, t, (int)m, r, d_out,
-                                       dYrows + (size_t)r0 * d_out, c, k, c + m, c + m + Tg, (const double*)dTg, (const double*)(dRg + r0), rows, Tg,
-                                       (double*)dSurv, (double*)dBpart);
-                    HIPCHK(hipGetLastError());
+                    int nwg = 0;
+                    ENS_TRY(pass.launch(t, r, tg.dev + (size_t)r0 * d_out, dTg, dRg + r0, rows, dSurv, &nwg));
                     HIPCHK(hipMemcpy2DAsync(dCurves + r0, (size_t)rows * sizeof(double), dSurv, (size_t)r * sizeof(double), (size_t)r * sizeof(double),
                                             (size_t)Tg * d_out, hipMemcpyDeviceToDevice, h->stream));
                     return 0;
@@ -1437,7 +1462,7 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
             got.resize((size_t)Tg * T);
             for (int o = 0; o < d_out; ++o) {
                 // job j of the column: the curve at tau_{g0 + j}, [Tg][d_out][rows] in dCurves
-                hipLaunchKernelGGL(k_ens_auc_gather<double>, dim3(ens_grid(npad), (unsigned)Tg), dim3(ENS_TB), 0, h->stream,
+                hipLaunchKernelGGL(k_ens_sorted_gather<double>, dim3(ens_grid(npad), (unsigned)Tg), dim3(ENS_TB), 0, h->stream,
                                    (const double*)(dCurves + (size_t)o * rows), (size_t)rows * d_out, Tg, (const int*)(dSrc + (size_t)o * npad), npad,
                                    (double*)dSorted, dBad + (size_t)m * d_out + (size_t)o * T + g0, 1);
                 HIPCHK(hipGetLastError());

@@ -46,7 +46,7 @@
 //             per element; each steps its networks' pmf recurrences over a tile of k in registers, the per-k mixtures meet in LDS
 //             (windows, tiles, gaps and summation order: at the kernel).  All fp64, contraction off, no atomics.
 //   concordance a chunk [c][d_out][n] like the moments' (a network's concordance index needs all of its rows, so the NETWORKS are cut):
-//             k_ens_conc_gather copies one output's scores into the order the host sorted the rows in, k_ens_concordance counts the
+//             k_ens_sorted_gather copies one output's scores into the order the host sorted the rows in, k_ens_concordance counts the
 //             concordant and tied pairs among the comparable ones (definition: include/tbnn.h, tbnn_ensemble_concordance): row tiles in
 //             registers against score tiles from LDS, compares only, 64-bit integer atomics (layout and work list: at the kernel).
 //   brier       the block [m][d_out][rb] of all m networks, untransformed: k_ens_brier forms the Weibull survival probabilities of every
@@ -55,7 +55,7 @@
 //             over the wave, one partial per (workgroup, network, column, time), k_ens_brier_finish in workgroup order.  fp64, contraction
 //             off, no atomics.
 //   auc         both: per network a chunk [c][d_out][n] like the concordance index's, for the mixture k_ens_brier's curves of a block of rows.
-//             k_ens_auc_gather copies one output's scores into the host's padded, time-sorted layout; k_ens_auc compares every (case,
+//             k_ens_sorted_gather copies one output's scores into the host's padded, time-sorted layout; k_ens_auc compares every (case,
 //             control) pair once for all grid times and adds the IPCW-weighted running counts at each grid boundary its descending walk
 //             crosses (definition: include/tbnn.h, tbnn_ensemble_auc; layout, work list and summation order: at the kernel); the slabs go
 //             through k_ens_brier_finish.  Integer counts, fp64 sums in a fixed order, contraction off, no atomics.
@@ -1690,21 +1690,24 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_count_crps(const float* __restri
 // comparable to sorted position i are a SUFFIX [jstart_i, n) -- an event's starts behind its run of equal-time events, a censored row's is
 // empty (jstart_i = n) -- so the times are not looked at again: the kernels compare scores only, and no floating-point arithmetic happens here.
 //
-// k_ens_conc_gather: S[net][i] = out[net][perm[i]] for i < n (writes coalesced, reads gathered), NaN for n <= i < npad = n rounded up to
-// ENS_CI: a NaN is neither below nor equal to anything, so the padding needs no mask.  bad[net * bad_stride] = 1 where the network holds a
-// NaN among its n scores: every writer stores the same value, a plain store.  T = float: the c networks of a chunk, `stride` values apart
-// in out; T = double: the one posterior-mean score (c = 1).
+// k_ens_sorted_gather, the gather of both pair kernels (this one and k_ens_auc): src[npad] is the row a position of the host's sorted
+// layout holds, -1 for padding (here: perm, then -1 from position n to npad = n rounded up to ENS_CI; the AUC's segments: at k_ens_auc).
+// S[job][i] = in[job * stride + src[i]] (writes coalesced, reads gathered), NaN where src[i] < 0: a NaN is neither below nor equal to
+// anything, so the padding needs no mask.  bad[job * bad_stride] = 1 where a job holds a NaN among its rows: every writer stores the same
+// value, a plain store.  T = float: the c networks of a chunk, `stride` values apart in `in`; T = double: the one posterior-mean score
+// (c = 1), or the mixture's survival curve at one grid time per job.
 template <class T>
-__global__ __launch_bounds__(ENS_TB) void k_ens_conc_gather(const T* __restrict__ out, size_t stride, int c, const int* __restrict__ perm, long n,
-                                                             long npad, T* __restrict__ S, int* __restrict__ bad, int bad_stride) {
-    for (int net = blockIdx.y; net < c; net += gridDim.y) {
+__global__ __launch_bounds__(ENS_TB) void k_ens_sorted_gather(const T* __restrict__ in, size_t stride, int c, const int* __restrict__ src, long npad,
+                                                               T* __restrict__ S, int* __restrict__ bad, int bad_stride) {
+    for (int job = blockIdx.y; job < c; job += gridDim.y) {
         for (long i = (long)blockIdx.x * ENS_TB + threadIdx.x; i < npad; i += (long)gridDim.x * ENS_TB) {
+            const int k = src[i];
             T v = (T)NAN;
-            if (i < n) {
-                v = out[(size_t)net * stride + perm[i]];
-                if (v != v) bad[(size_t)net * bad_stride] = 1;
+            if (k >= 0) {
+                v = in[(size_t)job * stride + k];
+                if (v != v) bad[(size_t)job * bad_stride] = 1;
             }
-            S[(size_t)net * npad + i] = v;
+            S[(size_t)job * npad + i] = v;
         }
     }
 }
@@ -1966,26 +1969,8 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_brier_finish(const double* __res
 // The host sorts the rows of one output by time and lays them out in SEGMENTS: segment s < T holds the rows with tau_{s-1} < t <= tau_s,
 // segment T those with t > tau_T, each padded to a multiple of ENS_AUC_G positions, the whole to a multiple of ENS_CI (npad).  src[npad]
 // is the row a position holds, -1 for padding.  The controls at tau_g are then the suffix [ppos_g, npad), ppos_g the start of segment
-// g + 1, and the cases at tau_g the events of the segments up to g: the device never reads a time.
-//
-// k_ens_auc_gather: S[job][i] = in[job * stride + src[i]], NaN where src[i] < 0 -- a NaN is neither below nor equal to anything, so the
-// padding needs no mask.  bad[job * bad_stride] = 1 where a job holds a NaN among its rows (every writer stores the same value).
-// T = float: the networks of a chunk; T = double: the mixture's curve at one grid time per job.
-template <class T>
-__global__ __launch_bounds__(ENS_TB) void k_ens_auc_gather(const T* __restrict__ in, size_t stride, int c, const int* __restrict__ src, long npad,
-                                                            T* __restrict__ S, int* __restrict__ bad, int bad_stride) {
-    for (int job = blockIdx.y; job < c; job += gridDim.y) {
-        for (long i = (long)blockIdx.x * ENS_TB + threadIdx.x; i < npad; i += (long)gridDim.x * ENS_TB) {
-            const int k = src[i];
-            T v = (T)NAN;
-            if (k >= 0) {
-                v = in[(size_t)job * stride + k];
-                if (v != v) bad[(size_t)job * bad_stride] = 1;
-            }
-            S[(size_t)job * npad + i] = v;
-        }
-    }
-}
+// g + 1, and the cases at tau_g the events of the segments up to g: the device never reads a time.  k_ens_sorted_gather (above) copies
+// the scores into that layout.
 
 // S[njobs][npad]: the sorted scores of the launch's jobs (a network's outputs, fp32; or the mixture's survival probabilities at ONE grid
 // time, fp64: larger means a later event in both, so a pair (case i, control j) is concordant iff s_i < s_j).  pseg[npad]: the segment of

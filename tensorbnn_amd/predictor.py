@@ -489,15 +489,43 @@ class predictor(object):
                                            likelihood=lik.kind, sd=self._network_sd(lik, n), weights=w)
         return (Fb, F) if isinstance(lik, (PoissonLikelihood, NegativeBinomialLikelihood)) else F
 
+    # ---- survival data under a WeibullLikelihood: curves, concordance, Brier score, time-dependent AUC ----
+    def _weibull_likelihood(self, likelihood, method, why):
+        """the likelihood a survival method judges under (None: the predictor's own); any but a WeibullLikelihood is refused with the
+        method's own sentence `why`"""
+        from .likelihood import WeibullLikelihood
+        lik = self.likelihood if likelihood is None else likelihood
+        if not isinstance(lik, WeibullLikelihood):
+            raise ValueError(f"{method} needs a WeibullLikelihood: {why.format(lik=type(lik).__name__)}")
+        return lik
+
+    @staticmethod
+    def _default_grid(y, method):
+        """32 equally spaced times from the 10 % to the 90 % quantile of the observed event times of y, pooled over the columns"""
+        ev = y[y > 0]
+        if np.unique(ev).size < 2:
+            raise ValueError(f"{method}: the default grid needs at least two distinct event times in Y; pass times")
+        return np.linspace(*np.quantile(ev.astype(np.float64), [0.1, 0.9]), 32)
+
+    @staticmethod
+    def _trapezoid(v, ts):
+        """[..., T] -> [...]: the trapezoid of v over the times ts divided by tau_T - tau_1 (NaN for T < 2)"""
+        if ts.size < 2:
+            return np.full(v.shape[:-1], np.nan)
+        return np.sum(0.5 * (v[..., 1:] + v[..., :-1]) * np.diff(ts), axis=-1) / (ts[-1] - ts[0])
+
+    @staticmethod
+    def _event_counts(y, d_out):
+        """n_events, n_censored int64 [d_out] of the signed targets y"""
+        y = y.reshape(-1, d_out)
+        return {"n_events": (y > 0).sum(axis=0).astype(np.int64), "n_censored": (y < 0).sum(axis=0).astype(np.int64)}
+
     def survival(self, X, times, n=1, weights=None, likelihood=None):
         """The posterior-mean survival curve of every row of X under a WeibullLikelihood: S(t) = 1 - F(t), the probability that the event
         has not happened by time t, float64 [len(times), d_out, rows].  times: finite and > 0.  n, weights, likelihood: as
         predictiveCDF's.  (A host loop of predictiveCDF over the times, one device reduction per time; brierScore(curves=True) returns
         the same curves from one pass on the device.)"""
-        from .likelihood import WeibullLikelihood
-        lik = self.likelihood if likelihood is None else likelihood
-        if not isinstance(lik, WeibullLikelihood):
-            raise ValueError("survival needs a WeibullLikelihood: the survival curve is that of a time to an event")
+        lik = self._weibull_likelihood(likelihood, "survival", "the survival curve is that of a time to an event")
         ts = np.asarray(times, dtype=np.float64).reshape(-1)
         if ts.size < 1 or not (np.all(np.isfinite(ts)) and np.all(ts > 0)):
             raise ValueError("survival: times must be finite and > 0, at least one")
@@ -520,11 +548,8 @@ class predictor(object):
         picked network -- the posterior distribution of C; mean, sd, q05, q50, q95 [d_out] of per_network over the networks whose C is
         not NaN (weighted where weights is given: weighted mean and variance, quantiles of the weighted inverted CDF); n_bad, the count
         of NaN entries of per_network (a NaN score, or no comparable pair); comparable, n_events, n_censored int64 [d_out]."""
-        from .likelihood import WeibullLikelihood
-        lik = self.likelihood if likelihood is None else likelihood
-        if not isinstance(lik, WeibullLikelihood):
-            raise ValueError("concordance needs a WeibullLikelihood: the pairs are ordered by times to an event with a censoring flag, not "
-                             f"by the targets of a {type(lik).__name__}")
+        self._weibull_likelihood(likelihood, "concordance",
+                                 "the pairs are ordered by times to an event with a censoring flag, not by the targets of a {lik}")
         picked, w = self._picked(n, weights)
         y = np.asarray(Y, dtype=np.float32)
         res = self._ensure_chain().ensemble_concordance(picked, Y=y, X=np.asarray(X, dtype=np.float32), weights=w)
@@ -534,10 +559,8 @@ class predictor(object):
             with np.errstate(divide="ignore", invalid="ignore"):
                 return np.where((conc >= 0) & (comp > 0), (conc + 0.5 * tied) / comp, np.nan)
         per = ratio(res["concordant"], res["tied"])
-        d_out = per.shape[1]
         out = {"c_index": ratio(res["mean_concordant"], res["mean_tied"]), "per_network": per, "n_bad": int(np.isnan(per).sum()),
-               "comparable": res["comparable"], "n_events": (y.reshape(-1, d_out) > 0).sum(axis=0).astype(np.int64),
-               "n_censored": (y.reshape(-1, d_out) < 0).sum(axis=0).astype(np.int64)}
+               "comparable": res["comparable"], **self._event_counts(y, per.shape[1])}
         out.update(self._per_network_stats(per, w))
         return out
 
@@ -574,33 +597,18 @@ class predictor(object):
         mean, sd, q05, q50, q95 [d_out] as concordance forms them; mean_weight [T, d_out], the mean weight (1 when the censoring
         distribution comes from Y itself); n_events, n_censored int64 [d_out]; n_bad, the count of NaN entries of ibs_per_network; and,
         with curves=True, curves [T, d_out, rows], the mixture's survival probabilities on the grid."""
-        from .likelihood import WeibullLikelihood
-        lik = self.likelihood if likelihood is None else likelihood
-        if not isinstance(lik, WeibullLikelihood):
-            raise ValueError("brierScore needs a WeibullLikelihood: the score is that of survival curves against times to an event with a "
-                             f"censoring flag, not the targets of a {type(lik).__name__}")
+        lik = self._weibull_likelihood(likelihood, "brierScore", "the score is that of survival curves against times to an event with a "
+                                       "censoring flag, not the targets of a {lik}")
         y = np.asarray(Y, dtype=np.float32)
-        if times is None:
-            ev = np.unique(y[y > 0])
-            if ev.size < 2:
-                raise ValueError("brierScore: the default grid needs at least two distinct event times in Y; pass times")
-            times = np.linspace(*np.quantile(y[y > 0].astype(np.float64), [0.1, 0.9]), 32)
-        ts = np.asarray(times, dtype=np.float64).reshape(-1)
+        ts = np.asarray(self._default_grid(y, "brierScore") if times is None else times, dtype=np.float64).reshape(-1)
         picked, w = self._picked(n, weights)
         self._network_sd(lik, n)                                       # (sets the shape on the forward chain)
         res = self._ensure_chain().ensemble_brier(picked, ts, Y=y, X=np.asarray(X, dtype=np.float32), weights=w, likelihood=lik.kind,
                                                   censoringY=censoringY, curves=curves)
-        d_out = res["brier"].shape[0]
-
-        def ibs(b):                                                    # [..., T] -> [...]
-            if ts.size < 2:
-                return np.full(b.shape[:-1], np.nan)
-            return np.sum(0.5 * (b[..., 1:] + b[..., :-1]) * np.diff(ts), axis=-1) / (ts[-1] - ts[0])
-        per = ibs(res["per_network"])
-        out = {"times": ts, "brier": res["brier"].T.copy(), "per_network": res["per_network"].transpose(0, 2, 1).copy(), "ibs": ibs(res["brier"]),
-               "ibs_per_network": per, "mean_weight": res["mean_weight"].T.copy(), "n_bad": int(np.isnan(per).sum()),
-               "n_events": (y.reshape(-1, d_out) > 0).sum(axis=0).astype(np.int64),
-               "n_censored": (y.reshape(-1, d_out) < 0).sum(axis=0).astype(np.int64)}
+        per = self._trapezoid(res["per_network"], ts)
+        out = {"times": ts, "brier": res["brier"].T.copy(), "per_network": res["per_network"].transpose(0, 2, 1).copy(),
+               "ibs": self._trapezoid(res["brier"], ts), "ibs_per_network": per, "mean_weight": res["mean_weight"].T.copy(),
+               "n_bad": int(np.isnan(per).sum()), **self._event_counts(y, res["brier"].shape[0])}
         out.update(self._per_network_stats(per, w))
         if curves:
             out["curves"] = res["curves"]
@@ -618,31 +626,18 @@ class predictor(object):
         where a time has no case or no control); iauc_per_network [m', d_out] with its mean, sd, q05, q50, q95 [d_out] as concordance
         forms them; case_weight [T, d_out], the sum of the case weights; n_controls int64 [T, d_out]; n_bad, the count of NaN entries
         of iauc_per_network."""
-        from .likelihood import WeibullLikelihood
-        lik = self.likelihood if likelihood is None else likelihood
-        if not isinstance(lik, WeibullLikelihood):
-            raise ValueError("timeDependentAuc needs a WeibullLikelihood: cases and controls are told apart by times to an event with a "
-                             f"censoring flag, not by the targets of a {type(lik).__name__}")
+        lik = self._weibull_likelihood(likelihood, "timeDependentAuc", "cases and controls are told apart by times to an event with a "
+                                       "censoring flag, not by the targets of a {lik}")
         y = np.asarray(Y, dtype=np.float32)
-        if times is None:
-            ev = np.unique(y[y > 0])
-            if ev.size < 2:
-                raise ValueError("timeDependentAuc: the default grid needs at least two distinct event times in Y; pass times")
-            times = np.linspace(*np.quantile(y[y > 0].astype(np.float64), [0.1, 0.9]), 32)
-        ts = np.asarray(times, dtype=np.float64).reshape(-1)
+        ts = np.asarray(self._default_grid(y, "timeDependentAuc") if times is None else times, dtype=np.float64).reshape(-1)
         picked, w = self._picked(n, weights)
         self._network_sd(lik, n)                                       # (sets the shape on the forward chain)
         res = self._ensure_chain().ensemble_auc(picked, ts, Y=y, X=np.asarray(X, dtype=np.float32), weights=w, likelihood=lik.kind,
                                                 censoringY=censoringY)
-
-        def iauc(a):                                                   # [..., T] -> [...]
-            if ts.size < 2:
-                return np.full(a.shape[:-1], np.nan)
-            return np.sum(0.5 * (a[..., 1:] + a[..., :-1]) * np.diff(ts), axis=-1) / (ts[-1] - ts[0])
-        per = iauc(res["per_network"])
-        out = {"times": ts, "auc": res["auc"].T.copy(), "per_network": res["per_network"].transpose(0, 2, 1).copy(), "iauc": iauc(res["auc"]),
-               "iauc_per_network": per, "case_weight": res["case_weight"].T.copy(), "n_controls": res["n_controls"].T.copy(),
-               "n_bad": int(np.isnan(per).sum())}
+        per = self._trapezoid(res["per_network"], ts)
+        out = {"times": ts, "auc": res["auc"].T.copy(), "per_network": res["per_network"].transpose(0, 2, 1).copy(),
+               "iauc": self._trapezoid(res["auc"], ts), "iauc_per_network": per, "case_weight": res["case_weight"].T.copy(),
+               "n_controls": res["n_controls"].T.copy(), "n_bad": int(np.isnan(per).sum())}
         out.update(self._per_network_stats(per, w))
         return out
 

@@ -71,6 +71,17 @@ def test_against_reference(native, n, m, d_out, kind, weighted):
     ch.close()
 
 
+def test_staged_rows_and_targets(native):
+    """X = None, Y = None: the rows and the targets staged with set_validation, the targets copied back to the host for its sort; one row
+    past a tile edge with two columns, so the padded perm and its per-column offsets too"""
+    ch, thetas, X, Y, _w = problem(native, T + 1, 2, 2)
+    ch.set_validation(X, Y)
+    res = ch.ensemble_concordance(thetas)
+    assert res["concordant"].shape == (2, 2) and res["mean_score"].shape == (2, T + 1)
+    check(ch, thetas, X, Y, None, res)
+    ch.close()
+
+
 def test_constant_score_and_nan(native):
     """a network whose weights are 0 ties every comparable pair (C = 1/2); a NaN bias gives that network -1 and leaves the others their counts"""
     ch, thetas, X, Y, _w = problem(native, T + 1, 5, 1)
