@@ -676,6 +676,43 @@ int tbnn_ipcw_weights(const float* Y, int64_t n, int32_t d_out, const float* G_Y
 int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, int likelihood, const float* net_w, int which,
                       const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times, int32_t T,
                       double* auc_mix_out, double* auc_net_out, double* case_weight_out, int64_t* controls_out);
+/* Uno's concordance index with inverse-probability-of-censoring weights (Uno, Cai, Pencina, D'Agostino, Wei 2011) of a survival ensemble
+ * on a grid of truncation times: Harrell's pairs, each weighted by 1 / G(t_i-)^2, so that the limit of the estimate does not depend on the
+ * censoring distribution and a training set and a test set censored differently can be compared.  Counted on the device, per network and
+ * for the posterior-mean score.  Arguments up to `n` are tbnn_ensemble_concordance's (no likelihood: the scores are the raw outputs),
+ * G_Y .. T are tbnn_ensemble_brier's.  Per output column o, each its own survival problem:
+ *   targets         t_i = |y_i|, e_i = (y_i > 0), as everywhere else
+ *   grid            `times`, under the rules of tbnn_ensemble_brier: finite, > 0, strictly ascending, 1 <= T <= 256
+ *   case at tau_g   row i iff e_i = 1 and t_i < tau_g.  STRICT, as Uno et al. have it: tbnn_ensemble_auc's case is t_i <= tau_g
+ *   comparable      the ordered pair (i, j) under exactly the rule of tbnn_ensemble_concordance: t_i < t_j, or t_i == t_j and e_j = 0;
+ *                   in the sorted order of that entry point the partners of position i are again the suffix [jstart_i, n)
+ *   weight          omega_i = r_i * r_i, r_i = 1 / G(t_i-): the row_ginv_out of tbnn_ipcw_weights, from the scored rows or from G_Y,
+ *                   squared by one fp64 multiply on the host.  A needed weight whose G is 0 is NaN, and so is every value it enters
+ *   N_g             the sum over the cases i at tau_g of omega_i (2 #{j in the suffix: s_i < s_j} + #{j in the suffix: s_i == s_j})
+ *   D_g             the sum over the same cases of omega_i (n - jstart_i), formed on the host in fp64 in sorted order
+ *   C(tau_g)        N_g / (2 D_g); NaN where D_g is 0 or NaN
+ *   scores          as tbnn_ensemble_concordance's: per network the raw fp32 outputs compared as fp32; the posterior-mean score sbar in
+ *                   fp64 from the moments kernels, compared in fp64.  The network weights enter sbar alone
+ * NaN: a network with a NaN score in a column reports NaN at every time for that column; a NaN in sbar does the same to the mean's row.
+ * With no censored row (G == 1, omega == 1) and tau above every time, C is Harrell's (concordant + tied / 2) / comparable exactly: all
+ * sums are then integers below 2^53.
+ * Staging and work.  The host staging is tbnn_ensemble_concordance's sort and suffixes; it also gives every case its SEGMENT, the first
+ * g with t_i < tau_g, so that the cases at tau_g are the segments up to g.  k_ens_conc_ipcw walks Harrell's tiles -- 1024 sorted rows in
+ * registers, the partner tiles through LDS, work items of at most 8 partner tiles -- with one 32-bit counter per ROW that holds
+ * 2 (s_i < s_j) + (s_i == s_j): at most 2 x 1024 x 8 = 2^14 per item, so it cannot wrap and widens to fp64 exactly.  Rows that are no
+ * case at tau_T take no part and tiles past tau_T are not visited.  At the end of an item omega_i x count_i is formed (one rounding per
+ * row) and summed per segment in a fixed order: a lane's four rows, the wave, the four waves; a workgroup walks its items in list order
+ * into its own slab of T doubles per network, a finish kernel adds the slabs in workgroup order, and the host adds the segments up in
+ * ascending g, once, and divides.  At most 1024 workgroups per network and 2^22 doubles of slabs per launch whatever n.  The work list
+ * depends on n, the sort and the grid alone.  No atomics: the same bits from run to run and whatever the network chunks.  The networks
+ * are cut into chunks as for tbnn_ensemble_concordance.  n is at most 2^22 rows.
+ * c_mean_out: host [d_out][T], of sbar; c_net_out: host [m][d_out][T]; pair_weight_out: host [d_out][T], D_g; cases_out: host
+ * [d_out][T], the cases at tau_g; each may be NULL, not all four.
+ * Refused, with nothing written: what tbnn_ensemble_concordance refuses, T outside 1 .. 256, a time that is not finite, not > 0 or not
+ * above its predecessor, G_Y with n_g < 1, a target that is 0 or not finite in Y or G_Y. */
+int tbnn_ensemble_concordance_ipcw(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int which,
+                                   const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times, int32_t T,
+                                   double* c_mean_out, double* c_net_out, double* pair_weight_out, int64_t* cases_out);
 /* Out-of-sample model comparison: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman, Gabry 2017; Vehtari,
  * Simpson, Gelman, Yao, Gabry 2024) and WAIC, from the m x n matrix of per-network, per-row log-likelihoods, which is formed and reduced on the
  * device.  The algorithm is the R package loo's, continuous in its inputs (not ArviZ's variant, which drops fit weights below 10 eps).

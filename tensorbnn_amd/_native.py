@@ -134,6 +134,8 @@ SYMBOLS = [
     ("tbnn_ipcw_weights", C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int64, _dp, C.c_int32, _dp, _dp]),
     ("tbnn_ensemble_auc", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, _fp, C.c_int64, _dp, C.c_int32,
                                     _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    ("tbnn_ensemble_concordance_ipcw", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, _fp, _fp, C.c_int64, _fp, C.c_int64, _dp, C.c_int32,
+                                                 _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     ("tbnn_ensemble_loo", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int64, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     ("tbnn_set_lik_df", C.c_int, [_H, C.c_float]),
     ("tbnn_metrics", C.c_int, [_H, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _dp]),
@@ -759,6 +761,28 @@ class Chain:
             out["per_network"] = np.empty((m, self.d_out, ts.size), dtype=np.float64)
         _check(lib.tbnn_ensemble_auc(self._h, _p(th), m, th.shape[1], lik, _p(w), int(which), _p(xp), _p(yp), n, *grid, _pd(out["auc"]),
                                      _pd(out.get("per_network")), _pd(out["case_weight"]), out["n_controls"].ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def ensemble_concordance_ipcw(self, thetas, times, Y=None, X=None, which: int = 1, weights=None, censoringY=None, per_network: bool = True):
+        """Uno's concordance index with inverse-probability-of-censoring weights of a survival ensemble at the truncation times `times`
+        (the rules of ensemble_brier), its pairs counted on the device once for all times (tbnn_ensemble_concordance_ipcw; the
+        definition is in include/tbnn.h): Harrell's comparable pairs (ensemble_concordance), restricted at tau to the events BEFORE tau
+        and weighted by 1 / G(t-)^2, so that the value does not depend on how the rows are censored.  Scores: the raw outputs.  A dict:
+        c_index float64 [d_out, T], of the posterior-mean score; per_network [m, d_out, T] (per_network=True); pair_weight float64
+        [d_out, T], the weighted count of comparable pairs D; n_cases int64 [d_out, T].  NaN where D is 0 or NaN, or a NaN score.
+        censoringY: the targets the censoring distribution is estimated from (None: the scored rows'); weights: one per network or None
+        (equal), read by the mean score alone; Y None with X None: the staged targets"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        yp, _sd, _lik = self._ensemble_targets(th.shape[0], xp, n, Y, None, None)
+        m = th.shape[0]
+        ts, _gy, grid = self._survival_grid(times, censoringY)
+        out = {"c_index": np.empty((self.d_out, ts.size), dtype=np.float64), "pair_weight": np.empty((self.d_out, ts.size), dtype=np.float64),
+               "n_cases": np.empty((self.d_out, ts.size), dtype=np.int64)}
+        if per_network:
+            out["per_network"] = np.empty((m, self.d_out, ts.size), dtype=np.float64)
+        _check(lib.tbnn_ensemble_concordance_ipcw(self._h, _p(th), m, th.shape[1], _p(w), int(which), _p(xp), _p(yp), n, *grid, _pd(out["c_index"]),
+                                                  _pd(out.get("per_network")), _pd(out["pair_weight"]),
+                                                  out["n_cases"].ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
     def ensemble_loo(self, thetas, Y=None, X=None, which: int = 1, likelihood=None, sd=None, r_eff: float = 1.0, pointwise: bool = False,

@@ -975,13 +975,11 @@ static void surv_cut_spans(std::vector<int4>& items, int t, int j0, int ntile, i
         items.push_back(make_int4(t, j0 + (int)((long)len * p / parts), j0 + (int)((long)len * (p + 1) / parts), w));
 }
 
-// The host staging of one output column of tbnn_ensemble_concordance (definition: include/tbnn.h; layout: k_ens_concordance).
-// perm[npad]: the rows in surv_order, -1 from position n on (k_ens_sorted_gather's padding).  jstart[npad]: in that order the rows
-// comparable to position i are the suffix [jstart_i, n) -- an event's starts behind its run of equal-time events, a censored row's is
-// empty (n), as is every position from n on.  *comparable = sum_i (n - jstart_i).  The work items of the column are appended to `items`:
-// per i-tile the j-tiles from the one that holds the tile's smallest jstart_i < n to the last (surv_cut_spans, ENS_CONC_SPAN), each with
-// the first j-tile at or above the tile's largest jstart_i < n (no mask from there on).  Nothing here reads a score.
-static void conc_stage(const SurvColumn& y, long n, long npad, int* perm, int* jstart, std::vector<int4>& items, int64_t* comparable) {
+// The sorted order and the comparable suffixes of one output column, for both concordance kernels.  perm[npad]: the rows in surv_order,
+// -1 from position n on (k_ens_sorted_gather's padding).  jstart[npad]: in that order the rows comparable to position i are the suffix
+// [jstart_i, n) -- an event's starts behind its run of equal-time events, a censored row's is empty (n), as is every position from n on.
+// Returns sum_i (n - jstart_i).
+static int64_t surv_suffixes(const SurvColumn& y, long n, long npad, int* perm, int* jstart) {
     surv_order(y, n, perm);
     int64_t comp = 0;
     for (long i = 0; i < n;) {
@@ -991,7 +989,15 @@ static void conc_stage(const SurvColumn& y, long n, long npad, int* perm, int* j
         for (; i < e; ++i) { jstart[i] = (int)e; comp += n - e; }
     }
     for (long i = n; i < npad; ++i) { perm[i] = -1; jstart[i] = (int)n; }
-    *comparable = comp;
+    return comp;
+}
+
+// The host staging of one output column of tbnn_ensemble_concordance (definition: include/tbnn.h; layout: k_ens_concordance).
+// perm, jstart [npad]: surv_suffixes'; *comparable = sum_i (n - jstart_i).  The work items of the column are appended to `items`:
+// per i-tile the j-tiles from the one that holds the tile's smallest jstart_i < n to the last (surv_cut_spans, ENS_CONC_SPAN), each with
+// the first j-tile at or above the tile's largest jstart_i < n (no mask from there on).  Nothing here reads a score.
+static void conc_stage(const SurvColumn& y, long n, long npad, int* perm, int* jstart, std::vector<int4>& items, int64_t* comparable) {
+    *comparable = surv_suffixes(y, n, npad, perm, jstart);
     const int ntile = (int)(npad / ENS_CI);
     for (int t = 0; t < ntile; ++t) {
         long lo = n, hi = -1;
@@ -1497,6 +1503,194 @@ extern "C" int tbnn_ensemble_auc(tbnn_handle h, const float* thetas, int32_t m, 
             if (case_weight_out) case_weight_out[e] = Wc[e];
             if (controls_out) controls_out[e] = ctrl[e];
         }
+    return 0;
+}
+
+// The host staging of one output column of tbnn_ensemble_concordance_ipcw (definition: include/tbnn.h; layout: k_ens_conc_ipcw).
+// rginv: the column's 1 / G(t_r-) in row order.  perm, jstart [npad]: surv_suffixes'.  The cases at tau_g are a prefix of that order:
+// the events with t < tau_g.  seg[npad]: the first g with t_i < tau_g where position i holds a case that has a partner (jstart_i < n),
+// T for every other; omega[npad]: r_i * r_i there, 0 elsewhere.  D[T] = the sum over the cases at tau_g of omega_i (n - jstart_i), added
+// in sorted order (a case without a partner enters as omega_i * 0: NaN where its weight is); cases[T]: their count.  The work items of
+// the column are appended to `items`: per i-tile that holds a case with a partner, Harrell's j-tiles over those cases alone
+// (surv_cut_spans, ENS_CONC_SPAN), each with the first unmasked j-tile and the tile's range of segments packed as k_ens_conc_ipcw
+// reads them.  Nothing here reads a score.
+static void conc_ipcw_stage(const SurvColumn& y, long n, long npad, const double* times, int T, const double* rginv, int* perm, int* jstart,
+                            int* seg, double* omega, double* D, int64_t* cases, std::vector<int4>& items) {
+    surv_suffixes(y, n, npad, perm, jstart);
+    for (long i = 0; i < npad; ++i) { seg[i] = T; omega[i] = 0.0; }
+    int g = 0;
+    double d = 0.0;
+    int64_t count = 0;
+    for (long i = 0; i < n && g < T; ++i) {
+        const int row = perm[i];
+        while (g < T && !((double)y.time(row) < times[g])) { D[g] = d; cases[g] = count; ++g; }
+        if (g == T || !y.event(row)) continue;
+        const double om = rginv[row] * rginv[row];
+        d += om * (double)(n - jstart[i]);
+        ++count;
+        if (jstart[i] < n) { seg[i] = g; omega[i] = om; }
+    }
+    for (; g < T; ++g) { D[g] = d; cases[g] = count; }
+    const int ntile = (int)(npad / ENS_CI);
+    for (int t = 0; t < ntile; ++t) {
+        long lo = n, hi = -1;
+        int slo = T, shi = -1;
+        for (long i = (long)t * ENS_CI; i < (long)(t + 1) * ENS_CI; ++i)
+            if (seg[i] < T) {
+                lo = std::min<long>(lo, jstart[i]); hi = std::max<long>(hi, jstart[i]);
+                slo = std::min(slo, seg[i]); shi = std::max(shi, seg[i]);
+            }
+        if (hi >= 0) surv_cut_spans(items, t, (int)(lo / ENS_CI), ntile, ENS_CONC_SPAN, (int)((hi + ENS_CI - 1) / ENS_CI) | (slo << 16) | (int)((unsigned)shi << 24));
+    }
+}
+
+// Uno's IPCW concordance index on a grid of truncation times (definition: include/tbnn.h; kernels: k_ens_sorted_gather,
+// k_ens_conc_ipcw, k_ens_brier_finish).  The driver is tbnn_ensemble_concordance's: the NETWORKS are cut (ensemble_forward), half of
+// the chunk budget for the predictions and half for the sorted copy of one column; the posterior-mean score is k_ens_moments' mean,
+// counted after the last chunk as one fp64 job (slot m of the flags and of num).  Slabs: [workgroups][jobs of a launch][T] within
+// ENS_AUC_PART doubles whatever n, as tbnn_ensemble_auc's; k_ens_brier_finish adds them in workgroup order into num [d_out][m + 1][T],
+// per SEGMENT; the host adds the segments up in ascending g and divides by 2 D_g.
+extern "C" int tbnn_ensemble_concordance_ipcw(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int which,
+                                              const float* X, const float* Y, int64_t n, const float* G_Y, int64_t n_g, const double* times,
+                                              int32_t T, double* c_mean_out, double* c_net_out, double* pair_weight_out, int64_t* cases_out) {
+    NEED(h);
+    const std::string who = "ensemble_concordance_ipcw";
+    const int d_out = h->nd.d_out;
+    if (!c_mean_out && !c_net_out && !pair_weight_out && !cases_out) return fail(-1, who + ": every output is null");
+    if (X && !Y) return fail(-1, who + ": rows X without their targets Y");
+    ENS_TRY(surv_check_grid(who, times, T));
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    ENS_TRY(ens_check_targets(h, who, which, X, Y, n));
+    ENS_TRY(surv_check_targets(who, Y, n, d_out, G_Y, n_g, true));
+    const size_t dT = (size_t)d_out * T, slots = ((size_t)m + 1) * d_out;
+    SurvTargets tg;
+    std::vector<int> perm, js, seg, hbad(slots);
+    std::vector<double> rgi, omega, D(dT), num(slots * T, 0.0);
+    std::vector<int64_t> ncase(dT);
+    std::vector<int4> items;
+    std::vector<size_t> item_off((size_t)d_out + 1, 0);
+    Buf<int> dPerm, dJs, dSeg, dBad;
+    Buf<int4> dItems;
+    Buf<float> dS, dW;
+    Buf<double> dOmega, acc, dSm, dPart, dNum;
+    long rows = 0, npad = 0, tot = 0;
+    // column o of the sorted scores S[jobs][npad]: the pair kernel over the column's work items, a bounded number of jobs per launch, and
+    // the slabs' sum into slot `slot` on of num
+    auto count_pairs = [&](auto* S, int jobs, int o, size_t slot) -> int {
+        using V = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
+        const size_t ni = item_off[o + 1] - item_off[o];
+        if (!ni) return 0;                                          // (no case with a partner: num is not read)
+        const int nwg = (int)std::min<size_t>(ni, ENS_AUC_MAX_WG), per = (int)std::max<size_t>(1, (size_t)ENS_AUC_PART / ((size_t)nwg * T));
+        for (int j0 = 0; j0 < jobs; j0 += per) {
+            const int cj = std::min(per, jobs - j0);
+            hipLaunchKernelGGL(k_ens_conc_ipcw<V>, dim3((unsigned)nwg, (unsigned)std::min(cj, 65535)), dim3(ENS_TB), 0, h->stream, S + (size_t)j0 * npad, cj,
+                               npad, (const int*)(dJs + (size_t)o * npad), (const int*)(dSeg + (size_t)o * npad), (const double*)(dOmega + (size_t)o * npad),
+                               (int)T, (const int4*)(dItems + item_off[o]), (int)ni, (double*)dPart);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_ens_brier_finish, dim3(ens_grid((long)cj * T)), dim3(ENS_TB), 0, h->stream, (const double*)dPart, nwg, (long)cj * T,
+                               dNum + ((size_t)o * (m + 1) + slot + j0) * T, 1);
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
+    };
+    const bool pairs = c_mean_out || c_net_out;
+    ENS_TRY(ensemble_forward(h, who, thetas, m, theta_stride, which, X, n, std::max<size_t>(1, ens_chunk_floats() / 2),
+        [&](long r, int chunk) -> int {
+            rows = r;
+            ENS_TRY(surv_check_rows(who, rows));
+            npad = (rows + ENS_CI - 1) / ENS_CI * ENS_CI;
+            tot = rows * d_out;
+            const float* Yrows = Y;
+            if (!Y) {
+                // (no kernel here reads a target, so the caller's are not uploaded: only the staged ones go through tg)
+                ENS_TRY(tg.stage(h, which, nullptr, rows));
+                Yrows = tg.host;
+                ENS_TRY(surv_check_targets(who, Yrows, rows, d_out, nullptr, 0, false));
+            }
+            rgi.resize((size_t)d_out * rows);
+            ENS_TRY(tbnn_ipcw_weights(Yrows, rows, d_out, G_Y, n_g, times, T, rgi.data(), nullptr));
+            perm.resize((size_t)d_out * npad);
+            js.resize(perm.size());
+            seg.resize(perm.size());
+            omega.resize(perm.size());
+            for (int o = 0; o < d_out; ++o) {
+                const size_t a = (size_t)o * npad, b = (size_t)o * T;
+                conc_ipcw_stage(SurvColumn{Yrows, d_out, o}, rows, npad, times, T, rgi.data() + (size_t)o * rows, perm.data() + a, js.data() + a,
+                                seg.data() + a, omega.data() + a, D.data() + b, ncase.data() + b, items);
+                item_off[o + 1] = items.size();
+            }
+            if (!pairs) return 0;
+            ENS_TRY(ens_upload(h, dPerm, perm.data(), perm.size()));
+            ENS_TRY(ens_upload(h, dJs, js.data(), js.size()));
+            ENS_TRY(ens_upload(h, dSeg, seg.data(), seg.size()));
+            ENS_TRY(ens_upload(h, dOmega, omega.data(), omega.size()));
+            if (!items.empty()) ENS_TRY(ens_upload(h, dItems, items.data(), items.size()));
+            HIPCHK(dBad.alloc(slots));
+            HIPCHK(hipMemsetAsync(dBad, 0, slots * sizeof(int), h->stream));
+            HIPCHK(dNum.alloc(slots * T));
+            size_t most = 0;
+            for (int o = 0; o < d_out; ++o) most = std::max(most, item_off[o + 1] - item_off[o]);
+            HIPCHK(dPart.alloc(std::max<size_t>((size_t)T, std::min<size_t>(ENS_AUC_PART, std::min<size_t>(most, ENS_AUC_MAX_WG) * T * (size_t)chunk))));
+            if (c_net_out) HIPCHK(dS.alloc((size_t)chunk * npad));
+            if (c_mean_out) {
+                HIPCHK(acc.alloc(3 * (size_t)tot));
+                HIPCHK(dSm.alloc((size_t)npad));
+                if (net_w) ENS_TRY(ens_upload(h, dW, net_w, (size_t)m));
+            }
+            return 0;
+        },
+        [&](int i0, int c, const float* dOut, long) -> int {
+            if (c_mean_out) {
+                hipLaunchKernelGGL(k_ens_moments, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, dOut, c, tot, (int)TBNN_XFORM_NONE, 1.f, 0.f,
+                                   net_w ? (const float*)(dW + i0) : nullptr, (int)(i0 == 0), (double*)acc);
+                HIPCHK(hipGetLastError());
+            }
+            for (int o = 0; o < d_out && c_net_out; ++o) {
+                hipLaunchKernelGGL(k_ens_sorted_gather<float>, dim3(ens_grid(npad), (unsigned)std::min(c, 65535)), dim3(ENS_TB), 0, h->stream, dOut + (size_t)o * rows,
+                                   (size_t)tot, c, (const int*)(dPerm + (size_t)o * npad), npad, (float*)dS, dBad + (size_t)i0 * d_out + o, d_out);
+                HIPCHK(hipGetLastError());
+                ENS_TRY(count_pairs((const float*)dS, c, o, (size_t)i0));
+            }
+            return 0;
+        }));
+    if (c_mean_out) {
+        hipLaunchKernelGGL(k_ens_moments_finish, dim3(ens_grid(tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, tot, W);
+        HIPCHK(hipGetLastError());
+        for (int o = 0; o < d_out; ++o) {
+            hipLaunchKernelGGL(k_ens_sorted_gather<double>, dim3(ens_grid(npad), 1), dim3(ENS_TB), 0, h->stream, (const double*)(acc + (size_t)o * rows), (size_t)0, 1,
+                               (const int*)(dPerm + (size_t)o * npad), npad, (double*)dSm, dBad + (size_t)m * d_out + o, d_out);
+            HIPCHK(hipGetLastError());
+            ENS_TRY(count_pairs((const double*)dSm, 1, o, (size_t)m));
+        }
+    }
+    if (pairs) {
+        HIPCHK(hipMemcpyAsync(hbad.data(), dBad, slots * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        for (int o = 0; o < d_out; ++o) {
+            if (item_off[o + 1] == item_off[o]) continue;
+            const size_t a = (size_t)o * (m + 1) * T, first = c_net_out ? 0 : (size_t)m * T, last = ((size_t)m + (c_mean_out ? 1 : 0)) * T;
+            HIPCHK(hipMemcpyAsync(num.data() + a + first, dNum + a + first, (last - first) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    // C(tau_g) = N_g / (2 D_g), N_g the segments' sums added up in ascending g; NaN where D_g is 0 or NaN, or the job holds a NaN score
+    auto put = [&](double* dst, int o, size_t slot) {
+        double s = 0.0;
+        for (int32_t g = 0; g < T; ++g) {
+            s += num[((size_t)o * (m + 1) + slot) * T + g];
+            const double d = D[(size_t)o * T + g];
+            dst[g] = d > 0.0 && !hbad[slot * d_out + o] ? s / (2.0 * d) : (double)NAN;
+        }
+    };
+    for (int o = 0; o < d_out; ++o) {
+        for (int32_t i = 0; i < m && c_net_out; ++i) put(c_net_out + ((size_t)i * d_out + o) * T, o, (size_t)i);
+        if (c_mean_out) put(c_mean_out + (size_t)o * T, o, (size_t)m);
+        for (int32_t g = 0; g < T; ++g) {
+            if (pair_weight_out) pair_weight_out[(size_t)o * T + g] = D[(size_t)o * T + g];
+            if (cases_out) cases_out[(size_t)o * T + g] = ncase[(size_t)o * T + g];
+        }
+    }
     return 0;
 }
 

@@ -2086,3 +2086,114 @@ __global__ __launch_bounds__(ENS_TB) void k_ens_auc(const T* __restrict__ S, int
         if (tid < nT) part[((size_t)blockIdx.x * njobs + job) * nT + tid] = mine;
     }
 }
+
+// ---- Uno's IPCW concordance index of a survival ensemble on a grid of truncation times (tbnn_ensemble_concordance_ipcw) ----
+// Harrell's layout with the weight on the ROW.  S[njobs][npad]: the scores in surv_order (k_ens_sorted_gather: NaN from position n on);
+// jstart[npad]: the suffix starts of k_ens_concordance; seg[npad]: of a position that holds a case with a partner (an event with
+// t_i < tau_T and jstart_i < n) the first g with t_i < tau_g, nT for every other; omega[npad]: the case's weight 1 / G(t_i-)^2, NaN where
+// G is 0 (0 where seg is nT).  items: the host's work list, (i-tile, first j-tile, one past the last, w), w = the first j-tile that
+// needs no mask | the smallest segment among the tile's cases << 16 | the largest << 24 (tiles < 2^16, segments < 2^8).  part: one slab
+// [nT] per (workgroup, job), [gridDim.x][njobs][nT]: the sums omega_i (2 concordant + tied) over the cases of SEGMENT g -- not yet of
+// time g: the host adds the segments up -- of the items the workgroup walked.
+//
+// The walk is k_ens_concordance's: ENS_CI sorted rows in registers, ENS_CR per lane, the j-tiles through double-buffered LDS with one
+// barrier per tile and 16-byte broadcast reads, the unmasked loop from tile w on and the compare j >= jstart_i below it.  A row that is
+// no case at tau_T takes s_i = NaN and drops out of every compare; i-tiles without a case are not in the list (the cases are a prefix
+// of the order, so those are all tiles at or past tau_T).
+// Counters.  Where Harrell's lane keeps two totals, a lane here keeps ONE 32-bit counter PER ROW, since the weight belongs to the row:
+// it holds 2 (s_i < s_j) + (s_i == s_j), added as (s_i <= s_j) + (s_i < s_j) -- two compares and two adds per pair, Harrell's count, on
+// ENS_CR registers instead of two.  An item covers at most ENS_CONC_SPAN j-tiles, so a counter ends at most at
+// 2 ENS_CI ENS_CONC_SPAN = 2^14: it cannot wrap, and its conversion to fp64 is exact.
+// Weighted sums, no atomics.  At the item's end a lane forms omega_i * (double)count_i, one rounding per row.  For each segment g of the
+// tile's range the rows of that segment -- the others enter as +0.0, by a select -- are summed in a FIXED order: a lane's four rows in r
+// order, the wave by an xor butterfly, the four waves in wave order through LDS (two alternating slots, one barrier per segment);
+// thread g adds the sum to the register it keeps for segment g.  Workgroup x walks items x, x + gridDim.x, ... in list order and stores
+// its registers into its slab with plain stores; k_ens_brier_finish adds the slabs in workgroup order.  gridDim.x is
+// min(items, ENS_AUC_MAX_WG) whatever the chunk and the list depends on n, the sort and the grid alone, so a job's bits depend on nothing
+// else.  Every read stays inside npad.
+template <class T>
+__global__ __launch_bounds__(ENS_TB) void k_ens_conc_ipcw(const T* __restrict__ S, int njobs, long npad, const int* __restrict__ jstart,
+                                                           const int* __restrict__ seg, const double* __restrict__ omega, int nT,
+                                                           const int4* __restrict__ items, int nitems, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    typedef T V4 __attribute__((ext_vector_type(4)));
+    static_assert(ENS_CI == 4 * ENS_TB, "a thread stages four scores of a j-tile");
+    static_assert(ENS_BRIER_MAX_T <= ENS_TB && ENS_BRIER_MAX_T <= 256, "thread g keeps the sum of segment g; a segment packs into 8 bits");
+    __shared__ V4 tile[2][ENS_TB];
+    __shared__ double red[2][ENS_TB / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int b = 0, e = 0;
+    for (int job = blockIdx.y; job < njobs; job += gridDim.y) {
+        const T* __restrict__ s = S + (size_t)job * npad;
+        double mine = 0.0;                                          // thread g: segment g's sum over this workgroup's items
+        for (int ii = blockIdx.x; ii < nitems; ii += gridDim.x) {
+            const int4 it = items[ii];
+            const int jfree = it.w & 0xffff, glo = (it.w >> 16) & 0xff, ghi = (int)((unsigned)it.w >> 24);
+            const long i0 = (long)it.x * ENS_CI;
+            T si[ENS_CR];
+            int js[ENS_CR], sg[ENS_CR];
+            unsigned cnt[ENS_CR];
+#pragma unroll
+            for (int r = 0; r < ENS_CR; ++r) {
+                const long i = i0 + tid + ENS_TB * r;
+                const T v = s[i];
+                js[r] = jstart[i];
+                sg[r] = seg[i];
+                si[r] = sg[r] < nT ? v : (T)NAN;
+                cnt[r] = 0;
+            }
+            V4 nxt = *(const V4*)(s + (size_t)it.y * ENS_CI + 4 * tid);
+            for (int J = it.y; J < it.z; ++J) {
+                tile[b][tid] = nxt;
+                __syncthreads();
+                if (J + 1 < it.z) nxt = *(const V4*)(s + (size_t)(J + 1) * ENS_CI + 4 * tid);
+                if (J >= jfree) {
+#pragma unroll 2
+                    for (int q = 0; q < ENS_TB; ++q) {
+                        const V4 v = tile[b][q];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                            for (int r = 0; r < ENS_CR; ++r) {
+                                cnt[r] += si[r] <= v[k];
+                                cnt[r] += si[r] < v[k];
+                            }
+                        }
+                    }
+                } else {
+                    const int jb = J * ENS_CI;
+#pragma unroll 2
+                    for (int q = 0; q < ENS_TB; ++q) {
+                        const V4 v = tile[b][q];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int j = jb + 4 * q + k;
+#pragma unroll
+                            for (int r = 0; r < ENS_CR; ++r) {
+                                const bool on = j >= js[r];
+                                cnt[r] += on & (si[r] <= v[k]);
+                                cnt[r] += on & (si[r] < v[k]);
+                            }
+                        }
+                    }
+                }
+                b ^= 1;
+            }
+            double wc[ENS_CR];
+#pragma unroll
+            for (int r = 0; r < ENS_CR; ++r) wc[r] = omega[i0 + tid + ENS_TB * r] * (double)cnt[r];
+            for (int g = glo; g <= ghi; ++g) {
+                double v = 0.0;
+#pragma unroll
+                for (int r = 0; r < ENS_CR; ++r) v += sg[r] == g ? wc[r] : 0.0;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (lane == 0) red[e & 1][wave] = v;
+                __syncthreads();
+                if (tid == g) mine += ((red[e & 1][0] + red[e & 1][1]) + red[e & 1][2]) + red[e & 1][3];
+                ++e;
+            }
+        }
+        if (tid < nT) part[((size_t)blockIdx.x * njobs + job) * nT + tid] = mine;
+    }
+}

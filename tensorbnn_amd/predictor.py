@@ -564,6 +564,28 @@ class predictor(object):
         out.update(self._per_network_stats(per, w))
         return out
 
+    def concordanceIpcw(self, X, Y, times=None, n=1, weights=None, likelihood=None, censoringY=None):
+        """Uno's concordance index of the ensemble under a WeibullLikelihood (Uno et al. 2011) at the truncation times `times`:
+        concordance's pairs, restricted at tau to the events before tau and weighted by the inverse probability of censoring,
+        1 / G(t-)^2.  Harrell's C (concordance) is biased under heavy censoring -- its limit depends on the censoring distribution --
+        so its posterior distribution on a training set and on a test set censored differently cannot be compared; this one's can.  Y,
+        times (None: brierScore's default grid), censoringY, n, weights: as brierScore's.  The pairs are counted on the device, once
+        for all times (the definition is in include/tbnn.h, tbnn_ensemble_concordance_ipcw).  Returns a dict: times [T]; c_index float64
+        [d_out, T], of the posterior-mean score; per_network [m', d_out, T] -- the posterior distribution of C at every time -- with
+        its mean, sd, q05, q50, q95 [d_out, T] as concordance forms them; pair_weight [d_out, T], the weighted count of comparable
+        pairs; n_cases int64 [d_out, T], the events before tau; n_bad, the count of NaN entries of per_network."""
+        self._weibull_likelihood(likelihood, "concordanceIpcw",
+                                 "the pairs are ordered by times to an event with a censoring flag, not by the targets of a {lik}")
+        y = np.asarray(Y, dtype=np.float32)
+        ts = np.asarray(self._default_grid(y, "concordanceIpcw") if times is None else times, dtype=np.float64).reshape(-1)
+        picked, w = self._picked(n, weights)
+        res = self._ensure_chain().ensemble_concordance_ipcw(picked, ts, Y=y, X=np.asarray(X, dtype=np.float32), weights=w, censoringY=censoringY)
+        per = res["per_network"]
+        out = {"times": ts, **res, "n_bad": int(np.isnan(per).sum())}
+        stats = self._per_network_stats(per.reshape(per.shape[0], -1), w)
+        out.update({k: v.reshape(per.shape[1:]) for k, v in stats.items()})
+        return out
+
     @staticmethod
     def _per_network_stats(per, w):
         """mean, sd, q05, q50, q95 [d_out] of a per-network score per [m', d_out] over the networks whose score is not NaN (weighted where

@@ -11,7 +11,8 @@ THE QUADRATIC HOST FIGURE IS EXTRAPOLATED: the boolean [n, n] matrices are run o
 time scaled by (n / HOST_ROWS)^2 m / HOST_NETS, plus the measured forward_many: not a measurement at the full size.  The Fenwick route is
 measured at the full row count on HOST_NETS networks and scaled by m / HOST_NETS (linear in the networks).
 Prints one JSON line per shape with the library's build id, the pairs per call, and whether the device's counts equal both host routes'
-on what those ran.  Needs a gfx950 device; there is no fallback."""
+on what those ran.  --ipcw: instead of all that, Uno's IPCW C beside Harrell's at the flagship shapes (ipcw_leg).
+Needs a gfx950 device; there is no fallback."""
 import json
 import os
 import statistics
@@ -81,9 +82,45 @@ def fenwick_counts(y, s):
     return comparable, conc, tied
 
 
+def ipcw_leg():
+    """--ipcw: Uno's IPCW C (Chain.ensemble_concordance_ipcw: tbnn_ensemble_concordance_ipcw, the pair kernel k_ens_conc_ipcw) beside
+    Harrell's at the flagship shapes, T = 1 (the 90 % quantile of the times) and T = 32 (10 % .. 90 %): whole calls, the two entry
+    points alternating inside every repetition, one warm-up round, then the median of five.  One JSON line per (rows, T)."""
+    name, dims = "flagship", SHAPES[0][1]
+    for n in (10_000, 100_000):
+        rng = np.random.default_rng(0)
+        X = rng.standard_normal((n, dims[0])).astype(np.float32)
+        base = np.concatenate([(rng.standard_normal(o * i + o) * (2.0 / i) ** 0.5) for i, o in zip(dims[:-1], dims[1:])])
+        thetas = (base[None, :] + 0.1 * rng.standard_normal((M, base.size))).astype(np.float32)
+        layers = [(dims[i], dims[i + 1], nat.ACT_RELU if i < len(dims) - 2 else nat.ACT_NONE, 0) for i in range(len(dims) - 1)]
+        ch = nat.Chain(layers, likelihood=nat.LIK_FIXED_GAUSSIAN, fixed_sd=0.3)
+        t_ev = np.exp(ch.forward_many(thetas[:1], X=X)[0, 0].astype(np.float64)) * rng.exponential(1.0, n)
+        t_ce = rng.exponential(np.quantile(t_ev, 0.75), n)
+        Y = np.where(t_ev <= t_ce, t_ev, -t_ce).astype(np.float32)[:, None]
+        q = lambda p: np.quantile(np.abs(Y).astype(np.float64), p)
+        for times in (np.array([q(0.9)]), np.linspace(q(0.1), q(0.9), 32)):
+            legs = {"harrell": lambda: ch.ensemble_concordance(thetas, Y=Y, X=X), "ipcw": lambda: ch.ensemble_concordance_ipcw(thetas, times, Y=Y, X=X)}
+            took = {k: [] for k in legs}
+            for rep in range(6):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    got = fn()
+                    if rep:                                # (repetition 0 is the warm-up)
+                        took[k].append(time.perf_counter() - t0)
+            ms = {k: 1e3 * statistics.median(v) for k, v in took.items()}
+            print(json.dumps({"shape": f"{name} {n}", "dims": dims, "networks": M, "rows": n, "T": int(times.size), "kernel": ch.kernel_name,
+                              "build_id": nat.build_id(), "censored_share": float(np.mean(Y < 0)), "harrell_ms": round(ms["harrell"], 3),
+                              "ipcw_ms": round(ms["ipcw"], 3), "ipcw_over_harrell": round(ms["ipcw"] / ms["harrell"], 3),
+                              "spread_ms": {k: [round(1e3 * min(v), 3), round(1e3 * max(v), 3)] for k, v in took.items()},
+                              "c_index_last": float(got["c_index"][0, -1])}), flush=True)
+        ch.close()
+
+
 def main():
     if nat.device_count() < 1:
         sys.exit("time_concordance: no gfx950 device")
+    if "--ipcw" in sys.argv[1:]:
+        return ipcw_leg()
     for name, dims, n in SHAPES:
         rng = np.random.default_rng(0)
         X = (rng.standard_normal((n, dims[0])) / np.sqrt(max(dims[0] / 16.0, 1.0))).astype(np.float32)
