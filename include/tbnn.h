@@ -315,6 +315,27 @@ enum { TBNN_XFORM_NONE = 0, TBNN_XFORM_EXP = 1, TBNN_XFORM_SIGMOID = 2, TBNN_XFO
  * summed in fp64 in network order.  mean_out, var_out: host [d_out][n] doubles; var_out may be NULL. */
 int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
                           float scale, float shift, int which, const float* X, int64_t n, double* mean_out, double* var_out);
+/* Input sensitivities: which inputs drive the prediction, and how sure is the posterior of that?  Arguments up to `scale` as
+ * tbnn_ensemble_moments' (there is no shift: it does not enter a derivative), `which`, X and n likewise.  For network i, row r, output o and
+ * input k
+ *   J_i[o][k][r] = scale * g'(f_i,o(x_r)) * d f_i,o / d x_k (x_r)
+ * f the network's output after its last layer's own activation, g the element-wise transform: g' = 1 (TBNN_XFORM_NONE), g (EXP),
+ * g (1 - g) (SIGMOID).  The derivative is the exact reverse pass of the network in fp32; the activations' derivatives are taken from the
+ * fp32 activation OUTPUTS as the training kernels take them (relu: 1 where a > 0, else 0 -- 0 at the kink; tanh 1 - a^2; sigmoid a (1 - a);
+ * exp a; elu 1 where a > 0, else a + 1).  Values are in the networks' own (normalised) units.  With W = sum_i w_i, summed in fp64 in network
+ * order:
+ *   mean_out = sum_i w_i J_i / W,  var_out = sum_i w_i (J_i - mean)^2 / W (population form),  abs_out = sum_i w_i |J_i| / W
+ * each host [d_out][d_in][n] doubles, each may be NULL; abs_out does not cancel where the networks disagree in sign: its mean over the rows
+ * is a feature importance.  jac_out: host [m][d_out][d_in][n] floats, every network's own Jacobian, or NULL.  A J_i that is not finite makes
+ * that element NaN in all three planes, whatever the network's weight.  The same bits from run to run and whatever the chunks.
+ * One kernel on the FP32 matrix pipe, no forward pass of the handle's kernel family and no weight image: it runs on a handle of any family.
+ * Refused, with nothing written: every output NULL; TBNN_XFORM_SOFTMAX (it couples a row's outputs: not built); weights breaking the rules
+ * above; what tbnn_ensemble_moments refuses of m, theta_stride, which and n; 64 rows of the four fp64 planes of d_out d_in elements above the
+ * block budget of 2^28 floats; and a shape whose 16-row tile does not fit the LDS:
+ *   (d_in + sum of the layers' outputs) * 17 + 2 * (widest layer output) * 17 + 2176 floats > 40944. */
+int tbnn_ensemble_input_grad(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
+                             float scale, int which, const float* X, int64_t n, double* mean_out, double* var_out, double* abs_out,
+                             float* jac_out);
 /* Data log-likelihood of the rows under each of the m networks, reduced both ways.  likelihood: the TBNN_LIK_* to judge under,
  * independent of the handle's own; sd: m per-network standard deviations for the Gaussian kinds, or NULL = the descriptor's fixed_sd
  * (clipped to [1e-8, 1e8], layer.py:60-64).  Y: host targets [n, d_out] of the rows; NULL with X NULL = the staged targets of `which`

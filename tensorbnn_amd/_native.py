@@ -117,6 +117,7 @@ SYMBOLS = [
     ("tbnn_predict", C.c_int, [_H, C.c_int, _fp, _fp]),
     ("tbnn_forward_many", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int64, _fp]),
     ("tbnn_ensemble_moments", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
+    ("tbnn_ensemble_input_grad", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp, _dp, _fp]),
     ("tbnn_ensemble_quantiles", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp,
                                           C.c_int32, _dp]),
     ("tbnn_ensemble_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
@@ -580,6 +581,22 @@ class Chain:
         _check(lib.tbnn_ensemble_moments(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), float(shift), int(which),
                                          _p(xp), n, _pd(mean), _pd(vr)))
         return mean, vr
+
+    def ensemble_input_grad(self, thetas, X=None, which: int = 0, weights=None, xform: int = XFORM_NONE, scale: float = 1.0,
+                            per_network: bool = False):
+        """input sensitivities of an ensemble, formed and reduced on the device (tbnn_ensemble_input_grad; the definition is in
+        include/tbnn.h): thetas [m, P] -> a dict of float64 arrays [d_out, d_in, rows] -- mean, var (population form) and abs_mean of
+        J = scale * g'(f) * df/dx over the networks -- and, per_network=True, per_network: float32 [m, d_out, d_in, rows], every network's
+        own Jacobian.  weights: one per network or None (equal).  X None: the staged rows (0 train, 1 validation)"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        shape = (self.d_out, self.d_in, n)
+        out = {k: np.empty(shape, dtype=np.float64) for k in ("mean", "var", "abs_mean")}
+        jac = np.empty((th.shape[0],) + shape, dtype=np.float32) if per_network else None
+        _check(lib.tbnn_ensemble_input_grad(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), int(which), _p(xp), n,
+                                            _pd(out["mean"]), _pd(out["var"]), _pd(out["abs_mean"]), _p(jac)))
+        if per_network:
+            out["per_network"] = jac
+        return out
 
     def ensemble_uncertainty(self, thetas, X=None, which: int = 1, weights=None, likelihood=None):
         """classification uncertainty over an ensemble, reduced on the device (tbnn_ensemble_uncertainty; the definition is in

@@ -1764,3 +1764,100 @@ extern "C" int tbnn_ensemble_loo(tbnn_handle h, const float* thetas, int32_t m, 
             return 0;
         }, extra);
 }
+
+// ---- input sensitivities: the Jacobian of every network and its moments (kernels_input_grad.hpp; definition: include/tbnn.h) ----
+// the tile of k_ens_input_grad for this network: 64 rows where the LDS map fits with at least one output per group, else 16; og = the most
+// outputs per group that fit.  Refused: a shape whose 16-row tile does not fit
+struct IgPlan { int rt = 0, og = 0, maxOut = 0; long floats = 0; };
+static int ig_plan(const std::string& who, const NetDev& nd, IgPlan* p) {
+    int mo = 0;
+    for (int l = 0; l < nd.nl; ++l) mo = std::max(mo, nd.out[l]);
+    p->maxOut = mo;
+    for (int rt : {64, 16})
+        for (int og = std::min(nd.d_out, IG_OG); og >= 1; --og) {
+            const long f = ig_lds_floats(nd.d_in, nd.sumOut, mo, rt, og);
+            if (f <= IG_LDS_MAX) { p->rt = rt; p->og = og; p->floats = f; return 0; }
+        }
+    return fail(-1, who + ": the 16-row tile needs " + std::to_string(ig_lds_floats(nd.d_in, nd.sumOut, mo, 16, 1)) +
+                        " floats of LDS, (d_in + sumOut) 17 + 2 maxOut 17 + " + std::to_string(2 * IG_PANEL) + ", above the limit of " +
+                        std::to_string(IG_LDS_MAX));
+}
+#define IG_LAUNCH(RT, F)                                                                                                                   \
+    hipLaunchKernelGGL((k_ens_input_grad<RT, F>), dim3((unsigned)((r + RT - 1) / RT)), dim3(RT * 4), 0, h->stream, h->nd, (const float*)dTh, c, x, \
+                       r, pl.og, pl.maxOut, xform, scale, w, (int)(i0 == 0), (double*)acc, (float*)dJ)
+
+extern "C" int tbnn_ensemble_input_grad(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
+                                        float scale, int which, const float* X, int64_t n, double* mean_out, double* var_out, double* abs_out,
+                                        float* jac_out) {
+    NEED(h);
+    const std::string who = "ensemble_input_grad";
+    const NetDev& nd = h->nd;
+    if (!mean_out && !var_out && !abs_out && !jac_out) return fail(-1, who + ": every output is null");
+    if (xform == TBNN_XFORM_SOFTMAX)
+        return fail(-1, who + ": TBNN_XFORM_SOFTMAX couples the outputs of a row: its sensitivities are not built (NONE, EXP and SIGMOID are)");
+    ENS_TRY(ens_check_xform(who, xform, nd.d_out));
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    IgPlan pl;
+    ENS_TRY(ig_plan(who, nd, &pl));
+    // per row: four fp64 planes of d_out d_in elements, counted in floats
+    const size_t E = (size_t)nd.d_out * nd.d_in, per_row = 8 * E;
+    ENS_TRY(ens_block_rows(who, 0, per_row, nullptr, "rows of the sensitivity planes"));
+    EnsStage st{h};
+    ENS_TRY(st.stage_rows(who, thetas, m, theta_stride, which, X, n));
+    long rb = 0;
+    ENS_TRY(ens_block_rows(who, st.rows, per_row, &rb, "rows of the sensitivity planes"));
+    // networks per chunk: the staged thetas, and every network's Jacobian of a block where it is wanted, within the budget
+    size_t chunk = std::min<size_t>((size_t)m, ens_chunk_floats() / (size_t)nd.P);
+    if (jac_out) chunk = std::min(chunk, ens_chunk_floats() / (E * (size_t)rb));
+    chunk = std::max<size_t>(chunk, 1);
+    Buf<float> dTh, dW, dJ;
+    Buf<double> acc;
+    HIPCHK(dTh.alloc(chunk * nd.P));
+    HIPCHK(acc.alloc(4 * E * (size_t)rb));
+    if (jac_out) HIPCHK(dJ.alloc(chunk * E * (size_t)rb));
+    if (net_w) ENS_TRY(ens_upload(h, dW, net_w, (size_t)m));
+    const bool once = chunk >= (size_t)m;                   // one chunk: its thetas are staged for the first block alone
+    const long rows = st.rows;
+    auto run = [&]() -> int {
+        for (long r0 = 0; r0 < rows; r0 += rb) {
+            const long r = std::min(rb, rows - r0);
+            const size_t tot = E * (size_t)r;
+            const float* x = st.dX + (size_t)r0 * nd.d_in;
+            for (int i0 = 0; i0 < m; i0 += (int)chunk) {
+                const int c = std::min((int)chunk, m - i0);
+                if (!once || r0 == 0)
+                    HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
+                                            (size_t)nd.P * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
+                const float* w = net_w ? dW + i0 : nullptr;
+                if (pl.rt == 64) {
+                    if (pl.floats <= IG_LDS_MIN) IG_LAUNCH(64, IG_LDS_MIN);
+                    else if (pl.floats <= IG_LDS_MID) IG_LAUNCH(64, IG_LDS_MID);
+                    else IG_LAUNCH(64, IG_LDS_MAX);
+                } else {
+                    if (pl.floats <= IG_LDS_MIN) IG_LAUNCH(16, IG_LDS_MIN);
+                    else if (pl.floats <= IG_LDS_MID) IG_LAUNCH(16, IG_LDS_MID);
+                    else IG_LAUNCH(16, IG_LDS_MAX);
+                }
+                HIPCHK(hipGetLastError());
+                // the chunk's Jacobians [c d_out d_in][r] -> jac_out[m d_out d_in][rows] at network i0, column r0
+                if (jac_out)
+                    HIPCHK(hipMemcpy2DAsync(jac_out + (size_t)i0 * E * rows + r0, (size_t)rows * sizeof(float), dJ, (size_t)r * sizeof(float),
+                                            (size_t)r * sizeof(float), (size_t)c * E, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+            }
+            hipLaunchKernelGGL(k_ens_input_grad_finish, dim3(ens_grid((long)tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, (long)tot, W);
+            HIPCHK(hipGetLastError());
+            if (mean_out) ENS_TRY(ens_copy_planes(h, mean_out, r0, rows, acc, r, E));
+            if (var_out) ENS_TRY(ens_copy_planes(h, var_out, r0, rows, acc + tot, r, E));
+            if (abs_out) ENS_TRY(ens_copy_planes(h, abs_out, r0, rows, acc + 3 * tot, r, E));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+        return 0;
+    };
+    const int rc = run();
+    hipStreamSynchronize(h->stream);
+    return rc;
+}
+#undef IG_LAUNCH

@@ -254,6 +254,26 @@ class predictor(object):
             return m, m + v + (v + m * m) / self.likelihood.dispersion
         return (m, m + v) if countVariance else (m, v)
 
+    def inputGradient(self, inputMatrix, weights=None, perNetwork=False, n=1):
+        """Which inputs drive the prediction, and how sure is the posterior of that?  The Jacobian d t_o / d x_k of every n-th network at
+        every row, t = transform(f) with the transform predictMoments picks for the predictor's likelihood, formed and reduced on the
+        device (tbnn_ensemble_input_grad; the definition is in include/tbnn.h).  Returns a dict of float64 arrays: mean, sd and abs_mean
+        [d_out, d_in, rows] -- the posterior mean, the posterior sd and the posterior mean of |J| per element --, importance [d_out, d_in],
+        the mean of abs_mean over the rows, and importance_sd, its sd over the rows; perNetwork=True adds per_network, float32
+        [networks, d_out, d_in, rows].  In the networks' own (normalised) units, as crps.  A CategoricalLikelihood is refused: the softmax
+        couples a row's outputs, and its sensitivities are not built."""
+        from .likelihood import CategoricalLikelihood
+        if isinstance(self.likelihood, CategoricalLikelihood):
+            raise ValueError("inputGradient: the softmax of a CategoricalLikelihood couples a row's outputs; its sensitivities are not built")
+        picked, w = self._picked(n, weights)
+        res = self._ensure_chain().ensemble_input_grad(picked, X=np.asarray(inputMatrix, dtype=np.float32), weights=w,
+                                                       xform=self._TRANSFORMS[self._transform(None)], per_network=perNetwork)
+        out = {"mean": res["mean"], "sd": np.sqrt(res["var"]), "abs_mean": res["abs_mean"],
+               "importance": res["abs_mean"].mean(axis=2), "importance_sd": res["abs_mean"].std(axis=2)}
+        if perNetwork:
+            out["per_network"] = res["per_network"]
+        return out
+
     def predictQuantiles(self, inputMatrix, probs, n=1, weights=None, transform=None, sd=1.0, mean=0.0, method=None):
         """Posterior quantiles of every n-th network's predictions at the probabilities `probs`, float64 [n_probs, d_out, rows] (a scalar
         `probs`: [d_out, rows]), selected on the device: only the result crosses to the host.  Per value t = transform(f) * sd + mean,
