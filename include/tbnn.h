@@ -336,6 +336,26 @@ int tbnn_ensemble_moments(tbnn_handle h, const float* thetas, int32_t m, int64_t
 int tbnn_ensemble_input_grad(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
                              float scale, int which, const float* X, int64_t n, double* mean_out, double* var_out, double* abs_out,
                              float* jac_out);
+/* Integrated-gradients attributions (Sundararajan et al. 2017): what does each input contribute to the move of the prediction from a baseline
+ * x0 to the row x, and how sure is the posterior of that?  Arguments up to `n` as tbnn_ensemble_input_grad's.  baseline: host [d_in] floats,
+ * one baseline for all rows, in the networks' normalised units; NULL = zeros, the training mean.  points = P: the path points, 16, 32 or 64.
+ * In fp32, with d = x - x0 and a_s = (float)s / (float)(P - 1):
+ *   x_s = fmaf(a_s, d, x0) for s < P - 1,  x_{P-1} = x exactly;  q_0 = q_{P-1} = 1 / (2 (P - 1)), q_s = 1 / (P - 1) otherwise (trapezoid)
+ *   A_i[o][k][r] = d_k(r) * sum_s q_s J_i[o][k](x_s(r))
+ * J exactly the Jacobian tbnn_ensemble_input_grad defines (scale, g', act' from the fp32 activation outputs).  In exact arithmetic and up to
+ * the quadrature the attributions of a row sum to scale (g(f(x)) - g(f(x0))).  mean_out, var_out, abs_out: host [d_out][d_in][n] doubles,
+ * each may be NULL: the weighted moments of A_i over the networks by the definition, the NaN rule and the fp64 network-order sums of
+ * tbnn_ensemble_input_grad's planes.  attr_out: host [m][d_out][d_in][n] floats, every network's own attributions, or NULL.  diff_out: host
+ * [m][d_out][n] floats or NULL: scale * (g(f_i(x)) - g(f_i(x0))) in fp32 from the forward pass at the two end points, which the path holds;
+ * diff - sum_k A is the completeness gap of the quadrature.  The same bits from run to run and whatever the chunks.
+ * One kernel on the FP32 matrix pipe: the path points are the rows of the matrix tiles, formed on the device (nothing of size P n is
+ * stored), and the quadrature sum is taken before the product with the first layer's weights, which therefore runs once per row, not P times.
+ * Refused, with nothing written: everything tbnn_ensemble_input_grad refuses (TBNN_XFORM_SOFTMAX included; every output NULL counts
+ * diff_out too); points outside {16, 32, 64}; a baseline value that is not finite; and points > 16 on a shape that fits the 16-row tile only:
+ *   (d_in + sum of the layers' outputs) * 65 + 2 * (widest layer output) * 65 + 2176 floats > 40944. */
+int tbnn_ensemble_integrated_grad(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
+                                  float scale, int which, const float* X, const float* baseline, int64_t n, int32_t points,
+                                  double* mean_out, double* var_out, double* abs_out, float* attr_out, float* diff_out);
 /* Data log-likelihood of the rows under each of the m networks, reduced both ways.  likelihood: the TBNN_LIK_* to judge under,
  * independent of the handle's own; sd: m per-network standard deviations for the Gaussian kinds, or NULL = the descriptor's fixed_sd
  * (clipped to [1e-8, 1e8], layer.py:60-64).  Y: host targets [n, d_out] of the rows; NULL with X NULL = the staged targets of `which`

@@ -118,6 +118,8 @@ SYMBOLS = [
     ("tbnn_forward_many", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int, _fp, C.c_int64, _fp]),
     ("tbnn_ensemble_moments", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
     ("tbnn_ensemble_input_grad", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp, _dp, _fp]),
+    ("tbnn_ensemble_integrated_grad", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_float, C.c_int, _fp, _fp, C.c_int64, C.c_int32,
+                                                _dp, _dp, _dp, _fp, _fp]),
     ("tbnn_ensemble_quantiles", C.c_int, [_H, _fp, C.c_int32, C.c_int64, _fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp,
                                           C.c_int32, _dp]),
     ("tbnn_ensemble_diagnostics", C.c_int, [_H, _fp, C.c_int32, C.c_int64, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, _fp, C.c_int64, _dp, _dp]),
@@ -596,6 +598,29 @@ class Chain:
                                             _pd(out["mean"]), _pd(out["var"]), _pd(out["abs_mean"]), _p(jac)))
         if per_network:
             out["per_network"] = jac
+        return out
+
+    def ensemble_integrated_grad(self, thetas, X=None, baseline=None, points: int = 16, weights=None, xform: int = XFORM_NONE,
+                                 scale: float = 1.0, per_network: bool = False, which: int = 0):
+        """integrated-gradients attributions of an ensemble, formed and reduced on the device (tbnn_ensemble_integrated_grad; the
+        definition is in include/tbnn.h): thetas [m, P] -> a dict of mean, var (population form) and abs_mean, float64
+        [d_out, d_in, rows], of A = (x - x0) * the trapezoid sum of J over `points` (16, 32 or 64) path points from the baseline x0
+        ([d_in]; None: zeros) to x; diff: float32 [m, d_out, rows], scale * (g(f(x)) - g(f(x0))) of every network, what its attributions
+        sum to up to the quadrature; and, per_network=True, per_network: float32 [m, d_out, d_in, rows].  weights: one per network or None
+        (equal).  X None: the staged rows (0 train, 1 validation)"""
+        th, xp, n, w = self._ensemble_args(thetas, X, which, weights)
+        base = None if baseline is None else _f32(baseline).reshape(-1)
+        if base is not None and base.size != self.d_in:
+            raise ValueError(f"baseline must hold {self.d_in} values")
+        shape = (self.d_out, self.d_in, n)
+        out = {k: np.empty(shape, dtype=np.float64) for k in ("mean", "var", "abs_mean")}
+        out["diff"] = np.empty((th.shape[0], self.d_out, n), dtype=np.float32)
+        attr = np.empty((th.shape[0],) + shape, dtype=np.float32) if per_network else None
+        _check(lib.tbnn_ensemble_integrated_grad(self._h, _p(th), th.shape[0], th.shape[1], _p(w), int(xform), float(scale), int(which), _p(xp),
+                                                 _p(base), n, int(points), _pd(out["mean"]), _pd(out["var"]), _pd(out["abs_mean"]), _p(attr),
+                                                 _p(out["diff"])))
+        if per_network:
+            out["per_network"] = attr
         return out
 
     def ensemble_uncertainty(self, thetas, X=None, which: int = 1, weights=None, likelihood=None):

@@ -1861,3 +1861,101 @@ extern "C" int tbnn_ensemble_input_grad(tbnn_handle h, const float* thetas, int3
     return rc;
 }
 #undef IG_LAUNCH
+
+// ---- integrated gradients: every network's attributions along a path from a baseline, and their moments (kernels_path_grad.hpp;
+// definition: include/tbnn.h).  The tile is ig_plan's -- the kernel needs no LDS beyond the Jacobian's map --, holding rt / points rows ----
+#define PG_LAUNCH(RT, F)                                                                                                                   \
+    hipLaunchKernelGGL((k_ens_path_grad<RT, F>), dim3((unsigned)((r + dr - 1) / dr)), dim3(RT * 4), 0, h->stream, h->nd, (const float*)dTh, c, x, \
+                       (const float*)dBase, r, (int)points, pl.og, pl.maxOut, xform, scale, w, (int)(i0 == 0), (double*)acc, (float*)dA, (float*)dD)
+
+extern "C" int tbnn_ensemble_integrated_grad(tbnn_handle h, const float* thetas, int32_t m, int64_t theta_stride, const float* net_w, int xform,
+                                             float scale, int which, const float* X, const float* baseline, int64_t n, int32_t points,
+                                             double* mean_out, double* var_out, double* abs_out, float* attr_out, float* diff_out) {
+    NEED(h);
+    const std::string who = "ensemble_integrated_grad";
+    const NetDev& nd = h->nd;
+    if (!mean_out && !var_out && !abs_out && !attr_out && !diff_out) return fail(-1, who + ": every output is null");
+    if (xform == TBNN_XFORM_SOFTMAX)
+        return fail(-1, who + ": TBNN_XFORM_SOFTMAX couples the outputs of a row: its attributions are not built (NONE, EXP and SIGMOID are)");
+    ENS_TRY(ens_check_xform(who, xform, nd.d_out));
+    if (m < 1) return fail(-1, who + ": null pointer, m < 1 or theta_stride < P");
+    if (points != 16 && points != 32 && points != 64) return fail(-1, who + ": points must be 16, 32 or 64");
+    std::vector<float> base((size_t)nd.d_in, 0.f);
+    for (int k = 0; baseline && k < nd.d_in; ++k) {
+        if (!std::isfinite(baseline[k])) return fail(-1, who + ": baseline " + std::to_string(k) + " is not finite");
+        base[k] = baseline[k];
+    }
+    double W = 0.0;
+    ENS_TRY(ens_check_weights(who, net_w, m, &W));
+    IgPlan pl;
+    ENS_TRY(ig_plan(who, nd, &pl));
+    if (points > pl.rt)
+        return fail(-1, who + ": points = " + std::to_string(points) + " needs the 64-row tile, " +
+                            std::to_string(ig_lds_floats(nd.d_in, nd.sumOut, pl.maxOut, 64, 1)) +
+                            " floats of LDS, (d_in + sumOut) 65 + 2 maxOut 65 + " + std::to_string(2 * IG_PANEL) + ", above the limit of " +
+                            std::to_string(IG_LDS_MAX) + ": this shape takes points = 16 only");
+    const long dr = pl.rt / points;                        // rows of a tile: the path takes the other factor of its MFMA rows
+    const size_t E = (size_t)nd.d_out * nd.d_in, per_row = 8 * E;
+    ENS_TRY(ens_block_rows(who, 0, per_row, nullptr, "rows of the attribution planes"));
+    EnsStage st{h};
+    ENS_TRY(st.stage_rows(who, thetas, m, theta_stride, which, X, n));
+    long rb = 0;
+    ENS_TRY(ens_block_rows(who, st.rows, per_row, &rb, "rows of the attribution planes"));
+    size_t chunk = std::min<size_t>((size_t)m, ens_chunk_floats() / (size_t)nd.P);
+    if (attr_out) chunk = std::min(chunk, ens_chunk_floats() / (E * (size_t)rb));
+    else if (diff_out) chunk = std::min(chunk, ens_chunk_floats() / ((size_t)nd.d_out * (size_t)rb));
+    chunk = std::max<size_t>(chunk, 1);
+    Buf<float> dTh, dW, dA, dD, dBase;
+    Buf<double> acc;
+    HIPCHK(dTh.alloc(chunk * nd.P));
+    HIPCHK(acc.alloc(4 * E * (size_t)rb));
+    if (attr_out) HIPCHK(dA.alloc(chunk * E * (size_t)rb));
+    if (diff_out) HIPCHK(dD.alloc(chunk * nd.d_out * (size_t)rb));
+    if (net_w) ENS_TRY(ens_upload(h, dW, net_w, (size_t)m));
+    ENS_TRY(ens_upload(h, dBase, base.data(), base.size()));
+    const bool once = chunk >= (size_t)m;                   // one chunk: its thetas are staged for the first block alone
+    const long rows = st.rows;
+    auto run = [&]() -> int {
+        for (long r0 = 0; r0 < rows; r0 += rb) {
+            const long r = std::min(rb, rows - r0);
+            const size_t tot = E * (size_t)r;
+            const float* x = st.dX + (size_t)r0 * nd.d_in;
+            for (int i0 = 0; i0 < m; i0 += (int)chunk) {
+                const int c = std::min((int)chunk, m - i0);
+                if (!once || r0 == 0)
+                    HIPCHK(hipMemcpy2DAsync(dTh, (size_t)nd.P * sizeof(float), thetas + (size_t)i0 * theta_stride, (size_t)theta_stride * sizeof(float),
+                                            (size_t)nd.P * sizeof(float), (size_t)c, hipMemcpyHostToDevice, h->stream));
+                const float* w = net_w ? dW + i0 : nullptr;
+                if (pl.rt == 64) {
+                    if (pl.floats <= IG_LDS_MIN) PG_LAUNCH(64, IG_LDS_MIN);
+                    else if (pl.floats <= IG_LDS_MID) PG_LAUNCH(64, IG_LDS_MID);
+                    else PG_LAUNCH(64, IG_LDS_MAX);
+                } else {
+                    if (pl.floats <= IG_LDS_MIN) PG_LAUNCH(16, IG_LDS_MIN);
+                    else if (pl.floats <= IG_LDS_MID) PG_LAUNCH(16, IG_LDS_MID);
+                    else PG_LAUNCH(16, IG_LDS_MAX);
+                }
+                HIPCHK(hipGetLastError());
+                // the chunk's attributions [c d_out d_in][r] -> attr_out[m d_out d_in][rows] at network i0, column r0; diff likewise
+                if (attr_out)
+                    HIPCHK(hipMemcpy2DAsync(attr_out + (size_t)i0 * E * rows + r0, (size_t)rows * sizeof(float), dA, (size_t)r * sizeof(float),
+                                            (size_t)r * sizeof(float), (size_t)c * E, hipMemcpyDeviceToHost, h->stream));
+                if (diff_out)
+                    HIPCHK(hipMemcpy2DAsync(diff_out + (size_t)i0 * nd.d_out * rows + r0, (size_t)rows * sizeof(float), dD, (size_t)r * sizeof(float),
+                                            (size_t)r * sizeof(float), (size_t)c * nd.d_out, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+            }
+            hipLaunchKernelGGL(k_ens_input_grad_finish, dim3(ens_grid((long)tot)), dim3(ENS_TB), 0, h->stream, (double*)acc, (long)tot, W);
+            HIPCHK(hipGetLastError());
+            if (mean_out) ENS_TRY(ens_copy_planes(h, mean_out, r0, rows, acc, r, E));
+            if (var_out) ENS_TRY(ens_copy_planes(h, var_out, r0, rows, acc + tot, r, E));
+            if (abs_out) ENS_TRY(ens_copy_planes(h, abs_out, r0, rows, acc + 3 * tot, r, E));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+        return 0;
+    };
+    const int rc = run();
+    hipStreamSynchronize(h->stream);
+    return rc;
+}
+#undef PG_LAUNCH

@@ -21,6 +21,7 @@
 #include "kernels_layered.hpp"
 #include "kernels_ensemble.hpp"
 #include "kernels_input_grad.hpp"
+#include "kernels_path_grad.hpp"
 #include "kernels_optim.hpp"
 #include "aot_ops.hpp"
 #include <mutex>

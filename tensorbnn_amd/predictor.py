@@ -274,6 +274,32 @@ class predictor(object):
             out["per_network"] = res["per_network"]
         return out
 
+    def integratedGradients(self, inputMatrix, baseline=None, points=16, perNetwork=False, weights=None, n=1):
+        """What does each input contribute to the move of the prediction from a baseline to the row, and how sure is the posterior of
+        that?  Integrated gradients (Sundararajan et al. 2017) of every n-th network: A = (x - x0) times the trapezoid sum of the Jacobian
+        inputGradient defines over `points` (16, 32 or 64) points of the straight path from the baseline x0 ([d_in]; None: zeros, the
+        training mean of normalised inputs) to x, formed and reduced on the device (tbnn_ensemble_integrated_grad; the definition is in
+        include/tbnn.h).  Returns a dict of float64 arrays: mean, sd and abs_mean [d_out, d_in, rows]; importance and importance_sd
+        [d_out, d_in], the mean and the sd of abs_mean over the rows; diff_mean [d_out, rows], the posterior mean of t(x) - t(x0), what a
+        row's attributions sum to up to the quadrature; completeness_gap [d_out, rows], the posterior mean of diff_i - sum_k A_i, which
+        more points shrink; perNetwork=True adds per_network, float32 [networks, d_out, d_in, rows].  In the networks' own (normalised)
+        units.  A CategoricalLikelihood is refused as inputGradient refuses it."""
+        from .likelihood import CategoricalLikelihood
+        if isinstance(self.likelihood, CategoricalLikelihood):
+            raise ValueError("integratedGradients: the softmax of a CategoricalLikelihood couples a row's outputs; its attributions are not built")
+        picked, w = self._picked(n, weights)
+        res = self._ensure_chain().ensemble_integrated_grad(picked, X=np.asarray(inputMatrix, dtype=np.float32), baseline=baseline,
+                                                            points=points, weights=w, xform=self._TRANSFORMS[self._transform(None)],
+                                                            per_network=perNetwork)
+        ws = np.ones(len(picked)) if w is None else np.asarray(w, dtype=np.float64)
+        diff_mean = np.tensordot(ws / ws.sum(), res["diff"].astype(np.float64), axes=1)
+        out = {"mean": res["mean"], "sd": np.sqrt(res["var"]), "abs_mean": res["abs_mean"],
+               "importance": res["abs_mean"].mean(axis=2), "importance_sd": res["abs_mean"].std(axis=2),
+               "diff_mean": diff_mean, "completeness_gap": diff_mean - res["mean"].sum(axis=1)}
+        if perNetwork:
+            out["per_network"] = res["per_network"]
+        return out
+
     def predictQuantiles(self, inputMatrix, probs, n=1, weights=None, transform=None, sd=1.0, mean=0.0, method=None):
         """Posterior quantiles of every n-th network's predictions at the probabilities `probs`, float64 [n_probs, d_out, rows] (a scalar
         `probs`: [d_out, rows]), selected on the device: only the result crosses to the host.  Per value t = transform(f) * sd + mean,
